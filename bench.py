@@ -249,6 +249,52 @@ def verify_last_step(A, torch, dev, images, last, halo_img, B, W, H, NF, cap, ra
     return res
 
 
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: all files together stay below this
+DUMP_MAX_FRAMES = 128              # frames whose keypoints / descriptors / matches are written in full
+DUMP_SEED = 20240                  # the sample of frames is fixed: same arguments, same frames
+
+
+def dump_outputs(out_dir, torch, dev, last, B, cap, KP_DTYPE, MATCH_DTYPE):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, as DIR/<name>.npy:
+    counts.npy / nmatches.npy (B,) float64, every frame; frames.npy (S,) float64, the sampled frame indices (first, last and
+    a seeded random set); keypoints.npy (S, K, 6) float32 = x, y, size, angle, response, octave; descriptors.npy (S, K, 32)
+    float32, one byte per value; matches.npy (S, M, 3) float32 = query_idx, train_idx, distance. K and M are the largest
+    counts in the sample; rows past a frame's own count are 0. Returns {name: bytes}."""
+    cnt = last["counts"].cpu().numpy().astype(np.int64)
+    nms = last["nmatches"].cpu().numpy().astype(np.int64)
+    per_frame = cap * (6 + 32 + 3) * 4 + 8
+    S = int(max(min(B, 2), min(B, DUMP_MAX_FRAMES, (DUMP_BUDGET_BYTES - 2 * 8 * B - 4096) // per_frame)))
+    if S >= B:
+        frames = np.arange(B)
+    else:
+        inner = np.random.default_rng(DUMP_SEED).choice(np.arange(1, B - 1), size=S - 2, replace=False)
+        frames = np.sort(np.concatenate([[0, B - 1], inner]))
+    idx = torch.as_tensor(frames, dtype=torch.int64, device=dev)
+    kp = np.ascontiguousarray(last["kps"].index_select(0, idx).cpu().numpy()).view(KP_DTYPE).reshape(S, cap)
+    ds = last["desc"].index_select(0, idx).cpu().numpy()
+    mt = np.ascontiguousarray(last["matches"].index_select(0, idx).cpu().numpy()).view(MATCH_DTYPE).reshape(S, cap)
+    K = int(cnt[frames].max())
+    M = int(nms[frames].max())
+    keypoints = np.zeros((S, K, 6), np.float32)
+    descriptors = np.zeros((S, K, 32), np.float32)
+    matches = np.zeros((S, M, 3), np.float32)
+    for i, f in enumerate(frames):
+        n, m = int(cnt[f]), int(nms[f])
+        for j, name in enumerate(("x", "y", "size", "angle", "response", "octave")):
+            keypoints[i, :n, j] = kp[name][i, :n]
+        descriptors[i, :n] = ds[i, :n]
+        for j, name in enumerate(("query_idx", "train_idx", "distance")):
+            matches[i, :m, j] = mt[name][i, :m]
+    arrays = {"counts": cnt.astype(np.float64), "nmatches": nms.astype(np.float64), "frames": frames.astype(np.float64),
+              "keypoints": keypoints, "descriptors": descriptors, "matches": matches}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, "--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: int(a.nbytes) for name, a in arrays.items()}
+
+
 def single_frame_latency(A, dev, images, W, H, NF, n=48):
     """What a frame-at-a-time caller of IFeatureExtractor::extract / IMatcher::match sees (one frame in flight, pageable host
     buffers in and out, PCIe both ways, sync per call): the host entry points replay a hipGraph of a latency schedule.
@@ -476,10 +522,16 @@ def main():
                          "extractor handle and stream, so that the VALU-bound FAST/blur launches of one part run beside the "
                          "memory-bound select/describe launches of another (chunk-level pipelining; results unchanged)")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's shard: counts and match "
+                         "counts of every frame, keypoints / descriptors / matches of a fixed sample of frames) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # we are the parent: start the ranks, relay rank 0's line. Nothing below runs in this process.
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -733,6 +785,10 @@ def main():
     mat.set_profiling(False)
     cnt_host = last["counts"].cpu().numpy()
     nm_host = last["nmatches"].cpu().numpy()
+    # before anything else writes into the output sets (the streamed leg and the extra step below reuse them)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, torch, dev, last, B, cap, A.KP_DTYPE, A.MATCH_DTYPE)
 
     # ---- untimed: verify what the timed region produced (every rank verifies its own shard) ----
     verification = None
@@ -938,6 +994,8 @@ def main():
         staging["note"] = ("upload of this rank's %d frames before the timed region; not part of `value`. The extractor "
                            "consumes %.1f GB/s of frames at the measured rate" % (B, out["value"] / max(n_gpus, 1) * W * H / 1e9))
         out["h2d_staging"] = staging
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         if n_gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(W, H, NF, args.cpu_budget)
         print(json.dumps(out), flush=True)

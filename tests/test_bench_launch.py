@@ -59,6 +59,48 @@ def test_bench_prefix_golden_matches_the_oracle(aria, oracle):
     assert B.match_digest(len(m), m)[:16] == g["match"][3]
 
 
+def test_dump_outputs_writes_the_last_step_as_float_arrays(aria, tmp_path):
+    """--dump-outputs: the output set of a step (the byte layouts bench.py's device buffers hold) comes back field by field
+    as float arrays, rows past each frame's count zeroed, on a fixed sample of frames that includes the first and the last."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench as B
+    nf, cap = 300, 64
+    rng = np.random.default_rng(5)
+    cnt = rng.integers(0, cap + 1, nf).astype(np.int32)
+    nms = rng.integers(0, cap + 1, nf).astype(np.int32)
+    kp = np.zeros((nf, cap), aria.KP_DTYPE)
+    for name in ("x", "y", "size", "angle", "response"):
+        kp[name] = rng.random((nf, cap), dtype=np.float32) * 640
+    kp["octave"] = rng.integers(0, 8, (nf, cap))
+    mt = np.zeros((nf, cap), aria.MATCH_DTYPE)
+    mt["query_idx"], mt["train_idx"] = rng.integers(0, cap, (nf, cap)), rng.integers(0, cap, (nf, cap))
+    mt["distance"] = rng.integers(0, 257, (nf, cap))
+    desc = rng.integers(0, 256, (nf, cap, 32), dtype=np.uint8)
+    last = dict(kps=torch.from_numpy(kp.view(np.uint8).reshape(nf, cap, 24)), desc=torch.from_numpy(desc),
+                counts=torch.from_numpy(cnt), matches=torch.from_numpy(mt.view(np.uint8).reshape(nf, cap, 12)),
+                nmatches=torch.from_numpy(nms))
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    sizes = [B.dump_outputs(d, torch, torch.device("cpu"), last, nf, cap, aria.KP_DTYPE, aria.MATCH_DTYPE) for d in dirs]
+    assert sizes[0] == sizes[1] and sum(sizes[0].values()) <= 64 << 20
+    got = [{n: np.load(os.path.join(d, n + ".npy")) for n in sizes[0]} for d in dirs]
+    for n, a in got[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, got[1][n]), n
+    g = got[0]
+    assert np.array_equal(g["counts"], cnt) and np.array_equal(g["nmatches"], nms)
+    frames = g["frames"].astype(int)
+    assert len(frames) == B.DUMP_MAX_FRAMES and frames[0] == 0 and frames[-1] == nf - 1 and len(set(frames)) == len(frames)
+    assert g["keypoints"].shape[1] == cnt[frames].max() and g["matches"].shape[1] == nms[frames].max()
+    for i, f in enumerate(frames):
+        n, m = cnt[f], nms[f]
+        for j, name in enumerate(("x", "y", "size", "angle", "response", "octave")):
+            assert np.array_equal(g["keypoints"][i, :n, j], kp[name][f, :n].astype(np.float32)), (f, name)
+        for j, name in enumerate(("query_idx", "train_idx", "distance")):
+            assert np.array_equal(g["matches"][i, :m, j], mt[name][f, :m].astype(np.float32)), (f, name)
+        assert np.array_equal(g["descriptors"][i, :n], desc[f, :n])
+        assert not g["keypoints"][i, n:].any() and not g["descriptors"][i, n:].any() and not g["matches"][i, m:].any()
+
+
 @pytest.mark.gpu
 def test_default_bench_chunk8192_two_streams_is_verified():
     """The path the headline number uses (one 8192-frame chunk, extractor and matcher on two streams, double-buffered
