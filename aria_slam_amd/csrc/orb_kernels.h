@@ -80,6 +80,7 @@ struct EnvConfig {
     int band_xcd_map;      // ARIA_BAND_XCD_MAP=0: plain (strip, frame) grid order in the batch FAST/blur launches
     int select_bitonic;    // ARIA_SELECT_SORT=bitonic: k_select always takes its LDS bitonic sort (default: histogram bins + in-bin ranks)
     int desc_stamps;       // ARIA_DESC_STAMPS=1
+    int desc_quad;         // ARIA_DESC_IMPL=quad: the batch Q4 describe launches take the 4-keypoints-per-wave body
     int fast_blur_impl;    // 2 = band kernel, all VALU (fast_blur_band.hip, default), 1 = band kernel with the blur on the
                            // matrix cores (band_mfma.hip, ARIA_FAST_BLUR_IMPL=mfma: same bits, 23 % fewer VALU instructions,
                            // same time -- DESIGN.md section 4), 0 = 64x32 LDS tiles (ARIA_FAST_BLUR_IMPL=tile)

@@ -10,6 +10,7 @@
 //   k_describe    a6.6  intensity-centroid angle (one keypoint per 16-lane DPP row, integer moments, fastAtan2)
 //                 a6.8  256-bit rBRIEF: lane l16 of a row evaluates tests 16*it + l16; one 64-bit ballot per iteration
 //                       carries 16 descriptor bits for each of the wave's four keypoints (LSB-first bytes)
+//                 batch path (Q4 levels): 16 keypoints per wave in four such rounds, the angle and sincos once (describe16)
 // All of it is HBM/LDS/VALU-integer work; nothing here is a dense contraction, so no MFMA.
 // Float stages are compiled with -ffp-contract=off so that they round exactly like the SSE3-baseline
 // OpenCV build the CPU reference path uses (no FMA).
@@ -767,14 +768,362 @@ constexpr int kDescArenaBlocks = 32;
 // 40 x 40 row-major LDS window. Row-major levels (band kernel: single-frame schedule, tiny images): 37 rows x 64 bytes.
 constexpr int kDescQ = 10;                   // row quads and dword columns of the Q4 window
 constexpr int kDescPitchQ = 4 * kDescQ;      // 40
-template <int MODE, bool Q4>
-__global__ __launch_bounds__(64 * kDescWaves) void k_describe(Plan P, FrameSrc S, const uint8_t* __restrict__ raw,
+
+// ---- the batch Q4 form: 16 keypoints per wave (k_describe<0, true, true> / <1, true, true>) ----
+// The 4-keypoint form pays the per-keypoint chain that does not need a whole DPP row -- slot bookkeeping, fastAtan2, the
+// double-precision sincos, the record store -- once per instruction stream of 4 keypoints. Here a wave owns 16 slots
+// of one level and runs four rounds of the DPP-row form; that chain runs once for the 16, on the lanes
+// (row g, l16 = r) = keypoint 4r + g ("its lane"):
+//   records  : lane (g, l16 < 4) loads the sel record of keypoint 4 * l16 + g (lanes l16 >= 4 repeat l16 & 3)
+//   round r  : row g takes its keypoint's values from lane (g, r) with one ds_swizzle per value (and_mask 0x10, or_mask r)
+//   moments  : 4 rounds (raw window -> LDS, moments, parked into lane (g, r) by a constant-mask v_cndmask); the next
+//              round's raw window is requested before the current one is reduced
+//   angle    : fastAtan2, degree -> radian, det_sincos once -- the same code on other lanes, so the same bits
+//   pattern  : 4 rounds (Q4 blurred window -> LDS, the pattern loop unchanged); the next round's window is in flight
+//              during the current one, the first during the angle phase
+//   output   : the descriptor words per round as before, the 16 keypoint records at the end from their lanes
+// MODE 0: the frames' regular slots. A wave = 16 consecutive slots of one level: (sel_cap + 15) / 16 waves per level, the
+// slots inside a level in their tile order. MODE 1: the tie-storm arena in its layout (blocks of four entries of one
+// (frame, level)): a wave takes four blocks, one per round, with the round's frame and level.
+constexpr int kDesc16Kp = 16;
+// lane (g, l16) <- lane (g, r): `src` = the byte address of lane (g, r), from row_src(r)
+__device__ __forceinline__ int row_src(int r) { return (((int)(threadIdx.x & 0x30)) | r) << 2; }
+__device__ __forceinline__ int row_pick(int v, int src) { return __builtin_amdgcn_ds_bpermute(src, v); }
+
+// waves of 16 slots per frame (MODE 0 grid: ceil(this / kDescWaves) blocks per frame)
+__host__ __device__ __forceinline__ int desc16_waves_per_frame(const Plan& P) {
+    int w = 0;
+    for (int i = 0; i < kLevels; i++) w += (P.lv[i].sel_cap + kDesc16Kp - 1) / kDesc16Kp;
+    return w;
+}
+
+template <int MODE>
+__device__ __forceinline__ void describe16(const Plan& P, const FrameSrc& S, const uint8_t* __restrict__ raw,
+                                           const uint8_t* __restrict__ blur, const uint4* __restrict__ sel,
+                                           const int* __restrict__ sel_cnt, aria_keypoint* __restrict__ kps,
+                                           uint8_t* __restrict__ desc, int* __restrict__ counts, int kp_cap,
+                                           int* __restrict__ err, int n_frames, int blocks_per_frame,
+                                           unsigned long long* __restrict__ stamps,
+                                           const uint4* __restrict__ osel, const int* __restrict__ ovf, int osel_cap,
+                                           const int blk_in) {
+    constexpr bool ARENA = MODE == 1;
+#define DSTAMP16(k) do { if (stamps && (threadIdx.x & 63) == 0) stamps[((size_t)blockIdx.x * kDescWaves + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+    DSTAMP16(0);
+    constexpr int kPatchBytes = kDescPitchQ * kDescPitchQ;
+    static_assert(kPatchBytes >= 31 * kIcPitch && kPatchBytes % 16 == 0, "the raw window shares the allocation");
+    __shared__ __attribute__((aligned(16))) uint8_t s_patch[kDescKp][kPatchBytes];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int grp = lane >> 4, l16 = lane & 15;
+    const int rs = l16 & 3;                                   // the round whose keypoint (4 rs + grp) this lane's record is
+    uint8_t* const win = s_patch[wv * 4 + grp];
+
+    // ---- bookkeeping once per 16 keypoints ----
+    int frame = 0, l = 0, base = 0;                           // MODE 0: the wave's; MODE 1: per round (below)
+    uint4 sv;
+    bool valid;                                               // this lane's record is a keypoint to describe (l16 < 4)
+    uint32_t act = 0;                                         // wave-uniform: bit r = round r has work
+    if constexpr (!ARENA) {
+        const int blk = __builtin_amdgcn_readfirstlane(blk_in);
+        const int xcd = blk & 7, j = blk >> 3;                // XCD-aware block -> frame map (as in the 4-keypoint form)
+        frame = __builtin_amdgcn_readfirstlane((j / blocks_per_frame) * 8 + xcd);
+        if (frame >= n_frames) return;
+        const int w = __builtin_amdgcn_readfirstlane((j % blocks_per_frame) * kDescWaves + wv);   // wave of the frame
+        const int* cnt = sel_cnt + frame * kLevels;
+        int total = 0, wl = 0, i0 = -1;
+#pragma unroll
+        for (int i = 0; i < kLevels; i++) {
+            const int ci = cnt[i];
+            const int nw = (P.lv[i].sel_cap + kDesc16Kp - 1) / kDesc16Kp;
+            if (w >= wl && w < wl + nw) { l = i; base = total; i0 = kDesc16Kp * (w - wl); }
+            wl += nw;
+            total += ci;
+        }
+        if (w == 0 && lane == 0) {                            // counts stay within kp_cap; ERRBIT_KPCAP below, rows needed in err[2]
+            counts[frame] = min(total, kp_cap);
+            if (total > kp_cap) atomicMax(err + 2, total);
+        }
+        if (i0 < 0) return;
+        l = __builtin_amdgcn_readfirstlane(l);
+        base = __builtin_amdgcn_readfirstlane(base);
+        const int nk = min(kDesc16Kp, min(cnt[l], P.lv[l].sel_cap) - i0);
+        if (nk <= 0) return;
+        act = (1u << ((nk + 3) >> 2)) - 1u;
+        const int k = 4 * rs + grp;
+        valid = l16 < 4 && k < nk;
+        sv = sel[(int64_t)frame * P.sel_frame_entries + P.lv[l].sel_off + i0 + min(k, nk - 1)];
+    } else {
+        // arena: entries e0 .. e0 + 15 = four blocks of four; block r is round r. Padding (rank 0xFFFFFFFF) ends a block.
+        const int e0 = __builtin_amdgcn_readfirstlane((blk_in * kDescWaves + wv) * kDesc16Kp);
+        const int n_arena = min(ovf[1], osel_cap);
+        if (e0 >= n_arena) return;
+        const bool blk_ok = e0 + 4 * rs < n_arena;            // osel_cap is a multiple of 4: the whole block is in bounds
+        const int eb = e0 + 4 * rs;
+        const bool live = blk_ok && osel[eb + grp].z != 0xFFFFFFFFu;
+        const unsigned long long vm = __ballot(live && l16 < 4);
+        const int nkr = __popcll(vm & (0x0001000100010001ull << rs));    // live entries of this lane's block
+        valid = l16 < 4 && grp < nkr;
+        // rounds with work form a prefix (every block of a well-formed arena has a live first entry); a block without one
+        // ends the wave's work
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            if ((vm & (0x0001000100010001ull << r)) && act == (1u << r) - 1u) act |= 1u << r;
+        if (act == 0) return;
+        sv = blk_ok ? osel[eb + min(grp, max(nkr, 1) - 1)] : make_uint4(0u, 0u, 0u, 0u);
+    }
+    auto round_fl = [&](int r, int& fr, int& lr) {           // the round's frame and level (uniform)
+        if constexpr (ARENA) {
+            const uint32_t tag = (uint32_t)__builtin_amdgcn_readlane((int)sv.w, r);    // lane (0, r): the block's first entry
+            fr = (int)(tag & 0xFFFFFFu);
+            lr = (int)(tag >> 24);
+        } else {
+            fr = frame; lr = l;
+        }
+    };
+    const int x_s = sv.x & 0xFFFF, y_s = sv.x >> 16;
+    if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+    DSTAMP16(1);
+
+    // ---- moment rounds ----
+    uint32_t icm[16];
+#pragma unroll
+    for (int k = 0; k < 16; k += 4) {
+        const uint4 m4 = *reinterpret_cast<const uint4*>(&kIcMask.m[l16][k]);
+        icm[k] = m4.x; icm[k + 1] = m4.y; icm[k + 2] = m4.z; icm[k + 3] = m4.w;
+    }
+    const int rr = l16 / 3, cc = l16 - 3 * rr;             // raw window: lane -> (row mod 5, piece), five rows per instruction
+    const int hp = l16 >> 3, jj = l16 & 7;
+    const uint32_t wu = 0x04030201u + 0x04040404u * (uint32_t)jj;
+    DwordQuad rv[7];
+    int sh_n = 0;                                           // the requested round's sub-dword shift
+    // request round r's raw 31 x 48 windows (as in the 4-keypoint form: 16-byte pieces, lanes cover whole rows); the level
+    // base is uniform, the lane's offset inside the level a 32-bit value
+    auto raw_issue = [&](int r) {
+        int fr, lr;
+        round_fl(r, fr, lr);
+        int pitch;
+        const uint8_t* img = raw_level_ptr(P, S, raw, fr, lr, pitch);
+        const bool raw_dword = __builtin_amdgcn_readfirstlane((lr > 0) || S.aligned4) != 0;
+        const bool raw_a16 = __builtin_amdgcn_readfirstlane((lr > 0) || S.aligned16) != 0;
+        const int xy = row_pick((int)sv.x, row_src(r));
+        const int x = xy & 0xFFFF, y = (int)((uint32_t)xy >> 16);
+        const int xr = raw_a16 ? ((x - kHalfPatch) & ~15) : ((x - kHalfPatch) & ~3);
+        sh_n = (x - xr) - kHalfPatch;
+        const uint32_t o = (uint32_t)((y - kHalfPatch) * pitch + xr + 16 * cc);
+        if (raw_dword) {
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                const int row = (5 * k + 5 < 31) ? 5 * k + rr : min(5 * k + rr, 30);
+                rv[k] = *reinterpret_cast<const DwordQuad*>(img + (o + (uint32_t)(row * pitch)));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                const int row = (5 * k + 5 < 31) ? 5 * k + rr : min(5 * k + rr, 30);
+                const uint8_t* q = img + (o + (uint32_t)(row * pitch));
+                rv[k].a = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+                rv[k].b = (uint32_t)q[4] | ((uint32_t)q[5] << 8) | ((uint32_t)q[6] << 16) | ((uint32_t)q[7] << 24);
+                rv[k].c = (uint32_t)q[8] | ((uint32_t)q[9] << 8) | ((uint32_t)q[10] << 16) | ((uint32_t)q[11] << 24);
+                rv[k].d = (uint32_t)q[12] | ((uint32_t)q[13] << 8) | ((uint32_t)q[14] << 16) | ((uint32_t)q[15] << 24);
+            }
+        }
+    };
+    // request round r's blurred Q4 window: 10 x 10 pieces of 16 bytes, 7 per lane (the last lanes repeat piece 99)
+    constexpr int kPv = 7;
+    DwordQuad pv[kPv];
+    int pq[kPv], pc[kPv];
+#pragma unroll
+    for (int k = 0; k < kPv; k++) {
+        const int p = min(16 * k + l16, kDescQ * kDescQ - 1);
+        pq[k] = (p * 205) >> 11;                            // p / 10 for p < 1024
+        pc[k] = p - kDescQ * pq[k];
+    }
+    auto blur_issue = [&](int r) {
+        int fr, lr;
+        round_fl(r, fr, lr);
+        const uint8_t* bl = blur + (int64_t)fr * P.blur_frame_bytes + P.lv[lr].blur_off;
+        const int qp = P.lv[lr].pitch * 4;
+        const int xy = row_pick((int)sv.x, row_src(r));
+        const int x = xy & 0xFFFF, y = (int)((uint32_t)xy >> 16);
+        const uint32_t o = (uint32_t)(((y - kDescR) >> 2) * qp + ((x - kDescR) >> 2) * 16);
+#pragma unroll
+        for (int k = 0; k < kPv; k++)
+            pv[k] = *reinterpret_cast<const DwordQuad*>(bl + (o + (uint32_t)(pq[k] * qp + pc[k] * 16)));
+    };
+
+    int m10_s = 0, m01_s = 0;                               // parked moments: lane (g, r) <- round r, row g
+    const int nr = 32 - __builtin_clz(act);                 // rounds with work (a prefix)
+    // one moment round: raw window -> LDS, then the next request (`next`) flies while this round reduces
+    auto moment_round = [&](int r, auto next) {
+        const int sh = sh_n;
+        {
+            uint8_t* sr = win + 16 * cc;
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                const int row = (5 * k + 5 < 31) ? 5 * k + rr : min(5 * k + rr, 30);
+                *reinterpret_cast<uint4*>(sr + row * kIcPitch) = make_uint4(rv[k].a, rv[k].b, rv[k].c, rv[k].d);
+            }
+        }
+        next();
+        __builtin_amdgcn_wave_barrier();
+        // orb.cpp ICAngles, dword-wise (see the 4-keypoint form)
+        const uint8_t* rbase = win + 4 * jj + (sh & ~3);
+        uint32_t acc_u = 0, acc_v = 0, acc_s = 0;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const int rw = min(2 * k + hp, 30);
+            const uint32_t lo = *reinterpret_cast<const uint32_t*>(rbase + rw * kIcPitch);
+            const uint32_t hi = *reinterpret_cast<const uint32_t*>(rbase + rw * kIcPitch + 4);
+            const uint32_t pix = __builtin_amdgcn_alignbyte(hi, lo, sh) & icm[k];
+            acc_u = __builtin_amdgcn_udot4(pix, wu, acc_u, false);
+            acc_v = __builtin_amdgcn_udot4(pix, 0x01010101u * (uint32_t)(2 * k + 1), acc_v, false);
+            acc_s = __builtin_amdgcn_sad_u8(pix, 0u, acc_s);
+        }
+        const int sum_u = row16_sum((int)acc_u), sum_v = row16_sum((int)acc_v);
+        const int s_half = row8_sum((int)acc_s);
+        const int s_othr = __builtin_amdgcn_update_dpp(0, s_half, 0x140, 0xF, 0xF, true);
+        const int s_all = s_half + s_othr;
+        const int s_hp1 = hp ? s_half : s_othr;
+        if (l16 == r) {
+            m10_s = sum_u - 16 * s_all;
+            m01_s = sum_v + s_hp1 - 16 * s_all;
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    raw_issue(0);
+#pragma unroll 1
+    for (int r = 0; r < nr - 1; r++) moment_round(r, [&] { raw_issue(r + 1); });
+    moment_round(nr - 1, [&] { blur_issue(0); });         // the last round: the first blurred windows fly instead
+    if (stamps) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
+    DSTAMP16(2);
+
+    // ---- the angle once per 16 keypoints (lane (g, r)) ----
+    const float angle_s = fast_atan2_deg((float)m01_s, (float)m10_s);
+    float ang = angle_s;
+    ang *= (float)(3.1415926535897932384626433832795 / 180.f);
+    double sd, cd;
+    det_sincos((double)ang, sd, cd);
+    const float a_s = (float)cd, b_s = (float)sd;
+    // output row of the lane's keypoint, -1 = not written
+    int base_s = base, frame_s = frame, l_s = l;
+    if constexpr (ARENA) {
+        const uint32_t tag = sv.w;
+        frame_s = (int)(tag & 0xFFFFFFu);
+        l_s = (int)(tag >> 24);
+        base_s = 0;
+        if (valid) {
+            const int* cnt = sel_cnt + frame_s * kLevels;
+            for (int i = 0; i < l_s; i++) base_s += cnt[i];
+        }
+    }
+    const int oidx_s = base_s + (int)sv.z;
+    const bool fits_s = oidx_s < kp_cap;
+    if (valid && !fits_s) atomicOr(err, ERRBIT_KPCAP);
+    const int orow_s = (valid && fits_s) ? oidx_s : -1;
+    if (stamps) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
+    DSTAMP16(3);
+
+    // ---- pattern rounds: orb.cpp computeOrbDescriptors (WTA_K 2), exactly the 4-keypoint form's loop ----
+    int pat[16];
+#pragma unroll
+    for (int it = 0; it < 16; it += 4) {
+        const uint4 p4 = *reinterpret_cast<const uint4*>(&kPattern31.w[l16][it]);
+        pat[it] = (int)p4.x; pat[it + 1] = (int)p4.y; pat[it + 2] = (int)p4.z; pat[it + 3] = (int)p4.w;
+    }
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const f2 magic = {12582912.0f, 12582912.0f};
+    constexpr uint32_t kMagicBits = 0x4B400000u;
+    constexpr int kPitchL = kDescPitchQ;
+#pragma unroll 1
+    for (int r = 0; r < nr; r++) {
+        const int src = row_src(r);
+        const int xy = row_pick((int)sv.x, src);
+        const int x = xy & 0xFFFF, y = (int)((uint32_t)xy >> 16);
+        const int xs = (x - kDescR) & ~3, ys = (y - kDescR) & ~3;
+        const float a = __int_as_float(row_pick(__float_as_int(a_s), src));
+        const float b = __int_as_float(row_pick(__float_as_int(b_s), src));
+        const int orow = row_pick(orow_s, src);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < kPv; k++) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(win + (4 * pq[k]) * kPitchL + 4 * pc[k]);
+            d[0] = pv[k].a; d[kPitchL / 4] = pv[k].b; d[2 * kPitchL / 4] = pv[k].c; d[3 * kPitchL / 4] = pv[k].d;
+        }
+        if (r + 1 < nr) blur_issue(r + 1);                  // the next round's windows fly during this one
+        const uint8_t* bc = win + (y - ys) * kPitchL + (x - xs);
+        __builtin_amdgcn_wave_barrier();
+        const f2 aa = {a, a}, bb = {b, b}, nbb = {-b, -b};
+        const uint8_t* bc0 = bc - (size_t)(0x400000u * (uint32_t)kPitchL + kMagicBits);
+        // the pattern words are round-invariant: keep their 64 converted coordinates from being hoisted out of the rounds
+        // (they would hold 64 registers across the whole phase)
+#pragma unroll
+        for (int it = 0; it < 16; it++) asm volatile("" : "+v"(pat[it]));
+        uint32_t mine = 0;
+#pragma unroll
+        for (int it = 0; it < 16; it++) {
+            const float px0 = (float)(signed char)(pat[it] & 0xFF), py0 = (float)(signed char)((pat[it] >> 8) & 0xFF);
+            const float px1 = (float)(signed char)((pat[it] >> 16) & 0xFF), py1 = (float)(signed char)((pat[it] >> 24) & 0xFF);
+            const f2 PX = {px0, px1}, PY = {py0, py1};
+            const f2 fx = PX * aa + PY * nbb + magic;
+            const f2 fy = PX * bb + PY * aa + magic;
+            const uint32_t o0 = __umul24(__float_as_uint(fy.x), kPitchL) + __float_as_uint(fx.x);
+            const uint32_t o1 = __umul24(__float_as_uint(fy.y), kPitchL) + __float_as_uint(fx.y);
+            const int t0 = bc0[o0];
+            const int t1 = bc0[o1];
+            const unsigned long long m = __ballot(t0 < t1);
+            if (__builtin_amdgcn_inverse_ballot_w64(0x0001000100010001ull << it)) mine = (uint32_t)(m >> (16 * grp)) & 0xFFFFu;
+        }
+        if (orow >= 0) {
+            int fr, lr;
+            round_fl(r, fr, lr);
+            *reinterpret_cast<uint16_t*>(desc + ((int64_t)fr * kp_cap + orow) * 32 + 2 * l16) = (uint16_t)mine;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (stamps) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
+    DSTAMP16(4);
+
+    // ---- the 16 keypoint records from their lanes ----
+    if (orow_s >= 0) {
+        float scale = P.lv[l].scale;
+        if constexpr (ARENA) {                                // (the lane's level: a select chain, no indexed kernel argument)
+#pragma unroll
+            for (int i = 1; i < kLevels; i++)
+                if (l_s == i) scale = P.lv[i].scale;
+        }
+        aria_keypoint k;
+        k.x = (float)x_s * scale;
+        k.y = (float)y_s * scale;
+        k.size = kPatchSize * scale;
+        k.angle = angle_s;
+        k.response = __uint_as_float(sv.y);
+        k.octave = l_s;
+        kps[(int64_t)frame_s * kp_cap + orow_s] = k;
+    }
+    DSTAMP16(5);
+#undef DSTAMP16
+}
+
+template <int MODE, bool Q4, bool W16 = false>
+__global__ __launch_bounds__(64 * kDescWaves, W16 && MODE == 0 ? 4 : 1) void k_describe(Plan P, FrameSrc S, const uint8_t* __restrict__ raw,
                                                   const uint8_t* __restrict__ blur, const uint4* __restrict__ sel,
                                                   const int* __restrict__ sel_cnt, aria_keypoint* __restrict__ kps,
                                                   uint8_t* __restrict__ desc, int* __restrict__ counts, int kp_cap,
                                                   int* __restrict__ err, int n_frames, int blocks_per_frame,
                                                   unsigned long long* __restrict__ stamps,
                                                   const uint4* __restrict__ osel, const int* __restrict__ ovf, int osel_cap) {
+    if constexpr (W16) {
+        static_assert(Q4 && MODE < 2, "the 16-keypoint form is the batch Q4 form");
+        if constexpr (MODE == 0) {
+            describe16<0>(P, S, raw, blur, sel, sel_cnt, kps, desc, counts, kp_cap, err, n_frames, blocks_per_frame, stamps,
+                          osel, ovf, osel_cap, (int)blockIdx.x);
+        } else {
+            const int n_blk = (min(ovf[1], osel_cap) + kDescWaves * kDesc16Kp - 1) / (kDescWaves * kDesc16Kp);
+            for (int blk = blockIdx.x; blk < n_blk; blk += gridDim.x)
+                describe16<1>(P, S, raw, blur, sel, sel_cnt, kps, desc, counts, kp_cap, err, n_frames, blocks_per_frame,
+                              stamps, osel, ovf, osel_cap, blk);
+        }
+        return;
+    }
     // diagnostic only (ARIA_DESC_STAMPS=1): s_memtime at the phase boundaries of every wave
 #define DSTAMP(k) do { if (stamps && (threadIdx.x & 63) == 0) stamps[((size_t)blockIdx.x * kDescWaves + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
     DSTAMP(0);
@@ -1074,6 +1423,7 @@ const EnvConfig& env_config() {
         c.band_xcd_map = env_is("ARIA_BAND_XCD_MAP", '0') ? 0 : 1;
         c.band_trim = env_is("ARIA_BAND_TRIM", '0') ? 0 : 1;
         c.desc_stamps = env_is("ARIA_DESC_STAMPS", '1') ? 1 : 0;
+        c.desc_quad = env_is("ARIA_DESC_IMPL", 'q') ? 1 : 0;
         c.fast_blur_impl = env_is("ARIA_FAST_BLUR_IMPL", 't') ? 0 : env_is("ARIA_FAST_BLUR_IMPL", 'm') ? 1 : 2;
         c.pyr_impl = env_is("ARIA_PYRAMID_IMPL", 'f') ? 1 : 0;
         c.rs_impl = env_is("ARIA_RESIZE_IMPL", 'd') ? 0 : env_is("ARIA_RESIZE_IMPL", 'l') ? 1 : 2;
@@ -1267,7 +1617,9 @@ void launch_extract_chunk(const Plan& P, const FrameSrc& S, const DeviceScratch&
     // ---- a6.6 + a6.8 angle + descriptor ----
     if (prof) prof->begin(STAGE_DESCRIBE, st);
     {
-        const int bpf = (P.sel_frame_entries + kDescKp - 1) / kDescKp;
+        // batch Q4 levels: 16 keypoints per wave (describe16); the variants build keeps the 4-keypoint body (ARIA_DESC_IMPL=quad)
+        const bool w16 = !latency && ctx.last_blur_q4 && !E.desc_quad;
+        const int bpf = w16 ? (desc16_waves_per_frame(P) + kDescWaves - 1) / kDescWaves : (P.sel_frame_entries + kDescKp - 1) / kDescKp;
         const int frames8 = (n_frames + 7) / 8 * 8;
         const size_t nwaves = (size_t)bpf * frames8 * kDescWaves;
         // diagnostic: ARIA_DESC_STAMPS=1 prints mean phase lengths
@@ -1277,14 +1629,23 @@ void launch_extract_chunk(const Plan& P, const FrameSrc& S, const DeviceScratch&
             ARIA_LAUNCH(prof, (k_describe<2, false>), dim3((unsigned)(bpf * frames8 + kDescArenaBlocks)), dim3(64 * kDescWaves), 0, st, P, S,
                         D.raw, D.blur, D.sel, D.sel_cnt, d_kps, d_desc, d_counts, kp_cap, D.err, n_frames, bpf, stp,
                         (const uint4*)D.osel, (const int*)D.ovf, D.osel_cap);
+        } else if (w16) {
+            ARIA_LAUNCH(prof, (k_describe<0, true, true>), dim3((unsigned)(bpf * frames8)), dim3(64 * kDescWaves), 0, st, P, S, D.raw,
+                        D.blur, D.sel, D.sel_cnt, d_kps, d_desc, d_counts, kp_cap, D.err, n_frames, bpf, stp, (const uint4*)nullptr,
+                        (const int*)nullptr, 0);
+            // arena pass of the tie-storm fallback: every block finds the arena empty on ordinary images
+            ARIA_LAUNCH(prof, (k_describe<1, true, true>), dim3(256), dim3(64 * kDescWaves), 0, st, P, S,
+                        D.raw, D.blur, D.sel, D.sel_cnt, d_kps, d_desc, d_counts, kp_cap, D.err, n_frames, bpf,
+                        (unsigned long long*)nullptr, (const uint4*)D.osel, (const int*)D.ovf, D.osel_cap);
+#ifdef ARIA_VARIANTS
         } else if (ctx.last_blur_q4) {
             ARIA_LAUNCH(prof, (k_describe<0, true>), dim3((unsigned)(bpf * frames8)), dim3(64 * kDescWaves), 0, st, P, S, D.raw, D.blur,
                         D.sel, D.sel_cnt, d_kps, d_desc, d_counts, kp_cap, D.err, n_frames, bpf, stp, (const uint4*)nullptr,
                         (const int*)nullptr, 0);
-            // arena pass of the tie-storm fallback: every block finds the arena empty on ordinary images
             ARIA_LAUNCH(prof, (k_describe<1, true>), dim3(256), dim3(64 * kDescWaves), 0, st, P, S,
                         D.raw, D.blur, D.sel, D.sel_cnt, d_kps, d_desc, d_counts, kp_cap, D.err, n_frames, bpf,
                         (unsigned long long*)nullptr, (const uint4*)D.osel, (const int*)D.ovf, D.osel_cap);
+#endif
         } else {
             ARIA_LAUNCH(prof, (k_describe<0, false>), dim3((unsigned)(bpf * frames8)), dim3(64 * kDescWaves), 0, st, P, S, D.raw, D.blur,
                         D.sel, D.sel_cnt, d_kps, d_desc, d_counts, kp_cap, D.err, n_frames, bpf, stp, (const uint4*)nullptr,
@@ -1298,13 +1659,19 @@ void launch_extract_chunk(const Plan& P, const FrameSrc& S, const DeviceScratch&
             std::vector<unsigned long long> hs(nwaves * 8);
             hipMemcpy(hs.data(), stp, hs.size() * 8, hipMemcpyDeviceToHost);
             double ph[6] = {0}; size_t n = 0;
+            const int np = w16 ? 5 : 6;            // 16-keypoint form: stamps 0..5; 4-keypoint form: 0..6
             for (size_t w = 0; w < nwaves; w++) {
-                if (!hs[w * 8 + 6] || !hs[w * 8 + 5] || !hs[w * 8 + 1]) continue;      // wave left early (empty slots: only stamps 0 and 6)
-                for (int k = 0; k < 6; k++) ph[k] += (double)(hs[w * 8 + k + 1] - hs[w * 8 + k]);
+                if (!hs[w * 8 + np] || !hs[w * 8 + 1]) continue;      // wave left early (empty slots)
+                if (!w16 && !hs[w * 8 + 5]) continue;
+                for (int k = 0; k < np; k++) ph[k] += (double)(hs[w * 8 + k + 1] - hs[w * 8 + k]);
                 n++;
             }
-            if (n) fprintf(stderr, "[describe stamps] %zu waves, 100 MHz ticks: sel %.1f windows %.1f moments+atan %.1f sincos %.1f pattern %.1f store %.1f\n",
-                           n, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n, ph[5] / n);
+            if (n && w16)
+                fprintf(stderr, "[describe stamps] 16-kp form, %zu waves, 100 MHz ticks: sel %.1f moment rounds %.1f atan+sincos %.1f pattern rounds %.1f records %.1f\n",
+                        n, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n);
+            else if (n)
+                fprintf(stderr, "[describe stamps] %zu waves, 100 MHz ticks: sel %.1f windows %.1f moments+atan %.1f sincos %.1f pattern %.1f store %.1f\n",
+                        n, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n, ph[5] / n);
         }
     }
     if (prof) prof->end(st);
