@@ -42,6 +42,9 @@ EXPORTS = [
     "aria_copy_h2d_async", "aria_copy_d2h_async", "aria_copy_d2d_async", "aria_fill_async", "aria_stream_synchronize",
     "aria_event_create", "aria_event_destroy", "aria_event_record", "aria_stream_wait_event", "aria_event_synchronize",
     "aria_event_elapsed_ms", "aria_matcher_knn_kernel",
+    # two-view relative pose (essential-matrix RANSAC + recoverPose), additive to ABI 4
+    "aria_pose_default_config", "aria_pose_create", "aria_pose_destroy", "aria_pose_stream", "aria_pose_check",
+    "aria_pose_estimate", "aria_pose_estimate_batch_device", "aria_pose_debug_hypotheses",
 ]
 
 
@@ -54,6 +57,18 @@ class OrbConfig(C.Structure):
 class MatcherConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("max_query", C.c_int),
                 ("max_train", C.c_int)]
+
+
+class PoseConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("hypotheses", C.c_int),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("threshold_px", C.c_double), ("distance_thresh", C.c_double), ("seed", C.c_uint64)]
+
+
+# aria_pose_result (192 bytes)
+POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,)), ("n_matches", "<i4"),
+                              ("n_inliers", "<i4"), ("n_pose_inliers", "<i4"), ("best_hypothesis", "<i4"),
+                              ("refined", "<i4"), ("valid", "<i4")])
 
 
 class AriaError(RuntimeError):
@@ -187,10 +202,30 @@ def load_library():
                                            C.POINTER(C.c_int64)]
     L.aria_matcher_stream.argtypes = [C.c_void_p]
     L.aria_matcher_sync.argtypes = [C.c_void_p]
+    if hasattr(L, "aria_pose_create"):   # absent from A/B builds of the extractor sources alone (tools/build_ab.sh)
+        _bind_pose(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
     return L
+
+
+def _bind_pose(L):
+    L.aria_pose_default_config.restype = None
+    L.aria_pose_default_config.argtypes = [C.c_void_p]
+    L.aria_pose_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.aria_pose_destroy.restype = None
+    L.aria_pose_destroy.argtypes = [C.c_void_p]
+    L.aria_pose_stream.restype = C.c_void_p
+    L.aria_pose_stream.argtypes = [C.c_void_p]
+    L.aria_pose_check.argtypes = [C.c_void_p]
+    L.aria_pose_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p]
+    L.aria_pose_estimate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p]
+    L.aria_pose_debug_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def status_string(status):

@@ -12,6 +12,7 @@
 #include <optional>
 #include <vector>
 
+#include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
 
 namespace aria::pipeline {
@@ -35,6 +36,12 @@ struct FrontEndConfig {
     // (factory::createHip does that) the match is queued behind extractAsync and one wait covers both (the async shape of
     // docs/milestones/H12_CLEAN_ARCHITECTURE.md:711-716). Results are identical either way; false = always the host port calls.
     bool device_handoff = true;
+    // Pose stage of the evaluation loop (src/euroc_eval.cpp:178-201): essential-matrix RANSAC + recoverPose of previous ->
+    // current on the device (aria_hip/HipPoseEstimator.hpp), whatever legacy_order is, on the match list after the
+    // dynamic-object filter, when it has >= 8 entries (:179). Off by default: results without it are unchanged.
+    bool estimate_pose = false;
+    adapters::hip::PoseIntrinsics pose_intrinsics{};      // the caller's K (EuRoC cam0 by default, as euroc_eval.cpp uses)
+    int pose_hypotheses = 1024;
 };
 
 // COCO ids of src/main.cpp:29-40: person, bicycle, car, motorcycle, bus, train, truck, bird, cat, dog
@@ -47,6 +54,9 @@ struct FrontEndResult {
     int filtered_count = 0;                   // matches dropped by the dynamic-object filter (main.cpp:172)
     bool is_keyframe = false;                 // the frame was handed to the loop detector
     std::optional<core::LoopCandidate> loop;  // what ILoopDetector::detect returned for it
+    // estimate_pose: previous -> current (x_cur ~ R x_prev + t, |t| = 1); empty on the first frame, with < 8 matches or
+    // when no pose was found. The caller applies its own acceptance test (euroc_eval.cpp:191: n_pose_inliers > 10).
+    std::optional<adapters::hip::TwoViewPose> pose;
 };
 
 class FrontEnd {
@@ -85,6 +95,7 @@ private:
     std::function<void(const FrontEndResult&)> callback_;
     std::uint64_t next_id_ = 0;
     int handoff_mode_ = 0;
+    std::unique_ptr<adapters::hip::HipPoseEstimator> pose_;   // created on the first frame that needs it (estimate_pose)
 };
 
 }  // namespace aria::pipeline

@@ -123,6 +123,16 @@ const FrontEndResult& FrontEnd::processFrame(const std::uint8_t* image_data, int
         result_.matches.resize(kept);
     }
     detections_.clear();
+    result_.pose.reset();
+    if (cfg_.estimate_pose && prev_ && result_.matches.size() >= 8) {        // euroc_eval.cpp:178-188
+        if (!pose_) {
+            auto* hx = dynamic_cast<adapters::hip::OrbHipExtractor*>(extractor_.get());
+            pose_ = std::make_unique<adapters::hip::HipPoseEstimator>(cfg_.pose_intrinsics, cfg_.pose_hypotheses, 1.0, 50.0, 0,
+                                                                     nullptr, hx ? hx->device() : 0);
+        }
+        // view 1 = previous frame: the query side in the legacy order, the train side in SlamPipeline's
+        result_.pose = pose_->estimate(*prev_, *cur_, result_.matches, cfg_.legacy_order, (int)(cur_->id & 0x7fffffff));
+    }
     result_.is_keyframe = false;
     result_.loop.reset();
     if (loop_detector_ && prev_ && (int)result_.matches.size() >= cfg_.keyframe_min_matches) {

@@ -1,5 +1,5 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--devices N] [--shards K]
-//                [--batch B] [--decode-threads T]
+//                [--batch B] [--decode-threads T] [--pose FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -21,10 +21,17 @@
 // come back per chunk. Same per-frame results (hashes, keyframes, loops) as the frame-at-a-time run; the summary names
 // decode, staging and kernel time apart. The loop-closure step then runs over the merged stream as in the sharded mode.
 //
+// --pose FILE: the pose stage of euroc_eval.cpp:178-201 on the frame-at-a-time path (one shard, no --batch): previous ->
+// current by essential-matrix RANSAC + recoverPose on the device (FrontEndConfig::estimate_pose, EuRoC cam0 intrinsics);
+// current_pose = current_pose * [R t] when n_pose_inliers > 10 (:191-206). FILE gets one TUM line per frame,
+// "timestamp tx ty tz qx qy qz qw" of current_pose. Without the flag nothing of this runs and the output is unchanged.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
 #include <algorithm>
+#include <array>
+#include <cmath>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -73,12 +80,12 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--devices N] [--shards K] [--batch B] [--decode-threads T]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file]\n", argv[0]);
         return -1;                                                        // euroc_eval.cpp:64-70
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
-    std::string csv;
+    std::string csv, pose_file;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -87,12 +94,17 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--shards") && i + 1 < argc) shards = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--decode-threads") && i + 1 < argc) decode_threads = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--pose") && i + 1 < argc) pose_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
     if (shards < 1) shards = devices;
     if (batch < 0) batch = 0;
     if (decode_threads < 1) decode_threads = 1;
+    if (!pose_file.empty() && (batch > 0 || devices > 1 || shards > 1)) {
+        std::fprintf(stderr, "--pose runs on the frame-at-a-time path only (no --batch, --devices, --shards)\n");
+        return -1;
+    }
     {
         // --devices names HIP ordinals 0 .. N-1: refuse up front what the machine does not have (FactoryConfig::cuda_device,
         // include/factory/PipelineFactory.hpp:24, is taken on trust by the reference)
@@ -120,6 +132,9 @@ int main(int argc, char** argv) {
     const bool sharded = shards > 1;
     const bool posthoc_loop = loop && (sharded || batch > 0);      // the loop step over the merged stream, after the shards
     std::vector<pipeline::BatchStats> bstats((size_t)shards);
+    // --pose: current_pose per frame (4x4 row-major), chained as euroc_eval.cpp:202-206 does
+    std::vector<std::array<double, 16>> traj(pose_file.empty() ? 0 : N);
+    long long n_pose_updates = 0;
     const auto t0 = std::chrono::steady_clock::now();
 
     // one shard = one FrontEnd (its own extractor + matcher handles on its device) over frames [first, hi)
@@ -153,14 +168,29 @@ int main(int argc, char** argv) {
             fc.max_features = max_features;
             fc.frontend.legacy_order = legacy;
             fc.enable_loop_closure = loop && !posthoc_loop;               // LoopClosureDetector(200, 0.4, 50), euroc_eval.cpp:103
+            fc.frontend.estimate_pose = !pose_file.empty();
             std::unique_ptr<pipeline::FrontEnd> fe = factory::createHip(fc);
             std::vector<std::uint8_t> gray;
             int fw = 0, fh = 0;
             auto t_last = std::chrono::steady_clock::now();
+            std::array<double, 16> current_pose = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
             for (std::size_t i = sp.first; i < sp.hi; i++) {
                 seq.read(i, gray, fw, fh);
                 const pipeline::FrontEndResult& r = fe->processFrame(gray.data(), fw, fh, seq.at(i).timestamp);
                 if (i < sp.lo) continue;                                   // the halo frame only provides the previous descriptors
+                if (!traj.empty()) {
+                    if (r.pose && r.pose->n_pose_inliers > 10) {           // euroc_eval.cpp:191
+                        const std::array<double, 16> d = adapters::hip::poseMatrix(*r.pose), c = current_pose;
+                        for (int a = 0; a < 4; a++)
+                            for (int b = 0; b < 4; b++) {
+                                double v = 0.0;
+                                for (int k = 0; k < 4; k++) v += c[(size_t)(a * 4 + k)] * d[(size_t)(k * 4 + b)];
+                                current_pose[(size_t)(a * 4 + b)] = v;     // current_pose = current_pose * delta (:206)
+                            }
+                        n_pose_updates++;
+                    }
+                    traj[i] = current_pose;
+                }
                 FrameRecord& o = rec[i];
                 o.keypoints = r.frame->numKeypoints();
                 o.matches = r.matches.size();
@@ -244,5 +274,30 @@ int main(int argc, char** argv) {
                     t.d2h_s > 0 ? t.d2h_bytes / t.d2h_s * 1e-9 : 0.0, t.deliver_s, t.wall_s);
     }
     if (loop) std::printf("keyframes %lld loops %lld\n", n_keyframes, n_loops);
+    if (!pose_file.empty()) {
+        std::ofstream tf(pose_file);
+        tf << std::fixed << std::setprecision(9);
+        for (std::size_t i = 0; i < N; i++) {
+            const std::array<double, 16>& T = traj[i];
+            double q[4];                                                   // rotation -> quaternion (x, y, z, w)
+            const double tr = T[0] + T[5] + T[10];
+            if (tr > 0) {
+                const double s = std::sqrt(tr + 1.0) * 2;
+                q[3] = 0.25 * s; q[0] = (T[9] - T[6]) / s; q[1] = (T[2] - T[8]) / s; q[2] = (T[4] - T[1]) / s;
+            } else if (T[0] > T[5] && T[0] > T[10]) {
+                const double s = std::sqrt(1.0 + T[0] - T[5] - T[10]) * 2;
+                q[3] = (T[9] - T[6]) / s; q[0] = 0.25 * s; q[1] = (T[1] + T[4]) / s; q[2] = (T[2] + T[8]) / s;
+            } else if (T[5] > T[10]) {
+                const double s = std::sqrt(1.0 + T[5] - T[0] - T[10]) * 2;
+                q[3] = (T[2] - T[8]) / s; q[0] = (T[1] + T[4]) / s; q[1] = 0.25 * s; q[2] = (T[6] + T[9]) / s;
+            } else {
+                const double s = std::sqrt(1.0 + T[10] - T[0] - T[5]) * 2;
+                q[3] = (T[4] - T[1]) / s; q[0] = (T[2] + T[8]) / s; q[1] = (T[6] + T[9]) / s; q[2] = 0.25 * s;
+            }
+            tf << seq.at(i).timestamp << ' ' << T[3] << ' ' << T[7] << ' ' << T[11] << ' ' << q[0] << ' ' << q[1] << ' ' << q[2]
+               << ' ' << q[3] << '\n';
+        }
+        std::printf("pose updates %lld of %zu frames -> %s\n", n_pose_updates, N > 0 ? N - 1 : 0, pose_file.c_str());
+    }
     return 0;
 }

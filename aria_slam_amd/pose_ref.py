@@ -1,0 +1,322 @@
+"""NumPy fp64 restatement of the two-view relative pose stage (include/aria_orb_hip.h, "two-view relative pose";
+kernels in aria_slam_amd/csrc/pose_ransac.hip): the same sample hash, minimal solver, scoring, refit and recoverPose.
+
+Tests hold the device to it, and it serves as a CPU fallback for callers without a GPU. Where the device and this module
+use different but equivalent numerics (3x3 / 9x9 eigen-solvers: Jacobi there, LAPACK here; Sampson test in fp32 there,
+fp64 here) results agree to rounding; inlier decisions can differ only for points within rounding of the threshold.
+"""
+import numpy as np
+
+from ._lib import KP_DTYPE, MATCH_DTYPE
+
+# EuRoC cam0 (reference src/legacy/EuRoCReader.cpp:11-17)
+EUROC_K = (458.654, 457.296, 367.215, 248.375)
+PIVOT_TOL = 1e-9
+RANK_TOL = 1e-9
+MAX_RETRY = 256
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(x):
+    """splitmix64 on a uint64 array (wrapping arithmetic)."""
+    x = np.asarray(x, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def hypothesis_keys(seed, pair, hs):
+    """key(pair, h) = splitmix64(splitmix64(splitmix64(seed) ^ pair) ^ h) for every h in hs."""
+    s = splitmix64(np.array([seed & _M64], np.uint64))
+    p = splitmix64(s ^ np.uint64(pair & 0xFFFFFFFF))
+    return splitmix64(p ^ np.asarray(hs, np.uint64))
+
+
+def draw(keys, j, retry, n):
+    """((splitmix64(key ^ (8 retry + j)) >> 32) * n) >> 32."""
+    r = splitmix64(np.asarray(keys, np.uint64) ^ np.uint64(8 * retry + j))
+    with np.errstate(over="ignore"):
+        return (((r >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def sample_indices(seed, pair, hypotheses, n):
+    """(hypotheses, 8) sample indices; a row of -1 for n < 8 or a slot that stayed duplicate after MAX_RETRY draws."""
+    H = int(hypotheses)
+    out = np.full((H, 8), -1, np.int64)
+    if n < 8:
+        return out
+    keys = hypothesis_keys(seed, pair, np.arange(H, dtype=np.uint64))
+    ok = np.ones(H, bool)
+    for j in range(8):
+        todo = np.ones(H, bool)
+        for retry in range(MAX_RETRY):
+            if not todo.any():
+                break
+            c = draw(keys[todo], j, retry, n)
+            dup = (out[todo, :j] == c[:, None]).any(axis=1)
+            rows = np.flatnonzero(todo)
+            out[rows[~dup], j] = c[~dup]
+            todo[rows[~dup]] = False
+        ok &= ~todo
+    out[~ok] = -1
+    return out
+
+
+def normalise(kp_query, kp_train, matches, query_is_first=True, K=EUROC_K):
+    """(n, 4) float32 point pairs (x1, y1, x2, y2) as the device stages them."""
+    fx, fy, cx, cy = K
+    kq = np.asarray(kp_query).view(KP_DTYPE) if len(kp_query) else np.zeros(0, KP_DTYPE)
+    kt = np.asarray(kp_train).view(KP_DTYPE) if len(kp_train) else np.zeros(0, KP_DTYPE)
+    m = np.asarray(matches).view(MATCH_DTYPE) if len(matches) else np.zeros(0, MATCH_DTYPE)
+    a, b = kq[m["query_idx"]], kt[m["train_idx"]]
+    k1, k2 = (a, b) if query_is_first else (b, a)
+    pts = np.empty((len(m), 4), np.float32)
+    pts[:, 0] = (k1["x"].astype(np.float64) - cx) / fx
+    pts[:, 1] = (k1["y"].astype(np.float64) - cy) / fy
+    pts[:, 2] = (k2["x"].astype(np.float64) - cx) / fx
+    pts[:, 3] = (k2["y"].astype(np.float64) - cy) / fy
+    return pts
+
+
+def design_rows(pts):
+    """Rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1] of x2^T E x1 = 0, fp64."""
+    p = np.asarray(pts, np.float64)
+    x1, y1, x2, y2 = p[..., 0], p[..., 1], p[..., 2], p[..., 3]
+    return np.stack([x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, np.ones_like(x1)], axis=-1)
+
+
+def project_essential(f):
+    """(E, ok): E = (u1 v1^T + u2 v2^T) / sqrt(2) of the 3x3 reading of each row of f (..., 9); ok = sigma2 > RANK_TOL sigma1."""
+    F = np.asarray(f, np.float64).reshape(-1, 3, 3)
+    U, s, Vt = np.linalg.svd(F)
+    E = (U[:, :, 0, None] * Vt[:, None, 0, :] + U[:, :, 1, None] * Vt[:, None, 1, :]) / np.sqrt(2.0)
+    ok = s[:, 1] > RANK_TOL * s[:, 0]
+    E[~ok] = 0.0
+    return E.reshape(-1, 9), ok
+
+
+def solve_minimal(samples):
+    """Normalised 8-point on (H, 8, 4) point samples: Gaussian elimination with partial pivoting (the device's order of
+    operations), back substitution with f8 = 1, unit norm, projection. Returns (E (H, 9) fp64, valid (H,))."""
+    A = design_rows(samples).copy()
+    H = A.shape[0]
+    ar = np.arange(H)
+    amax = np.abs(A).reshape(H, -1).max(axis=1)
+    ok = np.ones(H, bool)
+    for c in range(8):
+        col = np.abs(A[:, c:, c])
+        piv = c + np.argmax(col, axis=1)
+        ok &= col.max(axis=1) > PIVOT_TOL * amax
+        rc = A[:, c, :].copy()
+        A[:, c, :] = A[ar, piv, :]
+        A[ar, piv, :] = rc
+        inv = 1.0 / np.where(ok, A[:, c, c], 1.0)
+        f = A[:, c + 1:, c] * inv[:, None]
+        A[:, c + 1:, c + 1:] = A[:, c + 1:, c + 1:] - f[:, :, None] * A[:, c, None, c + 1:]
+    sol = np.zeros((H, 9))
+    sol[:, 8] = 1.0
+    with np.errstate(all="ignore"):
+        for c in range(7, -1, -1):
+            s = np.zeros(H)
+            for k in range(c + 1, 9):
+                s = s + A[:, c, k] * sol[:, k]
+            sol[:, c] = -s / np.where(ok, A[:, c, c], 1.0)
+        nrm = np.zeros(H)
+        for k in range(9):
+            nrm = nrm + sol[:, k] * sol[:, k]
+        sol = sol / np.sqrt(nrm)[:, None]
+    sol[~ok] = 1.0
+    E, ok2 = project_essential(sol)
+    ok &= ok2
+    E[~ok] = 0.0
+    return E, ok
+
+
+def sampson_inliers(E, pts, thr2):
+    """(H, n) bool: r^2 <= thr2 * d with d > 0 (the device's division-free Sampson test), fp64 on the given E and points."""
+    e = np.asarray(E, np.float64).reshape(-1, 9)
+    p = np.asarray(pts, np.float64)
+    x1, y1, x2, y2 = (p[:, i][None, :] for i in range(4))
+    E_ = [e[:, k, None] for k in range(9)]
+    ex0 = E_[0] * x1 + E_[1] * y1 + E_[2]
+    ex1 = E_[3] * x1 + E_[4] * y1 + E_[5]
+    ex2 = E_[6] * x1 + E_[7] * y1 + E_[8]
+    et0 = E_[0] * x2 + E_[3] * y2 + E_[6]
+    et1 = E_[1] * x2 + E_[4] * y2 + E_[7]
+    r = x2 * ex0 + y2 * ex1 + ex2
+    d = ex0 * ex0 + ex1 * ex1 + et0 * et0 + et1 * et1
+    return (d > 0) & (r * r <= thr2 * d)
+
+
+def sampson_error(E, pts):
+    """(H, n) squared Sampson distance r^2 / d (inf where d == 0)."""
+    e = np.asarray(E, np.float64).reshape(-1, 9)
+    p = np.asarray(pts, np.float64)
+    x1, y1, x2, y2 = (p[:, i][None, :] for i in range(4))
+    ex0 = e[:, 0, None] * x1 + e[:, 1, None] * y1 + e[:, 2, None]
+    ex1 = e[:, 3, None] * x1 + e[:, 4, None] * y1 + e[:, 5, None]
+    ex2 = e[:, 6, None] * x1 + e[:, 7, None] * y1 + e[:, 8, None]
+    et0 = e[:, 0, None] * x2 + e[:, 3, None] * y2 + e[:, 6, None]
+    et1 = e[:, 1, None] * x2 + e[:, 4, None] * y2 + e[:, 7, None]
+    r = x2 * ex0 + y2 * ex1 + ex2
+    d = ex0 * ex0 + ex1 * ex1 + et0 * et0 + et1 * et1
+    with np.errstate(all="ignore"):
+        return np.where(d > 0, r * r / np.where(d > 0, d, 1.0), np.inf)
+
+
+def threshold2(threshold_px=1.0, K=EUROC_K):
+    t = threshold_px / ((K[0] + K[1]) * 0.5)
+    return float(np.float32(t * t))
+
+
+def hypotheses(pts, seed=0, pair=0, n_hyp=1024, threshold_px=1.0, K=EUROC_K):
+    """What aria_pose_debug_hypotheses returns: (sample_idx (H, 8), E (H, 9) fp64, counts (H,), -1 = invalid)."""
+    n = len(pts)
+    idx = sample_indices(seed, pair, n_hyp, n)
+    valid = (idx >= 0).all(axis=1)
+    E = np.zeros((n_hyp, 9))
+    counts = np.full(n_hyp, -1, np.int64)
+    if valid.any():
+        Ev, ok = solve_minimal(np.asarray(pts)[idx[valid]])
+        rows = np.flatnonzero(valid)
+        E[rows[ok]] = Ev[ok]
+        valid[rows[~ok]] = False
+    if valid.any():
+        Ef = E[valid].astype(np.float32)
+        counts[valid] = sampson_inliers(Ef, pts, threshold2(threshold_px, K)).sum(axis=1)
+    return idx, E, counts
+
+
+def decompose_essential(E):
+    """cv::decomposeEssentialMat: [(R1, t), (R2, t), (R1, -t), (R2, -t)]."""
+    U, _s, Vt = np.linalg.svd(np.asarray(E, np.float64).reshape(3, 3))
+    if np.linalg.det(U) < 0:
+        U = -U
+    if np.linalg.det(Vt) < 0:
+        Vt = -Vt
+    W = np.array([[0.0, 1, 0], [-1, 0, 0], [0, 0, 1]])
+    R1, R2, t = U @ W @ Vt, U @ W.T @ Vt, U[:, 2].copy()
+    return [(R1, t), (R2, t), (R1, -t), (R2, -t)]
+
+
+def cheirality(R, t, pts, dist=50.0):
+    """(n,) bool: least-squares depths (z1, z2) of z2 x2 = z1 R x1 + t both in (0, dist)."""
+    p = np.asarray(pts, np.float64)
+    x1 = np.stack([p[:, 0], p[:, 1], np.ones(len(p))], axis=1)
+    x2 = np.stack([p[:, 2], p[:, 3], np.ones(len(p))], axis=1)
+    a = x1 @ np.asarray(R).T
+    aa, bb, ab = (a * a).sum(1), (x2 * x2).sum(1), (a * x2).sum(1)
+    at, bt = a @ t, x2 @ t
+    det = aa * bb - ab * ab
+    with np.errstate(all="ignore"):
+        z1 = (ab * bt - at * bb) / det
+        z2 = (aa * bt - ab * at) / det
+    return (det > 0) & (z1 > 0) & (z1 < dist) & (z2 > 0) & (z2 < dist)
+
+
+def estimate_points(pts, seed=0, pair=0, n_hyp=1024, threshold_px=1.0, distance_thresh=50.0, K=EUROC_K):
+    """The whole stage on (n, 4) normalised point pairs. Returns a dict with the fields of aria_pose_result and the mask."""
+    n = len(pts)
+    res = dict(R=np.eye(3), t=np.zeros(3), E=np.zeros((3, 3)), n_matches=n, n_inliers=0, n_pose_inliers=0,
+               best_hypothesis=-1, refined=0, valid=0, mask=np.zeros(n, np.uint8))
+    if n < 8:
+        return res
+    _idx, E, counts = hypotheses(pts, seed, pair, n_hyp, threshold_px, K)
+    best = int(np.argmax(counts))            # first maximum: ties to the lowest h
+    if counts[best] < 0:
+        return res
+    thr2 = threshold2(threshold_px, K)
+    Ew = E[best].astype(np.float32).astype(np.float64)
+    inl = sampson_inliers(Ew, pts, thr2)[0]
+    final_E, final_inl, refined = Ew, inl, 0
+    if inl.sum() >= 8:
+        A = design_rows(np.asarray(pts)[inl])
+        M = A.T @ A
+        _w, V = np.linalg.eigh(M)
+        Er, ok = project_essential(V[:, 0])
+        if ok[0]:
+            inl_r = sampson_inliers(Er[0].astype(np.float32), pts, thr2)[0]
+            if inl_r.sum() >= inl.sum():
+                final_E, final_inl, refined = Er[0], inl_r, 1
+    cands = decompose_essential(final_E)
+    masks = [cheirality(R, t, np.asarray(pts)[final_inl], distance_thresh) for R, t in cands]
+    g = [int(m.sum()) for m in masks]
+    c = 0 if (g[0] >= g[1] and g[0] >= g[2] and g[0] >= g[3]) else 1 if (g[1] >= g[2] and g[1] >= g[3]) else 2 if g[2] >= g[3] else 3
+    mask = np.zeros(n, np.uint8)
+    mask[np.flatnonzero(final_inl)[masks[c]]] = 1
+    res.update(R=cands[c][0], t=cands[c][1], E=np.asarray(final_E).reshape(3, 3), n_inliers=int(final_inl.sum()),
+               n_pose_inliers=g[c], best_hypothesis=best, refined=refined, valid=1, mask=mask)
+    return res
+
+
+def estimate(kp_query, kp_train, matches, query_is_first=True, seed=0, pair=0, n_hyp=1024, threshold_px=1.0,
+             distance_thresh=50.0, K=EUROC_K):
+    """aria_pose_estimate on the CPU."""
+    pts = normalise(kp_query, kp_train, matches, query_is_first, K)
+    return estimate_points(pts, seed, pair, n_hyp, threshold_px, distance_thresh, K)
+
+
+def rotation_error_deg(R1, R2):
+    c = (np.trace(np.asarray(R1).T @ np.asarray(R2)) - 1.0) / 2.0
+    return float(np.degrees(np.arccos(np.clip(c, -1.0, 1.0))))
+
+
+def angle_deg(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    c = a @ b / (np.linalg.norm(a) * np.linalg.norm(b))
+    return float(np.degrees(np.arccos(np.clip(c, -1.0, 1.0))))
+
+
+def rot(axis, deg):
+    """Rotation matrix about a unit axis."""
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    th = np.radians(deg)
+    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+
+
+def synth_two_view(seed, n, R, t, outlier_frac=0.0, noise_px=0.5, K=EUROC_K, width=752, height=480, depth=(2.0, 20.0)):
+    """Synthetic matched keypoints of a 3-D scene seen by camera 1 (identity) and camera 2 (X2 = R X1 + t).
+
+    Returns (kp_query, kp_train, matches, inlier_truth): query = view 1, train = view 2, match i pairs keypoint i with i;
+    the first round(n * outlier_frac) matches (shuffled among the rest) pair view-1 points with random view-2 pixels."""
+    fx, fy, cx, cy = K
+    rng = np.random.default_rng(seed)
+    R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
+    p1 = np.zeros((n, 2))
+    p2 = np.zeros((n, 2))
+    k = 0
+    while k < n:
+        u = rng.uniform(0, width, 4 * n)
+        v = rng.uniform(0, height, 4 * n)
+        z = rng.uniform(depth[0], depth[1], 4 * n)
+        X1 = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], axis=1)
+        X2 = X1 @ R.T + t
+        keep = X2[:, 2] > 0.5
+        u2 = fx * X2[:, 0] / np.where(keep, X2[:, 2], 1) + cx
+        v2 = fy * X2[:, 1] / np.where(keep, X2[:, 2], 1) + cy
+        keep &= (u2 >= 0) & (u2 < width) & (v2 >= 0) & (v2 < height)
+        sel = np.flatnonzero(keep)[: n - k]
+        p1[k:k + len(sel)] = np.stack([u[sel], v[sel]], 1)
+        p2[k:k + len(sel)] = np.stack([u2[sel], v2[sel]], 1)
+        k += len(sel)
+    p1 += rng.normal(0, noise_px, p1.shape)
+    p2 += rng.normal(0, noise_px, p2.shape)
+    n_out = int(round(n * outlier_frac))
+    truth = np.ones(n, bool)
+    out_idx = rng.permutation(n)[:n_out]
+    truth[out_idx] = False
+    p2[out_idx] = np.stack([rng.uniform(0, width, n_out), rng.uniform(0, height, n_out)], 1)
+    kq = np.zeros(n, KP_DTYPE)
+    kt = np.zeros(n, KP_DTYPE)
+    kq["x"], kq["y"] = p1[:, 0], p1[:, 1]
+    kt["x"], kt["y"] = p2[:, 0], p2[:, 1]
+    for kk in (kq, kt):
+        kk["size"] = 31.0
+        kk["response"] = 1.0
+    m = np.zeros(n, MATCH_DTYPE)
+    m["query_idx"] = np.arange(n)
+    m["train_idx"] = np.arange(n)
+    return kq, kt, m, truth

@@ -367,6 +367,97 @@ int aria_stream_wait_event(int device, void* stream, void* event);
 int aria_event_synchronize(int device, void* event);
 int aria_event_elapsed_ms(void* start_event, void* stop_event, float* ms);
 
+/* ---- two-view relative pose: cv::findEssentialMat(pts1, pts2, K, RANSAC, 0.999, 1.0) + cv::recoverPose, the step every
+ * consumer of a match list takes next in the reference (src/euroc_eval.cpp:178-201, src/main.cpp:186-191,
+ * src/legacy/LoopClosure.cpp:116-190), on the device and batched over pairs. Additive to ABI 4.
+ *
+ * Points. For match m, view 1 is the query keypoint and view 2 the train keypoint when query_is_first = 1 (the legacy
+ *   executables' order, euroc_eval.cpp:181-182: query = previous frame), the other way round when 0. Coordinates are
+ *   normalised by the config's intrinsics in fp64 and rounded to fp32: ((x - cx) / fx, (y - cy) / fy).
+ * Pose. x2 ~ R x1 + t with |t| = 1 (recoverPose's convention); E satisfies x2^T E x1 = 0 and has unit Frobenius norm.
+ *   R, E row-major.
+ * Inliers. Squared Sampson distance in normalised coordinates against thr2 = (threshold_px / ((fx + fy) / 2))^2, as
+ *   findEssentialMat sets it, evaluated in fp32 and division-free: with Ex1 = E x1, Etx2 = E^T x2, r = x2^T E x1,
+ *   d = Ex1[0]^2 + Ex1[1]^2 + Etx2[0]^2 + Etx2[1]^2, a point is an inlier when d > 0 and r^2 <= thr2 * d.
+ * Hypotheses. `hypotheses` per pair (multiple of 64, 64..16384). All arithmetic modulo 2^64 on uint64:
+ *     splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *                    x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31)
+ *     key(pair, h)          = splitmix64(splitmix64(splitmix64(seed) ^ pair) ^ h)     pair = pair_base + p (as uint32)
+ *     draw(pair, h, j, r)   = ((splitmix64(key(pair, h) ^ (8 r + j)) >> 32) * n) >> 32  in [0, n)
+ *   Sample j = 0..7 of hypothesis h is draw(pair, h, j, r) for the first r = 0, 1, ... whose value differs from samples
+ *   0..j-1; a slot still duplicate after 256 draws makes the hypothesis invalid. Results therefore depend on (seed, pair
+ *   id, points) only, not on how pairs are batched (aria_slam_amd/pose_ref.py restates this in Python).
+ * Minimal solver. Normalised 8-point on the sample: rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1] (fp64), Gaussian
+ *   elimination with partial pivoting (first row of largest |a|); a pivot with |pivot| <= 1e-9 * max|A_ij| marks the sample
+ *   rank-deficient: invalid. Back substitution with f8 = 1, scale to unit norm, then projection onto the essential manifold:
+ *   E = (u1 v1^T + u2 v2^T) / sqrt(2) from the SVD of the solution (invalid if sigma2 <= 1e-9 sigma1). The points already
+ *   are in normalised camera coordinates (|x| ~ 1), so Hartley's conditioning transform is not applied again.
+ * Winner. Most inliers; ties to the lowest h; an invalid hypothesis scores -1. Integer counts, fixed reduction order.
+ * Refit. When the winner has >= 8 inliers: one least-squares 8-point fit over them -- the 9x9 normal matrix summed in fp64
+ *   in a fixed order (per thread over its strided share of the matches, then a fixed tree), its smallest eigenvector
+ *   (cyclic Jacobi), projected onto the manifold and rescored; kept (refined = 1) when its inlier count is >= the winner's.
+ * recoverPose. E is decomposed into (R1, t), (R2, t), (R1, -t), (R2, -t) (R1 = U W V^T, R2 = U W^T V^T, t = u3). Every
+ *   RANSAC inlier is triangulated under each candidate -- least-squares depths (z1, z2) of z2 x2 = z1 R x1 + t, where
+ *   OpenCV solves the equivalent DLT -- and counted when 0 < z1 < distance_thresh and 0 < z2 < distance_thresh. The
+ *   candidate with the most points wins (recoverPose's order of preference on ties); n_pose_inliers is that count (its
+ *   return value), the mask is the RANSAC mask AND that candidate's cheirality mask.
+ * Validity. valid = 0 when a pair has fewer than 8 matches or no valid hypothesis: R = I, t = 0, E = 0, counts 0,
+ *   best_hypothesis = -1, mask all zeros. No field is ever NaN or Inf. Acceptance thresholds stay with the caller (e.g.
+ *   n_pose_inliers > 10, euroc_eval.cpp:191).
+ * Determinism. No float atomics; every result is bitwise reproducible run to run and independent of the batch split. */
+typedef struct aria_pose_s* aria_pose_t;
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_pose_config)                                                    */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle creates and owns one. An owned stream is
+                                * non-blocking: it is NOT ordered against the legacy default stream (where torch works
+                                * by default), so a caller that fills inputs there must synchronise first or pass its
+                                * own stream                                                                        */
+    int      hypotheses;       /* per pair: multiple of 64, 64..16384 (default 1024)                            */
+    double   fx, fy, cx, cy;   /* intrinsics (default EuRoC cam0, src/legacy/EuRoCReader.cpp:11-17)              */
+    double   threshold_px;     /* findEssentialMat's threshold in pixels (default 1.0)                           */
+    double   distance_thresh;  /* recoverPose's depth bound (default 50, OpenCV's)                               */
+    uint64_t seed;             /* sample hash seed (default 0)                                                   */
+} aria_pose_config;
+typedef struct {
+    double R[9], t[3], E[9];
+    int    n_matches, n_inliers, n_pose_inliers, best_hypothesis, refined, valid;
+} aria_pose_result;
+
+void  aria_pose_default_config(aria_pose_config* cfg);
+int   aria_pose_create(const aria_pose_config* cfg, aria_pose_t* out);
+void  aria_pose_destroy(aria_pose_t h);
+void* aria_pose_stream(aria_pose_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check:
+ * ARIA_E_INVALID when some pair's counts (n_matches outside [0, match_cap], a keypoint count outside [0, kp_stride]) or
+ * match indices were out of range. Such a pair is detected before any keypoint is read and skipped (valid = 0,
+ * n_matches = 0, zero mask); the other pairs are unaffected. */
+int   aria_pose_check(aria_pose_t h);
+/* One pair, host buffers; blocks. pair_base is the pair id the sample hash uses (the batch call's pair_base + p gives
+ * the same result). mask (optional): n_matches bytes, 1 = RANSAC inlier in front of both cameras. Out-of-range match
+ * indices: ARIA_E_INVALID. */
+int   aria_pose_estimate(aria_pose_t h, const aria_keypoint* kp_query, int nq, const aria_keypoint* kp_train, int nt,
+                         const aria_match* matches, int n_matches, int query_is_first, int pair_base, aria_pose_result* out,
+                         uint8_t* mask);
+/* Device-resident batch form over what aria_orb_extract_batch_device and aria_matcher_match_batch_device leave in HBM.
+ * Pair p reads keypoints at d_kp_query + p*kp_stride (d_nq[p] of them) and d_kp_train + p*kp_stride (d_nt[p]), matches at
+ * d_matches + p*match_cap (d_nmatches[p] of them); writes d_out[p] and, if d_mask is not NULL, match_cap bytes at
+ * d_mask + p*match_cap (zero beyond the pair's matches). The sample hash sees pair id pair_base + p. Consecutive frames
+ * of one batch (pair p: query f = p + 1, train f = p, as in the dynamic-filter example above) are
+ *   aria_pose_estimate_batch_device(h, kps + kp_cap, cnt + 1, kps, cnt, kp_cap, matches, nmatches, B - 1, match_cap,
+ *                                   0, pair_base, out, mask);      // view 1 = train = previous frame
+ * Enqueued on the handle's stream; no synchronisation (the first call with a larger batch grows the workspace, which waits
+ * for the stream). Errors in the data are deferred to aria_pose_check. */
+int   aria_pose_estimate_batch_device(aria_pose_t h, const aria_keypoint* d_kp_query, const int* d_nq,
+                                      const aria_keypoint* d_kp_train, const int* d_nt, int64_t kp_stride,
+                                      const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
+                                      int query_is_first, int pair_base, aria_pose_result* d_out, uint8_t* d_mask);
+/* Test hook: for one pair (host buffers), every hypothesis's 8 sample indices (sample_idx[h*8 + j]; -1 when n < 8),
+ * E (E[h*9 + k], fp32 as scored; zero when invalid) and inlier count (counts[h], -1 when invalid). Blocks. */
+int   aria_pose_debug_hypotheses(aria_pose_t h, const aria_keypoint* kp_query, int nq, const aria_keypoint* kp_train, int nt,
+                                 const aria_match* matches, int n_matches, int query_is_first, int pair_base, int* sample_idx,
+                                 float* E, int* counts);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);

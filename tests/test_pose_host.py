@@ -1,0 +1,179 @@
+"""Two-view relative pose (include/aria_orb_hip.h, "two-view relative pose"): the parts that need no GPU -- exports, the NumPy
+restatement (aria_slam_amd/pose_ref.py) against ground truth, the sample hash, the kernels' listing and the C++ adapter build."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import isa_kernel_stats as S   # noqa: E402
+
+POSE_SYMBOLS = ["aria_pose_default_config", "aria_pose_create", "aria_pose_destroy", "aria_pose_stream", "aria_pose_check",
+                "aria_pose_estimate", "aria_pose_estimate_batch_device", "aria_pose_debug_hypotheses"]
+
+
+def test_pose_symbols_exported_and_listed(aria):
+    from aria_slam_amd import _lib
+    L = aria.load_library()
+    header = open(os.path.join(ROOT, "include", "aria_orb_hip.h")).read()
+    for name in POSE_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % name, header), "%s not declared in the header" % name
+        assert hasattr(L, name), "libaria_orb_hip.so does not export %s" % name
+        assert name in _lib.EXPORTS, "%s missing from _lib.EXPORTS" % name
+    assert aria.abi_version() == 4
+
+
+def test_pose_record_layouts(aria):
+    import ctypes as C
+    from aria_slam_amd import _lib
+    assert _lib.POSE_RESULT_DTYPE.itemsize == 192          # double R[9], t[3], E[9] + 6 ints
+    assert C.sizeof(_lib.PoseConfig) == 80
+    cfg = _lib.PoseConfig()
+    aria.load_library().aria_pose_default_config(C.byref(cfg))
+    assert cfg.struct_size == 80 and cfg.hypotheses == 1024 and cfg.threshold_px == 1.0 and cfg.distance_thresh == 50.0
+    assert (cfg.fx, cfg.fy, cfg.cx, cfg.cy) == (458.654, 457.296, 367.215, 248.375)
+
+
+def _splitmix64(x):
+    m = (1 << 64) - 1
+    x = (x + 0x9E3779B97F4A7C15) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
+
+
+def _samples_int(seed, pair, h, n):
+    """The header's definition in plain Python integers."""
+    key = _splitmix64(_splitmix64(_splitmix64(seed) ^ pair) ^ h)
+    out = []
+    for j in range(8):
+        for retry in range(256):
+            v = ((_splitmix64(key ^ (8 * retry + j)) >> 32) * n) >> 32
+            if v not in out:
+                out.append(v)
+                break
+    return out
+
+
+KNOWN = [((0, 0, 100), [[12, 16, 31, 41, 22, 92, 46, 82], [85, 13, 10, 61, 71, 49, 50, 97], [89, 83, 36, 47, 95, 31, 5, 82]]),
+         ((1, 7, 600), [[26, 524, 195, 103, 263, 434, 594, 589], [591, 116, 122, 589, 194, 234, 343, 16],
+                        [147, 481, 569, 574, 319, 571, 282, 437]]),
+         ((12345, 4095, 8), [[0, 3, 2, 1, 7, 4, 5, 6], [4, 5, 2, 3, 1, 0, 7, 6], [6, 3, 0, 2, 7, 4, 1, 5]])]
+
+
+@pytest.mark.parametrize("args,want", KNOWN)
+def test_sample_hash_known_answers(args, want):
+    from aria_slam_amd import pose_ref as P
+    seed, pair, n = args
+    assert [_samples_int(seed, pair, h, n) for h in range(3)] == want
+    assert P.sample_indices(seed, pair, 3, n).tolist() == want
+    assert (P.sample_indices(seed, pair, 64, 7) == -1).all()          # n < 8: no sample
+
+
+MOTIONS = {
+    "forward": (np.eye(3), [0.0, 0.0, 1.0]),
+    "sideways": (np.eye(3), [1.0, 0.0, 0.0]),
+    "diagonal_rot5": ("rot5", [1.0, 0.3, 1.0]),
+    "yaw15": ("yaw15", [0.5, 0.0, 1.0]),
+}
+
+
+def motion(name):
+    from aria_slam_amd import pose_ref as P
+    R, t = MOTIONS[name]
+    if isinstance(R, str):
+        R = P.rot([0.3, 1.0, 0.2], 5.0) if R == "rot5" else P.rot([0.0, 1.0, 0.0], 15.0)
+    t = np.asarray(t, np.float64)
+    return R, t / np.linalg.norm(t)
+
+
+@pytest.mark.parametrize("name", sorted(MOTIONS))
+@pytest.mark.parametrize("outliers", [0.0, 0.2])
+def test_pose_ref_recovers_ground_truth(name, outliers):
+    """Points at 2-20 m, sigma = 0.5 px, unit baseline (so every point lies within recoverPose's distance bound of 50)."""
+    from aria_slam_amd import pose_ref as P
+    R, t = motion(name)
+    kq, kt, m, truth = P.synth_two_view(11, 200, R, t, outliers)
+    r = P.estimate(kq, kt, m)
+    assert r["valid"] == 1
+    assert P.rotation_error_deg(r["R"], R) < 0.5
+    assert P.angle_deg(r["t"], t) < 3.0
+    sel = r["mask"] == 1
+    assert truth[sel].mean() >= 0.95 and sel[truth].mean() >= 0.8, (truth[sel].mean(), sel[truth].mean())
+    assert abs(np.linalg.norm(r["t"]) - 1.0) < 1e-9 and abs(np.linalg.det(r["R"]) - 1.0) < 1e-9
+    assert r["n_pose_inliers"] == int(r["mask"].sum()) <= r["n_inliers"]
+
+
+def test_pose_ref_minimal_solver_satisfies_its_sample():
+    from aria_slam_amd import pose_ref as P
+    R, t = motion("yaw15")
+    kq, kt, m, _ = P.synth_two_view(3, 100, R, t, 0.0, noise_px=0.0)
+    pts = P.normalise(kq, kt, m)
+    idx, E, counts = P.hypotheses(pts, n_hyp=64)
+    ok = counts >= 0
+    assert ok.sum() >= 60            # a near-degenerate sample may fall under the pivot tolerance
+    # noise-free points: every minimal solution is the true E (up to sign) and takes every point
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    Eg = (tx @ R).ravel()
+    Eg /= np.linalg.norm(Eg)
+    assert np.allclose(np.abs(E[ok] @ Eg), 1.0, atol=1e-6)
+    assert (counts[ok] == 100).all()
+
+
+def test_pose_ref_edges():
+    from aria_slam_amd import pose_ref as P
+    R, t = motion("forward")
+    kq, kt, m, _ = P.synth_two_view(5, 20, R, t)
+    for n in (0, 7):
+        r = P.estimate(kq, kt, m[:n])
+        assert r["valid"] == 0 and not r["mask"].any() and np.array_equal(r["R"], np.eye(3)) and not r["t"].any()
+    one = m.copy()
+    one["query_idx"] = 0
+    one["train_idx"] = 0
+    r = P.estimate(kq, kt, one)
+    assert r["valid"] == 0 and np.isfinite(r["R"]).all() and np.isfinite(r["t"]).all()
+
+
+def _listing():
+    csrc = os.path.join(ROOT, "aria_slam_amd", "csrc")
+    out = os.path.join(ROOT, "build", "isa")
+    os.makedirs(out, exist_ok=True)
+    path = os.path.join(out, "pose_ransac.s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                           "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + csrc, "--cuda-device-only", "-S", "-w", "-o", path, os.path.join(csrc, "pose_ransac.hip")])
+    return open(path).read()
+
+
+def test_pose_kernels_cross_compile_and_scoring_has_no_scratch():
+    text = _listing()
+    for k in ("k_pose_stage", "k_pose_hyp", "k_pose_score", "k_pose_finish"):
+        body, meta = S.kernel_body(text, k)
+        assert len(body) > 50, k
+    body, meta = S.kernel_body(text, "k_pose_score")
+    assert meta.get("ScratchSize", -1) == 0, meta
+    in_loop, outside = S.scratch_accesses(text, "k_pose_score")
+    assert not in_loop and not outside
+    assert meta.get("LDSByteSize", 0) <= 64 * 1024
+
+
+def test_pose_ransac_is_in_the_product_build_and_reads_no_environment():
+    mk = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "Makefile")).read()
+    src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
+    assert "pose_ransac.hip" in src_line
+    src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "pose_ransac.hip")).read()
+    assert "getenv" not in src
+
+
+def test_host_adapters_build_with_the_pose_estimator(aria):
+    pkg = os.path.join(ROOT, "aria_slam_amd")
+    subprocess.check_call(["make", "-C", os.path.join(pkg, "host"), "-s"])
+    so = os.path.join(pkg, "libaria_hip_adapters.so")
+    syms = subprocess.run(["nm", "-DC", so], capture_output=True, text=True, check=True).stdout
+    assert "aria::adapters::hip::HipPoseEstimator::estimate" in syms
+    assert "aria::adapters::hip::makeGeometricVerifier" in syms
+    assert os.path.exists(os.path.join(pkg, "euroc_frontend"))
