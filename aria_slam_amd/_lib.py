@@ -45,6 +45,11 @@ EXPORTS = [
     # two-view relative pose (essential-matrix RANSAC + recoverPose), additive to ABI 4
     "aria_pose_default_config", "aria_pose_create", "aria_pose_destroy", "aria_pose_stream", "aria_pose_check",
     "aria_pose_estimate", "aria_pose_estimate_batch_device", "aria_pose_debug_hypotheses",
+    # two-view triangulation and point map (Mapper::triangulate + filters), additive to ABI 4
+    "aria_map_default_config", "aria_map_create", "aria_map_destroy", "aria_map_stream", "aria_map_check",
+    "aria_map_triangulate", "aria_map_triangulate_batch_device", "aria_map_points_needed", "aria_map_size",
+    "aria_map_capacity", "aria_map_clear", "aria_map_reserve", "aria_map_read", "aria_map_device_points",
+    "aria_map_filter_outliers", "aria_map_filter_distance",
 ]
 
 
@@ -69,6 +74,18 @@ class PoseConfig(C.Structure):
 POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,)), ("n_matches", "<i4"),
                               ("n_inliers", "<i4"), ("n_pose_inliers", "<i4"), ("best_hypothesis", "<i4"),
                               ("refined", "<i4"), ("valid", "<i4")])
+
+
+class MapConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double),
+                ("min_parallax_deg", C.c_double), ("max_reproj_px", C.c_double), ("capacity", C.c_int64),
+                ("min_pose_inliers", C.c_int), ("reserved", C.c_int)]
+
+
+# aria_map_point (72 bytes)
+MAP_POINT_DTYPE = np.dtype([("id", "<u8"), ("X", "<f8", (3,)), ("quality", "<f8"), ("err", "<f4", (2,)), ("pair", "<i4"),
+                            ("match", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("gray", "u1"), ("pad", "u1", (7,))])
 
 
 class AriaError(RuntimeError):
@@ -204,6 +221,8 @@ def load_library():
     L.aria_matcher_sync.argtypes = [C.c_void_p]
     if hasattr(L, "aria_pose_create"):   # absent from A/B builds of the extractor sources alone (tools/build_ab.sh)
         _bind_pose(L)
+    if hasattr(L, "aria_map_create"):
+        _bind_map(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -226,6 +245,31 @@ def _bind_pose(L):
                                                   C.c_void_p]
     L.aria_pose_debug_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def _bind_map(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    L.aria_map_default_config.restype = None
+    L.aria_map_default_config.argtypes = [p]
+    L.aria_map_create.argtypes = [p, C.POINTER(C.c_void_p)]
+    L.aria_map_destroy.restype = None
+    L.aria_map_destroy.argtypes = [p]
+    L.aria_map_stream.restype = p
+    L.aria_map_stream.argtypes = [p]
+    L.aria_map_check.argtypes = [p]
+    L.aria_map_triangulate.argtypes = [p, p, i, p, i, p, i, i, p, p, p, i, i, i, p, i, p]
+    L.aria_map_triangulate_batch_device.argtypes = [p, p, p, p, p, i64, p, p, i, i, i, i, p, p, p, p, i64, i, i, i, p]
+    L.aria_map_points_needed.argtypes = [p, C.POINTER(C.c_int64)]
+    L.aria_map_size.argtypes = [p, C.POINTER(C.c_int64)]
+    L.aria_map_capacity.restype = i64
+    L.aria_map_capacity.argtypes = [p]
+    L.aria_map_clear.argtypes = [p]
+    L.aria_map_reserve.argtypes = [p, i64]
+    L.aria_map_read.argtypes = [p, i64, i64, p]
+    L.aria_map_device_points.restype = p
+    L.aria_map_device_points.argtypes = [p]
+    L.aria_map_filter_outliers.argtypes = [p]
+    L.aria_map_filter_distance.argtypes = [p, C.c_double]
 
 
 def status_string(status):

@@ -10,6 +10,7 @@
 #ifdef ARIA_HIP_USE_REFERENCE_HEADERS
 #include "interfaces/IFeatureExtractor.hpp"
 #include "interfaces/ILoopDetector.hpp"
+#include "interfaces/IMapper.hpp"
 #include "interfaces/IMatcher.hpp"
 #else
 
@@ -17,6 +18,8 @@
 #include <cstdint>
 #include <memory>
 #include <optional>
+#include <string>
+#include <utility>
 #include <vector>
 
 namespace aria::core {
@@ -67,6 +70,56 @@ struct LoopCandidate {
     alignas(16) double relative_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 };
 
+// Minimal stand-ins for the three Eigen types the mapper port uses (Vector3d, Matrix3d, Matrix4d): element access only
+template <int R, int C>
+struct Matrix {
+    double d[R * C] = {};
+    double& operator()(int r, int c) { return d[r * C + c]; }
+    double operator()(int r, int c) const { return d[r * C + c]; }
+    double& operator()(int i) { return d[i]; }
+    double operator()(int i) const { return d[i]; }
+    static Matrix Identity() {
+        Matrix m;
+        for (int i = 0; i < (R < C ? R : C); i++) m(i, i) = 1.0;
+        return m;
+    }
+};
+using Vector3 = Matrix<3, 1>;
+using Matrix3 = Matrix<3, 3>;
+using Matrix4 = Matrix<4, 4>;
+
+struct Quaternion {
+    double w = 1, x = 0, y = 0, z = 0;
+};
+
+// include/core/Types.hpp:48-66 (descriptor, observations, num_observations: what the mapper fills)
+struct MapPoint {
+    std::uint64_t id = 0;
+    Vector3 position;
+    Vector3 normal;
+    std::vector<std::uint8_t> descriptor;
+    std::vector<std::pair<std::uint64_t, int>> observations;   // keyframe id -> keypoint index
+    int num_observations = 0;
+    float min_distance = 0.0f, max_distance = 0.0f;
+    bool is_bad = false;
+};
+
+// include/core/Types.hpp:69-88: position + orientation; toMatrix() = [R(q) t; 0 1]
+struct Pose {
+    Vector3 position;
+    Quaternion orientation;
+    double timestamp = 0.0;
+    Matrix4 toMatrix() const {
+        const double w = orientation.w, x = orientation.x, y = orientation.y, z = orientation.z;
+        Matrix4 T = Matrix4::Identity();
+        T(0, 0) = 1 - 2 * (y * y + z * z); T(0, 1) = 2 * (x * y - z * w); T(0, 2) = 2 * (x * z + y * w);
+        T(1, 0) = 2 * (x * y + z * w); T(1, 1) = 1 - 2 * (x * x + z * z); T(1, 2) = 2 * (y * z - x * w);
+        T(2, 0) = 2 * (x * z - y * w); T(2, 1) = 2 * (y * z + x * w); T(2, 2) = 1 - 2 * (x * x + y * y);
+        for (int r = 0; r < 3; r++) T(r, 3) = position(r);
+        return T;
+    }
+};
+
 }  // namespace aria::core
 
 namespace aria::interfaces {
@@ -109,6 +162,21 @@ public:
     virtual void setMinMatches(int n) = 0;
 };
 using LoopDetectorPtr = std::unique_ptr<ILoopDetector>;
+
+// include/interfaces/IMapper.hpp:11-45
+class IMapper {
+public:
+    virtual ~IMapper() = default;
+    virtual void triangulate(const core::Frame& frame1, const core::Frame& frame2, const core::Pose& pose1, const core::Pose& pose2,
+                             const std::vector<core::Match>& matches, const core::Matrix3& K,
+                             std::vector<core::MapPoint>& new_points) = 0;
+    virtual const std::vector<core::MapPoint>& getMapPoints() const = 0;
+    virtual void exportPLY(const std::string& filename) const = 0;
+    virtual void exportPCD(const std::string& filename) const = 0;
+    virtual void clear() = 0;
+    virtual std::size_t size() const = 0;
+};
+using MapperPtr = std::unique_ptr<IMapper>;
 
 }  // namespace aria::interfaces
 

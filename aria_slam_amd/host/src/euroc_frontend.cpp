@@ -1,5 +1,5 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--devices N] [--shards K]
-//                [--batch B] [--decode-threads T] [--pose FILE]
+//                [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -25,6 +25,11 @@
 // current by essential-matrix RANSAC + recoverPose on the device (FrontEndConfig::estimate_pose, EuRoC cam0 intrinsics);
 // current_pose = current_pose * [R t] when n_pose_inliers > 10 (:191-206). FILE gets one TUM line per frame,
 // "timestamp tx ty tz qx qy qz qw" of current_pose. Without the flag nothing of this runs and the output is unchanged.
+// --map FILE.ply (needs --pose): the mapping step of euroc_eval.cpp:218-222, 291, 326 -- after every accepted pose update
+// the previous -> current pair is triangulated on the device (aria_hip/HipMapper.hpp) with the previous and the updated
+// current_pose as world-to-camera extrinsics and the previous image for colour; at the end filterOutliers, then the PLY
+// export, and "map N points -> FILE" is printed. The composition current_pose * delta is the reference's and is not
+// geometrically consistent after the first pair; the batch form with pose records is.
 //
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
@@ -49,6 +54,7 @@
 #include "aria_hip/FrontEnd.hpp"
 #include "aria_hip/HipFactory.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
+#include "aria_hip/HipMapper.hpp"
 #include "aria_hip/Shard.hpp"
 #include "aria_orb_hip.h"
 
@@ -80,12 +86,12 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply]\n", argv[0]);
         return -1;                                                        // euroc_eval.cpp:64-70
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
-    std::string csv, pose_file;
+    std::string csv, pose_file, map_file;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -95,12 +101,17 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--decode-threads") && i + 1 < argc) decode_threads = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--pose") && i + 1 < argc) pose_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
     if (shards < 1) shards = devices;
     if (batch < 0) batch = 0;
     if (decode_threads < 1) decode_threads = 1;
+    if (!map_file.empty() && pose_file.empty()) {
+        std::fprintf(stderr, "--map needs --pose (it triangulates along the estimated trajectory)\n");
+        return -1;
+    }
     if (!pose_file.empty() && (batch > 0 || devices > 1 || shards > 1)) {
         std::fprintf(stderr, "--pose runs on the frame-at-a-time path only (no --batch, --devices, --shards)\n");
         return -1;
@@ -135,6 +146,7 @@ int main(int argc, char** argv) {
     // --pose: current_pose per frame (4x4 row-major), chained as euroc_eval.cpp:202-206 does
     std::vector<std::array<double, 16>> traj(pose_file.empty() ? 0 : N);
     long long n_pose_updates = 0;
+    std::size_t map_points = 0;
     const auto t0 = std::chrono::steady_clock::now();
 
     // one shard = one FrontEnd (its own extractor + matcher handles on its device) over frames [first, hi)
@@ -174,6 +186,14 @@ int main(int argc, char** argv) {
             int fw = 0, fh = 0;
             auto t_last = std::chrono::steady_clock::now();
             std::array<double, 16> current_pose = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            std::unique_ptr<adapters::hip::HipMapper> mapper;           // --map
+            std::vector<std::uint8_t> prev_gray;
+            int pw = 0, ph = 0;
+            if (!map_file.empty()) {
+                adapters::hip::MapperConfig mc;
+                mc.device = fc.hip_device;
+                mapper = std::make_unique<adapters::hip::HipMapper>(mc);
+            }
             for (std::size_t i = sp.first; i < sp.hi; i++) {
                 seq.read(i, gray, fw, fh);
                 const pipeline::FrontEndResult& r = fe->processFrame(gray.data(), fw, fh, seq.at(i).timestamp);
@@ -188,9 +208,13 @@ int main(int argc, char** argv) {
                                 current_pose[(size_t)(a * 4 + b)] = v;     // current_pose = current_pose * delta (:206)
                             }
                         n_pose_updates++;
+                        if (mapper && r.previous)                          // euroc_eval.cpp:218-222: view 1 = previous frame
+                            mapper->triangulateExtrinsics(*r.previous, *r.frame, r.matches, c.data(), current_pose.data(),
+                                                          prev_gray.data(), pw, ph, fc.frontend.legacy_order);
                     }
                     traj[i] = current_pose;
                 }
+                if (mapper) { prev_gray.swap(gray); pw = fw; ph = fh; }
                 FrameRecord& o = rec[i];
                 o.keypoints = r.frame->numKeypoints();
                 o.matches = r.matches.size();
@@ -206,6 +230,11 @@ int main(int argc, char** argv) {
                     t_last = now;
                     std::printf("Frame %zu/%zu | FPS: %.1f | keypoints: %zu | matches: %zu\n", d, N, fps, o.keypoints, o.matches);
                 }
+            }
+            if (mapper) {                                                  // euroc_eval.cpp:291, 326
+                mapper->filterOutliers();
+                mapper->exportPLY(map_file);
+                map_points = mapper->size();
             }
         } catch (const std::exception& e) {
             errors[(size_t)s] = e.what();
@@ -299,5 +328,6 @@ int main(int argc, char** argv) {
         }
         std::printf("pose updates %lld of %zu frames -> %s\n", n_pose_updates, N > 0 ? N - 1 : 0, pose_file.c_str());
     }
+    if (!map_file.empty()) std::printf("map %zu points -> %s\n", map_points, map_file.c_str());
     return 0;
 }

@@ -458,6 +458,113 @@ int   aria_pose_debug_hypotheses(aria_pose_t h, const aria_keypoint* kp_query, i
                                  const aria_match* matches, int n_matches, int query_is_first, int pair_base, int* sample_idx,
                                  float* E, int* counts);
 
+/* ---- two-view triangulation and point map: the reference's Mapper::triangulate (src/legacy/Mapper.cpp:7-120, thresholds
+ * include/legacy/Mapper.hpp:67-70), the step euroc_eval.cpp:218-222 takes after every accepted pose, with filterOutliers
+ * (:126-158) and filterByDistance (:160-168), on the device and batched over pairs into a map that stays in HBM. Additive
+ * to ABI 4.
+ *
+ * Points and poses. For match m, x1 / x2 are the view-1 / view-2 keypoint pixels (fp32 as stored, used in fp64); view 1 is
+ *   the query side when query_is_first = 1 (as in the pose stage). Each view has world-to-camera extrinsics [R_i | t_i]
+ *   (3x4 row-major fp64, x_cam = R X + t -- how Mapper::triangulate uses its Matrix4d arguments); P_i = K [R_i | t_i]
+ *   with rows (fx r0 + cx r2, fy r1 + cy r2, r2) of [R_i | t_i].
+ * DLT (cv::triangulatePoints). A is the 4x4 with rows x1 P1[2] - P1[0], y1 P1[2] - P1[1], x2 P2[2] - P2[0],
+ *   y2 P2[2] - P2[1]; X is the right singular vector of its smallest singular value, by a one-sided (Hestenes) Jacobi SVD
+ *   in fp64: columns a_0..a_3 of A, V = I; one sweep visits the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) in that order;
+ *   with alpha = |a_i|^2, beta = |a_j|^2, gamma = a_i.a_j a pair is skipped when |gamma| <= 10 DBL_EPSILON sqrt(alpha beta),
+ *   else zeta = (beta - alpha) / (2 gamma), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (sign(0) = +1),
+ *   c = 1 / sqrt(1 + t^2), s = c t, and (a_i, a_j) <- (c a_i - s a_j, s a_i + c a_j), the same on V's columns. Sweeps stop
+ *   after the first one that rotates no pair, or after 30. X = the column of V whose rotated a_k has the least |a_k|^2
+ *   (ties: lowest k); it has unit norm up to rounding. The point is rejected when |X[3]| < 1e-10, else dehomogenised.
+ * Tests, in the reference's order, in fp64; a NaN fails every test:
+ *   depth       keep when min_depth <= z_cam_i <= max_depth in both views;
+ *   parallax    C_i = -R_i^T t_i, ray_i = (X - C_i) / |X - C_i|, parallax = acos(min(1, |ray1.ray2|)) * 180 / pi;
+ *               rejected when below min_parallax_deg;
+ *   reprojection err_i = sqrt((fx Xc / Zc + cx - u)^2 + (fy Yc / Zc + cy - v)^2) per view; rejected when either exceeds
+ *               max_reproj_px.
+ *   A pair with fewer than 8 matches adds nothing (Mapper.cpp:13, on the pair's match count before any mask).
+ * Colour and quality. gray = the view-1 image byte at (clamp((int)x1, 0, W-1), clamp((int)y1, 0, H-1)); 127 without an
+ *   image (the reference's default colour 0.5 as its export writes it, (int)(0.5 * 255)). quality = 1 / (err1 + err2 + 0.1).
+ * Candidates. Every match, or those with a nonzero byte in the optional per-match mask (e.g. the pose stage's).
+ * Map. Kept points are appended in pair order, then match order; id is a map-wide sequence number (next_id_++) that
+ *   clear() resets. An append whose points do not all fit the capacity appends whole pairs in order while they fit and
+ *   drops the rest (deferred ARIA_E_OUTPUT_TOO_SMALL; aria_map_points_needed tells what to reserve).
+ * Filters (both compact stably and keep ids).
+ *   filter_outliers: nothing below 10 points (Mapper.cpp:136); else mean = sum p / n, sd = sqrt(sum |p - mean|^2 / n),
+ *     each sum in fp64 over blocks of 1024 consecutive points (per thread in order, then a fixed tree) added in block
+ *     order; points with |p - mean| > 3 sd are removed.
+ *   filter_distance(d): points with |p| > d are removed.
+ * Determinism. No float atomics; the map after a sequence of calls is bitwise reproducible run to run and independent of
+ *   how the same pairs were split into batch calls.
+ * Known reference defect, not reproduced: Mapper.cpp:52-58 reads cv::triangulatePoints' output with at<double> where
+ *   OpenCV 4.9 creates it with the (float) type of the input points; the stage computes what that code intends. */
+typedef struct aria_map_s* aria_map_t;
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_map_config)                                                     */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking, as in
+                                * aria_pose_config)                                                               */
+    double   fx, fy, cx, cy;   /* intrinsics (default EuRoC cam0)                                                */
+    double   min_depth;        /* default 0.1; depth units are those of the extrinsics (baseline units with pose
+                                * records, |t| = 1)                                                               */
+    double   max_depth;        /* default 50                                                                     */
+    double   min_parallax_deg; /* default 1.0                                                                    */
+    double   max_reproj_px;    /* default 2.0                                                                    */
+    int64_t  capacity;         /* initial arena capacity in points (default 65536)                               */
+    int      min_pose_inliers; /* pose-record gate of the batch form: n_pose_inliers <= this adds nothing (default 10) */
+    int      reserved;
+} aria_map_config;
+typedef struct {
+    uint64_t id;               /* map-wide sequence number                                                       */
+    double   X[3];             /* world point                                                                    */
+    double   quality;          /* 1 / (err1 + err2 + 0.1)                                                        */
+    float    err[2];           /* reprojection errors in views 1, 2 (px)                                         */
+    int      pair, match;      /* pair id, index in the pair's match list                                        */
+    int      idx1, idx2;       /* view-1 / view-2 keypoint index                                                 */
+    uint8_t  gray;             /* view-1 image byte, 127 without an image                                        */
+    uint8_t  pad[7];
+} aria_map_point;              /* 72 bytes                                                                       */
+
+void  aria_map_default_config(aria_map_config* cfg);
+int   aria_map_create(const aria_map_config* cfg, aria_map_t* out);
+void  aria_map_destroy(aria_map_t h);
+void* aria_map_stream(aria_map_t h);
+/* Synchronises the handle's stream and returns the deferred error of the calls since the last check, once:
+ * ARIA_E_INVALID when some pair's counts or match indices were out of range (that pair was skipped before any keypoint
+ * was read, the others are unaffected), else ARIA_E_OUTPUT_TOO_SMALL when an append was cut at the capacity. */
+int   aria_map_check(aria_map_t h);
+/* One pair from host buffers; blocks, appends, and grows the arena itself when needed. pose1 / pose2: 12 doubles each,
+ * [R | t] row-major. image1 (optional): view 1's gray image, W x H bytes with `pitch` bytes per row. mask (optional):
+ * n_matches bytes, nonzero = candidate. *n_added = points appended. Out-of-range match indices: ARIA_E_INVALID. */
+int   aria_map_triangulate(aria_map_t h, const aria_keypoint* kp_query, int nq, const aria_keypoint* kp_train, int nt,
+                           const aria_match* matches, int n_matches, int query_is_first, const double* pose1,
+                           const double* pose2, const uint8_t* image1, int width, int height, int pitch, const uint8_t* mask,
+                           int pair_id, int* n_added);
+/* Device-resident batch form over what the batch extract, match and pose calls leave in HBM, with the pointer and stride
+ * conventions of aria_pose_estimate_batch_device: pair p reads keypoints at d_kp_query + p*kp_stride (d_nq[p] of them)
+ * and d_kp_train + p*kp_stride (d_nt[p]), matches at d_matches + p*match_cap (d_nmatches[p]); its points carry pair id
+ * pair_base + p. Poses: d_extrinsics (24 doubles per pair: [R1|t1], [R2|t2]) or, when that is NULL, d_pose records used as
+ * [I|0], [R|t]; a record with valid == 0 or n_pose_inliers <= min_pose_inliers adds nothing. Optional: d_mask (match_cap
+ * bytes per pair), view-1 images at d_img + p*img_stride (W x H, `pitch` bytes per row), d_added[p] = points appended
+ * (0 for a pair dropped at the capacity). Enqueued on the handle's stream; no synchronisation (the first call with a larger
+ * batch grows the workspace, which waits for the stream). Errors in the data are deferred to aria_map_check. */
+int   aria_map_triangulate_batch_device(aria_map_t h, const aria_keypoint* d_kp_query, const int* d_nq,
+                                        const aria_keypoint* d_kp_train, const int* d_nt, int64_t kp_stride,
+                                        const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
+                                        int query_is_first, int pair_base, const double* d_extrinsics,
+                                        const aria_pose_result* d_pose, const uint8_t* d_mask, const uint8_t* d_img,
+                                        int64_t img_stride, int width, int height, int pitch, int* d_added);
+/* The largest map size an append since create / the last clear asked for (what to reserve after a cut). Blocks. */
+int   aria_map_points_needed(aria_map_t h, int64_t* needed);
+int   aria_map_size(aria_map_t h, int64_t* size);                  /* blocks */
+int64_t aria_map_capacity(aria_map_t h);
+int   aria_map_clear(aria_map_t h);                                /* size 0, ids restart at 0 */
+int   aria_map_reserve(aria_map_t h, int64_t capacity);            /* grows, keeps the contents; blocks */
+int   aria_map_read(aria_map_t h, int64_t first, int64_t count, aria_map_point* out);   /* blocks */
+/* The arena on the device: aria_map_size points. Valid until the next reserve, grow or filter. */
+const aria_map_point* aria_map_device_points(aria_map_t h);
+int   aria_map_filter_outliers(aria_map_t h);                      /* enqueued */
+int   aria_map_filter_distance(aria_map_t h, double max_distance); /* enqueued */
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
