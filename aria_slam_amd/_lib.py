@@ -50,6 +50,9 @@ EXPORTS = [
     "aria_map_triangulate", "aria_map_triangulate_batch_device", "aria_map_points_needed", "aria_map_size",
     "aria_map_capacity", "aria_map_clear", "aria_map_reserve", "aria_map_read", "aria_map_device_points",
     "aria_map_filter_outliers", "aria_map_filter_distance",
+    # fundamental-matrix RANSAC (findFundamentalMat FM_RANSAC, loop verification), additive to ABI 4
+    "aria_fund_default_config", "aria_fund_create", "aria_fund_destroy", "aria_fund_stream", "aria_fund_check",
+    "aria_fund_estimate", "aria_fund_estimate_batch_device", "aria_fund_debug_hypotheses",
 ]
 
 
@@ -74,6 +77,16 @@ class PoseConfig(C.Structure):
 POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,)), ("n_matches", "<i4"),
                               ("n_inliers", "<i4"), ("n_pose_inliers", "<i4"), ("best_hypothesis", "<i4"),
                               ("refined", "<i4"), ("valid", "<i4")])
+
+
+class FundConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("hypotheses", C.c_int),
+                ("threshold_px", C.c_double), ("seed", C.c_uint64)]
+
+
+# aria_fund_result (96 bytes)
+FUND_RESULT_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<i4"), ("n_inliers", "<i4"), ("n_models", "<i4"),
+                              ("best_hypothesis", "<i4"), ("best_root", "<i4"), ("valid", "<i4")])
 
 
 class MapConfig(C.Structure):
@@ -223,6 +236,8 @@ def load_library():
         _bind_pose(L)
     if hasattr(L, "aria_map_create"):
         _bind_map(L)
+    if hasattr(L, "aria_fund_create"):
+        _bind_fund(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -270,6 +285,21 @@ def _bind_map(L):
     L.aria_map_device_points.argtypes = [p]
     L.aria_map_filter_outliers.argtypes = [p]
     L.aria_map_filter_distance.argtypes = [p, C.c_double]
+
+
+def _bind_fund(L):
+    p, i = C.c_void_p, C.c_int
+    L.aria_fund_default_config.restype = None
+    L.aria_fund_default_config.argtypes = [p]
+    L.aria_fund_create.argtypes = [p, C.POINTER(C.c_void_p)]
+    L.aria_fund_destroy.restype = None
+    L.aria_fund_destroy.argtypes = [p]
+    L.aria_fund_stream.restype = p
+    L.aria_fund_stream.argtypes = [p]
+    L.aria_fund_check.argtypes = [p]
+    L.aria_fund_estimate.argtypes = [p, p, i, p, i, p, i, i, i, p, p]
+    L.aria_fund_estimate_batch_device.argtypes = [p, p, p, p, p, C.c_int64, p, p, i, i, i, i, p, p, p, p]
+    L.aria_fund_debug_hypotheses.argtypes = [p, p, i, p, i, p, i, i, i, p, p, p, p]
 
 
 def status_string(status):

@@ -1,0 +1,174 @@
+"""Fundamental-matrix RANSAC on the device (include/aria_orb_hip.h, "fundamental-matrix RANSAC"): what the reference's
+loop-closure verification computes with cv::findFundamentalMat(pts1, pts2, FM_RANSAC, 3.0, 0.99) (src/legacy/
+LoopClosure.cpp:116-155). aria_slam_amd.fund_ref restates the stage in NumPy.
+
+verify_loop_candidates chains it into the pose stage on the device, as LoopClosureDetector::verifyGeometry +
+computeRelativePose do on the CPU: one F batch over every candidate with the inliers compacted in HBM, then one pose batch
+over those inliers.
+
+As with HipPoseEstimator, the handle's own stream is non-blocking: device buffers filled on torch's default stream must be
+synchronised before estimate_batch_device, or the estimator must be created on the caller's stream."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import FUND_RESULT_DTYPE, KP_DTYPE, MATCH_DTYPE, POSE_RESULT_DTYPE, check
+from .frontend import _ptr
+from .pose import _kps
+
+# computeRelativePose's hard-coded intrinsics (LoopClosure.cpp:171-174): the K of the pose estimator a caller passes to
+# verify_loop_candidates to verify as the reference does
+REFERENCE_LOOP_K = (700.0, 700.0, 320.0, 180.0)
+
+
+def _matches(matches):
+    m = np.ascontiguousarray(matches)
+    if len(m) and m.dtype != MATCH_DTYPE:
+        m = m.view(MATCH_DTYPE)
+    return m
+
+
+def _result_dict(rec, mask=None):
+    r = dict(F=rec["F"].reshape(3, 3).copy())
+    for k in ("n_matches", "n_inliers", "n_models", "best_hypothesis", "best_root", "valid"):
+        r[k] = int(rec[k])
+    r["record"] = rec.tobytes()          # the raw aria_fund_result (96 bytes)
+    if mask is not None:
+        r["mask"] = mask
+    return r
+
+
+class HipFundamentalEstimator:
+    """Binding of aria_fund_t; defaults are findFundamentalMat's as the reference calls it (threshold 3 px)."""
+
+    def __init__(self, hypotheses=1024, threshold_px=3.0, seed=0, stream=None, device=0):
+        self._L = _lib.load_library()
+        cfg = _lib.FundConfig()
+        self._L.aria_fund_default_config(C.byref(cfg))
+        cfg.device = device
+        cfg.stream = stream
+        cfg.hypotheses = hypotheses
+        cfg.threshold_px = threshold_px
+        cfg.seed = seed
+        self.config = cfg
+        h = C.c_void_p()
+        check(self._L.aria_fund_create(C.byref(cfg), C.byref(h)), "aria_fund_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.aria_fund_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def estimate(self, kp1, kp2, matches, query_is_first=True, pair_base=0):
+        """One pair, host arrays (kp1 = query keypoints, kp2 = train keypoints, MATCH_DTYPE matches). Returns a dict of the
+        aria_fund_result fields (F 3x3, counts, valid) and `mask` (uint8 per match, 1 = inlier of F)."""
+        kq, kt, m = _kps(kp1), _kps(kp2), _matches(matches)
+        rec = np.zeros(1, FUND_RESULT_DTYPE)
+        mask = np.zeros(max(len(m), 1), np.uint8)
+        check(self._L.aria_fund_estimate(self._h, kq.ctypes.data if len(kq) else None, len(kq),
+                                         kt.ctypes.data if len(kt) else None, len(kt), m.ctypes.data if len(m) else None,
+                                         len(m), 1 if query_is_first else 0, pair_base, rec.ctypes.data, mask.ctypes.data),
+              "aria_fund_estimate")
+        return _result_dict(rec[0], mask[:len(m)])
+
+    def estimate_batch_device(self, d_kp_query, d_nq, d_kp_train, d_nt, kp_stride, d_matches, d_nmatches, n_pairs, match_cap,
+                              d_out, d_mask=None, d_inliers=None, d_ninliers=None, query_is_first=True, pair_base=0):
+        """aria_fund_estimate_batch_device: device pointers (torch tensors or ints); d_out holds n_pairs * 96 bytes
+        (FUND_RESULT_DTYPE records); d_inliers / d_ninliers (both or neither) receive the compacted F inliers, the match
+        input of HipPoseEstimator.estimate_batch_device. Enqueued on the handle's stream; check() synchronises."""
+        check(self._L.aria_fund_estimate_batch_device(self._h, _ptr(d_kp_query), _ptr(d_nq), _ptr(d_kp_train), _ptr(d_nt),
+                                                      kp_stride, _ptr(d_matches), _ptr(d_nmatches), n_pairs, match_cap,
+                                                      1 if query_is_first else 0, pair_base, _ptr(d_out), _ptr(d_mask),
+                                                      _ptr(d_inliers), _ptr(d_ninliers)),
+              "aria_fund_estimate_batch_device")
+
+    def debug_hypotheses(self, kp1, kp2, matches, query_is_first=True, pair_base=0):
+        """(sample_idx (H, 7) int32, n_models (H,) int32, F (H, 3, 9) float64, counts (H, 3) int32) of one pair."""
+        kq, kt, m = _kps(kp1), _kps(kp2), _matches(matches)
+        H = self.config.hypotheses
+        idx = np.zeros((H, 7), np.int32)
+        nm = np.zeros(H, np.int32)
+        F = np.zeros((H, 3, 9), np.float64)
+        cnt = np.zeros((H, 3), np.int32)
+        check(self._L.aria_fund_debug_hypotheses(self._h, kq.ctypes.data if len(kq) else None, len(kq),
+                                                 kt.ctypes.data if len(kt) else None, len(kt),
+                                                 m.ctypes.data if len(m) else None, len(m), 1 if query_is_first else 0,
+                                                 pair_base, idx.ctypes.data, nm.ctypes.data, F.ctypes.data, cnt.ctypes.data),
+              "aria_fund_debug_hypotheses")
+        return idx, nm, F, cnt
+
+    def check(self):
+        """Synchronise; raise on a deferred error of the batch calls (out-of-range counts or match indices)."""
+        check(self._L.aria_fund_check(self._h), "aria_fund_check")
+
+    def status(self):
+        """aria_fund_check's status code, without raising."""
+        return self._L.aria_fund_check(self._h)
+
+    @property
+    def stream(self):
+        return self._L.aria_fund_stream(self._h)
+
+
+def verify_loop_candidates(fund, pose, candidates, min_matches, pair_base=0):
+    """LoopClosureDetector::verifyGeometry + computeRelativePose (LoopClosure.cpp:116-195) for every candidate of one call,
+    on the device: one F batch with the inliers compacted in HBM, then one pose batch over them. candidates: a list of
+    (kp_query, kp_train, matches) host arrays, view 1 = the query keyframe; pose: a HipPoseEstimator, built with
+    K = REFERENCE_LOOP_K and threshold 1 px to verify as the reference does. Candidate c uses pair id pair_base + c in both
+    stages. Returns per candidate dict(accepted, T (4x4 [R t; 0 1], identity when rejected), matches (the F inliers),
+    fund (aria_fund_result fields), pose (aria_pose_result fields or None))."""
+    import torch
+
+    B = len(candidates)
+    if B == 0:
+        return []
+    kps = [(_kps(a), _kps(b), _matches(m)) for a, b, m in candidates]
+    stride = max(1, max(max(len(a), len(b)) for a, b, _ in kps))
+    cap = max(1, max(len(m) for _a, _b, m in kps))
+    kq = np.zeros((B, stride), KP_DTYPE)
+    kt = np.zeros((B, stride), KP_DTYPE)
+    mm = np.zeros((B, cap), MATCH_DTYPE)
+    nq, nt, nm = (np.zeros(B, np.int32) for _ in range(3))
+    for c, (a, b, m) in enumerate(kps):
+        kq[c, :len(a)], kt[c, :len(b)], mm[c, :len(m)] = a, b, m
+        nq[c], nt[c], nm[c] = len(a), len(b), len(m)
+    dev = torch.device("cuda", fund.config.device)
+    d = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).to(dev)
+    dkq, dkt, dmm, dnq, dnt, dnm = d(kq), d(kt), d(mm), d(nq), d(nt), d(nm)
+    fout = torch.zeros(B * FUND_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    inl = torch.zeros(B * cap * MATCH_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    ninl = torch.zeros(B, dtype=torch.int32, device=dev)
+    pout = torch.zeros(B * POSE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)          # the handles' own streams are not ordered against torch's default stream
+    fund.estimate_batch_device(dkq, dnq, dkt, dnt, stride, dmm, dnm, B, cap, fout, None, inl, ninl, True, pair_base)
+    fund.check()                         # also orders the F results before the pose stage reads them
+    pose.estimate_batch_device(dkq, dnq, dkt, dnt, stride, inl, ninl, B, cap, pout, None, True, pair_base)
+    pose.check()
+    frec = np.frombuffer(fout.cpu().numpy().tobytes(), FUND_RESULT_DTYPE)
+    prec = np.frombuffer(pout.cpu().numpy().tobytes(), POSE_RESULT_DTYPE)
+    inl_h = inl.cpu().numpy().view(MATCH_DTYPE).reshape(B, cap)
+    ninl_h = ninl.cpu().numpy()
+    out = []
+    for c in range(B):
+        f, p = _result_dict(frec[c]), None
+        r = dict(accepted=False, T=np.eye(4), matches=np.zeros(0, MATCH_DTYPE), fund=f, pose=None)
+        ok = nm[c] >= min_matches and f["valid"] and f["n_inliers"] >= min_matches and ninl_h[c] >= 8
+        if ok:
+            p = dict(R=prec[c]["R"].reshape(3, 3).copy(), t=prec[c]["t"].copy(), n_inliers=int(prec[c]["n_inliers"]),
+                     n_pose_inliers=int(prec[c]["n_pose_inliers"]), valid=int(prec[c]["valid"]))
+            r["pose"] = p
+            ok = p["valid"] == 1 and p["n_pose_inliers"] >= min_matches
+        if ok:
+            T = np.eye(4)
+            T[:3, :3], T[:3, 3] = p["R"], p["t"]
+            r.update(accepted=True, T=T, matches=inl_h[c, :ninl_h[c]].copy())
+        out.append(r)
+    return out

@@ -7,11 +7,13 @@
 // database holds min_frames_between keyframes (:34-36); candidates = keyframes at least min_frames_between older than
 // the query (:81) with descriptors (:83), kNN-2 + ratio 0.7 in double (:92), score = good / max(1, |query keypoints|)
 // (:98), kept above 0.1 (:99), best five by score (:105-111); then per candidate: score >= min_score (:42), and a
-// verification step. The reference's verification is geometric (essential-matrix RANSAC in OpenCV, :116-190), which is
+// verification step. The reference's verification is geometric (F-RANSAC, then E-RANSAC + recoverPose in OpenCV, :116-195), which is
 // outside the feature front-end: here a candidate is accepted when its ratio-0.7 match list has at least min_matches
 // entries (the same bound verifyGeometry applies to its inliers), unless the caller installs a verifier (setVerifier),
 // which receives the query keyframe, the matched keyframe's id and the candidate (match list filled) and may reject it or fill in
-// the relative pose.
+// the relative pose. makeReferenceVerifier (aria_hip/HipFundamentalEstimator.hpp) is the reference's verification on the
+// device: F-RANSAC, then E-RANSAC + recoverPose on the F inliers with computeRelativePose's K; makeGeometricVerifier
+// (aria_hip/HipPoseEstimator.hpp) is an E-RANSAC-only variant with the caller's K.
 #pragma once
 #include <functional>
 #include <optional>

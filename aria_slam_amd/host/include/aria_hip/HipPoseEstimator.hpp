@@ -3,9 +3,10 @@
 // every match list (src/euroc_eval.cpp:178-201, src/legacy/LoopClosure.cpp:116-190), as essential-matrix RANSAC on the device.
 //
 // makeGeometricVerifier turns it into a HipLoopDetector::Verifier (opt-in; the detector's default stays the match-count
-// test). Two differences from the reference's LoopClosureDetector: it verifies with E-RANSAC where verifyGeometry used
-// F-RANSAC (cv::findFundamentalMat, LoopClosure.cpp:141-143), and the caller passes K where computeRelativePose hard-codes
-// its own (:171-174).
+// test). Three differences from the reference's LoopClosureDetector: it verifies with E-RANSAC where verifyGeometry used
+// F-RANSAC (cv::findFundamentalMat, LoopClosure.cpp:141-143), the caller passes K where computeRelativePose hard-codes its
+// own (:171-174), and candidate.matches keeps the pose inliers where the reference keeps the F inliers (:58).
+// makeReferenceVerifier (aria_hip/HipFundamentalEstimator.hpp) has none of them: it accepts the reference's loops.
 #pragma once
 #include <array>
 #include <functional>
@@ -98,7 +99,8 @@ std::array<double, 16> poseMatrix(const TwoViewPose& p);
 // LoopClosure.cpp:116-190 over the device: estimate the pose query -> match (view 1 = the query keyframe, whose keypoints
 // candidate.matches index as query_idx); reject when n_pose_inliers < min_inliers (:181-183), else fill
 // candidate.relative_pose ([R t; 0 1]; column-major storage in the stand-in's double[16], as Eigen::Matrix4d stores it) and
-// keep only the pose inliers in candidate.matches. `keyframes` resolves a match id to the
+// keep only the pose inliers in candidate.matches (the reference keeps the F inliers; see makeReferenceVerifier for its
+// exact acceptance). `keyframes` resolves a match id to the
 // keyframe's frame (its keypoints): the detector's database keeps descriptors only, so the caller, who holds the keyframes,
 // supplies them.
 using KeyFrameLookup = std::function<const core::Frame*(std::uint64_t id)>;

@@ -1,5 +1,5 @@
-// euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--devices N] [--shards K]
-//                [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
+// euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
+//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -31,6 +31,12 @@
 // export, and "map N points -> FILE" is printed. The composition current_pose * delta is the reference's and is not
 // geometrically consistent after the first pair; the batch form with pose records is.
 //
+// --loop-verify reference (needs --loop): a loop candidate is accepted as LoopClosureDetector accepts it -- F-RANSAC on its
+// ratio-0.7 list, then E-RANSAC + recoverPose on the F inliers with computeRelativePose's K (aria_hip/
+// HipFundamentalEstimator.hpp, makeReferenceVerifier; LoopClosure.cpp:116-195) -- instead of by the list's length alone.
+// The loop step then runs over the merged stream as in the sharded mode, keeping the keypoints of the keyframes the
+// database holds. Keyframes are the default run's; the loops are a subset of its. Without the flag nothing changes.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -41,6 +47,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <exception>
 #include <fstream>
 #include <iomanip>
@@ -53,6 +60,7 @@
 #include "aria_hip/BatchFrontEnd.hpp"
 #include "aria_hip/FrontEnd.hpp"
 #include "aria_hip/HipFactory.hpp"
+#include "aria_hip/HipFundamentalEstimator.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/Shard.hpp"
@@ -86,12 +94,12 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply]\n", argv[0]);
         return -1;                                                        // euroc_eval.cpp:64-70
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
-    std::string csv, pose_file, map_file;
+    std::string csv, pose_file, map_file, loop_verify;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -102,12 +110,18 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--decode-threads") && i + 1 < argc) decode_threads = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--pose") && i + 1 < argc) pose_file = argv[++i];
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
     if (shards < 1) shards = devices;
     if (batch < 0) batch = 0;
     if (decode_threads < 1) decode_threads = 1;
+    if (!loop_verify.empty() && (loop_verify != "reference" || !loop)) {
+        std::fprintf(stderr, "--loop-verify reference needs --loop (the only verification mode is 'reference')\n");
+        return -1;
+    }
+    const bool verify_reference = !loop_verify.empty();
     if (!map_file.empty() && pose_file.empty()) {
         std::fprintf(stderr, "--map needs --pose (it triangulates along the estimated trajectory)\n");
         return -1;
@@ -141,7 +155,8 @@ int main(int argc, char** argv) {
     std::atomic<std::size_t> done{0};
     int w = 0, h = 0;
     const bool sharded = shards > 1;
-    const bool posthoc_loop = loop && (sharded || batch > 0);      // the loop step over the merged stream, after the shards
+    // the loop step over the merged stream, after the shards (--loop-verify: it needs the keyframes' keypoints)
+    const bool posthoc_loop = loop && (sharded || batch > 0 || verify_reference);
     std::vector<pipeline::BatchStats> bstats((size_t)shards);
     // --pose: current_pose per frame (4x4 row-major), chained as euroc_eval.cpp:202-206 does
     std::vector<std::array<double, 16>> traj(pose_file.empty() ? 0 : N);
@@ -257,6 +272,16 @@ int main(int argc, char** argv) {
         fc.max_features = max_features;
         adapters::hip::HipLoopDetector ld(fc.loop_min_frames_between, fc.loop_min_score, fc.loop_min_matches,
                                           ((max_features + 8 * 64 + 63) / 64) * 64, 500, nullptr, 0);
+        std::unique_ptr<adapters::hip::HipFundamentalEstimator> fund;
+        std::unique_ptr<adapters::hip::HipPoseEstimator> pose;
+        std::deque<std::size_t> held;                                  // keyframes in the database, oldest first
+        if (verify_reference) {
+            fund = std::make_unique<adapters::hip::HipFundamentalEstimator>();
+            pose = std::make_unique<adapters::hip::HipPoseEstimator>(adapters::hip::referenceLoopIntrinsics());
+            ld.setVerifier(adapters::hip::makeReferenceVerifier(*fund, *pose, fc.loop_min_matches, [&](std::uint64_t id) {
+                return id < N && rec[(size_t)id].frame ? rec[(size_t)id].frame.get() : nullptr;
+            }));
+        }
         for (std::size_t i = 1; i < N; i++) {
             FrameRecord& o = rec[i];
             if ((int)o.matches < fc.frontend.keyframe_min_matches || !o.frame) continue;
@@ -268,6 +293,10 @@ int main(int argc, char** argv) {
             auto lp = ld.detect(kf);
             ld.addKeyFrame(kf);
             o.is_keyframe = true;
+            if (verify_reference) {                                    // keep the keypoints of the 500 keyframes held
+                held.push_back(i);
+                if (held.size() > 500) { rec[held.front()].frame.reset(); held.pop_front(); }
+            }
             if (lp) { o.loop_match_id = (long long)lp->match_id; o.loop_score = lp->score; }
         }
     }

@@ -41,15 +41,16 @@ def draw(keys, j, retry, n):
         return (((r >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
 
 
-def sample_indices(seed, pair, hypotheses, n):
-    """(hypotheses, 8) sample indices; a row of -1 for n < 8 or a slot that stayed duplicate after MAX_RETRY draws."""
+def sample_indices(seed, pair, hypotheses, n, k=8):
+    """(hypotheses, k) sample indices (slots j = 0..k-1; the fundamental-matrix stage draws k = 7 with the same formulas);
+    a row of -1 for n < k or a slot that stayed duplicate after MAX_RETRY draws."""
     H = int(hypotheses)
-    out = np.full((H, 8), -1, np.int64)
-    if n < 8:
+    out = np.full((H, k), -1, np.int64)
+    if n < k:
         return out
     keys = hypothesis_keys(seed, pair, np.arange(H, dtype=np.uint64))
     ok = np.ones(H, bool)
-    for j in range(8):
+    for j in range(k):
         todo = np.ones(H, bool)
         for retry in range(MAX_RETRY):
             if not todo.any():

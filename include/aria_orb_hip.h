@@ -565,6 +565,95 @@ const aria_map_point* aria_map_device_points(aria_map_t h);
 int   aria_map_filter_outliers(aria_map_t h);                      /* enqueued */
 int   aria_map_filter_distance(aria_map_t h, double max_distance); /* enqueued */
 
+/* ---- fundamental-matrix RANSAC: cv::findFundamentalMat(pts1, pts2, FM_RANSAC, 3.0, 0.99, mask), the geometric check of
+ * a loop candidate in the reference (src/legacy/LoopClosure.cpp:116-155, verifyGeometry), on the device and batched over
+ * pairs. The F inliers, compacted in match order, are exactly the match input of aria_pose_estimate_batch_device, so a
+ * loop candidate is verified F -> E without a round trip to the host (computeRelativePose, :158-195). Additive to ABI 4.
+ *
+ * Points. As in the pose stage: for match m, view 1 is the query keypoint when query_is_first = 1, the train keypoint when
+ *   0. Coordinates are the stored fp32 pixels. F satisfies x2^T F x1 = 0 in pixel coordinates, row-major, fp64.
+ * Small inputs. A pair with fewer than 15 matches has valid = 0 and costs no work. OpenCV takes other branches there
+ *   (n = 7: the 7-point solver alone, mask all ones; 8..14: LMeDS); they are not restated.
+ * Hypotheses. `hypotheses` per pair (multiple of 64, 64..16384). Sample slots j = 0..6 are drawn with the pose stage's
+ *   hash, formulas unchanged (draw(pair, h, j, r), 256 redraws per slot; a slot still duplicate makes the hypothesis invalid).
+ * Sample check (FMEstimatorCallback::checkSubset). OpenCV's haveCollinearPoints in both views, in fp64 from the fp32
+ *   points: slot 6 against every pair (j, k), k < j < 6, with d1 = p_j - p_6, d2 = p_k - p_6; collinear when
+ *   |d2.x d1.y - d2.y d1.x| <= FLT_EPSILON (|d1.x| + |d1.y| + |d2.x| + |d2.y|). A collinear sample makes the hypothesis
+ *   invalid where OpenCV draws again: the fixed budget shrinks a little on near-degenerate data.
+ * Minimal solver (run7Point, fp64). Each view of the sample is normalised on its own: centroid c, mean distance m from it
+ *   (invalid when m < FLT_EPSILON), u = (x - c) sqrt(2) / m. Rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1] of the
+ *   normalised points; Gaussian elimination over columns 0..6 with partial pivoting (first row of largest |a|); a pivot
+ *   with |pivot| <= 1e-9 * max|A_ij| makes the hypothesis invalid (x1 == x2 for every match has rank 6 and lands here).
+ *   Back substitution gives the null-space basis g1 (f7 = 1, f8 = 0) and g2 (f7 = 0, f8 = 1). With f1 = g1 - g2, f2 = g2
+ *   the cubic det(l f1 + f2) = c0 l^3 + c1 l^2 + c2 l + c3 has run7Point's coefficients; |c0| <= 1e-12 max|c_i| makes the
+ *   hypothesis invalid (our rule). Real roots in closed form -- trigonometric for three (Q^3 - R^2 > 0), Cardano for one --
+ *   sorted ascending as k = 0..2. Per root, as run7Point: s = f1[8] l + f2[8]; if |s| > DBL_EPSILON the model is
+ *   (l f1 + f2) / s with F[8] = 1, else l f1 + f2 with F[8] = 0; F = T2^T F T1 (de-normalised); F /= F[8] when
+ *   |F[8]| > FLT_EPSILON. A hypothesis with a non-finite model entry is invalid. The rank-2 members of the pencil do not
+ *   depend on the basis, so the models equal run7Point's (SVD basis) up to rounding.
+ * Inliers (computeError). With (a, b, c) = F x1, d2 = x2 . (a, b, c) and (a', b', c') = F^T x2, a point is an inlier when
+ *   a^2 + b^2 > 0, a'^2 + b'^2 > 0 and max(d2^2 / (a^2 + b^2), d2^2 / (a'^2 + b'^2)) <= threshold_px^2. Evaluated in fp32,
+ *   division-free, on points conditioned once per pair: per view the centroid c and RMS distance d of all the pair's
+ *   matches (fp64 sums in a fixed order; d = 1 below 1 px), u = (x - c) / d, G = A2^T F A1 (A = [[d, 0, cx], [0, d, cy],
+ *   [0, 0, 1]]) scaled to max|G_ij| = 1; with l = G u1, l' = G^T u2, r = u2 . l: inlier when D2 = l0^2 + l1^2 > 0,
+ *   D1 = l'0^2 + l'1^2 > 0, r^2 <= (thr / d2)^2 D2 and r^2 <= (thr / d1)^2 D1. For every point whose fp64 pixel-space
+ *   error lies more than a relative 1e-3 from thr^2 the decision equals the fp64 form's (aria_slam_amd/fund_ref.py).
+ * Winner. Most inliers over all (h, k); ties to the lowest h, then the lowest k; an invalid model scores -1. A winner
+ *   needs at least 7 inliers (OpenCV's count > max(best, 6)), else valid = 0. Integer counts, fixed reduction order, no
+ *   refit: F is the winning minimal model, the mask its inliers.
+ * Validity. valid = 0: F = 0, n_inliers = n_models = 0, best_hypothesis = best_root = -1, mask zero, compacted count 0.
+ *   No field is ever NaN or Inf.
+ * Determinism. No float atomics; every result is bitwise reproducible run to run and independent of the batch split.
+ * Not restated: USAC, OpenCV's RNG sequence and its adaptive stop (the budget is fixed; the default 1024 covers the
+ *   reference's 1000 iterations). Parity with a running OpenCV is not pinned by any test. */
+typedef struct aria_fund_s* aria_fund_t;
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_fund_config)                                                    */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle creates and owns one. An owned stream is
+                                * non-blocking: it is NOT ordered against the legacy default stream (where torch works
+                                * by default), so a caller that fills inputs there must synchronise first or pass its
+                                * own stream                                                                        */
+    int      hypotheses;       /* per pair: multiple of 64, 64..16384 (default 1024)                            */
+    double   threshold_px;     /* findFundamentalMat's threshold in pixels (default 3.0, LoopClosure.cpp:143)    */
+    uint64_t seed;             /* sample hash seed (default 0)                                                   */
+} aria_fund_config;
+typedef struct {
+    double F[9];               /* row-major, pixel coordinates, x2^T F x1 = 0                                    */
+    int    n_matches, n_inliers, n_models, best_hypothesis, best_root, valid;   /* n_models: valid models scored */
+} aria_fund_result;            /* 96 bytes                                                                       */
+
+void  aria_fund_default_config(aria_fund_config* cfg);
+int   aria_fund_create(const aria_fund_config* cfg, aria_fund_t* out);
+void  aria_fund_destroy(aria_fund_t h);
+void* aria_fund_stream(aria_fund_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check, once:
+ * ARIA_E_INVALID when some pair's counts or match indices were out of range. Such a pair is detected before any keypoint
+ * is read and skipped (valid = 0, n_matches = 0, zero mask, compacted count 0); the other pairs are unaffected. */
+int   aria_fund_check(aria_fund_t h);
+/* One pair, host buffers; blocks. pair_base is the pair id of the sample hash. mask (optional): n_matches bytes,
+ * 1 = inlier of F. Out-of-range match indices: ARIA_E_INVALID. */
+int   aria_fund_estimate(aria_fund_t h, const aria_keypoint* kp_query, int nq, const aria_keypoint* kp_train, int nt,
+                         const aria_match* matches, int n_matches, int query_is_first, int pair_base, aria_fund_result* out,
+                         uint8_t* mask);
+/* Device-resident batch form with the conventions of aria_pose_estimate_batch_device (keypoints at p*kp_stride, matches
+ * at p*match_cap, pair id pair_base + p). Writes d_out[p] and, each optional: d_mask (match_cap bytes at p*match_cap, zero
+ * beyond the pair's matches); d_inliers (the F inliers' aria_match records in match order at p*match_cap, zero records
+ * beyond the count) with d_ninliers[p] = their count -- pass both or neither; they are the (d_matches, d_nmatches) input
+ * of aria_pose_estimate_batch_device with the same keypoints and match_cap. Enqueued on the handle's stream; no
+ * synchronisation (a larger batch grows the workspace, which waits for the stream). Data errors: aria_fund_check. */
+int   aria_fund_estimate_batch_device(aria_fund_t h, const aria_keypoint* d_kp_query, const int* d_nq,
+                                      const aria_keypoint* d_kp_train, const int* d_nt, int64_t kp_stride,
+                                      const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
+                                      int query_is_first, int pair_base, aria_fund_result* d_out, uint8_t* d_mask,
+                                      aria_match* d_inliers, int* d_ninliers);
+/* Test hook: for one pair (host buffers), per hypothesis h: the 7 sample indices (sample_idx[h*7 + j]; -1 when n < 15 or
+ * the slot stayed duplicate), the number of valid models n_models[h] (0, 1 or 3), the models F[h*27 + k*9 + e] (fp64, zero
+ * for k >= n_models[h]) and their inlier counts counts[h*3 + k] (-1 for k >= n_models[h]). Blocks. */
+int   aria_fund_debug_hypotheses(aria_fund_t h, const aria_keypoint* kp_query, int nq, const aria_keypoint* kp_train, int nt,
+                                 const aria_match* matches, int n_matches, int query_is_first, int pair_base, int* sample_idx,
+                                 int* n_models, double* F, int* counts);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
