@@ -53,6 +53,9 @@ EXPORTS = [
     # fundamental-matrix RANSAC (findFundamentalMat FM_RANSAC, loop verification), additive to ABI 4
     "aria_fund_default_config", "aria_fund_create", "aria_fund_destroy", "aria_fund_stream", "aria_fund_check",
     "aria_fund_estimate", "aria_fund_estimate_batch_device", "aria_fund_debug_hypotheses",
+    # SE(3) pose-graph optimisation (PoseGraphOptimizer: LM over VertexSE3 / EdgeSE3), additive to ABI 4
+    "aria_graph_default_config", "aria_graph_create", "aria_graph_destroy", "aria_graph_stream", "aria_graph_check",
+    "aria_graph_optimize", "aria_graph_optimize_batch_device", "aria_graph_debug_linearize",
 ]
 
 
@@ -82,6 +85,28 @@ POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8
 class FundConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("hypotheses", C.c_int),
                 ("threshold_px", C.c_double), ("seed", C.c_uint64)]
+
+
+class GraphConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("max_graphs", C.c_int),
+                ("max_vertices", C.c_int), ("max_edges", C.c_int), ("pcg_max_iters", C.c_int), ("pcg_rel_tol", C.c_double)]
+
+
+class GraphEdge(C.Structure):
+    _fields_ = [("from_", C.c_int32), ("to", C.c_int32), ("info_scale", C.c_double), ("Z", C.c_double * 12)]
+
+
+class GraphResult(C.Structure):
+    _fields_ = [("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_", C.c_double),
+                ("iterations_done", C.c_int), ("trials", C.c_int), ("pcg_iterations", C.c_int), ("valid", C.c_int),
+                ("stop_reason", C.c_int), ("reserved", C.c_int)]
+
+
+# aria_graph_edge (112 bytes) and aria_graph_result (48 bytes)
+GRAPH_EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("info_scale", "<f8"), ("Z", "<f8", (12,))])
+GRAPH_RESULT_DTYPE = np.dtype([("chi2_initial", "<f8"), ("chi2_final", "<f8"), ("lambda", "<f8"), ("iterations_done", "<i4"),
+                               ("trials", "<i4"), ("pcg_iterations", "<i4"), ("valid", "<i4"), ("stop_reason", "<i4"),
+                               ("reserved", "<i4")])
 
 
 # aria_fund_result (96 bytes)
@@ -238,6 +263,8 @@ def load_library():
         _bind_map(L)
     if hasattr(L, "aria_fund_create"):
         _bind_fund(L)
+    if hasattr(L, "aria_graph_create"):
+        _bind_graph(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -300,6 +327,21 @@ def _bind_fund(L):
     L.aria_fund_estimate.argtypes = [p, p, i, p, i, p, i, i, i, p, p]
     L.aria_fund_estimate_batch_device.argtypes = [p, p, p, p, p, C.c_int64, p, p, i, i, i, i, p, p, p, p]
     L.aria_fund_debug_hypotheses.argtypes = [p, p, i, p, i, p, i, i, i, p, p, p, p]
+
+
+def _bind_graph(L):
+    p, i = C.c_void_p, C.c_int
+    L.aria_graph_default_config.restype = None
+    L.aria_graph_default_config.argtypes = [p]
+    L.aria_graph_create.argtypes = [p, C.POINTER(C.c_void_p)]
+    L.aria_graph_destroy.restype = None
+    L.aria_graph_destroy.argtypes = [p]
+    L.aria_graph_stream.restype = p
+    L.aria_graph_stream.argtypes = [p]
+    L.aria_graph_check.argtypes = [p]
+    L.aria_graph_optimize.argtypes = [p, p, i, i, p, i, i, p]
+    L.aria_graph_optimize_batch_device.argtypes = [p, p, p, p, p, p, i, i, p]
+    L.aria_graph_debug_linearize.argtypes = [p, p, i, i, p, i, p, p, p, p]
 
 
 def status_string(status):

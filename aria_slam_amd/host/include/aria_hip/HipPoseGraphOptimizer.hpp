@@ -1,0 +1,87 @@
+// aria::adapters::hip::HipPoseGraphOptimizer -- the reference's PoseGraphOptimizer (include/legacy/LoopClosure.hpp:80-113,
+// src/legacy/LoopClosure.cpp:197-312: g2o VertexSE3 / EdgeSE3 under Levenberg-Marquardt) over the C-ABI
+// (include/aria_orb_hip.h, "SE(3) pose-graph optimisation"; aria_slam_amd/graph_ref.py is the definition of the stage, parity
+// with a running g2o is not pinned).
+//
+// The class keeps the graph on the host as the reference class does: ids map to dense vertex indices in the order they were
+// first added, and the first one added is the fixed vertex (LoopClosure.cpp:246-249); setInitialPose on a known id
+// overwrites the estimate; an edge that names an unknown id is dropped silently (:258-261); loop edges carry 10x the
+// information; getOptimizedPose of an unknown id is the identity; getAllPoses is in ascending id order. optimize() sends the
+// graph through aria_graph_optimize; the device handle is created at the first optimize() and grown when the graph outgrows
+// it.
+//
+// Poses are GraphPose: Eigen::Matrix4d with the reference's headers, the row-major stand-in core::Matrix4 without them; both
+// are read and written through operator()(row, col). loopRelativePose turns LoopCandidate::relative_pose (double[16] in
+// the stand-in, stored column-major like Eigen's) into one.
+#pragma once
+#include <map>
+#include <vector>
+
+#include "aria_hip/compat.hpp"
+#include "aria_orb_hip.h"
+
+namespace aria::adapters::hip {
+
+#ifdef ARIA_HIP_USE_REFERENCE_HEADERS
+using GraphPose = Eigen::Matrix4d;
+#else
+using GraphPose = core::Matrix4;
+#endif
+
+namespace detail {
+template <typename M>
+auto toGraphPose(const M& m, int) -> decltype(m(0, 0), GraphPose()) {
+    GraphPose T = GraphPose::Identity();
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) T(r, c) = m(r, c);
+    return T;
+}
+template <typename M>
+GraphPose toGraphPose(const M& m, long) {
+    GraphPose T = GraphPose::Identity();
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) T(r, c) = m[c * 4 + r];
+    return T;
+}
+// one entry of a LoopCandidate::relative_pose, for code that fills one with either set of headers
+template <typename M>
+auto setEntry(M& m, int r, int c, double v, int) -> decltype(m(0, 0) = 0.0, void()) { m(r, c) = v; }
+template <typename M>
+void setEntry(M& m, int r, int c, double v, long) { m[c * 4 + r] = v; }
+}  // namespace detail
+
+// LoopCandidate::relative_pose as a GraphPose, with either set of headers
+inline GraphPose loopRelativePose(const core::LoopCandidate& c) { return detail::toGraphPose(c.relative_pose, 0); }
+
+class HipPoseGraphOptimizer {
+public:
+    explicit HipPoseGraphOptimizer(int pcg_max_iters = 1000, double pcg_rel_tol = 1e-8, void* stream = nullptr, int device = 0);
+    ~HipPoseGraphOptimizer();
+    HipPoseGraphOptimizer(const HipPoseGraphOptimizer&) = delete;
+    HipPoseGraphOptimizer& operator=(const HipPoseGraphOptimizer&) = delete;
+
+    // the reference class's surface
+    void addOdometryEdge(int from_id, int to_id, const GraphPose& relative_pose, double info_scale = 1.0);
+    void addLoopEdge(int from_id, int to_id, const GraphPose& relative_pose, double info_scale = 1.0);
+    void setInitialPose(int id, const GraphPose& pose);
+    void optimize(int iterations = 10);
+    GraphPose getOptimizedPose(int id) const;
+    std::vector<GraphPose> getAllPoses() const;
+    void clear();
+
+    const aria_graph_result& lastResult() const { return last_; }
+    std::size_t numVertices() const { return poses_.size() / 12; }
+    std::size_t numEdges() const { return edges_.size(); }
+
+private:
+    [[noreturn]] static void fail(const char* where, int status);
+    void addEdge(int from_id, int to_id, const double rows[12], double info_scale);
+    aria_graph_t h_ = nullptr;
+    aria_graph_config cfg_{};
+    std::map<int, int> index_;               // id -> vertex index, in order of first setInitialPose
+    std::vector<double> poses_;              // 12 per vertex, rows of [R t]
+    std::vector<aria_graph_edge> edges_;
+    aria_graph_result last_{};
+};
+
+}  // namespace aria::adapters::hip

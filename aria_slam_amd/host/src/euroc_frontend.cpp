@@ -1,5 +1,6 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
+//                [--optimize FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -37,6 +38,18 @@
 // The loop step then runs over the merged stream as in the sharded mode, keeping the keypoints of the keyframes the
 // database holds. Keyframes are the default run's; the loops are a subset of its. Without the flag nothing changes.
 //
+// --optimize FILE (needs --pose, --loop and --loop-verify reference, so that accepted candidates carry relative_pose): the
+// pose graph of euroc_eval.cpp through aria_hip/HipPoseGraphOptimizer.hpp -- setInitialPose(frame, current_pose) and
+// addOdometryEdge(frame - 1, frame, delta) exactly where :211-215 adds them (after every accepted pose update; the first
+// vertex added is the fixed one and an edge to a frame without a vertex is dropped, as in the reference), one
+// addLoopEdge(query_id, match_id, relative_pose) per accepted loop candidate (:235), then the final optimize(50) and one
+// TUM line per frame from getOptimizedPose (:282-288). DEVIATIONS: (1) the loop step of this driver runs post hoc over the
+// merged stream, so the reference's optimize(10) after every loop and its reset of current_pose to the optimised pose
+// (:237-238) are NOT reproduced; the odometry chain is the one --pose writes. (2) A frame without an accepted pose is no
+// vertex; its line holds the optimised pose of the last vertex before it, as its --pose line holds current_pose (the
+// reference's class would answer the identity for it). Without the flag nothing changes; --pose FILE and the CSV are
+// byte-identical with and without it.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -63,6 +76,7 @@
 #include "aria_hip/HipFundamentalEstimator.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
+#include "aria_hip/HipPoseGraphOptimizer.hpp"
 #include "aria_hip/Shard.hpp"
 #include "aria_orb_hip.h"
 
@@ -94,12 +108,14 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file]\n"
+                             "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
+                             "                   the per-loop optimize(10) and reset of current_pose of the reference are not reproduced (the loop step is post hoc)\n", argv[0]);
         return -1;                                                        // euroc_eval.cpp:64-70
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
-    std::string csv, pose_file, map_file, loop_verify;
+    std::string csv, pose_file, map_file, loop_verify, optimize_file;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -111,6 +127,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pose") && i + 1 < argc) pose_file = argv[++i];
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
+        else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -122,6 +139,10 @@ int main(int argc, char** argv) {
         return -1;
     }
     const bool verify_reference = !loop_verify.empty();
+    if (!optimize_file.empty() && (pose_file.empty() || !verify_reference)) {
+        std::fprintf(stderr, "--optimize needs --pose, --loop and --loop-verify reference (loop edges carry the verified relative pose)\n");
+        return -1;
+    }
     if (!map_file.empty() && pose_file.empty()) {
         std::fprintf(stderr, "--map needs --pose (it triangulates along the estimated trajectory)\n");
         return -1;
@@ -162,6 +183,16 @@ int main(int argc, char** argv) {
     std::vector<std::array<double, 16>> traj(pose_file.empty() ? 0 : N);
     long long n_pose_updates = 0;
     std::size_t map_points = 0;
+    // --optimize: the reference's PoseGraphOptimizer over the device (euroc_eval.cpp:211-215, 235, 282-288)
+    std::unique_ptr<adapters::hip::HipPoseGraphOptimizer> graph;
+    if (!optimize_file.empty()) graph = std::make_unique<adapters::hip::HipPoseGraphOptimizer>();
+    std::vector<long long> last_vertex(graph ? N : 0, -1);                 // per frame: the last frame at or before it that is a vertex
+    auto graphPose = [](const std::array<double, 16>& T) {
+        adapters::hip::GraphPose m = adapters::hip::GraphPose::Identity();
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) m(a, b) = T[(size_t)(a * 4 + b)];
+        return m;
+    };
     const auto t0 = std::chrono::steady_clock::now();
 
     // one shard = one FrontEnd (its own extractor + matcher handles on its device) over frames [first, hi)
@@ -223,11 +254,17 @@ int main(int argc, char** argv) {
                                 current_pose[(size_t)(a * 4 + b)] = v;     // current_pose = current_pose * delta (:206)
                             }
                         n_pose_updates++;
+                        if (graph) {                                       // euroc_eval.cpp:211-215
+                            graph->setInitialPose((int)i, graphPose(current_pose));
+                            if (i > 0) graph->addOdometryEdge((int)i - 1, (int)i, graphPose(d));
+                            last_vertex[i] = (long long)i;
+                        }
                         if (mapper && r.previous)                          // euroc_eval.cpp:218-222: view 1 = previous frame
                             mapper->triangulateExtrinsics(*r.previous, *r.frame, r.matches, c.data(), current_pose.data(),
                                                           prev_gray.data(), pw, ph, fc.frontend.legacy_order);
                     }
                     traj[i] = current_pose;
+                    if (graph && last_vertex[i] < 0 && i > 0) last_vertex[i] = last_vertex[i - 1];
                 }
                 if (mapper) { prev_gray.swap(gray); pw = fw; ph = fh; }
                 FrameRecord& o = rec[i];
@@ -298,6 +335,8 @@ int main(int argc, char** argv) {
                 if (held.size() > 500) { rec[held.front()].frame.reset(); held.pop_front(); }
             }
             if (lp) { o.loop_match_id = (long long)lp->match_id; o.loop_score = lp->score; }
+            if (lp && graph)                                               // euroc_eval.cpp:235
+                graph->addLoopEdge((int)lp->query_id, (int)lp->match_id, adapters::hip::loopRelativePose(*lp));
         }
     }
 
@@ -332,11 +371,12 @@ int main(int argc, char** argv) {
                     t.d2h_s > 0 ? t.d2h_bytes / t.d2h_s * 1e-9 : 0.0, t.deliver_s, t.wall_s);
     }
     if (loop) std::printf("keyframes %lld loops %lld\n", n_keyframes, n_loops);
-    if (!pose_file.empty()) {
-        std::ofstream tf(pose_file);
+    // one TUM line per frame: "timestamp tx ty tz qx qy qz qw" of a 4x4 row-major pose
+    auto write_tum = [&](const std::string& path, auto&& pose_of) {
+        std::ofstream tf(path);
         tf << std::fixed << std::setprecision(9);
         for (std::size_t i = 0; i < N; i++) {
-            const std::array<double, 16>& T = traj[i];
+            const std::array<double, 16> T = pose_of(i);
             double q[4];                                                   // rotation -> quaternion (x, y, z, w)
             const double tr = T[0] + T[5] + T[10];
             if (tr > 0) {
@@ -355,7 +395,25 @@ int main(int argc, char** argv) {
             tf << seq.at(i).timestamp << ' ' << T[3] << ' ' << T[7] << ' ' << T[11] << ' ' << q[0] << ' ' << q[1] << ' ' << q[2]
                << ' ' << q[3] << '\n';
         }
+    };
+    if (!pose_file.empty()) {
+        write_tum(pose_file, [&](std::size_t i) { return traj[i]; });
         std::printf("pose updates %lld of %zu frames -> %s\n", n_pose_updates, N > 0 ? N - 1 : 0, pose_file.c_str());
+    }
+    if (graph) {                                                           // euroc_eval.cpp:282-288
+        graph->optimize(50);
+        write_tum(optimize_file, [&](std::size_t i) {
+            if (last_vertex[i] < 0) return traj[i];                        // before the first vertex: current_pose, the identity
+            const adapters::hip::GraphPose m = graph->getOptimizedPose((int)last_vertex[i]);
+            std::array<double, 16> T{};
+            for (int a = 0; a < 4; a++)
+                for (int b = 0; b < 4; b++) T[(size_t)(a * 4 + b)] = m(a, b);
+            return T;
+        });
+        const aria_graph_result& gr = graph->lastResult();
+        std::printf("pose graph %zu vertices %zu edges | chi2 %.6g -> %.6g in %d iterations (%d solves, %d PCG iterations) -> %s\n",
+                    graph->numVertices(), graph->numEdges(), gr.chi2_initial, gr.chi2_final, gr.iterations_done, gr.trials,
+                    gr.pcg_iterations, optimize_file.c_str());
     }
     if (!map_file.empty()) std::printf("map %zu points -> %s\n", map_points, map_file.c_str());
     return 0;

@@ -654,6 +654,83 @@ int   aria_fund_debug_hypotheses(aria_fund_t h, const aria_keypoint* kp_query, i
                                  const aria_match* matches, int n_matches, int query_is_first, int pair_base, int* sample_idx,
                                  int* n_models, double* F, int* counts);
 
+/* ---- SE(3) pose-graph optimisation: the reference's PoseGraphOptimizer (include/legacy/LoopClosure.hpp:80-113,
+ * src/legacy/LoopClosure.cpp:197-312), g2o's VertexSE3 / EdgeSE3 graph under Levenberg-Marquardt, batched over graphs.
+ * Additive to ABI 4. aria_slam_amd/graph_ref.py restates the stage in NumPy and is its definition; parity with a running
+ * g2o is not pinned by any test (g2o and Eigen are not available to this project).
+ *
+ * Pose. 12 doubles, the rows of [R t]. A graph's vertices are the dense indices 0..n-1 (the id -> index map, the dropping
+ *   of edges that name an unknown id and the x10 of loop edges live in the adapters); one vertex is fixed.
+ * Update. X <- X * fromMQT(d), d = (tx, ty, tz, qx, qy, qz), w = sqrt(1 - |q|^2), for |q|^2 > 1 the quaternion (0, -q)
+ *   normalised; the rotation is then replaced by that of its unit quaternion.
+ * Error. e = toMQT(Z^-1 Xi^-1 Xj) with the quaternion's w >= 0; chi2 = sum info_scale * e.e. Analytic Jacobians.
+ * LM. lambda0 = 1e-5 max diag(H) per call; a trial solves (H + lambda I) dx = b; rho = (chi2 - chi2_new) / (dx.(lambda dx
+ *   + b) + 1e-3); accepted when rho > 0 and chi2_new is finite, then lambda *= max(1/3, 1 - (2 rho - 1)^3), ni = 2;
+ *   otherwise lambda *= ni, ni *= 2 and the poses are restored; at most 10 trials; an iteration whose trials all fail ends
+ *   the call (stop_reason 1). No robust kernel.
+ * Solver. Block-Jacobi preconditioned conjugate gradients in fp64, from x = 0, until |r| <= pcg_rel_tol |b| or
+ *   pcg_max_iters; |b| = 0 gives dx = 0. One workgroup per graph, no communication between workgroups.
+ * Invalid input. Counts below 0, a fixed index outside [0, n), an edge index outside [0, n), an edge from a vertex to
+ *   itself or an info_scale that is negative or not finite: that graph gets valid = 0, stop_reason 2, before any of its
+ *   poses is read, and its poses are not written; the other graphs of the batch are unaffected.
+ * Determinism. No float atomics; H is gathered per vertex over its edges in edge order; sums are fixed trees. Every pose
+ *   and result is bitwise reproducible run to run and independent of the graph's place in a batch and of the batch split.
+ *   The fixed vertex is never written; with iterations = 0 no pose is written. */
+typedef struct aria_graph_s* aria_graph_t;
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_graph_config)                                                   */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking: not
+                                * ordered against the legacy default stream, see aria_fund_config)               */
+    int      max_graphs;       /* graphs in flight per launch (scratch slots), 1..65535 (default 1); a larger batch
+                                * runs as consecutive launches                                                    */
+    int      max_vertices;     /* per graph, 1..2^20 (default 4096)                                              */
+    int      max_edges;        /* per graph, 1..2^22 (default 8192)                                              */
+    int      pcg_max_iters;    /* cap of one solve (default 1000)                                                */
+    double   pcg_rel_tol;      /* stop at |r| <= pcg_rel_tol |b| (default 1e-8)                                  */
+} aria_graph_config;           /* 40 bytes                                                                       */
+typedef struct {
+    int32_t  from, to;         /* vertex indices of the graph                                                    */
+    double   info_scale;       /* information = info_scale * I6                                                  */
+    double   Z[12];            /* the measured pose of `to` in the frame of `from`, rows of [R t]                */
+} aria_graph_edge;             /* 112 bytes                                                                      */
+typedef struct {
+    double   chi2_initial, chi2_final, lambda;
+    int      iterations_done;  /* iterations with an accepted trial                                              */
+    int      trials;           /* linear solves                                                                  */
+    int      pcg_iterations;   /* over all solves                                                                */
+    int      valid;
+    int      stop_reason;      /* 0 = the iteration count, 1 = every trial of an iteration failed, 2 = invalid   */
+    int      reserved;
+} aria_graph_result;           /* 48 bytes                                                                       */
+
+void  aria_graph_default_config(aria_graph_config* cfg);
+int   aria_graph_create(const aria_graph_config* cfg, aria_graph_t* out);
+void  aria_graph_destroy(aria_graph_t h);
+void* aria_graph_stream(aria_graph_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check, once:
+ * ARIA_E_INVALID when some graph was invalid (above), else ARIA_E_TOO_LARGE when some graph had more vertices or edges
+ * than the handle was created for (that graph: valid = 0, nothing read, nothing written). */
+int   aria_graph_check(aria_graph_t h);
+/* One graph, host arrays; blocks. poses_inout: n_vertices * 12 doubles. Invalid input: ARIA_E_INVALID, larger than the
+ * handle: ARIA_E_TOO_LARGE, in both cases nothing is written. */
+int   aria_graph_optimize(aria_graph_t h, double* poses_inout, int n_vertices, int fixed_index, const aria_graph_edge* edges,
+                          int n_edges, int iterations, aria_graph_result* result);
+/* Device-resident batch: graph g owns the vertices d_vertex_offset[g] .. d_vertex_offset[g+1] of d_poses (12 doubles each)
+ * and the edges d_edge_offset[g] .. d_edge_offset[g+1] of d_edges (indices relative to the graph), fixed vertex
+ * d_fixed[g]; both offset arrays hold n_graphs + 1 entries. Writes d_poses in place and d_results[g]. Enqueued on the
+ * handle's stream: every LM iteration of a graph runs inside one launch, there is no host synchronisation. Data errors:
+ * aria_graph_check. */
+int   aria_graph_optimize_batch_device(aria_graph_t h, double* d_poses, const int* d_vertex_offset,
+                                       const aria_graph_edge* d_edges, const int* d_edge_offset, const int* d_fixed,
+                                       int n_graphs, int iterations, aria_graph_result* d_results);
+/* Test hook: one graph (host arrays) linearised at its poses. chi2; b (n_vertices * 6); H_diag (n_vertices * 36, row-major
+ * 6x6 diagonal blocks); H_off (n_edges * 36, the block at (from, to) of every edge, row-major; its transpose sits at
+ * (to, from)). Nothing of the fixed vertex is removed. Blocks. */
+int   aria_graph_debug_linearize(aria_graph_t h, const double* poses, int n_vertices, int fixed_index,
+                                 const aria_graph_edge* edges, int n_edges, double* chi2, double* b, double* H_diag,
+                                 double* H_off);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
