@@ -56,6 +56,10 @@ EXPORTS = [
     # SE(3) pose-graph optimisation (PoseGraphOptimizer: LM over VertexSE3 / EdgeSE3), additive to ABI 4
     "aria_graph_default_config", "aria_graph_create", "aria_graph_destroy", "aria_graph_stream", "aria_graph_check",
     "aria_graph_optimize", "aria_graph_optimize_batch_device", "aria_graph_debug_linearize",
+    # visual-inertial fusion (SensorFusion EKF + IMUPreintegrator), additive to ABI 4
+    "aria_fuse_default_config", "aria_fuse_create", "aria_fuse_destroy", "aria_fuse_stream", "aria_fuse_check",
+    "aria_fuse_filter_init", "aria_fuse_run_batch_device", "aria_fuse_run", "aria_fuse_visual_from_pose_device",
+    "aria_fuse_preintegrate_batch_device", "aria_fuse_preintegrate",
 ]
 
 
@@ -107,6 +111,54 @@ GRAPH_EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("info_scale", "<f8
 GRAPH_RESULT_DTYPE = np.dtype([("chi2_initial", "<f8"), ("chi2_final", "<f8"), ("lambda", "<f8"), ("iterations_done", "<i4"),
                                ("trials", "<i4"), ("pcg_iterations", "<i4"), ("valid", "<i4"), ("stop_reason", "<i4"),
                                ("reserved", "<i4")])
+
+
+class FuseConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("gravity", C.c_double * 3),
+                ("accel_noise", C.c_double), ("gyro_noise", C.c_double), ("accel_bias_walk", C.c_double),
+                ("gyro_bias_walk", C.c_double), ("pos_noise", C.c_double), ("rot_noise", C.c_double)]
+
+
+class ImuSample(C.Structure):
+    _fields_ = [("t", C.c_double), ("accel", C.c_double * 3), ("gyro", C.c_double * 3)]
+
+
+class FuseVisual(C.Structure):
+    _fields_ = [("t", C.c_double), ("R", C.c_double * 9), ("p", C.c_double * 3), ("accept", C.c_int), ("reserved", C.c_int)]
+
+
+class FuseFilter(C.Structure):
+    _fields_ = [("p", C.c_double * 3), ("v", C.c_double * 3), ("q", C.c_double * 4), ("ba", C.c_double * 3),
+                ("bg", C.c_double * 3), ("P", C.c_double * 225), ("last_imu_time", C.c_double),
+                ("last_visual_time", C.c_double), ("gravity", C.c_double * 3), ("accel_noise", C.c_double),
+                ("gyro_noise", C.c_double), ("accel_bias_walk", C.c_double), ("gyro_bias_walk", C.c_double),
+                ("pos_noise", C.c_double), ("rot_noise", C.c_double), ("initialized", C.c_int), ("reserved", C.c_int)]
+
+
+class FuseState(C.Structure):
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("v", C.c_double * 3), ("q", C.c_double * 4), ("ba", C.c_double * 3),
+                ("bg", C.c_double * 3), ("P_diag", C.c_double * 15), ("n_predicted", C.c_int), ("n_skipped", C.c_int),
+                ("n_ignored", C.c_int), ("n_updates", C.c_int), ("initialized", C.c_int), ("valid", C.c_int)]
+
+
+class PreintResult(C.Structure):
+    _fields_ = [("delta_p", C.c_double * 3), ("delta_v", C.c_double * 3), ("delta_q", C.c_double * 4), ("dt_sum", C.c_double),
+                ("cov", C.c_double * 81), ("n_used", C.c_int), ("valid", C.c_int)]
+
+
+# aria_imu_sample (56 bytes), aria_fuse_visual (112), aria_fuse_filter (2024), aria_fuse_state (280), aria_preint_result (744)
+IMU_SAMPLE_DTYPE = np.dtype([("t", "<f8"), ("accel", "<f8", (3,)), ("gyro", "<f8", (3,))])
+FUSE_VISUAL_DTYPE = np.dtype([("t", "<f8"), ("R", "<f8", (9,)), ("p", "<f8", (3,)), ("accept", "<i4"), ("reserved", "<i4")])
+FUSE_FILTER_DTYPE = np.dtype([("p", "<f8", (3,)), ("v", "<f8", (3,)), ("q", "<f8", (4,)), ("ba", "<f8", (3,)), ("bg", "<f8", (3,)),
+                              ("P", "<f8", (225,)), ("last_imu_time", "<f8"), ("last_visual_time", "<f8"),
+                              ("gravity", "<f8", (3,)), ("accel_noise", "<f8"), ("gyro_noise", "<f8"),
+                              ("accel_bias_walk", "<f8"), ("gyro_bias_walk", "<f8"), ("pos_noise", "<f8"), ("rot_noise", "<f8"),
+                              ("initialized", "<i4"), ("reserved", "<i4")])
+FUSE_STATE_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("v", "<f8", (3,)), ("q", "<f8", (4,)), ("ba", "<f8", (3,)),
+                             ("bg", "<f8", (3,)), ("P_diag", "<f8", (15,)), ("n_predicted", "<i4"), ("n_skipped", "<i4"),
+                             ("n_ignored", "<i4"), ("n_updates", "<i4"), ("initialized", "<i4"), ("valid", "<i4")])
+PREINT_RESULT_DTYPE = np.dtype([("delta_p", "<f8", (3,)), ("delta_v", "<f8", (3,)), ("delta_q", "<f8", (4,)), ("dt_sum", "<f8"),
+                                ("cov", "<f8", (81,)), ("n_used", "<i4"), ("valid", "<i4")])
 
 
 # aria_fund_result (96 bytes)
@@ -265,6 +317,8 @@ def load_library():
         _bind_fund(L)
     if hasattr(L, "aria_graph_create"):
         _bind_graph(L)
+    if hasattr(L, "aria_fuse_create"):
+        _bind_fuse(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -342,6 +396,24 @@ def _bind_graph(L):
     L.aria_graph_optimize.argtypes = [p, p, i, i, p, i, i, p]
     L.aria_graph_optimize_batch_device.argtypes = [p, p, p, p, p, p, i, i, p]
     L.aria_graph_debug_linearize.argtypes = [p, p, i, i, p, i, p, p, p, p]
+
+
+def _bind_fuse(L):
+    p, i = C.c_void_p, C.c_int
+    L.aria_fuse_default_config.restype = None
+    L.aria_fuse_default_config.argtypes = [p]
+    L.aria_fuse_create.argtypes = [p, C.POINTER(C.c_void_p)]
+    L.aria_fuse_destroy.restype = None
+    L.aria_fuse_destroy.argtypes = [p]
+    L.aria_fuse_stream.restype = p
+    L.aria_fuse_stream.argtypes = [p]
+    L.aria_fuse_check.argtypes = [p]
+    L.aria_fuse_filter_init.argtypes = [p, p]
+    L.aria_fuse_run_batch_device.argtypes = [p, p, p, p, i, p, p, p, i, i, p]
+    L.aria_fuse_run.argtypes = [p, p, p, i, p, p, i, p]
+    L.aria_fuse_visual_from_pose_device.argtypes = [p, p, p, i, i, p]
+    L.aria_fuse_preintegrate_batch_device.argtypes = [p, p, i, p, p, i, p, p]
+    L.aria_fuse_preintegrate.argtypes = [p, p, i, p, p, i, p, p]
 
 
 def status_string(status):

@@ -4,7 +4,11 @@
 // as the reference reads it (src/legacy/EuRoCReader.cpp:23-27, 70-108: skip header/comment lines, split at the
 // first comma, trim, sort by timestamp; :277-309: imread(IMREAD_GRAYSCALE)). OpenCV's imgcodecs is replaced by a
 // dependency-free PNG decoder (zlib inflate only): 8-bit, non-interlaced, colour types 0 (gray), 2 (RGB), 4 (gray+a),
-// 6 (RGBA); colour is converted with OpenCV's BGR2GRAY fixed-point weights. IMU / ground truth are out of scope.
+// 6 (RGBA); colour is converted with OpenCV's BGR2GRAY fixed-point weights.
+//     <root>/mav0/imu0/data.csv      "#timestamp [ns],w_x,w_y,w_z,a_x,a_y,a_z": gyro in columns 1-3, accelerometer in 4-6
+// is read when it is there (EuRoCReader.cpp:110-154: rows of fewer than 7 fields dropped, sorted by timestamp), together with
+// the samples every image consumes (getNext, :295-305: prev_image_time < t <= image_time, 0 before the first image); a
+// sequence without imu0 still loads. Ground truth is out of scope.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -17,6 +21,12 @@ struct AslImage {
     std::string path;
 };
 
+struct AslImu {
+    double timestamp = 0.0;          // seconds
+    double accel[3] = {0, 0, 0};     // m/s^2
+    double gyro[3] = {0, 0, 0};      // rad/s
+};
+
 class AslSequence {
 public:
     // dataset_path may be the sequence root (containing mav0/) or the mav0 directory itself
@@ -25,9 +35,15 @@ public:
     const AslImage& at(std::size_t i) const { return images_[i]; }
     // Decodes image i to 8-bit grayscale, row-major, tightly packed. Throws std::runtime_error on a bad file.
     void read(std::size_t i, std::vector<std::uint8_t>& gray, int& width, int& height) const;
+    // imu0, sorted by timestamp (empty without imu0), and the samples [imuBegin(i), imuEnd(i)) that image i consumes
+    const std::vector<AslImu>& imu() const { return imu_; }
+    std::size_t imuBegin(std::size_t i) const { return imu_begin_[i]; }
+    std::size_t imuEnd(std::size_t i) const { return imu_end_[i]; }
 
 private:
     std::vector<AslImage> images_;
+    std::vector<AslImu> imu_;
+    std::vector<std::size_t> imu_begin_, imu_end_;
 };
 
 // PNG -> 8-bit grayscale (see header comment). Throws std::runtime_error.

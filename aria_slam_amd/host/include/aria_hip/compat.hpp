@@ -12,6 +12,7 @@
 #include "interfaces/ILoopDetector.hpp"
 #include "interfaces/IMapper.hpp"
 #include "interfaces/IMatcher.hpp"
+#include "interfaces/ISensorFusion.hpp"
 #else
 
 #include <cstddef>
@@ -109,6 +110,7 @@ struct Pose {
     Vector3 position;
     Quaternion orientation;
     double timestamp = 0.0;
+    Matrix<6, 6> covariance = Matrix<6, 6>::Identity();
     Matrix4 toMatrix() const {
         const double w = orientation.w, x = orientation.x, y = orientation.y, z = orientation.z;
         Matrix4 T = Matrix4::Identity();
@@ -118,6 +120,13 @@ struct Pose {
         for (int r = 0; r < 3; r++) T(r, 3) = position(r);
         return T;
     }
+};
+
+// include/core/Types.hpp:90-94
+struct ImuMeasurement {
+    double timestamp = 0.0;
+    Vector3 accel;          // m/s^2
+    Vector3 gyro;           // rad/s
 };
 
 }  // namespace aria::core
@@ -177,6 +186,19 @@ public:
     virtual std::size_t size() const = 0;
 };
 using MapperPtr = std::unique_ptr<IMapper>;
+
+// include/interfaces/ISensorFusion.hpp:9-30 (getVelocity returns Eigen::Vector3d there)
+class ISensorFusion {
+public:
+    virtual ~ISensorFusion() = default;
+    virtual void predictIMU(const core::ImuMeasurement& imu) = 0;
+    virtual void updateVO(const core::Pose& vo_pose) = 0;
+    virtual core::Pose getFusedPose() const = 0;
+    virtual core::Vector3 getVelocity() const = 0;
+    virtual void reset() = 0;
+    virtual void reset(const core::Pose& initial_pose) = 0;
+};
+using SensorFusionPtr = std::unique_ptr<ISensorFusion>;
 
 }  // namespace aria::interfaces
 

@@ -125,6 +125,39 @@ bool AslSequence::load(const std::string& dataset_path) {
         images_.push_back(img);
     }
     std::stable_sort(images_.begin(), images_.end(), [](const AslImage& a, const AslImage& b) { return a.timestamp < b.timestamp; });
+    // imu0 beside cam0 (EuRoCReader.cpp:110-154); its absence is not an error
+    imu_.clear();
+    std::ifstream imu_file(cam.substr(0, cam.size() - 4) + "imu0/data.csv");
+    if (imu_file.is_open()) {
+        std::getline(imu_file, line);                                         // header (:119)
+        while (std::getline(imu_file, line)) {
+            if (line.empty() || line[0] == '#') continue;                     // :122
+            std::stringstream ss(line);
+            std::string token;
+            std::vector<std::string> tokens;
+            while (std::getline(ss, token, ',')) tokens.push_back(token);
+            if (tokens.size() < 7) continue;                                  // :132
+            AslImu m;
+            m.timestamp = std::strtod(tokens[0].c_str(), nullptr) * 1e-9;
+            for (int k = 0; k < 3; k++) {                                     // timestamp, gyro xyz, accel xyz (:137-143)
+                m.gyro[k] = std::strtod(tokens[(std::size_t)(1 + k)].c_str(), nullptr);
+                m.accel[k] = std::strtod(tokens[(std::size_t)(4 + k)].c_str(), nullptr);
+            }
+            imu_.push_back(m);
+        }
+        std::stable_sort(imu_.begin(), imu_.end(), [](const AslImu& a, const AslImu& b) { return a.timestamp < b.timestamp; });
+    }
+    // getNext (:295-305): image i takes the samples with prev_image_time < t <= image_time, in order
+    imu_begin_.assign(images_.size(), 0);
+    imu_end_.assign(images_.size(), 0);
+    std::size_t k = 0;
+    for (std::size_t i = 0; i < images_.size(); i++) {
+        const double prev = i > 0 ? images_[i - 1].timestamp : 0.0, now = images_[i].timestamp;
+        while (k < imu_.size() && imu_[k].timestamp <= now && !(imu_[k].timestamp > prev)) k++;   // consumed, not handed on
+        imu_begin_[i] = k;
+        while (k < imu_.size() && imu_[k].timestamp <= now) k++;
+        imu_end_[i] = k;
+    }
     return !images_.empty();                                                  // :105
 }
 
@@ -163,6 +196,24 @@ int aria_asl_list(const char* dataset_path, double* timestamps, int cap, char* f
     for (std::size_t i = 0; i < s.size() && (int)i < cap; i++) timestamps[i] = s.at(i).timestamp;
     if (first_path && first_path_cap > 0) std::snprintf(first_path, (std::size_t)first_path_cap, "%s", s.at(0).path.c_str());
     return (int)s.size();
+}
+
+// IMU samples as rows [t, accel xyz, gyro xyz] (the layout of aria_imu_sample) and [begin, end) per image; returns the number
+// of samples (0 without imu0) or -1. n_images receives the number of images.
+int aria_asl_imu(const char* dataset_path, double* samples, int cap, int* ranges, int image_cap, int* n_images) {
+    aria::io::AslSequence s;
+    if (!s.load(dataset_path)) return -1;
+    const auto& imu = s.imu();
+    for (std::size_t i = 0; i < imu.size() && (int)i < cap; i++) {
+        samples[7 * i] = imu[i].timestamp;
+        for (int k = 0; k < 3; k++) { samples[7 * i + 1 + k] = imu[i].accel[k]; samples[7 * i + 4 + k] = imu[i].gyro[k]; }
+    }
+    for (std::size_t i = 0; i < s.size() && (int)i < image_cap; i++) {
+        ranges[2 * i] = (int)s.imuBegin(i);
+        ranges[2 * i + 1] = (int)s.imuEnd(i);
+    }
+    if (n_images) *n_images = (int)s.size();
+    return (int)imu.size();
 }
 
 }  // extern "C"

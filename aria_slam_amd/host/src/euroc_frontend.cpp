@@ -1,13 +1,14 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
-//                [--optimize FILE]
+//                [--optimize FILE] [--fuse FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
 //   extract ORB (2000 features by default, euroc_eval.cpp:88) -> kNN-2 + ratio 0.75 against the previous frame
 // (:168-175) -> report; with --loop also the loop-closure candidate step of :103, 230-247 (every frame with >= 8 matches
 // becomes a keyframe: detect against the HBM-resident database with LoopClosureDetector(200, 0.4, 50)'s parameters, then
-// add). Pose estimation, EKF, YOLO, geometric verification and mapping are out of scope.
+// add). The later stages of that loop are flags of their own below (--pose, --map, --loop-verify, --optimize, --fuse); YOLO
+// (it needs model weights) and the visualisation are out of scope.
 //
 // --devices N / --shards K: the sequence is cut into K contiguous shards (default K = N) with a one-frame halo
 // (aria_hip/Shard.hpp); every shard gets its own host thread and its own extractor + matcher handles (PipelineFactory's
@@ -50,6 +51,14 @@
 // reference's class would answer the identity for it). Without the flag nothing changes; --pose FILE and the CSV are
 // byte-identical with and without it.
 //
+// --fuse FILE (needs --pose; the sequence needs mav0/imu0): the SensorFusion EKF of euroc_eval.cpp on the device (include/
+// aria_orb_hip.h, "visual-inertial fusion"). Every frame first hands the filter the IMU samples between the previous image and
+// this one (:139-142, the ranges of EuRoCReader::getNext), then, when its pose was accepted, addVisualPose(timestamp, R, t)
+// with the RELATIVE R, t of recoverPose (unit-length t), which is what :209 passes -- not the accumulated current_pose. The
+// whole track runs as one aria_fuse_run after the last frame; FILE gets one TUM line per frame of the fused position and
+// orientation after that frame's events (the filter's initial state before the first accepted pose), and "fused N updates
+// ..." is printed. Without the flag nothing changes; --pose FILE and the CSV are byte-identical with and without it.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -77,6 +86,7 @@
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
+#include "aria_hip/HipSensorFusion.hpp"
 #include "aria_hip/Shard.hpp"
 #include "aria_orb_hip.h"
 
@@ -108,14 +118,15 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file]\n"
+                             "  --fuse file: EKF visual-inertial fusion over imu0 and the --pose stage's relative poses (needs --pose), one TUM line per frame\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
                              "                   the per-loop optimize(10) and reset of current_pose of the reference are not reproduced (the loop step is post hoc)\n", argv[0]);
         return -1;                                                        // euroc_eval.cpp:64-70
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
-    std::string csv, pose_file, map_file, loop_verify, optimize_file;
+    std::string csv, pose_file, map_file, loop_verify, optimize_file, fuse_file;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -128,6 +139,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
         else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--fuse") && i + 1 < argc) fuse_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -142,6 +154,10 @@ int main(int argc, char** argv) {
     if (!optimize_file.empty() && (pose_file.empty() || !verify_reference)) {
         std::fprintf(stderr, "--optimize needs --pose, --loop and --loop-verify reference (loop edges carry the verified relative pose)\n");
         return -1;
+    }
+    if (!fuse_file.empty() && pose_file.empty()) {
+        std::fprintf(stderr, "--fuse needs --pose (the filter is updated with the pose stage's relative poses)\n");
+        return 1;
     }
     if (!map_file.empty() && pose_file.empty()) {
         std::fprintf(stderr, "--map needs --pose (it triangulates along the estimated trajectory)\n");
@@ -182,6 +198,8 @@ int main(int argc, char** argv) {
     // --pose: current_pose per frame (4x4 row-major), chained as euroc_eval.cpp:202-206 does
     std::vector<std::array<double, 16>> traj(pose_file.empty() ? 0 : N);
     long long n_pose_updates = 0;
+    // --fuse: the visual record of every frame (euroc_eval.cpp:209), filled where the pose is accepted
+    std::vector<aria_fuse_visual> fuse_visual(fuse_file.empty() ? 0 : N);
     std::size_t map_points = 0;
     // --optimize: the reference's PoseGraphOptimizer over the device (euroc_eval.cpp:211-215, 235, 282-288)
     std::unique_ptr<adapters::hip::HipPoseGraphOptimizer> graph;
@@ -254,6 +272,14 @@ int main(int argc, char** argv) {
                                 current_pose[(size_t)(a * 4 + b)] = v;     // current_pose = current_pose * delta (:206)
                             }
                         n_pose_updates++;
+                        if (!fuse_visual.empty()) {                        // euroc_eval.cpp:209: the relative R, t
+                            aria_fuse_visual& v = fuse_visual[i];
+                            for (int a = 0; a < 3; a++) {
+                                for (int b = 0; b < 3; b++) v.R[a * 3 + b] = d[(size_t)(a * 4 + b)];
+                                v.p[a] = d[(size_t)(a * 4 + 3)];
+                            }
+                            v.accept = 1;
+                        }
                         if (graph) {                                       // euroc_eval.cpp:211-215
                             graph->setInitialPose((int)i, graphPose(current_pose));
                             if (i > 0) graph->addOdometryEdge((int)i - 1, (int)i, graphPose(d));
@@ -399,6 +425,42 @@ int main(int argc, char** argv) {
     if (!pose_file.empty()) {
         write_tum(pose_file, [&](std::size_t i) { return traj[i]; });
         std::printf("pose updates %lld of %zu frames -> %s\n", n_pose_updates, N > 0 ? N - 1 : 0, pose_file.c_str());
+    }
+    if (!fuse_file.empty()) {                                              // euroc_eval.cpp:139-142, 209
+        if (seq.imu().empty()) { std::fprintf(stderr, "--fuse: the sequence has no mav0/imu0/data.csv\n"); return 1; }
+        std::vector<aria_imu_sample> samples;
+        std::vector<int> imu_end(N);
+        for (std::size_t i = 0; i < N; i++) {
+            for (std::size_t k = seq.imuBegin(i); k < seq.imuEnd(i); k++) {
+                const io::AslImu& m = seq.imu()[k];
+                aria_imu_sample sm{};
+                sm.t = m.timestamp;
+                for (int a = 0; a < 3; a++) { sm.accel[a] = m.accel[a]; sm.gyro[a] = m.gyro[a]; }
+                samples.push_back(sm);
+            }
+            imu_end[i] = (int)samples.size();
+            fuse_visual[i].t = seq.at(i).timestamp;
+            if (!fuse_visual[i].accept) fuse_visual[i].R[0] = fuse_visual[i].R[4] = fuse_visual[i].R[8] = 1.0;
+        }
+        std::vector<aria_fuse_state> states(N);
+        try {
+            adapters::hip::HipSensorFusion fusion;
+            fusion.run(samples.data(), (int)samples.size(), imu_end.data(), fuse_visual.data(), (int)N, states.data());
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "--fuse: %s\n", e.what());
+            return 1;
+        }
+        std::ofstream tf(fuse_file);
+        tf << std::fixed << std::setprecision(9);
+        long long predicted = 0, skipped = 0, ignored = 0, updates = 0;
+        for (std::size_t i = 0; i < N; i++) {
+            const aria_fuse_state& st = states[i];
+            tf << seq.at(i).timestamp << ' ' << st.p[0] << ' ' << st.p[1] << ' ' << st.p[2] << ' ' << st.q[1] << ' ' << st.q[2] << ' '
+               << st.q[3] << ' ' << st.q[0] << '\n';
+            predicted += st.n_predicted; skipped += st.n_skipped; ignored += st.n_ignored; updates += st.n_updates;
+        }
+        std::printf("fused %lld updates | imu samples %zu: %lld predicted %lld skipped %lld before the first pose -> %s\n", updates,
+                    samples.size(), predicted, skipped, ignored, fuse_file.c_str());
     }
     if (graph) {                                                           // euroc_eval.cpp:282-288
         graph->optimize(50);

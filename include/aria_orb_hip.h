@@ -731,6 +731,125 @@ int   aria_graph_debug_linearize(aria_graph_t h, const double* poses, int n_vert
                                  const aria_graph_edge* edges, int n_edges, double* chi2, double* b, double* H_diag,
                                  double* H_off);
 
+/* ---- visual-inertial fusion: the reference's SensorFusion EKF (include/legacy/IMU.hpp:53-118, src/legacy/IMU.cpp:102-305)
+ * and IMUPreintegrator (IMU.hpp:17-51, IMU.cpp:28-100), batched over tracks and over image intervals. Additive to ABI 4.
+ * aria_slam_amd/fusion_ref.py restates both classes in NumPy and is their definition; parity with an Eigen build of the
+ * reference is not pinned by any test (Eigen is not available to this project).
+ *
+ * State. p, v (world), q = (w, x, y, z) body -> world, accelerometer and gyro bias, P 15x15 row-major over the error state
+ *   [p, v, theta, ba, bg]. fp64 throughout.
+ * Events. Frame f of a track first consumes the IMU samples [imu_end[f-1], imu_end[f]) of the track (imu_end[-1] = 0), then
+ *   its visual record when accept != 0 (src/euroc_eval.cpp:139-142, :209), then one aria_fuse_state is written.
+ * IMU sample (addIMU + predictEKF, IMU.cpp:126-222). Ignored while the filter is not initialised. dt = t - last_imu_time;
+ *   dt <= 0 or dt > 0.1 only moves last_imu_time (counted as skipped). Otherwise a = accel - ba, w = gyro - bg, R = R(q)
+ *   of the orientation BEFORE the gyro step; q <- normalize(q * AngleAxis(|w dt|, w dt / |w dt|)) when |w dt| > 1e-10;
+ *   a_w = R a + g; p += v dt + ((0.5 a_w) dt) dt; v += a_w dt; P <- F P F^T + G Q G^T with the reference's F (identity plus
+ *   six 3x3 blocks) and G (five blocks), Q = diag(accel_noise^2, gyro_noise^2, accel_bias_walk^2, gyro_bias_walk^2) x I3;
+ *   P <- 0.5 (P + P^T).
+ * Visual record (addVisualPose + updateEKF, IMU.cpp:224-305). The first accepted record initialises p = p_meas, q = quat(R),
+ *   v = 0, both times = t. Later ones: innovation [p_meas - p, log(normalize(quat(R) * q^-1))], S = P_hh + diag(pos_noise^2 x3,
+ *   rot_noise^2 x3) over the rows / columns h = {0, 1, 2, 6, 7, 8}, K = P_:h S^-1, p, v, ba, bg += K innov,
+ *   q <- normalize(exp(dx_theta) * q), Joseph form, P <- 0.5 (P + P^T), last_visual_time = t.
+ * Ours by definition (Eigen internals written out). quat(R): trace > 0 branch, else the largest diagonal entry (first of
+ *   equals), no sign forced on w. log(q): angle = 2 atan2(|vec|, |w|), axis = vec / |vec|, negated when w < 0, zero vector when
+ *   |vec| = 0: independent of the sign of q. S^-1: Cholesky (lower, no pivoting), applied as two triangular solves; a pivot
+ *   that is not > 0 skips the update (nothing changes but last_visual_time; n_updates stays 0).
+ * Invalid input. A non-finite field of a sample or of a visual record, imu_end decreasing, negative or beyond the track's
+ *   samples, an offset array that decreases or leaves [0, total]: the track is invalid, detected before anything else of it
+ *   is read; its filter is not written, its states are zeroed (valid = 0; not written at all when its frame range itself is
+ *   out of bounds), the other tracks are unaffected, and aria_fuse_check reports ARIA_E_INVALID. For valid input no output is
+ *   ever NaN or Inf.
+ * Determinism. No float atomics. A track's bits depend on its filter record and its events only: reproducible run to run,
+ *   independent of the track's place in a batch, of its neighbours, of the batch split, and of feeding the track in chunks
+ *   through the filter record (the counters of aria_fuse_state are per frame for that reason).
+ * Preintegration (IMUPreintegrator::integrate). Interval i integrates the samples [begin[i], end[i]). The first sample only
+ *   sets the time; dt <= 0 or dt > 0.5 is skipped; a_w = delta_q * a with delta_q BEFORE this sample's rotation, the
+ *   covariance's F and G with delta_q AFTER it; noise 0.01 / 0.001; the 9x9 covariance [p, v, theta] is not symmetrised.
+ *   begin > end, a range outside [0, n_imu] or a non-finite sample: valid = 0, the record zeroed, ARIA_E_INVALID deferred. */
+typedef struct aria_fuse_s* aria_fuse_t;
+typedef struct {
+    double   t;                /* seconds                                                                        */
+    double   accel[3];         /* m/s^2                                                                          */
+    double   gyro[3];          /* rad/s                                                                          */
+} aria_imu_sample;             /* 56 bytes (IMUMeasurement, IMU.hpp:6-10)                                        */
+typedef struct {
+    double   t;
+    double   R[9];             /* row-major                                                                      */
+    double   p[3];
+    int      accept;           /* 0: the frame has no measurement (src/euroc_eval.cpp:191)                       */
+    int      reserved;
+} aria_fuse_visual;            /* 112 bytes                                                                      */
+typedef struct {
+    double   p[3], v[3], q[4], ba[3], bg[3];
+    double   P[225];
+    double   last_imu_time, last_visual_time;      /* -1 before the first event                                 */
+    double   gravity[3];                           /* (0, 0, -9.81), IMU.hpp:105                                */
+    double   accel_noise, gyro_noise, accel_bias_walk, gyro_bias_walk, pos_noise, rot_noise;   /* IMU.hpp:108-113 */
+    int      initialized;
+    int      reserved;
+} aria_fuse_filter;            /* 2024 bytes: everything SensorFusion holds, so a sequence can be fed in chunks   */
+typedef struct {
+    double   t;                /* the frame's visual timestamp                                                   */
+    double   p[3], v[3], q[4], ba[3], bg[3];
+    double   P_diag[15];
+    int      n_predicted;      /* this frame's IMU samples that propagated the state                            */
+    int      n_skipped;        /* ... that only moved last_imu_time (dt <= 0 or dt > 0.1)                        */
+    int      n_ignored;        /* ... that arrived before the filter was initialised                             */
+    int      n_updates;        /* 1 when the frame's visual record updated the filter (the initialising one: 0)   */
+    int      initialized;      /* after the frame                                                                */
+    int      valid;
+} aria_fuse_state;             /* 280 bytes                                                                      */
+typedef struct {
+    double   delta_p[3], delta_v[3], delta_q[4], dt_sum;
+    double   cov[81];          /* row-major 9x9                                                                  */
+    int      n_used;           /* samples that integrated (neither the first nor skipped)                        */
+    int      valid;
+} aria_preint_result;          /* 744 bytes                                                                      */
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_fuse_config)                                                     */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking: not
+                                * ordered against the legacy default stream, see aria_pose_config)               */
+    double   gravity[3];       /* what aria_fuse_filter_init writes into a filter: the reference's defaults       */
+    double   accel_noise, gyro_noise, accel_bias_walk, gyro_bias_walk, pos_noise, rot_noise;
+} aria_fuse_config;            /* 88 bytes                                                                       */
+
+void  aria_fuse_default_config(aria_fuse_config* cfg);
+int   aria_fuse_create(const aria_fuse_config* cfg, aria_fuse_t* out);
+void  aria_fuse_destroy(aria_fuse_t h);
+void* aria_fuse_stream(aria_fuse_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when some track or interval was invalid (above). */
+int   aria_fuse_check(aria_fuse_t h);
+/* SensorFusion's constructor (IMU.cpp:104-124) and member defaults (IMU.hpp:87-117): zero state, identity orientation,
+ * P0 = diag(0.01 x9, 0.001 x3, 0.0001 x3), times -1, not initialised; gravity and noise from cfg (NULL: the defaults).
+ * Host only. */
+int   aria_fuse_filter_init(aria_fuse_filter* filter, const aria_fuse_config* cfg);
+/* Device-resident batch: track k owns the samples d_imu_offset[k] .. d_imu_offset[k+1] of d_imu and the frames
+ * d_frame_offset[k] .. d_frame_offset[k+1] of d_imu_end, d_visual and d_states; both offset arrays hold n_tracks + 1 entries
+ * and must stay within [0, n_imu_total] and [0, n_frames_total]. d_imu_end is relative to the track's first sample.
+ * d_filters_inout[k] is read at the start and written at the end, so a sequence may be fed in chunks. Enqueued on the
+ * handle's stream, one launch, no synchronisation. Data errors: aria_fuse_check. */
+int   aria_fuse_run_batch_device(aria_fuse_t h, aria_fuse_filter* d_filters_inout, const aria_imu_sample* d_imu,
+                                 const int* d_imu_offset, int n_imu_total, const int* d_imu_end, const aria_fuse_visual* d_visual,
+                                 const int* d_frame_offset, int n_frames_total, int n_tracks, aria_fuse_state* d_states);
+/* One track, host arrays; blocks. Invalid input: ARIA_E_INVALID, the filter untouched, the states zeroed. */
+int   aria_fuse_run(aria_fuse_t h, aria_fuse_filter* filter_inout, const aria_imu_sample* imu, int n_imu, const int* imu_end,
+                    const aria_fuse_visual* visual, int n_frames, aria_fuse_state* states);
+/* Measurements from what aria_pose_estimate_batch_device leaves in HBM, without a host round trip: t = d_timestamps[i],
+ * R, p = the result's R, t, accept = valid && n_pose_inliers > min_pose_inliers (src/euroc_eval.cpp:191). This is the
+ * RELATIVE pose with unit-length t, which is what euroc_eval.cpp:209 hands the filter. Enqueued on the handle's stream. */
+int   aria_fuse_visual_from_pose_device(aria_fuse_t h, const aria_pose_result* d_pose_results, const double* d_timestamps, int n,
+                                        int min_pose_inliers, aria_fuse_visual* d_visual);
+/* Preintegration of n_intervals intervals [d_begin[i], d_end[i]) of d_imu (n_imu samples). d_bias: 6 doubles (accelerometer,
+ * gyro bias; IMUPreintegrator::setBias) shared by the call, or NULL = zero. Enqueued on the handle's stream. */
+int   aria_fuse_preintegrate_batch_device(aria_fuse_t h, const aria_imu_sample* d_imu, int n_imu, const int* d_begin,
+                                          const int* d_end, int n_intervals, const double* d_bias_or_null,
+                                          aria_preint_result* d_out);
+/* The same over host arrays; blocks. */
+int   aria_fuse_preintegrate(aria_fuse_t h, const aria_imu_sample* imu, int n_imu, const int* begin, const int* end,
+                             int n_intervals, const double* bias_or_null, aria_preint_result* out);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
