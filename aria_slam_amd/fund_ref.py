@@ -49,8 +49,10 @@ def sample_indices(seed, pair, hypotheses, n):
 
 
 def collinear(x, y):
-    """haveCollinearPoints on (H, 7) coordinates: slot 6 against every pair of slots 0..5 (fp64)."""
-    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    """haveCollinearPoints on (H, 7) coordinates: slot 6 against every pair of slots 0..5 (fp64, or the type given)."""
+    x, y = np.asarray(x), np.asarray(y)
+    if x.dtype != np.longdouble:
+        x, y = x.astype(np.float64), y.astype(np.float64)
     col = np.zeros(x.shape[0], bool)
     for j in range(1, 6):
         dx1, dy1 = x[:, j] - x[:, 6], y[:, j] - y[:, 6]
@@ -62,29 +64,35 @@ def collinear(x, y):
 
 def _normalisation(x, y):
     """run7Point's per-sample transform: centroid (mx, my) and scale sqrt(2) / mean distance; ok = mean >= FLT_EPSILON."""
-    t = 1.0 / 7.0
-    mx, my = np.zeros(x.shape[0]), np.zeros(x.shape[0])
+    t = x.dtype.type(1.0) / x.dtype.type(7.0)
+    mx, my = np.zeros(x.shape[0], x.dtype), np.zeros(x.shape[0], x.dtype)
     for i in range(7):
         mx = mx + x[:, i]
         my = my + y[:, i]
     mx, my = mx * t, my * t
-    s = np.zeros(x.shape[0])
+    s = np.zeros(x.shape[0], x.dtype)
     for i in range(7):
         a, b = x[:, i] - mx, y[:, i] - my
         s = s + np.sqrt(a * a + b * b)
     s = s * t
     ok = s >= FLT_EPS
-    return mx, my, np.sqrt(2.0) / np.where(ok, s, 1.0), ok
+    return mx, my, np.sqrt(x.dtype.type(2.0)) / np.where(ok, s, 1.0), ok
 
 
 def _rows(x1, y1, x2, y2):
     return np.stack([x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, np.ones_like(x1)], axis=-1)
 
 
+def _wide(a):
+    """fp64, unless the array already is np.longdouble (the extended run of solve7)."""
+    a = np.asarray(a)
+    return a if a.dtype == np.longdouble else a.astype(np.float64)
+
+
 def cubic_coefficients(f1, f2):
     """run7Point's expansion of det(l f1 + f2) = c0 l^3 + c1 l^2 + c2 l + c3 for (H, 9) f1, f2. Returns (H, 4)."""
-    f1 = [np.asarray(f1, np.float64)[:, i] for i in range(9)]
-    f2 = [np.asarray(f2, np.float64)[:, i] for i in range(9)]
+    f1 = [_wide(f1)[:, i] for i in range(9)]
+    f2 = [_wide(f2)[:, i] for i in range(9)]
     t0 = f2[4] * f2[8] - f2[5] * f2[7]
     t1 = f2[3] * f2[8] - f2[5] * f2[6]
     t2 = f2[3] * f2[7] - f2[4] * f2[6]
@@ -108,22 +116,24 @@ def cubic_roots(c):
     """Real roots of c0 l^3 + c1 l^2 + c2 l + c3 (rows of (H, 4)), closed form as the device computes them: the
     trigonometric form when Q^3 - R^2 > 0 (three roots, ascending), Cardano otherwise (one). Returns (roots (H, 3), n (H,));
     n = 0 where |c0| <= 1e-12 max|c_i|."""
-    c = np.asarray(c, np.float64)
+    c = _wide(c)
+    T = c.dtype.type
+    two_pi_3 = TWO_PI_3 if T is np.float64 else T(2) * np.arccos(T(-1)) / T(3)
     c0, c1, c2, c3 = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
     ok = np.abs(c0) > CUBIC_TOL * np.abs(c).max(axis=1)
     with np.errstate(all="ignore"):
         d0 = np.where(ok, c0, 1.0)
         a1, a2, a3 = c1 / d0, c2 / d0, c3 / d0
-        Q = (a1 * a1 - 3.0 * a2) * (1.0 / 9.0)
-        R = (a1 * (2.0 * a1 * a1 - 9.0 * a2) + 27.0 * a3) * (1.0 / 54.0)
-        disc = (a1 * a1 * (a2 * a2 - 4.0 * a1 * a3) + 2.0 * a2 * (9.0 * a1 * a3 - 2.0 * a2 * a2) - 27.0 * a3 * a3) * (1.0 / 108.0)
+        Q = (a1 * a1 - 3.0 * a2) * (T(1) / T(9))
+        R = (a1 * (2.0 * a1 * a1 - 9.0 * a2) + 27.0 * a3) * (T(1) / T(54))
+        disc = (a1 * a1 * (a2 * a2 - 4.0 * a1 * a3) + 2.0 * a2 * (9.0 * a1 * a3 - 2.0 * a2 * a2) - 27.0 * a3 * a3) * (T(1) / T(108))
         three = disc > 0.0
         theta = np.arccos(np.clip(R / np.sqrt(np.where(three, Q * Q * Q, 1.0)), -1.0, 1.0))
-        sq, th, sh = -2.0 * np.sqrt(np.where(three, Q, 0.0)), theta * (1.0 / 3.0), a1 * (1.0 / 3.0)
-        r3 = np.sort(np.stack([sq * np.cos(th) - sh, sq * np.cos(th + TWO_PI_3) - sh, sq * np.cos(th - TWO_PI_3) - sh], 1), 1)
+        sq, th, sh = -2.0 * np.sqrt(np.where(three, Q, 0.0)), theta * (T(1) / T(3)), a1 * (T(1) / T(3))
+        r3 = np.sort(np.stack([sq * np.cos(th) - sh, sq * np.cos(th + two_pi_3) - sh, sq * np.cos(th - two_pi_3) - sh], 1), 1)
         e = np.cbrt(np.sqrt(np.where(three, 0.0, -disc)) + np.abs(R))
         e = np.where(R > 0.0, -e, e)
-        r1 = (e + Q / e) - a1 * (1.0 / 3.0)
+        r1 = (e + Q / e) - a1 * (T(1) / T(3))
     roots = np.where(three[:, None], r3, np.stack([r1, np.zeros_like(r1), np.zeros_like(r1)], 1))
     n = np.where(ok, np.where(three, 3, 1), 0)
     roots[n == 0] = 0.0
@@ -133,23 +143,24 @@ def cubic_roots(c):
 def _models(f1, f2, roots, nroots, mx1, my1, s1, mx2, my2, s2):
     """run7Point's per-root model, de-normalised and scaled to F[8] = 1: (H, 3, 9), zero for k >= nroots."""
     H = f1.shape[0]
-    F = np.zeros((H, 3, 9))
+    dt = f1.dtype
+    F = np.zeros((H, 3, 9), dt)
     T1x, T1y, T2x, T2y = -s1 * mx1, -s1 * my1, -s2 * mx2, -s2 * my2
     with np.errstate(all="ignore"):
         for k in range(3):
-            lam, mu = roots[:, k].copy(), np.ones(H)
+            lam, mu = roots[:, k].copy(), np.ones(H, dt)
             s = f1[:, 8] * lam + f2[:, 8]
             big = np.abs(s) > DBL_EPS
             mu = np.where(big, 1.0 / np.where(big, s, 1.0), mu)
             lam = np.where(big, lam * mu, lam)
             Fn = f1 * lam[:, None] + f2 * mu[:, None]
             Fn[:, 8] = np.where(big, 1.0, 0.0)
-            M = np.empty((H, 9))
+            M = np.empty((H, 9), dt)
             for j in range(3):
                 M[:, j] = s2 * Fn[:, j]
                 M[:, 3 + j] = s2 * Fn[:, 3 + j]
                 M[:, 6 + j] = (T2x * Fn[:, j] + T2y * Fn[:, 3 + j]) + Fn[:, 6 + j]
-            G = np.empty((H, 9))
+            G = np.empty((H, 9), dt)
             for i in range(3):
                 G[:, 3 * i] = M[:, 3 * i] * s1
                 G[:, 3 * i + 1] = M[:, 3 * i + 1] * s1
@@ -161,11 +172,12 @@ def _models(f1, f2, roots, nroots, mx1, my1, s1, mx2, my2, s2):
     return F
 
 
-def solve7(samples, basis="elimination"):
-    """run7Point on (H, 7, 4) pixel samples (fp32 values, fp64 arithmetic). Returns (F (H, 3, 9), n_models (H,)).
+def solve7(samples, basis="elimination", dtype=np.float64):
+    """run7Point on (H, 7, 4) pixel samples (fp32 values, fp64 arithmetic; dtype=np.longdouble is the extended run that the
+    GPU tests measure the fp64 one against: every step is array arithmetic). Returns (F (H, 3, 9), n_models (H,)).
     basis="svd" takes the null space from the SVD as OpenCV does (f1, f2 = the last two right singular vectors) instead of
     the elimination basis -- the test of basis independence."""
-    p = np.asarray(samples, np.float64)
+    p = np.asarray(samples, dtype)
     H = p.shape[0]
     x1, y1, x2, y2 = p[..., 0], p[..., 1], p[..., 2], p[..., 3]
     ok = ~collinear(x1, y1) & ~collinear(x2, y2)
@@ -191,12 +203,12 @@ def solve7(samples, basis="elimination"):
             inv = 1.0 / np.where(ok, A[:, c, c], 1.0)
             f = A[:, c + 1:, c] * inv[:, None]
             A[:, c + 1:, c + 1:] = A[:, c + 1:, c + 1:] - f[:, :, None] * A[:, c, None, c + 1:]
-        g1, g2 = np.zeros((H, 9)), np.zeros((H, 9))
+        g1, g2 = np.zeros((H, 9), dtype), np.zeros((H, 9), dtype)
         g1[:, 7], g2[:, 8] = 1.0, 1.0
         piv = np.where(ok[:, None], A[:, np.arange(7), np.arange(7)], 1.0)
         with np.errstate(all="ignore"):
             for c in range(6, -1, -1):
-                u, v = np.zeros(H), np.zeros(H)
+                u, v = np.zeros(H, dtype), np.zeros(H, dtype)
                 for k in range(c + 1, 9):
                     u = u + A[:, c, k] * g1[:, k]
                     v = v + A[:, c, k] * g2[:, k]
@@ -260,14 +272,15 @@ def hypotheses(pts, seed=0, pair=0, n_hyp=1024, threshold_px=3.0):
     return idx, nm, F, counts
 
 
-def estimate_points(pts, seed=0, pair=0, n_hyp=1024, threshold_px=3.0):
-    """The whole stage on (n, 4) pixel pairs: a dict with the fields of aria_fund_result and the mask."""
+def estimate_points(pts, seed=0, pair=0, n_hyp=1024, threshold_px=3.0, hyp=None):
+    """The whole stage on (n, 4) pixel pairs: a dict with the fields of aria_fund_result and the mask. hyp: hypotheses()'s
+    result for these arguments, if the caller has it already."""
     n = len(pts)
     res = dict(F=np.zeros((3, 3)), n_matches=n, n_inliers=0, n_models=0, best_hypothesis=-1, best_root=-1, valid=0,
                mask=np.zeros(n, np.uint8))
     if n < MIN_MATCHES:
         return res
-    _idx, nm, F, counts = hypotheses(pts, seed, pair, n_hyp, threshold_px)
+    _idx, nm, F, counts = hyp if hyp is not None else hypotheses(pts, seed, pair, n_hyp, threshold_px)
     flat = counts.reshape(-1)
     best = int(np.argmax(flat))              # first maximum: ties to the lowest h, then k
     if flat[best] < MIN_INLIERS:

@@ -4,6 +4,9 @@ kernels in aria_slam_amd/csrc/pose_ransac.hip): the same sample hash, minimal so
 Tests hold the device to it, and it serves as a CPU fallback for callers without a GPU. Where the device and this module
 use different but equivalent numerics (3x3 / 9x9 eigen-solvers: Jacobi there, LAPACK here; Sampson test in fp32 there,
 fp64 here) results agree to rounding; inlier decisions can differ only for points within rounding of the threshold.
+
+estimate(dtype=np.longdouble) is the yardstick that rounding is measured against (tools/pose_gap.py, tests/test_gpu_pose.py):
+the refit, the decomposition and the depths in extended precision through jacobi_eigh, since LAPACK stops at fp64.
 """
 import numpy as np
 
@@ -190,8 +193,68 @@ def hypotheses(pts, seed=0, pair=0, n_hyp=1024, threshold_px=1.0, K=EUROC_K):
     return idx, E, counts
 
 
-def decompose_essential(E):
-    """cv::decomposeEssentialMat: [(R1, t), (R2, t), (R1, -t), (R2, -t)]."""
+def jacobi_eigh(M, dtype=np.longdouble, sweeps=40):
+    """Cyclic Jacobi on a symmetric matrix, array arithmetic only, so it runs in np.longdouble where LAPACK does not.
+    Returns (eigenvalues ascending, eigenvectors in columns). The rotation is the device's (jacobi_rotate)."""
+    A = np.array(M, dtype=dtype)
+    N = A.shape[0]
+    V = np.eye(N, dtype=dtype)
+    tiny = np.finfo(dtype).eps * dtype(1e-3)
+    one, two = dtype(1), dtype(2)
+    with np.errstate(all="ignore"):
+        for _sweep in range(sweeps):
+            d = np.abs(np.diag(A)).sum()
+            if np.abs(A).sum() - d <= tiny * d:
+                break
+            for p in range(N - 1):
+                for q in range(p + 1, N):
+                    apq = A[p, q]
+                    if apq == 0:
+                        continue
+                    theta = (A[q, q] - A[p, p]) / (two * apq)
+                    t = (one if theta >= 0 else -one) / (np.abs(theta) + np.sqrt(theta * theta + one))
+                    c = one / np.sqrt(t * t + one)
+                    s = t * c
+                    ap, aq = A[:, p].copy(), A[:, q].copy()
+                    A[:, p], A[:, q] = c * ap - s * aq, s * ap + c * aq
+                    ap, aq = A[p, :].copy(), A[q, :].copy()
+                    A[p, :], A[q, :] = c * ap - s * aq, s * ap + c * aq
+                    A[p, q] = A[q, p] = 0
+                    vp, vq = V[:, p].copy(), V[:, q].copy()
+                    V[:, p], V[:, q] = c * vp - s * vq, s * vp + c * vq
+    w = np.diag(A).copy()
+    order = np.argsort(w, kind="stable")
+    return w[order], V[:, order]
+
+
+def project_essential_jacobi(f, dtype=np.longdouble):
+    """project_essential as the device computes it, in `dtype`: v_i from the Jacobi eigenvectors of E^T E, u_i = E v_i /
+    sigma_i, third columns as cross products. Returns (E (9,), ok, U (3, 3), V (3, 3)), U and V right-handed, in columns."""
+    E = np.asarray(f, dtype).reshape(3, 3)
+    w, Vv = jacobi_eigh(E.T @ E, dtype)
+    zero = dtype(0)
+    s0, s1 = np.sqrt(max(w[2], zero)), np.sqrt(max(w[1], zero))
+    if not s1 > dtype(RANK_TOL) * s0:
+        return np.zeros(9, dtype), False, np.eye(3, dtype=dtype), np.eye(3, dtype=dtype)
+    v1, v2 = Vv[:, 2], Vv[:, 1]
+    u1, u2 = E @ v1 / s0, E @ v2 / s1
+    out = (np.outer(u1, v1) + np.outer(u2, v2)) / np.sqrt(dtype(2))
+    U = np.stack([u1, u2, np.cross(u1, u2)], axis=1)
+    V = np.stack([v1, v2, np.cross(v1, v2)], axis=1)
+    return out.reshape(9), True, U, V
+
+
+def decompose_essential(E, dtype=None):
+    """cv::decomposeEssentialMat: [(R1, t), (R2, t), (R1, -t), (R2, -t)]. dtype=None: LAPACK's SVD in fp64; otherwise the
+    Jacobi path in `dtype` (identity and zero for a rank-1 E, as on the device). The two paths may order the four
+    candidates differently: both SVDs are valid."""
+    if dtype is not None:
+        _e, ok, U, V = project_essential_jacobi(E, dtype)
+        if not ok:
+            return [(np.eye(3, dtype=dtype), np.zeros(3, dtype))] * 4
+        W = np.array([[0.0, 1, 0], [-1, 0, 0], [0, 0, 1]], dtype)
+        R1, R2, t = U @ W @ V.T, U @ W.T @ V.T, U[:, 2].copy()
+        return [(R1, t), (R2, t), (R1, -t), (R2, -t)]
     U, _s, Vt = np.linalg.svd(np.asarray(E, np.float64).reshape(3, 3))
     if np.linalg.det(U) < 0:
         U = -U
@@ -202,29 +265,43 @@ def decompose_essential(E):
     return [(R1, t), (R2, t), (R1, -t), (R2, -t)]
 
 
-def cheirality(R, t, pts, dist=50.0):
-    """(n,) bool: least-squares depths (z1, z2) of z2 x2 = z1 R x1 + t both in (0, dist)."""
-    p = np.asarray(pts, np.float64)
-    x1 = np.stack([p[:, 0], p[:, 1], np.ones(len(p))], axis=1)
-    x2 = np.stack([p[:, 2], p[:, 3], np.ones(len(p))], axis=1)
-    a = x1 @ np.asarray(R).T
+def depths(R, t, pts, dtype=np.float64):
+    """(det, z1, z2) per point: the least-squares depths of z2 x2 = z1 R x1 + t and the determinant they divide by."""
+    p = np.asarray(pts, dtype)
+    x1 = np.stack([p[:, 0], p[:, 1], np.ones(len(p), dtype)], axis=1)
+    x2 = np.stack([p[:, 2], p[:, 3], np.ones(len(p), dtype)], axis=1)
+    a = x1 @ np.asarray(R, dtype).T
+    t = np.asarray(t, dtype)
     aa, bb, ab = (a * a).sum(1), (x2 * x2).sum(1), (a * x2).sum(1)
     at, bt = a @ t, x2 @ t
     det = aa * bb - ab * ab
     with np.errstate(all="ignore"):
         z1 = (ab * bt - at * bb) / det
         z2 = (aa * bt - ab * at) / det
+    return det, z1, z2
+
+
+def cheirality(R, t, pts, dist=50.0, dtype=np.float64):
+    """(n,) bool: least-squares depths (z1, z2) of z2 x2 = z1 R x1 + t both in (0, dist)."""
+    det, z1, z2 = depths(R, t, pts, dtype)
     return (det > 0) & (z1 > 0) & (z1 < dist) & (z2 > 0) & (z2 < dist)
 
 
-def estimate_points(pts, seed=0, pair=0, n_hyp=1024, threshold_px=1.0, distance_thresh=50.0, K=EUROC_K):
-    """The whole stage on (n, 4) normalised point pairs. Returns a dict with the fields of aria_pose_result and the mask."""
+def estimate_points(pts, seed=0, pair=0, n_hyp=1024, threshold_px=1.0, distance_thresh=50.0, K=EUROC_K, dtype=None, hyp=None):
+    """The whole stage on (n, 4) normalised point pairs. Returns a dict with the fields of aria_pose_result and the mask,
+    plus what the tests need to judge a case: `candidate` (the index chosen among decompose_essential's four), `good`
+    (their cheirality counts), `winner_E` (the winning hypothesis's fp32 E), `refit_E` (the refitted E whether or not it
+    was taken; None without a refit) and `n_winner` / `n_refit` (the two inlier counts that decide `refined`). hyp: hypotheses()'s result for these arguments,
+    if the caller has it already. dtype=None: the refit and the decomposition through LAPACK in fp64. With a dtype
+    (np.longdouble: the yardstick of the GPU tests) they run through jacobi_eigh in that type, as do the normal matrix and
+    the depths; the hypotheses and every inlier test are the same in both."""
     n = len(pts)
     res = dict(R=np.eye(3), t=np.zeros(3), E=np.zeros((3, 3)), n_matches=n, n_inliers=0, n_pose_inliers=0,
-               best_hypothesis=-1, refined=0, valid=0, mask=np.zeros(n, np.uint8))
+               best_hypothesis=-1, refined=0, valid=0, mask=np.zeros(n, np.uint8), candidate=-1, good=[0, 0, 0, 0],
+               winner_E=np.zeros(9), refit_E=None, n_winner=0, n_refit=0)
     if n < 8:
         return res
-    _idx, E, counts = hypotheses(pts, seed, pair, n_hyp, threshold_px, K)
+    _idx, E, counts = hyp if hyp is not None else hypotheses(pts, seed, pair, n_hyp, threshold_px, K)
     best = int(np.argmax(counts))            # first maximum: ties to the lowest h
     if counts[best] < 0:
         return res
@@ -232,31 +309,40 @@ def estimate_points(pts, seed=0, pair=0, n_hyp=1024, threshold_px=1.0, distance_
     Ew = E[best].astype(np.float32).astype(np.float64)
     inl = sampson_inliers(Ew, pts, thr2)[0]
     final_E, final_inl, refined = Ew, inl, 0
+    refit_E, n_refit = None, 0
     if inl.sum() >= 8:
         A = design_rows(np.asarray(pts)[inl])
-        M = A.T @ A
-        _w, V = np.linalg.eigh(M)
-        Er, ok = project_essential(V[:, 0])
+        if dtype is None:
+            M = A.T @ A
+            _w, V = np.linalg.eigh(M)
+            Er, ok = project_essential(V[:, 0])
+        else:
+            A = A.astype(dtype)                      # products of two fp32 values: exact in fp64
+            _w, V = jacobi_eigh(A.T @ A, dtype)
+            Er, ok, _U, _V = project_essential_jacobi(V[:, 0], dtype)
+            Er, ok = Er[None, :], [ok]
         if ok[0]:
             inl_r = sampson_inliers(Er[0].astype(np.float32), pts, thr2)[0]
+            refit_E, n_refit = Er[0], int(inl_r.sum())
             if inl_r.sum() >= inl.sum():
                 final_E, final_inl, refined = Er[0], inl_r, 1
-    cands = decompose_essential(final_E)
-    masks = [cheirality(R, t, np.asarray(pts)[final_inl], distance_thresh) for R, t in cands]
+    cands = decompose_essential(final_E, dtype)
+    masks = [cheirality(R, t, np.asarray(pts)[final_inl], distance_thresh, dtype or np.float64) for R, t in cands]
     g = [int(m.sum()) for m in masks]
     c = 0 if (g[0] >= g[1] and g[0] >= g[2] and g[0] >= g[3]) else 1 if (g[1] >= g[2] and g[1] >= g[3]) else 2 if g[2] >= g[3] else 3
     mask = np.zeros(n, np.uint8)
     mask[np.flatnonzero(final_inl)[masks[c]]] = 1
     res.update(R=cands[c][0], t=cands[c][1], E=np.asarray(final_E).reshape(3, 3), n_inliers=int(final_inl.sum()),
-               n_pose_inliers=g[c], best_hypothesis=best, refined=refined, valid=1, mask=mask)
+               n_pose_inliers=g[c], best_hypothesis=best, refined=refined, valid=1, mask=mask, candidate=c, good=g,
+               winner_E=Ew.reshape(9), refit_E=refit_E, n_winner=int(inl.sum()), n_refit=n_refit)
     return res
 
 
 def estimate(kp_query, kp_train, matches, query_is_first=True, seed=0, pair=0, n_hyp=1024, threshold_px=1.0,
-             distance_thresh=50.0, K=EUROC_K):
+             distance_thresh=50.0, K=EUROC_K, dtype=None):
     """aria_pose_estimate on the CPU."""
     pts = normalise(kp_query, kp_train, matches, query_is_first, K)
-    return estimate_points(pts, seed, pair, n_hyp, threshold_px, distance_thresh, K)
+    return estimate_points(pts, seed, pair, n_hyp, threshold_px, distance_thresh, K, dtype)
 
 
 def rotation_error_deg(R1, R2):

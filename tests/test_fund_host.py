@@ -255,3 +255,62 @@ def test_host_adapters_build_with_the_reference_verifier(aria):
     assert "aria::adapters::hip::makeReferenceVerifier" in syms
     usage = subprocess.run([os.path.join(pkg, "euroc_frontend")], capture_output=True, text=True)
     assert "--loop-verify" in usage.stderr
+
+
+# ---- the case table of the GPU tests (tests/ransac_cases.py): what it covers, proven with the restatement alone ------------
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ransac_cases as RC   # noqa: E402
+
+
+@pytest.mark.parametrize("case", RC.FUND_CASES + RC.FUND_BATCH, ids=RC.case_id)
+def test_table_case_can_be_decided(case):
+    """Conditions on the inputs, not measurements: a case that violates one is replaced, the condition stays."""
+    from aria_slam_amd import fund_ref as F
+    rep = RC.fund_report(case)
+    assert rep["unambiguous"]                                   # no other model within the in-band points of the winner
+    assert rep["in_band"] <= RC.in_band_limit(case.n)
+    if rep["ref"]["valid"]:
+        assert rep["F_ext"] is not None                         # the extended solve finds the same number of roots
+        assert rep["ref"]["n_inliers"] >= F.MIN_INLIERS
+
+
+def test_table_covers_the_finish_kernel():
+    from aria_slam_amd import fund_ref as F
+    cases = RC.FUND_CASES
+    reps = [RC.fund_report(c) for c in cases]
+    assert {15, 16, 40, 150, 300, 600, 2047, 2048, 2049, 4096} <= {c.n for c in cases}
+    assert {64, 320, 1024, 4096} <= {c.H for c in cases}
+    assert {0, 3, RC.HIGH_SEED} <= {c.seed for c in cases} and {0, 5, 1000000} <= {c.pair_base for c in cases}
+    assert {1.0, 3.0} <= {c.threshold_px for c in cases} and {True, False} <= {c.query_is_first for c in cases}
+    valid = [r for r in reps if r["ref"]["valid"]]
+    assert {r["ref"]["best_root"] for r in valid} == {0, 1, 2}
+    assert any(not r["ref"]["valid"] and r["case"].n >= F.MIN_MATCHES for r in reps)     # fails MIN_INLIERS
+    assert sum(r["exact"] for r in reps) >= 0.8 * len(reps) and not all(r["exact"] for r in reps)
+    # tie scenes: the true F takes all n wherever it is among a sample's roots; the winner is the lowest (h, root) of them
+    ties = [r for r in valid if r["case"].noise_px == 0.0 and 0 < r["case"].copies < 1]
+    winners = sorted(r["ref"]["best_hypothesis"] for r in ties)
+    assert winners[0] >= 1 and winners[-1] >= 256
+    for r in ties:
+        c = r["case"]
+        _idx, _nm, _F, counts = F.hypotheses(r["pts"], c.seed, c.pair_base, c.H, c.threshold_px)
+        flat = counts.reshape(-1)
+        best = 3 * r["ref"]["best_hypothesis"] + r["ref"]["best_root"]
+        assert flat.max() == c.n == r["ref"]["n_inliers"]
+        assert (flat[best + 1:] == c.n).sum() >= 1 and (flat[:best] < c.n).all()
+
+
+def test_solve7_extended_run_follows_the_fp64_run():
+    """The np.longdouble run of solve7 (the yardstick of the device's F) takes the fp64 run's decisions and lands on its
+    models wherever the sample is well conditioned."""
+    from aria_slam_amd import fund_ref as F
+    rep = RC.fund_report(RC.FUND_CASES[8])
+    c = rep["case"]
+    idx = F.sample_indices(c.seed, c.pair_base, 256, c.n)
+    a, na = F.solve7(rep["pts"][idx])
+    b, nb = F.solve7(rep["pts"][idx], dtype=np.longdouble)
+    assert b.dtype == np.longdouble and (na == nb).mean() > 0.99
+    same = na == nb
+    sc = np.abs(b[same]).max(axis=2, keepdims=True)
+    sc[sc == 0] = 1
+    d = np.abs(a[same] / sc - b[same] / sc).max(axis=(1, 2)).astype(np.float64)
+    assert np.median(d) < 1e-14

@@ -1,11 +1,16 @@
 """Two-view relative pose on the MI355X (aria_pose_*, kernels in aria_slam_amd/csrc/pose_ransac.hip): hypotheses against the
-NumPy restatement, ground-truth accuracy, batch == single and determinism, edge cases, the device chain extract -> match ->
-pose, and the C++ adapters."""
+NumPy restatement, the whole stage against it over the case table of tests/ransac_cases.py, ground-truth accuracy,
+batch == single and determinism, edge cases, the device chain extract -> match -> pose, and the C++ adapters."""
 import os
 import subprocess
 
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ransac_cases as RC   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -269,3 +274,190 @@ def test_cpp_pose_selftest(aria):
     assert kv["verifier_accept"][0] == "1" and kv["verifier_accept"][1] == kv["verifier_accept"][2]   # matches cut to inliers
     assert float(kv["verifier_accept"][3]) < 0.5               # relative_pose rotation = the scene's
     assert kv["frontend"][0] == "1" and kv["frontend"][1] == "1" and kv["frontend"][2] == "0"   # pose on frame 1, none on frame 0, off by default
+
+
+# ---- the whole stage against pose_ref.estimate over the case table (tests/ransac_cases.py) -------------------------------
+# GAP, measured on the CPU with the committed restatement (tools/pose_gap.py prints these tables): per exact-set case, the
+# largest difference of E (unit norm, sign-aligned), R and t between pose_ref's fp64 run (LAPACK) and its np.longdouble run
+# (jacobi_eigh for the refit's 9x9 and the decomposition's 3x3). E's gap is 0 where the refit is not taken: E is then the
+# winning hypothesis's fp32 E, the same numbers in both runs.
+POSE_GAP = {    # case: (E, R, t)
+     0: (2.16e-13, 2.14e-14, 3.06e-13),   # s72-n8-H64
+     1: (9.04e-14, 5.07e-14, 1.26e-13),   # s70-n9-H64
+     2: (0.00e+00, 2.15e-16, 1.88e-16),   # s15-n9-H1024
+     3: (1.89e-13, 2.66e-14, 2.74e-13),   # s19-n40-H320
+     4: (3.17e-14, 1.85e-14, 4.47e-14),   # s20-n40-H64
+     5: (0.00e+00, 4.55e-16, 1.22e-16),   # s21-n40-H320
+     6: (0.00e+00, 6.01e-16, 1.63e-16),   # s22-n150-H320
+     7: (0.00e+00, 3.93e-16, 1.46e-16),   # s25-n150-H1024
+     8: (3.28e-14, 3.90e-15, 4.30e-14),   # s27-n300-H320
+     9: (7.67e-14, 1.22e-14, 1.00e-13),   # s28-n300-H1024
+    10: (0.00e+00, 2.32e-16, 8.86e-17),   # s29-n300-H320
+    11: (1.10e-13, 6.72e-15, 1.56e-13),   # s30-n600-H320
+    12: (5.53e-14, 1.39e-14, 7.83e-14),   # s32-n600-H320
+    13: (2.95e-14, 2.67e-15, 4.17e-14),   # s33-n600-H64
+    14: (1.68e-13, 2.55e-14, 2.37e-13),   # s35-n2047-H320
+    15: (2.17e-14, 1.90e-14, 1.66e-14),   # s34-n2047-H64
+    16: (4.28e-14, 1.01e-15, 5.95e-14),   # s37-n2047-H320
+    17: (5.93e-14, 2.19e-14, 5.63e-14),   # s38-n2048-H320
+    18: (1.31e-13, 1.96e-14, 1.88e-13),   # s41-n2048-H64
+    19: (4.36e-15, 8.19e-16, 6.16e-15),   # s42-n2049-H64
+    20: (1.12e-14, 9.70e-16, 1.48e-14),   # s46-n4096-H320
+    21: (1.23e-13, 1.91e-14, 1.41e-13),   # s50-n300-H4096
+    23: (3.26e-14, 7.19e-15, 4.16e-14),   # s60-n150-H1024
+    24: (2.88e-13, 4.98e-14, 3.26e-13),   # s60-n150-H1024
+}
+POSE_BATCH_GAP = {    # case: (E, R, t)
+     0: (2.77e-14, 3.75e-15, 3.54e-14),   # s200-n300-H320
+     2: (3.09e-15, 8.58e-16, 4.01e-15),   # s208-n2047-H320
+     4: (8.58e-14, 1.25e-14, 1.09e-13),   # s216-n2048-H320
+     5: (0.00e+00, 2.45e-16, 1.48e-16),   # s217-n8-H320
+     6: (1.01e-13, 1.91e-14, 1.33e-13),   # s218-n2049-H320
+     7: (1.04e-13, 2.76e-14, 1.09e-13),   # s221-n40-H320
+     8: (1.06e-14, 1.36e-15, 1.39e-14),   # s224-n600-H320
+    10: (2.11e-13, 2.60e-14, 2.94e-13),   # s230-n150-H320
+}
+
+
+def _compare_pose(r, rep, gap, label):
+    """One device result against the restatement's report of the case (tests/ransac_cases.py). Exact-set cases: every
+    discrete field and the mask equal, E (up to sign), R and t within 10 * GAP of the extended run. Other cases: the
+    winner equal, the counts within the in-band and near-cheirality points, the mask different only at those points."""
+    c, ref, ext = rep["case"], rep["ref"], rep["ext"]
+    assert r["n_matches"] == c.n, label
+    if rep["exact"]:
+        for k in ("valid", "best_hypothesis", "refined", "n_inliers", "n_pose_inliers"):
+            assert r[k] == ref[k], (label, k, r[k], ref[k])
+        assert r["mask"].tobytes() == ref["mask"].tobytes(), label
+        if not ref["valid"]:
+            assert np.array_equal(r["R"], np.eye(3)) and not r["t"].any() and not r["E"].any(), label
+            return
+        dE = RC.e_diff(r["E"], ext["E"])
+        dR, dt = RC.rt_diff(r["R"], r["t"], ext)            # the chosen pose as values, not its index among the four
+        print("%s: E %.2e (allowed %.2e)  R %.2e (allowed %.2e)  t %.2e (allowed %.2e)" %
+              (label, dE, 10 * gap[0], dR, 10 * gap[1], dt, 10 * gap[2]))
+        assert dE <= 10 * gap[0] and dR <= 10 * gap[1] and dt <= 10 * gap[2], label
+        return
+    soft = rep["in_band"] + rep["near"]
+    assert r["valid"] == ref["valid"] == 1 and r["best_hypothesis"] == ref["best_hypothesis"], label
+    assert abs(r["n_inliers"] - ref["n_inliers"]) <= soft and abs(r["n_pose_inliers"] - ref["n_pose_inliers"]) <= soft, label
+    assert not ((r["mask"] != ref["mask"]) & ~rep["soft"]).any(), label
+    if ref["refit_E"] is not None and abs(ref["n_refit"] - ref["n_winner"]) > soft:
+        assert r["refined"] == ref["refined"], label
+    print("%s: not exact-set (%d in-band, %d near-cheirality): n_inliers %d / %d, n_pose_inliers %d / %d, mask differs at %d" %
+          (label, rep["in_band"], rep["near"], r["n_inliers"], ref["n_inliers"], r["n_pose_inliers"], ref["n_pose_inliers"],
+           int((r["mask"] != ref["mask"]).sum())))
+
+
+@pytest.mark.parametrize("i", range(len(RC.POSE_CASES)), ids=lambda i: RC.case_id(RC.POSE_CASES[i]))
+def test_whole_stage_equals_the_reference(aria, i):
+    """aria_pose_estimate against pose_ref.estimate on every case of the table: match counts at the gates (8, 9), mid sizes,
+    around the 2048-point tile and 4096; H = 64, 320 (dead lanes in the score and finish blocks), 1024, 4096; seeds 0, 3
+    and one with the top bit set; pair ids 0, 5, 1 000 000; thresholds 0.25 / 1 / 3 px; distance 50 and 5; both cameras;
+    both view orders; ties won by hypothesis 1 and 306; no refit; no valid hypothesis. tests/test_pose_host.py proves
+    with the restatement alone that every case can be decided and what the table covers.
+
+    Tolerance: measured, not chosen. The device is allowed 10 * GAP against the restatement's np.longdouble run, GAP being
+    the fp64 run's own distance from it (POSE_GAP above, tools/pose_gap.py): one decade for another eigen-solver and
+    another summation order. What the device showed is in DESIGN.md section 10.
+
+    GAP as measured (tools/pose_gap.py prints it; the case numbers index the table of tests/ransac_cases.py):
+        case  n      H      E         R         t
+        0     8      64     2.16e-13  2.14e-14  3.06e-13
+        1     9      64     9.04e-14  5.07e-14  1.26e-13
+        2     9      1024   0.00e+00  2.15e-16  1.88e-16
+        3     40     320    1.89e-13  2.66e-14  2.74e-13
+        4     40     64     3.17e-14  1.85e-14  4.47e-14
+        5     40     320    0.00e+00  4.55e-16  1.22e-16
+        6     150    320    0.00e+00  6.01e-16  1.63e-16
+        7     150    1024   0.00e+00  3.93e-16  1.46e-16
+        8     300    320    3.28e-14  3.90e-15  4.30e-14
+        9     300    1024   7.67e-14  1.22e-14  1.00e-13
+        10    300    320    0.00e+00  2.32e-16  8.86e-17
+        11    600    320    1.10e-13  6.72e-15  1.56e-13
+        12    600    320    5.53e-14  1.39e-14  7.83e-14
+        13    600    64     2.95e-14  2.67e-15  4.17e-14
+        14    2047   320    1.68e-13  2.55e-14  2.37e-13
+        15    2047   64     2.17e-14  1.90e-14  1.66e-14
+        16    2047   320    4.28e-14  1.01e-15  5.95e-14
+        17    2048   320    5.93e-14  2.19e-14  5.63e-14
+        18    2048   64     1.31e-13  1.96e-14  1.88e-13
+        19    2049   64     4.36e-15  8.19e-16  6.16e-15
+        20    4096   320    1.12e-14  9.70e-16  1.48e-14
+        21    300    4096   1.23e-13  1.91e-14  1.41e-13
+        23    150    1024   3.26e-14  7.19e-15  4.16e-14
+        24    150    1024   2.88e-13  4.98e-14  3.26e-13
+    Cases 22 (no valid hypothesis) and 25-27 (not exact-set) have no row: E, R and t are not compared there."""
+    c = RC.POSE_CASES[i]
+    rep = RC.pose_report(c)
+    e = aria.HipPoseEstimator(K=c.K, hypotheses=c.H, threshold_px=c.threshold_px, distance_thresh=c.distance_thresh, seed=c.seed)
+    try:
+        r = e.estimate(*RC.scene(c), c.query_is_first, c.pair_base)
+    finally:
+        e.close()
+    _compare_pose(r, rep, POSE_GAP.get(i), "case %d (%s)" % (i, RC.case_id(c)))
+
+
+def test_batch_launch_equals_the_reference(aria, torch_cuda):
+    """aria_pose_estimate_batch_device, one launch over RC.POSE_BATCH: 300, 0, 2047, 5, 2048, 8, 2049, 40, 600, 7 and 150
+    matches side by side, each pair against pose_ref.estimate with its own pair id (tolerances: POSE_BATCH_GAP).
+
+    GAP as measured (tools/pose_gap.py prints it; by pair of the launch):
+        case  n      H      E         R         t
+        0     300    320    2.77e-14  3.75e-15  3.54e-14
+        2     2047   320    3.09e-15  8.58e-16  4.01e-15
+        4     2048   320    8.58e-14  1.25e-14  1.09e-13
+        5     8      320    0.00e+00  2.45e-16  1.48e-16
+        6     2049   320    1.01e-13  1.91e-14  1.33e-13
+        7     40     320    1.04e-13  2.76e-14  1.09e-13
+        8     600    320    1.06e-14  1.36e-15  1.39e-14
+        10    150    320    2.11e-13  2.60e-14  2.94e-13
+    """
+    torch = torch_cuda
+    dev = torch.device("cuda", 0)
+    cases = RC.POSE_BATCH
+    c0 = cases[0]
+    cap = max(c.n for c in cases)
+    pairs = [RC.scene(c) for c in cases]
+    bufs = _pack(torch, pairs, cap, dev)
+    out = torch.zeros(len(cases) * 192, dtype=torch.uint8, device=dev)
+    mask = torch.full((len(cases) * cap,), 7, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    e = aria.HipPoseEstimator(K=c0.K, hypotheses=c0.H, threshold_px=c0.threshold_px, distance_thresh=c0.distance_thresh,
+                              seed=c0.seed)
+    try:
+        _run_batch(torch, e, bufs, cap, 0, len(cases), RC.POSE_BATCH_BASE, dev, out, mask)
+        e.check()
+    finally:
+        e.close()
+    rec = np.frombuffer(out.cpu().numpy().tobytes(), aria._lib.POSE_RESULT_DTYPE)
+    mk = mask.cpu().numpy().reshape(len(cases), cap)
+    from aria_slam_amd.pose import _result_dict
+    for p, c in enumerate(cases):
+        assert not mk[p, c.n:].any(), p
+        _compare_pose(_result_dict(rec[p], mk[p, :c.n].copy()), RC.pose_report(c), POSE_BATCH_GAP.get(p),
+                      "pair %d (%s)" % (p, RC.case_id(c)))
+
+
+@pytest.mark.parametrize("n,hyp", [(2049, 64), (2049, 320), (4096, 64), (4096, 320)])
+def test_hypothesis_counts_across_the_tile_and_the_block(aria, n, hyp):
+    """test_hypotheses_equal_the_reference's comparison, the same "near" rule, with the points crossing the 2048-point LDS
+    tile of k_pose_score and hypothesis counts that leave dead lanes in its 256-wide block."""
+    from aria_slam_amd import pose_ref as P
+    R, t = _motion(3)
+    kq, kt, m, _ = P.synth_two_view(10, n, R, t, 0.3)
+    e = aria.HipPoseEstimator(hypotheses=hyp, seed=3)
+    try:
+        idx, E, cnt = e.debug_hypotheses(kq, kt, m, pair_base=5)
+    finally:
+        e.close()
+    pts = P.normalise(kq, kt, m)
+    ridx, rE, rcnt = P.hypotheses(pts, seed=3, pair=5, n_hyp=hyp)
+    assert idx.shape == (hyp, 8) and np.array_equal(idx, ridx)
+    both = (cnt >= 0) & (rcnt >= 0)
+    assert np.array_equal(cnt >= 0, rcnt >= 0) and both.sum() >= 0.95 * hyp
+    err = P.sampson_error(rE[both].astype(np.float32), pts)
+    near = (np.abs(err / P.threshold2() - 1.0) < 1e-3).sum(axis=1)
+    assert (np.abs(cnt[both] - rcnt[both]) <= near).all()
+    beyond = P.sampson_inliers(rE[both].astype(np.float32), pts[2048:], P.threshold2()).sum(axis=1)
+    assert (beyond > 0).sum() >= 5                 # the reference's counts reach past the first tile (n = 2049: by one point)

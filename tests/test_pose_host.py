@@ -177,3 +177,81 @@ def test_host_adapters_build_with_the_pose_estimator(aria):
     assert "aria::adapters::hip::HipPoseEstimator::estimate" in syms
     assert "aria::adapters::hip::makeGeometricVerifier" in syms
     assert os.path.exists(os.path.join(pkg, "euroc_frontend"))
+
+
+# ---- the case table of the GPU tests (tests/ransac_cases.py): what it covers, proven with the restatement alone ------------
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ransac_cases as RC   # noqa: E402
+
+
+@pytest.mark.parametrize("case", RC.POSE_CASES + RC.POSE_BATCH, ids=RC.case_id)
+def test_table_case_can_be_decided(case):
+    """Conditions on the inputs, not measurements: a case that violates one is replaced, the condition stays."""
+    rep = RC.pose_report(case)
+    ref = rep["ref"]
+    assert rep["unambiguous"]                                   # no other hypothesis within the in-band points of the winner
+    assert rep["in_band"] <= RC.in_band_limit(case.n)
+    for k in ("valid", "best_hypothesis", "refined", "n_inliers", "n_pose_inliers"):
+        assert rep["ext"][k] == ref[k]                          # the extended run takes every decision the fp64 run takes
+    assert np.array_equal(rep["ext"]["mask"], ref["mask"])
+    if not ref["valid"]:
+        return
+    assert rep["margin"] > rep["near"]                          # the chosen candidate beats the other three outright
+    if not rep["exact"]:
+        # a point of the winner's own band would change the refit's input, and with it decisions outside any band; and
+        # `refined` must not hang on the in-band points
+        assert rep["band_winner"] == 0
+        assert ref["refit_E"] is None or abs(ref["n_refit"] - ref["n_winner"]) > rep["in_band"]
+
+
+def test_table_covers_the_finish_kernel():
+    reps = [RC.pose_report(c) for c in RC.POSE_CASES]
+    cases = RC.POSE_CASES
+    assert {8, 9, 40, 150, 300, 600, 2047, 2048, 2049, 4096} <= {c.n for c in cases}
+    assert {64, 320, 1024, 4096} <= {c.H for c in cases}
+    assert {0, 3, RC.HIGH_SEED} <= {c.seed for c in cases} and RC.HIGH_SEED >> 63 == 1
+    assert {0, 5, 1000000} <= {c.pair_base for c in cases}
+    assert {0.25, 1.0, 3.0} <= {c.threshold_px for c in cases} and {50.0, 5.0} <= {c.distance_thresh for c in cases}
+    assert {RC.EUROC, RC.LOOP} <= {c.K for c in cases} and {True, False} <= {c.query_is_first for c in cases}
+    valid = [r for r in reps if r["ref"]["valid"]]
+    assert {r["ref"]["refined"] for r in valid} == {0, 1}
+    assert any(r["ref"]["n_winner"] < 8 for r in valid)                       # no refit runs
+    assert {r["ref"]["candidate"] for r in valid} == {0, 1, 2, 3}
+    assert any(not r["ref"]["valid"] and r["case"].n >= 8 for r in reps)      # no valid hypothesis
+    # with distance_thresh = 5 part of the inliers of a 2-20 m scene fails the depth test
+    assert any(r["case"].distance_thresh == 5.0 and 0 < r["ref"]["n_pose_inliers"] < r["ref"]["n_inliers"] for r in valid)
+    assert sum(r["exact"] for r in reps) >= 0.8 * len(reps) and not all(r["exact"] for r in reps)
+    # tie scenes: every valid hypothesis counts all n, the winner is the first of them -- one beyond hypothesis 0 and one
+    # beyond the first stride of the finish block, each with a later hypothesis at the same count
+    ties = [r for r in valid if r["case"].noise_px == 0.0 and 0 < r["case"].copies < 1]
+    winners = sorted(r["ref"]["best_hypothesis"] for r in ties)
+    assert winners[0] >= 1 and winners[-1] >= 256
+    for r in ties:
+        c = r["case"]
+        _idx, _E, counts = _case_hypotheses(r)
+        assert counts.max() == c.n == r["ref"]["n_winner"]
+        assert (counts[r["ref"]["best_hypothesis"] + 1:] == c.n).sum() >= 1 and (counts[:r["ref"]["best_hypothesis"]] < c.n).all()
+
+
+def _case_hypotheses(rep):
+    from aria_slam_amd import pose_ref as P
+    c = rep["case"]
+    return P.hypotheses(rep["pts"], c.seed, c.pair_base, c.H, c.threshold_px, c.K)
+
+
+def test_extended_path_agrees_with_lapack():
+    """jacobi_eigh in np.longdouble against LAPACK in fp64 on a refit's normal matrix, and the Jacobi decomposition against
+    the SVD one as sets of four candidates."""
+    from aria_slam_amd import pose_ref as P
+    rep = RC.pose_report(RC.POSE_CASES[9])
+    pts = rep["pts"]
+    A = P.design_rows(pts[rep["ref"]["mask"] == 1])
+    w, V = np.linalg.eigh(A.T @ A)
+    wx, Vx = P.jacobi_eigh((A.astype(np.longdouble)).T @ A.astype(np.longdouble))
+    assert wx.dtype == np.longdouble and np.abs(w - wx.astype(np.float64)).max() <= 1e-12 * w.max()
+    assert abs(abs(float(V[:, 0] @ Vx[:, 0].astype(np.float64))) - 1.0) < 1e-12
+    assert np.abs((Vx.T @ Vx).astype(np.float64) - np.eye(9)).max() < 1e-17
+    a = P.decompose_essential(rep["ref"]["E"])
+    b = P.decompose_essential(rep["ref"]["E"], np.longdouble)
+    for R, t in a:
+        assert min(max(np.abs(R - R2.astype(np.float64)).max(), np.abs(t - t2.astype(np.float64)).max()) for R2, t2 in b) < 1e-13
