@@ -60,6 +60,9 @@ EXPORTS = [
     "aria_fuse_default_config", "aria_fuse_create", "aria_fuse_destroy", "aria_fuse_stream", "aria_fuse_check",
     "aria_fuse_filter_init", "aria_fuse_run_batch_device", "aria_fuse_run", "aria_fuse_visual_from_pose_device",
     "aria_fuse_preintegrate_batch_device", "aria_fuse_preintegrate",
+    # trajectory evaluation (ground-truth sampling, ATE / RPE, Umeyama alignment), additive to ABI 4
+    "aria_eval_default_config", "aria_eval_create", "aria_eval_destroy", "aria_eval_stream", "aria_eval_check",
+    "aria_eval_sample_truth_device", "aria_eval_sample_truth", "aria_eval_batch_device", "aria_eval_batch",
 ]
 
 
@@ -159,6 +162,34 @@ FUSE_STATE_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("v", "<f8", (3,)
                              ("n_ignored", "<i4"), ("n_updates", "<i4"), ("initialized", "<i4"), ("valid", "<i4")])
 PREINT_RESULT_DTYPE = np.dtype([("delta_p", "<f8", (3,)), ("delta_v", "<f8", (3,)), ("delta_q", "<f8", (4,)), ("dt_sum", "<f8"),
                                 ("cov", "<f8", (81,)), ("n_used", "<i4"), ("valid", "<i4")])
+
+
+class EvalConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("align_mode", C.c_int),
+                ("rpe_delta", C.c_int)]
+
+
+class EvalTruth(C.Structure):
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("q", C.c_double * 4), ("v", C.c_double * 3), ("bg", C.c_double * 3),
+                ("ba", C.c_double * 3)]
+
+
+class EvalResult(C.Structure):
+    _fields_ = [("ate_raw", C.c_double), ("rpe_raw", C.c_double), ("scale", C.c_double), ("R", C.c_double * 9),
+                ("t", C.c_double * 3), ("sigma", C.c_double * 3), ("ate_rmse", C.c_double), ("ate_mean", C.c_double),
+                ("ate_max", C.c_double), ("rpe_aligned", C.c_double), ("n_poses", C.c_int), ("n_used", C.c_int),
+                ("n_rpe_pairs", C.c_int), ("align_valid", C.c_int), ("valid", C.c_int), ("reserved", C.c_int)]
+
+
+# aria_eval_truth (136 bytes) and aria_eval_result (200 bytes)
+EVAL_TRUTH_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("q", "<f8", (4,)), ("v", "<f8", (3,)), ("bg", "<f8", (3,)),
+                             ("ba", "<f8", (3,))])
+EVAL_RESULT_DTYPE = np.dtype([("ate_raw", "<f8"), ("rpe_raw", "<f8"), ("scale", "<f8"), ("R", "<f8", (9,)), ("t", "<f8", (3,)),
+                              ("sigma", "<f8", (3,)), ("ate_rmse", "<f8"), ("ate_mean", "<f8"), ("ate_max", "<f8"),
+                              ("rpe_aligned", "<f8"), ("n_poses", "<i4"), ("n_used", "<i4"), ("n_rpe_pairs", "<i4"),
+                              ("align_valid", "<i4"), ("valid", "<i4"), ("reserved", "<i4")])
+EVAL_ALIGN_NONE, EVAL_ALIGN_SE3, EVAL_ALIGN_SIM3 = 0, 1, 2
+EVAL_EST_POSE12, EVAL_EST_FUSE_STATE, EVAL_EST_XYZ = 0, 1, 2
 
 
 # aria_fund_result (96 bytes)
@@ -319,6 +350,8 @@ def load_library():
         _bind_graph(L)
     if hasattr(L, "aria_fuse_create"):
         _bind_fuse(L)
+    if hasattr(L, "aria_eval_create"):
+        _bind_eval(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -414,6 +447,22 @@ def _bind_fuse(L):
     L.aria_fuse_visual_from_pose_device.argtypes = [p, p, p, i, i, p]
     L.aria_fuse_preintegrate_batch_device.argtypes = [p, p, i, p, p, i, p, p]
     L.aria_fuse_preintegrate.argtypes = [p, p, i, p, p, i, p, p]
+
+
+def _bind_eval(L):
+    p, i = C.c_void_p, C.c_int
+    L.aria_eval_default_config.restype = None
+    L.aria_eval_default_config.argtypes = [p]
+    L.aria_eval_create.argtypes = [p, C.POINTER(C.c_void_p)]
+    L.aria_eval_destroy.restype = None
+    L.aria_eval_destroy.argtypes = [p]
+    L.aria_eval_stream.restype = p
+    L.aria_eval_stream.argtypes = [p]
+    L.aria_eval_check.argtypes = [p]
+    L.aria_eval_sample_truth_device.argtypes = [p, p, i, p, i, p, p]
+    L.aria_eval_sample_truth.argtypes = [p, p, i, p, i, p, p]
+    L.aria_eval_batch_device.argtypes = [p, p, i, p, i, i, p, i, i, p, i, i, p, p]
+    L.aria_eval_batch.argtypes = [p, p, i, p, i, i, p, i, i, p, i, i, p, p]
 
 
 def status_string(status):

@@ -8,7 +8,12 @@
 //     <root>/mav0/imu0/data.csv      "#timestamp [ns],w_x,w_y,w_z,a_x,a_y,a_z": gyro in columns 1-3, accelerometer in 4-6
 // is read when it is there (EuRoCReader.cpp:110-154: rows of fewer than 7 fields dropped, sorted by timestamp), together with
 // the samples every image consumes (getNext, :295-305: prev_image_time < t <= image_time, 0 before the first image); a
-// sequence without imu0 still loads. Ground truth is out of scope.
+// sequence without imu0 still loads.
+//     <root>/mav0/state_groundtruth_estimate0/data.csv   "#timestamp, p xyz, q wxyz, v xyz, b_w xyz, b_a xyz" (17 fields)
+// is read when it is there (EuRoCReader.cpp:37-41, 157-216: rows of fewer than 17 fields dropped, sorted by timestamp -- a
+// stable sort here, ours by definition), else <root>/mav0/leica0/data.csv is tried as the reference does. A Leica file has 4
+// fields per row, so under the 17-field rule the fallback yields no rows, exactly as in the reference; a sequence without
+// ground truth still loads.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -27,6 +32,15 @@ struct AslImu {
     double gyro[3] = {0, 0, 0};      // rad/s
 };
 
+struct AslGroundTruth {              // the 17 doubles of aria_eval_truth, in its order
+    double timestamp = 0.0;          // seconds
+    double p[3] = {0, 0, 0};
+    double q[4] = {1, 0, 0, 0};      // w, x, y, z
+    double v[3] = {0, 0, 0};
+    double bg[3] = {0, 0, 0};
+    double ba[3] = {0, 0, 0};
+};
+
 class AslSequence {
 public:
     // dataset_path may be the sequence root (containing mav0/) or the mav0 directory itself
@@ -39,11 +53,15 @@ public:
     const std::vector<AslImu>& imu() const { return imu_; }
     std::size_t imuBegin(std::size_t i) const { return imu_begin_[i]; }
     std::size_t imuEnd(std::size_t i) const { return imu_end_[i]; }
+    // ground truth, sorted by timestamp (empty when the sequence has none)
+    const std::vector<AslGroundTruth>& groundTruth() const { return ground_truth_; }
+    bool hasGroundTruth() const { return !ground_truth_.empty(); }
 
 private:
     std::vector<AslImage> images_;
     std::vector<AslImu> imu_;
     std::vector<std::size_t> imu_begin_, imu_end_;
+    std::vector<AslGroundTruth> ground_truth_;
 };
 
 // PNG -> 8-bit grayscale (see header comment). Throws std::runtime_error.

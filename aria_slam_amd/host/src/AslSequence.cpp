@@ -27,6 +27,30 @@ bool file_exists(const std::string& p) {
     return f.good();
 }
 
+// EuRoCReader::loadGroundTruth (:157-216). Returns whether any row was read.
+bool load_ground_truth(const std::string& csv, std::vector<AslGroundTruth>& out) {
+    std::ifstream file(csv);
+    if (!file.is_open()) return false;
+    std::string line;
+    std::getline(file, line);                                                 // header (:166)
+    while (std::getline(file, line)) {
+        if (line.empty() || line[0] == '#') continue;                         // :169
+        std::stringstream ss(line);
+        std::string token;
+        std::vector<std::string> tokens;
+        while (std::getline(ss, token, ',')) tokens.push_back(token);
+        if (tokens.size() < 17) continue;                                     // :179
+        AslGroundTruth g;
+        double* d = &g.timestamp;                                             // 17 packed doubles (static_assert below)
+        d[0] = std::strtod(tokens[0].c_str(), nullptr) * 1e-9;
+        for (std::size_t k = 1; k < 17; k++) d[k] = std::strtod(tokens[k].c_str(), nullptr);
+        out.push_back(g);
+    }
+    std::stable_sort(out.begin(), out.end(), [](const AslGroundTruth& a, const AslGroundTruth& b) { return a.timestamp < b.timestamp; });
+    return !out.empty();
+}
+static_assert(sizeof(AslGroundTruth) == 17 * sizeof(double), "AslGroundTruth is 17 packed doubles");
+
 }  // namespace
 
 void decode_png_gray(const std::vector<std::uint8_t>& file, std::vector<std::uint8_t>& gray, int& width, int& height) {
@@ -158,6 +182,11 @@ bool AslSequence::load(const std::string& dataset_path) {
         while (k < imu_.size() && imu_[k].timestamp <= now) k++;
         imu_end_[i] = k;
     }
+    // ground truth beside cam0 (EuRoCReader.cpp:37-41): state_groundtruth_estimate0, else leica0; neither is an error
+    ground_truth_.clear();
+    const std::string mav = cam.substr(0, cam.size() - 4);
+    if (!load_ground_truth(mav + "state_groundtruth_estimate0/data.csv", ground_truth_))
+        load_ground_truth(mav + "leica0/data.csv", ground_truth_);            // 4 fields per row: no row survives (:179)
     return !images_.empty();                                                  // :105
 }
 
@@ -214,6 +243,15 @@ int aria_asl_imu(const char* dataset_path, double* samples, int cap, int* ranges
     }
     if (n_images) *n_images = (int)s.size();
     return (int)imu.size();
+}
+
+// Ground truth as rows of 17 doubles (the layout of aria_eval_truth); returns the number of rows (0 without any) or -1.
+int aria_asl_ground_truth(const char* dataset_path, double* rows, int cap) {
+    aria::io::AslSequence s;
+    if (!s.load(dataset_path)) return -1;
+    const auto& gt = s.groundTruth();
+    for (std::size_t i = 0; i < gt.size() && (int)i < cap; i++) std::memcpy(rows + 17 * i, &gt[i], 17 * sizeof(double));
+    return (int)gt.size();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
-//                [--optimize FILE] [--fuse FILE]
+//                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -59,6 +59,17 @@
 // orientation after that frame's events (the filter's initial state before the first accepted pose), and "fused N updates
 // ..." is printed. Without the flag nothing changes; --pose FILE and the CSV are byte-identical with and without it.
 //
+// --eval FILE (needs --pose; the sequence needs ground truth, mav0/state_groundtruth_estimate0): the last step of
+// euroc_eval.cpp on the device (include/aria_orb_hip.h, "trajectory evaluation"). Ground truth is sampled at every frame's
+// timestamp (:247-252, EuRoCReader::getGroundTruth) and the --pose trajectory, plus the --optimize and --fuse trajectories when
+// those flags are given, are scored against it by position in the trajectory, as :285-288 pairs them. FILE gets one line per
+// trajectory, "name align n_poses n_used ate_raw rpe_raw align_valid scale ate_rmse ate_mean ate_max rpe_aligned sigma1 sigma2
+// sigma3": the reference's computeATE / computeRPE (no alignment) and the figures after the alignment --eval-align chooses
+// (default sim3: a chain of unit-length translations has no scale of its own); --rpe-delta N is computeRPE's delta (default
+// 10). Frames the filter had not been initialised for take no part in the --fuse line. The reference's two-line "Trajectory
+// Error" report (:303-305) is printed with its raw numbers, for the --optimize trajectory when there is one (the reference
+// reports the optimised poses), else for --pose. Without the flag nothing changes and every other output is byte-identical.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -74,6 +85,7 @@
 #include <fstream>
 #include <iomanip>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -87,6 +99,7 @@
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
 #include "aria_hip/HipSensorFusion.hpp"
+#include "aria_hip/HipTrajectoryEvaluator.hpp"
 #include "aria_hip/Shard.hpp"
 #include "aria_orb_hip.h"
 
@@ -118,7 +131,8 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N]\n"
+                             "  --eval file: ATE / RPE of the --pose (and --optimize, --fuse) trajectories against the sequence's ground truth (needs --pose)\n"
                              "  --fuse file: EKF visual-inertial fusion over imu0 and the --pose stage's relative poses (needs --pose), one TUM line per frame\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
                              "                   the per-loop optimize(10) and reset of current_pose of the reference are not reproduced (the loop step is post hoc)\n", argv[0]);
@@ -126,7 +140,8 @@ int main(int argc, char** argv) {
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
-    std::string csv, pose_file, map_file, loop_verify, optimize_file, fuse_file;
+    std::string csv, pose_file, map_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
+    int rpe_delta = 10;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -140,6 +155,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
         else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
         else if (!std::strcmp(argv[i], "--fuse") && i + 1 < argc) fuse_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--eval") && i + 1 < argc) eval_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--eval-align") && i + 1 < argc) eval_align = argv[++i];
+        else if (!std::strcmp(argv[i], "--rpe-delta") && i + 1 < argc) rpe_delta = std::atoi(argv[++i]);
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -157,6 +175,12 @@ int main(int argc, char** argv) {
     }
     if (!fuse_file.empty() && pose_file.empty()) {
         std::fprintf(stderr, "--fuse needs --pose (the filter is updated with the pose stage's relative poses)\n");
+        return 1;
+    }
+    const int eval_mode = eval_align == "none" ? ARIA_EVAL_ALIGN_NONE : eval_align == "se3" ? ARIA_EVAL_ALIGN_SE3
+                          : eval_align == "sim3" ? ARIA_EVAL_ALIGN_SIM3 : -1;
+    if (!eval_file.empty() && (pose_file.empty() || eval_mode < 0 || rpe_delta < 1)) {
+        std::fprintf(stderr, "--eval needs --pose, --eval-align none|se3|sim3 and --rpe-delta >= 1\n");
         return 1;
     }
     if (!map_file.empty() && pose_file.empty()) {
@@ -185,6 +209,12 @@ int main(int argc, char** argv) {
     }
     std::printf("Loaded: %zu images\n", seq.size());
     const std::size_t N = seq.size();
+    if (!eval_file.empty() && !seq.hasGroundTruth()) {
+        std::fprintf(stderr, "--eval: the sequence has no mav0/state_groundtruth_estimate0/data.csv with 17-field rows\n");
+        return 1;
+    }
+    std::vector<aria_fuse_state> fused_states;                             // --eval: what --fuse and --optimize leave
+    std::vector<double> optimized_xyz;
     if ((std::size_t)shards > N && N > 0) shards = (int)N;
 
     std::vector<FrameRecord> rec(N);
@@ -450,6 +480,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--fuse: %s\n", e.what());
             return 1;
         }
+        if (!eval_file.empty()) fused_states = states;
         std::ofstream tf(fuse_file);
         tf << std::fixed << std::setprecision(9);
         long long predicted = 0, skipped = 0, ignored = 0, updates = 0;
@@ -472,11 +503,64 @@ int main(int argc, char** argv) {
                 for (int b = 0; b < 4; b++) T[(size_t)(a * 4 + b)] = m(a, b);
             return T;
         });
+        if (!eval_file.empty())
+            for (std::size_t i = 0; i < N; i++) {
+                std::array<double, 16> T = traj[i];
+                if (last_vertex[i] >= 0) {
+                    const adapters::hip::GraphPose m = graph->getOptimizedPose((int)last_vertex[i]);
+                    for (int a = 0; a < 3; a++) T[(size_t)(a * 4 + 3)] = m(a, 3);
+                }
+                for (int a = 0; a < 3; a++) optimized_xyz.push_back(T[(size_t)(a * 4 + 3)]);
+            }
         const aria_graph_result& gr = graph->lastResult();
         std::printf("pose graph %zu vertices %zu edges | chi2 %.6g -> %.6g in %d iterations (%d solves, %d PCG iterations) -> %s\n",
                     graph->numVertices(), graph->numEdges(), gr.chi2_initial, gr.chi2_final, gr.iterations_done, gr.trials,
                     gr.pcg_iterations, optimize_file.c_str());
     }
     if (!map_file.empty()) std::printf("map %zu points -> %s\n", map_points, map_file.c_str());
+    if (!eval_file.empty()) {                                              // euroc_eval.cpp:247-252, 294-305
+        try {
+            aria_eval_config ec;
+            aria_eval_default_config(&ec);
+            ec.align_mode = eval_mode;
+            ec.rpe_delta = rpe_delta;
+            adapters::hip::HipTrajectoryEvaluator ev(&ec);
+            std::vector<aria_eval_truth> gt(seq.groundTruth().size()), truth;
+            static_assert(sizeof(io::AslGroundTruth) == sizeof(aria_eval_truth), "AslGroundTruth has aria_eval_truth's layout");
+            std::memcpy(gt.data(), seq.groundTruth().data(), gt.size() * sizeof(aria_eval_truth));
+            std::vector<double> ts(N);
+            for (std::size_t i = 0; i < N; i++) ts[i] = seq.at(i).timestamp;
+            if (ev.sampleGroundTruth(gt, ts, truth) != ARIA_OK) {
+                std::fprintf(stderr, "--eval: the ground truth is not usable (a non-finite field or decreasing timestamps)\n");
+                return 1;
+            }
+            std::vector<double> pose_xyz;
+            for (std::size_t i = 0; i < N; i++)
+                for (int a = 0; a < 3; a++) pose_xyz.push_back(traj[i][(size_t)(a * 4 + 3)]);
+            const int off[2] = {0, (int)N};
+            std::ofstream ef(eval_file);
+            ef << std::setprecision(17);
+            aria_eval_result report{};
+            auto score = [&](const char* name, const void* est, int kind) {
+                aria_eval_result r{};
+                if (ev.evaluateBatch(est, kind, off, (int)N, 1, truth.data(), (int)N, false, nullptr, nullptr, &r) != ARIA_OK)
+                    throw std::runtime_error(std::string("trajectory '") + name + "' holds a non-finite position");
+                ef << name << ' ' << eval_align << ' ' << r.n_poses << ' ' << r.n_used << ' ' << r.ate_raw << ' ' << r.rpe_raw << ' '
+                   << r.align_valid << ' ' << r.scale << ' ' << r.ate_rmse << ' ' << r.ate_mean << ' ' << r.ate_max << ' '
+                   << r.rpe_aligned << ' ' << r.sigma[0] << ' ' << r.sigma[1] << ' ' << r.sigma[2] << '\n';
+                std::printf("eval %s: %d of %d poses | raw ATE %.4f m RPE %.4f m | %s-aligned ATE rmse %.4f mean %.4f max %.4f m RPE %.4f m scale %.6g\n",
+                            name, r.n_used, r.n_poses, r.ate_raw, r.rpe_raw, eval_align.c_str(), r.ate_rmse, r.ate_mean, r.ate_max,
+                            r.rpe_aligned, r.scale);
+                return r;
+            };
+            report = score("pose", pose_xyz.data(), ARIA_EVAL_EST_XYZ);
+            if (!optimized_xyz.empty()) report = score("optimize", optimized_xyz.data(), ARIA_EVAL_EST_XYZ);
+            if (!fused_states.empty()) score("fuse", fused_states.data(), ARIA_EVAL_EST_FUSE_STATE);
+            std::printf("\nTrajectory Error:\n  ATE (RMSE): %.4f m\n  RPE (RMSE): %.4f m\n", report.ate_raw, report.rpe_raw);   // :303-305
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "--eval: %s\n", e.what());
+            return 1;
+        }
+    }
     return 0;
 }

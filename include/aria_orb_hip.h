@@ -850,6 +850,106 @@ int   aria_fuse_preintegrate_batch_device(aria_fuse_t h, const aria_imu_sample* 
 int   aria_fuse_preintegrate(aria_fuse_t h, const aria_imu_sample* imu, int n_imu, const int* begin, const int* end,
                              int n_intervals, const double* bias_or_null, aria_preint_result* out);
 
+/* ---- trajectory evaluation: the reference's ground-truth lookup (EuRoCReader::getGroundTruth, src/legacy/EuRoCReader.cpp:
+ * 311-346) and its trajectory error (computeATE / computeRPE, src/euroc_eval.cpp:28-61), plus the Umeyama alignment its
+ * documentation defines ATE with (docs/milestones/H07_EUROC_DATASET_AUDIT.md:602-611) and its code leaves out. Batched over
+ * query timestamps and over trajectories. Additive to ABI 4. aria_slam_amd/eval_ref.py restates all of it in NumPy and is the
+ * definition; parity with an Eigen build of the reference is not pinned by any test (Eigen is not available to this project).
+ * fp64 throughout.
+ *
+ * Ground-truth sampling. Query t takes the lower bound over the n_gt rows (first row with timestamp >= t). Past the last row:
+ *   the last row, copied (its own timestamp included). At or before the first row: the first row, copied. Otherwise rows
+ *   a = lower bound - 1, b = lower bound, alpha = (t - t_a) / (t_b - t_a) with t_a < t <= t_b (an exact hit of row b gives
+ *   alpha = 1 between b - 1 and b); p, v, bg, ba = (1 - alpha) a + alpha b in that operation order; q = slerp as Eigen writes
+ *   it, ours by definition: d = a.b; |d| >= 1 - 2^-52: weights 1 - alpha and alpha; else th = acos |d|, weights
+ *   sin((1 - alpha) th) / sin th and sin(alpha th) / sin th; the second weight negated when d < 0; not renormalised. The
+ *   output's t is the query. Invalid: n_gt < 1, a non-finite field of any row, a timestamp smaller than its predecessor's --
+ *   found by a scan of its own before any row is sampled; then EVERY output of the call is zeroed with valid = 0. A non-finite
+ *   query invalidates its own output only. Either defers ARIA_E_INVALID to aria_eval_check.
+ * Trajectory metrics. Trajectory k owns the poses offset[k] .. offset[k+1] of the estimate (the convention of d_vertex_offset
+ *   of aria_graph_optimize_batch_device, which can be passed as it is). Positions are read in place: ARIA_EVAL_EST_POSE12 =
+ *   entries 3, 7, 11 of 12-double [R t] rows, ARIA_EVAL_EST_FUSE_STATE = p of aria_fuse_state records,
+ *   ARIA_EVAL_EST_XYZ = packed triples. Truth positions are p of aria_eval_truth records, indexed like the estimate, or
+ *   (truth_shared != 0) one trajectory of n_truth records that every trajectory is scored against, pose i against record
+ *   i - offset[k]. A pose is USED when its mask byte (optional array, one byte per pose) is nonzero and, for fuse states, its
+ *   record has initialized != 0 and valid != 0. n = number of used poses, sums over used poses in index order:
+ *     ate_raw  = sqrt(sum |e_i - g_i|^2 / n), -1 when n = 0                                  (computeATE: no alignment)
+ *     rpe_raw  = sqrt(sum |(e_i - e_{i-delta}) - (g_i - g_{i-delta})|^2 / pairs) over the i >= delta whose two ends are both
+ *                used, -1 when there is no such pair (so whenever the length <= delta)           (computeRPE)
+ *     Umeyama (estimate onto truth), two passes: centroids mu_e, mu_g; C = sum (g_i - mu_g)(e_i - mu_e)^T / n, var =
+ *       sum |e_i - mu_e|^2 / n. C = U diag(sigma) V^T by one-sided Jacobi ON C ITSELF (never C^T C: that squares the
+ *       condition number), sigma sorted descending, u3 := u1 x u2. R = [u1 u2 u3] diag(1, 1, det V) V^T, which is Umeyama's
+ *       U diag(1, 1, det U det V) V^T whatever sign the third left vector had; scale = (sigma1 + sigma2 + d sigma3) / var with
+ *       d = det U det V (similarity) or 1 exactly (rigid); t = mu_g - scale R mu_e. Mode none: scale 1, R = I, t = 0.
+ *     ate_rmse / ate_mean / ate_max of |scale R e_i + t - g_i|, rpe_aligned of |scale R (e_i - e_{i-delta}) - (g_i - g_{i-delta})|.
+ *   Degenerate alignment (rigid and similarity only): n < 3, or sigma2 <= 1e-10 sigma1 (collinear or coincident points; the
+ *   threshold is a definition): align_valid = 0, scale, R, t and the aligned fields are -1, the raw fields, sigma and the
+ *   counts stay filled. In mode none only n = 0 is degenerate.
+ * Invalid input. offset[k] > offset[k+1], a range leaving [0, n_poses_total] (or [0, n_truth] for truth that is not shared), a
+ *   shared truth whose length differs from the trajectory's, rpe_delta < 1, an align mode or estimate kind that does not
+ *   exist, a non-finite position of a used pose or of its truth: that trajectory's result is zeroed (valid = 0), its per-pose
+ *   errors are written as 0 when its range is in bounds and not at all otherwise, the other trajectories are unaffected,
+ *   and aria_eval_check reports ARIA_E_INVALID once.
+ * Determinism. No float atomics; fixed-tree reductions. A trajectory's bits depend on its own poses, truth and mask only:
+ *   reproducible run to run, independent of its place in the batch, of its neighbours and of how the batch is split
+ *   (a call of more than 32768 trajectories is split into launches of that many by the library itself). */
+typedef struct aria_eval_s* aria_eval_t;
+enum { ARIA_EVAL_ALIGN_NONE = 0, ARIA_EVAL_ALIGN_SE3 = 1, ARIA_EVAL_ALIGN_SIM3 = 2 };
+enum { ARIA_EVAL_EST_POSE12 = 0, ARIA_EVAL_EST_FUSE_STATE = 1, ARIA_EVAL_EST_XYZ = 2 };
+typedef struct {
+    double   t;                /* seconds                                                                        */
+    double   p[3];
+    double   q[4];             /* w, x, y, z                                                                     */
+    double   v[3], bg[3], ba[3];
+} aria_eval_truth;             /* 136 bytes: the columns of state_groundtruth_estimate0/data.csv, in their order  */
+typedef struct {
+    double   ate_raw, rpe_raw;
+    double   scale, R[9], t[3];                    /* row-major; aligned = scale R e + t                          */
+    double   sigma[3];                             /* singular values of C, descending                            */
+    double   ate_rmse, ate_mean, ate_max, rpe_aligned;
+    int      n_poses;          /* length of the trajectory                                                       */
+    int      n_used;           /* poses that took part                                                           */
+    int      n_rpe_pairs;
+    int      align_valid;
+    int      valid;
+    int      reserved;
+} aria_eval_result;            /* 200 bytes                                                                      */
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_eval_config)                                                     */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking: not
+                                * ordered against the legacy default stream, see aria_pose_config)               */
+    int      align_mode;       /* what a caller passes on when it has no preference: ARIA_EVAL_ALIGN_SIM3         */
+    int      rpe_delta;        /* likewise: 10 (computeRPE's default)                                            */
+} aria_eval_config;            /* 24 bytes                                                                       */
+
+void  aria_eval_default_config(aria_eval_config* cfg);
+int   aria_eval_create(const aria_eval_config* cfg, aria_eval_t* out);
+void  aria_eval_destroy(aria_eval_t h);
+void* aria_eval_stream(aria_eval_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when some call or trajectory was invalid (above). */
+int   aria_eval_check(aria_eval_t h);
+/* n queries against n_gt ground-truth rows, all in HBM. d_valid (optional): n ints, 1 = sampled. Enqueued on the handle's
+ * stream (a scan of the rows, then one lane per query), no synchronisation. */
+int   aria_eval_sample_truth_device(aria_eval_t h, const aria_eval_truth* d_gt, int n_gt, const double* d_timestamps, int n,
+                                    aria_eval_truth* d_out, int* d_valid_or_null);
+/* The same over host arrays; blocks. Invalid input: ARIA_E_INVALID (the outputs zeroed as above). */
+int   aria_eval_sample_truth(aria_eval_t h, const aria_eval_truth* gt, int n_gt, const double* timestamps, int n,
+                             aria_eval_truth* out, int* valid_or_null);
+/* n_traj trajectories over device arrays. d_est: n_poses_total records of est_kind. d_offset: n_traj + 1 ints. d_truth:
+ * n_truth records. d_mask (optional): n_poses_total bytes. d_pose_err (optional): n_poses_total doubles, the aligned error
+ * of every used pose, -1 for a pose that is not used or when the alignment is degenerate. Trajectories may share poses (they
+ * are only read); a shared pose's entry of d_pose_err is then that of one of its trajectories. One workgroup per trajectory.
+ * Enqueued on the handle's stream, no synchronisation. Data errors: aria_eval_check. */
+int   aria_eval_batch_device(aria_eval_t h, const void* d_est, int est_kind, const int* d_offset, int n_poses_total, int n_traj,
+                             const aria_eval_truth* d_truth, int n_truth, int truth_shared, const uint8_t* d_mask_or_null,
+                             int align_mode, int rpe_delta, double* d_pose_err_or_null, aria_eval_result* d_results);
+/* The same over host arrays; blocks. ARIA_E_INVALID when some trajectory was invalid (the others are still scored). */
+int   aria_eval_batch(aria_eval_t h, const void* est, int est_kind, const int* offset, int n_poses_total, int n_traj,
+                      const aria_eval_truth* truth, int n_truth, int truth_shared, const uint8_t* mask_or_null, int align_mode,
+                      int rpe_delta, double* pose_err_or_null, aria_eval_result* results);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
