@@ -263,11 +263,12 @@ def direct(D, W, edges, b, lam, fixed):
 
 def optimize(poses, edges, fixed=0, iterations=10, solver="pcg", pcg_max_iters=1000, pcg_rel_tol=1e-8):
     """Levenberg-Marquardt as defined in the header of this file. Returns (poses (V, 4, 4), result dict with the fields of
-    aria_graph_result plus chi2_history, the chi2 after every accepted iteration)."""
+    aria_graph_result plus chi2_history, the chi2 after every accepted iteration, and trace, one entry per trial:
+    dict(iteration, trial, rho, accepted, lambda_ (before the trial), chi2_new, solver_iterations))."""
     poses = np.array(poses, np.float64).reshape(-1, 4, 4).copy()
     edges = [(int(i), int(j), float(s), np.asarray(Z, np.float64).reshape(4, 4)) for i, j, s, Z in edges]
     res = dict(chi2_initial=0.0, chi2_final=0.0, lambda_=0.0, iterations_done=0, trials=0, pcg_iterations=0, valid=1,
-               stop_reason=STOP_ITERATIONS, chi2_history=[])
+               stop_reason=STOP_ITERATIONS, chi2_history=[], trace=[])
     if not check_graph(len(poses), edges, fixed):
         res.update(valid=0, stop_reason=STOP_INVALID)
         return poses, res
@@ -293,7 +294,10 @@ def optimize(poses, edges, fixed=0, iterations=10, solver="pcg", pcg_max_iters=1
             scale = float((dx[free] * (lam * dx[free] + b[free])).sum()) + 1e-3
             lin = linearize(trial, edges)
             rho = (chi2 - lin[0]) / scale
-            if rho > 0 and np.isfinite(lin[0]):
+            ok = bool(rho > 0 and np.isfinite(lin[0]))
+            res["trace"].append(dict(iteration=_it, trial=_trial, rho=float(rho), accepted=ok, lambda_=float(lam),
+                                     chi2_new=float(lin[0]), solver_iterations=int(n)))
+            if ok:
                 poses = trial
                 chi2, b, D, W = lin
                 lam *= max(1.0 / 3.0, 1.0 - (2 * rho - 1) ** 3)

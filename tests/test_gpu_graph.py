@@ -16,12 +16,22 @@ Graphs of more than 512 vertices take the kernel's strided solver instead of the
 vertices, 3 loops) covers it. There the capped PCG lags the direct solve more: the CPU-measured gap is 1.01e-6 after 1
 iteration and 1.24e-3 after 5 (every solve ends at the cap), so the device is allowed 1.01e-5 and 1.24e-2. dense22 (200
 vertices, 599 edges) is one vertex per lane but too many edges for the on-chip form of that solver; its CPU-measured gap
-after 1 iteration is 3.7e-8, so the device is allowed 3.7e-7."""
+after 1 iteration is 3.7e-8, so the device is allowed 3.7e-7.
+
+The graphs above never make LM reject a trial. The rejected-trial path (the restore of the poses, lambda *= ni, ni *= 2, the
+ni = 2 reset, the ten-trial stop) runs on the cases of tests/graph_cases.py, under the same convention: ten times the
+CPU-measured direct-vs-pcg gap of that case after that many iterations (GAPS there, from tools/graph_gap.py) for the poses,
+for lambda and for chi2_final, the discrete fields equal to the pcg restatement's. tests/test_graph_host.py proves on the CPU
+that no decision of those cases is near enough to rho = 0 for the device's summation order to flip it."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import graph_cases as GC   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -98,6 +108,7 @@ def test_lm_equals_the_restatement(opt, name):
         assert np.isfinite(P).all()
         assert gap_direct <= TOL, (name, its, gap_direct)
         assert _fields(r) == _fields(rp), (r, rp)
+        # these graphs never reject a trial (trials == iterations_done); the ones that do are tests/graph_cases.py's, below
         assert r["iterations_done"] == its and r["stop_reason"] == G.STOP_ITERATIONS
         assert abs(r["chi2_initial"] - rp["chi2_initial"]) <= 1e-9 * rp["chi2_initial"]
         assert r["chi2_final"] <= r["chi2_initial"]
@@ -145,6 +156,86 @@ def test_lm_equals_the_restatement_with_more_edges_than_the_lds_holds(aria):
     _P5, rp5 = G.optimize(poses, edges, 0, 5, "pcg")
     assert np.isfinite(P5).all() and _fields(r5) == _fields(rp5) and r5["chi2_final"] <= r["chi2_final"]
     o.close()
+
+
+# ---- the rejected-trial path (tests/graph_cases.py) ------------------------------------------------------------------------------
+def _handle_for(aria, opt, c):
+    if c.handle is None:
+        return opt
+    return aria.HipPoseGraphOptimizer(max_vertices=c.handle[0], max_edges=c.handle[1])
+
+
+@pytest.mark.parametrize("name", [c.name for c in GC.CASES if c.name not in GC.EXEMPT])
+def test_rejected_trials_equal_the_restatement(aria, opt, name):
+    """LM's state restarts at every call, so the runs of 1, 2, ..., K iterations pin the number of rejections before every
+    accept, and lambda and chi2 after it."""
+    from aria_slam_amd import graph_ref as G
+    c = GC.BY_NAME[name]
+    poses, edges = GC.graph(name)
+    o = _handle_for(aria, opt, c)
+    try:
+        share = [0.0, 0.0, 0.0]
+        for k in range(1, c.iterations + 1):
+            P, r = o.optimize_graph(poses, edges, c.fixed, k)
+            (Pd, rd), (Pp, rp) = GC.reference(name, k, "direct"), GC.reference(name, k, "pcg")
+            got = (np.abs(P - Pd).max(), GC.rel(r["lambda_"], rd["lambda_"]), GC.rel(r["chi2_final"], rd["chi2_final"]))
+            allowed = [10 * g for g in GC.GAPS[name][k - 1]]
+            share = [max(s, g / a) for s, g, a in zip(share, got, allowed)]
+            print("%s %d iterations, %s: device vs direct pose %.3g lambda %.3g chi2 %.3g (allowed %.3g %.3g %.3g), device vs pcg "
+                  "restatement pose %.3g lambda %.3g; trials %d, %d PCG iterations (restatement %d)"
+                  % (name, k, GC.pattern(rp), *got, *allowed, np.abs(P - Pp).max(), GC.rel(r["lambda_"], rp["lambda_"]), r["trials"],
+                     r["pcg_iterations"], rp["pcg_iterations"]))
+            assert np.isfinite(P).all()
+            assert _fields(r) == _fields(rp), (k, r, rp)
+            assert r["iterations_done"] == k and r["stop_reason"] == G.STOP_ITERATIONS
+            assert got[0] <= allowed[0], (k, got, allowed)
+            assert got[1] <= allowed[1], (k, got, allowed)
+            assert got[2] <= allowed[2], (k, got, allowed)
+            assert abs(r["chi2_initial"] - rp["chi2_initial"]) <= 1e-9 * rp["chi2_initial"]
+            assert P[c.fixed].tobytes() == poses[c.fixed].tobytes()       # the fixed vertex is bitwise unchanged
+        assert r["trials"] == len(c.pattern)
+        print("%s: largest share of the allowance: pose %.3g lambda %.3g chi2_final %.3g" % (name, *share))
+    finally:
+        if o is not opt:
+            o.close()
+
+
+def test_an_exact_minimum_rejects_ten_zero_steps(opt):
+    """chi2 = 0 and b = 0: every trial is a zero step with rho == 0, which `rho > 0` rejects. lambda0 is 1e-5 times a sum of
+    products of multiples of 1/4 (exact in fp64 in any order) and every later factor is a power of two, so lambda is
+    compared exactly."""
+    from aria_slam_amd import graph_ref as G
+    c = GC.BY_NAME["exact"]
+    poses, edges = GC.graph(c.name)
+    for k in (1, c.iterations):
+        P, r = opt.optimize_graph(poses, edges, c.fixed, k)
+        _Pp, rp = GC.reference(c.name, k, "pcg")
+        print("exact minimum, %d iterations:" % k, {f: r[f] for f in r if f != "record"})
+        assert P.tobytes() == poses.tobytes()
+        assert _fields(r) == _fields(rp) and (r["trials"], r["iterations_done"]) == (10, 0)
+        assert r["stop_reason"] == G.STOP_TRIALS and r["valid"] == 1
+        assert r["chi2_initial"] == 0.0 and r["chi2_final"] == 0.0
+        assert r["lambda_"] == rp["lambda_"] == 3963167672086.0366
+
+
+def test_an_overflowing_chi2_rejects_every_trial_and_returns_the_poses(opt):
+    """Every info_scale is 1e306 (finite, valid): chi2 is inf at the input and inf or NaN after any step, so every trial
+    fails the finiteness guard whatever the solver does with the non-finite system. Only what the restatement fixes is
+    asserted: the discrete fields and the poses, bitwise. The loops it runs are the ten trials and the capped PCG."""
+    from aria_slam_amd import graph_ref as G
+    c = GC.BY_NAME["overflow"]
+    poses, edges = GC.graph(c.name)
+    g = _graph("chain8")
+    P0, r0 = opt.optimize_graph(g[0], g[1], 0, 3)
+    for k in (1, c.iterations):
+        P, r = opt.optimize_graph(poses, edges, c.fixed, k)
+        _Pp, rp = GC.reference(c.name, k, "pcg")
+        print("overflow, %d iterations:" % k, {f: r[f] for f in r if f != "record"})
+        assert P.tobytes() == poses.tobytes()
+        assert _fields(r) == _fields(rp) == (0, 10, G.STOP_TRIALS, 1)
+    # nothing non-finite stays behind in the handle's scratch: a gentle graph is bitwise what it was before
+    P1, r1 = opt.optimize_graph(g[0], g[1], 0, 3)
+    assert P1.tobytes() == P0.tobytes() and r1["record"] == r0["record"] and r1["iterations_done"] == 3
 
 
 # ---- it closes loops ----------------------------------------------------------------------------------------------------------------
@@ -205,6 +296,46 @@ def test_batch_position_split_and_rerun_are_bitwise_identical(aria, opt, torch_c
         for Pk, Rk in (((P1 + P2)[k], (R1 + R2)[k]), (P3[k], R3[k]), (P4[k], R4[k])):
             assert Pk.tobytes() == P[k].tobytes() and Rk["record"] == R[k]["record"], k
         assert P[k][batch[k][2]].tobytes() == np.asarray(batch[k][0])[batch[k][2]].tobytes()     # fixed vertices
+
+
+def test_a_rejecting_graph_is_bitwise_identical_wherever_it_runs(aria, opt, torch_cuda):
+    """A graph whose LM rejects (separate104: rrrrAArAArA) alone, first, in the middle and last in a batch beside graphs that
+    never reject, in a split batch and on a handle with one slot: its poses and record are the same bits everywhere, and its
+    neighbours are bitwise what they are without it."""
+    c = GC.BY_NAME["separate104"]
+    R = GC.graph(c.name) + (c.fixed,)
+    its = c.iterations
+    others = [_graph("random7") + (0,), _graph("chain8") + (3,), _graph("floating9") + (0,)]
+    P0, r0 = opt.optimize_graph(R[0], R[1], R[2], its)
+    _Pp, rp = GC.reference(c.name, its, "pcg")
+    assert _fields(r0) == _fields(rp) and r0["trials"] == len(c.pattern) > r0["iterations_done"] == its
+    Pn, Rn, st = opt.optimize_batch(others, its)                     # the neighbours without it
+    assert st == 0 and all(r["trials"] == r["iterations_done"] == its for r in Rn)
+    one = aria.HipPoseGraphOptimizer(max_vertices=512, max_edges=1024, max_graphs=1)
+    for pos in range(len(others) + 1):
+        batch = others[:pos] + [R] + others[pos:]
+        where = [k for k in range(len(batch)) if k != pos]
+        runs = [opt.optimize_batch(batch, its)[:2]]
+        Pa, Ra, _ = opt.optimize_batch(batch[:2], its)               # split in two calls
+        Pb, Rb, _ = opt.optimize_batch(batch[2:], its)
+        runs.append((Pa + Pb, Ra + Rb))
+        runs.append(one.optimize_batch(batch, its)[:2])              # every graph its own launch
+        for P, Rs in runs:
+            assert P[pos].tobytes() == P0.tobytes() and Rs[pos]["record"] == r0["record"], pos
+            for k, n in zip(where, range(len(others))):
+                assert P[k].tobytes() == Pn[n].tobytes() and Rs[k]["record"] == Rn[n]["record"], (pos, k)
+    P1, R1, _ = one.optimize_batch([R], its)                         # alone in a batch call, alone on the one-slot handle
+    P2, R2, _ = opt.optimize_batch([R], its)
+    one.close()
+    assert P1[0].tobytes() == P2[0].tobytes() == P0.tobytes() and R1[0]["record"] == R2[0]["record"] == r0["record"]
+    # more graphs than slots: the handle's own split into launches, the rejecting graph in each of them
+    batch = [R, others[0], others[1], others[2], others[1], R, others[0]]
+    P, Rs, st = opt.optimize_batch(batch, its)
+    assert st == 0
+    for k in (0, 5):
+        assert P[k].tobytes() == P0.tobytes() and Rs[k]["record"] == r0["record"]
+    for k, n in ((1, 0), (2, 1), (3, 2), (4, 1), (6, 0)):
+        assert P[k].tobytes() == Pn[n].tobytes() and Rs[k]["record"] == Rn[n]["record"]
 
 
 # ---- the edges of the input space ------------------------------------------------------------------------------------------------------

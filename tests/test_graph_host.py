@@ -1,7 +1,8 @@
 """SE(3) pose-graph optimisation (include/aria_orb_hip.h, "SE(3) pose-graph optimisation"): the parts that need no GPU --
 exports and layouts, the NumPy restatement (aria_slam_amd/graph_ref.py: the SE(3) pieces, the Jacobians against central
-differences, PCG against the direct solve, LM's monotone chi2, the reference class's bookkeeping), the kernel's listing and
-the C++ adapter build."""
+differences, PCG against the direct solve, LM's monotone chi2, the reference class's bookkeeping), the case table of the
+rejected-trial path (tests/graph_cases.py: pattern, margin and coverage, proved with the restatement alone), the kernel's
+listing and the C++ adapter build."""
 import ctypes as C
 import os
 import re
@@ -13,6 +14,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import graph_cases as GC       # noqa: E402
 import isa_kernel_stats as S   # noqa: E402
 
 GRAPH_SYMBOLS = ["aria_graph_default_config", "aria_graph_create", "aria_graph_destroy", "aria_graph_stream", "aria_graph_check",
@@ -173,6 +176,132 @@ def test_lm_edges_of_the_input_space():
         chain.append(chain[-1] @ Z)
     P, r = G.optimize(np.array(chain), edges[:9], 0, 5)
     assert np.abs(P - np.array(chain)).max() < 1e-9 and r["chi2_final"] <= r["chi2_initial"]
+
+
+# ---- the rejected-trial path: what tests/graph_cases.py holds, decided by the restatement alone -------------------------------
+def _runs(c):
+    return GC.reference(c.name, c.iterations, "direct"), GC.reference(c.name, c.iterations, "pcg")
+
+
+def test_trace_has_one_entry_per_trial_and_changes_nothing_else():
+    from aria_slam_amd import graph_ref as G
+    c = GC.BY_NAME["separate104"]
+    poses, edges = GC.graph(c.name)
+    P, r = G.optimize(poses, edges, c.fixed, c.iterations, "pcg")
+    tr = r["trace"]
+    assert len(tr) == r["trials"] and sum(t["accepted"] for t in tr) == r["iterations_done"]
+    assert sum(t["solver_iterations"] for t in tr) == r["pcg_iterations"]
+    assert all(set(t) == {"iteration", "trial", "rho", "accepted", "lambda_", "chi2_new", "solver_iterations"} for t in tr)
+    assert [t["chi2_new"] for t in tr if t["accepted"]] == r["chi2_history"]
+    # the iteration counts up at every accept, the trial restarts at 0; lambda before a trial follows the header's rule
+    it, trial, ni = 0, 0, 2.0
+    for a, b in zip(tr, tr[1:] + [None]):
+        assert (a["iteration"], a["trial"]) == (it, trial)
+        if a["accepted"]:
+            nxt, it, trial, ni = a["lambda_"] * GC.update_factor(a["rho"]), it + 1, 0, 2.0
+        else:
+            nxt, trial, ni = a["lambda_"] * ni, trial + 1, ni * 2
+        assert nxt == (b["lambda_"] if b else r["lambda_"])
+    # a shorter call is the beginning of a longer one
+    _P, r2 = G.optimize(poses, edges, c.fixed, 2, "pcg")
+    assert r2["trace"] == tr[:len(r2["trace"])] and r2["trace"][-1]["accepted"]
+
+
+@pytest.mark.parametrize("name", [c.name for c in GC.CASES])
+def test_rejected_trial_case_has_its_pattern_under_both_solvers_with_a_margin(name):
+    """A condition on the inputs: no decision of a case is near enough to rho = 0 for another summation order to flip it."""
+    from aria_slam_amd import graph_ref as G
+    c = GC.BY_NAME[name]
+    poses, edges = GC.graph(name)
+    assert G.check_graph(len(poses), edges, c.fixed)
+    (Pd, rd), (Pp, rp) = _runs(c)
+    assert GC.pattern(rd) == GC.pattern(rp) == c.pattern
+    rho_d, rho_p = (np.array([t["rho"] for t in r["trace"]]) for r in (rd, rp))
+    for r, P in ((rd, Pd), (rp, Pp)):
+        assert r["trials"] == len(c.pattern) and r["iterations_done"] == c.pattern.count("A") and r["valid"] == 1
+        assert P[c.fixed].tobytes() == poses[c.fixed].tobytes()
+    if name not in GC.EXEMPT:
+        assert rd["iterations_done"] == c.iterations and rd["stop_reason"] == G.STOP_ITERATIONS
+        lo = np.minimum(np.abs(rho_d), np.abs(rho_p))
+        print(name, "min |rho| %.3g, min |rho| / |rho_direct - rho_pcg| %.3g" % (lo.min(), (lo / np.abs(rho_d - rho_p)).min()))
+        assert (lo >= GC.RHO_MIN).all(), lo.min()
+        assert (lo >= GC.RHO_MARGIN * np.abs(rho_d - rho_p)).all()
+        # the copied figures are this table's: one entry per k, the smallest |rho| as recorded, and every gap of every k
+        # within a factor of two of its record. On the build the table was measured on they agree to the three digits
+        # printed; the band is for another NumPy / SciPy build, where a PCG solve may stop one iteration earlier or later
+        # and move a gap by the ratio of two consecutive residuals. The device's allowance is ten times the record.
+        assert len(GC.GAPS[name]) == c.iterations and abs(GC.MIN_RHO[name] - lo.min()) <= 1e-3
+        for k in range(1, c.iterations + 1):
+            for got, want in zip(GC.gap(name, k), GC.GAPS[name][k - 1]):
+                assert 0.5 * want <= got <= 2 * want, (k, GC.gap(name, k), GC.GAPS[name][k - 1])
+        return
+    assert name not in GC.GAPS
+    for r, P in ((rd, Pd), (rp, Pp)):
+        assert (r["iterations_done"], r["trials"], r["stop_reason"]) == (0, G.MAX_TRIALS, G.STOP_TRIALS)
+        assert P.tobytes() == poses.tobytes()
+    if name == "exact":                      # exempt: rho is exactly 0, the case that tells rho > 0 from rho >= 0
+        assert not rho_d.any() and not rho_p.any()
+        lam0 = 1e-5 * max(G.linearize(poses, edges)[2][v, k, k] for v in range(1, len(poses)) for k in range(6))
+        for r in (rd, rp):
+            assert r["chi2_initial"] == r["chi2_final"] == 0.0 and r["pcg_iterations"] == 0
+            assert r["lambda_"] == lam0 * 2.0 ** 55 == 3963167672086.0366
+            assert [t["lambda_"] for t in r["trace"]] == [lam0 * 2.0 ** (k * (k + 1) // 2) for k in range(10)]
+    else:                                    # exempt: rho is not finite, the trial the finiteness guard is there for
+        assert name == "overflow" and all(np.isfinite(e[2]) for e in edges)
+        assert not np.isfinite(rho_d).any() and not np.isfinite(rho_p).any()
+        for r in (rd, rp):
+            assert not any(np.isfinite(t["chi2_new"]) for t in r["trace"]) and not np.isfinite(r["chi2_initial"])
+
+
+def test_the_table_covers_the_rejected_trial_path():
+    from aria_slam_amd import graph_ref as G
+    src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "graph_optimize.hip")).read()
+    lanes = int(re.search(r"GRAPH_BLOCK\s*=\s*(\d+)", src).group(1))
+    assert lanes == 512 and int(re.search(r"GRAPH_MAX_TRIALS\s*=\s*(\d+)", src).group(1)) == G.MAX_TRIALS == 10
+    on_chip_edges = 544                      # the on-chip form of the one-vertex-per-lane solver holds this many (DESIGN.md 13)
+    seen = set()
+    for c in GC.CASES:
+        poses, edges = GC.graph(c.name)
+        tr = GC.reference(c.name, c.iterations, "pcg")[1]["trace"]
+        rejecting = sorted({t["iteration"] for t in tr if not t["accepted"]})
+        accepts = c.pattern.count("A")
+        if c.name in GC.EXEMPT:
+            seen.add("exact minimum" if all(t["rho"] == 0.0 for t in tr) else "overflow")
+            continue
+        assert GC.pattern({"trace": tr}) == c.pattern
+        if c.pattern.count("r") == 1:
+            seen.add("one rejection, first iteration" if rejecting == [0] else "one rejection, later iteration")
+        if "rrr" in c.pattern:
+            seen.add("ni reaches 8")
+        if len(rejecting) >= 2 and accepts > rejecting[-1]:      # every iteration ends in an accept: accepts lie between
+            seen.add("separate iterations" if "separate iterations" not in seen else "separate iterations, twice")
+        if rejecting and len(poses) <= lanes and len(edges) > on_chip_edges:
+            assert c.handle and c.handle[0] <= lanes and c.handle[1] >= len(edges)
+            seen.add("off-chip W")
+        if rejecting and len(poses) > lanes:
+            assert c.handle and c.handle[0] == 1024 and c.handle[1] >= len(edges)
+            seen.add("strided solver")
+        if rejecting and len(poses) <= lanes and len(edges) <= on_chip_edges:
+            assert c.handle is None
+            seen.add("on-chip W")
+        if rejecting and c.fixed != 0:
+            seen.add("fixed vertex")
+        # the two ends of the update factor, each clear of its threshold by 0.05
+        for t in tr:
+            raw = 1.0 - (2.0 * t["rho"] - 1.0) ** 3
+            if t["accepted"] and raw <= 1.0 / 3.0 - 0.05:
+                assert t["rho"] > GC.CLAMP_RHO and GC.update_factor(t["rho"]) == 1.0 / 3.0
+                seen.add("clamp")
+            if t["accepted"] and raw >= 1.05:
+                seen.add("lambda grows on an accept")
+    want = {"one rejection, first iteration", "one rejection, later iteration", "ni reaches 8", "separate iterations",
+            "separate iterations, twice", "off-chip W", "strided solver", "on-chip W", "fixed vertex", "clamp",
+            "lambda grows on an accept", "exact minimum", "overflow"}
+    assert seen == want, want ^ seen
+    # the trials the table's notes name (there counted from 1): "clamp" trial 2, "first" trial 2, "three" trial 4
+    rho = lambda name, k: GC.reference(name, GC.BY_NAME[name].iterations, "pcg")[1]["trace"][k]["rho"]
+    assert GC.update_factor(rho("clamp", 1)) == 1.0 / 3.0 < min(GC.update_factor(rho("clamp", 0)), GC.update_factor(rho("clamp", 2)))
+    assert GC.update_factor(rho("first", 1)) > 1.05 and GC.update_factor(rho("three", 3)) > 1.05
 
 
 # ---- the reference class's bookkeeping ---------------------------------------------------------------------------------------
