@@ -63,6 +63,10 @@ EXPORTS = [
     # trajectory evaluation (ground-truth sampling, ATE / RPE, Umeyama alignment), additive to ABI 4
     "aria_eval_default_config", "aria_eval_create", "aria_eval_destroy", "aria_eval_stream", "aria_eval_check",
     "aria_eval_sample_truth_device", "aria_eval_sample_truth", "aria_eval_batch_device", "aria_eval_batch",
+    # object detector around the network (TRTInference preprocess / postprocess + NMSBoxes), additive to ABI 4
+    "aria_det_default_config", "aria_det_create", "aria_det_destroy", "aria_det_stream", "aria_det_check",
+    "aria_det_device_buffers", "aria_det_preprocess_batch_device", "aria_det_postprocess_batch_device", "aria_det_preprocess",
+    "aria_det_postprocess", "aria_det_resize_table", "aria_det_algorithmic_bytes",
 ]
 
 
@@ -190,6 +194,17 @@ EVAL_RESULT_DTYPE = np.dtype([("ate_raw", "<f8"), ("rpe_raw", "<f8"), ("scale", 
                               ("align_valid", "<i4"), ("valid", "<i4"), ("reserved", "<i4")])
 EVAL_ALIGN_NONE, EVAL_ALIGN_SE3, EVAL_ALIGN_SIM3 = 0, 1, 2
 EVAL_EST_POSE12, EVAL_EST_FUSE_STATE, EVAL_EST_XYZ = 0, 1, 2
+
+
+class DetConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("input_w", C.c_int), ("input_h", C.c_int),
+                ("max_batch", C.c_int), ("max_candidates", C.c_int), ("out_half", C.c_int), ("reserved", C.c_int)]
+
+
+# aria_detection == aria::core::Detection (24 bytes) and aria_box (16 bytes)
+DETECTION_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("confidence", "<f4"), ("class_id", "<i4")])
+BOX_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
+DET_MAX_CANDIDATES, DET_MAX_CLASS_IDS = 1024, 32
 
 
 # aria_fund_result (96 bytes)
@@ -352,6 +367,8 @@ def load_library():
         _bind_fuse(L)
     if hasattr(L, "aria_eval_create"):
         _bind_eval(L)
+    if hasattr(L, "aria_det_create"):
+        _bind_det(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -463,6 +480,26 @@ def _bind_eval(L):
     L.aria_eval_sample_truth.argtypes = [p, p, i, p, i, p, p]
     L.aria_eval_batch_device.argtypes = [p, p, i, p, i, i, p, i, i, p, i, i, p, p]
     L.aria_eval_batch.argtypes = [p, p, i, p, i, i, p, i, i, p, i, i, p, p]
+
+
+def _bind_det(L):
+    p, i, f = C.c_void_p, C.c_int, C.c_float
+    L.aria_det_default_config.restype = None
+    L.aria_det_default_config.argtypes = [p]
+    L.aria_det_create.argtypes = [p, C.POINTER(C.c_void_p)]
+    L.aria_det_destroy.restype = None
+    L.aria_det_destroy.argtypes = [p]
+    L.aria_det_stream.restype = p
+    L.aria_det_stream.argtypes = [p]
+    L.aria_det_check.argtypes = [p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.aria_det_device_buffers.argtypes = [p] + [C.POINTER(C.c_void_p)] * 6
+    L.aria_det_preprocess_batch_device.argtypes = [p, p, i, i, i, i, C.c_int64, i, i, p]
+    L.aria_det_postprocess_batch_device.argtypes = [p, p, i, i, i, i, f, f, p, i, p, p, i, p, p, i]
+    L.aria_det_preprocess.argtypes = [p, p, i, i, i, i, i, p]
+    L.aria_det_postprocess.argtypes = [p, p, i, i, i, f, f, p, i, p, i, C.POINTER(C.c_int), p, i, C.POINTER(C.c_int)]
+    L.aria_det_resize_table.argtypes = [i, i, p, i]
+    L.aria_det_algorithmic_bytes.restype = C.c_int64
+    L.aria_det_algorithmic_bytes.argtypes = [i, i, i, i, i, i]
 
 
 def status_string(status):

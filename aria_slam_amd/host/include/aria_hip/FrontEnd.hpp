@@ -27,9 +27,13 @@ struct FrontEndConfig {
     // euroc_eval.cpp:179) becomes a keyframe -- detect() against the database first, then addKeyFrame().
     int keyframe_min_matches = 8;
     // PipelineConfig::filter_dynamic_objects (include/pipeline/SlamPipeline.hpp:20): matches with an endpoint inside a
-    // detection of a dynamic class are dropped, as the legacy executable does (src/main.cpp:29-50, 164-175). The detector is
-    // not part of this repository: its boxes for the current frame arrive through FrontEnd::setDetections().
+    // detection of a dynamic class are dropped, as the legacy executable does (src/main.cpp:29-50, 164-175). The boxes of the
+    // current frame come from the injected detector (FrontEnd::setDetector: aria_hip/HipObjectDetector.hpp runs everything
+    // around the network on the device; only the network itself is not part of this repository) or, without one, arrive
+    // through FrontEnd::setDetections().
     bool filter_dynamic_objects = true;
+    float detector_conf = 0.5f;        // IObjectDetector's defaults (IObjectDetector.hpp:26-27; main.cpp:150 uses the same)
+    float detector_nms = 0.45f;
     // When the injected pair is OrbHipExtractor + HipMatcher on one device, the descriptors stay on the device between the
     // two calls -- the getGpuDescriptors() / matchGpu hand-off the reference declares (OrbCudaExtractor.hpp:34-35,
     // CudaMatcher.hpp:22-28): no descriptor upload per frame. If both were also constructed on the SAME stream
@@ -71,7 +75,14 @@ public:
 
     // Detections of the NEXT frame to be processed (the reference runs YOLO beside ORB on the same image, main.cpp:132-150);
     // consumed by that processFrame call.
-    void setDetections(std::vector<core::Detection> detections) { detections_ = std::move(detections); }
+    void setDetections(std::vector<core::Detection> detections) { detections_ = std::move(detections); have_detections_ = true; }
+    // Optional injected detector (SlamPipeline's constructor takes one, include/pipeline/SlamPipeline.hpp:32-40). With one,
+    // every processFrame whose detections were not set by hand runs it beside the extraction (main.cpp:132-150): detectAsync
+    // before extract, getDetections after -- the same matches as setDetections() with that detector's output for the frame.
+    // A HipObjectDetector gets the gray image as it is (detectGray); any other implementation gets it replicated to RGB.
+    // Without one, nothing changes.
+    void setDetector(interfaces::ObjectDetectorPtr detector) { detector_ = std::move(detector); }
+    interfaces::IObjectDetector* detector() { return detector_.get(); }
     void setCallback(std::function<void(const FrontEndResult&)> cb) { callback_ = std::move(cb); }
     std::uint64_t framesProcessed() const { return next_id_; }
     interfaces::IFeatureExtractor& extractor() { return *extractor_; }
@@ -88,8 +99,11 @@ private:
     interfaces::FeatureExtractorPtr extractor_;
     interfaces::MatcherPtr matcher_;
     interfaces::LoopDetectorPtr loop_detector_;
+    interfaces::ObjectDetectorPtr detector_;
     FrontEndConfig cfg_;
     std::vector<core::Detection> detections_;
+    bool have_detections_ = false;                // setDetections() was called for the next frame
+    std::vector<std::uint8_t> rgb_;               // the gray image replicated for a detector that is not the HIP one
     std::unique_ptr<core::Frame> cur_, prev_;
     FrontEndResult result_;
     std::function<void(const FrontEndResult&)> callback_;

@@ -8,6 +8,7 @@
 #include <memory>
 
 #include "aria_hip/FrontEnd.hpp"
+#include "aria_hip/HipObjectDetector.hpp"
 #include "aria_hip/compat.hpp"
 
 namespace aria::factory {
@@ -34,5 +35,12 @@ struct HipComponents {
 
 HipComponents createHipComponents(const HipFactoryConfig& cfg);
 std::unique_ptr<pipeline::FrontEnd> createHip(const HipFactoryConfig& cfg = {});
+// The fourth component SlamPipeline's constructor takes (include/pipeline/SlamPipeline.hpp:32-40): the detector around the
+// caller's network, on cfg.hip_device. It gets a stream of its own unless det.stream names one (the reference's detector has
+// its own too, TRTInference.cpp:53), so it runs beside the extraction. createHip(cfg, hook) also injects it into the FrontEnd.
+interfaces::ObjectDetectorPtr createHipDetector(const HipFactoryConfig& cfg, adapters::hip::HipObjectDetector::InferenceHook hook,
+                                                adapters::hip::ObjectDetectorConfig det = {});
+std::unique_ptr<pipeline::FrontEnd> createHip(const HipFactoryConfig& cfg, adapters::hip::HipObjectDetector::InferenceHook hook,
+                                              adapters::hip::ObjectDetectorConfig det = {});
 
 }  // namespace aria::factory

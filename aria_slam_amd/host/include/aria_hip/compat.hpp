@@ -12,6 +12,7 @@
 #include "interfaces/ILoopDetector.hpp"
 #include "interfaces/IMapper.hpp"
 #include "interfaces/IMatcher.hpp"
+#include "interfaces/IObjectDetector.hpp"
 #include "interfaces/ISensorFusion.hpp"
 #else
 
@@ -158,6 +159,19 @@ public:
     }
 };
 using MatcherPtr = std::unique_ptr<IMatcher>;
+
+// include/interfaces/IObjectDetector.hpp:10-48 (image_data: RGB, row-major, 3 channels)
+class IObjectDetector {
+public:
+    virtual ~IObjectDetector() = default;
+    virtual void detect(const std::uint8_t* image_data, int width, int height, std::vector<core::Detection>& detections,
+                        float conf_threshold = 0.5f, float nms_threshold = 0.45f) = 0;
+    virtual void detectAsync(const std::uint8_t* image_data, int width, int height) = 0;
+    virtual void getDetections(std::vector<core::Detection>& detections, float conf_threshold = 0.5f,
+                               float nms_threshold = 0.45f) = 0;
+    virtual void sync() = 0;
+};
+using ObjectDetectorPtr = std::unique_ptr<IObjectDetector>;
 
 // include/interfaces/ILoopDetector.hpp:11-31
 class ILoopDetector {

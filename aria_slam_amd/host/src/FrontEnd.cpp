@@ -6,6 +6,7 @@
 #include <utility>
 
 #include "aria_hip/HipMatcher.hpp"
+#include "aria_hip/HipObjectDetector.hpp"
 #include "aria_hip/OrbHipExtractor.hpp"
 
 namespace aria::pipeline {
@@ -102,7 +103,20 @@ const FrontEndResult& FrontEnd::processFrame(const std::uint8_t* image_data, int
     f->id = next_id_++;
     f->timestamp = timestamp;
     result_.matches.clear();
+    // the detector runs beside the extraction (main.cpp:132-150); a frame whose detections were set by hand keeps those
+    const bool run_detector = detector_ && cfg_.filter_dynamic_objects && !have_detections_;
+    if (run_detector) {
+        if (auto* hd = dynamic_cast<adapters::hip::HipObjectDetector*>(detector_.get())) {
+            hd->detectGrayAsync(image_data, width, height);
+        } else {
+            rgb_.resize((std::size_t)width * height * 3);                       // GRAY2BGR, src/euroc_eval.cpp:149
+            for (std::size_t i = 0, n = (std::size_t)width * height; i < n; i++) rgb_[3 * i] = rgb_[3 * i + 1] = rgb_[3 * i + 2] = image_data[i];
+            detector_->detectAsync(rgb_.data(), width, height);
+        }
+    }
     extractAndMatch(image_data, width, height, *f);
+    if (run_detector) detector_->getDetections(detections_, cfg_.detector_conf, cfg_.detector_nms);
+    have_detections_ = false;
 
     prev_ = std::move(cur_);
     cur_ = std::move(f);

@@ -39,4 +39,17 @@ std::unique_ptr<pipeline::FrontEnd> createHip(const HipFactoryConfig& cfg) {
     return fe;
 }
 
+interfaces::ObjectDetectorPtr createHipDetector(const HipFactoryConfig& cfg, adapters::hip::HipObjectDetector::InferenceHook hook,
+                                                adapters::hip::ObjectDetectorConfig det) {
+    det.device = cfg.hip_device;
+    return std::make_unique<adapters::hip::HipObjectDetector>(std::move(hook), det);
+}
+
+std::unique_ptr<pipeline::FrontEnd> createHip(const HipFactoryConfig& cfg, adapters::hip::HipObjectDetector::InferenceHook hook,
+                                              adapters::hip::ObjectDetectorConfig det) {
+    std::unique_ptr<pipeline::FrontEnd> fe = createHip(cfg);
+    fe->setDetector(createHipDetector(cfg, std::move(hook), std::move(det)));
+    return fe;
+}
+
 }  // namespace aria::factory

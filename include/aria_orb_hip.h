@@ -950,6 +950,99 @@ int   aria_eval_batch(aria_eval_t h, const void* est, int est_kind, const int* o
                       const aria_eval_truth* truth, int n_truth, int truth_shared, const uint8_t* mask_or_null, int align_mode,
                       int rpe_delta, double* pose_err_or_null, aria_eval_result* results);
 
+/* ---- object detector: everything the reference does AROUND its network, on the device and batched over frames. The
+ * reference's detector (include/interfaces/IObjectDetector.hpp:10-46; src/legacy/TRTInference.cpp) resizes and repacks the
+ * image on the host (TRTInference::preprocess, :68-93), runs the engine, copies the [300, 6] head back and decodes it on the
+ * host (TRTInference::postprocess, :95-142, with cv::dnn::NMSBoxes): two blocking copies per frame. Here the network is the
+ * caller's (anything that reads d_input and writes d_raw on a stream) and the two stages around it are kernels, so the boxes
+ * reach aria_flag_keypoints_device without leaving HBM. aria_slam_amd/detect_ref.py restates both stages in NumPy and is the
+ * definition; the device is bitwise equal to it. Additive to ABI 4.
+ *
+ * Preprocess. cv::resize(image, Size(input_w, input_h)) as the 8-bit INTER_LINEAR fixed-point path computes it (a stretch,
+ *   no letterbox): per axis, in fp32, f = (d + 0.5f) * (src / (float)dst) - 0.5f, s = floor(f), f -= s; s < 0 -> s = 0, f = 0;
+ *   s >= src - 1 -> s = src - 1, f = 0 (both taps the last pixel); weights a = cvRound(f * 2048) and 2048 - a. Horizontal pass
+ *   S = p[s] * (2048 - a) + p[s + 1] * a in int32, vertical pass (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.
+ *   The value is then (float)v * (float)(1.0 / 255.0) (convertTo, :76), stored planar (HWC -> CHW, :79-87) as fp32, or rounded
+ *   once to fp16 (nearest even) when the handle was created with out_half. channels = 3: interleaved pixels; swap_rb = 1
+ *   exchanges planes 0 and 2 (cvtColor BGR2RGB, :75). channels = 1: the gray plane written three times (what GRAY2BGR in front
+ *   of detect() gives, src/euroc_eval.cpp:149).
+ * Postprocess. Frame f's candidates are n_candidates rows [x1, y1, x2, y2, confidence, class_id] of floats in network-input
+ *   coordinates. scale_x = (float)src_width / input_w, scale_y likewise (:164-165). A candidate takes part when
+ *   confidence >= conf (:116; NaN fails) and confidence > conf (NMSBoxes' own, strict, test); bx = (int)(x * scale) is the fp32
+ *   product truncated toward zero (:118-121); class_id = (int)raw[5]. NMSBoxes: stable sort by descending score (ties keep
+ *   candidate order), then greedy in that order: a box is kept when 1.f - (float)jaccardDistance(box, k) <= nms for EVERY box k
+ *   kept before it -- a suppressed box suppresses nothing. jaccardDistance on Rect(x1, y1, x2 - x1, y2 - y1) in fp64: 0 when
+ *   Aa + Ab <= DBL_EPSILON, else 1 - Aab / (Aa + Ab - Aab), the intersection empty when its width or height is <= 0.
+ *   Kept boxes are written in that order as aria_detection (corners (float)bx1, by1, bx2, by2); those whose class is in the
+ *   dynamic set are also written as aria_box -- the corners mode 0 of aria_flag_keypoints_device expects.
+ * Divergences from the reference, both where it is undefined: a candidate with a non-finite coordinate or a scaled
+ *   coordinate outside +-2^20 is dropped before NMS (the cast to int is undefined there); areas are exact (cv::Rect::area()
+ *   overflows int). class_id saturates at the int range and is 0 for a NaN.
+ * Determinism. No float atomics; a frame's rows depend on its own candidates only: reproducible run to run and independent
+ *   of the frame's place in the batch and of its neighbours. */
+typedef struct aria_det_s* aria_det_t;
+/* == aria::core::Detection (include/core/Types.hpp:103-112), 24 bytes */
+typedef struct { float x1, y1, x2, y2, confidence; int class_id; } aria_detection;
+#define ARIA_DET_MAX_CANDIDATES 1024
+#define ARIA_DET_MAX_CLASS_IDS 32
+typedef struct {
+    int   struct_size;     /* = sizeof(aria_det_config)                                                       */
+    int   device;
+    void* stream;          /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking: not ordered
+                            * against the legacy default stream, see aria_pose_config). The network runs on a stream of the
+                            * caller's choice: give the handle THAT stream, or order the three steps with events          */
+    int   input_w;         /* network input size (default 640 x 640, TRTInference.cpp:38-40)                  */
+    int   input_h;
+    int   max_batch;       /* frames per call (default 1)                                                     */
+    int   max_candidates;  /* rows of the network's head per frame, <= 1024 (default 300, TRTInference.cpp:105) */
+    int   out_half;        /* 0: d_input is fp32 (default), 1: fp16                                           */
+    int   reserved;
+} aria_det_config;         /* 40 bytes */
+
+void  aria_det_default_config(aria_det_config* cfg);
+int   aria_det_create(const aria_det_config* cfg, aria_det_t* out);
+void  aria_det_destroy(aria_det_t h);
+void* aria_det_stream(aria_det_t h);
+/* Synchronises the handle's stream and returns the deferred error of the postprocess calls since the last check, once:
+ * ARIA_E_OUTPUT_TOO_SMALL when some frame kept more rows than det_cap or box_cap (its lists were truncated and its counts
+ * are the truncated ones); *det_rows_needed / *box_rows_needed (either may be NULL) then tell the largest counts any frame
+ * needed since the last check (0 when nothing was truncated on that side). */
+int   aria_det_check(aria_det_t h, int* det_rows_needed, int* box_rows_needed);
+/* Buffers that belong to the handle, allocated on the first call, for callers without a device allocator of their own (the
+ * C++ adapter): max_batch network inputs (3 * input_h * input_w elements each), max_batch * max_candidates * 6 floats of raw
+ * head, and max_batch * max_candidates rows of each result list with their counts. Any output pointer may be NULL. */
+int   aria_det_device_buffers(aria_det_t h, void** d_input, float** d_raw, aria_detection** d_dets, int** d_ndets,
+                              aria_box** d_boxes, int** d_nboxes);
+/* TRTInference::preprocess (src/legacy/TRTInference.cpp:68-93) for n_frames images in HBM: frame f at d_images +
+ * f * frame_stride, rows row_stride bytes apart (what aria_orb_extract_batch_device reads, as it lies), channels 1 or 3.
+ * Writes d_input[f][3][input_h][input_w] (fp32 or fp16; 16-byte aligned for full-width stores). Enqueued on the handle's
+ * stream, no synchronisation. Argument errors (channels, n_frames > max_batch, non-positive sizes, sizes above 16384,
+ * strides smaller than the rows they hold) are returned before any launch. */
+int   aria_det_preprocess_batch_device(aria_det_t h, const uint8_t* d_images, int n_frames, int width, int height,
+                                       int row_stride, int64_t frame_stride, int channels, int swap_rb, void* d_input);
+/* TRTInference::postprocess (src/legacy/TRTInference.cpp:95-142) for n_frames heads in HBM: frame f's candidates at d_raw +
+ * f * n_candidates * 6. class_ids: HOST list of up to 32 dynamic class ids; NULL = the ten of src/main.cpp:29-40;
+ * n_class_ids < 0 = every class. Writes frame f's detections at d_dets + f * det_cap and d_ndets[f]; when d_boxes is not NULL
+ * the dynamic subset at d_boxes + f * box_cap and d_nboxes[f] -- the layout aria_flag_keypoints_device reads. One workgroup
+ * per frame. Enqueued on the handle's stream, no synchronisation; truncation is deferred to aria_det_check. */
+int   aria_det_postprocess_batch_device(aria_det_t h, const float* d_raw, int n_frames, int n_candidates, int src_width,
+                                        int src_height, float conf, float nms, const int* class_ids, int n_class_ids,
+                                        aria_detection* d_dets, int* d_ndets, int det_cap, aria_box* d_boxes, int* d_nboxes,
+                                        int box_cap);
+/* Blocking host forms on caller-owned host buffers (staged through the handle). image: packed rows of row_stride bytes;
+ * input: 3 * input_h * input_w elements. raw: n_candidates * 6 floats; up to det_cap / box_cap rows are written and
+ * *n_dets / *n_boxes are the counts NEEDED: ARIA_E_OUTPUT_TOO_SMALL when one exceeds its capacity. boxes / n_boxes may be NULL. */
+int   aria_det_preprocess(aria_det_t h, const uint8_t* image, int width, int height, int row_stride, int channels, int swap_rb,
+                          void* input);
+int   aria_det_postprocess(aria_det_t h, const float* raw, int n_candidates, int src_width, int src_height, float conf, float nms,
+                           const int* class_ids, int n_class_ids, aria_detection* dets, int det_cap, int* n_dets,
+                           aria_box* boxes, int box_cap, int* n_boxes);
+/* The per-axis table of the resize (host-only, no handle, for tests): entry d = first tap | weight of the second tap << 16.
+ * Returns the entries written or a negative status. */
+int   aria_det_resize_table(int src, int dst, uint32_t* out, int cap);
+/* Algorithmic bytes of one preprocessed frame: width * height * channels read + 3 * input_w * input_h * element written. */
+int64_t aria_det_algorithmic_bytes(int width, int height, int channels, int input_w, int input_h, int out_half);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
