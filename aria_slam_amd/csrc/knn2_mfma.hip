@@ -9,8 +9,8 @@
 // widened to a byte: v_mfma_i32_32x32x32_i8, one instruction = 32 trains x 32 queries x 32 bits in 32 cycles, against
 // 8 x (v_xor + v_bcnt) per single pair on the vector ALU. The bytes are scaled (train bit -> -128, query bit -> 64)
 // and the accumulator is preloaded with 4096 popcount(t) + train index, so that the MFMA itself delivers the sortable
-// key  4096 (popcount(t) - 2 |q & t|) + index  and the vector ALU is left with exactly the running top-2 (two
-// v_med3 per distance). All arithmetic is integer: bit-identical to the VALU kernel.
+// key  4096 (popcount(t) - 2 |q & t|) + index  and the vector ALU is left with exactly the running top-2 (five
+// three-input instructions per four distances, top2_quad). All arithmetic is integer: bit-identical to the VALU kernel.
 // Why single-bit bytes (0x80 / 0x40 / 0) and not +-1 or +-127: the matrix pipe's clock gives way under load by
 // operand toggle rate (tools/microbench/mfma_i8_power.hip: 16.3 ns per MFMA per SIMD on zeros, 17.2 on single-bit
 // bytes, 20.4 on +-64 x +-127, 22.1 on random bytes) -- the sparse encoding is worth 15 % of the kernel.
@@ -102,13 +102,55 @@ __device__ __forceinline__ int sum8(int v) {
     return v;
 }
 
-// (m1 <= m2) <- the two smallest of {m1, m2, key}; all three are positive normal floats by bit pattern, so
-// min(a, b) = med3(a, b, +0) and no NaN/denormal rule is ever involved (fminf would add a canonicalising v_max)
+// Running top-2 of a lane: (m1 <= m2) are the two smallest keys seen so far. All keys are positive normal floats by bit
+// pattern (kKeyBias; the FP4 values are positive), so the integer order of the bits is the float order, no NaN/denormal rule is
+// ever involved (fminf would add a canonicalising v_max) and v_min3_i32 on the bits agrees with v_med3_f32 on the values.
+//
+// Grouped form (the product), four new keys d0..d3 per step:
+//     tA = med3(m1, d0, d1)    b1  = min3(m1, d0, d1)
+//     tB = med3(b1, d2, d3)    m1' = min3(b1, d2, d3)
+//     m2' = min3(m2, tA, tB)
+// med3(m1, d0, d1) is the second smallest of the three, and m2 >= m1 >= min3(m1, d0, d1) always, so the second smallest of
+// {m1, m2, d0, d1} is min(m2, tA); two such steps share one min3 on the runner-up chain. Five three-input instructions per
+// four keys (1.25 per key), exact for any multiset -- equal keys included (the kNone / kNoneF padding and the initial values
+// repeat) -- because the two smallest VALUES of a multiset do not depend on how they are found.
+// Per-distance form (-DARIA_KNN_TOP2_SINGLE=1, the form until round 5, kept for A/B builds through tools/build_ab.sh):
+//     m2' = med3(m1, m2, d)    m1' = med3(m1, d, +0) = min(m1, d)          two instructions per key.
+#ifndef ARIA_KNN_TOP2_SINGLE
+#define ARIA_KNN_TOP2_SINGLE 0
+#endif
+// independent (m1, m2) chains per column tile, fed in turn and merged in the epilogue: the per-distance form needs two for
+// instruction-level parallelism; the grouped form is one chain (dependency depth 8 min3 per 16 keys)
+#ifndef ARIA_KNN_TOP2_CHAINS
+#define ARIA_KNN_TOP2_CHAINS (ARIA_KNN_TOP2_SINGLE ? 2 : 1)
+#endif
+constexpr int kChains = ARIA_KNN_TOP2_CHAINS;
+static_assert(kChains == 1 || kChains == 2, "one or two top-2 chains per column tile");
+
 __device__ __forceinline__ void top2_update(float& m1, float& m2, int key) {
     const float k = __int_as_float(key);
     const float n2 = __builtin_amdgcn_fmed3f(m1, m2, k);
     m1 = __builtin_amdgcn_fmed3f(m1, k, 0.0f);
     m2 = n2;
+}
+__device__ __forceinline__ float min3_bits(float a, float b, float c) {      // -> v_min3_i32
+    return __int_as_float(min(min(__float_as_int(a), __float_as_int(b)), __float_as_int(c)));
+}
+__device__ __forceinline__ void top2_quad(float& m1, float& m2, float d0, float d1, float d2, float d3) {
+    const float tA = __builtin_amdgcn_fmed3f(m1, d0, d1);
+    const float b1 = min3_bits(m1, d0, d1);
+    const float tB = __builtin_amdgcn_fmed3f(b1, d2, d3);
+    m1 = min3_bits(b1, d2, d3);
+    m2 = min3_bits(m2, tA, tB);
+}
+// (best, runner-up) bit patterns of a column tile from its chains
+__device__ __forceinline__ void top2_merge_chains(const float (&m1)[kChains], const float (&m2)[kChains], int& a1, int& a2) {
+    a1 = __float_as_int(m1[0]); a2 = __float_as_int(m2[0]);
+    if (kChains == 2) {
+        const int x1 = a1, x2 = a2, y1 = __float_as_int(m1[kChains - 1]), y2 = __float_as_int(m2[kChains - 1]);
+        a1 = min(x1, y1);
+        a2 = min(max(x1, y1), min(x2, y2));
+    }
 }
 
 // key -> (distance << 16 | train index), the form the rest of the matcher uses
@@ -181,12 +223,12 @@ __device__ __forceinline__ void knn2_body(
         }
     };
 
-    // running (best, runner-up) per column tile, two independent chains (even / odd accumulator registers)
-    float m1[NC][2], m2[NC][2];
+    // running (best, runner-up) per column tile (kChains chains, see top2_quad)
+    float m1[NC][kChains], m2[NC][kChains];
 #pragma unroll
     for (int c = 0; c < NC; c++)
 #pragma unroll
-        for (int p = 0; p < 2; p++) { m1[c][p] = __int_as_float(0x7F7FFFFF); m2[c][p] = __int_as_float(0x7F7FFFFF); }
+        for (int p = 0; p < kChains; p++) { m1[c][p] = __int_as_float(0x7F7FFFFF); m2[c][p] = __int_as_float(0x7F7FFFFF); }
 
     const int it0 = tsplit ? (int)blockIdx.y * tsplit : 0;
     const int ntiles = tsplit ? min((nt + TT - 1) / TT, it0 + tsplit) : (nt + TT - 1) / TT;
@@ -217,26 +259,35 @@ __device__ __forceinline__ void knn2_body(
                     acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], B[cp][s], acc0, 0, 0, 0);
                     acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[s], B[cp + 1][s], acc1, 0, 0, 0);
                 }
+#if ARIA_KNN_TOP2_SINGLE
 #pragma unroll
                 for (int j = 0; j < 16; j++) {
-                    top2_update(m1[cp][j & 1], m2[cp][j & 1], WIDE ? (acc0[j] << 10) + bs[j] : acc0[j]);
-                    top2_update(m1[cp + 1][j & 1], m2[cp + 1][j & 1], WIDE ? (acc1[j] << 10) + bs[j] : acc1[j]);
+                    top2_update(m1[cp][j % kChains], m2[cp][j % kChains], WIDE ? (acc0[j] << 10) + bs[j] : acc0[j]);
+                    top2_update(m1[cp + 1][j % kChains], m2[cp + 1][j % kChains], WIDE ? (acc1[j] << 10) + bs[j] : acc1[j]);
                 }
+#else
+                auto key0 = [&](int j) { return __int_as_float(WIDE ? (acc0[j] << 10) + bs[j] : acc0[j]); };
+                auto key1 = [&](int j) { return __int_as_float(WIDE ? (acc1[j] << 10) + bs[j] : acc1[j]); };
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    top2_quad(m1[cp][g % kChains], m2[cp][g % kChains], key0(4 * g), key0(4 * g + 1), key0(4 * g + 2), key0(4 * g + 3));
+                    top2_quad(m1[cp + 1][g % kChains], m2[cp + 1][g % kChains], key1(4 * g), key1(4 * g + 1), key1(4 * g + 2),
+                              key1(4 * g + 3));
+                }
+#endif
             }
         }
         store_tile(it + 1, buf ^ 1);
         __syncthreads();
     }
 
-    // merge the two chains of a column tile, then lanes l and l ^ 32 (same query, disjoint trains); plain integer
+    // merge the chains of a column tile, then lanes l and l ^ 32 (same query, disjoint trains); plain integer
     // compares from here on
     uint32_t k0[NC], k1[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) {
-        const int x1 = __float_as_int(m1[c][0]), x2 = __float_as_int(m2[c][0]);
-        const int y1 = __float_as_int(m1[c][1]), y2 = __float_as_int(m2[c][1]);
-        const int a1 = min(x1, y1);
-        const int a2 = min(max(x1, y1), min(x2, y2));
+        int a1, a2;
+        top2_merge_chains(m1[c], m2[c], a1, a2);
         const int p1 = __shfl_xor(a1, 32), p2 = __shfl_xor(a2, 32);
         k0[c] = final_key<WIDE>(min(a1, p1), pq[c]);
         k1[c] = final_key<WIDE>(min(max(a1, p1), min(a2, p2)), pq[c]);
@@ -274,7 +325,7 @@ __device__ __forceinline__ void knn2_body(
 // form covers 32, with fp32 accumulators in which everything here is an exact integer multiple of 2^-12:
 //     key = (popcount(t) + 257 - 2 |q & t|) + index / 4096          (< 1024, 22 significant bits)
 // preloaded as (popcount(t) + 257) + index / 4096, so the MFMA again delivers the sortable key and the vector ALU keeps the
-// running top-2 with v_med3_f32 on the VALUES (all positive). Fragments are half the size of the int8 ones (16 bytes per lane
+// running top-2 on the VALUES (all positive: v_med3_f32, and v_min3_i32 on their bit patterns). Fragments are half the size of the int8 ones (16 bytes per lane
 // and k-step of 64 bits): half the LDS traffic and registers per distance. Lane map as above: row / column = lane & 31,
 // K half = lane >> 5 (32 bits -> 32 nibbles), identical for A and B.
 constexpr int kRowF = 144;           // LDS bytes per widened train: 128 + 16 (ds_read_b128 of the 16-lane groups conflict-free)
@@ -346,11 +397,11 @@ __device__ __forceinline__ void knn2_body_fp4(
         }
     };
 
-    float m1[NC][2], m2[NC][2];
+    float m1[NC][kChains], m2[NC][kChains];
 #pragma unroll
     for (int c = 0; c < NC; c++)
 #pragma unroll
-        for (int p = 0; p < 2; p++) { m1[c][p] = 3.0e38f; m2[c][p] = 3.0e38f; }
+        for (int p = 0; p < kChains; p++) { m1[c][p] = 3.0e38f; m2[c][p] = 3.0e38f; }
 
     const int it0 = tsplit ? (int)blockIdx.y * tsplit : 0;
     const int ntiles = tsplit ? min((nt + TT - 1) / TT, it0 + tsplit) : (nt + TT - 1) / TT;
@@ -383,20 +434,27 @@ __device__ __forceinline__ void knn2_body_fp4(
                     acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b0, acc0, 4, 4, 0, 0, 0, 0);
                     acc1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b1, acc1, 4, 4, 0, 0, 0, 0);
                 }
+#if ARIA_KNN_TOP2_SINGLE
 #pragma unroll
                 for (int j = 0; j < 16; j++) {
-                    { const float k = acc0[j]; const float n2 = __builtin_amdgcn_fmed3f(m1[cp][j & 1], m2[cp][j & 1], k);
-                      m1[cp][j & 1] = __builtin_amdgcn_fmed3f(m1[cp][j & 1], k, 0.0f); m2[cp][j & 1] = n2; }
-                    { const float k = acc1[j]; const float n2 = __builtin_amdgcn_fmed3f(m1[cp + 1][j & 1], m2[cp + 1][j & 1], k);
-                      m1[cp + 1][j & 1] = __builtin_amdgcn_fmed3f(m1[cp + 1][j & 1], k, 0.0f); m2[cp + 1][j & 1] = n2; }
+                    top2_update(m1[cp][j % kChains], m2[cp][j % kChains], __float_as_int(acc0[j]));
+                    top2_update(m1[cp + 1][j % kChains], m2[cp + 1][j % kChains], __float_as_int(acc1[j]));
                 }
+#else
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    top2_quad(m1[cp][g % kChains], m2[cp][g % kChains], acc0[4 * g], acc0[4 * g + 1], acc0[4 * g + 2], acc0[4 * g + 3]);
+                    top2_quad(m1[cp + 1][g % kChains], m2[cp + 1][g % kChains], acc1[4 * g], acc1[4 * g + 1], acc1[4 * g + 2],
+                              acc1[4 * g + 3]);
+                }
+#endif
             }
         }
         store_tile(it + 1, buf ^ 1);
         __syncthreads();
     }
 
-    // merge the two chains of a column tile, then lanes l and l ^ 32 (same query, disjoint trains): the keys are positive
+    // merge the chains of a column tile, then lanes l and l ^ 32 (same query, disjoint trains): the keys are positive
     // floats, whose order is the order of their bit patterns
     uint32_t k0[NC], k1[NC];
     auto to_key = [&](int bits, int pqc) -> uint32_t {
@@ -408,10 +466,8 @@ __device__ __forceinline__ void knn2_body_fp4(
     };
 #pragma unroll
     for (int c = 0; c < NC; c++) {
-        const int x1 = __float_as_int(m1[c][0]), x2 = __float_as_int(m2[c][0]);
-        const int y1 = __float_as_int(m1[c][1]), y2 = __float_as_int(m2[c][1]);
-        const int a1 = min(x1, y1);
-        const int a2 = min(max(x1, y1), min(x2, y2));
+        int a1, a2;
+        top2_merge_chains(m1[c], m2[c], a1, a2);
         const int p1 = __shfl_xor(a1, 32), p2 = __shfl_xor(a2, 32);
         k0[c] = to_key(min(a1, p1), pq[c]);
         k1[c] = to_key(min(max(a1, p1), min(a2, p2)), pq[c]);
@@ -448,9 +504,27 @@ __device__ __forceinline__ void knn2_body_fp4(
 // 128-train tiles instead of 64: +0.4 %. The int8 kernel above: 297.3 k / 0.778. A software-pipelined inner loop (the MFMAs of
 // column tile c between the top-2 updates of tile c - 1) needs 220 VGPRs = 2 waves per SIMD and measures 0.50 us like this form
 // at 3: the two pipes overlap across waves, not inside one.
-constexpr int kFp4Nc = 4, kFp4Tt = 64;
+// Round 6, with the grouped top-2 (5 instead of 8 vector instructions per MFMA), the same shapes again (two bench.py runs each
+// in one session, frames/s / kNN-2 us per pair): 512 queries at 3 waves 384.0 k, 381.3 k / 0.453, 0.455; at 2 waves 385.2 k,
+// 385.0 k / 0.489, 0.487; 1024 queries at 2 waves 397.9 k, 397.4 k / 0.438, 0.437; 256 queries at 4 waves 391.9 k, 389.4 k /
+// 0.505, 0.515; 128-train tiles 382.2 k, 381.8 k / 0.455, 0.465; the grouped update on two chains 380.1 k, 382.0 k / 0.443,
+// 0.458. The 1024-query shape is ahead by more than the spread in these two rounds but has not been through the six-run
+// interleaved rule, and a workgroup of 1024 queries does the full work for a pair with a few hundred: not adopted, DESIGN.md
+// section 4. The shapes are built through tools/build_ab.sh with the three defines below (NC column tiles of 32 queries per
+// wave, TT trains per staged tile, waves per SIMD the batch kernel is compiled for). The product takes the defaults.
+#ifndef ARIA_KNN_FP4_NC
+#define ARIA_KNN_FP4_NC 4
+#endif
+#ifndef ARIA_KNN_FP4_TT
+#define ARIA_KNN_FP4_TT 64
+#endif
+#ifndef ARIA_KNN_FP4_WAVES
+#define ARIA_KNN_FP4_WAVES 3
+#endif
+constexpr int kFp4Nc = ARIA_KNN_FP4_NC, kFp4Tt = ARIA_KNN_FP4_TT;
+static_assert(kFp4Nc % 2 == 0 && kFp4Tt % 32 == 0, "column tiles go in pairs, train tiles in row tiles of 32");
 template <int MODE, int NC, int TT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NC == kFp4Nc ? 3 : 2))) void k_knn2_fp4(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NC == kFp4Nc && TT == kFp4Tt ? ARIA_KNN_FP4_WAVES : 2))) void k_knn2_fp4(
     const uint8_t* __restrict__ q, const int* __restrict__ nq_arr, int nq_fixed, const uint8_t* __restrict__ t,
     const int* __restrict__ nt_arr, int nt_fixed, int64_t q_stride, int64_t t_stride, uint2* __restrict__ keys, int maxq,
     double ratio, int* __restrict__ good, int tsplit, const int* __restrict__ gate, int gate_want) {
