@@ -67,6 +67,9 @@ EXPORTS = [
     "aria_det_default_config", "aria_det_create", "aria_det_destroy", "aria_det_stream", "aria_det_check",
     "aria_det_device_buffers", "aria_det_preprocess_batch_device", "aria_det_postprocess_batch_device", "aria_det_preprocess",
     "aria_det_postprocess", "aria_det_resize_table", "aria_det_algorithmic_bytes",
+    # sparse stereo on rectified pairs (depth per keypoint, metric scale of a relative pose), additive to ABI 4
+    "aria_stereo_default_config", "aria_stereo_create", "aria_stereo_destroy", "aria_stereo_stream", "aria_stereo_check",
+    "aria_stereo_match_batch_device", "aria_stereo_match", "aria_stereo_scale_batch_device", "aria_stereo_scale_pose",
 ]
 
 
@@ -224,6 +227,20 @@ MAP_POINT_DTYPE = np.dtype([("id", "<u8"), ("X", "<f8", (3,)), ("quality", "<f8"
                             ("match", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("gray", "u1"), ("pad", "u1", (7,))])
 
 
+class StereoConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("baseline", C.c_double), ("min_disparity", C.c_double),
+                ("max_disparity", C.c_double), ("band_factor", C.c_double), ("median_factor", C.c_double),
+                ("th_hamming", C.c_int), ("sad_half_window", C.c_int), ("sad_slide", C.c_int), ("max_octave_diff", C.c_int),
+                ("min_scale_matches", C.c_int), ("reserved", C.c_int)]
+
+
+# aria_stereo_obs (32 bytes) and aria_stereo_scale (16 bytes)
+STEREO_OBS_DTYPE = np.dtype([("u_right", "<f4"), ("disparity", "<f4"), ("depth", "<f4"), ("X", "<f4"), ("Y", "<f4"),
+                             ("right_idx", "<i4"), ("hamming", "<i4"), ("sad", "<i4")])
+STEREO_SCALE_DTYPE = np.dtype([("scale", "<f8"), ("n_used", "<i4"), ("valid", "<i4")])
+
+
 class AriaError(RuntimeError):
     def __init__(self, status, where=""):
         self.status = status
@@ -369,6 +386,8 @@ def load_library():
         _bind_eval(L)
     if hasattr(L, "aria_det_create"):
         _bind_det(L)
+    if hasattr(L, "aria_stereo_create"):
+        _bind_stereo(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -500,6 +519,22 @@ def _bind_det(L):
     L.aria_det_resize_table.argtypes = [i, i, p, i]
     L.aria_det_algorithmic_bytes.restype = C.c_int64
     L.aria_det_algorithmic_bytes.argtypes = [i, i, i, i, i, i]
+
+
+def _bind_stereo(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    L.aria_stereo_default_config.restype = None
+    L.aria_stereo_default_config.argtypes = [p]
+    L.aria_stereo_create.argtypes = [p, C.POINTER(C.c_void_p)]
+    L.aria_stereo_destroy.restype = None
+    L.aria_stereo_destroy.argtypes = [p]
+    L.aria_stereo_stream.restype = p
+    L.aria_stereo_stream.argtypes = [p]
+    L.aria_stereo_check.argtypes = [p]
+    L.aria_stereo_match_batch_device.argtypes = [p, p, p, i64, i, i, i, p, p, p, p, p, p, i64, i, p, p, p, i]
+    L.aria_stereo_match.argtypes = [p, p, p, i, i, i, p, p, i, p, p, i, p, p, C.POINTER(C.c_int)]
+    L.aria_stereo_scale_batch_device.argtypes = [p, p, p, p, p, i, i, p, p, p, p, i64, i, p]
+    L.aria_stereo_scale_pose.argtypes = [p, p, p, p, i, i, p, i, p, i, p]
 
 
 def status_string(status):

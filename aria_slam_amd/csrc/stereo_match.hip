@@ -1,0 +1,743 @@
+// Sparse stereo on rectified pairs: a depth per left keypoint and the metric scale of a relative pose. Semantics in
+// include/aria_orb_hip.h ("sparse stereo"); aria_slam_amd/stereo_ref.py is the definition and this file equals it bit for bit.
+//
+// k_stereo_match  one 256-thread workgroup per pair, one launch:
+//   sort     the pair's right keypoints by integer row into LDS (counting sort over the H rows: histogram, scan, scatter --
+//            integer LDS atomics only; the order inside a row is free because the winner is the minimum of (distance, j))
+//   search   16 lanes per left keypoint, 16 keypoints per round: the candidates are the contiguous LDS span of the rows
+//            within the widest band of the allowed octaves (+-1 row of slack for the fp32 subtraction); every candidate takes
+//            the exact fp32 tests of the header and 8 xor + popcount on the descriptor, four candidates per lane and step
+//            with their descriptor loads issued together; min over the 16 lanes by shuffles
+//   slide    the same 16 lanes, a lane per shift: (2w+1) rows of v_sad_u8 on unaligned dwords, the odd tail column taken as
+//            the window's last dword shifted down (both sides alike, so genuine zero pixels count); the window size is a
+//            template constant, so a window's loads are all in flight together; the best shift and its two neighbours by
+//            shuffles inside the 16-lane row (no LDS, no barrier in the keypoint loop); lane 0 does the fp32 sub-pixel chain
+//   median   exact selection of the SAD at index n/2 by two 256-bin integer histograms (high byte gathered on the fly)
+//   filter   records above median_factor * med reset to unmatched; survivors compacted in left-index order (ballot + mbcnt)
+// k_stereo_scale  one workgroup per pose: s_m of the usable matches as order-preserving 64-bit keys in LDS, the value at
+//   index n/2 by an 8-pass radix selection (integer histograms), so the fp64 result has no order dependence at all.
+// No float atomics. No grid barrier.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+
+#include "common.h"
+#include "orb_plan.h"
+
+using namespace aria;
+
+static_assert(sizeof(aria_stereo_obs) == 32, "aria_stereo_obs is 32 bytes");
+static_assert(sizeof(aria_stereo_scale) == 16, "aria_stereo_scale is 16 bytes");
+static_assert(sizeof(aria_stereo_config) == 112, "aria_stereo_config is 112 bytes");
+
+namespace {
+
+constexpr int ST_BLOCK = 256;
+constexpr int ST_GROUP = 16;                       // lanes per left keypoint
+constexpr int ST_KPB = ST_BLOCK / ST_GROUP;        // left keypoints per round
+constexpr int ST_MAX_KP = 8192;                    // kp_stride / match_cap bound: 16 B of LDS per right keypoint
+constexpr int ST_MAX_DIM = 4096;                   // image side bound: 4 B of LDS per row
+constexpr int ST_MAX_W = 7, ST_MAX_L = 16;
+constexpr int ST_MAX_SHIFTS = 2 * ST_MAX_L + 1;
+constexpr int ST_PASSES = (ST_MAX_SHIFTS + ST_GROUP - 1) / ST_GROUP;
+constexpr int ST_UNROLL = 4;                        // candidates per lane and step of the search
+constexpr int ERRBIT_STEREO_INPUT = 1;
+
+struct StereoParams {
+    float fx, fy, cx, cy, fb, mind, maxd, band, medf;
+    int th, w, L, mod;
+    float scale[kLevels];
+};
+
+__device__ __forceinline__ aria_stereo_obs unmatched_obs() {
+    aria_stereo_obs o;
+    o.u_right = 0.0f; o.disparity = 0.0f; o.depth = -1.0f; o.X = 0.0f; o.Y = 0.0f;
+    o.right_idx = -1; o.hamming = 0; o.sad = 0;
+    return o;
+}
+
+__device__ __forceinline__ float level_scale(const StereoParams& prm, int o) {
+    const int k = min(max(o, 0), kLevels - 1);
+    float s = prm.scale[0];
+#pragma unroll
+    for (int l = 1; l < kLevels; l++) s = (k == l) ? prm.scale[l] : s;   // no runtime-indexed array: stays in registers
+    return s;
+}
+
+__device__ __forceinline__ int row_key(float y, int H) { return (int)fminf(fmaxf(floorf(y), 0.0f), (float)(H - 1)); }
+
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
+// A window row of 2 HW + 1 (odd, 3..15) bytes at p as four dwords, bytes beyond the width zero. Reads nothing outside the row:
+// the tail is the dword that ENDS at the last byte, shifted down past the bytes the full dwords already hold.
+template <int HW>
+__device__ __forceinline__ void load_row(const uint8_t* p, uint32_t r[4]) {
+    constexpr int width = 2 * HW + 1, nfull = width >> 2, rem = width & 3;
+#pragma unroll
+    for (int k = 0; k < 4; k++) r[k] = 0;
+#pragma unroll
+    for (int k = 0; k < nfull; k++) r[k] = ld_u32(p + 4 * k);
+    if constexpr (width >= 4) r[nfull] = ld_u32(p + width - 4) >> (8 * (4 - rem));
+    else r[0] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+}
+
+// SAD of the left window at lp against the right windows at rp + shift, shift = lane + 16 * pass < nsh: one shift per lane and
+// pass. Every row loop has a constant trip count, so the loads of a whole window are issued together.
+template <int HW>
+__device__ __forceinline__ void sad_slide(const uint8_t* lp, const uint8_t* rp, int pitch, int lane, int nsh,
+                                          uint32_t acc[ST_PASSES]) {
+    constexpr int width = 2 * HW + 1, nd = (width + 3) / 4;
+    uint32_t a[width][4];
+#pragma unroll
+    for (int r = 0; r < width; r++) load_row<HW>(lp + (int64_t)r * pitch, a[r]);
+#pragma unroll
+    for (int ps = 0; ps < ST_PASSES; ps++) {
+        const int sh = lane + ps * ST_GROUP;
+        if (sh < nsh) {
+            uint32_t b[width][4];
+#pragma unroll
+            for (int r = 0; r < width; r++) load_row<HW>(rp + (int64_t)r * pitch + sh, b[r]);
+            uint32_t t = 0;
+#pragma unroll
+            for (int r = 0; r < width; r++)
+#pragma unroll
+                for (int q = 0; q < nd; q++) t = __builtin_amdgcn_sad_u8(a[r][q], b[r][q], t);
+            acc[ps] = t;
+        }
+    }
+}
+
+// wave-ordered stable compaction of one 256-thread round: this lane's slot (valid when keep) and the round's total
+__device__ __forceinline__ int block_compact(bool keep, int* wsum, int& total) {
+    const unsigned long long b = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    if (lane == 0) wsum[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < ST_BLOCK / 64; w++) {
+        before += (w < wave) ? wsum[w] : 0;
+        total += wsum[w];
+    }
+    __syncthreads();
+    return before + rank;
+}
+
+// index of the bin holding rank k of a 256-bin histogram (k < total); k becomes the rank inside that bin
+__device__ __forceinline__ int hist_select(const int* hist, int& k) {
+    int cum = 0, b = 0;
+    for (; b < 255; b++) {
+        const int c = hist[b];
+        if (cum + c > k) break;
+        cum += c;
+    }
+    k -= cum;
+    return b;
+}
+
+__global__ __launch_bounds__(ST_BLOCK) void k_stereo_match(
+    const uint8_t* __restrict__ img_l, const uint8_t* __restrict__ img_r, int64_t img_stride, int W, int H, int pitch,
+    const aria_keypoint* __restrict__ kp_l, const uint8_t* __restrict__ desc_l, const int* __restrict__ n_l,
+    const aria_keypoint* __restrict__ kp_r, const uint8_t* __restrict__ desc_r, const int* __restrict__ n_r, int64_t kp_stride,
+    StereoParams prm, aria_stereo_obs* __restrict__ obs, aria_match* __restrict__ matches, int* __restrict__ nmatches,
+    int match_cap, int* __restrict__ err) {
+    extern __shared__ int st_lds[];
+    __shared__ int s_hist[256];
+    __shared__ int s_part[ST_BLOCK];
+    __shared__ int wsum[ST_BLOCK / 64];
+    __shared__ int s_n, s_bin, s_k, s_med;
+
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int nL = n_l[p], nR = n_r[p];
+    aria_stereo_obs* po = obs + (int64_t)p * kp_stride;
+    const aria_stereo_obs none = unmatched_obs();
+    if (nL < 0 || nL > kp_stride || nR < 0 || nR > kp_stride) {   // uniform: the pair is skipped
+        for (int64_t i = tid; i < kp_stride; i += ST_BLOCK) po[i] = none;
+        if (tid == 0) {
+            nmatches[p] = 0;
+            atomicOr(err, ERRBIT_STEREO_INPUT);
+        }
+        return;
+    }
+    int* pos = st_lds;                                   // [H]: row histogram -> row starts -> (after the scatter) row ends
+    float* rx = (float*)(st_lds + H);
+    float* ry = rx + kp_stride;
+    int* ro = (int*)(ry + kp_stride);
+    int* rj = ro + kp_stride;
+    const aria_keypoint* kl = kp_l + (int64_t)p * kp_stride;
+    const aria_keypoint* kr = kp_r + (int64_t)p * kp_stride;
+    const uint8_t* dl = desc_l + (int64_t)p * kp_stride * 32;
+    const uint8_t* dr = desc_r + (int64_t)p * kp_stride * 32;
+    const uint8_t* il = img_l + (int64_t)p * img_stride;
+    const uint8_t* ir = img_r + (int64_t)p * img_stride;
+
+    for (int64_t i = nL + tid; i < kp_stride; i += ST_BLOCK) po[i] = none;
+    for (int r = tid; r < H; r += ST_BLOCK) pos[r] = 0;
+    s_hist[tid] = 0;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+
+    // ---- sort the right keypoints by row ----
+    for (int j = tid; j < nR; j += ST_BLOCK) atomicAdd(&pos[row_key(kr[j].y, H)], 1);
+    __syncthreads();
+    {
+        const int chunk = (H + ST_BLOCK - 1) / ST_BLOCK, r0 = tid * chunk, r1 = min(r0 + chunk, H);
+        int sum = 0;
+        for (int r = r0; r < r1; r++) sum += pos[r];
+        s_part[tid] = sum;
+        __syncthreads();
+        int run = 0;
+        for (int t = 0; t < tid; t++) run += s_part[t];
+        for (int r = r0; r < r1; r++) {
+            const int c = pos[r];
+            pos[r] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < nR; j += ST_BLOCK) {
+        const aria_keypoint k = kr[j];
+        const int slot = atomicAdd(&pos[row_key(k.y, H)], 1);
+        rx[slot] = k.x; ry[slot] = k.y; ro[slot] = k.octave; rj[slot] = j;
+    }
+    __syncthreads();
+
+    // ---- per left keypoint: candidates, SAD slide, sub-pixel ----
+    // No workgroup barrier inside the loop: a keypoint lives in one 16-lane row of one wave, so the waves run ahead of each
+    // other and hide each other's load latency.
+    const int g = tid / ST_GROUP, l = tid % ST_GROUP;
+    const int nsh = 2 * prm.L + 1;
+    for (int base = 0; base < nL; base += ST_KPB) {      // uniform trip count: every lane reaches the shuffles
+        const int i = base + g;
+        const bool live = i < nL;
+        aria_keypoint k{};
+        int best = INT_MAX;
+        if (live) {
+            k = kl[i];
+            const uint4 a0 = *reinterpret_cast<const uint4*>(dl + (int64_t)i * 32);
+            const uint4 a1 = *reinterpret_cast<const uint4*>(dl + (int64_t)i * 32 + 16);
+            const int omax = (int)min(max((long long)k.octave + prm.mod, 0ll), (long long)(kLevels - 1));
+            const float rmax = prm.band * level_scale(prm, omax);
+            const float flo = fminf(fmaxf(floorf(k.y - rmax) - 1.0f, 0.0f), (float)(H - 1));
+            const float fhi = fminf(fmaxf(floorf(k.y + rmax) + 1.0f, 0.0f), (float)(H - 1));
+            const int lo = (int)flo, hi = (int)fhi;
+            const int s = lo > 0 ? pos[lo - 1] : 0, e = pos[hi];
+            const float xlo = k.x - prm.maxd, xhi = k.x - prm.mind;
+            // four candidates per lane and step, their descriptors fetched before any test is known: the loads of a step
+            // are in flight together (a slot past the span re-reads its last entry and is discarded)
+            for (int c0 = s; c0 < e; c0 += ST_UNROLL * ST_GROUP) {
+#pragma unroll
+                for (int u = 0; u < ST_UNROLL; u++) {
+                    const int c = c0 + u * ST_GROUP + l;
+                    const int cc = min(c, e - 1);
+                    const float xr = rx[cc], yr = ry[cc];
+                    const int orr = ro[cc], j = rj[cc];
+                    const uint4 b0 = *reinterpret_cast<const uint4*>(dr + (int64_t)j * 32);
+                    const uint4 b1 = *reinterpret_cast<const uint4*>(dr + (int64_t)j * 32 + 16);
+                    const long long od = (long long)orr - (long long)k.octave;
+                    const bool ok = c < e && (od <= prm.mod && -od <= prm.mod) &&
+                                    (fabsf(yr - k.y) <= prm.band * level_scale(prm, orr)) && (xlo <= xr && xr <= xhi);
+                    const int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
+                                  __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+                    best = ok ? min(best, (d << 16) | j) : best;   // least distance, ties to the lowest j
+                }
+            }
+        }
+#pragma unroll
+        for (int m = ST_GROUP / 2; m > 0; m >>= 1) best = min(best, __shfl_xor(best, m, ST_GROUP));
+        const int j = best & 0xFFFF, ham = best >> 16;
+        bool ok = live && best != INT_MAX && ham < prm.th;
+        int ul = 0, vl = 0, ur = 0;
+        if (ok) {
+            const float big = 1.0e6f;
+            ul = (int)rintf(fminf(fmaxf(k.x, -big), big));
+            vl = (int)rintf(fminf(fmaxf(k.y, -big), big));
+            ur = (int)rintf(fminf(fmaxf(kr[j].x, -big), big));
+            const int w = prm.w, L = prm.L;
+            ok = ul - w >= 0 && ul + w <= W - 1 && vl - w >= 0 && vl + w <= H - 1 && ur - L - w >= 0 && ur + L + w <= W - 1;
+        }
+        uint32_t acc[ST_PASSES];
+#pragma unroll
+        for (int ps = 0; ps < ST_PASSES; ps++) acc[ps] = 0;
+        if (ok) {
+            const int64_t row0 = (int64_t)(vl - prm.w) * pitch;
+            const uint8_t* lp = il + row0 + (ul - prm.w);
+            const uint8_t* rp = ir + row0 + (ur - prm.L - prm.w);
+            switch (prm.w) {                             // uniform; the window size as a constant unrolls the rows
+                case 1: sad_slide<1>(lp, rp, pitch, l, nsh, acc); break;
+                case 2: sad_slide<2>(lp, rp, pitch, l, nsh, acc); break;
+                case 3: sad_slide<3>(lp, rp, pitch, l, nsh, acc); break;
+                case 4: sad_slide<4>(lp, rp, pitch, l, nsh, acc); break;
+                case 5: sad_slide<5>(lp, rp, pitch, l, nsh, acc); break;
+                case 6: sad_slide<6>(lp, rp, pitch, l, nsh, acc); break;
+                default: sad_slide<7>(lp, rp, pitch, l, nsh, acc); break;
+            }
+        }
+        // the best shift of the row: least SAD, ties to the lowest shift, as the minimum of (sad << 6 | shift); its two
+        // neighbours come from the lanes (and passes) that hold them
+        int pk = INT_MAX;
+#pragma unroll
+        for (int ps = 0; ps < ST_PASSES; ps++) {
+            const int sh = l + ps * ST_GROUP;
+            pk = (sh < nsh) ? min(pk, (int)((acc[ps] << 6) | (uint32_t)sh)) : pk;
+        }
+#pragma unroll
+        for (int m = ST_GROUP / 2; m > 0; m >>= 1) pk = min(pk, __shfl_xor(pk, m, ST_GROUP));
+        const int bi = pk & 63, bv = pk >> 6;
+        int d1 = 0, d3 = 0;
+#pragma unroll
+        for (int ps = 0; ps < ST_PASSES; ps++) {
+            const int v1 = __shfl((int)acc[ps], (bi - 1) & (ST_GROUP - 1), ST_GROUP);
+            const int v3 = __shfl((int)acc[ps], (bi + 1) & (ST_GROUP - 1), ST_GROUP);
+            d1 = (((bi - 1) >> 4) == ps) ? v1 : d1;
+            d3 = (((bi + 1) >> 4) == ps) ? v3 : d3;
+        }
+        if (live && l == 0) {
+            aria_stereo_obs o = none;
+            if (ok && bi != 0 && bi != nsh - 1) {
+                const int d2 = bv;
+                const int den = 2 * (d1 + d3 - 2 * d2);
+                if (den != 0) {
+                    const float delta = (float)(d1 - d3) / (float)den;
+                    float disp = (float)(ul - ur - (bi - prm.L)) - delta;
+                    if (prm.mind <= disp && disp < prm.maxd) {
+                        disp = fmaxf(disp, 0.01f);
+                        const float depth = prm.fb / disp;
+                        o.u_right = k.x - disp;
+                        o.disparity = disp;
+                        o.depth = depth;
+                        o.X = (k.x - prm.cx) * depth / prm.fx;
+                        o.Y = (k.y - prm.cy) * depth / prm.fy;
+                        o.right_idx = j; o.hamming = ham; o.sad = d2;
+                        atomicAdd(&s_hist[d2 >> 8], 1);
+                        atomicAdd(&s_n, 1);
+                    }
+                }
+            }
+            po[i] = o;
+        }
+    }
+    __syncthreads();                                     // the records and the histogram are complete
+
+    // ---- the SAD at index n/2 of the ascending list ----
+    const int n = s_n;
+    if (n > 0) {
+        if (tid == 0) {
+            int kk = n / 2;
+            s_bin = hist_select(s_hist, kk);
+            s_k = kk;
+        }
+        __syncthreads();
+        const int bin = s_bin;
+        s_hist[tid] = 0;
+        __syncthreads();
+        for (int i = tid; i < nL; i += ST_BLOCK) {
+            const aria_stereo_obs o = po[i];
+            if (o.right_idx >= 0 && (o.sad >> 8) == bin) atomicAdd(&s_hist[o.sad & 255], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int kk = s_k;
+            s_med = (bin << 8) | hist_select(s_hist, kk);
+        }
+        __syncthreads();
+    }
+    const float cut = prm.medf * (float)(n > 0 ? s_med : 0);
+
+    // ---- filter + compaction in left-index order ----
+    aria_match* pm = matches + (int64_t)p * match_cap;
+    int run = 0;
+    for (int base = 0; base < nL; base += ST_BLOCK) {
+        const int i = base + tid;
+        bool keep = false;
+        aria_stereo_obs o = none;
+        if (i < nL) {
+            o = po[i];
+            keep = o.right_idx >= 0 && !((float)o.sad > cut);
+            if (o.right_idx >= 0 && !keep) po[i] = none;
+        }
+        int total;
+        const int slot = block_compact(keep, wsum, total);
+        if (keep) {
+            aria_match m;
+            m.query_idx = i; m.train_idx = o.right_idx; m.distance = (float)o.hamming;
+            pm[run + slot] = m;
+        }
+        run += total;
+    }
+    if (tid == 0) nmatches[p] = run;
+}
+
+// fp64 -> a 64-bit key whose unsigned order is the numeric order, and back
+__device__ __forceinline__ unsigned long long order_key(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_value(unsigned long long k) {
+    const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+    return __longlong_as_double((long long)b);
+}
+
+__global__ __launch_bounds__(ST_BLOCK) void k_stereo_scale(
+    const aria_pose_result* __restrict__ pose, const uint8_t* __restrict__ mask, const aria_match* __restrict__ matches,
+    const int* __restrict__ nmatches, int match_cap, int query_is_first, const aria_stereo_obs* __restrict__ obs_q,
+    const int* __restrict__ nq, const aria_stereo_obs* __restrict__ obs_t, const int* __restrict__ nt, int64_t kp_stride,
+    int min_matches, aria_stereo_scale* __restrict__ out, int* __restrict__ err) {
+    extern __shared__ unsigned long long sc_keys[];      // [match_cap]
+    __shared__ int s_hist[256];
+    __shared__ int wsum[ST_BLOCK / 64];
+    __shared__ int bad, s_digit, s_k;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int n = nmatches[p], nqp = nq[p], ntp = nt[p];
+    if (tid == 0) bad = (n < 0 || n > match_cap || nqp < 0 || nqp > kp_stride || ntp < 0 || ntp > kp_stride) ? 1 : 0;
+    __syncthreads();
+    const aria_match* mp = matches + (int64_t)p * match_cap;
+    if (!bad) {
+        int mine = 0;
+        for (int i = tid; i < n; i += ST_BLOCK) {
+            const aria_match a = mp[i];
+            mine |= (a.query_idx < 0 || a.query_idx >= nqp || a.train_idx < 0 || a.train_idx >= ntp);
+        }
+        if (mine) atomicOr(&bad, 1);
+    }
+    __syncthreads();
+    aria_stereo_scale res;
+    res.scale = 1.0; res.n_used = 0; res.valid = 0;
+    const aria_pose_result* pr = pose + p;
+    if (bad || !pr->valid) {
+        if (tid == 0) {
+            out[p] = res;
+            if (bad) atomicOr(err, ERRBIT_STEREO_INPUT);
+        }
+        return;
+    }
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; k++) R[k] = pr->R[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] = pr->t[k];
+    const aria_stereo_obs* oq = obs_q + (int64_t)p * kp_stride;
+    const aria_stereo_obs* ot = obs_t + (int64_t)p * kp_stride;
+    const uint8_t* mk = mask ? mask + (int64_t)p * match_cap : nullptr;
+    int run = 0;
+    for (int base = 0; base < n; base += ST_BLOCK) {
+        const int i = base + tid;
+        bool use = false;
+        double s = 0.0;
+        if (i < n && (!mk || mk[i])) {
+            const aria_match a = mp[i];
+            const aria_stereo_obs q = oq[a.query_idx], tr = ot[a.train_idx];
+            const aria_stereo_obs o1 = query_is_first ? q : tr, o2 = query_is_first ? tr : q;
+            use = o1.right_idx >= 0 && o2.right_idx >= 0;
+            const double x1 = o1.X, y1 = o1.Y, z1 = o1.depth, x2 = o2.X, y2 = o2.Y, z2 = o2.depth;
+            const double d0 = x2 - (R[0] * x1 + R[1] * y1 + R[2] * z1);
+            const double d1 = y2 - (R[3] * x1 + R[4] * y1 + R[5] * z1);
+            const double d2 = z2 - (R[6] * x1 + R[7] * y1 + R[8] * z1);
+            s = t[0] * d0 + t[1] * d1 + t[2] * d2;
+        }
+        int total;
+        const int slot = block_compact(use, wsum, total);
+        if (use) sc_keys[run + slot] = order_key(s);
+        run += total;
+    }
+    __syncthreads();
+    res.n_used = run;
+    if (run < min_matches || run == 0) {
+        if (tid == 0) out[p] = res;
+        return;
+    }
+    // radix selection of rank run / 2, most significant byte first
+    unsigned long long prefix = 0;
+    if (tid == 0) s_k = run / 2;
+    for (int pass = 0; pass < 8; pass++) {
+        const int shift = 56 - 8 * pass;
+        s_hist[tid] = 0;
+        __syncthreads();
+        for (int i = tid; i < run; i += ST_BLOCK) {
+            const unsigned long long key = sc_keys[i];
+            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_hist[(int)((key >> shift) & 255)], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int kk = s_k;
+            s_digit = hist_select(s_hist, kk);
+            s_k = kk;
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)s_digit << shift;
+    }
+    if (tid == 0) {
+        const double sc = key_value(prefix);
+        if (sc > 0.0) { res.scale = sc; res.valid = 1; }
+        out[p] = res;
+    }
+}
+
+}  // namespace
+
+// ---- C-ABI --------------------------------------------------------------------------------------------------------------
+struct aria_stereo_s {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    aria_stereo_config cfg{};
+    StereoParams prm{};
+    int* d_err = nullptr;
+    // single-pair staging of the blocking host forms (grow-only)
+    uint8_t* d_img = nullptr;          size_t img_cap = 0;     // left, right: 2 * W * H
+    aria_keypoint* d_kp = nullptr;     size_t kp_cap = 0;      // left, right: 2 * cap
+    uint8_t* d_desc = nullptr;         size_t desc_cap = 0;    // 2 * cap * 32
+    aria_stereo_obs* d_obs = nullptr;  size_t obs_cap = 0;     // match: cap; scale: query + train
+    aria_match* d_m = nullptr;         size_t m_cap = 0;
+    uint8_t* d_mask = nullptr;         size_t mask_cap = 0;
+    int* d_counts = nullptr;                                   // 4 ints
+    aria_pose_result* d_pose = nullptr;
+    aria_stereo_scale* d_scale = nullptr;
+};
+
+namespace {
+
+template <typename T>
+int grow(aria_stereo_s* h, T*& p, size_t& cap, size_t need) {
+    if (need <= cap) return ARIA_OK;
+    ARIA_HIP(hipStreamSynchronize(h->stream));
+    if (p) { ARIA_HIP(hipFree(p)); p = nullptr; cap = 0; }
+    ARIA_HIP(hipMalloc((void**)&p, need * sizeof(T)));
+    cap = need;
+    return ARIA_OK;
+}
+
+bool fin(double v) { return std::isfinite(v); }
+
+bool bad_config(const aria_stereo_config* c) {
+    return !c || c->struct_size != (int)sizeof(aria_stereo_config) || !(c->fx > 0) || !(c->fy > 0) || !fin(c->fx) || !fin(c->fy) ||
+           !fin(c->cx) || !fin(c->cy) || !(c->baseline > 0) || !fin(c->baseline) || !fin(c->min_disparity) ||
+           !fin(c->max_disparity) || !(c->max_disparity > c->min_disparity) || !(c->band_factor >= 0) || !fin(c->band_factor) ||
+           !(c->median_factor >= 0) || !fin(c->median_factor) || c->th_hamming < 0 || c->th_hamming > 257 ||
+           c->sad_half_window < 1 || c->sad_half_window > ST_MAX_W || c->sad_slide < 1 || c->sad_slide > ST_MAX_L ||
+           c->max_octave_diff < 0 || c->max_octave_diff > kLevels || c->min_scale_matches < 1;
+}
+
+StereoParams make_params(const aria_stereo_config& c) {
+    StereoParams p{};
+    p.fx = (float)c.fx; p.fy = (float)c.fy; p.cx = (float)c.cx; p.cy = (float)c.cy;
+    p.fb = p.fx * (float)c.baseline;                     // the product formed once, in fp32
+    p.mind = (float)c.min_disparity; p.maxd = (float)c.max_disparity;
+    p.band = (float)c.band_factor; p.medf = (float)c.median_factor;
+    p.th = c.th_hamming; p.w = c.sad_half_window; p.L = c.sad_slide; p.mod = c.max_octave_diff;
+    // scale[o] of aria_orb_level_info (orb_plan.cpp layer_scale)
+    for (int l = 0; l < kLevels; l++) p.scale[l] = (float)std::pow((double)kScaleFactor, (double)l);
+    return p;
+}
+
+size_t match_lds_bytes(int H, int64_t kp_stride) { return ((size_t)H + 4 * (size_t)kp_stride) * sizeof(int); }
+
+}  // namespace
+
+extern "C" {
+
+void aria_stereo_default_config(aria_stereo_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->struct_size = (int)sizeof(aria_stereo_config);
+    c->fx = 458.654; c->fy = 457.296; c->cx = 367.215; c->cy = 248.375;   // EuRoC cam0, as the pose and map stages
+    c->baseline = 0.110;                                                   // EuRoC's nominal stereo baseline
+    c->min_disparity = 0.0;
+    c->max_disparity = c->fx;                                              // depth >= baseline
+    c->band_factor = 2.0;
+    c->median_factor = 2.1;
+    c->th_hamming = 75;
+    c->sad_half_window = 5;
+    c->sad_slide = 5;
+    c->max_octave_diff = 1;
+    c->min_scale_matches = 5;
+}
+
+int aria_stereo_create(const aria_stereo_config* c, aria_stereo_t* out) {
+    if (!out || bad_config(c)) return ARIA_E_INVALID;
+    *out = nullptr;
+    int ndev = 0;
+    ARIA_HIP(hipGetDeviceCount(&ndev));
+    if (c->device < 0 || c->device >= ndev) {
+        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
+        return ARIA_E_NO_DEVICE;
+    }
+    ARIA_HIP(hipSetDevice(c->device));
+    aria_stereo_s* h = new (std::nothrow) aria_stereo_s();
+    if (!h) return ARIA_E_OOM;
+    h->device = c->device;
+    h->cfg = *c;
+    h->prm = make_params(*c);
+    if (c->stream) {
+        h->stream = (hipStream_t)c->stream;
+    } else {
+        hipError_t e = create_stream(&h->stream);
+        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
+        h->owns_stream = true;
+    }
+    hipError_t e = hipMalloc((void**)&h->d_err, sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_pose, sizeof(aria_pose_result));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_scale, sizeof(aria_stereo_scale));
+    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, sizeof(int));
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_match), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)match_lds_bytes(ST_MAX_DIM, ST_MAX_KP));
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_scale), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                ST_MAX_KP * (int)sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        const int rc = hip_fail(e, "aria_stereo_create", __FILE__, __LINE__);
+        aria_stereo_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return ARIA_OK;
+}
+
+void aria_stereo_destroy(aria_stereo_t h) {
+    if (!h) return;
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    void* bufs[] = {h->d_err, h->d_img, h->d_kp, h->d_desc, h->d_obs, h->d_m, h->d_mask, h->d_counts, h->d_pose, h->d_scale};
+    for (void* b : bufs)
+        if (b) hipFree(b);
+    if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
+    delete h;
+}
+
+void* aria_stereo_stream(aria_stereo_t h) { return h ? (void*)h->stream : nullptr; }
+
+int aria_stereo_check(aria_stereo_t h) {
+    if (!h) return ARIA_E_INVALID;
+    ARIA_HIP(hipSetDevice(h->device));
+    ARIA_HIP(hipStreamSynchronize(h->stream));
+    int bits = 0;
+    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
+    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    return (bits & ERRBIT_STEREO_INPUT) ? ARIA_E_INVALID : ARIA_OK;
+}
+
+int aria_stereo_match_batch_device(aria_stereo_t h, const uint8_t* d_img_left, const uint8_t* d_img_right, int64_t img_stride,
+                                   int width, int height, int pitch, const aria_keypoint* d_kp_left,
+                                   const uint8_t* d_desc_left, const int* d_n_left, const aria_keypoint* d_kp_right,
+                                   const uint8_t* d_desc_right, const int* d_n_right, int64_t kp_stride, int n_pairs,
+                                   aria_stereo_obs* d_obs, aria_match* d_matches, int* d_nmatches, int match_cap) {
+    if (!h || !d_img_left || !d_img_right || !d_kp_left || !d_desc_left || !d_n_left || !d_kp_right || !d_desc_right ||
+        !d_n_right || !d_obs || !d_matches || !d_nmatches || n_pairs < 0 || kp_stride < 1 || kp_stride > ST_MAX_KP ||
+        match_cap < kp_stride || width < 1 || height < 1 || width > ST_MAX_DIM || height > ST_MAX_DIM || pitch < width ||
+        (n_pairs > 1 && img_stride < (int64_t)pitch * (height - 1) + width))
+        return ARIA_E_INVALID;
+    if (n_pairs == 0) return ARIA_OK;
+    ARIA_HIP(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_stereo_match, dim3(n_pairs), dim3(ST_BLOCK), match_lds_bytes(height, kp_stride), h->stream, d_img_left,
+                       d_img_right, img_stride, width, height, pitch, d_kp_left, d_desc_left, d_n_left, d_kp_right, d_desc_right,
+                       d_n_right, kp_stride, h->prm, d_obs, d_matches, d_nmatches, match_cap, h->d_err);
+    ARIA_HIP(hipGetLastError());
+    return ARIA_OK;
+}
+
+int aria_stereo_match(aria_stereo_t h, const uint8_t* img_left, const uint8_t* img_right, int width, int height, int pitch,
+                      const aria_keypoint* kp_left, const uint8_t* desc_left, int n_left, const aria_keypoint* kp_right,
+                      const uint8_t* desc_right, int n_right, aria_stereo_obs* obs, aria_match* matches, int* n_matches) {
+    if (!h || !img_left || !img_right || width < 1 || height < 1 || width > ST_MAX_DIM || height > ST_MAX_DIM || pitch < width ||
+        n_left < 0 || n_right < 0 || n_left > ST_MAX_KP || n_right > ST_MAX_KP || (n_left && (!kp_left || !desc_left || !obs)) ||
+        (n_right && (!kp_right || !desc_right)))
+        return ARIA_E_INVALID;
+    if (n_matches) *n_matches = 0;
+    ARIA_HIP(hipSetDevice(h->device));
+    const size_t cap = (size_t)std::max(std::max(n_left, n_right), 1), px = (size_t)width * height;
+    int rc;
+    if ((rc = grow(h, h->d_img, h->img_cap, 2 * px)) != ARIA_OK) return rc;
+    if ((rc = grow(h, h->d_kp, h->kp_cap, 2 * cap)) != ARIA_OK) return rc;
+    if ((rc = grow(h, h->d_desc, h->desc_cap, 2 * cap * 32)) != ARIA_OK) return rc;
+    if ((rc = grow(h, h->d_obs, h->obs_cap, cap)) != ARIA_OK) return rc;
+    if ((rc = grow(h, h->d_m, h->m_cap, cap)) != ARIA_OK) return rc;
+    // the staging halves sit at the buffers' current capacity, not at this call's
+    aria_keypoint* d_kr = h->d_kp + h->kp_cap / 2;
+    uint8_t* d_dr = h->d_desc + h->desc_cap / 2;
+    uint8_t* d_ir = h->d_img + h->img_cap / 2;
+    const int counts[4] = {n_left, n_right, 0, 0};
+    ARIA_HIP(hipMemcpy2DAsync(h->d_img, (size_t)width, img_left, (size_t)pitch, (size_t)width, (size_t)height,
+                              hipMemcpyHostToDevice, h->stream));
+    ARIA_HIP(hipMemcpy2DAsync(d_ir, (size_t)width, img_right, (size_t)pitch, (size_t)width, (size_t)height,
+                              hipMemcpyHostToDevice, h->stream));
+    if (n_left) {
+        ARIA_HIP(hipMemcpyAsync(h->d_kp, kp_left, sizeof(aria_keypoint) * n_left, hipMemcpyHostToDevice, h->stream));
+        ARIA_HIP(hipMemcpyAsync(h->d_desc, desc_left, (size_t)32 * n_left, hipMemcpyHostToDevice, h->stream));
+    }
+    if (n_right) {
+        ARIA_HIP(hipMemcpyAsync(d_kr, kp_right, sizeof(aria_keypoint) * n_right, hipMemcpyHostToDevice, h->stream));
+        ARIA_HIP(hipMemcpyAsync(d_dr, desc_right, (size_t)32 * n_right, hipMemcpyHostToDevice, h->stream));
+    }
+    ARIA_HIP(memcpy_on(h->stream, h->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
+    rc = aria_stereo_match_batch_device(h, h->d_img, d_ir, 0, width, height, width, h->d_kp, h->d_desc, h->d_counts, d_kr, d_dr,
+                                        h->d_counts + 1, (int64_t)cap, 1, h->d_obs, h->d_m, h->d_counts + 2, (int)cap);
+    if (rc != ARIA_OK) return rc;
+    int nm = 0;
+    ARIA_HIP(memcpy_on(h->stream, &nm, h->d_counts + 2, sizeof(int), hipMemcpyDeviceToHost));
+    if (n_left) ARIA_HIP(memcpy_on(h->stream, obs, h->d_obs, sizeof(aria_stereo_obs) * n_left, hipMemcpyDeviceToHost));
+    if (nm && matches) ARIA_HIP(memcpy_on(h->stream, matches, h->d_m, sizeof(aria_match) * nm, hipMemcpyDeviceToHost));
+    if (n_matches) *n_matches = nm;
+    return aria_stereo_check(h);
+}
+
+int aria_stereo_scale_batch_device(aria_stereo_t h, const aria_pose_result* d_pose, const uint8_t* d_mask,
+                                   const aria_match* d_matches, const int* d_nmatches, int match_cap, int query_is_first,
+                                   const aria_stereo_obs* d_obs_query, const int* d_nq, const aria_stereo_obs* d_obs_train,
+                                   const int* d_nt, int64_t kp_stride, int n_pairs, aria_stereo_scale* d_out) {
+    if (!h || !d_pose || !d_matches || !d_nmatches || !d_obs_query || !d_nq || !d_obs_train || !d_nt || !d_out || n_pairs < 0 ||
+        match_cap < 1 || match_cap > ST_MAX_KP || kp_stride < 0)
+        return ARIA_E_INVALID;
+    if (n_pairs == 0) return ARIA_OK;
+    ARIA_HIP(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_stereo_scale, dim3(n_pairs), dim3(ST_BLOCK), (size_t)match_cap * sizeof(unsigned long long), h->stream,
+                       d_pose, d_mask, d_matches, d_nmatches, match_cap, query_is_first ? 1 : 0, d_obs_query, d_nq, d_obs_train,
+                       d_nt, kp_stride, h->cfg.min_scale_matches, d_out, h->d_err);
+    ARIA_HIP(hipGetLastError());
+    return ARIA_OK;
+}
+
+int aria_stereo_scale_pose(aria_stereo_t h, const aria_pose_result* pose, const uint8_t* mask, const aria_match* matches,
+                           int n_matches, int query_is_first, const aria_stereo_obs* obs_query, int nq,
+                           const aria_stereo_obs* obs_train, int nt, aria_stereo_scale* out) {
+    if (!h || !pose || !out || n_matches < 0 || n_matches > ST_MAX_KP || nq < 0 || nt < 0 || (n_matches && !matches) ||
+        (nq && !obs_query) || (nt && !obs_train))
+        return ARIA_E_INVALID;
+    for (int i = 0; i < n_matches; i++)
+        if (matches[i].query_idx < 0 || matches[i].query_idx >= nq || matches[i].train_idx < 0 || matches[i].train_idx >= nt)
+            return ARIA_E_INVALID;
+    ARIA_HIP(hipSetDevice(h->device));
+    const size_t cap = (size_t)std::max(std::max(nq, nt), 1), mcap = (size_t)std::max(n_matches, 1);
+    int rc;
+    if ((rc = grow(h, h->d_obs, h->obs_cap, 2 * cap)) != ARIA_OK) return rc;
+    if ((rc = grow(h, h->d_m, h->m_cap, mcap)) != ARIA_OK) return rc;
+    if ((rc = grow(h, h->d_mask, h->mask_cap, mcap)) != ARIA_OK) return rc;
+    aria_stereo_obs* d_ot = h->d_obs + h->obs_cap / 2;
+    const int counts[4] = {nq, nt, n_matches, 0};
+    if (nq) ARIA_HIP(hipMemcpyAsync(h->d_obs, obs_query, sizeof(aria_stereo_obs) * nq, hipMemcpyHostToDevice, h->stream));
+    if (nt) ARIA_HIP(hipMemcpyAsync(d_ot, obs_train, sizeof(aria_stereo_obs) * nt, hipMemcpyHostToDevice, h->stream));
+    if (n_matches) ARIA_HIP(hipMemcpyAsync(h->d_m, matches, sizeof(aria_match) * n_matches, hipMemcpyHostToDevice, h->stream));
+    if (mask && n_matches) ARIA_HIP(hipMemcpyAsync(h->d_mask, mask, (size_t)n_matches, hipMemcpyHostToDevice, h->stream));
+    ARIA_HIP(hipMemcpyAsync(h->d_pose, pose, sizeof(aria_pose_result), hipMemcpyHostToDevice, h->stream));
+    ARIA_HIP(memcpy_on(h->stream, h->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
+    rc = aria_stereo_scale_batch_device(h, h->d_pose, mask ? h->d_mask : nullptr, h->d_m, h->d_counts + 2, (int)mcap,
+                                        query_is_first, h->d_obs, h->d_counts, d_ot, h->d_counts + 1, (int64_t)(h->obs_cap / 2), 1,
+                                        h->d_scale);
+    if (rc != ARIA_OK) return rc;
+    ARIA_HIP(memcpy_on(h->stream, out, h->d_scale, sizeof(aria_stereo_scale), hipMemcpyDeviceToHost));
+    return aria_stereo_check(h);
+}
+
+}  // extern "C"

@@ -14,6 +14,11 @@
 // stable sort here, ours by definition), else <root>/mav0/leica0/data.csv is tried as the reference does. A Leica file has 4
 // fields per row, so under the 17-field rule the fallback yields no rows, exactly as in the reference; a sequence without
 // ground truth still loads.
+//     <root>/mav0/cam1/data.csv + data/*.png   the right camera of a stereo rig, in cam0's format
+// is read when it is there (the reference's reader names cam1 and never reads it): a cam1 image is paired with the cam0 image
+// of EQUAL timestamp (the parsed seconds are compared). hasRight(i) tells whether image i has a partner; a sequence without
+// cam1 loads exactly as before.
+// The stereo stage (aria_hip/HipStereoMatcher.hpp) needs RECTIFIED pairs; this reader does not rectify.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -56,9 +61,14 @@ public:
     // ground truth, sorted by timestamp (empty when the sequence has none)
     const std::vector<AslGroundTruth>& groundTruth() const { return ground_truth_; }
     bool hasGroundTruth() const { return !ground_truth_.empty(); }
+    // cam1: whether image i has a right image of equal timestamp, and its decoded pixels (throws like read())
+    bool hasRight(std::size_t i) const { return i < right_.size() && !right_[i].empty(); }
+    bool hasStereo() const;          // cam1 is there and every cam0 image has its partner
+    void readRight(std::size_t i, std::vector<std::uint8_t>& gray, int& width, int& height) const;
 
 private:
     std::vector<AslImage> images_;
+    std::vector<std::string> right_;             // per image: path of the cam1 partner, empty without one
     std::vector<AslImu> imu_;
     std::vector<std::size_t> imu_begin_, imu_end_;
     std::vector<AslGroundTruth> ground_truth_;

@@ -51,6 +51,38 @@ bool load_ground_truth(const std::string& csv, std::vector<AslGroundTruth>& out)
 }
 static_assert(sizeof(AslGroundTruth) == 17 * sizeof(double), "AslGroundTruth is 17 packed doubles");
 
+// "timestamp,filename" rows of a camera's data.csv (EuRoCReader.cpp:70-108), sorted by timestamp. False when the file is absent.
+bool load_camera(const std::string& cam, std::vector<AslImage>& out) {
+    std::ifstream file(cam + "/data.csv");
+    if (!file.is_open()) return false;
+    std::string line;
+    std::getline(file, line);                                                 // header (EuRoCReader.cpp:78-79)
+    while (std::getline(file, line)) {
+        if (line.empty() || line[0] == '#') continue;                         // :82
+        std::stringstream ss(line);
+        std::string ts, name;
+        std::getline(ss, ts, ',');
+        std::getline(ss, name, ',');
+        const auto b = name.find_first_not_of(" \t");
+        if (b == std::string::npos) continue;
+        name.erase(0, b);
+        name.erase(name.find_last_not_of(" \t\r\n") + 1);                     // :90-91
+        AslImage img;
+        img.timestamp = std::strtod(ts.c_str(), nullptr) * 1e-9;              // nanoseconds -> seconds
+        img.path = cam + "/data/" + name;
+        out.push_back(img);
+    }
+    std::stable_sort(out.begin(), out.end(), [](const AslImage& a, const AslImage& b) { return a.timestamp < b.timestamp; });
+    return true;
+}
+
+void read_gray(const std::string& path, std::vector<std::uint8_t>& gray, int& width, int& height) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    std::vector<std::uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    decode_png_gray(bytes, gray, width, height);
+}
+
 }  // namespace
 
 void decode_png_gray(const std::vector<std::uint8_t>& file, std::vector<std::uint8_t>& gray, int& width, int& height) {
@@ -129,26 +161,19 @@ bool AslSequence::load(const std::string& dataset_path) {
     images_.clear();
     std::string cam = dataset_path + "/mav0/cam0";
     if (!file_exists(cam + "/data.csv")) cam = dataset_path + "/cam0";        // path already points at mav0
-    std::ifstream file(cam + "/data.csv");
-    if (!file.is_open()) return false;
+    if (!load_camera(cam, images_)) return false;
     std::string line;
-    std::getline(file, line);                                                 // header (EuRoCReader.cpp:78-79)
-    while (std::getline(file, line)) {
-        if (line.empty() || line[0] == '#') continue;                         // :82
-        std::stringstream ss(line);
-        std::string ts, name;
-        std::getline(ss, ts, ',');
-        std::getline(ss, name, ',');
-        const auto b = name.find_first_not_of(" \t");
-        if (b == std::string::npos) continue;
-        name.erase(0, b);
-        name.erase(name.find_last_not_of(" \t\r\n") + 1);                     // :90-91
-        AslImage img;
-        img.timestamp = std::strtod(ts.c_str(), nullptr) * 1e-9;              // nanoseconds -> seconds
-        img.path = cam + "/data/" + name;
-        images_.push_back(img);
+    // cam1 beside cam0, paired by equal timestamp; its absence is not an error
+    right_.clear();
+    std::vector<AslImage> cam1;
+    if (load_camera(cam.substr(0, cam.size() - 4) + "cam1", cam1)) {
+        right_.assign(images_.size(), std::string());
+        std::size_t k = 0;
+        for (std::size_t i = 0; i < images_.size(); i++) {                    // both lists are sorted
+            while (k < cam1.size() && cam1[k].timestamp < images_[i].timestamp) k++;
+            if (k < cam1.size() && cam1[k].timestamp == images_[i].timestamp) right_[i] = cam1[k].path;
+        }
     }
-    std::stable_sort(images_.begin(), images_.end(), [](const AslImage& a, const AslImage& b) { return a.timestamp < b.timestamp; });
     // imu0 beside cam0 (EuRoCReader.cpp:110-154); its absence is not an error
     imu_.clear();
     std::ifstream imu_file(cam.substr(0, cam.size() - 4) + "imu0/data.csv");
@@ -191,11 +216,19 @@ bool AslSequence::load(const std::string& dataset_path) {
 }
 
 void AslSequence::read(std::size_t i, std::vector<std::uint8_t>& gray, int& width, int& height) const {
-    const AslImage& im = images_.at(i);
-    std::ifstream f(im.path, std::ios::binary);
-    if (!f) throw std::runtime_error("cannot open " + im.path);
-    std::vector<std::uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    decode_png_gray(bytes, gray, width, height);
+    read_gray(images_.at(i).path, gray, width, height);
+}
+
+bool AslSequence::hasStereo() const {
+    if (right_.empty()) return false;
+    for (const std::string& p : right_)
+        if (p.empty()) return false;
+    return true;
+}
+
+void AslSequence::readRight(std::size_t i, std::vector<std::uint8_t>& gray, int& width, int& height) const {
+    if (!hasRight(i)) throw std::runtime_error("no cam1 image for " + images_.at(i).path);
+    read_gray(right_[i], gray, width, height);
 }
 
 }  // namespace aria::io
@@ -224,6 +257,14 @@ int aria_asl_list(const char* dataset_path, double* timestamps, int cap, char* f
     if (!s.load(dataset_path)) return -1;
     for (std::size_t i = 0; i < s.size() && (int)i < cap; i++) timestamps[i] = s.at(i).timestamp;
     if (first_path && first_path_cap > 0) std::snprintf(first_path, (std::size_t)first_path_cap, "%s", s.at(0).path.c_str());
+    return (int)s.size();
+}
+
+// Per image 1 when it has a cam1 partner of equal timestamp, else 0; returns the number of images or -1.
+int aria_asl_stereo(const char* dataset_path, int* has_right, int cap) {
+    aria::io::AslSequence s;
+    if (!s.load(dataset_path)) return -1;
+    for (std::size_t i = 0; i < s.size() && (int)i < cap; i++) has_right[i] = s.hasRight(i) ? 1 : 0;
     return (int)s.size();
 }
 

@@ -1,6 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
+//                [--stereo BASELINE_M] [--stereo-out FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -70,6 +71,15 @@
 // Error" report (:303-305) is printed with its raw numbers, for the --optimize trajectory when there is one (the reference
 // reports the optimised poses), else for --pose. Without the flag nothing changes and every other output is byte-identical.
 //
+// --stereo BASELINE_M [--stereo-out FILE] (frame-at-a-time path; the sequence needs a mav0/cam1 image of equal timestamp for
+// every cam0 image, and the pairs must be RECTIFIED -- this driver does not rectify): sparse stereo on the device (include/
+// aria_orb_hip.h, "sparse stereo"; aria_hip/HipStereoMatcher.hpp). The right image of every frame is extracted by a second
+// extractor and every left keypoint gets a depth. One line per frame, "timestamp matched median_depth", goes to FILE (to the
+// standard output with the prefix "stereo " without --stereo-out). With --pose as well, the relative translation of every
+// accepted pose (|t| = 1 from recoverPose) is multiplied by the metric scale recovered from the two frames' stereo
+// observations when that is valid, before it is chained into current_pose, and the line gets two more columns, "scale_valid
+// scale" (0 1 for a frame without an accepted pose). Without --stereo nothing of this runs and every output is byte-identical.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -99,7 +109,9 @@
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
 #include "aria_hip/HipSensorFusion.hpp"
+#include "aria_hip/HipStereoMatcher.hpp"
 #include "aria_hip/HipTrajectoryEvaluator.hpp"
+#include "aria_hip/OrbHipExtractor.hpp"
 #include "aria_hip/Shard.hpp"
 #include "aria_orb_hip.h"
 
@@ -131,7 +143,9 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file]\n"
+                             "  --stereo baseline_m: sparse stereo over mav0/cam1 (rectified pairs): a depth per keypoint, one line per frame; with --pose the\n"
+                             "                       relative translations take the metric scale\n"
                              "  --eval file: ATE / RPE of the --pose (and --optimize, --fuse) trajectories against the sequence's ground truth (needs --pose)\n"
                              "  --fuse file: EKF visual-inertial fusion over imu0 and the --pose stage's relative poses (needs --pose), one TUM line per frame\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
@@ -142,6 +156,9 @@ int main(int argc, char** argv) {
     bool legacy = false, loop = false;
     std::string csv, pose_file, map_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
+    double stereo_baseline = 0.0;
+    bool stereo = false;
+    std::string stereo_file;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -158,6 +175,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--eval") && i + 1 < argc) eval_file = argv[++i];
         else if (!std::strcmp(argv[i], "--eval-align") && i + 1 < argc) eval_align = argv[++i];
         else if (!std::strcmp(argv[i], "--rpe-delta") && i + 1 < argc) rpe_delta = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--stereo") && i + 1 < argc) { stereo = true; stereo_baseline = std::atof(argv[++i]); }
+        else if (!std::strcmp(argv[i], "--stereo-out") && i + 1 < argc) stereo_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -191,6 +210,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--pose runs on the frame-at-a-time path only (no --batch, --devices, --shards)\n");
         return -1;
     }
+    if ((stereo || !stereo_file.empty()) && (!stereo || !(stereo_baseline > 0) || batch > 0 || devices > 1 || shards > 1)) {
+        std::fprintf(stderr, "--stereo needs a baseline in metres > 0 and runs on the frame-at-a-time path only (no --batch, --devices, --shards); "
+                             "--stereo-out needs --stereo\n");
+        return 1;
+    }
     {
         // --devices names HIP ordinals 0 .. N-1: refuse up front what the machine does not have (FactoryConfig::cuda_device,
         // include/factory/PipelineFactory.hpp:24, is taken on trust by the reference)
@@ -213,6 +237,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--eval: the sequence has no mav0/state_groundtruth_estimate0/data.csv with 17-field rows\n");
         return 1;
     }
+    if (stereo && !seq.hasStereo()) {
+        std::fprintf(stderr, "--stereo: the sequence has no mav0/cam1 image of equal timestamp for every cam0 image\n");
+        return 1;
+    }
+    struct StereoLine { int matched = 0; float median_depth = 0.0f; int scale_valid = 0; double scale = 1.0; };
+    std::vector<StereoLine> stereo_lines(stereo ? N : 0);
     std::vector<aria_fuse_state> fused_states;                             // --eval: what --fuse and --optimize leave
     std::vector<double> optimized_xyz;
     if ((std::size_t)shards > N && N > 0) shards = (int)N;
@@ -288,13 +318,46 @@ int main(int argc, char** argv) {
                 mc.device = fc.hip_device;
                 mapper = std::make_unique<adapters::hip::HipMapper>(mc);
             }
+            // --stereo: the right image has an extractor of its own; the observations of the previous frame stay for the scale
+            std::unique_ptr<adapters::hip::OrbHipExtractor> right_extractor;
+            std::unique_ptr<adapters::hip::HipStereoMatcher> stereo_matcher;
+            adapters::hip::StereoObservations stereo_cur, stereo_prev;
+            std::vector<std::uint8_t> right_gray;
+            core::Frame right_frame;
+            if (stereo) {
+                adapters::hip::StereoConfig sc;
+                sc.baseline = stereo_baseline;
+                sc.device = fc.hip_device;
+                right_extractor = std::make_unique<adapters::hip::OrbHipExtractor>(max_features, nullptr, fc.hip_device);
+                stereo_matcher = std::make_unique<adapters::hip::HipStereoMatcher>(sc);
+            }
             for (std::size_t i = sp.first; i < sp.hi; i++) {
                 seq.read(i, gray, fw, fh);
                 const pipeline::FrontEndResult& r = fe->processFrame(gray.data(), fw, fh, seq.at(i).timestamp);
                 if (i < sp.lo) continue;                                   // the halo frame only provides the previous descriptors
+                if (stereo) {
+                    int rw = 0, rh = 0;
+                    seq.readRight(i, right_gray, rw, rh);
+                    if (rw != fw || rh != fh) throw std::runtime_error("--stereo: cam1 image size differs from cam0's at " + seq.at(i).path);
+                    right_extractor->extract(right_gray.data(), rw, rh, right_frame);
+                    std::swap(stereo_prev, stereo_cur);
+                    stereo_cur = stereo_matcher->match(gray.data(), right_gray.data(), fw, fh, *r.frame, right_frame);
+                    stereo_lines[i].matched = (int)stereo_cur.matches.size();
+                    stereo_lines[i].median_depth = stereo_cur.medianDepth();
+                }
                 if (!traj.empty()) {
                     if (r.pose && r.pose->n_pose_inliers > 10) {           // euroc_eval.cpp:191
-                        const std::array<double, 16> d = adapters::hip::poseMatrix(*r.pose), c = current_pose;
+                        std::array<double, 16> d = adapters::hip::poseMatrix(*r.pose);
+                        const std::array<double, 16> c = current_pose;
+                        if (stereo && r.previous) {                        // view 1 = previous frame: the query side in the legacy order
+                            const bool q1 = fc.frontend.legacy_order;
+                            const aria_stereo_scale sc = stereo_matcher->scale(*r.pose, r.matches, q1, q1 ? stereo_prev.obs : stereo_cur.obs,
+                                                                               q1 ? stereo_cur.obs : stereo_prev.obs);
+                            stereo_lines[i].scale_valid = sc.valid;
+                            stereo_lines[i].scale = sc.scale;
+                            if (sc.valid)
+                                for (int a = 0; a < 3; a++) d[(size_t)(a * 4 + 3)] *= sc.scale;
+                        }
                         for (int a = 0; a < 4; a++)
                             for (int b = 0; b < 4; b++) {
                                 double v = 0.0;
@@ -518,6 +581,24 @@ int main(int argc, char** argv) {
                     gr.pcg_iterations, optimize_file.c_str());
     }
     if (!map_file.empty()) std::printf("map %zu points -> %s\n", map_points, map_file.c_str());
+    if (stereo) {
+        std::ofstream sf;
+        if (!stereo_file.empty()) sf.open(stereo_file);
+        long long matched = 0, scaled = 0;
+        for (std::size_t i = 0; i < N; i++) {
+            const StereoLine& l = stereo_lines[i];
+            char line[160];
+            int n = std::snprintf(line, sizeof(line), "%.9f %d %.9f", seq.at(i).timestamp, l.matched, (double)l.median_depth);
+            if (!pose_file.empty()) std::snprintf(line + n, sizeof(line) - (size_t)n, " %d %.9f", l.scale_valid, l.scale);
+            if (sf.is_open()) sf << line << '\n';
+            else std::printf("stereo %s\n", line);
+            matched += l.matched;
+            scaled += l.scale_valid;
+        }
+        std::printf("stereo baseline %.6g m | mean matched %.2f per frame", stereo_baseline, N ? (double)matched / N : 0.0);
+        if (!pose_file.empty()) std::printf(" | %lld relative poses scaled", scaled);
+        std::printf("%s%s\n", stereo_file.empty() ? "" : " -> ", stereo_file.c_str());
+    }
     if (!eval_file.empty()) {                                              // euroc_eval.cpp:247-252, 294-305
         try {
             aria_eval_config ec;

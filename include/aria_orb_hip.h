@@ -1043,6 +1043,104 @@ int   aria_det_resize_table(int src, int dst, uint32_t* out, int cap);
 /* Algorithmic bytes of one preprocessed frame: width * height * channels read + 3 * input_w * input_h * element written. */
 int64_t aria_det_algorithmic_bytes(int width, int height, int channels, int input_w, int input_h, int out_half);
 
+/* ---- sparse stereo: a depth per left keypoint of a RECTIFIED stereo pair, and the metric scale of a relative pose. The
+ * reference has no stereo code (its roadmap item H19; its EuRoC reader names cam1 and never reads it), so the NumPy
+ * restatement aria_slam_amd/stereo_ref.py is the definition and the device equals it bit for bit. Additive to ABI 4.
+ *
+ * Precondition. Both images are rectified: a scene point lies on the same row of both. Rectification and undistortion are
+ *   not part of the stage. Float parameters of the config are used as fp32; scale[o] is the fp32 level scale of
+ *   aria_orb_level_info, with the octave clamped to 0..7.
+ * 1. Candidates. For a left keypoint (xL, yL, oL), a right keypoint j = (xR, yR, oR) is a candidate when, in fp32 as
+ *   written, |oR - oL| <= max_octave_diff, |yR - yL| <= band_factor * scale[oR] and
+ *   xL - max_disparity <= xR <= xL - min_disparity. The best candidate has the least 256-bit Hamming distance, ties to the
+ *   lowest j. No candidate, or a best distance >= th_hamming: unmatched.
+ * 2. SAD slide on the level-0 images. uL0 = rint(xL), vL0 = rint(yL), uR0 = rint(xR_best), round-half-even. With w =
+ *   sad_half_window and L = sad_slide, both (2w+1)^2 windows are centred on row vL0; unmatched when the left window or a
+ *   right window at uR0 + inc, inc in [-L, L], leaves the image. SAD(inc) = sum |IL - IR| over the window, exact integers,
+ *   no centre normalisation. The best inc has the least SAD, ties to the lowest inc; a best inc at -L or +L is unmatched.
+ * 3. Sub-pixel. d1, d2, d3 = SAD(best - 1), SAD(best), SAD(best + 1); den = 2 (d1 + d3 - 2 d2), an integer; den == 0 is
+ *   unmatched. delta = (float)(d1 - d3) / (float)den; disparity = (float)(uL0 - uR0 - best) - delta; unmatched unless
+ *   min_disparity <= disparity < max_disparity; then disparity = max(disparity, 0.01f), u_right = xL - disparity,
+ *   depth = (fx * baseline) / disparity with the product formed once in fp32, X = (xL - cx) * depth / fx,
+ *   Y = (yL - cy) * depth / fy -- fp32, in this order, no contraction.
+ * 4. Median filter per pair. Over the surviving observations med is the SAD at index n / 2 of the ascending list; those with
+ *   (float)sad > median_factor * (float)med become unmatched (strict: a perfectly shifted pair has med = 0 and keeps its
+ *   zeros).
+ * Outputs per pair. kp_stride records aria_stereo_obs, one per left keypoint (records at and beyond the pair's left count
+ *   are written unmatched); an unmatched record holds right_idx = -1, depth = -1 and zero elsewhere; no NaN or Inf is ever
+ *   written. And the matched keypoints as aria_match (query_idx = left index, train_idx = right_idx, distance = hamming)
+ *   in ascending left index with their count -- the match input of aria_map_triangulate_batch_device with extrinsics
+ *   [I|0], [I|(-baseline, 0, 0)].
+ * Scale of a relative pose (x2 ~ R x1 + t, |t| = 1, aria_pose_result). Over every match whose mask byte is nonzero and
+ *   whose two observations have right_idx >= 0: X1, X2 = the views' (X, Y, depth) as fp64, s_m = t . (X2 - R X1) with R's
+ *   rows applied in order and every sum left to right. scale = the value at index n / 2 of the ascending s_m. valid = 0 and
+ *   scale = 1.0 when the pose record is invalid (n_used = 0), n_used < min_scale_matches, or scale <= 0.
+ * Determinism. No float atomics; bitwise reproducible and independent of the batch split. */
+typedef struct aria_stereo_s* aria_stereo_t;
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_stereo_config)                                                  */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking, as in
+                                 * aria_pose_config)                                                              */
+    double   fx, fy, cx, cy;    /* intrinsics of the rectified left camera (default EuRoC cam0)                   */
+    double   baseline;          /* metres (default 0.110, EuRoC's nominal)                                        */
+    double   min_disparity;     /* default 0                                                                      */
+    double   max_disparity;     /* default fx: depth >= baseline                                                  */
+    double   band_factor;       /* default 2.0, >= 0                                                              */
+    double   median_factor;     /* default 2.1, >= 0                                                              */
+    int      th_hamming;        /* default 75                                                                     */
+    int      sad_half_window;   /* w: default 5, 1..7                                                             */
+    int      sad_slide;         /* L: default 5, 1..16                                                            */
+    int      max_octave_diff;   /* default 1, >= 0                                                                */
+    int      min_scale_matches; /* default 5, >= 1                                                                */
+    int      reserved;
+} aria_stereo_config;
+typedef struct {
+    float u_right, disparity, depth, X, Y;
+    int   right_idx, hamming, sad;
+} aria_stereo_obs;              /* 32 bytes                                                                       */
+typedef struct {
+    double scale;
+    int    n_used, valid;
+} aria_stereo_scale;            /* 16 bytes                                                                       */
+
+void  aria_stereo_default_config(aria_stereo_config* cfg);
+int   aria_stereo_create(const aria_stereo_config* cfg, aria_stereo_t* out);
+void  aria_stereo_destroy(aria_stereo_t h);
+void* aria_stereo_stream(aria_stereo_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check, once:
+ * ARIA_E_INVALID when some pair's keypoint counts were outside [0, kp_stride] (match: the pair is skipped -- every record
+ * unmatched, no matches; the others are unaffected) or, in the scale call, its counts or match indices were out of range
+ * (valid = 0, n_used = 0). */
+int   aria_stereo_check(aria_stereo_t h);
+/* Device-resident batch form over what aria_orb_extract_batch_device leaves in HBM for the left and the right frames.
+ * Pair p reads the level-0 images at d_img_left / d_img_right + p*img_stride (W x H bytes, `pitch` bytes per row,
+ * W, H <= 4096), keypoints at d_kp_* + p*kp_stride (d_n_*[p] of them) and descriptors at d_desc_* + p*kp_stride*32;
+ * writes kp_stride records at d_obs + p*kp_stride, the match list at d_matches + p*match_cap (match_cap >= kp_stride)
+ * and d_nmatches[p]. kp_stride <= 8192. Enqueued on the handle's stream, no synchronisation. */
+int   aria_stereo_match_batch_device(aria_stereo_t h, const uint8_t* d_img_left, const uint8_t* d_img_right, int64_t img_stride,
+                                     int width, int height, int pitch, const aria_keypoint* d_kp_left,
+                                     const uint8_t* d_desc_left, const int* d_n_left, const aria_keypoint* d_kp_right,
+                                     const uint8_t* d_desc_right, const int* d_n_right, int64_t kp_stride, int n_pairs,
+                                     aria_stereo_obs* d_obs, aria_match* d_matches, int* d_nmatches, int match_cap);
+/* One pair from host buffers; blocks. obs: n_left records; matches: up to n_left rows, *n_matches = their count. */
+int   aria_stereo_match(aria_stereo_t h, const uint8_t* img_left, const uint8_t* img_right, int width, int height, int pitch,
+                        const aria_keypoint* kp_left, const uint8_t* desc_left, int n_left, const aria_keypoint* kp_right,
+                        const uint8_t* desc_right, int n_right, aria_stereo_obs* obs, aria_match* matches, int* n_matches);
+/* Metric scale of n_pairs relative poses, with the pointer and stride conventions of aria_pose_estimate_batch_device: pair p
+ * reads d_pose[p], matches at d_matches + p*match_cap (d_nmatches[p]; match_cap <= 8192), the optional mask at
+ * d_mask + p*match_cap (NULL = every match) and the stereo observations of the query / train frames at
+ * d_obs_query / d_obs_train + p*kp_stride (d_nq[p] / d_nt[p] keypoints); view 1 is the query side when query_is_first = 1.
+ * Writes d_out[p]. Enqueued on the handle's stream, no synchronisation. */
+int   aria_stereo_scale_batch_device(aria_stereo_t h, const aria_pose_result* d_pose, const uint8_t* d_mask,
+                                     const aria_match* d_matches, const int* d_nmatches, int match_cap, int query_is_first,
+                                     const aria_stereo_obs* d_obs_query, const int* d_nq, const aria_stereo_obs* d_obs_train,
+                                     const int* d_nt, int64_t kp_stride, int n_pairs, aria_stereo_scale* d_out);
+/* One pose from host buffers; blocks. Out-of-range match indices: ARIA_E_INVALID. */
+int   aria_stereo_scale_pose(aria_stereo_t h, const aria_pose_result* pose, const uint8_t* mask, const aria_match* matches,
+                             int n_matches, int query_is_first, const aria_stereo_obs* obs_query, int nq,
+                             const aria_stereo_obs* obs_train, int nt, aria_stereo_scale* out);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
