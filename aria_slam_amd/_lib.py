@@ -394,15 +394,21 @@ def load_library():
     return L
 
 
+def _bind_handle(L, prefix):
+    """The prototypes every stage handle has: aria_<prefix>_default_config / _create / _destroy / _stream / _check."""
+    fn = lambda name: getattr(L, "aria_%s_%s" % (prefix, name))   # noqa: E731
+    fn("default_config").restype = None
+    fn("default_config").argtypes = [C.c_void_p]
+    fn("create").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    fn("destroy").restype = None
+    fn("destroy").argtypes = [C.c_void_p]
+    fn("stream").restype = C.c_void_p
+    fn("stream").argtypes = [C.c_void_p]
+    fn("check").argtypes = [C.c_void_p]
+
+
 def _bind_pose(L):
-    L.aria_pose_default_config.restype = None
-    L.aria_pose_default_config.argtypes = [C.c_void_p]
-    L.aria_pose_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.aria_pose_destroy.restype = None
-    L.aria_pose_destroy.argtypes = [C.c_void_p]
-    L.aria_pose_stream.restype = C.c_void_p
-    L.aria_pose_stream.argtypes = [C.c_void_p]
-    L.aria_pose_check.argtypes = [C.c_void_p]
+    _bind_handle(L, "pose")
     L.aria_pose_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]
     L.aria_pose_estimate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -414,14 +420,7 @@ def _bind_pose(L):
 
 def _bind_map(L):
     p, i, i64 = C.c_void_p, C.c_int, C.c_int64
-    L.aria_map_default_config.restype = None
-    L.aria_map_default_config.argtypes = [p]
-    L.aria_map_create.argtypes = [p, C.POINTER(C.c_void_p)]
-    L.aria_map_destroy.restype = None
-    L.aria_map_destroy.argtypes = [p]
-    L.aria_map_stream.restype = p
-    L.aria_map_stream.argtypes = [p]
-    L.aria_map_check.argtypes = [p]
+    _bind_handle(L, "map")
     L.aria_map_triangulate.argtypes = [p, p, i, p, i, p, i, i, p, p, p, i, i, i, p, i, p]
     L.aria_map_triangulate_batch_device.argtypes = [p, p, p, p, p, i64, p, p, i, i, i, i, p, p, p, p, i64, i, i, i, p]
     L.aria_map_points_needed.argtypes = [p, C.POINTER(C.c_int64)]
@@ -439,14 +438,7 @@ def _bind_map(L):
 
 def _bind_fund(L):
     p, i = C.c_void_p, C.c_int
-    L.aria_fund_default_config.restype = None
-    L.aria_fund_default_config.argtypes = [p]
-    L.aria_fund_create.argtypes = [p, C.POINTER(C.c_void_p)]
-    L.aria_fund_destroy.restype = None
-    L.aria_fund_destroy.argtypes = [p]
-    L.aria_fund_stream.restype = p
-    L.aria_fund_stream.argtypes = [p]
-    L.aria_fund_check.argtypes = [p]
+    _bind_handle(L, "fund")
     L.aria_fund_estimate.argtypes = [p, p, i, p, i, p, i, i, i, p, p]
     L.aria_fund_estimate_batch_device.argtypes = [p, p, p, p, p, C.c_int64, p, p, i, i, i, i, p, p, p, p]
     L.aria_fund_debug_hypotheses.argtypes = [p, p, i, p, i, p, i, i, i, p, p, p, p]
@@ -454,14 +446,7 @@ def _bind_fund(L):
 
 def _bind_graph(L):
     p, i = C.c_void_p, C.c_int
-    L.aria_graph_default_config.restype = None
-    L.aria_graph_default_config.argtypes = [p]
-    L.aria_graph_create.argtypes = [p, C.POINTER(C.c_void_p)]
-    L.aria_graph_destroy.restype = None
-    L.aria_graph_destroy.argtypes = [p]
-    L.aria_graph_stream.restype = p
-    L.aria_graph_stream.argtypes = [p]
-    L.aria_graph_check.argtypes = [p]
+    _bind_handle(L, "graph")
     L.aria_graph_optimize.argtypes = [p, p, i, i, p, i, i, p]
     L.aria_graph_optimize_batch_device.argtypes = [p, p, p, p, p, p, i, i, p]
     L.aria_graph_debug_linearize.argtypes = [p, p, i, i, p, i, p, p, p, p]
@@ -469,14 +454,7 @@ def _bind_graph(L):
 
 def _bind_fuse(L):
     p, i = C.c_void_p, C.c_int
-    L.aria_fuse_default_config.restype = None
-    L.aria_fuse_default_config.argtypes = [p]
-    L.aria_fuse_create.argtypes = [p, C.POINTER(C.c_void_p)]
-    L.aria_fuse_destroy.restype = None
-    L.aria_fuse_destroy.argtypes = [p]
-    L.aria_fuse_stream.restype = p
-    L.aria_fuse_stream.argtypes = [p]
-    L.aria_fuse_check.argtypes = [p]
+    _bind_handle(L, "fuse")
     L.aria_fuse_filter_init.argtypes = [p, p]
     L.aria_fuse_run_batch_device.argtypes = [p, p, p, p, i, p, p, p, i, i, p]
     L.aria_fuse_run.argtypes = [p, p, p, i, p, p, i, p]
@@ -487,14 +465,7 @@ def _bind_fuse(L):
 
 def _bind_eval(L):
     p, i = C.c_void_p, C.c_int
-    L.aria_eval_default_config.restype = None
-    L.aria_eval_default_config.argtypes = [p]
-    L.aria_eval_create.argtypes = [p, C.POINTER(C.c_void_p)]
-    L.aria_eval_destroy.restype = None
-    L.aria_eval_destroy.argtypes = [p]
-    L.aria_eval_stream.restype = p
-    L.aria_eval_stream.argtypes = [p]
-    L.aria_eval_check.argtypes = [p]
+    _bind_handle(L, "eval")
     L.aria_eval_sample_truth_device.argtypes = [p, p, i, p, i, p, p]
     L.aria_eval_sample_truth.argtypes = [p, p, i, p, i, p, p]
     L.aria_eval_batch_device.argtypes = [p, p, i, p, i, i, p, i, i, p, i, i, p, p]
@@ -503,13 +474,7 @@ def _bind_eval(L):
 
 def _bind_det(L):
     p, i, f = C.c_void_p, C.c_int, C.c_float
-    L.aria_det_default_config.restype = None
-    L.aria_det_default_config.argtypes = [p]
-    L.aria_det_create.argtypes = [p, C.POINTER(C.c_void_p)]
-    L.aria_det_destroy.restype = None
-    L.aria_det_destroy.argtypes = [p]
-    L.aria_det_stream.restype = p
-    L.aria_det_stream.argtypes = [p]
+    _bind_handle(L, "det")
     L.aria_det_check.argtypes = [p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.aria_det_device_buffers.argtypes = [p] + [C.POINTER(C.c_void_p)] * 6
     L.aria_det_preprocess_batch_device.argtypes = [p, p, i, i, i, i, C.c_int64, i, i, p]
@@ -523,14 +488,7 @@ def _bind_det(L):
 
 def _bind_stereo(L):
     p, i, i64 = C.c_void_p, C.c_int, C.c_int64
-    L.aria_stereo_default_config.restype = None
-    L.aria_stereo_default_config.argtypes = [p]
-    L.aria_stereo_create.argtypes = [p, C.POINTER(C.c_void_p)]
-    L.aria_stereo_destroy.restype = None
-    L.aria_stereo_destroy.argtypes = [p]
-    L.aria_stereo_stream.restype = p
-    L.aria_stereo_stream.argtypes = [p]
-    L.aria_stereo_check.argtypes = [p]
+    _bind_handle(L, "stereo")
     L.aria_stereo_match_batch_device.argtypes = [p, p, p, i64, i, i, i, p, p, p, p, p, p, i64, i, p, p, p, i]
     L.aria_stereo_match.argtypes = [p, p, p, i, i, i, p, p, i, p, p, i, p, p, C.POINTER(C.c_int)]
     L.aria_stereo_scale_batch_device.argtypes = [p, p, p, p, p, i, i, p, p, p, p, i64, i, p]

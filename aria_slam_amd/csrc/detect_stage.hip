@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "common.h"
+#include "stage_handle.h"
 
 using namespace aria;
 
@@ -271,12 +272,8 @@ void det_build_table(int src, int dst, uint32_t* out) {
 }  // namespace
 
 // ---- C-ABI ------------------------------------------------------------------------------------------------------------------
-struct aria_det_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_det_s : StageHandle {          // d_err: [0] bits, [1] det rows needed, [2] box rows needed
     aria_det_config cfg{};
-    int* d_err = nullptr;                  // [0] bits, [1] det rows needed, [2] box rows needed
     uint32_t* d_tab = nullptr;             // x table at 0, y table at DET_MAX_DIM
     std::vector<uint32_t> h_tab;           // host copy (kept while the upload may be in flight)
     int tab_key[4] = {0, 0, 0, 0};         // W, H, in_w, in_h of the tables on the device
@@ -286,8 +283,7 @@ struct aria_det_s {
     aria_detection* d_dets = nullptr;
     aria_box* d_boxes = nullptr;
     int* d_counts = nullptr;               // ndets at 0, nboxes at max_batch
-    void* d_img = nullptr;                 // staging of aria_det_preprocess
-    size_t img_cap = 0;
+    DeviceBuffer<uint8_t> d_img;           // staging of aria_det_preprocess
 };
 
 namespace {
@@ -358,29 +354,15 @@ int aria_det_create(const aria_det_config* c, aria_det_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_det_config)) return ARIA_E_INVALID;
     *out = nullptr;
     if (!det_config_ok(c)) return ARIA_E_INVALID;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_det_s* h = new (std::nothrow) aria_det_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
+    int rc = stage_open(h, c->device, c->stream, 4, "aria_det_create");
+    if (rc == ARIA_OK) {
+        const hipError_t e = hipMalloc((void**)&h->d_tab, 2 * DET_MAX_DIM * sizeof(uint32_t));
+        if (e != hipSuccess) rc = hip_fail(e, "aria_det_create", __FILE__, __LINE__);
     }
-    hipError_t e = hipMalloc((void**)&h->d_err, 4 * sizeof(int));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tab, 2 * DET_MAX_DIM * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "aria_det_create", __FILE__, __LINE__);
+    if (rc != ARIA_OK) {
         aria_det_destroy(h);
         return rc;
     }
@@ -390,12 +372,7 @@ int aria_det_create(const aria_det_config* c, aria_det_t* out) {
 
 void aria_det_destroy(aria_det_t h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_err, h->d_tab, h->d_input, h->d_raw, h->d_dets, h->d_boxes, h->d_counts, h->d_img};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_tab, h->d_input, h->d_raw, h->d_dets, h->d_boxes, h->d_counts});
     delete h;
 }
 
@@ -405,12 +382,10 @@ int aria_det_check(aria_det_t h, int* det_rows_needed, int* box_rows_needed) {
     if (!h) return ARIA_E_INVALID;
     if (det_rows_needed) *det_rows_needed = 0;
     if (box_rows_needed) *box_rows_needed = 0;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int w[3] = {0, 0, 0};
-    ARIA_HIP(memcpy_on(h->stream, w, h->d_err, sizeof(w), hipMemcpyDeviceToHost));
+    const int rc = stage_read_errors(h, w, 3);
+    if (rc != ARIA_OK) return rc;
     if (!w[0]) return ARIA_OK;
-    ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(w)));
     if (det_rows_needed) *det_rows_needed = w[1];
     if (box_rows_needed) *box_rows_needed = w[2];
     return ARIA_E_OUTPUT_TOO_SMALL;
@@ -484,18 +459,11 @@ int aria_det_preprocess(aria_det_t h, const uint8_t* image, int width, int heigh
     int rc = det_ensure_buffers(h);
     if (rc != ARIA_OK) return rc;
     const size_t bytes = (size_t)row_stride * height;
-    if (h->img_cap < bytes) {
-        ARIA_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_img) (void)hipFree(h->d_img);
-        h->d_img = nullptr;
-        h->img_cap = 0;
-        ARIA_HIP(hipMalloc(&h->d_img, bytes));
-        h->img_cap = bytes;
-    }
+    if ((rc = h->d_img.reserve(h->stream, bytes)) != ARIA_OK) return rc;
     // (the last row may be shorter than row_stride in the caller's buffer)
     const size_t used = (size_t)row_stride * (height - 1) + (size_t)width * channels;
     ARIA_HIP(memcpy_on(h->stream, h->d_img, image, used, hipMemcpyHostToDevice));
-    rc = aria_det_preprocess_batch_device(h, (const uint8_t*)h->d_img, 1, width, height, row_stride, (int64_t)bytes, channels, swap_rb,
+    rc = aria_det_preprocess_batch_device(h, h->d_img, 1, width, height, row_stride, (int64_t)bytes, channels, swap_rb,
                                           h->d_input);
     if (rc != ARIA_OK) return rc;
     ARIA_HIP(memcpy_on(h->stream, input, h->d_input, 3 * (size_t)h->cfg.input_w * h->cfg.input_h * det_elem(h), hipMemcpyDeviceToHost));

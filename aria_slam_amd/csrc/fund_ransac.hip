@@ -26,6 +26,8 @@
 #include <vector>
 
 #include "common.h"
+#include "ransac_device.h"
+#include "stage_handle.h"
 
 using namespace aria;
 
@@ -44,19 +46,6 @@ constexpr double FUND_2PI_3 = 2.0 * 3.14159265358979323846 / 3.0;
 constexpr int ERRBIT_FUND_INPUT = 1;       // a pair's counts or match indices were out of range (pair skipped)
 constexpr int FUND_COND = 8;               // per-pair conditioning record: c1x, c1y, d1, c2x, c2y, d2, -, -
 
-// the pose stage's sample hash (pose_ransac.hip), unchanged
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ int fund_draw(uint64_t hkey, uint32_t j, uint32_t retry, uint32_t n) {
-    const uint64_t r = splitmix64(hkey ^ (uint64_t)(retry * 8u + j));
-    return (int)(((r >> 32) * (uint64_t)n) >> 32);
-}
-
 // computeError in conditioned coordinates, division-free: q = (u1x, u1y, u2x, u2y), g = G (fp32), t1 / t2 = (thr / d_i)^2
 __device__ __forceinline__ int fund_inlier(const float* g, float4 q, float t1, float t2) {
     const float l0 = g[0] * q.x + g[1] * q.y + g[2];
@@ -72,12 +61,6 @@ __device__ __forceinline__ int fund_inlier(const float* g, float4 q, float t1, f
 __device__ __forceinline__ float fund_thr(double thr, double d) {
     const double t = thr / d;
     return (float)(t * t);
-}
-
-__device__ __forceinline__ void swap_if(bool c, double& a, double& b) {
-    const double x = a, y = b;
-    a = c ? y : x;
-    b = c ? x : y;
 }
 
 // haveCollinearPoints: slot 6 against every pair of slots 0..5
@@ -368,22 +351,7 @@ __global__ __launch_bounds__(64) void k_fund_hyp(const float4* __restrict__ pix,
     int idx[7];
 #pragma unroll
     for (int j = 0; j < 7; j++) idx[j] = -1;
-    if (ok) {
-        const uint64_t hkey = splitmix64(splitmix64(splitmix64(seed) ^ (uint64_t)(uint32_t)(pair_base + p)) ^ (uint64_t)h);
-#pragma unroll
-        for (int j = 0; j < 7; j++) {
-            int v = -1;
-            for (int retry = 0; retry < FUND_MAX_RETRY; retry++) {
-                const int c = fund_draw(hkey, (uint32_t)j, (uint32_t)retry, (uint32_t)n);
-                bool dup = false;
-#pragma unroll
-                for (int k = 0; k < j; k++) dup |= idx[k] == c;
-                if (!dup) { v = c; break; }
-            }
-            idx[j] = v;
-            ok &= v >= 0;
-        }
-    }
+    if (ok) ok = draw_sample<7, FUND_MAX_RETRY>(seed, (uint32_t)(pair_base + p), h, n, idx);
     if (dbg_idx) {
 #pragma unroll
         for (int j = 0; j < 7; j++) dbg_idx[h * 7 + j] = idx[j];
@@ -563,40 +531,23 @@ __global__ __launch_bounds__(FUND_FINISH_BLOCK) void k_fund_finish(const float4*
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
-struct aria_fund_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_fund_s : StageHandle {
     aria_fund_config cfg{};
-    int* d_err = nullptr;
     // grow-only workspace of the batch path
-    float4* d_pix = nullptr;  size_t pix_cap = 0;      // [n_pairs][match_cap] pixel points
-    float4* d_pts = nullptr;  size_t pts_cap = 0;      // [n_pairs][match_cap] conditioned points
-    double* d_cond = nullptr; size_t cond_cap = 0;     // [n_pairs][8]
-    int* d_npts = nullptr;    size_t np_cap = 0;       // [n_pairs]
-    double* d_F = nullptr;    size_t F_cap = 0;        // [n_pairs][27][H]
-    float* d_G = nullptr;     size_t G_cap = 0;        // [n_pairs][27][H]
-    int* d_nmod = nullptr;    size_t nmod_cap = 0;     // [n_pairs][H]
-    int* d_cnt = nullptr;     size_t cnt_cap = 0;      // [n_pairs][H][3]
-    // single-pair staging (aria_fund_estimate, aria_fund_debug_hypotheses)
-    aria_keypoint* d_kq = nullptr; aria_keypoint* d_kt = nullptr; size_t kp_cap = 0;
-    aria_match* d_m = nullptr; uint8_t* d_mask = nullptr; size_t m_cap = 0;
-    int* d_counts = nullptr;              // [0] nq, [1] nt, [2] n_matches
+    DeviceBuffer<float4> d_pix;           // [n_pairs][match_cap] pixel points
+    DeviceBuffer<float4> d_pts;           // [n_pairs][match_cap] conditioned points
+    DeviceBuffer<double> d_cond;          // [n_pairs][8]
+    DeviceBuffer<int> d_npts;             // [n_pairs]
+    DeviceBuffer<double> d_F;             // [n_pairs][27][H]
+    DeviceBuffer<float> d_G;              // [n_pairs][27][H]
+    DeviceBuffer<int> d_nmod;             // [n_pairs][H]
+    DeviceBuffer<int> d_cnt;              // [n_pairs][H][3]
+    PairStaging pair;                     // aria_fund_estimate, aria_fund_debug_hypotheses
     aria_fund_result* d_res = nullptr;
-    int* d_dbg = nullptr; size_t dbg_cap = 0;
+    DeviceBuffer<int> d_dbg;
 };
 
 namespace {
-
-template <typename T>
-int fgrow(aria_fund_s* h, T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return ARIA_OK;
-    ARIA_HIP(hipStreamSynchronize(h->stream));   // earlier work on the stream may still read the old block
-    if (p) { ARIA_HIP(hipFree(p)); p = nullptr; cap = 0; }
-    ARIA_HIP(hipMalloc((void**)&p, need * sizeof(T)));
-    cap = need;
-    return ARIA_OK;
-}
 
 int fund_enqueue(aria_fund_t h, const aria_keypoint* d_kq, const int* d_nq, const aria_keypoint* d_kt, const int* d_nt,
                  int64_t kp_stride, const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
@@ -605,14 +556,14 @@ int fund_enqueue(aria_fund_t h, const aria_keypoint* d_kq, const int* d_nq, cons
     const int H = h->cfg.hypotheses;
     const size_t P = (size_t)n_pairs;
     int rc;
-    if ((rc = fgrow(h, h->d_pix, h->pix_cap, P * match_cap)) != ARIA_OK) return rc;
-    if ((rc = fgrow(h, h->d_pts, h->pts_cap, P * match_cap)) != ARIA_OK) return rc;
-    if ((rc = fgrow(h, h->d_cond, h->cond_cap, P * FUND_COND)) != ARIA_OK) return rc;
-    if ((rc = fgrow(h, h->d_npts, h->np_cap, P)) != ARIA_OK) return rc;
-    if ((rc = fgrow(h, h->d_F, h->F_cap, P * H * 27)) != ARIA_OK) return rc;
-    if ((rc = fgrow(h, h->d_G, h->G_cap, P * H * 27)) != ARIA_OK) return rc;
-    if ((rc = fgrow(h, h->d_nmod, h->nmod_cap, P * H)) != ARIA_OK) return rc;
-    if ((rc = fgrow(h, h->d_cnt, h->cnt_cap, P * H * 3)) != ARIA_OK) return rc;
+    if ((rc = h->d_pix.reserve(h->stream, P * match_cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_pts.reserve(h->stream, P * match_cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_cond.reserve(h->stream, P * FUND_COND)) != ARIA_OK) return rc;
+    if ((rc = h->d_npts.reserve(h->stream, P)) != ARIA_OK) return rc;
+    if ((rc = h->d_F.reserve(h->stream, P * H * 27)) != ARIA_OK) return rc;
+    if ((rc = h->d_G.reserve(h->stream, P * H * 27)) != ARIA_OK) return rc;
+    if ((rc = h->d_nmod.reserve(h->stream, P * H)) != ARIA_OK) return rc;
+    if ((rc = h->d_cnt.reserve(h->stream, P * H * 3)) != ARIA_OK) return rc;
     const aria_fund_config& c = h->cfg;
     hipLaunchKernelGGL(k_fund_stage, dim3(n_pairs), dim3(FUND_STAGE_BLOCK), 0, h->stream, d_kq, d_nq, d_kt, d_nt, kp_stride,
                        d_matches, d_nmatches, match_cap, query_is_first ? 1 : 0, h->d_pix, h->d_pts, h->d_cond, h->d_npts,
@@ -629,34 +580,12 @@ int fund_enqueue(aria_fund_t h, const aria_keypoint* d_kq, const int* d_nq, cons
     return ARIA_OK;
 }
 
-// uploads one pair (host buffers) into the single-pair staging; rejects out-of-range indices on the host
-int fund_stage_single(aria_fund_t h, const aria_keypoint* kq, int nq, const aria_keypoint* kt, int nt, const aria_match* matches,
-                      int n) {
-    if (nq < 0 || nt < 0 || n < 0 || (nq && !kq) || (nt && !kt) || (n && !matches)) return ARIA_E_INVALID;
-    for (int i = 0; i < n; i++)
-        if (matches[i].query_idx < 0 || matches[i].query_idx >= nq || matches[i].train_idx < 0 || matches[i].train_idx >= nt)
-            return ARIA_E_INVALID;
-    int rc;
-    const size_t kcap = (size_t)std::max(std::max(nq, nt), 1);
-    if (kcap > h->kp_cap) {
-        size_t a = h->kp_cap, b = h->kp_cap;
-        if ((rc = fgrow(h, h->d_kq, a, kcap)) != ARIA_OK) return rc;
-        if ((rc = fgrow(h, h->d_kt, b, kcap)) != ARIA_OK) return rc;
-        h->kp_cap = kcap;
-    }
-    const size_t mcap = (size_t)std::max(n, 1);
-    if (mcap > h->m_cap) {
-        size_t a = h->m_cap, b = h->m_cap;
-        if ((rc = fgrow(h, h->d_m, a, mcap)) != ARIA_OK) return rc;
-        if ((rc = fgrow(h, h->d_mask, b, mcap)) != ARIA_OK) return rc;
-        h->m_cap = mcap;
-    }
-    const int counts[4] = {nq, nt, n, 0};
-    if (nq) ARIA_HIP(hipMemcpyAsync(h->d_kq, kq, sizeof(aria_keypoint) * nq, hipMemcpyHostToDevice, h->stream));
-    if (nt) ARIA_HIP(hipMemcpyAsync(h->d_kt, kt, sizeof(aria_keypoint) * nt, hipMemcpyHostToDevice, h->stream));
-    if (n) ARIA_HIP(hipMemcpyAsync(h->d_m, matches, sizeof(aria_match) * n, hipMemcpyHostToDevice, h->stream));
-    ARIA_HIP(memcpy_on(h->stream, h->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
-    return ARIA_OK;
+// the batch form over the one staged pair
+int fund_enqueue_staged(aria_fund_t h, int query_is_first, int pair_base, int* d_dbg, bool finish) {
+    const PairStaging& s = h->pair;
+    return fund_enqueue(h, s.d_kq, s.d_counts, s.d_kt, s.d_counts + 1, s.kp_stride, s.d_m, s.d_counts + 2, 1, s.match_cap,
+                        query_is_first, pair_base, finish ? h->d_res : nullptr, finish ? s.d_mask.p : nullptr, nullptr, nullptr,
+                        d_dbg, finish);
 }
 
 }  // namespace
@@ -679,30 +608,16 @@ int aria_fund_create(const aria_fund_config* c, aria_fund_t* out) {
     if (c->hypotheses < 64 || c->hypotheses > 16384 || (c->hypotheses % 64)) return ARIA_E_INVALID;
     if (!(c->threshold_px > 0) || !std::isfinite(c->threshold_px)) return ARIA_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_fund_s* h = new (std::nothrow) aria_fund_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
+    int rc = stage_open(h, c->device, c->stream, 1, "aria_fund_create");
+    if (rc == ARIA_OK) rc = h->pair.create(h->stream);
+    if (rc == ARIA_OK) {
+        const hipError_t e = hipMalloc((void**)&h->d_res, sizeof(aria_fund_result));
+        if (e != hipSuccess) rc = hip_fail(e, "aria_fund_create", __FILE__, __LINE__);
     }
-    hipError_t e = hipMalloc((void**)&h->d_err, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_res, sizeof(aria_fund_result));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, sizeof(int));
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "aria_fund_create", __FILE__, __LINE__);
+    if (rc != ARIA_OK) {
         aria_fund_destroy(h);
         return rc;
     }
@@ -712,13 +627,7 @@ int aria_fund_create(const aria_fund_config* c, aria_fund_t* out) {
 
 void aria_fund_destroy(aria_fund_t h) {
     if (!h) return;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_err, h->d_pix, h->d_pts, h->d_cond, h->d_npts, h->d_F, h->d_G, h->d_nmod, h->d_cnt, h->d_kq, h->d_kt,
-                    h->d_m, h->d_mask, h->d_counts, h->d_res, h->d_dbg};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_res});
     delete h;
 }
 
@@ -726,11 +635,9 @@ void* aria_fund_stream(aria_fund_t h) { return h ? (void*)h->stream : nullptr; }
 
 int aria_fund_check(aria_fund_t h) {
     if (!h) return ARIA_E_INVALID;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int bits = 0;
-    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
     return (bits & ERRBIT_FUND_INPUT) ? ARIA_E_INVALID : ARIA_OK;
 }
 
@@ -753,15 +660,11 @@ int aria_fund_estimate(aria_fund_t h, const aria_keypoint* kp_query, int nq, con
                        uint8_t* mask) {
     if (!h || !out || pair_base < 0 || n_matches > (1 << 20)) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int rc = fund_stage_single(h, kp_query, nq, kp_train, nt, matches, n_matches);
+    int rc = h->pair.upload(h->stream, kp_query, nq, kp_train, nt, matches, n_matches);
     if (rc != ARIA_OK) return rc;
-    const int cap = std::max(n_matches, 1);
-    const int64_t stride = (int64_t)std::max(std::max(nq, nt), 1);
-    rc = fund_enqueue(h, h->d_kq, h->d_counts, h->d_kt, h->d_counts + 1, stride, h->d_m, h->d_counts + 2, 1, cap, query_is_first,
-                      pair_base, h->d_res, h->d_mask, nullptr, nullptr, nullptr, true);
-    if (rc != ARIA_OK) return rc;
+    if ((rc = fund_enqueue_staged(h, query_is_first, pair_base, nullptr, true)) != ARIA_OK) return rc;
     ARIA_HIP(hipMemcpyAsync(out, h->d_res, sizeof(aria_fund_result), hipMemcpyDeviceToHost, h->stream));
-    if (mask && n_matches) ARIA_HIP(hipMemcpyAsync(mask, h->d_mask, (size_t)n_matches, hipMemcpyDeviceToHost, h->stream));
+    if (mask && n_matches) ARIA_HIP(hipMemcpyAsync(mask, h->pair.d_mask, (size_t)n_matches, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
     return aria_fund_check(h);
 }
@@ -771,15 +674,11 @@ int aria_fund_debug_hypotheses(aria_fund_t h, const aria_keypoint* kp_query, int
                                int* n_models, double* F, int* counts) {
     if (!h || !sample_idx || !n_models || !F || !counts || pair_base < 0 || n_matches > (1 << 20)) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int rc = fund_stage_single(h, kp_query, nq, kp_train, nt, matches, n_matches);
+    int rc = h->pair.upload(h->stream, kp_query, nq, kp_train, nt, matches, n_matches);
     if (rc != ARIA_OK) return rc;
     const int H = h->cfg.hypotheses;
-    if ((rc = fgrow(h, h->d_dbg, h->dbg_cap, (size_t)H * 7)) != ARIA_OK) return rc;
-    const int cap = std::max(n_matches, 1);
-    const int64_t stride = (int64_t)std::max(std::max(nq, nt), 1);
-    rc = fund_enqueue(h, h->d_kq, h->d_counts, h->d_kt, h->d_counts + 1, stride, h->d_m, h->d_counts + 2, 1, cap, query_is_first,
-                      pair_base, nullptr, nullptr, nullptr, nullptr, h->d_dbg, false);
-    if (rc != ARIA_OK) return rc;
+    if ((rc = h->d_dbg.reserve(h->stream, (size_t)H * 7)) != ARIA_OK) return rc;
+    if ((rc = fund_enqueue_staged(h, query_is_first, pair_base, h->d_dbg, false)) != ARIA_OK) return rc;
     std::vector<double> soa((size_t)27 * H);
     ARIA_HIP(hipMemcpyAsync(sample_idx, h->d_dbg, sizeof(int) * 7 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(n_models, h->d_nmod, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, h->stream));

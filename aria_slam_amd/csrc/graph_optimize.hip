@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "stage_handle.h"
 
 using namespace aria;
 
@@ -805,12 +806,8 @@ __global__ __launch_bounds__(GRAPH_BLOCK) void k_graph_lm(double* poses_all, con
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
-struct aria_graph_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_graph_s : StageHandle {
     aria_graph_config cfg{};
-    int* d_err = nullptr;
     double* d_v = nullptr;     // [max_graphs] vertex scratch
     double* d_e = nullptr;     // [max_graphs] edge scratch
     int* d_i = nullptr;        // [max_graphs] adjacency
@@ -877,43 +874,29 @@ int aria_graph_create(const aria_graph_config* c, aria_graph_t* out) {
         !(c->pcg_rel_tol < 1))
         return ARIA_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_graph_s* h = new (std::nothrow) aria_graph_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
+    int rc = stage_open(h, c->device, c->stream, 1, "aria_graph_create");
+    if (rc == ARIA_OK) {
+        // more than 64 KiB of dynamic LDS has to be asked for; where that is refused the solve keeps W and p in HBM
+        h->wlds_edges = std::min(c->max_edges, GRAPH_LDS_EDGES);
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_graph_lm), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)graph_lds_bytes(h->wlds_edges)) != hipSuccess) {
+            (void)hipGetLastError();
+            h->wlds_edges = 0;
+        }
+        const size_t G = (size_t)c->max_graphs, V = (size_t)c->max_vertices, E = (size_t)c->max_edges;
+        hipError_t e = hipMalloc((void**)&h->d_v, G * V * VERT_DOUBLES * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_e, G * E * EDGE_DOUBLES * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_i, G * graph_int_words(c->max_vertices, c->max_edges) * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_poses, V * 12 * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_edges, E * sizeof(aria_graph_edge));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_off, 8 * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_res, sizeof(aria_graph_result));
+        if (e != hipSuccess) rc = hip_fail(e, "aria_graph_create", __FILE__, __LINE__);
     }
-    // more than 64 KiB of dynamic LDS has to be asked for; where that is refused the solve keeps W and p in HBM
-    h->wlds_edges = std::min(c->max_edges, GRAPH_LDS_EDGES);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_graph_lm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)graph_lds_bytes(h->wlds_edges)) != hipSuccess) {
-        (void)hipGetLastError();
-        h->wlds_edges = 0;
-    }
-    const size_t G = (size_t)c->max_graphs, V = (size_t)c->max_vertices, E = (size_t)c->max_edges;
-    hipError_t e = hipMalloc((void**)&h->d_err, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_v, G * V * VERT_DOUBLES * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_e, G * E * EDGE_DOUBLES * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_i, G * graph_int_words(c->max_vertices, c->max_edges) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_poses, V * 12 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_edges, E * sizeof(aria_graph_edge));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_off, 8 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_res, sizeof(aria_graph_result));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, sizeof(int));
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "aria_graph_create", __FILE__, __LINE__);
+    if (rc != ARIA_OK) {
         aria_graph_destroy(h);
         return rc;
     }
@@ -923,12 +906,7 @@ int aria_graph_create(const aria_graph_config* c, aria_graph_t* out) {
 
 void aria_graph_destroy(aria_graph_t h) {
     if (!h) return;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_err, h->d_v, h->d_e, h->d_i, h->d_poses, h->d_edges, h->d_off, h->d_res};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_v, h->d_e, h->d_i, h->d_poses, h->d_edges, h->d_off, h->d_res});
     delete h;
 }
 
@@ -936,11 +914,9 @@ void* aria_graph_stream(aria_graph_t h) { return h ? (void*)h->stream : nullptr;
 
 int aria_graph_check(aria_graph_t h) {
     if (!h) return ARIA_E_INVALID;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int bits = 0;
-    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
     if (bits & ERRBIT_GRAPH_INPUT) return ARIA_E_INVALID;
     return (bits & ERRBIT_GRAPH_LARGE) ? ARIA_E_TOO_LARGE : ARIA_OK;
 }

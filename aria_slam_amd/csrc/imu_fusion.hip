@@ -20,6 +20,7 @@
 #include <new>
 
 #include "common.h"
+#include "stage_handle.h"
 
 using namespace aria;
 
@@ -631,12 +632,8 @@ __global__ void k_visual_from_pose(const aria_pose_result* __restrict__ res, con
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
-struct aria_fuse_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_fuse_s : StageHandle {
     aria_fuse_config cfg{};
-    int* d_err = nullptr;
     // staging of the host forms (aria_fuse_run, aria_fuse_preintegrate), grown on demand
     void* d_buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t cap[6] = {0, 0, 0, 0, 0, 0};
@@ -705,28 +702,11 @@ int aria_fuse_filter_init(aria_fuse_filter* f, const aria_fuse_config* cfg) {
 int aria_fuse_create(const aria_fuse_config* c, aria_fuse_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_fuse_config)) return ARIA_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_fuse_s* h = new (std::nothrow) aria_fuse_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
-    }
-    hipError_t e = hipMalloc((void**)&h->d_err, sizeof(int));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, sizeof(int));
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "aria_fuse_create", __FILE__, __LINE__);
+    const int rc = stage_open(h, c->device, c->stream, 1, "aria_fuse_create");
+    if (rc != ARIA_OK) {
         aria_fuse_destroy(h);
         return rc;
     }
@@ -736,12 +716,7 @@ int aria_fuse_create(const aria_fuse_config* c, aria_fuse_t* out) {
 
 void aria_fuse_destroy(aria_fuse_t h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_err) (void)hipFree(h->d_err);
-    for (void* b : h->d_buf)
-        if (b) (void)hipFree(b);
-    if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_buf[0], h->d_buf[1], h->d_buf[2], h->d_buf[3], h->d_buf[4], h->d_buf[5]});
     delete h;
 }
 
@@ -749,11 +724,9 @@ void* aria_fuse_stream(aria_fuse_t h) { return h ? (void*)h->stream : nullptr; }
 
 int aria_fuse_check(aria_fuse_t h) {
     if (!h) return ARIA_E_INVALID;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int bits = 0;
-    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
     return (bits & ERRBIT_FUSE_INPUT) ? ARIA_E_INVALID : ARIA_OK;
 }
 

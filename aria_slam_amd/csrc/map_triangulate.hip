@@ -22,6 +22,8 @@
 #include <new>
 
 #include "common.h"
+#include "ransac_device.h"
+#include "stage_handle.h"
 
 using namespace aria;
 
@@ -149,24 +151,6 @@ __device__ __forceinline__ bool triangulate_one(const double KP1[12], const doub
     return true;
 }
 
-// wave-ordered stable compaction of one 256-thread round: returns this lane's slot (valid when keep) and the round's total
-__device__ __forceinline__ int block_compact(bool keep, int* wsum, int& total) {
-    const unsigned long long b = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    if (lane == 0) wsum[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < MAP_BLOCK / 64; w++) {
-        before += (w < wave) ? wsum[w] : 0;
-        total += wsum[w];
-    }
-    __syncthreads();                                     // wsum is reused by the next round
-    return before + rank;
-}
-
 // ---- append 1: triangulate + compact into the pair's staging slot --------------------------------------------------------
 __global__ __launch_bounds__(MAP_BLOCK) void k_map_tri(const aria_keypoint* __restrict__ kq, const int* __restrict__ nq,
                                                        const aria_keypoint* __restrict__ kt, const int* __restrict__ nt,
@@ -262,7 +246,7 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_tri(const aria_keypoint* __re
             keep = triangulate_one(KP1, KP2, E1, E2, C1, C2, prm, k1.x, k1.y, k2.x, k2.y, X, e);
         }
         int total;
-        const int slot = block_compact(keep, wsum, total);
+        const int slot = block_compact<MAP_BLOCK>(keep, wsum, total);
         if (keep) {
             uint8_t g = 127;                             // (int)(0.5 * 255): the reference's default colour
             if (im) {
@@ -437,7 +421,7 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_flag(const aria_map_point* __
         }
         flags[i] = keep ? 1 : 0;
         int total;
-        block_compact(keep, wsum, total);
+        block_compact<MAP_BLOCK>(keep, wsum, total);
         kept += total;
     }
     if (threadIdx.x == 0) bcnt[blockIdx.x] = kept;
@@ -472,7 +456,7 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_fscatter(const aria_map_point
         const long long i = b0 + k * MAP_BLOCK + threadIdx.x;
         const bool keep = flags[i] != 0;
         int total;
-        const int slot = block_compact(keep, wsum, total);
+        const int slot = block_compact<MAP_BLOCK>(keep, wsum, total);
         if (keep) dst[o + slot] = src[i];
         o += total;
     }
@@ -481,12 +465,8 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_fscatter(const aria_map_point
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
-struct aria_map_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_map_s : StageHandle {
     aria_map_config cfg{};
-    int* d_err = nullptr;
     long long* d_meta = nullptr;                         // META_* slots
     double* d_stats = nullptr;                           // mean[3], threshold
     // the arena and its ping-pong twin (the filters scatter into the other one), `capacity` points each
@@ -494,33 +474,21 @@ struct aria_map_s {
     aria_map_point* d_arena2 = nullptr;
     int64_t capacity = 0;
     // grow-only workspace of the append path
-    aria_map_point* d_stage = nullptr; size_t stage_cap = 0;   // [n_pairs][match_cap]
-    int* d_cnt = nullptr;              size_t cnt_cap = 0;     // [n_pairs]
-    long long* d_off = nullptr;        size_t off_cap = 0;     // [n_pairs]
+    DeviceBuffer<aria_map_point> d_stage;                // [n_pairs][match_cap]
+    DeviceBuffer<int> d_cnt;                             // [n_pairs]
+    DeviceBuffer<long long> d_off;                       // [n_pairs]
     // grow-only workspace of the filters
-    double* d_part = nullptr;          size_t part_cap = 0;    // [n_blocks][3]
-    int* d_bcnt = nullptr;             size_t bcnt_cap = 0;    // [n_blocks]
-    long long* d_boff = nullptr;       size_t boff_cap = 0;    // [n_blocks]
-    uint8_t* d_flags = nullptr;        size_t flags_cap = 0;   // [n_blocks * span]
-    // single-pair staging (aria_map_triangulate)
-    aria_keypoint* d_kq = nullptr; aria_keypoint* d_kt = nullptr; size_t kp_cap = 0;
-    aria_match* d_m = nullptr; uint8_t* d_mask = nullptr; size_t m_cap = 0;
-    uint8_t* d_img = nullptr; size_t img_cap = 0;
-    int* d_counts = nullptr;                             // [0] nq, [1] nt, [2] n_matches
+    DeviceBuffer<double> d_part;                         // [n_blocks][3]
+    DeviceBuffer<int> d_bcnt;                            // [n_blocks]
+    DeviceBuffer<long long> d_boff;                      // [n_blocks]
+    DeviceBuffer<uint8_t> d_flags;                       // [n_blocks * span]
+    // single-pair staging (aria_map_triangulate): the pair, view 1's image, the two extrinsics
+    PairStaging pair;
+    DeviceBuffer<uint8_t> d_img;
     double* d_ext = nullptr;                             // 24 doubles
 };
 
 namespace {
-
-template <typename T>
-int grow(aria_map_s* h, T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return ARIA_OK;
-    ARIA_HIP(hipStreamSynchronize(h->stream));   // earlier work on the stream may still read the old block
-    if (p) { ARIA_HIP(hipFree(p)); p = nullptr; cap = 0; }
-    ARIA_HIP(hipMalloc((void**)&p, need * sizeof(T)));
-    cap = need;
-    return ARIA_OK;
-}
 
 MapParams map_params(const aria_map_config& c) {
     return MapParams{c.fx, c.fy, c.cx, c.cy, c.min_depth, c.max_depth, c.min_parallax_deg, c.max_reproj_px};
@@ -540,9 +508,9 @@ int enqueue_tri(aria_map_t h, const aria_keypoint* d_kq, const int* d_nq, const 
                 int query_is_first, int pair_base, const double* d_ext, const aria_pose_result* d_pose, const uint8_t* d_cand,
                 const uint8_t* d_img, int64_t img_stride, int W, int H, int pitch) {
     int rc;
-    if ((rc = grow(h, h->d_stage, h->stage_cap, (size_t)n_pairs * match_cap)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_cnt, h->cnt_cap, (size_t)n_pairs)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_off, h->off_cap, (size_t)n_pairs)) != ARIA_OK) return rc;
+    if ((rc = h->d_stage.reserve(h->stream, (size_t)n_pairs * match_cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_cnt.reserve(h->stream, (size_t)n_pairs)) != ARIA_OK) return rc;
+    if ((rc = h->d_off.reserve(h->stream, (size_t)n_pairs)) != ARIA_OK) return rc;
     hipLaunchKernelGGL(k_map_tri, dim3(n_pairs), dim3(MAP_BLOCK), 0, h->stream, d_kq, d_nq, d_kt, d_nt, kp_stride, d_matches,
                        d_nmatches, match_cap, query_is_first ? 1 : 0, pair_base, d_ext, d_pose, h->cfg.min_pose_inliers, d_cand,
                        d_img, img_stride, W, H, pitch, map_params(h->cfg), h->d_stage, h->d_cnt, h->d_err);
@@ -565,10 +533,10 @@ int enqueue_filter(aria_map_t h, int mode, double dist) {
     if (h->capacity == 0) return ARIA_OK;
     const int nb = (int)((h->capacity + MAP_FILT_SPAN - 1) / MAP_FILT_SPAN);
     int rc;
-    if ((rc = grow(h, h->d_part, h->part_cap, (size_t)nb * 3)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_bcnt, h->bcnt_cap, (size_t)nb)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_boff, h->boff_cap, (size_t)nb)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_flags, h->flags_cap, (size_t)nb * MAP_FILT_SPAN)) != ARIA_OK) return rc;
+    if ((rc = h->d_part.reserve(h->stream, (size_t)nb * 3)) != ARIA_OK) return rc;
+    if ((rc = h->d_bcnt.reserve(h->stream, (size_t)nb)) != ARIA_OK) return rc;
+    if ((rc = h->d_boff.reserve(h->stream, (size_t)nb)) != ARIA_OK) return rc;
+    if ((rc = h->d_flags.reserve(h->stream, (size_t)nb * MAP_FILT_SPAN)) != ARIA_OK) return rc;
     if (mode == 0) {
         hipLaunchKernelGGL(k_map_psum, dim3(nb), dim3(MAP_BLOCK), 0, h->stream, h->d_arena, h->d_meta, 0, h->d_stats, h->d_part);
         hipLaunchKernelGGL(k_map_stats, dim3(1), dim3(MAP_BLOCK), 0, h->stream, h->d_part, nb, h->d_meta, 0, h->d_stats);
@@ -636,33 +604,19 @@ void aria_map_default_config(aria_map_config* c) {
 int aria_map_create(const aria_map_config* c, aria_map_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_map_s* h = new (std::nothrow) aria_map_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
+    int rc = stage_open(h, c->device, c->stream, 1, "aria_map_create");
+    if (rc == ARIA_OK) rc = h->pair.create(h->stream);
+    if (rc == ARIA_OK) {
+        hipError_t e = hipMalloc((void**)&h->d_meta, META_SLOTS * sizeof(long long));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_stats, 4 * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_ext, 24 * sizeof(double));
+        if (e == hipSuccess) e = memset_on(h->stream, h->d_meta, 0, META_SLOTS * sizeof(long long));
+        if (e == hipSuccess) e = memset_on(h->stream, h->d_stats, 0, 4 * sizeof(double));
+        if (e != hipSuccess) rc = hip_fail(e, "aria_map_create", __FILE__, __LINE__);
     }
-    hipError_t e = hipMalloc((void**)&h->d_err, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_meta, META_SLOTS * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_stats, 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_ext, 24 * sizeof(double));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, sizeof(int));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_meta, 0, META_SLOTS * sizeof(long long));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_stats, 0, 4 * sizeof(double));
-    int rc = e == hipSuccess ? ARIA_OK : hip_fail(e, "aria_map_create", __FILE__, __LINE__);
     if (rc == ARIA_OK) rc = reserve(h, std::max<int64_t>(c->capacity, 1));
     if (rc != ARIA_OK) {
         aria_map_destroy(h);
@@ -674,13 +628,7 @@ int aria_map_create(const aria_map_config* c, aria_map_t* out) {
 
 void aria_map_destroy(aria_map_t h) {
     if (!h) return;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_err, h->d_meta, h->d_stats, h->d_arena, h->d_arena2, h->d_stage, h->d_cnt, h->d_off, h->d_part,
-                    h->d_bcnt, h->d_boff, h->d_flags, h->d_kq, h->d_kt, h->d_m, h->d_mask, h->d_img, h->d_counts, h->d_ext};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_meta, h->d_stats, h->d_arena, h->d_arena2, h->d_ext});
     delete h;
 }
 
@@ -688,11 +636,9 @@ void* aria_map_stream(aria_map_t h) { return h ? (void*)h->stream : nullptr; }
 
 int aria_map_check(aria_map_t h) {
     if (!h) return ARIA_E_INVALID;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int bits = 0;
-    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
     if (bits & ERRBIT_MAP_INPUT) return ARIA_E_INVALID;
     if (bits & ERRBIT_MAP_FULL) return ARIA_E_OUTPUT_TOO_SMALL;
     return ARIA_OK;
@@ -702,48 +648,26 @@ int aria_map_triangulate(aria_map_t h, const aria_keypoint* kp_query, int nq, co
                          const aria_match* matches, int n_matches, int query_is_first, const double* pose1,
                          const double* pose2, const uint8_t* image1, int width, int height, int pitch, const uint8_t* mask,
                          int pair_id, int* n_added) {
-    if (!h || !pose1 || !pose2 || nq < 0 || nt < 0 || n_matches < 0 || n_matches > (1 << 20) || pair_id < 0 ||
-        (nq && !kp_query) || (nt && !kp_train) || (n_matches && !matches))
-        return ARIA_E_INVALID;
+    if (!h || !pose1 || !pose2 || n_matches > (1 << 20) || pair_id < 0) return ARIA_E_INVALID;
     if (image1 && (width < 1 || height < 1 || pitch < width)) return ARIA_E_INVALID;
-    for (int i = 0; i < n_matches; i++)
-        if (matches[i].query_idx < 0 || matches[i].query_idx >= nq || matches[i].train_idx < 0 || matches[i].train_idx >= nt)
-            return ARIA_E_INVALID;
-    if (n_added) *n_added = 0;
     ARIA_HIP(hipSetDevice(h->device));
-    int rc;
-    const size_t kcap = (size_t)std::max(std::max(nq, nt), 1);
-    if (kcap > h->kp_cap) {
-        size_t a = h->kp_cap, b = h->kp_cap;
-        if ((rc = grow(h, h->d_kq, a, kcap)) != ARIA_OK) return rc;
-        if ((rc = grow(h, h->d_kt, b, kcap)) != ARIA_OK) return rc;
-        h->kp_cap = kcap;
-    }
-    const size_t mcap = (size_t)std::max(n_matches, 1);
-    if (mcap > h->m_cap) {
-        size_t a = h->m_cap, b = h->m_cap;
-        if ((rc = grow(h, h->d_m, a, mcap)) != ARIA_OK) return rc;
-        if ((rc = grow(h, h->d_mask, b, mcap)) != ARIA_OK) return rc;
-        h->m_cap = mcap;
-    }
-    if (image1 && (rc = grow(h, h->d_img, h->img_cap, (size_t)width * height)) != ARIA_OK) return rc;
+    PairStaging& s = h->pair;
+    int rc = s.prepare(h->stream, kp_query, nq, kp_train, nt, matches, n_matches);
+    if (rc != ARIA_OK) return rc;
+    if (n_added) *n_added = 0;
+    if (image1 && (rc = h->d_img.reserve(h->stream, (size_t)width * height)) != ARIA_OK) return rc;
     double ext[24];
     std::memcpy(ext, pose1, 12 * sizeof(double));
     std::memcpy(ext + 12, pose2, 12 * sizeof(double));
-    const int counts[4] = {nq, nt, n_matches, 0};
-    if (nq) ARIA_HIP(hipMemcpyAsync(h->d_kq, kp_query, sizeof(aria_keypoint) * nq, hipMemcpyHostToDevice, h->stream));
-    if (nt) ARIA_HIP(hipMemcpyAsync(h->d_kt, kp_train, sizeof(aria_keypoint) * nt, hipMemcpyHostToDevice, h->stream));
-    if (n_matches) ARIA_HIP(hipMemcpyAsync(h->d_m, matches, sizeof(aria_match) * n_matches, hipMemcpyHostToDevice, h->stream));
-    if (mask && n_matches) ARIA_HIP(hipMemcpyAsync(h->d_mask, mask, (size_t)n_matches, hipMemcpyHostToDevice, h->stream));
     if (image1)
         ARIA_HIP(hipMemcpy2DAsync(h->d_img, (size_t)width, image1, (size_t)pitch, (size_t)width, (size_t)height,
                                   hipMemcpyHostToDevice, h->stream));
     ARIA_HIP(hipMemcpyAsync(h->d_ext, ext, sizeof(ext), hipMemcpyHostToDevice, h->stream));
-    ARIA_HIP(memcpy_on(h->stream, h->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
-    const int cap = (int)mcap;
-    rc = enqueue_tri(h, h->d_kq, h->d_counts, h->d_kt, h->d_counts + 1, (int64_t)kcap, h->d_m, h->d_counts + 2, 1, cap,
-                     query_is_first, pair_id, h->d_ext, nullptr, mask ? h->d_mask : nullptr, image1 ? h->d_img : nullptr, 0,
-                     width, height, width);
+    if ((rc = s.copy(h->stream, kp_query, nq, kp_train, nt, matches, n_matches, mask)) != ARIA_OK) return rc;
+    const int cap = s.match_cap;
+    rc = enqueue_tri(h, s.d_kq, s.d_counts, s.d_kt, s.d_counts + 1, s.kp_stride, s.d_m, s.d_counts + 2, 1, cap, query_is_first,
+                     pair_id, h->d_ext, nullptr, mask ? s.d_mask.p : nullptr, image1 ? h->d_img.p : nullptr, 0, width, height,
+                     width);
     if (rc != ARIA_OK) return rc;
     // the blocking form grows the arena itself
     int kept = 0;

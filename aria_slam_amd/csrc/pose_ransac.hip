@@ -23,6 +23,8 @@
 #include <vector>
 
 #include "common.h"
+#include "ransac_device.h"
+#include "stage_handle.h"
 
 using namespace aria;
 
@@ -35,19 +37,6 @@ constexpr int POSE_MAX_RETRY = 256;        // redraws per sample slot (header: a
 constexpr double POSE_PIVOT_TOL = 1e-9;    // |pivot| <= tol * max|A_ij|: rank-deficient sample
 constexpr double POSE_RANK_TOL = 1e-9;     // sigma2 <= tol * sigma1 after the solve: not an essential matrix
 constexpr int ERRBIT_POSE_INPUT = 1;       // a pair's counts or match indices were out of range (pair skipped)
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// aria_orb_hip.h "Hypotheses": sample j (0..7) of hypothesis h of pair `pair`, draw number `retry`
-__device__ __forceinline__ int pose_draw(uint64_t hkey, uint32_t j, uint32_t retry, uint32_t n) {
-    const uint64_t r = splitmix64(hkey ^ (uint64_t)(retry * 8u + j));
-    return (int)(((r >> 32) * (uint64_t)n) >> 32);
-}
 
 // Sampson test of findEssentialMat in normalised coordinates, division-free: r^2 <= thr2 * d with d > 0
 __device__ __forceinline__ int pose_inlier(const float e[9], float4 q, float thr2) {
@@ -97,12 +86,6 @@ __device__ __forceinline__ void jacobi3(double A[9], double V[9]) {
         jacobi_rotate<3>(A, V, 0, 2);
         jacobi_rotate<3>(A, V, 1, 2);
     }
-}
-
-__device__ __forceinline__ void swap_if(bool c, double& a, double& b) {
-    const double x = a, y = b;
-    a = c ? y : x;
-    b = c ? x : y;
 }
 
 // Closest essential matrix (singular values (s, s, 0)) of e, scaled to unit Frobenius norm: (u1 v1^T + u2 v2^T) / sqrt(2),
@@ -206,22 +189,7 @@ __global__ __launch_bounds__(64) void k_pose_hyp(const float4* __restrict__ pts,
     int idx[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) idx[j] = -1;
-    if (ok) {
-        const uint64_t hkey = splitmix64(splitmix64(splitmix64(seed) ^ (uint64_t)(uint32_t)(pair_base + p)) ^ (uint64_t)h);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            int v = -1;
-            for (int retry = 0; retry < POSE_MAX_RETRY; retry++) {
-                const int c = pose_draw(hkey, (uint32_t)j, (uint32_t)retry, (uint32_t)n);
-                bool dup = false;
-#pragma unroll
-                for (int k = 0; k < j; k++) dup |= idx[k] == c;
-                if (!dup) { v = c; break; }
-            }
-            idx[j] = v;
-            ok &= v >= 0;
-        }
-    }
+    if (ok) ok = draw_sample<8, POSE_MAX_RETRY>(seed, (uint32_t)(pair_base + p), h, n, idx);
     if (dbg_idx) {
 #pragma unroll
         for (int j = 0; j < 8; j++) dbg_idx[h * 8 + j] = idx[j];
@@ -531,37 +499,20 @@ __global__ __launch_bounds__(POSE_FINISH_BLOCK) void k_pose_finish(const float4*
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
-struct aria_pose_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_pose_s : StageHandle {
     aria_pose_config cfg{};
-    int* d_err = nullptr;
     // grow-only workspace of the batch path
-    float4* d_pts = nullptr;  size_t pts_cap = 0;      // [n_pairs][match_cap]
-    int* d_npts = nullptr;    size_t np_cap = 0;       // [n_pairs]
-    float* d_E = nullptr;     size_t E_cap = 0;        // [n_pairs][9][H]
-    int* d_cnt = nullptr;     size_t cnt_cap = 0;      // [n_pairs][H]
-    uint8_t* d_ws = nullptr;  size_t ws_cap = 0;       // [n_pairs][match_cap] inlier flags
-    // single-pair staging (aria_pose_estimate, aria_pose_debug_hypotheses)
-    aria_keypoint* d_kq = nullptr; aria_keypoint* d_kt = nullptr; size_t kp_cap = 0;
-    aria_match* d_m = nullptr; uint8_t* d_mask = nullptr; size_t m_cap = 0;
-    int* d_counts = nullptr;              // [0] nq, [1] nt, [2] n_matches
+    DeviceBuffer<float4> d_pts;           // [n_pairs][match_cap]
+    DeviceBuffer<int> d_npts;             // [n_pairs]
+    DeviceBuffer<float> d_E;              // [n_pairs][9][H]
+    DeviceBuffer<int> d_cnt;              // [n_pairs][H]
+    DeviceBuffer<uint8_t> d_ws;           // [n_pairs][match_cap] inlier flags
+    PairStaging pair;                     // aria_pose_estimate, aria_pose_debug_hypotheses
     aria_pose_result* d_res = nullptr;
-    int* d_dbg = nullptr; size_t dbg_cap = 0;
+    DeviceBuffer<int> d_dbg;
 };
 
 namespace {
-
-template <typename T>
-int grow(aria_pose_s* h, T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return ARIA_OK;
-    ARIA_HIP(hipStreamSynchronize(h->stream));   // earlier work on the stream may still read the old block
-    if (p) { ARIA_HIP(hipFree(p)); p = nullptr; cap = 0; }
-    ARIA_HIP(hipMalloc((void**)&p, need * sizeof(T)));
-    cap = need;
-    return ARIA_OK;
-}
 
 float pose_thr2(const aria_pose_config& c) {
     const double t = c.threshold_px / ((c.fx + c.fy) * 0.5);
@@ -573,11 +524,11 @@ int enqueue(aria_pose_t h, const aria_keypoint* d_kq, const int* d_nq, const ari
             int pair_base, aria_pose_result* d_out, uint8_t* d_mask, int* d_dbg, bool finish) {
     const int H = h->cfg.hypotheses;
     int rc;
-    if ((rc = grow(h, h->d_pts, h->pts_cap, (size_t)n_pairs * match_cap)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_ws, h->ws_cap, (size_t)n_pairs * match_cap)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_npts, h->np_cap, (size_t)n_pairs)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_E, h->E_cap, (size_t)n_pairs * H * 9)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_cnt, h->cnt_cap, (size_t)n_pairs * H)) != ARIA_OK) return rc;
+    if ((rc = h->d_pts.reserve(h->stream, (size_t)n_pairs * match_cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_ws.reserve(h->stream, (size_t)n_pairs * match_cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_npts.reserve(h->stream, (size_t)n_pairs)) != ARIA_OK) return rc;
+    if ((rc = h->d_E.reserve(h->stream, (size_t)n_pairs * H * 9)) != ARIA_OK) return rc;
+    if ((rc = h->d_cnt.reserve(h->stream, (size_t)n_pairs * H)) != ARIA_OK) return rc;
     const aria_pose_config& c = h->cfg;
     hipLaunchKernelGGL(k_pose_stage, dim3(n_pairs), dim3(256), 0, h->stream, d_kq, d_nq, d_kt, d_nt, kp_stride, d_matches,
                        d_nmatches, match_cap, query_is_first ? 1 : 0, c.fx, c.fy, c.cx, c.cy, h->d_pts, h->d_npts, h->d_err);
@@ -592,33 +543,11 @@ int enqueue(aria_pose_t h, const aria_keypoint* d_kq, const int* d_nq, const ari
     return ARIA_OK;
 }
 
-// uploads one pair (host buffers) into the single-pair staging; rejects out-of-range indices on the host
-int stage_single(aria_pose_t h, const aria_keypoint* kq, int nq, const aria_keypoint* kt, int nt, const aria_match* matches, int n) {
-    if (nq < 0 || nt < 0 || n < 0 || (nq && !kq) || (nt && !kt) || (n && !matches)) return ARIA_E_INVALID;
-    for (int i = 0; i < n; i++)
-        if (matches[i].query_idx < 0 || matches[i].query_idx >= nq || matches[i].train_idx < 0 || matches[i].train_idx >= nt)
-            return ARIA_E_INVALID;
-    int rc;
-    const size_t kcap = (size_t)std::max(std::max(nq, nt), 1);
-    if (kcap > h->kp_cap) {
-        size_t a = h->kp_cap, b = h->kp_cap;
-        if ((rc = grow(h, h->d_kq, a, kcap)) != ARIA_OK) return rc;
-        if ((rc = grow(h, h->d_kt, b, kcap)) != ARIA_OK) return rc;
-        h->kp_cap = kcap;
-    }
-    const size_t mcap = (size_t)std::max(n, 1);
-    if (mcap > h->m_cap) {
-        size_t a = h->m_cap, b = h->m_cap;
-        if ((rc = grow(h, h->d_m, a, mcap)) != ARIA_OK) return rc;
-        if ((rc = grow(h, h->d_mask, b, mcap)) != ARIA_OK) return rc;
-        h->m_cap = mcap;
-    }
-    const int counts[4] = {nq, nt, n, 0};
-    if (nq) ARIA_HIP(hipMemcpyAsync(h->d_kq, kq, sizeof(aria_keypoint) * nq, hipMemcpyHostToDevice, h->stream));
-    if (nt) ARIA_HIP(hipMemcpyAsync(h->d_kt, kt, sizeof(aria_keypoint) * nt, hipMemcpyHostToDevice, h->stream));
-    if (n) ARIA_HIP(hipMemcpyAsync(h->d_m, matches, sizeof(aria_match) * n, hipMemcpyHostToDevice, h->stream));
-    ARIA_HIP(memcpy_on(h->stream, h->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
-    return ARIA_OK;
+// the batch form over the one staged pair
+int enqueue_staged(aria_pose_t h, int query_is_first, int pair_base, int* d_dbg, bool finish) {
+    const PairStaging& s = h->pair;
+    return enqueue(h, s.d_kq, s.d_counts, s.d_kt, s.d_counts + 1, s.kp_stride, s.d_m, s.d_counts + 2, 1, s.match_cap, query_is_first,
+                   pair_base, finish ? h->d_res : nullptr, finish ? s.d_mask.p : nullptr, d_dbg, finish);
 }
 
 }  // namespace
@@ -645,30 +574,16 @@ int aria_pose_create(const aria_pose_config* c, aria_pose_t* out) {
         !(c->distance_thresh > 0) || !std::isfinite(c->fx) || !std::isfinite(c->fy))
         return ARIA_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_pose_s* h = new (std::nothrow) aria_pose_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
+    int rc = stage_open(h, c->device, c->stream, 1, "aria_pose_create");
+    if (rc == ARIA_OK) rc = h->pair.create(h->stream);
+    if (rc == ARIA_OK) {
+        const hipError_t e = hipMalloc((void**)&h->d_res, sizeof(aria_pose_result));
+        if (e != hipSuccess) rc = hip_fail(e, "aria_pose_create", __FILE__, __LINE__);
     }
-    hipError_t e = hipMalloc((void**)&h->d_err, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_res, sizeof(aria_pose_result));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, sizeof(int));
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "aria_pose_create", __FILE__, __LINE__);
+    if (rc != ARIA_OK) {
         aria_pose_destroy(h);
         return rc;
     }
@@ -678,13 +593,7 @@ int aria_pose_create(const aria_pose_config* c, aria_pose_t* out) {
 
 void aria_pose_destroy(aria_pose_t h) {
     if (!h) return;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_err, h->d_pts, h->d_npts, h->d_E, h->d_cnt, h->d_ws, h->d_kq, h->d_kt, h->d_m, h->d_mask,
-                    h->d_counts, h->d_res, h->d_dbg};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_res});
     delete h;
 }
 
@@ -692,11 +601,9 @@ void* aria_pose_stream(aria_pose_t h) { return h ? (void*)h->stream : nullptr; }
 
 int aria_pose_check(aria_pose_t h) {
     if (!h) return ARIA_E_INVALID;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int bits = 0;
-    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
     return (bits & ERRBIT_POSE_INPUT) ? ARIA_E_INVALID : ARIA_OK;
 }
 
@@ -718,15 +625,11 @@ int aria_pose_estimate(aria_pose_t h, const aria_keypoint* kp_query, int nq, con
                        uint8_t* mask) {
     if (!h || !out || pair_base < 0 || n_matches > (1 << 20)) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int rc = stage_single(h, kp_query, nq, kp_train, nt, matches, n_matches);
+    int rc = h->pair.upload(h->stream, kp_query, nq, kp_train, nt, matches, n_matches);
     if (rc != ARIA_OK) return rc;
-    const int cap = std::max(n_matches, 1);
-    const int64_t stride = (int64_t)std::max(std::max(nq, nt), 1);
-    rc = enqueue(h, h->d_kq, h->d_counts, h->d_kt, h->d_counts + 1, stride, h->d_m, h->d_counts + 2, 1, cap, query_is_first,
-                 pair_base, h->d_res, h->d_mask, nullptr, true);
-    if (rc != ARIA_OK) return rc;
+    if ((rc = enqueue_staged(h, query_is_first, pair_base, nullptr, true)) != ARIA_OK) return rc;
     ARIA_HIP(hipMemcpyAsync(out, h->d_res, sizeof(aria_pose_result), hipMemcpyDeviceToHost, h->stream));
-    if (mask && n_matches) ARIA_HIP(hipMemcpyAsync(mask, h->d_mask, (size_t)n_matches, hipMemcpyDeviceToHost, h->stream));
+    if (mask && n_matches) ARIA_HIP(hipMemcpyAsync(mask, h->pair.d_mask, (size_t)n_matches, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
     return aria_pose_check(h);
 }
@@ -736,15 +639,11 @@ int aria_pose_debug_hypotheses(aria_pose_t h, const aria_keypoint* kp_query, int
                                float* E, int* counts) {
     if (!h || !sample_idx || !E || !counts || pair_base < 0 || n_matches > (1 << 20)) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int rc = stage_single(h, kp_query, nq, kp_train, nt, matches, n_matches);
+    int rc = h->pair.upload(h->stream, kp_query, nq, kp_train, nt, matches, n_matches);
     if (rc != ARIA_OK) return rc;
     const int H = h->cfg.hypotheses;
-    if ((rc = grow(h, h->d_dbg, h->dbg_cap, (size_t)H * 8)) != ARIA_OK) return rc;
-    const int cap = std::max(n_matches, 1);
-    const int64_t stride = (int64_t)std::max(std::max(nq, nt), 1);
-    rc = enqueue(h, h->d_kq, h->d_counts, h->d_kt, h->d_counts + 1, stride, h->d_m, h->d_counts + 2, 1, cap, query_is_first,
-                 pair_base, nullptr, nullptr, h->d_dbg, false);
-    if (rc != ARIA_OK) return rc;
+    if ((rc = h->d_dbg.reserve(h->stream, (size_t)H * 8)) != ARIA_OK) return rc;
+    if ((rc = enqueue_staged(h, query_is_first, pair_base, h->d_dbg, false)) != ARIA_OK) return rc;
     std::vector<float> soa((size_t)9 * H);
     ARIA_HIP(hipMemcpyAsync(sample_idx, h->d_dbg, sizeof(int) * 8 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(soa.data(), h->d_E, sizeof(float) * 9 * (size_t)H, hipMemcpyDeviceToHost, h->stream));

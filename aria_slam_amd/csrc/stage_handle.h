@@ -1,0 +1,149 @@
+// Host side of what the stage handles (aria_pose_t, aria_fund_t, aria_map_t, aria_graph_t, aria_fuse_t, aria_eval_t,
+// aria_det_t, aria_stereo_t) share: the lifecycle of device, stream and deferred-error words, grow-only device buffers, and
+// the single-pair staging of the blocking host forms that take a match list. Header-only; not part of the public interface.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <initializer_list>
+
+#include "common.h"
+
+namespace aria {
+
+// What every aria_<stage>_s starts with. d_err: the deferred-error words the stage's kernels OR into.
+struct StageHandle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    int* d_err = nullptr;
+};
+
+// Device-range check, hipSetDevice, the caller's stream or a new non-blocking one, d_err allocated and zeroed. `what` names
+// the entry point in aria_last_hip_error(). On failure the caller runs its destroy, which ends in stage_close.
+inline int stage_open(StageHandle* h, int device, void* stream, int err_words, const char* what) {
+    int ndev = 0;
+    ARIA_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) {
+        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", device, ndev);
+        return ARIA_E_NO_DEVICE;
+    }
+    ARIA_HIP(hipSetDevice(device));
+    h->device = device;
+    if (stream) {
+        h->stream = (hipStream_t)stream;
+    } else {
+        const hipError_t e = create_stream(&h->stream);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__);
+        h->owns_stream = true;
+    }
+    hipError_t e = hipMalloc((void**)&h->d_err, err_words * sizeof(int));
+    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, err_words * sizeof(int));
+    return e == hipSuccess ? ARIA_OK : hip_fail(e, what, __FILE__, __LINE__);
+}
+
+// Every destroy: the device made current, the stream drained, d_err and the stage's plain device pointers freed, the stream
+// destroyed if the handle made it (a borrowed stream stays the caller's). DeviceBuffer members free themselves with the handle.
+inline void stage_close(StageHandle* h, std::initializer_list<void*> bufs = {}) {
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->d_err) (void)hipFree(h->d_err);
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
+}
+
+// Synchronises, reads the first n deferred-error words and clears them when any is set. Each aria_<stage>_check maps the
+// bits to its own status on top of this.
+inline int stage_read_errors(StageHandle* h, int* words, int n) {
+    ARIA_HIP(hipSetDevice(h->device));
+    ARIA_HIP(hipStreamSynchronize(h->stream));
+    ARIA_HIP(memcpy_on(h->stream, words, h->d_err, n * sizeof(int), hipMemcpyDeviceToHost));
+    bool any = false;
+    for (int k = 0; k < n; k++) any |= words[k] != 0;
+    if (any) ARIA_HIP(memset_on(h->stream, h->d_err, 0, n * sizeof(int)));
+    return ARIA_OK;
+}
+
+// Grow-only device block: pointer and capacity (in elements) travel together, so a failed growth cannot leave a stale
+// capacity beside a null pointer -- after any failure the buffer is empty and the next reserve allocates again.
+template <typename T>
+struct DeviceBuffer {
+    T* p = nullptr;
+    size_t cap = 0;
+
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { release(); }
+    operator T*() const { return p; }
+
+    int reserve(hipStream_t st, size_t n) {
+        if (n <= cap) return ARIA_OK;
+        ARIA_HIP(hipStreamSynchronize(st));   // earlier work on the stream may still read the old block
+        T* old = p;
+        p = nullptr;
+        cap = 0;
+        if (old) ARIA_HIP(hipFree(old));
+        const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+        }
+        cap = n;
+        return ARIA_OK;
+    }
+
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// Single-pair staging of the blocking host forms of the pose, fundamental and map stages: one pair's keypoints, match list
+// and mask in the layout of the batch entry points, n_pairs = 1.
+struct PairStaging {
+    DeviceBuffer<aria_keypoint> d_kq, d_kt;
+    DeviceBuffer<aria_match> d_m;
+    DeviceBuffer<uint8_t> d_mask;
+    DeviceBuffer<int> d_counts;           // [0] nq, [1] nt, [2] n_matches
+    int64_t kp_stride = 1;                // of the last upload: max(nq, nt, 1) and max(n, 1), what the batch form is told
+    int match_cap = 1;
+
+    int create(hipStream_t st) { return d_counts.reserve(st, 4); }
+
+    // Rejects bad counts and out-of-range indices on the host, then grows the four buffers. No copy yet.
+    int prepare(hipStream_t st, const aria_keypoint* kq, int nq, const aria_keypoint* kt, int nt, const aria_match* matches, int n) {
+        if (nq < 0 || nt < 0 || n < 0 || (nq && !kq) || (nt && !kt) || (n && !matches)) return ARIA_E_INVALID;
+        for (int i = 0; i < n; i++)
+            if (matches[i].query_idx < 0 || matches[i].query_idx >= nq || matches[i].train_idx < 0 || matches[i].train_idx >= nt)
+                return ARIA_E_INVALID;
+        kp_stride = std::max(std::max(nq, nt), 1);
+        match_cap = std::max(n, 1);
+        int rc;
+        if ((rc = d_kq.reserve(st, (size_t)kp_stride)) != ARIA_OK) return rc;
+        if ((rc = d_kt.reserve(st, (size_t)kp_stride)) != ARIA_OK) return rc;
+        if ((rc = d_m.reserve(st, (size_t)match_cap)) != ARIA_OK) return rc;
+        return d_mask.reserve(st, (size_t)match_cap);
+    }
+
+    // Uploads what prepare() accepted: keypoints, matches, the optional input mask, the counts. Ends synchronised, so the
+    // host arrays, and anything else the caller has put on the stream before, are free again on return.
+    int copy(hipStream_t st, const aria_keypoint* kq, int nq, const aria_keypoint* kt, int nt, const aria_match* matches, int n,
+             const uint8_t* mask = nullptr) {
+        const int counts[4] = {nq, nt, n, 0};
+        if (nq) ARIA_HIP(hipMemcpyAsync(d_kq, kq, sizeof(aria_keypoint) * nq, hipMemcpyHostToDevice, st));
+        if (nt) ARIA_HIP(hipMemcpyAsync(d_kt, kt, sizeof(aria_keypoint) * nt, hipMemcpyHostToDevice, st));
+        if (n) ARIA_HIP(hipMemcpyAsync(d_m, matches, sizeof(aria_match) * n, hipMemcpyHostToDevice, st));
+        if (mask && n) ARIA_HIP(hipMemcpyAsync(d_mask, mask, (size_t)n, hipMemcpyHostToDevice, st));
+        ARIA_HIP(memcpy_on(st, d_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
+        return ARIA_OK;
+    }
+
+    int upload(hipStream_t st, const aria_keypoint* kq, int nq, const aria_keypoint* kt, int nt, const aria_match* matches, int n) {
+        const int rc = prepare(st, kq, nq, kt, nt, matches, n);
+        return rc != ARIA_OK ? rc : copy(st, kq, nq, kt, nt, matches, n);
+    }
+};
+
+}  // namespace aria

@@ -27,6 +27,8 @@
 #include <new>
 
 #include "common.h"
+#include "ransac_device.h"
+#include "stage_handle.h"
 #include "orb_plan.h"
 
 using namespace aria;
@@ -114,24 +116,6 @@ __device__ __forceinline__ void sad_slide(const uint8_t* lp, const uint8_t* rp, 
             acc[ps] = t;
         }
     }
-}
-
-// wave-ordered stable compaction of one 256-thread round: this lane's slot (valid when keep) and the round's total
-__device__ __forceinline__ int block_compact(bool keep, int* wsum, int& total) {
-    const unsigned long long b = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    if (lane == 0) wsum[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < ST_BLOCK / 64; w++) {
-        before += (w < wave) ? wsum[w] : 0;
-        total += wsum[w];
-    }
-    __syncthreads();
-    return before + rank;
 }
 
 // index of the bin holding rank k of a 256-bin histogram (k < total); k becomes the rank inside that bin
@@ -368,7 +352,7 @@ __global__ __launch_bounds__(ST_BLOCK) void k_stereo_match(
             if (o.right_idx >= 0 && !keep) po[i] = none;
         }
         int total;
-        const int slot = block_compact(keep, wsum, total);
+        const int slot = block_compact<ST_BLOCK>(keep, wsum, total);
         if (keep) {
             aria_match m;
             m.query_idx = i; m.train_idx = o.right_idx; m.distance = (float)o.hamming;
@@ -447,7 +431,7 @@ __global__ __launch_bounds__(ST_BLOCK) void k_stereo_scale(
             s = t[0] * d0 + t[1] * d1 + t[2] * d2;
         }
         int total;
-        const int slot = block_compact(use, wsum, total);
+        const int slot = block_compact<ST_BLOCK>(use, wsum, total);
         if (use) sc_keys[run + slot] = order_key(s);
         run += total;
     }
@@ -487,36 +471,22 @@ __global__ __launch_bounds__(ST_BLOCK) void k_stereo_scale(
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
-struct aria_stereo_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_stereo_s : StageHandle {
     aria_stereo_config cfg{};
     StereoParams prm{};
-    int* d_err = nullptr;
     // single-pair staging of the blocking host forms (grow-only)
-    uint8_t* d_img = nullptr;          size_t img_cap = 0;     // left, right: 2 * W * H
-    aria_keypoint* d_kp = nullptr;     size_t kp_cap = 0;      // left, right: 2 * cap
-    uint8_t* d_desc = nullptr;         size_t desc_cap = 0;    // 2 * cap * 32
-    aria_stereo_obs* d_obs = nullptr;  size_t obs_cap = 0;     // match: cap; scale: query + train
-    aria_match* d_m = nullptr;         size_t m_cap = 0;
-    uint8_t* d_mask = nullptr;         size_t mask_cap = 0;
+    DeviceBuffer<uint8_t> d_img;                               // left, right: 2 * W * H
+    DeviceBuffer<aria_keypoint> d_kp;                          // left, right: 2 * cap
+    DeviceBuffer<uint8_t> d_desc;                              // 2 * cap * 32
+    DeviceBuffer<aria_stereo_obs> d_obs;                       // match: cap; scale: query + train
+    DeviceBuffer<aria_match> d_m;
+    DeviceBuffer<uint8_t> d_mask;
     int* d_counts = nullptr;                                   // 4 ints
     aria_pose_result* d_pose = nullptr;
     aria_stereo_scale* d_scale = nullptr;
 };
 
 namespace {
-
-template <typename T>
-int grow(aria_stereo_s* h, T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return ARIA_OK;
-    ARIA_HIP(hipStreamSynchronize(h->stream));
-    if (p) { ARIA_HIP(hipFree(p)); p = nullptr; cap = 0; }
-    ARIA_HIP(hipMalloc((void**)&p, need * sizeof(T)));
-    cap = need;
-    return ARIA_OK;
-}
 
 bool fin(double v) { return std::isfinite(v); }
 
@@ -567,38 +537,24 @@ void aria_stereo_default_config(aria_stereo_config* c) {
 int aria_stereo_create(const aria_stereo_config* c, aria_stereo_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_stereo_s* h = new (std::nothrow) aria_stereo_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
     h->prm = make_params(*c);
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
+    int rc = stage_open(h, c->device, c->stream, 1, "aria_stereo_create");
+    if (rc == ARIA_OK) {
+        hipError_t e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_pose, sizeof(aria_pose_result));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_scale, sizeof(aria_stereo_scale));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_match), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)match_lds_bytes(ST_MAX_DIM, ST_MAX_KP));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_scale), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    ST_MAX_KP * (int)sizeof(unsigned long long));
+        if (e != hipSuccess) rc = hip_fail(e, "aria_stereo_create", __FILE__, __LINE__);
     }
-    hipError_t e = hipMalloc((void**)&h->d_err, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_pose, sizeof(aria_pose_result));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_scale, sizeof(aria_stereo_scale));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, sizeof(int));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_match), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)match_lds_bytes(ST_MAX_DIM, ST_MAX_KP));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_scale), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ST_MAX_KP * (int)sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "aria_stereo_create", __FILE__, __LINE__);
+    if (rc != ARIA_OK) {
         aria_stereo_destroy(h);
         return rc;
     }
@@ -608,12 +564,7 @@ int aria_stereo_create(const aria_stereo_config* c, aria_stereo_t* out) {
 
 void aria_stereo_destroy(aria_stereo_t h) {
     if (!h) return;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->d_err, h->d_img, h->d_kp, h->d_desc, h->d_obs, h->d_m, h->d_mask, h->d_counts, h->d_pose, h->d_scale};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    if (h->owns_stream && h->stream) hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_counts, h->d_pose, h->d_scale});
     delete h;
 }
 
@@ -621,11 +572,9 @@ void* aria_stereo_stream(aria_stereo_t h) { return h ? (void*)h->stream : nullpt
 
 int aria_stereo_check(aria_stereo_t h) {
     if (!h) return ARIA_E_INVALID;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int bits = 0;
-    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
     return (bits & ERRBIT_STEREO_INPUT) ? ARIA_E_INVALID : ARIA_OK;
 }
 
@@ -659,15 +608,15 @@ int aria_stereo_match(aria_stereo_t h, const uint8_t* img_left, const uint8_t* i
     ARIA_HIP(hipSetDevice(h->device));
     const size_t cap = (size_t)std::max(std::max(n_left, n_right), 1), px = (size_t)width * height;
     int rc;
-    if ((rc = grow(h, h->d_img, h->img_cap, 2 * px)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_kp, h->kp_cap, 2 * cap)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_desc, h->desc_cap, 2 * cap * 32)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_obs, h->obs_cap, cap)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_m, h->m_cap, cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_img.reserve(h->stream, 2 * px)) != ARIA_OK) return rc;
+    if ((rc = h->d_kp.reserve(h->stream, 2 * cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_desc.reserve(h->stream, 2 * cap * 32)) != ARIA_OK) return rc;
+    if ((rc = h->d_obs.reserve(h->stream, cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_m.reserve(h->stream, cap)) != ARIA_OK) return rc;
     // the staging halves sit at the buffers' current capacity, not at this call's
-    aria_keypoint* d_kr = h->d_kp + h->kp_cap / 2;
-    uint8_t* d_dr = h->d_desc + h->desc_cap / 2;
-    uint8_t* d_ir = h->d_img + h->img_cap / 2;
+    aria_keypoint* d_kr = h->d_kp + h->d_kp.cap / 2;
+    uint8_t* d_dr = h->d_desc + h->d_desc.cap / 2;
+    uint8_t* d_ir = h->d_img + h->d_img.cap / 2;
     const int counts[4] = {n_left, n_right, 0, 0};
     ARIA_HIP(hipMemcpy2DAsync(h->d_img, (size_t)width, img_left, (size_t)pitch, (size_t)width, (size_t)height,
                               hipMemcpyHostToDevice, h->stream));
@@ -721,10 +670,10 @@ int aria_stereo_scale_pose(aria_stereo_t h, const aria_pose_result* pose, const 
     ARIA_HIP(hipSetDevice(h->device));
     const size_t cap = (size_t)std::max(std::max(nq, nt), 1), mcap = (size_t)std::max(n_matches, 1);
     int rc;
-    if ((rc = grow(h, h->d_obs, h->obs_cap, 2 * cap)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_m, h->m_cap, mcap)) != ARIA_OK) return rc;
-    if ((rc = grow(h, h->d_mask, h->mask_cap, mcap)) != ARIA_OK) return rc;
-    aria_stereo_obs* d_ot = h->d_obs + h->obs_cap / 2;
+    if ((rc = h->d_obs.reserve(h->stream, 2 * cap)) != ARIA_OK) return rc;
+    if ((rc = h->d_m.reserve(h->stream, mcap)) != ARIA_OK) return rc;
+    if ((rc = h->d_mask.reserve(h->stream, mcap)) != ARIA_OK) return rc;
+    aria_stereo_obs* d_ot = h->d_obs + h->d_obs.cap / 2;
     const int counts[4] = {nq, nt, n_matches, 0};
     if (nq) ARIA_HIP(hipMemcpyAsync(h->d_obs, obs_query, sizeof(aria_stereo_obs) * nq, hipMemcpyHostToDevice, h->stream));
     if (nt) ARIA_HIP(hipMemcpyAsync(d_ot, obs_train, sizeof(aria_stereo_obs) * nt, hipMemcpyHostToDevice, h->stream));
@@ -732,8 +681,8 @@ int aria_stereo_scale_pose(aria_stereo_t h, const aria_pose_result* pose, const 
     if (mask && n_matches) ARIA_HIP(hipMemcpyAsync(h->d_mask, mask, (size_t)n_matches, hipMemcpyHostToDevice, h->stream));
     ARIA_HIP(hipMemcpyAsync(h->d_pose, pose, sizeof(aria_pose_result), hipMemcpyHostToDevice, h->stream));
     ARIA_HIP(memcpy_on(h->stream, h->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
-    rc = aria_stereo_scale_batch_device(h, h->d_pose, mask ? h->d_mask : nullptr, h->d_m, h->d_counts + 2, (int)mcap,
-                                        query_is_first, h->d_obs, h->d_counts, d_ot, h->d_counts + 1, (int64_t)(h->obs_cap / 2), 1,
+    rc = aria_stereo_scale_batch_device(h, h->d_pose, mask ? h->d_mask.p : nullptr, h->d_m, h->d_counts + 2, (int)mcap,
+                                        query_is_first, h->d_obs, h->d_counts, d_ot, h->d_counts + 1, (int64_t)(h->d_obs.cap / 2), 1,
                                         h->d_scale);
     if (rc != ARIA_OK) return rc;
     ARIA_HIP(memcpy_on(h->stream, out, h->d_scale, sizeof(aria_stereo_scale), hipMemcpyDeviceToHost));

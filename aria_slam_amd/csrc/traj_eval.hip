@@ -19,6 +19,7 @@
 #include <new>
 
 #include "common.h"
+#include "stage_handle.h"
 
 using namespace aria;
 
@@ -418,12 +419,8 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_traj_eval(const void* __restrict
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
-struct aria_eval_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+struct aria_eval_s : StageHandle {   // d_err: [0] deferred error bits, [1] the sampler's scan flag
     aria_eval_config cfg{};
-    int* d_err = nullptr;        // [0] deferred error bits, [1] the sampler's scan flag
     // staging of the host forms, grown on demand
     void* d_buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t cap[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -467,28 +464,11 @@ void aria_eval_default_config(aria_eval_config* c) {
 int aria_eval_create(const aria_eval_config* c, aria_eval_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_eval_config)) return ARIA_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    ARIA_HIP(hipGetDeviceCount(&ndev));
-    if (c->device < 0 || c->device >= ndev) {
-        std::snprintf(last_hip_error_buf(), 256, "device %d not present (%d devices)", c->device, ndev);
-        return ARIA_E_NO_DEVICE;
-    }
-    ARIA_HIP(hipSetDevice(c->device));
     aria_eval_s* h = new (std::nothrow) aria_eval_s();
     if (!h) return ARIA_E_OOM;
-    h->device = c->device;
     h->cfg = *c;
-    if (c->stream) {
-        h->stream = (hipStream_t)c->stream;
-    } else {
-        hipError_t e = create_stream(&h->stream);
-        if (e != hipSuccess) { delete h; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
-        h->owns_stream = true;
-    }
-    hipError_t e = hipMalloc((void**)&h->d_err, 2 * sizeof(int));
-    if (e == hipSuccess) e = memset_on(h->stream, h->d_err, 0, 2 * sizeof(int));
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "aria_eval_create", __FILE__, __LINE__);
+    const int rc = stage_open(h, c->device, c->stream, 2, "aria_eval_create");
+    if (rc != ARIA_OK) {
         aria_eval_destroy(h);
         return rc;
     }
@@ -498,12 +478,7 @@ int aria_eval_create(const aria_eval_config* c, aria_eval_t* out) {
 
 void aria_eval_destroy(aria_eval_t h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_err) (void)hipFree(h->d_err);
-    for (void* b : h->d_buf)
-        if (b) (void)hipFree(b);
-    if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    stage_close(h, {h->d_buf[0], h->d_buf[1], h->d_buf[2], h->d_buf[3], h->d_buf[4], h->d_buf[5], h->d_buf[6]});
     delete h;
 }
 
@@ -511,11 +486,9 @@ void* aria_eval_stream(aria_eval_t h) { return h ? (void*)h->stream : nullptr; }
 
 int aria_eval_check(aria_eval_t h) {
     if (!h) return ARIA_E_INVALID;
-    ARIA_HIP(hipSetDevice(h->device));
-    ARIA_HIP(hipStreamSynchronize(h->stream));
     int bits = 0;
-    ARIA_HIP(memcpy_on(h->stream, &bits, h->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (bits) ARIA_HIP(memset_on(h->stream, h->d_err, 0, sizeof(int)));
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
     return (bits & ERRBIT_EVAL_INPUT) ? ARIA_E_INVALID : ARIA_OK;
 }
 

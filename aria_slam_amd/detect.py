@@ -27,6 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import BOX_DTYPE, DETECTION_DTYPE, check
 from .detect_ref import ALL_CLASSES, DYNAMIC_CLASSES
 from .frontend import _ptr
@@ -43,45 +44,25 @@ def resize_table(src, dst):
     return (buf[:n] & 0xFFFF).astype(np.int32), (buf[:n] >> 16).astype(np.int32)
 
 
-class HipObjectDetector:
+class HipObjectDetector(StageHandle):
     """Binding of aria_det_t; the Python mirror of aria::adapters::hip::HipObjectDetector."""
+
+    _prefix, _config = "det", _lib.DetConfig
 
     def __init__(self, model=None, input_size=(640, 640), stream=None, device=0, max_batch=1, half=False, dynamic_classes=None,
                  max_candidates=300):
-        self._L = _lib.load_library()
-        cfg = _lib.DetConfig()
-        self._L.aria_det_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
+        cfg = self._default_config(device, stream)
         cfg.input_w, cfg.input_h = int(input_size[0]), int(input_size[1])
         cfg.max_batch = max_batch
         cfg.max_candidates = max_candidates
         cfg.out_half = int(bool(half))
-        self.config = cfg
         self.model = model
         self.dynamic_classes = dynamic_classes
-        h = C.c_void_p()
-        check(self._L.aria_det_create(C.byref(cfg), C.byref(h)), "aria_det_create")
-        self._h = h
+        self._create(cfg)
         self._input = None
         self._out = None
         self._pending = None
         self._raw = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_det_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def stream(self):
-        return self._L.aria_det_stream(self._h)
 
     def status(self):
         """(aria_det_check's status, detection rows needed, box rows needed), without raising."""

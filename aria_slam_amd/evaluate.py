@@ -9,11 +9,11 @@ run_batch_device left in HBM are scored where they lie and only the result recor
 
 As with the other stages, the handle's own stream is non-blocking: device buffers filled on torch's default stream must be
 synchronised before a *_device call, or the object must be created on the caller's stream."""
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import (EVAL_EST_FUSE_STATE, EVAL_EST_POSE12, EVAL_EST_XYZ, EVAL_RESULT_DTYPE, EVAL_TRUTH_DTYPE, FUSE_STATE_DTYPE,
                    check)
 from .frontend import _ptr
@@ -79,45 +79,17 @@ def _align(mode, default):
     return ALIGN_MODES[mode] if isinstance(mode, str) else int(mode)
 
 
-class HipTrajectoryEvaluator:
+class HipTrajectoryEvaluator(StageHandle):
     """Binding of aria_eval_t."""
 
+    _prefix, _config = "eval", _lib.EvalConfig
+
     def __init__(self, stream=None, device=0, align="sim3", rpe_delta=10):
-        self._L = _lib.load_library()
-        cfg = _lib.EvalConfig()
-        self._L.aria_eval_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
+        cfg = self._default_config(device, stream)
         cfg.align_mode = _align(align, cfg.align_mode)
         cfg.rpe_delta = rpe_delta
-        self.config = cfg
-        h = C.c_void_p()
-        check(self._L.aria_eval_create(C.byref(cfg), C.byref(h)), "aria_eval_create")
-        self._h = h
+        self._create(cfg)
         self.last_status = 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_eval_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def check(self):
-        """Synchronise; raise on a deferred error of the device calls (an invalid ground-truth table or trajectory)."""
-        check(self._L.aria_eval_check(self._h), "aria_eval_check")
-
-    def status(self):
-        """aria_eval_check's status code, without raising."""
-        return self._L.aria_eval_check(self._h)
-
-    @property
-    def stream(self):
-        return self._L.aria_eval_stream(self._h)
 
     # ---- ground truth
     def sample_ground_truth(self, gt, timestamps, raise_on_error=True):

@@ -8,11 +8,11 @@ over those inliers.
 
 As with HipPoseEstimator, the handle's own stream is non-blocking: device buffers filled on torch's default stream must be
 synchronised before estimate_batch_device, or the estimator must be created on the caller's stream."""
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import FUND_RESULT_DTYPE, KP_DTYPE, MATCH_DTYPE, POSE_RESULT_DTYPE, check
 from .frontend import _ptr
 from .pose import _kps
@@ -39,33 +39,17 @@ def _result_dict(rec, mask=None):
     return r
 
 
-class HipFundamentalEstimator:
+class HipFundamentalEstimator(StageHandle):
     """Binding of aria_fund_t; defaults are findFundamentalMat's as the reference calls it (threshold 3 px)."""
 
+    _prefix, _config = "fund", _lib.FundConfig
+
     def __init__(self, hypotheses=1024, threshold_px=3.0, seed=0, stream=None, device=0):
-        self._L = _lib.load_library()
-        cfg = _lib.FundConfig()
-        self._L.aria_fund_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
+        cfg = self._default_config(device, stream)
         cfg.hypotheses = hypotheses
         cfg.threshold_px = threshold_px
         cfg.seed = seed
-        self.config = cfg
-        h = C.c_void_p()
-        check(self._L.aria_fund_create(C.byref(cfg), C.byref(h)), "aria_fund_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_fund_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(cfg)
 
     def estimate(self, kp1, kp2, matches, query_is_first=True, pair_base=0):
         """One pair, host arrays (kp1 = query keypoints, kp2 = train keypoints, MATCH_DTYPE matches). Returns a dict of the
@@ -104,18 +88,6 @@ class HipFundamentalEstimator:
                                                  pair_base, idx.ctypes.data, nm.ctypes.data, F.ctypes.data, cnt.ctypes.data),
               "aria_fund_debug_hypotheses")
         return idx, nm, F, cnt
-
-    def check(self):
-        """Synchronise; raise on a deferred error of the batch calls (out-of-range counts or match indices)."""
-        check(self._L.aria_fund_check(self._h), "aria_fund_check")
-
-    def status(self):
-        """aria_fund_check's status code, without raising."""
-        return self._L.aria_fund_check(self._h)
-
-    @property
-    def stream(self):
-        return self._L.aria_fund_stream(self._h)
 
 
 def verify_loop_candidates(fund, pose, candidates, min_matches, pair_base=0):

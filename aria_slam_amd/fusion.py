@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import (FUSE_FILTER_DTYPE, FUSE_STATE_DTYPE, FUSE_VISUAL_DTYPE, IMU_SAMPLE_DTYPE, PREINT_RESULT_DTYPE, check)
 from .frontend import _ptr
 
@@ -66,40 +67,12 @@ def filter_from_ref(flt):
     return rec
 
 
-class _FuseHandle:
+class _FuseHandle(StageHandle):
+    _prefix, _config = "fuse", _lib.FuseConfig
+
     def __init__(self, stream=None, device=0):
-        self._L = _lib.load_library()
-        cfg = _lib.FuseConfig()
-        self._L.aria_fuse_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
-        self.config = cfg
-        h = C.c_void_p()
-        check(self._L.aria_fuse_create(C.byref(cfg), C.byref(h)), "aria_fuse_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_fuse_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def check(self):
-        """Synchronise; raise on a deferred error of the device calls (an invalid track or interval)."""
-        check(self._L.aria_fuse_check(self._h), "aria_fuse_check")
-
-    def status(self):
-        """aria_fuse_check's status code, without raising."""
-        return self._L.aria_fuse_check(self._h)
-
-    @property
-    def stream(self):
-        return self._L.aria_fuse_stream(self._h)
+        cfg = self._default_config(device, stream)
+        self._create(cfg)
 
 
 class HipSensorFusion(_FuseHandle):

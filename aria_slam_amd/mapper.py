@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import KP_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, check
 from .frontend import _ptr
 
@@ -60,41 +61,25 @@ def _pose12(T):
     return np.ascontiguousarray(T.reshape(-1)[:12])
 
 
-class HipMapper:
+class HipMapper(StageHandle):
     """Binding of aria_map_t. K = (fx, fy, cx, cy); defaults are EuRoC cam0 and the reference Mapper's thresholds."""
+
+    _prefix, _config = "map", _lib.MapConfig
 
     def __init__(self, K=None, min_depth=0.1, max_depth=50.0, min_parallax=1.0, max_reproj=2.0, capacity=1 << 16,
                  min_pose_inliers=10, stream=None, device=0):
-        self._L = _lib.load_library()
-        cfg = _lib.MapConfig()
-        self._L.aria_map_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
+        cfg = self._default_config(device, stream)
         if K is not None:
             cfg.fx, cfg.fy, cfg.cx, cfg.cy = (float(v) for v in K)
         cfg.min_depth, cfg.max_depth = min_depth, max_depth
         cfg.min_parallax_deg, cfg.max_reproj_px = min_parallax, max_reproj
         cfg.capacity = capacity
         cfg.min_pose_inliers = min_pose_inliers
-        self.config = cfg
-        h = C.c_void_p()
-        check(self._L.aria_map_create(C.byref(cfg), C.byref(h)), "aria_map_create")
-        self._h = h
+        self._create(cfg)
 
     @property
     def K(self):
         return (self.config.fx, self.config.fy, self.config.cx, self.config.cy)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_map_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def triangulate(self, kp1, kp2, matches, pose1, pose2, image=None, mask=None, query_is_first=True, pair_id=0):
         """One pair from host arrays; blocks and appends. kp1 = the query keypoints, kp2 = the train keypoints (frame dicts or
@@ -180,16 +165,3 @@ class HipMapper:
     def export_pcd(self, path):
         with open(path, "w") as f:
             f.write(pcd_text(self.read()))
-
-    def check(self):
-        """Synchronise; raise on a deferred error (bad counts or indices: ARIA_E_INVALID; a cut append:
-        ARIA_E_OUTPUT_TOO_SMALL)."""
-        check(self._L.aria_map_check(self._h), "aria_map_check")
-
-    def status(self):
-        """aria_map_check's status code, without raising."""
-        return self._L.aria_map_check(self._h)
-
-    @property
-    def stream(self):
-        return self._L.aria_map_stream(self._h)

@@ -5,11 +5,11 @@ cv::recoverPose, src/euroc_eval.cpp:178-201). aria_slam_amd.pose_ref restates th
 The handle's own stream is non-blocking: it is not ordered against the legacy default stream, where torch works unless told
 otherwise. Device buffers filled there must be synchronised (torch.cuda.synchronize()) before estimate_batch_device, or
 the estimator must be created on the caller's stream."""
-import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import KP_DTYPE, MATCH_DTYPE, POSE_RESULT_DTYPE, check
 from .frontend import _ptr
 
@@ -32,40 +32,24 @@ def _kps(frame_or_array):
     return k
 
 
-class HipPoseEstimator:
+class HipPoseEstimator(StageHandle):
     """Binding of aria_pose_t. K = (fx, fy, cx, cy); defaults are EuRoC cam0 and OpenCV's findEssentialMat / recoverPose."""
 
+    _prefix, _config = "pose", _lib.PoseConfig
+
     def __init__(self, K=None, hypotheses=1024, threshold_px=1.0, distance_thresh=50.0, seed=0, stream=None, device=0):
-        self._L = _lib.load_library()
-        cfg = _lib.PoseConfig()
-        self._L.aria_pose_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
+        cfg = self._default_config(device, stream)
         cfg.hypotheses = hypotheses
         if K is not None:
             cfg.fx, cfg.fy, cfg.cx, cfg.cy = (float(v) for v in K)
         cfg.threshold_px = threshold_px
         cfg.distance_thresh = distance_thresh
         cfg.seed = seed
-        self.config = cfg
-        h = C.c_void_p()
-        check(self._L.aria_pose_create(C.byref(cfg), C.byref(h)), "aria_pose_create")
-        self._h = h
+        self._create(cfg)
 
     @property
     def K(self):
         return (self.config.fx, self.config.fy, self.config.cx, self.config.cy)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_pose_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def estimate(self, kp1, kp2, matches, query_is_first=True, pair_base=0):
         """One pair, host arrays: kp1 = the query keypoints (frame dict or KP_DTYPE array), kp2 = the train keypoints,
@@ -108,15 +92,3 @@ class HipPoseEstimator:
                                                  pair_base, idx.ctypes.data, E.ctypes.data, cnt.ctypes.data),
               "aria_pose_debug_hypotheses")
         return idx, E, cnt
-
-    def check(self):
-        """Synchronise; raise on a deferred error of the batch calls (out-of-range counts or match indices)."""
-        check(self._L.aria_pose_check(self._h), "aria_pose_check")
-
-    def status(self):
-        """aria_pose_check's status code, without raising."""
-        return self._L.aria_pose_check(self._h)
-
-    @property
-    def stream(self):
-        return self._L.aria_pose_stream(self._h)

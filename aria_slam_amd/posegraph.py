@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import GRAPH_EDGE_DTYPE, GRAPH_RESULT_DTYPE, check
 from .frontend import _ptr
 from .graph_ref import PoseGraph
@@ -50,36 +51,20 @@ def _result_dict(rec):
     return r
 
 
-class HipPoseGraphOptimizer(PoseGraph):
+class HipPoseGraphOptimizer(StageHandle, PoseGraph):
     """Binding of aria_graph_t behind the reference class's methods. The first vertex added is the fixed one; loop edges
     carry 10x the information; edges that name an unknown id are dropped."""
+
+    _prefix, _config = "graph", _lib.GraphConfig
 
     def __init__(self, max_vertices=4096, max_edges=8192, max_graphs=1, pcg_max_iters=1000, pcg_rel_tol=1e-8, stream=None,
                  device=0):
         super().__init__()
-        self._L = _lib.load_library()
-        cfg = _lib.GraphConfig()
-        self._L.aria_graph_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
+        cfg = self._default_config(device, stream)
         cfg.max_graphs, cfg.max_vertices, cfg.max_edges = max_graphs, max_vertices, max_edges
         cfg.pcg_max_iters, cfg.pcg_rel_tol = pcg_max_iters, pcg_rel_tol
-        self.config = cfg
-        h = C.c_void_p()
-        check(self._L.aria_graph_create(C.byref(cfg), C.byref(h)), "aria_graph_create")
-        self._h = h
+        self._create(cfg)
         self.last_result = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_graph_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- the reference class's optimize(): the graph held by this object
     def optimize(self, iterations=10):
@@ -148,15 +133,3 @@ class HipPoseGraphOptimizer(PoseGraph):
                                                  rec.ctypes.data if E else None, E, C.byref(chi2), b.ctypes.data,
                                                  D.ctypes.data, W.ctypes.data), "aria_graph_debug_linearize")
         return chi2.value, b[:V], D[:V], W[:E]
-
-    def check(self):
-        """Synchronise; raise on a deferred error of the batch calls (an invalid or too large graph)."""
-        check(self._L.aria_graph_check(self._h), "aria_graph_check")
-
-    def status(self):
-        """aria_graph_check's status code, without raising."""
-        return self._L.aria_graph_check(self._h)
-
-    @property
-    def stream(self):
-        return self._L.aria_graph_stream(self._h)

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import StageHandle
 from ._lib import KP_DTYPE, MATCH_DTYPE, POSE_RESULT_DTYPE, STEREO_OBS_DTYPE, STEREO_SCALE_DTYPE, check
 from .frontend import _ptr
 
@@ -25,18 +26,16 @@ def _addr(a):
     return a.ctypes.data if len(a) else None
 
 
-class HipStereoMatcher:
+class HipStereoMatcher(StageHandle):
     """Binding of aria_stereo_t. K = (fx, fy, cx, cy) of the rectified left camera (default EuRoC cam0); max_disparity
     defaults to fx (depth >= baseline)."""
+
+    _prefix, _config = "stereo", _lib.StereoConfig
 
     def __init__(self, K=None, baseline=0.110, min_disparity=0.0, max_disparity=None, th_hamming=75, sad_half_window=5,
                  sad_slide=5, band_factor=2.0, max_octave_diff=1, median_factor=2.1, min_scale_matches=5, stream=None,
                  device=0):
-        self._L = _lib.load_library()
-        cfg = _lib.StereoConfig()
-        self._L.aria_stereo_default_config(C.byref(cfg))
-        cfg.device = device
-        cfg.stream = stream
+        cfg = self._default_config(device, stream)
         if K is not None:
             cfg.fx, cfg.fy, cfg.cx, cfg.cy = (float(v) for v in K)
         cfg.baseline = baseline
@@ -45,25 +44,11 @@ class HipStereoMatcher:
         cfg.th_hamming, cfg.sad_half_window, cfg.sad_slide = th_hamming, sad_half_window, sad_slide
         cfg.band_factor, cfg.max_octave_diff, cfg.median_factor = band_factor, max_octave_diff, median_factor
         cfg.min_scale_matches = min_scale_matches
-        self.config = cfg
-        h = C.c_void_p()
-        check(self._L.aria_stereo_create(C.byref(cfg), C.byref(h)), "aria_stereo_create")
-        self._h = h
+        self._create(cfg)
 
     @property
     def K(self):
         return (self.config.fx, self.config.fy, self.config.cx, self.config.cy)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.aria_stereo_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def match(self, img_left, img_right, left, right):
         """One rectified pair from host arrays; blocks. left / right: frame dicts of OrbHipExtractor.extract (keypoints,
@@ -132,15 +117,3 @@ class HipStereoMatcher:
             self._h, _ptr(d_pose), _ptr(d_mask), _ptr(d_matches), _ptr(d_nmatches), match_cap, 1 if query_is_first else 0,
             _ptr(d_obs_query), _ptr(d_nq), _ptr(d_obs_train), _ptr(d_nt), kp_stride, n_pairs, _ptr(d_out)),
             "aria_stereo_scale_batch_device")
-
-    def check(self):
-        """Synchronise; raise on a deferred error of the batch calls (out-of-range counts or match indices)."""
-        check(self._L.aria_stereo_check(self._h), "aria_stereo_check")
-
-    def status(self):
-        """aria_stereo_check's status code, without raising."""
-        return self._L.aria_stereo_check(self._h)
-
-    @property
-    def stream(self):
-        return self._L.aria_stereo_stream(self._h)

@@ -196,6 +196,8 @@ def test_detect_stage_is_in_the_product_build_without_float_atomics_or_environme
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
     assert "detect_stage.hip" in mk.split("SRC :=")[1].split("\n")[0]
     text = open(os.path.join(PKG, "csrc", "detect_stage.hip")).read()
+    # the rules below follow the code into the shared headers this file includes
+    text += "".join(open(os.path.join(PKG, "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h") if '#include "%s"' % h in text)
     assert "getenv" not in text and "atomicAdd(&s_m" in text
     for line in text.splitlines():
         if "atomic" in line and not line.lstrip().startswith("//"):

@@ -366,6 +366,8 @@ def test_traj_eval_is_in_the_product_build_reads_no_environment_and_has_no_float
     src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
     assert "traj_eval.hip" in src_line
     text = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "traj_eval.hip")).read()
+    # the rules below follow the code into the shared headers this file includes
+    text += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h") if '#include "%s"' % h in text)
     assert "getenv" not in text and "atomicAdd" not in text and "atomicMax" not in text and "unsafeAtomic" not in text
     assert set(re.findall(r"\batomic[A-Z]\w*", text)) == {"atomicOr"}      # the integer error word only
     hm = open(os.path.join(PKG, "host", "Makefile")).read()

@@ -348,6 +348,8 @@ def test_imu_fusion_is_in_the_product_build_reads_no_environment_and_has_no_floa
     src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
     assert "imu_fusion.hip" in src_line
     text = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "imu_fusion.hip")).read()
+    # the rules below follow the code into the shared headers this file includes
+    text += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h") if '#include "%s"' % h in text)
     assert "getenv" not in text and "atomicAdd" not in text
     assert "__syncthreads" not in text      # the recurrence has no workgroup barrier
 

@@ -199,6 +199,8 @@ def test_map_triangulate_is_in_the_product_build_and_reads_no_environment():
     src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
     assert "map_triangulate.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "map_triangulate.hip")).read()
+    # the rules below follow the code into the shared headers this file includes
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h") if '#include "%s"' % h in src)
     assert "getenv" not in src
 
 

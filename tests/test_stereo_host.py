@@ -250,6 +250,8 @@ def test_stereo_match_is_in_the_product_build_and_reads_no_environment():
     src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
     assert "stereo_match.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "stereo_match.hip")).read()
+    # the rules below follow the code into the shared headers this file includes
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h") if '#include "%s"' % h in src)
     assert "getenv" not in src
 
 

@@ -73,7 +73,7 @@ def main():
     models = float(rec["n_models"].sum())
     valid = int(rec["valid"].sum())
     evals = models * n
-    res = dict(pairs=B, matches=n, outliers=a.outliers, hypotheses=a.hypotheses, ms_median=ms, ms_min=float(np.min(times)),
+    res = dict(pairs=B, matches=n, outliers=a.outliers, hypotheses=a.hypotheses, ms_median=ms, ms_min=float(np.min(times)), ms_max=float(np.max(times)),
                us_per_pair=ms * 1e3 / B, models_per_hypothesis=models / max(1, valid) / a.hypotheses,
                error_evals_per_s=evals / (ms * 1e-3), valid=valid, mean_inliers=float(rec["n_inliers"].mean()))
     print("%d pairs x %d matches, %d hypotheses: %.3f ms (median of %d), %.3f us/pair, %.3f models/hypothesis, %.3g error "

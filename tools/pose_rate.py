@@ -67,7 +67,7 @@ def main():
     rec = np.frombuffer(out.cpu().numpy().tobytes(), A._lib.POSE_RESULT_DTYPE)
     ms = float(np.median(times))
     evals = float(B) * a.hypotheses * n
-    res = dict(pairs=B, matches=n, outliers=a.outliers, hypotheses=a.hypotheses, ms_median=ms, ms_min=float(np.min(times)),
+    res = dict(pairs=B, matches=n, outliers=a.outliers, hypotheses=a.hypotheses, ms_median=ms, ms_min=float(np.min(times)), ms_max=float(np.max(times)),
                us_per_pair=ms * 1e3 / B, sampson_evals_per_s=evals / (ms * 1e-3), valid=int(rec["valid"].sum()),
                mean_inliers=float(rec["n_inliers"].mean()), mean_pose_inliers=float(rec["n_pose_inliers"].mean()))
     print("%d pairs x %d matches, %d hypotheses: %.3f ms (median of %d), %.3f us/pair, %.3g hypothesis evaluations/s"
