@@ -70,6 +70,10 @@ EXPORTS = [
     # sparse stereo on rectified pairs (depth per keypoint, metric scale of a relative pose), additive to ABI 4
     "aria_stereo_default_config", "aria_stereo_create", "aria_stereo_destroy", "aria_stereo_stream", "aria_stereo_check",
     "aria_stereo_match_batch_device", "aria_stereo_match", "aria_stereo_scale_batch_device", "aria_stereo_scale_pose",
+    # undistortion and stereo rectification (radtan maps, batch remap in HBM, keypoints), additive to ABI 4
+    "aria_rect_default_config", "aria_rect_create", "aria_rect_destroy", "aria_rect_stream", "aria_rect_check",
+    "aria_rect_stereo_geometry", "aria_rect_remap_batch_device", "aria_rect_remap", "aria_rect_points_batch_device",
+    "aria_rect_points", "aria_rect_get_map", "aria_rect_algorithmic_bytes",
 ]
 
 
@@ -241,6 +245,23 @@ STEREO_OBS_DTYPE = np.dtype([("u_right", "<f4"), ("disparity", "<f4"), ("depth",
 STEREO_SCALE_DTYPE = np.dtype([("scale", "<f8"), ("n_used", "<i4"), ("valid", "<i4")])
 
 
+class RectCamera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 5),
+                ("R", C.c_double * 9)]
+
+
+class RectConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("src_width", C.c_int),
+                ("src_height", C.c_int), ("dst_width", C.c_int), ("dst_height", C.c_int), ("n_cameras", C.c_int),
+                ("cam", RectCamera * 2), ("new_fx", C.c_double), ("new_fy", C.c_double), ("new_cx", C.c_double),
+                ("new_cy", C.c_double), ("fill", C.c_int), ("reserved", C.c_int)]
+
+
+# an entry of the rectification map: qx | qy << 16 in 1/32 px, RECT_INVALID = no source
+RECT_MAP_DTYPE = np.dtype("<u4")
+RECT_INVALID = 0xFFFFFFFF
+
+
 class AriaError(RuntimeError):
     def __init__(self, status, where=""):
         self.status = status
@@ -388,6 +409,8 @@ def load_library():
         _bind_det(L)
     if hasattr(L, "aria_stereo_create"):
         _bind_stereo(L)
+    if hasattr(L, "aria_rect_create"):
+        _bind_rect(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -493,6 +516,19 @@ def _bind_stereo(L):
     L.aria_stereo_match.argtypes = [p, p, p, i, i, i, p, p, i, p, p, i, p, p, C.POINTER(C.c_int)]
     L.aria_stereo_scale_batch_device.argtypes = [p, p, p, p, p, i, i, p, p, p, p, i64, i, p]
     L.aria_stereo_scale_pose.argtypes = [p, p, p, p, i, i, p, i, p, i, p]
+
+
+def _bind_rect(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "rect")
+    L.aria_rect_stereo_geometry.argtypes = [p, p, p, p, p, C.POINTER(C.c_double)]
+    L.aria_rect_remap_batch_device.argtypes = [p, i, p, i64, i, i, p, i64, i]
+    L.aria_rect_remap.argtypes = [p, i, p, i, p, i]
+    L.aria_rect_points_batch_device.argtypes = [p, i, p, p, i64, i, p]
+    L.aria_rect_points.argtypes = [p, i, p, i, p]
+    L.aria_rect_get_map.argtypes = [p, i, p, i]
+    L.aria_rect_algorithmic_bytes.restype = i64
+    L.aria_rect_algorithmic_bytes.argtypes = [i, i]
 
 
 def status_string(status):

@@ -18,7 +18,13 @@
 // is read when it is there (the reference's reader names cam1 and never reads it): a cam1 image is paired with the cam0 image
 // of EQUAL timestamp (the parsed seconds are compared). hasRight(i) tells whether image i has a partner; a sequence without
 // cam1 loads exactly as before.
-// The stereo stage (aria_hip/HipStereoMatcher.hpp) needs RECTIFIED pairs; this reader does not rectify.
+// The stereo stage (aria_hip/HipStereoMatcher.hpp) needs RECTIFIED pairs; this reader does not rectify: see aria_rect_*
+// (aria_hip/HipRectifier.hpp), which takes the calibration read here.
+//     <root>/mav0/cam0/sensor.yaml, <root>/mav0/cam1/sensor.yaml
+// are read when they are there, key by key and line by line as the reference reads cam0's (EuRoCReader.cpp:220-275:
+// "intrinsics:" and "distortion_coefficients:" as bracketed lists on the key's line), plus "resolution:" and the 16 values of
+// T_BS's "data:" list, which may run over several lines. hasCalibration(cam) tells whether camera cam (0 or 1) has one; a
+// sequence without them loads exactly as before.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -46,6 +52,14 @@ struct AslGroundTruth {              // the 17 doubles of aria_eval_truth, in it
     double ba[3] = {0, 0, 0};
 };
 
+struct AslCalibration {             // one camera's sensor.yaml
+    double intrinsics[4] = {0, 0, 0, 0};     // fx, fy, cx, cy
+    double distortion[5] = {0, 0, 0, 0, 0};  // radtan k1, k2, p1, p2, k3 (k3 = 0 when the file has four)
+    double T_BS[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // sensor to body, row-major
+    int width = 0, height = 0;               // resolution, 0 when the file has none
+    std::string distortion_model;            // "radial-tangential" in EuRoC; empty when the file has none
+};
+
 class AslSequence {
 public:
     // dataset_path may be the sequence root (containing mav0/) or the mav0 directory itself
@@ -65,6 +79,10 @@ public:
     bool hasRight(std::size_t i) const { return i < right_.size() && !right_[i].empty(); }
     bool hasStereo() const;          // cam1 is there and every cam0 image has its partner
     void readRight(std::size_t i, std::vector<std::uint8_t>& gray, int& width, int& height) const;
+    // sensor.yaml of cam0 (cam = 0) / cam1 (cam = 1): whether it was there with four intrinsics, and its content (throws
+    // std::runtime_error without one)
+    bool hasCalibration(int cam) const { return cam >= 0 && cam < 2 && has_calibration_[cam]; }
+    const AslCalibration& calibration(int cam) const;
 
 private:
     std::vector<AslImage> images_;
@@ -72,7 +90,12 @@ private:
     std::vector<AslImu> imu_;
     std::vector<std::size_t> imu_begin_, imu_end_;
     std::vector<AslGroundTruth> ground_truth_;
+    AslCalibration calibration_[2];
+    bool has_calibration_[2] = {false, false};
 };
+
+// One sensor.yaml (see header comment). False when the file is missing or holds no four intrinsics.
+bool load_sensor_yaml(const std::string& path, AslCalibration& out);
 
 // PNG -> 8-bit grayscale (see header comment). Throws std::runtime_error.
 void decode_png_gray(const std::vector<std::uint8_t>& file, std::vector<std::uint8_t>& gray, int& width, int& height);

@@ -1,7 +1,8 @@
 // aria::adapters::hip::HipStereoMatcher -- sparse stereo over the C-ABI (include/aria_orb_hip.h, "sparse stereo"): a depth per
 // left keypoint of a RECTIFIED stereo pair and the metric scale of a relative pose. The reference has no stereo code (its
 // roadmap item H19); the definition is the NumPy restatement aria_slam_amd/stereo_ref.py, which the device equals bit for bit.
-// Rectification / undistortion is not part of the stage: the caller hands in row-aligned images.
+// Rectification / undistortion is not part of the stage: the caller hands in row-aligned images -- see aria_rect_*
+// (aria_hip/HipRectifier.hpp), which makes them from raw ones.
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -157,6 +157,69 @@ void decode_png_gray(const std::vector<std::uint8_t>& file, std::vector<std::uin
     height = h;
 }
 
+// the numbers of a bracketed list that starts on `text`'s first '[' (up to the closing ']' or the end of the text)
+static std::vector<double> bracket_numbers(const std::string& text) {
+    std::vector<double> v;
+    const std::size_t lo = text.find('[');
+    if (lo == std::string::npos) return v;
+    std::size_t hi = text.find(']', lo);
+    if (hi == std::string::npos) hi = text.size();
+    std::string body = text.substr(lo + 1, hi - lo - 1);
+    for (char& c : body)
+        if (c == ',') c = ' ';
+    std::stringstream ss(body);
+    std::string token;
+    while (ss >> token) {
+        char* end = nullptr;
+        const double d = std::strtod(token.c_str(), &end);
+        if (end != token.c_str()) v.push_back(d);
+    }
+    return v;
+}
+
+bool load_sensor_yaml(const std::string& path, AslCalibration& out) {
+    std::ifstream file(path);
+    if (!file.is_open()) return false;
+    out = AslCalibration{};
+    std::vector<std::string> lines;
+    std::string line;
+    while (std::getline(file, line)) lines.push_back(line);
+    bool in_tbs = false, have_k = false;
+    for (std::size_t n = 0; n < lines.size(); n++) {
+        const std::string& ln = lines[n];
+        const std::size_t first = ln.find_first_not_of(" \t");
+        if (first != std::string::npos && ln.compare(first, 4, "T_BS") == 0) in_tbs = true;
+        if (ln.find("intrinsics:") != std::string::npos) {                    // EuRoCReader.cpp:233
+            const std::vector<double> v = bracket_numbers(ln);
+            if (v.size() >= 4) { for (int k = 0; k < 4; k++) out.intrinsics[k] = v[(std::size_t)k]; have_k = true; }
+        } else if (ln.find("distortion_coefficients:") != std::string::npos) { // :247
+            const std::vector<double> v = bracket_numbers(ln);
+            for (std::size_t k = 0; k < v.size() && k < 5; k++) out.distortion[k] = v[k];
+        } else if (ln.find("distortion_model:") != std::string::npos) {
+            std::string m = ln.substr(ln.find(':') + 1);
+            const std::size_t a = m.find_first_not_of(" \t"), b = m.find_last_not_of(" \t\r");
+            out.distortion_model = a == std::string::npos ? std::string() : m.substr(a, b - a + 1);
+        } else if (ln.find("resolution:") != std::string::npos) {
+            const std::vector<double> v = bracket_numbers(ln);
+            if (v.size() >= 2) { out.width = (int)v[0]; out.height = (int)v[1]; }
+        } else if (in_tbs && ln.find("data:") != std::string::npos) {
+            std::string text = ln;
+            std::size_t k = n;
+            while (text.find(']') == std::string::npos && k + 1 < lines.size()) text += " " + lines[++k];
+            const std::vector<double> v = bracket_numbers(text);
+            if (v.size() == 16)
+                for (int j = 0; j < 16; j++) out.T_BS[j] = v[(std::size_t)j];
+            in_tbs = false;
+        }
+    }
+    return have_k;
+}
+
+const AslCalibration& AslSequence::calibration(int cam) const {
+    if (!hasCalibration(cam)) throw std::runtime_error("no mav0/cam" + std::to_string(cam) + "/sensor.yaml with intrinsics");
+    return calibration_[cam];
+}
+
 bool AslSequence::load(const std::string& dataset_path) {
     images_.clear();
     std::string cam = dataset_path + "/mav0/cam0";
@@ -174,6 +237,9 @@ bool AslSequence::load(const std::string& dataset_path) {
             if (k < cam1.size() && cam1[k].timestamp == images_[i].timestamp) right_[i] = cam1[k].path;
         }
     }
+    // sensor.yaml of both cameras; their absence is not an error
+    for (int c = 0; c < 2; c++)
+        has_calibration_[c] = load_sensor_yaml(cam.substr(0, cam.size() - 4) + "cam" + std::to_string(c) + "/sensor.yaml", calibration_[c]);
     // imu0 beside cam0 (EuRoCReader.cpp:110-154); its absence is not an error
     imu_.clear();
     std::ifstream imu_file(cam.substr(0, cam.size() - 4) + "imu0/data.csv");
@@ -266,6 +332,21 @@ int aria_asl_stereo(const char* dataset_path, int* has_right, int cap) {
     if (!s.load(dataset_path)) return -1;
     for (std::size_t i = 0; i < s.size() && (int)i < cap; i++) has_right[i] = s.hasRight(i) ? 1 : 0;
     return (int)s.size();
+}
+
+// Camera cam's sensor.yaml as 27 doubles: intrinsics[4], distortion[5], T_BS[16], width, height; returns 1 with a calibration,
+// 0 without, -1 when the sequence does not load.
+int aria_asl_calibration(const char* dataset_path, int cam, double* out27) {
+    aria::io::AslSequence s;
+    if (!s.load(dataset_path)) return -1;
+    if (!s.hasCalibration(cam)) return 0;
+    const aria::io::AslCalibration& c = s.calibration(cam);
+    std::memcpy(out27, c.intrinsics, 4 * sizeof(double));
+    std::memcpy(out27 + 4, c.distortion, 5 * sizeof(double));
+    std::memcpy(out27 + 9, c.T_BS, 16 * sizeof(double));
+    out27[25] = c.width;
+    out27[26] = c.height;
+    return 1;
 }
 
 // IMU samples as rows [t, accel xyz, gyro xyz] (the layout of aria_imu_sample) and [begin, end) per image; returns the number

@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -72,13 +72,20 @@
 // reports the optimised poses), else for --pose. Without the flag nothing changes and every other output is byte-identical.
 //
 // --stereo BASELINE_M [--stereo-out FILE] (frame-at-a-time path; the sequence needs a mav0/cam1 image of equal timestamp for
-// every cam0 image, and the pairs must be RECTIFIED -- this driver does not rectify): sparse stereo on the device (include/
+// every cam0 image, and the pairs must be RECTIFIED -- or --rectify given, see below): sparse stereo on the device (include/
 // aria_orb_hip.h, "sparse stereo"; aria_hip/HipStereoMatcher.hpp). The right image of every frame is extracted by a second
 // extractor and every left keypoint gets a depth. One line per frame, "timestamp matched median_depth", goes to FILE (to the
 // standard output with the prefix "stereo " without --stereo-out). With --pose as well, the relative translation of every
 // accepted pose (|t| = 1 from recoverPose) is multiplied by the metric scale recovered from the two frames' stereo
 // observations when that is valid, before it is chained into current_pose, and the line gets two more columns, "scale_valid
 // scale" (0 1 for a frame without an accepted pose). Without --stereo nothing of this runs and every output is byte-identical.
+//
+// --rectify (frame-at-a-time path; the sequence needs mav0/cam0/sensor.yaml, and mav0/cam1/sensor.yaml with --stereo): the
+// radtan distortion the reference parses and never applies is removed on the device (include/aria_orb_hip.h, "rectification";
+// aria_hip/HipRectifier.hpp). Without --stereo every cam0 image is undistorted before extraction (new K = cam0's K) and the
+// pose and map stages take that K. With --stereo both images of a frame are rectified with the rotations built from the two
+// T_BS, and the stereo, pose and map stages take the rectified K; a BASELINE_M of 0 then means the calibration's baseline. A
+// missing sensor.yaml is an error message and exit status 1. Without the flag every output is byte-identical.
 //
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
@@ -108,6 +115,7 @@
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
+#include "aria_hip/HipRectifier.hpp"
 #include "aria_hip/HipSensorFusion.hpp"
 #include "aria_hip/HipStereoMatcher.hpp"
 #include "aria_hip/HipTrajectoryEvaluator.hpp"
@@ -143,7 +151,9 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify]\n"
+                             "  --rectify: undistort cam0 (with --stereo: rectify cam0 and cam1) on the device from mav0/cam*/sensor.yaml; --stereo 0 then takes\n"
+                             "             the calibration's baseline\n"
                              "  --stereo baseline_m: sparse stereo over mav0/cam1 (rectified pairs): a depth per keypoint, one line per frame; with --pose the\n"
                              "                       relative translations take the metric scale\n"
                              "  --eval file: ATE / RPE of the --pose (and --optimize, --fuse) trajectories against the sequence's ground truth (needs --pose)\n"
@@ -157,7 +167,7 @@ int main(int argc, char** argv) {
     std::string csv, pose_file, map_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
-    bool stereo = false;
+    bool stereo = false, rectify = false;
     std::string stereo_file;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
@@ -177,6 +187,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rpe-delta") && i + 1 < argc) rpe_delta = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stereo") && i + 1 < argc) { stereo = true; stereo_baseline = std::atof(argv[++i]); }
         else if (!std::strcmp(argv[i], "--stereo-out") && i + 1 < argc) stereo_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--rectify")) rectify = true;
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -210,9 +221,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--pose runs on the frame-at-a-time path only (no --batch, --devices, --shards)\n");
         return -1;
     }
-    if ((stereo || !stereo_file.empty()) && (!stereo || !(stereo_baseline > 0) || batch > 0 || devices > 1 || shards > 1)) {
-        std::fprintf(stderr, "--stereo needs a baseline in metres > 0 and runs on the frame-at-a-time path only (no --batch, --devices, --shards); "
+    if ((stereo || !stereo_file.empty()) && (!stereo || !(stereo_baseline > 0 || (rectify && stereo_baseline == 0)) || batch > 0 || devices > 1 || shards > 1)) {
+        std::fprintf(stderr, "--stereo needs a baseline in metres > 0 (or 0 with --rectify: the calibration's) and runs on the frame-at-a-time path only (no --batch, --devices, --shards); "
                              "--stereo-out needs --stereo\n");
+        return 1;
+    }
+    if (rectify && (batch > 0 || devices > 1 || shards > 1)) {
+        std::fprintf(stderr, "--rectify runs on the frame-at-a-time path only (no --batch, --devices, --shards)\n");
         return 1;
     }
     {
@@ -241,6 +256,20 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--stereo: the sequence has no mav0/cam1 image of equal timestamp for every cam0 image\n");
         return 1;
     }
+    if (rectify) {
+        for (int c = 0; c < (stereo ? 2 : 1); c++) {
+            if (!seq.hasCalibration(c)) {
+                std::fprintf(stderr, "--rectify: the sequence has no mav0/cam%d/sensor.yaml with intrinsics\n", c);
+                return 1;
+            }
+            const std::string& model = seq.calibration(c).distortion_model;
+            if (!model.empty() && model != "radial-tangential" && model != "radtan") {
+                std::fprintf(stderr, "--rectify: cam%d's distortion model '%s' is not radial-tangential\n", c, model.c_str());
+                return 1;
+            }
+        }
+    }
+    double stereo_baseline_used = stereo_baseline;
     struct StereoLine { int matched = 0; float median_depth = 0.0f; int scale_valid = 0; double scale = 1.0; };
     std::vector<StereoLine> stereo_lines(stereo ? N : 0);
     std::vector<aria_fuse_state> fused_states;                             // --eval: what --fuse and --optimize leave
@@ -305,9 +334,37 @@ int main(int argc, char** argv) {
             fc.frontend.legacy_order = legacy;
             fc.enable_loop_closure = loop && !posthoc_loop;               // LoopClosureDetector(200, 0.4, 50), euroc_eval.cpp:103
             fc.frontend.estimate_pose = !pose_file.empty();
-            std::unique_ptr<pipeline::FrontEnd> fe = factory::createHip(fc);
-            std::vector<std::uint8_t> gray;
+            std::vector<std::uint8_t> gray, warped;
             int fw = 0, fh = 0;
+            // --rectify: the maps are built before the first frame; every later stage sees the new K
+            std::unique_ptr<adapters::hip::HipRectifier> rectifier;
+            adapters::hip::PoseIntrinsics new_K{};
+            if (rectify) {
+                adapters::hip::RectifierConfig rc;
+                rc.n_cameras = stereo ? 2 : 1;
+                rc.device = fc.hip_device;
+                for (int c = 0; c < rc.n_cameras; c++) {
+                    const io::AslCalibration& cal = seq.calibration(c);
+                    rc.cam[c].K = adapters::hip::PoseIntrinsics{cal.intrinsics[0], cal.intrinsics[1], cal.intrinsics[2], cal.intrinsics[3]};
+                    for (int k = 0; k < 5; k++) rc.cam[c].dist[k] = cal.distortion[k];
+                    for (int k = 0; k < 16; k++) rc.cam[c].T_BS[k] = cal.T_BS[k];
+                }
+                rc.src_width = seq.calibration(0).width;
+                rc.src_height = seq.calibration(0).height;
+                if (rc.src_width <= 0 || rc.src_height <= 0) seq.read(sp.first, gray, rc.src_width, rc.src_height);   // no resolution: key
+                rectifier = std::make_unique<adapters::hip::HipRectifier>(rc);
+                new_K = rectifier->newK();
+                fc.frontend.pose_intrinsics = new_K;
+                if (stereo && stereo_baseline == 0) stereo_baseline_used = rectifier->baseline();
+            }
+            auto warp = [&](int cam, std::vector<std::uint8_t>& img, int iw, int ih) {
+                if (!rectifier) return;
+                if (iw != rectifier->config().src_width || ih != rectifier->config().src_height)
+                    throw std::runtime_error("--rectify: an image is not of the calibration's resolution");
+                rectifier->remap(cam, img.data(), warped);
+                img.swap(warped);
+            };
+            std::unique_ptr<pipeline::FrontEnd> fe = factory::createHip(fc);
             auto t_last = std::chrono::steady_clock::now();
             std::array<double, 16> current_pose = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
             std::unique_ptr<adapters::hip::HipMapper> mapper;           // --map
@@ -316,6 +373,7 @@ int main(int argc, char** argv) {
             if (!map_file.empty()) {
                 adapters::hip::MapperConfig mc;
                 mc.device = fc.hip_device;
+                if (rectifier) mc.K = new_K;
                 mapper = std::make_unique<adapters::hip::HipMapper>(mc);
             }
             // --stereo: the right image has an extractor of its own; the observations of the previous frame stay for the scale
@@ -326,19 +384,22 @@ int main(int argc, char** argv) {
             core::Frame right_frame;
             if (stereo) {
                 adapters::hip::StereoConfig sc;
-                sc.baseline = stereo_baseline;
+                sc.baseline = stereo_baseline_used;
+                if (rectifier) sc.K = new_K;
                 sc.device = fc.hip_device;
                 right_extractor = std::make_unique<adapters::hip::OrbHipExtractor>(max_features, nullptr, fc.hip_device);
                 stereo_matcher = std::make_unique<adapters::hip::HipStereoMatcher>(sc);
             }
             for (std::size_t i = sp.first; i < sp.hi; i++) {
                 seq.read(i, gray, fw, fh);
+                warp(0, gray, fw, fh);
                 const pipeline::FrontEndResult& r = fe->processFrame(gray.data(), fw, fh, seq.at(i).timestamp);
                 if (i < sp.lo) continue;                                   // the halo frame only provides the previous descriptors
                 if (stereo) {
                     int rw = 0, rh = 0;
                     seq.readRight(i, right_gray, rw, rh);
                     if (rw != fw || rh != fh) throw std::runtime_error("--stereo: cam1 image size differs from cam0's at " + seq.at(i).path);
+                    warp(1, right_gray, rw, rh);
                     right_extractor->extract(right_gray.data(), rw, rh, right_frame);
                     std::swap(stereo_prev, stereo_cur);
                     stereo_cur = stereo_matcher->match(gray.data(), right_gray.data(), fw, fh, *r.frame, right_frame);
@@ -595,7 +656,7 @@ int main(int argc, char** argv) {
             matched += l.matched;
             scaled += l.scale_valid;
         }
-        std::printf("stereo baseline %.6g m | mean matched %.2f per frame", stereo_baseline, N ? (double)matched / N : 0.0);
+        std::printf("stereo baseline %.6g m | mean matched %.2f per frame", stereo_baseline_used, N ? (double)matched / N : 0.0);
         if (!pose_file.empty()) std::printf(" | %lld relative poses scaled", scaled);
         std::printf("%s%s\n", stereo_file.empty() ? "" : " -> ", stereo_file.c_str());
     }

@@ -1,6 +1,7 @@
 """Sparse stereo on the device (include/aria_orb_hip.h, "sparse stereo"): a depth per left keypoint of a RECTIFIED stereo
 pair and the metric scale of a relative pose. The reference has no stereo code; aria_slam_amd.stereo_ref is the definition
-and the device equals it bit for bit. Rectification / undistortion is not part of the stage.
+and the device equals it bit for bit. Rectification / undistortion is not part of the stage: see aria_rect_*
+(aria_slam_amd.rectify.HipRectifier), whose output images and new K this stage takes.
 
 As with HipPoseEstimator, the handle's own stream is non-blocking: device buffers filled on torch's default stream must be
 synchronised before a *_batch_device call, or the matcher must be created on the caller's stream."""

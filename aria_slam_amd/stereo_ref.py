@@ -3,7 +3,8 @@ csrc/stereo_match.hip). The reference project has no stereo code, so this file I
 bit for bit -- every fp32 step below is taken in np.float32 in the header's order, every fp64 step of the scale in the
 header's order, and the integer steps are exact.
 
-Inputs are rectified (row-aligned) image pairs; rectification / undistortion is not part of the stage.
+Inputs are rectified (row-aligned) image pairs; rectification / undistortion is not part of the stage: see aria_rect_*
+(rectify_ref.py).
 
 Also the synthetic rectified scene of the tests: a left image of random rectangles and a right view shifted by a known
 disparity per row."""

@@ -1048,7 +1048,7 @@ int64_t aria_det_algorithmic_bytes(int width, int height, int channels, int inpu
  * restatement aria_slam_amd/stereo_ref.py is the definition and the device equals it bit for bit. Additive to ABI 4.
  *
  * Precondition. Both images are rectified: a scene point lies on the same row of both. Rectification and undistortion are
- *   not part of the stage. Float parameters of the config are used as fp32; scale[o] is the fp32 level scale of
+ *   not part of the stage: see aria_rect_* ("rectification" below), whose output this stage reads. Float parameters of the config are used as fp32; scale[o] is the fp32 level scale of
  *   aria_orb_level_info, with the octave clamped to 0..7.
  * 1. Candidates. For a left keypoint (xL, yL, oL), a right keypoint j = (xR, yR, oR) is a candidate when, in fp32 as
  *   written, |oR - oL| <= max_octave_diff, |yR - yL| <= band_factor * scale[oR] and
@@ -1140,6 +1140,92 @@ int   aria_stereo_scale_batch_device(aria_stereo_t h, const aria_pose_result* d_
 int   aria_stereo_scale_pose(aria_stereo_t h, const aria_pose_result* pose, const uint8_t* mask, const aria_match* matches,
                              int n_matches, int query_is_first, const aria_stereo_obs* obs_query, int nq,
                              const aria_stereo_obs* obs_train, int nt, aria_stereo_scale* out);
+
+/* ---- rectification: undistortion and stereo rectification of image batches in HBM, and of keypoints. The reference parses
+ * the radtan coefficients of cam0/sensor.yaml and never uses them, and has no stereo rectification, so the NumPy restatement
+ * aria_slam_amd/rectify_ref.py is the definition and the device equals it bit for bit. Parity with OpenCV's stereoRectify,
+ * initUndistortRectifyMap and remap is not pinned and not claimed. Distortion model: radtan only, dist = k1, k2, p1, p2, k3
+ * (k3 optional, 0). The fisheye model (KB4) needs atan, which cannot be held bitwise between device and host: out of scope.
+ * Additive to ABI 4.
+ *
+ * Steps 1, 2 and 4 are fp64 without contraction, use only + - * / and sqrt, and sum left to right. Step 3 is integer.
+ * 1. Stereo geometry (host only, aria_rect_stereo_geometry). Inputs: K_l, K_r = (fx, fy, cx, cy) and the row-major 4x4 T_BS
+ *   (sensor to body, as in sensor.yaml) of both cameras. T = inverse_rigid(T_BS_r) T_BS_l, so x_r = R x_l + t; R is T's
+ *   rotation block after one Gram-Schmidt pass over its rows (row 0 normalised, row 1 less its part along row 0 and
+ *   normalised, row 2 their cross product), because sensor.yaml's 12 digits are orthonormal to 1e-12 only. The right
+ *   camera centre in the left frame is c = -R^T t; baseline = |c|. With z = (0, 0, 1): e_x = c / |c|,
+ *   e_y = (z + R^T z) x e_x normalised, e_z = e_x x e_y (Fusiello's construction: no trigonometry). R1 has the rows e_x, e_y,
+ *   e_z; R2 = R1 R^T. The right camera lands at +x: disparities are positive. New intrinsics left zero by the caller become
+ *   fx' = fy' = (fy_l + fy_r) / 2 and cx', cy' = the means of the two principal points.
+ * 2. Map. For camera c = (fx, fy, cx, cy, dist, R_c) and the destination pixel (u, v): x = (u - cx') / fx',
+ *   y = (v - cy') / fy'; (X, Y, Z) = R_c^T (x, y, 1); xn = X / Z, yn = Y / Z, r2 = xn xn + yn yn;
+ *   rad = ((k3 r2 + k2) r2 + k1) r2 + 1; xd = xn rad + (2 p1 xn yn + p2 (r2 + 2 xn xn));
+ *   yd = yn rad + (p1 (r2 + 2 yn yn) + 2 p2 xn yn); su = fx xd + cx, sv = fy yd + cy; qx = floor(su 32 + 0.5),
+ *   qy = floor(sv 32 + 0.5); ix = qx >> 5, iy = qy >> 5. The pixel is invalid when Z <= 0, su or sv is not finite, ix < 0,
+ *   iy < 0, ix + 1 > Wsrc - 1 or iy + 1 > Hsrc - 1. A valid entry is the uint32 qx | qy << 16, an invalid one 0xFFFFFFFF.
+ *   Sizes: source 2..2047, destination 1..2047 per dimension. Plain undistortion is R_c = I.
+ * 3. Pixel. fx5 = qx & 31, fy5 = qy & 31; a, b, c, d = the source bytes at (ix, iy), (ix + 1, iy), (ix, iy + 1),
+ *   (ix + 1, iy + 1); out = (a (32 - fx5)(32 - fy5) + b fx5 (32 - fy5) + c (32 - fx5) fy5 + d fx5 fy5 + 512) >> 10. An invalid
+ *   pixel takes `fill`.
+ * 4. Points. A keypoint's fp32 (x, y) widened to fp64: xd = (x - cx) / fx, yd = (y - cy) / fy; from (xd, yd) exactly 20
+ *   iterations of x <- (xd - dx) / rad, y <- (yd - dy) / rad with rad, dx, dy the expressions of step 2 at the current
+ *   (x, y); (X, Y, Z) = R_c (x, y, 1); u' = fx' X / Z + cx', v' = fy' Y / Z + cy', both stored as fp32; every other field of
+ *   the record is copied. Z <= 0 or a stored value that is not finite: (-1, -1). No NaN or Inf is ever written.
+ * Determinism. No float atomics; bitwise reproducible and independent of the batch split. */
+typedef struct aria_rect_s* aria_rect_t;
+typedef struct {
+    double fx, fy, cx, cy;      /* intrinsics of the raw camera                                                    */
+    double dist[5];             /* radtan k1, k2, p1, p2, k3                                                       */
+    double R[9];                /* rectifying rotation, row-major: x_rect = R x_cam; identity = plain undistortion */
+} aria_rect_camera;             /* 144 bytes                                                                       */
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_rect_config)                                                      */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    int      src_width, src_height;   /* raw images, 2..2047                                                       */
+    int      dst_width, dst_height;   /* undistorted / rectified images, 1..2047                                   */
+    int      n_cameras;         /* 1 or 2                                                                          */
+    aria_rect_camera cam[2];
+    double   new_fx, new_fy, new_cx, new_cy;   /* intrinsics of the destination images, shared by the cameras      */
+    int      fill;              /* byte of an invalid pixel, 0..255 (default 0)                                    */
+    int      reserved;
+} aria_rect_config;             /* 368 bytes                                                                       */
+
+/* EuRoC cam0 at 752x480, plain undistortion (R = I), new K = K, one camera. */
+void  aria_rect_default_config(aria_rect_config* cfg);
+/* Builds the maps of the cameras on the device. ARIA_E_INVALID for sizes out of range, non-positive or non-finite focal
+ * lengths, n_cameras outside 1..2, fill outside 0..255. */
+int   aria_rect_create(const aria_rect_config* cfg, aria_rect_t* out);
+void  aria_rect_destroy(aria_rect_t h);
+void* aria_rect_stream(aria_rect_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check, once:
+ * ARIA_E_INVALID when some frame's keypoint count was outside [0, kp_stride] (that frame is skipped, the others are
+ * unaffected). */
+int   aria_rect_check(aria_rect_t h);
+/* Step 1; host only, no handle. K_*: 4 doubles, T_BS_*: 16 doubles row-major. Fills cfg->cam[0].R, cfg->cam[1].R and each
+ * of cfg->new_fx, new_fy, new_cx, new_cy that is zero; *baseline (may be NULL) = |c| in the unit of T_BS. */
+int   aria_rect_stereo_geometry(const double* K_l, const double* K_r, const double* T_BS_l, const double* T_BS_r,
+                                aria_rect_config* cfg, double* baseline);
+/* Steps 2-3 over a batch in HBM: frame f of camera `cam` is read at d_src + f*src_stride (`src_pitch` <= 524288 bytes per row) and
+ * written at d_dst + f*dst_stride (`dst_pitch` bytes per row, any alignment); bytes outside the dst_width x dst_height
+ * pixels are never written. The output is the input layout of aria_orb_extract_batch_device and
+ * aria_stereo_match_batch_device. Enqueued on the handle's stream, no synchronisation. */
+int   aria_rect_remap_batch_device(aria_rect_t h, int cam, const uint8_t* d_src, int64_t src_stride, int src_pitch, int n_frames,
+                                   uint8_t* d_dst, int64_t dst_stride, int dst_pitch);
+/* One image from host buffers; blocks. */
+int   aria_rect_remap(aria_rect_t h, int cam, const uint8_t* src, int src_pitch, uint8_t* dst, int dst_pitch);
+/* Step 4 over what aria_orb_extract_batch_device left for raw images: frame f moves its d_n[f] keypoints at
+ * d_kp_in + f*kp_stride to d_kp_out + f*kp_stride (in place allowed; records at and beyond the count are not touched).
+ * Enqueued on the handle's stream, no synchronisation. */
+int   aria_rect_points_batch_device(aria_rect_t h, int cam, const aria_keypoint* d_kp_in, const int* d_n, int64_t kp_stride,
+                                    int n_frames, aria_keypoint* d_kp_out);
+/* One frame's keypoints from host buffers; blocks. */
+int   aria_rect_points(aria_rect_t h, int cam, const aria_keypoint* kp_in, int n, aria_keypoint* kp_out);
+/* Host read-back of a camera's map, dst_width * dst_height entries row by row. Returns the entries written or a negative
+ * status (ARIA_E_OUTPUT_TOO_SMALL when cap is less). */
+int   aria_rect_get_map(aria_rect_t h, int cam, uint32_t* out, int cap);
+/* Algorithmic bytes of one remapped image: one byte read and one written per destination pixel, 2 * W * H. */
+int64_t aria_rect_algorithmic_bytes(int dst_w, int dst_h);
 
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
