@@ -74,6 +74,10 @@ EXPORTS = [
     "aria_rect_default_config", "aria_rect_create", "aria_rect_destroy", "aria_rect_stream", "aria_rect_check",
     "aria_rect_stereo_geometry", "aria_rect_remap_batch_device", "aria_rect_remap", "aria_rect_points_batch_device",
     "aria_rect_points", "aria_rect_get_map", "aria_rect_algorithmic_bytes",
+    # dense stereo on rectified pairs (census + SGM disparity and depth maps, keypoint sampling), additive to ABI 4
+    "aria_dense_default_config", "aria_dense_create", "aria_dense_destroy", "aria_dense_stream", "aria_dense_check",
+    "aria_dense_compute_batch_device", "aria_dense_compute", "aria_dense_sample_batch_device", "aria_dense_sample",
+    "aria_dense_pairs_in_flight", "aria_dense_scratch_bytes_per_pair", "aria_dense_algorithmic_bytes",
 ]
 
 
@@ -257,6 +261,18 @@ class RectConfig(C.Structure):
                 ("new_cy", C.c_double), ("fill", C.c_int), ("reserved", C.c_int)]
 
 
+class DenseConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("baseline", C.c_double), ("num_disparities", C.c_int), ("P1", C.c_int),
+                ("P2", C.c_int), ("uniqueness", C.c_int), ("lr_max_diff", C.c_int), ("max_width", C.c_int),
+                ("max_height", C.c_int), ("reserved", C.c_int), ("scratch_bytes", C.c_int64)]
+
+
+# right_idx of a record sampled from a dense map (ARIA_DENSE_NO_KEYPOINT) and the disparity of an invalid pixel in 1/16 px
+DENSE_NO_KEYPOINT = 0x7FFFFFFF
+DENSE_INVALID = -16
+
+
 # an entry of the rectification map: qx | qy << 16 in 1/32 px, RECT_INVALID = no source
 RECT_MAP_DTYPE = np.dtype("<u4")
 RECT_INVALID = 0xFFFFFFFF
@@ -411,6 +427,8 @@ def load_library():
         _bind_stereo(L)
     if hasattr(L, "aria_rect_create"):
         _bind_rect(L)
+    if hasattr(L, "aria_dense_create"):
+        _bind_dense(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -529,6 +547,20 @@ def _bind_rect(L):
     L.aria_rect_get_map.argtypes = [p, i, p, i]
     L.aria_rect_algorithmic_bytes.restype = i64
     L.aria_rect_algorithmic_bytes.argtypes = [i, i]
+
+
+def _bind_dense(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "dense")
+    L.aria_dense_compute_batch_device.argtypes = [p, p, p, i64, i, i, i, i, p, i64, i, p, i64, i]
+    L.aria_dense_compute.argtypes = [p, p, p, i, i, i, p, p]
+    L.aria_dense_sample_batch_device.argtypes = [p, p, i64, i, i, i, p, p, i64, i, p]
+    L.aria_dense_sample.argtypes = [p, p, i, i, i, p, i, p]
+    L.aria_dense_pairs_in_flight.argtypes = [p]
+    L.aria_dense_scratch_bytes_per_pair.restype = i64
+    L.aria_dense_scratch_bytes_per_pair.argtypes = [i, i]
+    L.aria_dense_algorithmic_bytes.restype = i64
+    L.aria_dense_algorithmic_bytes.argtypes = [i, i]
 
 
 def status_string(status):

@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -87,6 +87,11 @@
 // T_BS, and the stereo, pose and map stages take the rectified K; a BASELINE_M of 0 then means the calibration's baseline. A
 // missing sensor.yaml is an error message and exit status 1. Without the flag every output is byte-identical.
 //
+// --dense FILE (needs --stereo BASELINE_M, which brings cam1 and the baseline; composes with --rectify): dense stereo on the
+// device (include/aria_orb_hip.h, "dense stereo"; aria_hip/HipDenseStereo.hpp) on the pair the sparse stage sees. FILE gets
+// one line per frame, "timestamp valid_share median_depth": the share of the pixels with a positive disparity and the depth
+// at index n / 2 of their ascending depths. Without the flag nothing of this runs and every output is byte-identical.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -115,6 +120,7 @@
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
+#include "aria_hip/HipDenseStereo.hpp"
 #include "aria_hip/HipRectifier.hpp"
 #include "aria_hip/HipSensorFusion.hpp"
 #include "aria_hip/HipStereoMatcher.hpp"
@@ -151,7 +157,8 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file]\n"
+                             "  --dense file: dense stereo (census + SGM, 64 disparities) on the --stereo pairs: valid share and median depth, one line per frame\n"
                              "  --rectify: undistort cam0 (with --stereo: rectify cam0 and cam1) on the device from mav0/cam*/sensor.yaml; --stereo 0 then takes\n"
                              "             the calibration's baseline\n"
                              "  --stereo baseline_m: sparse stereo over mav0/cam1 (rectified pairs): a depth per keypoint, one line per frame; with --pose the\n"
@@ -168,7 +175,7 @@ int main(int argc, char** argv) {
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
-    std::string stereo_file;
+    std::string stereo_file, dense_file;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -188,6 +195,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--stereo") && i + 1 < argc) { stereo = true; stereo_baseline = std::atof(argv[++i]); }
         else if (!std::strcmp(argv[i], "--stereo-out") && i + 1 < argc) stereo_file = argv[++i];
         else if (!std::strcmp(argv[i], "--rectify")) rectify = true;
+        else if (!std::strcmp(argv[i], "--dense") && i + 1 < argc) dense_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -224,6 +232,10 @@ int main(int argc, char** argv) {
     if ((stereo || !stereo_file.empty()) && (!stereo || !(stereo_baseline > 0 || (rectify && stereo_baseline == 0)) || batch > 0 || devices > 1 || shards > 1)) {
         std::fprintf(stderr, "--stereo needs a baseline in metres > 0 (or 0 with --rectify: the calibration's) and runs on the frame-at-a-time path only (no --batch, --devices, --shards); "
                              "--stereo-out needs --stereo\n");
+        return 1;
+    }
+    if (!dense_file.empty() && !stereo) {
+        std::fprintf(stderr, "--dense needs --stereo baseline_m (cam1 and the baseline)\n");
         return 1;
     }
     if (rectify && (batch > 0 || devices > 1 || shards > 1)) {
@@ -272,6 +284,8 @@ int main(int argc, char** argv) {
     double stereo_baseline_used = stereo_baseline;
     struct StereoLine { int matched = 0; float median_depth = 0.0f; int scale_valid = 0; double scale = 1.0; };
     std::vector<StereoLine> stereo_lines(stereo ? N : 0);
+    struct DenseLine { double valid_share = 0.0; float median_depth = 0.0f; };
+    std::vector<DenseLine> dense_lines(dense_file.empty() ? 0 : N);
     std::vector<aria_fuse_state> fused_states;                             // --eval: what --fuse and --optimize leave
     std::vector<double> optimized_xyz;
     if ((std::size_t)shards > N && N > 0) shards = (int)N;
@@ -382,6 +396,7 @@ int main(int argc, char** argv) {
             adapters::hip::StereoObservations stereo_cur, stereo_prev;
             std::vector<std::uint8_t> right_gray;
             core::Frame right_frame;
+            std::unique_ptr<adapters::hip::HipDenseStereo> dense_stereo;   // --dense: made at the first pair, for its size
             if (stereo) {
                 adapters::hip::StereoConfig sc;
                 sc.baseline = stereo_baseline_used;
@@ -405,6 +420,20 @@ int main(int argc, char** argv) {
                     stereo_cur = stereo_matcher->match(gray.data(), right_gray.data(), fw, fh, *r.frame, right_frame);
                     stereo_lines[i].matched = (int)stereo_cur.matches.size();
                     stereo_lines[i].median_depth = stereo_cur.medianDepth();
+                    if (!dense_file.empty()) {
+                        if (!dense_stereo) {
+                            adapters::hip::DenseStereoConfig dc;
+                            dc.baseline = stereo_baseline_used;
+                            if (rectifier) dc.K = new_K;
+                            dc.device = fc.hip_device;
+                            dc.max_width = fw;
+                            dc.max_height = fh;
+                            dense_stereo = std::make_unique<adapters::hip::HipDenseStereo>(dc);
+                        }
+                        const adapters::hip::DenseDepth dm = dense_stereo->compute(gray.data(), right_gray.data(), fw, fh);
+                        dense_lines[i].valid_share = dm.validShare();
+                        dense_lines[i].median_depth = dm.medianDepth();
+                    }
                 }
                 if (!traj.empty()) {
                     if (r.pose && r.pose->n_pose_inliers > 10) {           // euroc_eval.cpp:191
@@ -659,6 +688,18 @@ int main(int argc, char** argv) {
         std::printf("stereo baseline %.6g m | mean matched %.2f per frame", stereo_baseline_used, N ? (double)matched / N : 0.0);
         if (!pose_file.empty()) std::printf(" | %lld relative poses scaled", scaled);
         std::printf("%s%s\n", stereo_file.empty() ? "" : " -> ", stereo_file.c_str());
+    }
+    if (!dense_file.empty()) {
+        std::ofstream df(dense_file);
+        double share = 0.0;
+        for (std::size_t i = 0; i < N; i++) {
+            char line[160];
+            std::snprintf(line, sizeof(line), "%.9f %.9f %.9f", seq.at(i).timestamp, dense_lines[i].valid_share,
+                          (double)dense_lines[i].median_depth);
+            df << line << '\n';
+            share += dense_lines[i].valid_share;
+        }
+        std::printf("dense 64 disparities | mean valid share %.4f -> %s\n", N ? share / N : 0.0, dense_file.c_str());
     }
     if (!eval_file.empty()) {                                              // euroc_eval.cpp:247-252, 294-305
         try {

@@ -1227,6 +1227,90 @@ int   aria_rect_get_map(aria_rect_t h, int cam, uint32_t* out, int cap);
 /* Algorithmic bytes of one remapped image: one byte read and one written per destination pixel, 2 * W * H. */
 int64_t aria_rect_algorithmic_bytes(int dst_w, int dst_h);
 
+/* ---- dense stereo: a disparity for every pixel of a RECTIFIED pair (census + four-path semi-global matching over 64
+ * disparities), a depth map, and the stereo observation at each keypoint. The reference has no code for it (the rest of its
+ * roadmap item H19), so the NumPy restatement aria_slam_amd/dense_ref.py is the definition and the device equals it bit for
+ * bit. Additive to ABI 4.
+ *
+ * Inputs are two rectified 8-bit images of W x H (aria_rect_*); row y of the left corresponds to row y of the right. D = 64,
+ * d in 0..63. Steps 1-7 are integer arithmetic.
+ * 1. Census. Window 9 wide, 7 high, the 62 neighbours without the centre, coordinates clamped to the image; a bit is
+ *   neighbour < centre. The bit order inside the 64-bit word is not observable.
+ * 2. Cost. C(y, x, d) = popcount(cenL(y, x) ^ cenR(y, x - d)) when x - d >= 0, else the constant 64.
+ * 3. Aggregation over the four paths left-to-right, right-to-left, top-to-bottom, bottom-to-top with fixed P1, P2. At the
+ *   first pixel of a path L_r = C; after it L_r(p, d) = C(p, d) + min(L_r(q, d), L_r(q, d-1) + P1, L_r(q, d+1) + P1, m + P2) - m
+ *   with q the previous pixel and m = min_k L_r(q, k); d-1 / d+1 outside 0..63 do not take part. S = the sum over the paths.
+ *   1 <= P1 <= P2 <= 127, so L_r <= 64 + P2 fits a byte and S fits 16 bits.
+ * 4. Winner. best = argmin_d S(y, x, d), ties to the lowest d.
+ * 5. Uniqueness. Invalid when some d with |d - best| > 1 has S(d) * (100 - uniqueness) < S(best) * 100.
+ * 6. Left-right check (skipped as a whole when lr_max_diff < 0). dR(y, xr) = argmin over d with xr + d <= W - 1 of
+ *   S(y, xr + d, d), ties to the lowest d. Invalid when x - best < 0 or |dR(y, x - best) - best| > lr_max_diff.
+ * 7. Sub-pixel in 1/16 px. For 0 < best < 63: den2 = max(S(best-1) + S(best+1) - 2 S(best), 1),
+ *   d16 = 16 best + ((S(best-1) - S(best+1)) * 16 + den2) / (2 den2), the division truncating towards zero; d16 = 16 best at
+ *   best = 0 and best = 63; an invalid pixel holds -16. One int16 per pixel.
+ * 8. Depth, fp32, one rounding per operation: depth = fb / ((float)d16 * 0.0625f) with fb = (float)fx * (float)baseline formed
+ *   once; 0 where d16 <= 0. No NaN or Inf is ever written.
+ * 9. Keypoint sampling into aria_stereo_obs. u = rint(x), v = rint(y), round-half-even. Unmatched (the sparse stage's
+ *   unmatched record, byte for byte) when (u, v) is outside the image or d16(v, u) <= 0; otherwise
+ *   disparity = (float)d16 * 0.0625f and u_right, depth, X, Y by the fp32 chain of step 3 of the sparse stage,
+ *   right_idx = ARIA_DENSE_NO_KEYPOINT, hamming = 0, sad = 0. Records at and beyond the frame's count are written unmatched.
+ * Scratch. Per pair in flight and pixel: two census words (16 B), 64 partial sums of S as uint16 (128 B) and the packed
+ *   minimum of step 6 (4 B): 148 * max_width * max_height bytes. pairs in flight = scratch_bytes / that (at most 4096); a batch
+ *   of any size runs in groups of that many on the handle's stream.
+ * Determinism. The minimum of step 6 is an integer atomic-min on (S << 8 | d): order-independent. No float atomics; bitwise
+ *   reproducible and independent of the batch split. */
+#define ARIA_DENSE_NO_KEYPOINT 0x7FFFFFFF
+typedef struct aria_dense_s* aria_dense_t;
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_dense_config)                                                    */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    double   fx, fy, cx, cy;    /* intrinsics of the rectified left camera (default EuRoC cam0)                   */
+    double   baseline;          /* metres (default 0.110)                                                         */
+    int      num_disparities;   /* 64; anything else is ARIA_E_INVALID                                            */
+    int      P1, P2;            /* default 8, 32; 1 <= P1 <= P2 <= 127                                            */
+    int      uniqueness;        /* default 10, 0..99                                                              */
+    int      lr_max_diff;       /* default 1, <= 63; negative = no left-right check                               */
+    int      max_width, max_height;   /* default 752 x 480, 1..4096: the largest pair a call may bring            */
+    int      reserved;
+    int64_t  scratch_bytes;     /* HBM budget for census and S, default 1 GiB                                     */
+} aria_dense_config;            /* 96 bytes                                                                       */
+
+void  aria_dense_default_config(aria_dense_config* cfg);
+/* ARIA_E_INVALID for a bad field, and for a scratch_bytes that does not hold one pair of max_width x max_height. */
+int   aria_dense_create(const aria_dense_config* cfg, aria_dense_t* out);
+void  aria_dense_destroy(aria_dense_t h);
+void* aria_dense_stream(aria_dense_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check, once:
+ * ARIA_E_INVALID when some frame's keypoint count of a sampling call was outside [0, kp_stride] (that frame is skipped:
+ * every record unmatched; the others are unaffected). */
+int   aria_dense_check(aria_dense_t h);
+/* Steps 1-8 over a batch in HBM. Pair p reads its images at d_left / d_right + p*img_stride (`pitch` bytes per row) and
+ * writes W x H int16 at d_disp + p*disp_stride and, unless d_depth is NULL, W x H floats at d_depth + p*depth_stride;
+ * strides and pitches of the outputs are in elements, and elements outside the W x H pixels are never written.
+ * W <= max_width, H <= max_height; W < 64 is legal. Enqueued on the handle's stream, no synchronisation. */
+int   aria_dense_compute_batch_device(aria_dense_t h, const uint8_t* d_left, const uint8_t* d_right, int64_t img_stride, int width,
+                                      int height, int pitch, int n_pairs, int16_t* d_disp, int64_t disp_stride, int disp_pitch,
+                                      float* d_depth, int64_t depth_stride, int depth_pitch);
+/* One pair from host buffers; blocks. disp: width * height int16, depth (may be NULL): width * height floats, both dense. */
+int   aria_dense_compute(aria_dense_t h, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
+                         int16_t* disp, float* depth);
+/* Step 9 over a batch in HBM: frame f samples the map at d_disp + f*disp_stride at its d_n[f] keypoints at
+ * d_kp + f*kp_stride and writes kp_stride records at d_obs + f*kp_stride. kp_stride <= 2^20, n_frames <= 65535. Enqueued on
+ * the handle's stream, no synchronisation. */
+int   aria_dense_sample_batch_device(aria_dense_t h, const int16_t* d_disp, int64_t disp_stride, int disp_pitch, int width,
+                                     int height, const aria_keypoint* d_kp, const int* d_n, int64_t kp_stride, int n_frames,
+                                     aria_stereo_obs* d_obs);
+/* One frame from host buffers; blocks. disp_pitch in elements; obs: n records. */
+int   aria_dense_sample(aria_dense_t h, const int16_t* disp, int width, int height, int disp_pitch, const aria_keypoint* kp, int n,
+                        aria_stereo_obs* obs);
+/* Pairs the handle keeps in flight (see "Scratch"), or a negative status. */
+int   aria_dense_pairs_in_flight(aria_dense_t h);
+/* Scratch bytes one pair in flight needs at this size: 148 * width * height. Host only, no handle. */
+int64_t aria_dense_scratch_bytes_per_pair(int width, int height);
+/* Algorithmic bytes of one pair: both images read, the int16 disparity and the fp32 depth written, 8 * W * H. */
+int64_t aria_dense_algorithmic_bytes(int width, int height);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
