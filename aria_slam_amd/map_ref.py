@@ -11,6 +11,7 @@ from ._lib import KP_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE
 EUROC_K = (458.654, 457.296, 367.215, 248.375)
 SVD_EPS = 10.0 * np.finfo(np.float64).eps
 SVD_SWEEPS = 30
+SVD_SWEEPS_EXT = 60                                      # sweep cap of an extended-precision run (the tests' yardstick)
 W_EPS = 1e-10
 MIN_MATCHES = 8
 DEFAULTS = dict(min_depth=0.1, max_depth=50.0, min_parallax=1.0, max_reproj=2.0)
@@ -20,26 +21,29 @@ KEPT, AT_INFINITY, DEPTH, PARALLAX, REPROJ = 0, 1, 2, 3, 4
 PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
 
 
-def as_extrinsics(T):
+def as_extrinsics(T, dtype=np.float64):
     """[R | t] (3x4) from a 3x4 / 4x4 matrix or 12 row-major doubles."""
-    T = np.asarray(T, np.float64)
+    T = np.asarray(T, dtype)
     return T.reshape(-1)[:12].reshape(3, 4) if T.size in (12, 16) else T[:3, :4]
 
 
-def projection(K, E):
+def projection(K, E, dtype=np.float64):
     fx, fy, cx, cy = K
-    E = as_extrinsics(E)
+    E = as_extrinsics(E, dtype)
     return np.stack([fx * E[0] + cx * E[2], fy * E[1] + cy * E[2], E[2].copy()])
 
 
-def dlt_null_vectors(A):
+def dlt_null_vectors(A, dtype=np.float64):
     """A: (N, 4, 4) rows. One-sided Jacobi SVD per the header; returns (N, 4): the right singular vector of the smallest
-    singular value."""
+    singular value. dtype: np.float64 is the stage's arithmetic (10 DBL_EPSILON, 30 sweeps); any other type runs the same
+    steps with 10 of its own epsilon and a cap of 60 sweeps, so that the run is converged."""
+    A = np.asarray(A, dtype)
     N = A.shape[0]
+    eps, sweeps = (SVD_EPS, SVD_SWEEPS) if dtype == np.float64 else (10.0 * np.finfo(dtype).eps, SVD_SWEEPS_EXT)
     a = np.transpose(A, (0, 2, 1)).copy()                # a[:, c, :] = column c of A
-    v = np.broadcast_to(np.eye(4), (N, 4, 4)).copy()     # v[:, c, :] = column c of V
+    v = np.broadcast_to(np.eye(4, dtype=dtype), (N, 4, 4)).copy()     # v[:, c, :] = column c of V
     active = np.ones(N, bool)
-    for _ in range(SVD_SWEEPS):
+    for _ in range(sweeps):
         if not active.any():
             break
         rot_any = np.zeros(N, bool)
@@ -48,7 +52,7 @@ def dlt_null_vectors(A):
             alpha = ai[:, 0] * ai[:, 0] + ai[:, 1] * ai[:, 1] + ai[:, 2] * ai[:, 2] + ai[:, 3] * ai[:, 3]
             beta = aj[:, 0] * aj[:, 0] + aj[:, 1] * aj[:, 1] + aj[:, 2] * aj[:, 2] + aj[:, 3] * aj[:, 3]
             gamma = ai[:, 0] * aj[:, 0] + ai[:, 1] * aj[:, 1] + ai[:, 2] * aj[:, 2] + ai[:, 3] * aj[:, 3]
-            rot = active & (np.abs(gamma) > SVD_EPS * np.sqrt(alpha * beta))
+            rot = active & (np.abs(gamma) > eps * np.sqrt(alpha * beta))
             if not rot.any():
                 continue
             rot_any |= rot
@@ -72,20 +76,22 @@ def dlt_null_vectors(A):
     return v[np.arange(N), k, :]
 
 
-def triangulate_points(x1, x2, E1, E2, K=EUROC_K, min_depth=0.1, max_depth=50.0, min_parallax=1.0, max_reproj=2.0):
+def triangulate_points(x1, x2, E1, E2, K=EUROC_K, min_depth=0.1, max_depth=50.0, min_parallax=1.0, max_reproj=2.0,
+                       dtype=np.float64):
     """x1, x2: (N, 2) pixels (fp32 values); E1, E2: world-to-camera [R | t]. Returns (reason (N,) int, X (N, 3), err (N, 2)):
-    reason KEPT or the first test that rejected the point."""
-    x1 = np.asarray(x1, np.float32).astype(np.float64).reshape(-1, 2)
-    x2 = np.asarray(x2, np.float32).astype(np.float64).reshape(-1, 2)
-    E1, E2 = as_extrinsics(E1), as_extrinsics(E2)
-    P1, P2 = projection(K, E1), projection(K, E2)
+    reason KEPT or the first test that rejected the point. dtype: the arithmetic (see dlt_null_vectors); the inputs are
+    the same fp32 pixels and fp64 extrinsics, intrinsics and thresholds in either."""
+    x1 = np.asarray(x1, np.float32).astype(dtype).reshape(-1, 2)
+    x2 = np.asarray(x2, np.float32).astype(dtype).reshape(-1, 2)
+    E1, E2 = as_extrinsics(E1, dtype), as_extrinsics(E2, dtype)
+    P1, P2 = projection(K, E1, dtype), projection(K, E2, dtype)
     N = len(x1)
-    A = np.empty((N, 4, 4))
+    A = np.empty((N, 4, 4), dtype)
     A[:, 0] = x1[:, :1] * P1[2] - P1[0]
     A[:, 1] = x1[:, 1:] * P1[2] - P1[1]
     A[:, 2] = x2[:, :1] * P2[2] - P2[0]
     A[:, 3] = x2[:, 1:] * P2[2] - P2[1]
-    Xh = dlt_null_vectors(A) if N else np.zeros((0, 4))
+    Xh = dlt_null_vectors(A, dtype) if N else np.zeros((0, 4), dtype)
     reason = np.full(N, KEPT)
     inf = ~(np.abs(Xh[:, 3]) >= W_EPS)
     reason[inf] = AT_INFINITY
@@ -103,7 +109,8 @@ def triangulate_points(x1, x2, E1, E2, K=EUROC_K, min_depth=0.1, max_depth=50.0,
         n1 = np.sqrt(r1[:, 0] * r1[:, 0] + r1[:, 1] * r1[:, 1] + r1[:, 2] * r1[:, 2])
         n2 = np.sqrt(r2[:, 0] * r2[:, 0] + r2[:, 1] * r2[:, 1] + r2[:, 2] * r2[:, 2])
         cosp = (r1[:, 0] / n1) * (r2[:, 0] / n2) + (r1[:, 1] / n1) * (r2[:, 1] / n2) + (r1[:, 2] / n1) * (r2[:, 2] / n2)
-        par = np.arccos(np.minimum(1.0, np.abs(cosp))) * 180.0 / np.pi
+        pi = np.pi if dtype == np.float64 else np.arccos(dtype(-1))
+        par = np.arccos(np.minimum(1.0, np.abs(cosp))) * 180.0 / pi
         reason[(reason == KEPT) & ~(par >= min_parallax)] = PARALLAX
         e1x = fx * c1[:, 0] / c1[:, 2] + cx - x1[:, 0]
         e1y = fy * c1[:, 1] / c1[:, 2] + cy - x1[:, 1]
