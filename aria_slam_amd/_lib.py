@@ -78,6 +78,10 @@ EXPORTS = [
     "aria_dense_default_config", "aria_dense_create", "aria_dense_destroy", "aria_dense_stream", "aria_dense_check",
     "aria_dense_compute_batch_device", "aria_dense_compute", "aria_dense_sample_batch_device", "aria_dense_sample",
     "aria_dense_pairs_in_flight", "aria_dense_scratch_bytes_per_pair", "aria_dense_algorithmic_bytes",
+    # dense depth fusion (TSDF volume from depth maps along the trajectory, surface points), additive to ABI 4
+    "aria_tsdf_default_config", "aria_tsdf_create", "aria_tsdf_destroy", "aria_tsdf_stream", "aria_tsdf_check", "aria_tsdf_clear",
+    "aria_tsdf_integrate_batch_device", "aria_tsdf_integrate", "aria_tsdf_extract_points_device", "aria_tsdf_extract_points",
+    "aria_tsdf_device_voxels", "aria_tsdf_read_box", "aria_tsdf_volume_bytes", "aria_tsdf_algorithmic_bytes",
 ]
 
 
@@ -268,6 +272,18 @@ class DenseConfig(C.Structure):
                 ("max_height", C.c_int), ("reserved", C.c_int), ("scratch_bytes", C.c_int64)]
 
 
+class TsdfConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int),
+                ("nz", C.c_int), ("max_weight", C.c_int), ("min_weight", C.c_int), ("reserved", C.c_int), ("voxel", C.c_float),
+                ("trunc", C.c_float), ("origin", C.c_float * 3), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("reserved2", C.c_float), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+# aria_tsdf_voxel (8 bytes) and aria_tsdf_point (16 bytes)
+TSDF_VOXEL_DTYPE = np.dtype([("tsdf", "<f4"), ("weight", "<u2"), ("gray", "u1"), ("reserved", "u1")])
+TSDF_POINT_DTYPE = np.dtype([("X", "<f4", (3,)), ("gray", "u1"), ("axis", "u1"), ("weight", "<u2")])
+
+
 # right_idx of a record sampled from a dense map (ARIA_DENSE_NO_KEYPOINT) and the disparity of an invalid pixel in 1/16 px
 DENSE_NO_KEYPOINT = 0x7FFFFFFF
 DENSE_INVALID = -16
@@ -429,6 +445,8 @@ def load_library():
         _bind_rect(L)
     if hasattr(L, "aria_dense_create"):
         _bind_dense(L)
+    if hasattr(L, "aria_tsdf_create"):
+        _bind_tsdf(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -561,6 +579,23 @@ def _bind_dense(L):
     L.aria_dense_scratch_bytes_per_pair.argtypes = [i, i]
     L.aria_dense_algorithmic_bytes.restype = i64
     L.aria_dense_algorithmic_bytes.argtypes = [i, i]
+
+
+def _bind_tsdf(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "tsdf")
+    L.aria_tsdf_clear.argtypes = [p]
+    L.aria_tsdf_integrate_batch_device.argtypes = [p, p, i64, i, i, i, p, p, p, i64, i, i]
+    L.aria_tsdf_integrate.argtypes = [p, p, i, i, i, p, p, i]
+    L.aria_tsdf_extract_points_device.argtypes = [p, p, i64, p]
+    L.aria_tsdf_extract_points.argtypes = [p, p, i64, C.POINTER(i64)]
+    L.aria_tsdf_device_voxels.restype = p
+    L.aria_tsdf_device_voxels.argtypes = [p]
+    L.aria_tsdf_read_box.argtypes = [p, i, i, i, i, i, i, p]
+    L.aria_tsdf_volume_bytes.restype = i64
+    L.aria_tsdf_volume_bytes.argtypes = [i, i, i]
+    L.aria_tsdf_algorithmic_bytes.restype = i64
+    L.aria_tsdf_algorithmic_bytes.argtypes = [i, i, i, i, i, i]
 
 
 def status_string(status):

@@ -5,6 +5,8 @@
 #include <fstream>
 #include <stdexcept>
 
+#include "aria_hip/ply.hpp"
+
 namespace aria::adapters::hip {
 
 namespace {
@@ -110,20 +112,7 @@ const std::vector<core::MapPoint>& HipMapper::getMapPoints() const {
 void HipMapper::exportPLY(const std::string& filename) const {
     const std::vector<aria_map_point> recs = records();
     std::ofstream file = open_out(filename);
-    file << "ply\n";
-    file << "format ascii 1.0\n";
-    file << "element vertex " << recs.size() << "\n";
-    file << "property float x\n";
-    file << "property float y\n";
-    file << "property float z\n";
-    file << "property uchar red\n";
-    file << "property uchar green\n";
-    file << "property uchar blue\n";
-    file << "end_header\n";
-    for (const aria_map_point& p : recs) {
-        const int g = p.gray;
-        file << p.X[0] << " " << p.X[1] << " " << p.X[2] << " " << g << " " << g << " " << g << "\n";
-    }
+    writePLY(file, recs);
 }
 
 void HipMapper::exportPCD(const std::string& filename) const {

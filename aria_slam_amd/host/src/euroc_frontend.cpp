@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -92,6 +92,14 @@
 // one line per frame, "timestamp valid_share median_depth": the share of the pixels with a positive disparity and the depth
 // at index n / 2 of their ascending depths. Without the flag nothing of this runs and every output is byte-identical.
 //
+// --volume FILE.ply [--voxel M] (needs --pose, --stereo and --dense): dense depth fusion on the device (include/
+// aria_orb_hip.h, "dense depth fusion"; aria_hip/HipTsdfVolume.hpp). Every frame's dense depth map is integrated, with the left
+// image for gray, at the --pose chain's current_pose taken as world-to-camera extrinsics (as --map takes it), whose accepted
+// relative translations carry the --stereo scale. A frame without an accepted pose, or without a valid scale, is left out. The
+// volume has the default 256 x 256 x 128 voxels of M metres (default 0.05) and is centred on the first camera. At the end the
+// surface points are written as PLY (the --map header and vertex format) and "volume <points> <observed voxels>" is printed.
+// Without the flag nothing of this runs and every output is byte-identical.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -125,6 +133,7 @@
 #include "aria_hip/HipSensorFusion.hpp"
 #include "aria_hip/HipStereoMatcher.hpp"
 #include "aria_hip/HipTrajectoryEvaluator.hpp"
+#include "aria_hip/HipTsdfVolume.hpp"
 #include "aria_hip/OrbHipExtractor.hpp"
 #include "aria_hip/Shard.hpp"
 #include "aria_orb_hip.h"
@@ -157,7 +166,9 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m]\n"
+                             "  --volume file.ply: dense depth fusion of the --dense depth maps along the --pose chain (needs --pose, --stereo, --dense): the surface\n"
+                             "                     points of a TSDF volume centred on the first camera; --voxel m is the voxel edge (default 0.05)\n"
                              "  --dense file: dense stereo (census + SGM, 64 disparities) on the --stereo pairs: valid share and median depth, one line per frame\n"
                              "  --rectify: undistort cam0 (with --stereo: rectify cam0 and cam1) on the device from mav0/cam*/sensor.yaml; --stereo 0 then takes\n"
                              "             the calibration's baseline\n"
@@ -175,7 +186,8 @@ int main(int argc, char** argv) {
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
-    std::string stereo_file, dense_file;
+    std::string stereo_file, dense_file, volume_file;
+    double voxel = 0.05;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
         else if (!std::strcmp(argv[i], "--loop")) loop = true;
@@ -196,6 +208,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--stereo-out") && i + 1 < argc) stereo_file = argv[++i];
         else if (!std::strcmp(argv[i], "--rectify")) rectify = true;
         else if (!std::strcmp(argv[i], "--dense") && i + 1 < argc) dense_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--volume") && i + 1 < argc) volume_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--voxel") && i + 1 < argc) voxel = std::atof(argv[++i]);
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -236,6 +250,10 @@ int main(int argc, char** argv) {
     }
     if (!dense_file.empty() && !stereo) {
         std::fprintf(stderr, "--dense needs --stereo baseline_m (cam1 and the baseline)\n");
+        return 1;
+    }
+    if (!volume_file.empty() && (pose_file.empty() || !stereo || dense_file.empty() || !(voxel > 0))) {
+        std::fprintf(stderr, "--volume needs --pose (the trajectory), --stereo baseline_m (its metric scale), --dense file (the depth maps) and --voxel > 0\n");
         return 1;
     }
     if (rectify && (batch > 0 || devices > 1 || shards > 1)) {
@@ -304,6 +322,7 @@ int main(int argc, char** argv) {
     // --fuse: the visual record of every frame (euroc_eval.cpp:209), filled where the pose is accepted
     std::vector<aria_fuse_visual> fuse_visual(fuse_file.empty() ? 0 : N);
     std::size_t map_points = 0;
+    long long volume_points = 0, volume_observed = 0;   // --volume
     // --optimize: the reference's PoseGraphOptimizer over the device (euroc_eval.cpp:211-215, 235, 282-288)
     std::unique_ptr<adapters::hip::HipPoseGraphOptimizer> graph;
     if (!optimize_file.empty()) graph = std::make_unique<adapters::hip::HipPoseGraphOptimizer>();
@@ -397,6 +416,17 @@ int main(int argc, char** argv) {
             std::vector<std::uint8_t> right_gray;
             core::Frame right_frame;
             std::unique_ptr<adapters::hip::HipDenseStereo> dense_stereo;   // --dense: made at the first pair, for its size
+            std::unique_ptr<adapters::hip::HipTsdfVolume> volume;          // --volume: centred on the first camera, the world origin
+            adapters::hip::DenseDepth dense_map;
+            if (!volume_file.empty()) {
+                adapters::hip::TsdfVolumeConfig vc;
+                if (rectifier) vc.K = new_K;
+                vc.voxel = (float)voxel;
+                vc.trunc = 4.0f * vc.voxel;
+                vc.device = fc.hip_device;
+                vc.centreOn(0.0f, 0.0f, 0.0f);
+                volume = std::make_unique<adapters::hip::HipTsdfVolume>(vc);
+            }
             if (stereo) {
                 adapters::hip::StereoConfig sc;
                 sc.baseline = stereo_baseline_used;
@@ -430,9 +460,10 @@ int main(int argc, char** argv) {
                             dc.max_height = fh;
                             dense_stereo = std::make_unique<adapters::hip::HipDenseStereo>(dc);
                         }
-                        const adapters::hip::DenseDepth dm = dense_stereo->compute(gray.data(), right_gray.data(), fw, fh);
+                        adapters::hip::DenseDepth dm = dense_stereo->compute(gray.data(), right_gray.data(), fw, fh);
                         dense_lines[i].valid_share = dm.validShare();
                         dense_lines[i].median_depth = dm.medianDepth();
+                        if (volume) dense_map = std::move(dm);
                     }
                 }
                 if (!traj.empty()) {
@@ -468,6 +499,9 @@ int main(int argc, char** argv) {
                             if (i > 0) graph->addOdometryEdge((int)i - 1, (int)i, graphPose(d));
                             last_vertex[i] = (long long)i;
                         }
+                        // --volume: this frame's depth map at the updated pose, when the translation carries a metric scale
+                        if (volume && stereo_lines[i].scale_valid)
+                            volume->integrate(dense_map.depth.data(), fw, fh, current_pose.data(), gray.data());
                         if (mapper && r.previous)                          // euroc_eval.cpp:218-222: view 1 = previous frame
                             mapper->triangulateExtrinsics(*r.previous, *r.frame, r.matches, c.data(), current_pose.data(),
                                                           prev_gray.data(), pw, ph, fc.frontend.legacy_order);
@@ -496,6 +530,10 @@ int main(int argc, char** argv) {
                 mapper->filterOutliers();
                 mapper->exportPLY(map_file);
                 map_points = mapper->size();
+            }
+            if (volume) {
+                volume_points = (long long)volume->exportPLY(volume_file);
+                volume_observed = (long long)volume->observedVoxels();
             }
         } catch (const std::exception& e) {
             errors[(size_t)s] = e.what();
@@ -701,6 +739,7 @@ int main(int argc, char** argv) {
         }
         std::printf("dense 64 disparities | mean valid share %.4f -> %s\n", N ? share / N : 0.0, dense_file.c_str());
     }
+    if (!volume_file.empty()) std::printf("volume %lld %lld\n", volume_points, volume_observed);
     if (!eval_file.empty()) {                                              // euroc_eval.cpp:247-252, 294-305
         try {
             aria_eval_config ec;

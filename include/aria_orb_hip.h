@@ -1311,6 +1311,112 @@ int64_t aria_dense_scratch_bytes_per_pair(int width, int height);
 /* Algorithmic bytes of one pair: both images read, the int16 disparity and the fp32 depth written, 8 * W * H. */
 int64_t aria_dense_algorithmic_bytes(int width, int height);
 
+/* ---- dense depth fusion: the fp32 depth maps of aria_dense_* integrated along the trajectory into one truncated signed
+ * distance volume in HBM, and the surface points read back out of it. The reference has no code for it (its roadmap items
+ * H17, H20 and H22 sit on such a map), so the NumPy restatement aria_slam_amd/tsdf_ref.py is the definition and the device
+ * equals it bit for bit. Out of scope: normals, marching-cubes meshes, ray casting, bilinear depth lookup, volume shifting
+ * or hashing, and any path-planning or alert logic. Additive to ABI 4.
+ *
+ * Unless stated otherwise the arithmetic is fp32, one rounding per operation, no contraction, in exactly the order written.
+ * 1. Volume. nx, ny, nz voxels, each a multiple of 8 in 8..1024; `voxel` the edge in metres (> 0); origin[3] the world
+ *   corner of voxel (0,0,0); trunc > 0 and inv_trunc = 1.0f / trunc formed once; min_depth <= max_depth; max_weight and
+ *   min_weight in 1..65535; fx, fy, cx, cy converted once with (float). One aria_tsdf_voxel of 8 bytes per voxel at the
+ *   linear index (k*ny + j)*nx + i, x fastest; cleared = all bytes zero. The centre of voxel (i,j,k) is
+ *   c = origin + ((float)i + 0.5f) * voxel per axis.
+ * 2. Frame inputs. An fp32 depth map of W x H with a pitch in elements (what aria_dense_compute_batch_device writes);
+ *   world-to-camera extrinsics [R|t], 12 doubles row-major (one half of the mapper's d_extrinsics record, x_cam = R X + t),
+ *   each converted with (float) once; an optional gray image (`pitch` bytes per row); an optional byte mask per frame, 0 =
+ *   skip the frame. An unmasked frame with a non-finite extrinsic is skipped as a whole and defers ARIA_E_INVALID; the
+ *   other frames are unaffected.
+ * 3. Integration. For each voxel the frames are applied in ascending frame order:
+ *   a. xc = ((r00*cX + r01*cY) + r02*cZ) + t0; yc and zc the same from rows 1 and 2.
+ *   b. Reject unless zc >= min_depth (a NaN fails every test here and below).
+ *   c. iz = 1.0f / zc; u = (fx * xc) * iz + cx; v = (fy * yc) * iz + cy.
+ *   d. ur = rintf(u), vr = rintf(v), half-even. Reject unless 0 <= ur <= W-1 and 0 <= vr <= H-1, compared in float; then
+ *     ui = (int)ur, vi = (int)vr.
+ *   e. D = depth[vi, ui]. Reject unless D >= min_depth and D <= max_depth (drops 0, negatives, NaN and Inf).
+ *   f. sdf = D - zc. Reject if sdf < -trunc. s = fminf(1.0f, sdf * inv_trunc).
+ *   g. w = (float)weight; tsdf = (tsdf * w + s) / (w + 1.0f); weight = min(weight + 1, max_weight).
+ *   h. With an image, in 32-bit integers: g = image[vi, ui], gray = (gray*W0 + g + ((W0 + 1) >> 1)) / (W0 + 1) with W0 the
+ *     weight before step g. Without an image gray is untouched.
+ *   A rejected voxel-frame changes no byte.
+ * 4. Surface points. For voxel a in ascending linear index and axis in 0, 1, 2 (+x, +y, +z), b is the next voxel along
+ *   that axis if it is inside the volume. A point is emitted when both weights are >= min_weight and
+ *   (tsdf_a < 0) != (tsdf_b < 0), zero counting as non-negative: alpha = tsdf_a / (tsdf_a - tsdf_b); X = c_a with
+ *   alpha * voxel added on that axis; gray = alpha < 0.5f ? gray_a : gray_b; weight = min(weight_a, weight_b). The output
+ *   order is exactly this order. With a capacity `cap` the first min(total, cap) points are written, the count word
+ *   receives total, and total > cap defers ARIA_E_OUTPUT_TOO_SMALL.
+ * Determinism. No float atomics; a voxel is owned by one lane, which walks the frames of a call in order. The result is
+ *   bitwise independent of how the frames are split into calls and reproducible from run to run. */
+typedef struct aria_tsdf_s* aria_tsdf_t;
+typedef struct {
+    float    tsdf;              /* in units of trunc, [-1, 1]                                                      */
+    uint16_t weight;
+    uint8_t  gray;
+    uint8_t  reserved;          /* always 0                                                                        */
+} aria_tsdf_voxel;              /* 8 bytes                                                                         */
+typedef struct {
+    float    X[3];
+    uint8_t  gray;
+    uint8_t  axis;              /* 0, 1, 2: the crossing lies between voxel a and its +x, +y, +z neighbour         */
+    uint16_t weight;
+} aria_tsdf_point;              /* 16 bytes                                                                        */
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_tsdf_config)                                                     */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    int      nx, ny, nz;        /* default 256 x 256 x 128; each a multiple of 8 in 8..1024                        */
+    int      max_weight;        /* default 64, 1..65535                                                            */
+    int      min_weight;        /* default 2, 1..65535: what the extraction asks of both voxels                    */
+    int      reserved;
+    float    voxel;             /* default 0.05 m                                                                  */
+    float    trunc;             /* default 0.20 m                                                                  */
+    float    origin[3];         /* default (-6.4, -6.4, 0): the default camera at the world origin looks into it   */
+    float    min_depth, max_depth;   /* default 0.3, 10                                                            */
+    float    reserved2;
+    double   fx, fy, cx, cy;    /* intrinsics of the depth maps (default EuRoC cam0)                               */
+} aria_tsdf_config;             /* 104 bytes                                                                       */
+
+void  aria_tsdf_default_config(aria_tsdf_config* cfg);
+/* Allocates the volume (aria_tsdf_volume_bytes) once and zeroes it. ARIA_E_INVALID for a bad field, before any device is
+ * touched; a volume that does not fit returns the HIP error, before any kernel runs. */
+int   aria_tsdf_create(const aria_tsdf_config* cfg, aria_tsdf_t* out);
+void  aria_tsdf_destroy(aria_tsdf_t h);
+void* aria_tsdf_stream(aria_tsdf_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when some unmasked frame had a non-finite extrinsic (that frame was skipped), else
+ * ARIA_E_OUTPUT_TOO_SMALL when an extraction found more points than its capacity. */
+int   aria_tsdf_check(aria_tsdf_t h);
+/* Every byte of the volume back to zero. Enqueued on the handle's stream, no synchronisation. */
+int   aria_tsdf_clear(aria_tsdf_t h);
+/* Step 3 over a batch in HBM. Frame f reads its depth map at d_depth + f*depth_stride (`depth_pitch` elements per row, both
+ * in elements), its 12 doubles at d_extrinsics + 12*f, its byte at d_frame_mask + f (NULL = every frame) and its image at
+ * d_img + f*img_stride (`img_pitch` bytes per row; NULL = gray untouched). width, height in 1..16384, n_frames <= 65535.
+ * Every voxel record is read once and written at most once per call, whatever n_frames is. Enqueued on the handle's stream,
+ * no synchronisation. */
+int   aria_tsdf_integrate_batch_device(aria_tsdf_t h, const float* d_depth, int64_t depth_stride, int depth_pitch, int width,
+                                       int height, const double* d_extrinsics, const uint8_t* d_frame_mask, const uint8_t* d_img,
+                                       int64_t img_stride, int img_pitch, int n_frames);
+/* One frame from host buffers; blocks. depth_pitch in elements; img may be NULL. A non-finite extrinsic: ARIA_E_INVALID and
+ * the volume untouched. */
+int   aria_tsdf_integrate(aria_tsdf_t h, const float* depth, int width, int height, int depth_pitch, const double* extrinsics,
+                          const uint8_t* img, int img_pitch);
+/* Step 4 into HBM: the first min(total, cap) points at d_points (may be NULL when cap = 0), total at *d_count (device).
+ * Records beyond the written ones are not touched. Enqueued on the handle's stream, no synchronisation. */
+int   aria_tsdf_extract_points_device(aria_tsdf_t h, aria_tsdf_point* d_points, int64_t cap, int64_t* d_count);
+/* The same into host memory; blocks. *total = the points the volume holds; ARIA_E_OUTPUT_TOO_SMALL when cap is less (the
+ * first cap points are still written). points may be NULL when cap = 0. */
+int   aria_tsdf_extract_points(aria_tsdf_t h, aria_tsdf_point* points, int64_t cap, int64_t* total);
+/* The volume in HBM, nx*ny*nz records in the layout of rule 1; valid for the life of the handle. */
+aria_tsdf_voxel* aria_tsdf_device_voxels(aria_tsdf_t h);
+/* Host read-back of the box [i0, i0+ni) x [j0, j0+nj) x [k0, k0+nk): ni*nj*nk records, x fastest; blocks. */
+int   aria_tsdf_read_box(aria_tsdf_t h, int i0, int j0, int k0, int ni, int nj, int nk, aria_tsdf_voxel* out);
+/* 8 * nx * ny * nz, or ARIA_E_INVALID for sizes rule 1 refuses. Host only, no handle. */
+int64_t aria_tsdf_volume_bytes(int nx, int ny, int nz);
+/* Algorithmic bytes of one integration call: every record read and written once (16 B per voxel) and every depth pixel
+ * read once per frame (4 B). */
+int64_t aria_tsdf_algorithmic_bytes(int nx, int ny, int nz, int width, int height, int n_frames);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
