@@ -14,6 +14,7 @@ from .frontend import HipMatcher, OrbHipExtractor, flag_keypoints_device
 from .fusion import HipImuPreintegrator, HipSensorFusion
 from .fundamental import HipFundamentalEstimator, verify_loop_candidates
 from .mapper import HipMapper
+from .nav import HipPathPlanner
 from .pose import HipPoseEstimator
 from .posegraph import HipPoseGraphOptimizer
 from .rectify import HipRectifier, load_sensor_yaml
@@ -24,4 +25,4 @@ __all__ = ["KP_DTYPE", "MATCH_DTYPE", "AriaError", "abi_version", "build_library
            "status_string", "level_info", "resize_table", "algorithmic_bytes", "synth_frame_pair", "synth_sequence", "HipMatcher", "OrbHipExtractor", "flag_keypoints_device",
            "HipPoseEstimator", "HipMapper", "HipFundamentalEstimator", "verify_loop_candidates", "HipPoseGraphOptimizer",
            "HipSensorFusion", "HipImuPreintegrator", "HipTrajectoryEvaluator", "load_ground_truth_csv", "HipObjectDetector",
-           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume"]
+           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner"]

@@ -82,6 +82,11 @@ EXPORTS = [
     "aria_tsdf_default_config", "aria_tsdf_create", "aria_tsdf_destroy", "aria_tsdf_stream", "aria_tsdf_check", "aria_tsdf_clear",
     "aria_tsdf_integrate_batch_device", "aria_tsdf_integrate", "aria_tsdf_extract_points_device", "aria_tsdf_extract_points",
     "aria_tsdf_device_voxels", "aria_tsdf_read_box", "aria_tsdf_volume_bytes", "aria_tsdf_algorithmic_bytes",
+    # path planning (traversability grid from the TSDF volume, clearance and cost, goal fields, paths), additive to ABI 4
+    "aria_nav_default_config", "aria_nav_create", "aria_nav_destroy", "aria_nav_stream", "aria_nav_check",
+    "aria_nav_update_from_volume_device", "aria_nav_set_cells_device", "aria_nav_set_cells", "aria_nav_read_cells",
+    "aria_nav_read_clearance", "aria_nav_read_costs", "aria_nav_solve_device", "aria_nav_trace_device", "aria_nav_plan",
+    "aria_nav_device_fields", "aria_nav_read_field", "aria_nav_read_rounds", "aria_nav_field_bytes",
 ]
 
 
@@ -284,6 +289,22 @@ TSDF_VOXEL_DTYPE = np.dtype([("tsdf", "<f4"), ("weight", "<u2"), ("gray", "u1"),
 TSDF_POINT_DTYPE = np.dtype([("X", "<f4", (3,)), ("gray", "u1"), ("axis", "u1"), ("weight", "<u2")])
 
 
+class NavConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int),
+                ("nz", C.c_int), ("up_axis", C.c_int), ("band0", C.c_int), ("band1", C.c_int), ("min_weight", C.c_int),
+                ("occ_tsdf", C.c_float), ("occ_count", C.c_int), ("free_count", C.c_int), ("clear_radius", C.c_int),
+                ("block_d2", C.c_int), ("soft_d2", C.c_int), ("penalty", C.c_int), ("unknown_penalty", C.c_int),
+                ("allow_unknown", C.c_int), ("max_goals", C.c_int), ("voxel", C.c_float), ("origin", C.c_float * 3),
+                ("reserved", C.c_int)]
+
+
+# aria_nav_record (16 bytes); the states of a cell, the statuses of a query, the field value of an unreachable cell
+NAV_RECORD_DTYPE = np.dtype([("cost", "<i4"), ("n_cells", "<i4"), ("min_d2", "<i4"), ("status", "<i4")])
+NAV_FREE, NAV_OCCUPIED, NAV_UNKNOWN = 0, 1, 2
+NAV_OK, NAV_UNREACHABLE, NAV_OUT_OF_GRID, NAV_TRUNCATED = 0, 1, 2, 3
+NAV_INF = 0x7FFFFFFF
+
+
 # right_idx of a record sampled from a dense map (ARIA_DENSE_NO_KEYPOINT) and the disparity of an invalid pixel in 1/16 px
 DENSE_NO_KEYPOINT = 0x7FFFFFFF
 DENSE_INVALID = -16
@@ -447,6 +468,8 @@ def load_library():
         _bind_dense(L)
     if hasattr(L, "aria_tsdf_create"):
         _bind_tsdf(L)
+    if hasattr(L, "aria_nav_create"):
+        _bind_nav(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -596,6 +619,26 @@ def _bind_tsdf(L):
     L.aria_tsdf_volume_bytes.argtypes = [i, i, i]
     L.aria_tsdf_algorithmic_bytes.restype = i64
     L.aria_tsdf_algorithmic_bytes.argtypes = [i, i, i, i, i, i]
+
+
+def _bind_nav(L):
+    p, i = C.c_void_p, C.c_int
+    _bind_handle(L, "nav")
+    L.aria_nav_update_from_volume_device.argtypes = [p, p]
+    L.aria_nav_set_cells_device.argtypes = [p, p]
+    L.aria_nav_set_cells.argtypes = [p, p]
+    L.aria_nav_read_cells.argtypes = [p, p]
+    L.aria_nav_read_clearance.argtypes = [p, p]
+    L.aria_nav_read_costs.argtypes = [p, p]
+    L.aria_nav_solve_device.argtypes = [p, p, i]
+    L.aria_nav_trace_device.argtypes = [p, p, i, p, p, i]
+    L.aria_nav_plan.argtypes = [p, p, i, p, i, p, p, i]
+    L.aria_nav_device_fields.restype = p
+    L.aria_nav_device_fields.argtypes = [p]
+    L.aria_nav_read_field.argtypes = [p, i, p]
+    L.aria_nav_read_rounds.argtypes = [p, p, i]
+    L.aria_nav_field_bytes.restype = C.c_int64
+    L.aria_nav_field_bytes.argtypes = [i, i, i]
 
 
 def status_string(status):

@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -100,6 +100,14 @@
 // surface points are written as PLY (the --map header and vertex format) and "volume <points> <observed voxels>" is printed.
 // Without the flag nothing of this runs and every output is byte-identical.
 //
+// --plan FILE (needs --volume): path planning on the device (include/aria_orb_hip.h, "path planning"; aria_hip/
+// HipPathPlanner.hpp). After the volume is built its band [ny/2 - 8, ny/2 + 16) around the first camera's height is collapsed into
+// the traversability grid of the x-z plane (up_axis 1, the stage's default radii and penalties, which nobody has tuned on a
+// recording), and a path is planned from the cell under the first camera centre of the --pose chain to the cell under the last
+// (the centre of a world-to-camera pose [R|t] is -R^T t). FILE gets one "x y z" line per path cell, the cell's centre at the
+// middle of the band, and exactly one line "plan <status> <cost> <cells>" is printed (status 0 OK, 1 UNREACHABLE, 2 OUT_OF_GRID;
+// FILE is then empty). Without the flag nothing of this runs and every output is byte-identical.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -127,6 +135,7 @@
 #include "aria_hip/HipFundamentalEstimator.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
+#include "aria_hip/HipPathPlanner.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
 #include "aria_hip/HipDenseStereo.hpp"
 #include "aria_hip/HipRectifier.hpp"
@@ -166,7 +175,9 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file]\n"
+                             "  --plan file: a path over the --volume map from the cell under the first camera of the --pose chain to the cell under the last\n"
+                             "               (needs --volume): one x y z line per path cell\n"
                              "  --volume file.ply: dense depth fusion of the --dense depth maps along the --pose chain (needs --pose, --stereo, --dense): the surface\n"
                              "                     points of a TSDF volume centred on the first camera; --voxel m is the voxel edge (default 0.05)\n"
                              "  --dense file: dense stereo (census + SGM, 64 disparities) on the --stereo pairs: valid share and median depth, one line per frame\n"
@@ -186,7 +197,7 @@ int main(int argc, char** argv) {
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
-    std::string stereo_file, dense_file, volume_file;
+    std::string stereo_file, dense_file, volume_file, plan_file;
     double voxel = 0.05;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
@@ -210,6 +221,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--dense") && i + 1 < argc) dense_file = argv[++i];
         else if (!std::strcmp(argv[i], "--volume") && i + 1 < argc) volume_file = argv[++i];
         else if (!std::strcmp(argv[i], "--voxel") && i + 1 < argc) voxel = std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--plan") && i + 1 < argc) plan_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -254,6 +266,10 @@ int main(int argc, char** argv) {
     }
     if (!volume_file.empty() && (pose_file.empty() || !stereo || dense_file.empty() || !(voxel > 0))) {
         std::fprintf(stderr, "--volume needs --pose (the trajectory), --stereo baseline_m (its metric scale), --dense file (the depth maps) and --voxel > 0\n");
+        return 1;
+    }
+    if (!plan_file.empty() && volume_file.empty()) {
+        std::fprintf(stderr, "--plan needs --volume file.ply (the map it plans over)\n");
         return 1;
     }
     if (rectify && (batch > 0 || devices > 1 || shards > 1)) {
@@ -323,6 +339,7 @@ int main(int argc, char** argv) {
     std::vector<aria_fuse_visual> fuse_visual(fuse_file.empty() ? 0 : N);
     std::size_t map_points = 0;
     long long volume_points = 0, volume_observed = 0;   // --volume
+    aria_nav_record plan_record{ARIA_NAV_INF, 0, 0, ARIA_NAV_OUT_OF_GRID};   // --plan: a sequence without frames has no start
     // --optimize: the reference's PoseGraphOptimizer over the device (euroc_eval.cpp:211-215, 235, 282-288)
     std::unique_ptr<adapters::hip::HipPoseGraphOptimizer> graph;
     if (!optimize_file.empty()) graph = std::make_unique<adapters::hip::HipPoseGraphOptimizer>();
@@ -535,6 +552,26 @@ int main(int argc, char** argv) {
                 volume_points = (long long)volume->exportPLY(volume_file);
                 volume_observed = (long long)volume->observedVoxels();
             }
+            std::ofstream pf;
+            if (!plan_file.empty()) pf.open(plan_file);                    // created even when there is nothing to plan
+            if (volume && !plan_file.empty() && sp.hi > sp.first) {
+                adapters::hip::HipPathPlanner planner(adapters::hip::PathPlannerConfig::fromVolume(*volume));
+                planner.update(*volume);
+                auto cell_under = [&](const std::array<double, 16>& T) {    // the camera centre -R^T t of a world-to-camera pose
+                    float c[3];
+                    for (int a = 0; a < 3; a++) c[a] = (float)-(T[(size_t)a] * T[3] + T[(size_t)(4 + a)] * T[7] + T[(size_t)(8 + a)] * T[11]);
+                    return planner.cellOf(c[0], c[1], c[2]);
+                };
+                const std::array<std::int32_t, 2> start = cell_under(traj[sp.first]), goal = cell_under(traj[sp.hi - 1]);
+                const adapters::hip::PlanResult pr = planner.plan({goal}, {{start[0], start[1], 0}}, planner.nu() * planner.nv());
+                plan_record = pr.records[0];
+                pf << std::setprecision(9);
+                for (int k = 0; k < plan_record.n_cells; k++) {
+                    const std::int32_t c = pr.paths[(size_t)k];
+                    const std::array<float, 3> X = planner.centreOf(c % planner.nu(), c / planner.nu());
+                    pf << X[0] << ' ' << X[1] << ' ' << X[2] << '\n';
+                }
+            }
         } catch (const std::exception& e) {
             errors[(size_t)s] = e.what();
         }
@@ -740,6 +777,7 @@ int main(int argc, char** argv) {
         std::printf("dense 64 disparities | mean valid share %.4f -> %s\n", N ? share / N : 0.0, dense_file.c_str());
     }
     if (!volume_file.empty()) std::printf("volume %lld %lld\n", volume_points, volume_observed);
+    if (!plan_file.empty()) std::printf("plan %d %d %d\n", plan_record.status, plan_record.cost, plan_record.n_cells);
     if (!eval_file.empty()) {                                              // euroc_eval.cpp:247-252, 294-305
         try {
             aria_eval_config ec;

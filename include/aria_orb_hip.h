@@ -1315,7 +1315,7 @@ int64_t aria_dense_algorithmic_bytes(int width, int height);
  * distance volume in HBM, and the surface points read back out of it. The reference has no code for it (its roadmap items
  * H17, H20 and H22 sit on such a map), so the NumPy restatement aria_slam_amd/tsdf_ref.py is the definition and the device
  * equals it bit for bit. Out of scope: normals, marching-cubes meshes, ray casting, bilinear depth lookup, volume shifting
- * or hashing, and any path-planning or alert logic. Additive to ABI 4.
+ * or hashing, and any alert logic (path planning is the stage below). Additive to ABI 4.
  *
  * Unless stated otherwise the arithmetic is fp32, one rounding per operation, no contraction, in exactly the order written.
  * 1. Volume. nx, ny, nz voxels, each a multiple of 8 in 8..1024; `voxel` the edge in metres (> 0); origin[3] the world
@@ -1416,6 +1416,124 @@ int64_t aria_tsdf_volume_bytes(int nx, int ny, int nz);
 /* Algorithmic bytes of one integration call: every record read and written once (16 B per voxel) and every depth pixel
  * read once per frame (4 B). */
 int64_t aria_tsdf_algorithmic_bytes(int nx, int ny, int nz, int width, int height, int n_frames);
+
+/* ---- path planning: a 2-D traversability grid collapsed out of a height band of the volume of aria_tsdf_*, an exact
+ * clearance field and an integer cost map, exact cost-to-go fields for a batch of goals, and paths traced for a batch of
+ * queries. The reference has no code for it (its roadmap items H20 and H22 sit on such a map), so the NumPy restatement
+ * aria_slam_amd/nav_ref.py is the definition and the device equals it bit for bit. Out of scope: 3-D planning, RRT*,
+ * any-angle paths or path smoothing, moving obstacles, the alert logic of H22, audio, grids that shift with the camera, and
+ * fields split over more than one workgroup. Additive to ABI 4. ("plan" already names the ORB level plan, hence "nav".)
+ *
+ * All arithmetic is in integers; the one exception is the fp32 compare of rule 2.
+ * 1. Grid. The volume geometry nx, ny, nz as in rule 1 of the dense depth fusion: each a multiple of 8 in 8..1024. up_axis
+ *   is 0, 1 or 2; the plane axes (U, V) are the other two in ascending order and nu, nv their sizes. Cell (u, v) has the
+ *   linear index c = v*nu + u. The band is [band0, band1) on up_axis, 0 <= band0 < band1 <= n_up. A cell's state is a
+ *   uint8: 0 FREE, 1 OCCUPIED, 2 UNKNOWN. A new handle holds UNKNOWN cells.
+ * 2. Cells from a volume (aria_tsdf_voxel records in that stage's layout). Over the voxels of a cell's column inside the
+ *   band, n_seen counts weight >= min_weight and n_solid counts weight >= min_weight && tsdf < occ_tsdf (an fp32 compare).
+ *   The cell is OCCUPIED if n_solid >= occ_count, else FREE if n_seen >= free_count, else UNKNOWN. Cells may also be set
+ *   from a uint8 array; a value above 2 is ARIA_E_INVALID: the host form refuses the call, the device form defers the error
+ *   and leaves the old cells in place.
+ * 3. Clearance. R = clear_radius in 0..64, CAP = (R+1)*(R+1). d2(c) is the minimum of du*du + dv*dv over the OCCUPIED cells
+ *   with |du| <= R and |dv| <= R inside the grid, CAP when there is none; the grid border is no obstacle. uint16.
+ * 4. Cost. blocked(c) when the cell is OCCUPIED, or d2(c) < block_d2, or the cell is UNKNOWN and allow_unknown == 0. Else
+ *   pen(c) = (d2 < soft_d2 ? penalty*(soft_d2 - d2)/soft_d2 : 0) + (UNKNOWN ? unknown_penalty : 0) in 32-bit integers with
+ *   truncating division. 0 <= block_d2 <= soft_d2 <= CAP, soft_d2 >= 1, penalty and unknown_penalty in 0..1000. The cost
+ *   is a uint16, 0xFFFF = blocked. Every path cost stays below 2^31: at most 2^20 cells times a step of at most 14 + 2000.
+ * 5. Moves m = 0..7 in this order: (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,+1) (+1,-1) (-1,-1); base = 10 for m < 4, else
+ *   14. A move c -> b is allowed when b is inside the grid and not blocked; a diagonal move also needs (u+du, v) and
+ *   (u, v+dv) not blocked (paths do not cut corners). step(c -> b) = base + pen(b).
+ * 6. Goal field. For a goal cell g, D is the least solution of D(g) = 0 and D(c) = min over the allowed moves of
+ *   step(c -> b) + D(b) for c not blocked; D = 0x7FFFFFFF for blocked and unreachable cells. A goal that is blocked or
+ *   outside the grid gives an all-0x7FFFFFFF field; that is no error.
+ * 7. Paths. A query is (su, sv, goal_index). Status 2 OUT_OF_GRID: the start is outside the grid, the goal index is outside
+ *   [0, G), or that goal was outside the grid. 1 UNREACHABLE: D(start) = 0x7FFFFFFF. 0 OK. 3 TRUNCATED: more cells than
+ *   path_cap. For 0 and 3 the path starts at the start cell; from c the next cell is b of the FIRST m in move order that is
+ *   allowed and has step(c -> b) + D(b) == D(c); the path ends at g. The record: cost = D(start), n_cells (start and goal
+ *   included, the full length even when truncated), min_d2 over the full path, status; for status 1 and 2 cost =
+ *   0x7FFFFFFF, n_cells = 0, min_d2 = 0. The cells go to paths[q*path_cap + i] as linear indices: the first
+ *   min(n_cells, path_cap) are written and nothing beyond them is touched. Any TRUNCATED query defers
+ *   ARIA_E_OUTPUT_TOO_SMALL.
+ * Determinism. The least solution of rule 6 is unique, so the device result is bitwise independent of the relaxation
+ *   schedule, of the order in which concurrent relaxations see each other's integer updates, and of the run. No float
+ *   atomics, no grid-wide barrier; the convergence loop of a field is bounded by nu*nv + 1 rounds, and reaching the bound
+ *   defers ARIA_E_OVERFLOW. */
+typedef struct aria_nav_s* aria_nav_t;
+typedef struct {
+    int32_t  cost;              /* D(start), 0x7FFFFFFF for status 1 and 2                                         */
+    int32_t  n_cells;           /* the full length of the path, start and goal included                            */
+    int32_t  min_d2;            /* the least clearance d2 over the full path                                       */
+    int32_t  status;            /* 0 OK, 1 UNREACHABLE, 2 OUT_OF_GRID, 3 TRUNCATED                                 */
+} aria_nav_record;              /* 16 bytes                                                                        */
+#define ARIA_NAV_OK 0
+#define ARIA_NAV_UNREACHABLE 1
+#define ARIA_NAV_OUT_OF_GRID 2
+#define ARIA_NAV_TRUNCATED 3
+#define ARIA_NAV_INF 0x7FFFFFFF
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_nav_config)                                                      */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    int      nx, ny, nz;        /* the volume's geometry; default 256 x 256 x 128                                  */
+    int      up_axis;           /* default 1: the first camera's y is the world's vertical in this chain           */
+    int      band0, band1;      /* default [ny/2 - 8, ny/2 + 16) = [120, 144)                                      */
+    int      min_weight;        /* default 2, 1..65535                                                             */
+    float    occ_tsdf;          /* default 0: a seen voxel behind the surface is solid                             */
+    int      occ_count;         /* default 1, 1..1024                                                              */
+    int      free_count;        /* default 1, 1..1024                                                              */
+    int      clear_radius;      /* default 8, 0..64 cells                                                          */
+    int      block_d2;          /* default 16                                                                      */
+    int      soft_d2;           /* default 64                                                                      */
+    int      penalty;           /* default 20, 0..1000                                                             */
+    int      unknown_penalty;   /* default 10, 0..1000                                                             */
+    int      allow_unknown;     /* default 1; 0 = UNKNOWN cells are blocked                                        */
+    int      max_goals;         /* default 256, 1..65535: the goals of one solve                                   */
+    float    voxel;             /* default 0.05 m: for the world helpers of the bindings only                      */
+    float    origin[3];         /* default (-6.4, -6.4, 0)                                                         */
+    int      reserved;
+} aria_nav_config;              /* 104 bytes                                                                       */
+
+void  aria_nav_default_config(aria_nav_config* cfg);
+/* Allocates the grid and the field buffer (aria_nav_field_bytes) once. ARIA_E_INVALID for a bad field, before any device
+ * is touched. */
+int   aria_nav_create(const aria_nav_config* cfg, aria_nav_t* out);
+void  aria_nav_destroy(aria_nav_t h);
+void* aria_nav_stream(aria_nav_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when a set_cells_device call held a value above 2, else ARIA_E_OVERFLOW when a field did not settle within
+ * its bound (results are not valid), else ARIA_E_OUTPUT_TOO_SMALL when some query was TRUNCATED. */
+int   aria_nav_check(aria_nav_t h);
+/* Rules 2-4 from a volume in HBM (aria_tsdf_device_voxels of a volume of this geometry). Enqueued on the handle's stream,
+ * no synchronisation. */
+int   aria_nav_update_from_volume_device(aria_nav_t h, const aria_tsdf_voxel* d_voxels);
+/* Rules 3-4 on nu*nv given cells in HBM. Enqueued. */
+int   aria_nav_set_cells_device(aria_nav_t h, const uint8_t* d_cells);
+/* The same from host memory; blocks. */
+int   aria_nav_set_cells(aria_nav_t h, const uint8_t* cells);
+/* Host read-back of nu*nv cells, clearances and costs; each blocks. */
+int   aria_nav_read_cells(aria_nav_t h, uint8_t* out);
+int   aria_nav_read_clearance(aria_nav_t h, uint16_t* out);
+int   aria_nav_read_costs(aria_nav_t h, uint16_t* out);
+/* Rule 6 for n_goals goals (d_goals: 2*n_goals int32, u then v) into the handle's field buffer, one workgroup per goal.
+ * n_goals > max_goals is ARIA_E_INVALID; 0 is accepted. Enqueued. */
+int   aria_nav_solve_device(aria_nav_t h, const int32_t* d_goals, int n_goals);
+/* Rule 7 for n_queries queries (d_queries: 3*n_queries int32) against the fields of the last solve. d_paths may be NULL when
+ * path_cap is 0. A trace after the map changed and before a new solve is ARIA_E_INVALID, refused before anything is
+ * enqueued. Enqueued. */
+int   aria_nav_trace_device(aria_nav_t h, const int32_t* d_queries, int n_queries, aria_nav_record* d_records, int32_t* d_paths,
+                            int path_cap);
+/* Solve and trace from host arrays; blocks. Path entries that rule 7 does not write keep the caller's bytes.
+ * ARIA_E_OUTPUT_TOO_SMALL when some query was TRUNCATED (records and paths are still written). */
+int   aria_nav_plan(aria_nav_t h, const int32_t* goals, int n_goals, const int32_t* queries, int n_queries, aria_nav_record* records,
+                    int32_t* paths, int path_cap);
+/* The field buffer in HBM: goal g at + g*nu*nv, int32; valid for the life of the handle. */
+int32_t* aria_nav_device_fields(aria_nav_t h);
+/* Host read-back of the field of goal g of the last solve, nu*nv int32; blocks. */
+int   aria_nav_read_field(aria_nav_t h, int g, int32_t* out);
+/* The relaxation rounds each of the first n_goals goals of the last solve took (0 for a goal without a field); blocks. */
+int   aria_nav_read_rounds(aria_nav_t h, int32_t* out, int n_goals);
+/* 4 * nu * nv * max_goals, or ARIA_E_INVALID for sizes the stage refuses. Host only, no handle. */
+int64_t aria_nav_field_bytes(int nu, int nv, int max_goals);
 
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
