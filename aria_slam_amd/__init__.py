@@ -7,6 +7,7 @@ compute of its own and no CPU fallback: if the HIP library is missing or no GPU 
 """
 from ._lib import (KP_DTYPE, MATCH_DTYPE, AriaError, abi_version, algorithmic_bytes, build_library, build_variants_library, level_info,
                    library_path, load_library, resize_table, status_string, synth_frame_pair, synth_sequence)
+from .alert import HipObstacleAlerter
 from .dense import HipDenseStereo
 from .detect import HipObjectDetector
 from .evaluate import HipTrajectoryEvaluator, load_ground_truth_csv
@@ -25,4 +26,4 @@ __all__ = ["KP_DTYPE", "MATCH_DTYPE", "AriaError", "abi_version", "build_library
            "status_string", "level_info", "resize_table", "algorithmic_bytes", "synth_frame_pair", "synth_sequence", "HipMatcher", "OrbHipExtractor", "flag_keypoints_device",
            "HipPoseEstimator", "HipMapper", "HipFundamentalEstimator", "verify_loop_candidates", "HipPoseGraphOptimizer",
            "HipSensorFusion", "HipImuPreintegrator", "HipTrajectoryEvaluator", "load_ground_truth_csv", "HipObjectDetector",
-           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner"]
+           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner", "HipObstacleAlerter"]

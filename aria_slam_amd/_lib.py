@@ -87,6 +87,10 @@ EXPORTS = [
     "aria_nav_update_from_volume_device", "aria_nav_set_cells_device", "aria_nav_set_cells", "aria_nav_read_cells",
     "aria_nav_read_clearance", "aria_nav_read_costs", "aria_nav_solve_device", "aria_nav_trace_device", "aria_nav_plan",
     "aria_nav_device_fields", "aria_nav_read_field", "aria_nav_read_rounds", "aria_nav_field_bytes",
+    # obstacle alerts (depth zones and detection boxes measured exactly, priorities, cooldowns, events), additive to ABI 4
+    "aria_alert_default_config", "aria_alert_create", "aria_alert_destroy", "aria_alert_stream", "aria_alert_check",
+    "aria_alert_dets_seen", "aria_alert_measure_batch_device", "aria_alert_arbitrate_batch_device", "aria_alert_run_batch_device",
+    "aria_alert_measure", "aria_alert_arbitrate", "aria_alert_run", "aria_alert_zone_bounds", "aria_alert_algorithmic_bytes",
 ]
 
 
@@ -305,6 +309,28 @@ NAV_OK, NAV_UNREACHABLE, NAV_OUT_OF_GRID, NAV_TRUNCATED = 0, 1, 2, 3
 NAV_INF = 0x7FFFFFFF
 
 
+class AlertConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("width", C.c_int), ("height", C.c_int),
+                ("zone_top", C.c_int), ("zone_bottom", C.c_int), ("max_dets", C.c_int), ("min_valid", C.c_int),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("zone_pct_num", C.c_int), ("zone_pct_den", C.c_int),
+                ("det_pct_num", C.c_int), ("det_pct_den", C.c_int), ("zone_alert_m", C.c_float), ("default_depth", C.c_float),
+                ("crit_m", C.c_float), ("high_m", C.c_float), ("medium_m", C.c_float), ("beep_m", C.c_float),
+                ("obstacle_dangerous", C.c_int), ("n_dangerous", C.c_int), ("dangerous", C.c_int * 32),
+                ("max_events_per_frame", C.c_int), ("reserved", C.c_int), ("cooldown_ns", C.c_int64 * 4)]
+
+
+# aria_alert_meas (16 bytes), aria_alert_event (32 bytes), aria_alert_state (2320 bytes) and the values they hold
+ALERT_MEAS_DTYPE = np.dtype([("distance", "<f4"), ("n_valid", "<i4"), ("k", "<i4"), ("flags", "<i4")])
+ALERT_EVENT_DTYPE = np.dtype([("frame", "<i4"), ("source", "<i4"), ("class_id", "<i4"), ("direction", "<i4"), ("priority", "<i4"),
+                              ("distance", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])
+ALERT_STATE_DTYPE = np.dtype([("last_ns", "<i8", (256,)), ("last_prio1", "u1", (256,)), ("events_total", "<i8"), ("reserved", "<i8")])
+ALERT_SOURCES, ALERT_MAX_DETS = 64, 61
+ALERT_LOW, ALERT_MEDIUM, ALERT_HIGH, ALERT_CRITICAL = 0, 1, 2, 3
+ALERT_CENTER, ALERT_LEFT, ALERT_RIGHT = 0, 1, 2
+ALERT_BEEP, ALERT_CRITICAL_ALERT, ALERT_INTERRUPT, ALERT_NO_DEPTH = 1, 2, 4, 8
+ALERT_MEAS_SOURCE, ALERT_MEAS_OK = 1, 2
+
+
 # right_idx of a record sampled from a dense map (ARIA_DENSE_NO_KEYPOINT) and the disparity of an invalid pixel in 1/16 px
 DENSE_NO_KEYPOINT = 0x7FFFFFFF
 DENSE_INVALID = -16
@@ -470,6 +496,8 @@ def load_library():
         _bind_tsdf(L)
     if hasattr(L, "aria_nav_create"):
         _bind_nav(L)
+    if hasattr(L, "aria_alert_create"):
+        _bind_alert(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -639,6 +667,21 @@ def _bind_nav(L):
     L.aria_nav_read_rounds.argtypes = [p, p, i]
     L.aria_nav_field_bytes.restype = C.c_int64
     L.aria_nav_field_bytes.argtypes = [i, i, i]
+
+
+def _bind_alert(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "alert")
+    L.aria_alert_dets_seen.argtypes = [p]
+    L.aria_alert_measure_batch_device.argtypes = [p, p, i64, i, i, p, p, i, p]
+    L.aria_alert_arbitrate_batch_device.argtypes = [p, p, i, p, i, p, p, p, i, p, p, i, p]
+    L.aria_alert_run_batch_device.argtypes = [p, p, i64, i, i, p, p, i, p, i, p, p, p, i, p]
+    L.aria_alert_measure.argtypes = L.aria_alert_measure_batch_device.argtypes
+    L.aria_alert_arbitrate.argtypes = L.aria_alert_arbitrate_batch_device.argtypes
+    L.aria_alert_run.argtypes = L.aria_alert_run_batch_device.argtypes
+    L.aria_alert_zone_bounds.argtypes = [i, p]
+    L.aria_alert_algorithmic_bytes.restype = i64
+    L.aria_alert_algorithmic_bytes.argtypes = [i, i, i, i]
 
 
 def status_string(status):

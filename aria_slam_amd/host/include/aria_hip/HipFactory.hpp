@@ -9,6 +9,7 @@
 
 #include "aria_hip/FrontEnd.hpp"
 #include "aria_hip/HipObjectDetector.hpp"
+#include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/compat.hpp"
 
 namespace aria::factory {
@@ -42,5 +43,10 @@ interfaces::ObjectDetectorPtr createHipDetector(const HipFactoryConfig& cfg, ada
                                                 adapters::hip::ObjectDetectorConfig det = {});
 std::unique_ptr<pipeline::FrontEnd> createHip(const HipFactoryConfig& cfg, adapters::hip::HipObjectDetector::InferenceHook hook,
                                               adapters::hip::ObjectDetectorConfig det = {});
+// The consumer of a frame's depth map and boxes (the sketch's NavigationAudioEngine, H16:421-493) on cfg.hip_device: it speaks
+// through `audio` (not owned; nullptr = events only) and names detections by class_names.
+std::unique_ptr<adapters::hip::HipObstacleAlerter> createHipAlerter(const HipFactoryConfig& cfg, interfaces::IAudioFeedback* audio,
+                                                                    std::vector<std::string> class_names = {},
+                                                                    adapters::hip::ObstacleAlerterConfig alert = {});
 
 }  // namespace aria::factory

@@ -8,6 +8,7 @@
 #pragma once
 
 #ifdef ARIA_HIP_USE_REFERENCE_HEADERS
+#include "interfaces/IAudioFeedback.hpp"
 #include "interfaces/IFeatureExtractor.hpp"
 #include "interfaces/ILoopDetector.hpp"
 #include "interfaces/IMapper.hpp"
@@ -213,6 +214,26 @@ public:
     virtual void reset(const core::Pose& initial_pose) = 0;
 };
 using SensorFusionPtr = std::unique_ptr<ISensorFusion>;
+
+// include/interfaces/IAudioFeedback.hpp:7-78 (the port has no adapter in the reference; the obstacle alerter speaks through it)
+enum class AudioPriority { LOW, MEDIUM, HIGH, CRITICAL };
+enum class AudioDirection { CENTER, LEFT, RIGHT, BEHIND };
+class IAudioFeedback {
+public:
+    virtual ~IAudioFeedback() = default;
+    virtual bool initialize() = 0;
+    virtual void shutdown() = 0;
+    virtual bool isReady() const = 0;
+    virtual void speak(const std::string& text, AudioPriority priority = AudioPriority::MEDIUM, bool interrupt = false) = 0;
+    virtual void playBeep(AudioDirection direction, int frequency_hz = 800, int duration_ms = 200, float volume = 0.7f) = 0;
+    virtual void playCriticalAlert(AudioDirection direction) = 0;
+    virtual void setVolume(float volume) = 0;
+    virtual float getVolume() const = 0;
+    virtual void setMuted(bool muted) = 0;
+    virtual bool isMuted() const = 0;
+    virtual void spinOnce() = 0;
+};
+using AudioFeedbackPtr = std::unique_ptr<IAudioFeedback>;
 
 }  // namespace aria::interfaces
 

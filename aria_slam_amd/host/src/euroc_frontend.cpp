@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--alerts FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -108,6 +108,14 @@
 // middle of the band, and exactly one line "plan <status> <cost> <cells>" is printed (status 0 OK, 1 UNREACHABLE, 2 OUT_OF_GRID;
 // FILE is then empty). Without the flag nothing of this runs and every output is byte-identical.
 //
+// --alerts FILE (needs --dense): obstacle alerts on the device (include/aria_orb_hip.h, "obstacle alerts"; aria_hip/
+// HipObstacleAlerter.hpp). Every frame's dense depth map goes through a HipObstacleAlerter of the frame's size with the stage's
+// defaults (the band is the lower three quarters of the image; nobody has tuned them on a recording), at the timestamp
+// llround(seconds * 1e9) ns. This driver sets no object detector, so the sources are the three zones. The events are played
+// through a RecordingAudioFeedback, and FILE gets one line per event: "timestamp_ns frame source class_id direction priority
+// distance flags | call; call; ..." with the calls the event made on the port. "alerts <events> <frames>" is printed. Without the
+// flag nothing of this runs and every output is byte-identical.
+//
 // Prints the progress line every 100 frames like the reference (:271-277) and a summary; --csv writes
 // "frame,timestamp,keypoints,matches,hash,keyframe,loop_match_id,loop_score" per frame, hash = FNV-1a 64 over the frame's
 // keypoint records, descriptor rows and match records (what the parity test compares with the oracle's).
@@ -135,6 +143,7 @@
 #include "aria_hip/HipFundamentalEstimator.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
+#include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/HipPathPlanner.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
 #include "aria_hip/HipDenseStereo.hpp"
@@ -175,7 +184,8 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--alerts file]\n"
+                             "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
                              "  --plan file: a path over the --volume map from the cell under the first camera of the --pose chain to the cell under the last\n"
                              "               (needs --volume): one x y z line per path cell\n"
                              "  --volume file.ply: dense depth fusion of the --dense depth maps along the --pose chain (needs --pose, --stereo, --dense): the surface\n"
@@ -197,7 +207,7 @@ int main(int argc, char** argv) {
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
-    std::string stereo_file, dense_file, volume_file, plan_file;
+    std::string stereo_file, dense_file, volume_file, plan_file, alerts_file;
     double voxel = 0.05;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
@@ -222,6 +232,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--volume") && i + 1 < argc) volume_file = argv[++i];
         else if (!std::strcmp(argv[i], "--voxel") && i + 1 < argc) voxel = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--plan") && i + 1 < argc) plan_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--alerts") && i + 1 < argc) alerts_file = argv[++i];
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -270,6 +281,10 @@ int main(int argc, char** argv) {
     }
     if (!plan_file.empty() && volume_file.empty()) {
         std::fprintf(stderr, "--plan needs --volume file.ply (the map it plans over)\n");
+        return 1;
+    }
+    if (!alerts_file.empty() && dense_file.empty()) {
+        std::fprintf(stderr, "--alerts needs --dense file (the depth maps it measures)\n");
         return 1;
     }
     if (rectify && (batch > 0 || devices > 1 || shards > 1)) {
@@ -339,6 +354,8 @@ int main(int argc, char** argv) {
     std::vector<aria_fuse_visual> fuse_visual(fuse_file.empty() ? 0 : N);
     std::size_t map_points = 0;
     long long volume_points = 0, volume_observed = 0;   // --volume
+    long long alert_events = 0, alert_frames = 0;       // --alerts
+    std::vector<std::string> alert_lines;
     aria_nav_record plan_record{ARIA_NAV_INF, 0, 0, ARIA_NAV_OUT_OF_GRID};   // --plan: a sequence without frames has no start
     // --optimize: the reference's PoseGraphOptimizer over the device (euroc_eval.cpp:211-215, 235, 282-288)
     std::unique_ptr<adapters::hip::HipPoseGraphOptimizer> graph;
@@ -435,6 +452,8 @@ int main(int argc, char** argv) {
             std::unique_ptr<adapters::hip::HipDenseStereo> dense_stereo;   // --dense: made at the first pair, for its size
             std::unique_ptr<adapters::hip::HipTsdfVolume> volume;          // --volume: centred on the first camera, the world origin
             adapters::hip::DenseDepth dense_map;
+            adapters::hip::RecordingAudioFeedback alert_audio;             // --alerts: made at the first pair, for its size
+            std::unique_ptr<adapters::hip::HipObstacleAlerter> alerter;
             if (!volume_file.empty()) {
                 adapters::hip::TsdfVolumeConfig vc;
                 if (rectifier) vc.K = new_K;
@@ -480,6 +499,29 @@ int main(int argc, char** argv) {
                         adapters::hip::DenseDepth dm = dense_stereo->compute(gray.data(), right_gray.data(), fw, fh);
                         dense_lines[i].valid_share = dm.validShare();
                         dense_lines[i].median_depth = dm.medianDepth();
+                        if (!alerts_file.empty()) {
+                            if (!alerter) {
+                                adapters::hip::ObstacleAlerterConfig ac;
+                                ac.width = fw;
+                                ac.height = fh;
+                                ac.device = fc.hip_device;
+                                alerter = std::make_unique<adapters::hip::HipObstacleAlerter>(ac, &alert_audio);
+                            }
+                            const long long t_ns = std::llround(seq.at(i).timestamp * 1e9);
+                            std::size_t call = 0;                          // the frame's calls on the port, in the events' order
+                            for (const aria_alert_event& e : alerter->process(dm.depth.data(), {}, t_ns)) {
+                                char head[160];
+                                std::snprintf(head, sizeof(head), "%lld %zu %d %d %d %d %.9g %d |", t_ns, i, e.source, e.class_id, e.direction,
+                                              e.priority, (double)e.distance, e.flags);
+                                std::string line = head;
+                                const std::size_t n_calls = 1 + ((e.flags & ARIA_ALERT_BEEP) ? 1 : 0) + ((e.flags & ARIA_ALERT_CRITICAL_ALERT) ? 1 : 0);
+                                for (std::size_t k = 0; k < n_calls && call < alert_audio.log.size(); k++) line += (k ? "; " : " ") + alert_audio.log[call++];
+                                alert_lines.push_back(line);
+                                alert_events++;
+                            }
+                            alert_audio.log.clear();
+                            alert_frames++;
+                        }
                         if (volume) dense_map = std::move(dm);
                     }
                 }
@@ -778,6 +820,11 @@ int main(int argc, char** argv) {
     }
     if (!volume_file.empty()) std::printf("volume %lld %lld\n", volume_points, volume_observed);
     if (!plan_file.empty()) std::printf("plan %d %d %d\n", plan_record.status, plan_record.cost, plan_record.n_cells);
+    if (!alerts_file.empty()) {
+        std::ofstream af(alerts_file);
+        for (const std::string& l : alert_lines) af << l << '\n';
+        std::printf("alerts %lld %lld\n", alert_events, alert_frames);
+    }
     if (!eval_file.empty()) {                                              // euroc_eval.cpp:247-252, 294-305
         try {
             aria_eval_config ec;

@@ -1535,6 +1535,161 @@ int   aria_nav_read_rounds(aria_nav_t h, int32_t* out, int n_goals);
 /* 4 * nu * nv * max_goals, or ARIA_E_INVALID for sizes the stage refuses. Host only, no handle. */
 int64_t aria_nav_field_bytes(int nu, int nv, int max_goals);
 
+/* ---- obstacle alerts: a frame's fp32 depth map (aria_dense_*) and its NMS-ed boxes (aria_det_*) turned into a short,
+ * prioritised, non-repeating list of warnings for a person who walks: an exact order statistic of the valid depths inside
+ * three image zones and every detection box, a priority from class and distance, and per-key cooldowns that persist along
+ * a track. This is the reference's roadmap item H22 ("Depth-based alerts with spatial audio feedback; alert prioritisation
+ * by risk + zone + distance with anti-spam cooldowns"). The reference has the port IAudioFeedback
+ * (include/interfaces/IAudioFeedback.hpp:7-78, no adapter) and a sketch of the caller, NavigationAudioEngine
+ * (docs/milestones/H16_AUDIO_FEEDBACK.md:393-493), with no depth source and no canAnnounce; so the NumPy restatement
+ * aria_slam_amd/alert_ref.py is the definition, it restates the sketch's rules wherever the sketch has them, and the
+ * device equals it bit for bit. Out of scope: sound synthesis and TTS, traffic-light and sign classification (H22.1-2: a
+ * network), tracking of objects across frames, BEHIND, alerts from the volume or the plan, and tuning of the defaults
+ * (band, percentiles and zone_alert_m are assumptions nobody has tuned on a recording). Additive to ABI 4.
+ *
+ * Priorities and directions take the reference's enum values: LOW 0, MEDIUM 1, HIGH 2, CRITICAL 3; CENTER 0, LEFT 1,
+ * RIGHT 2 (BEHIND is never produced). The rule arithmetic is integer arithmetic and fp32 compares; the two fp32 divisions of
+ * rule 3 and the fp32 product (the division by the width) of rule 1 are formed in fp32 exactly as written.
+ * 1. Sources of a frame: up to 64. The config fixes width, height and the row band [zone_top, zone_bottom). Sources 0, 1, 2
+ *   are the zones CENTER, LEFT, RIGHT over that band: column x is LEFT when ((float)x + 0.5f) / (float)width < 0.35f, RIGHT
+ *   when it is > 0.65f, else CENTER (H16:463-468), in fp32; the host finds the two boundaries once, by that very test
+ *   (aria_alert_zone_bounds). Source 3 + i is detection i of the frame, i < min(d_ndets[f], max_dets), max_dets <= 61; the
+ *   records are aria_detection as aria_det_postprocess_batch_device writes them (d_dets + f*det_cap). A detection's
+ *   rectangle is columns [max(0, (int)x1), min(width, (int)x2)) and rows likewise (Rect(x1, y1, x2-x1, y2-y1)); it is empty
+ *   when a corner is non-finite or outside +-2^20. A count outside [0, det_cap] skips the frame's detections and defers
+ *   ARIA_E_INVALID. aria_alert_check notes the largest count seen above max_dets (aria_alert_dets_seen).
+ * 2. Measurement. The valid depths of a rectangle are those with min_depth <= D <= max_depth (fp32 compares; 0, negatives,
+ *   NaN and Inf drop out; 0 < min_depth <= max_depth, finite) in the fp32 depth map, which has a pitch in elements, as
+ *   aria_dense_compute_batch_device writes it. With n valid and n >= min_valid, distance is the value at index
+ *   k = (n * pct_num) / pct_den of the ascending list (64-bit integers, 0 <= pct_num < pct_den): zones use zone_pct
+ *   (default 5/100: the near edge, robust to speckle), detections det_pct (default 1/2: the median). Otherwise there is no
+ *   measurement. One 16-byte aria_alert_meas per source slot at d_meas + f*64; a slot that is no source, or has no
+ *   measurement, holds distance -1 and k 0. No NaN or Inf is ever written.
+ * 3. Candidates. A zone is a candidate when it has a measurement and distance < zone_alert_m; its class_id is -1 and its
+ *   direction its zone. A detection is always a candidate: without a measurement its distance is default_depth (5.0f,
+ *   H16:437) and the flag NO_DEPTH is set; its direction comes from cx = (x1 + x2) / 2.0f; nrm = cx / (float)width; LEFT
+ *   when nrm < 0.35f, else RIGHT when nrm > 0.65f, else CENTER (a NaN gives CENTER). Priority (H16:470-478):
+ *   distance < crit_m: CRITICAL; else distance < high_m and dangerous: HIGH; else distance < medium_m: MEDIUM; else LOW.
+ *   Dangerous: the class is in the config's list (up to 32 ids, default {0, 1, 2, 3, 5, 7}); class -1 is dangerous when
+ *   obstacle_dangerous is set. Flags: BEEP when distance < beep_m (1.5f, H16:453); CRITICAL_ALERT and INTERRUPT when
+ *   CRITICAL (H16:404-407).
+ * 4. Order inside a frame: descending priority, then ascending distance (fp32 compare), then ascending direction value,
+ *   then ascending source index: a strict total order.
+ * 5. Cooldowns. A candidate's key is class_key*3 + direction, class_key = 0 for class -1, else 1 + min(max(class_id, 0), 83):
+ *   255 keys in a table of 256. A track's state, aria_alert_state, is 2320 bytes; cleared = all zero bytes. Frames of a track
+ *   carry int64 timestamps in nanoseconds (EuRoC's own); a timestamp lower than that of the last accepted frame before it in
+ *   the call skips the frame and defers ARIA_E_INVALID. Candidates are walked in rule 4's order; one is announced when its key
+ *   was never announced, or its priority is above the key's last announced priority, or
+ *   t - last_ns[key] >= cooldown_ns[priority] (defaults 2000, 800, 500, 0 ms for LOW..CRITICAL, H16:395-400). At most
+ *   max_events_per_frame (default 2) are announced per frame. Announcing stores t and the priority in the key's state.
+ * 6. Events. Announced candidates are appended to the track's list (d_events + track*event_cap) as 32-byte
+ *   aria_alert_event, in frame order and then rule 4's order; `frame` is the index into the call's frames. d_nevents[track]
+ *   receives the total of the call, the first event_cap are written and nothing beyond them is touched; more defers
+ *   ARIA_E_OUTPUT_TOO_SMALL, and the state still advances as if all had been written. A track whose offsets are decreasing
+ *   or outside [0, n_frames] is skipped (0 events, the state untouched) and defers ARIA_E_INVALID.
+ * Determinism. The order statistic is an exact selection on the bit patterns (positive floats order as their bits) by
+ *   radix passes over LDS histograms filled by integer atomics: counts are order-independent. No float atomics anywhere.
+ *   Results are bitwise reproducible, independent of a frame's place in a batch and, for timestamps that do not decrease, of
+ *   how a track is cut into calls (the state does not hold the last timestamp: rule 5's test of it starts afresh with every
+ *   call). Tracks may share frames; frames are only read. */
+typedef struct aria_alert_s* aria_alert_t;
+#define ARIA_ALERT_SOURCES 64
+#define ARIA_ALERT_MAX_DETS 61
+#define ARIA_ALERT_LOW 0
+#define ARIA_ALERT_MEDIUM 1
+#define ARIA_ALERT_HIGH 2
+#define ARIA_ALERT_CRITICAL 3
+#define ARIA_ALERT_CENTER 0
+#define ARIA_ALERT_LEFT 1
+#define ARIA_ALERT_RIGHT 2
+#define ARIA_ALERT_BEEP 1
+#define ARIA_ALERT_CRITICAL_ALERT 2
+#define ARIA_ALERT_INTERRUPT 4
+#define ARIA_ALERT_NO_DEPTH 8
+#define ARIA_ALERT_MEAS_SOURCE 1   /* the slot is a source of the frame                                            */
+#define ARIA_ALERT_MEAS_OK 2       /* ... and has a measurement                                                    */
+typedef struct {
+    float    distance;          /* the order statistic, -1 = none                                                  */
+    int32_t  n_valid;           /* valid depths inside the rectangle                                               */
+    int32_t  k;                 /* the index taken, 0 without a measurement                                        */
+    int32_t  flags;             /* ARIA_ALERT_MEAS_*                                                               */
+} aria_alert_meas;              /* 16 bytes                                                                        */
+typedef struct {
+    int32_t  frame, source, class_id, direction, priority;
+    float    distance;
+    int32_t  flags, reserved;
+} aria_alert_event;             /* 32 bytes                                                                        */
+typedef struct {
+    int64_t  last_ns[256];      /* by key: the timestamp of the last announcement                                  */
+    uint8_t  last_prio1[256];   /* by key: its priority + 1, 0 = never                                             */
+    int64_t  events_total;      /* announcements over the life of the state                                        */
+    int64_t  reserved;
+} aria_alert_state;             /* 2320 bytes                                                                      */
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_alert_config)                                                    */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    int      width, height;     /* default 752 x 480, 1..8192                                                      */
+    int      zone_top, zone_bottom;   /* default [120, 480): 0 <= zone_top < zone_bottom <= height                 */
+    int      max_dets;          /* default 32, 0..61                                                               */
+    int      min_valid;         /* default 16, >= 1                                                                */
+    float    min_depth, max_depth;    /* default 0.1, 20 m                                                         */
+    int      zone_pct_num, zone_pct_den;   /* default 5 / 100                                                      */
+    int      det_pct_num, det_pct_den;     /* default 1 / 2                                                        */
+    float    zone_alert_m;      /* default 3.0                                                                     */
+    float    default_depth;     /* default 5.0, finite                                                             */
+    float    crit_m, high_m, medium_m, beep_m;   /* default 1.0, 2.0, 3.0, 1.5                                    */
+    int      obstacle_dangerous;   /* default 1                                                                    */
+    int      n_dangerous;       /* default 6, 0..32                                                                */
+    int      dangerous[32];     /* default {0, 1, 2, 3, 5, 7}                                                      */
+    int      max_events_per_frame;   /* default 2, 0..64                                                           */
+    int      reserved;
+    int64_t  cooldown_ns[4];    /* by priority, default 2000, 800, 500, 0 ms; >= 0                                 */
+} aria_alert_config;            /* 264 bytes                                                                       */
+
+void  aria_alert_default_config(aria_alert_config* cfg);
+/* ARIA_E_INVALID for a bad field (pct_num >= pct_den, max_dets > 61, an empty band, ...), before any device is touched. */
+int   aria_alert_create(const aria_alert_config* cfg, aria_alert_t* out);
+void  aria_alert_destroy(aria_alert_t h);
+void* aria_alert_stream(aria_alert_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when some frame's detection count was outside [0, det_cap], some timestamp decreased or some track's
+ * offsets were bad, else ARIA_E_OUTPUT_TOO_SMALL when some track announced more than event_cap events. */
+int   aria_alert_check(aria_alert_t h);
+/* The largest detection count above max_dets that the calls before the last aria_alert_check met (such a frame used its
+ * first max_dets detections), 0 when there was none. */
+int   aria_alert_dets_seen(aria_alert_t h);
+/* Rules 1-2 over n_frames depth maps in HBM: frame f at d_depth + f*depth_stride, `depth_pitch` elements per row (>= width).
+ * d_dets / d_ndets may both be NULL: zones only. Writes 64 records per frame at d_meas. Enqueued on the handle's stream. */
+int   aria_alert_measure_batch_device(aria_alert_t h, const float* d_depth, int64_t depth_stride, int depth_pitch, int n_frames,
+                                      const aria_detection* d_dets, const int* d_ndets, int det_cap, aria_alert_meas* d_meas);
+/* Rules 3-6 over n_tracks tracks: track t owns the frames [d_track_offset[t], d_track_offset[t+1]) of the n_frames frames
+ * that d_timestamps, d_meas, d_dets and d_ndets describe (d_dets / d_ndets may both be NULL). d_states[t] is read and
+ * written in place. Enqueued. */
+int   aria_alert_arbitrate_batch_device(aria_alert_t h, const int* d_track_offset, int n_tracks, const int64_t* d_timestamps,
+                                        int n_frames, const aria_alert_meas* d_meas, const aria_detection* d_dets, const int* d_ndets,
+                                        int det_cap, aria_alert_state* d_states, aria_alert_event* d_events, int event_cap,
+                                        int* d_nevents);
+/* Both, through a measurement buffer of the handle. Enqueued. */
+int   aria_alert_run_batch_device(aria_alert_t h, const float* d_depth, int64_t depth_stride, int depth_pitch, int n_frames,
+                                  const aria_detection* d_dets, const int* d_ndets, int det_cap, const int* d_track_offset,
+                                  int n_tracks, const int64_t* d_timestamps, aria_alert_state* d_states, aria_alert_event* d_events,
+                                  int event_cap, int* d_nevents);
+/* The same three over caller-owned host arrays; each blocks and returns what aria_alert_check would. Event slots that
+ * rule 6 does not write keep the caller's bytes. */
+int   aria_alert_measure(aria_alert_t h, const float* depth, int64_t depth_stride, int depth_pitch, int n_frames,
+                         const aria_detection* dets, const int* ndets, int det_cap, aria_alert_meas* meas);
+int   aria_alert_arbitrate(aria_alert_t h, const int* track_offset, int n_tracks, const int64_t* timestamps, int n_frames,
+                           const aria_alert_meas* meas, const aria_detection* dets, const int* ndets, int det_cap,
+                           aria_alert_state* states, aria_alert_event* events, int event_cap, int* nevents);
+int   aria_alert_run(aria_alert_t h, const float* depth, int64_t depth_stride, int depth_pitch, int n_frames,
+                     const aria_detection* dets, const int* ndets, int det_cap, const int* track_offset, int n_tracks,
+                     const int64_t* timestamps, aria_alert_state* states, aria_alert_event* events, int event_cap, int* nevents);
+/* out[0] = the first CENTER column, out[1] = the first RIGHT column of rule 1. Host only, no handle. */
+int   aria_alert_zone_bounds(int width, int out[2]);
+/* Algorithmic bytes of one measurement call: the band's pixels read once (4 B) plus 16 B per source slot, per frame. */
+int64_t aria_alert_algorithmic_bytes(int width, int zone_top, int zone_bottom, int n_frames);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
