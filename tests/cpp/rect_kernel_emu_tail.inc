@@ -27,12 +27,16 @@ void emu_remap(const uint32_t* map, int dst_w, int dst_h, const uint8_t* src, in
     const int pitch = emu_map_pitch(dst_w);
     const int gx = (dst_w + RECT_TILE_W - 1) / RECT_TILE_W, gy = (dst_h + RECT_TILE_H - 1) / RECT_TILE_H;
     const int gz = (n_frames + group - 1) / group;
+    g_src = src; g_src_stride = src_stride; g_src_pitch = src_pitch; g_src_w = src_w; g_src_h = src_h; g_src_frames = n_frames;
     for (int z = 0; z < gz; z++) for (int y = 0; y < gy; y++) for (int x = 0; x < gx; x++) for (int t = 0; t < RECT_BLOCK; t++) {
         blockIdx.x = x; blockIdx.y = y; blockIdx.z = z; threadIdx.x = t;
         k_rect_remap(map, pitch, dst_w, dst_h, src, src_stride, src_pitch, src_w, src_h, rows_ok, n_frames, group, dst, dst_stride, dst_pitch,
                      (uint32_t)fill);
     }
+    g_src = nullptr;
 }
+// loads of emu_remap calls that left the source images since the last call of this function
+long emu_bad_loads() { const long n = g_bad_loads; g_bad_loads = 0; return n; }
 void emu_points(const double* cam, const void* kp_in, const int* counts, int64_t kp_stride, int n_frames, void* kp_out, int* err) {
     const RectCam c = emu_cam(cam);
     for (int f = 0; f < n_frames; f++) for (int64_t b = 0; b < (kp_stride + RECT_BLOCK - 1) / RECT_BLOCK; b++)

@@ -1,6 +1,13 @@
 """Rectification on the MI355X (aria_rect_*, kernels in aria_slam_amd/csrc/rectify.hip) against its definition, the NumPy
 restatement aria_slam_amd/rectify_ref.py: every map word, every pixel and every keypoint field is BITWISE equal. A
-difference in a map word or in an fp32 coordinate is a contraction or ordering bug, never a tolerance."""
+difference in a map word or in an fp32 coordinate is a contraction or ordering bug, never a tolerance.
+
+Shapes (a)-(e) are one calibration at one source size. The cases of rectify_cases.EDGE_CASES add what they leave out: both
+sides of every term of k_rect_remap's choice between its read forms, three frame groups with a short last one, rotations far
+from the identity with k3 != 0 and Z <= 0, sources down to 2x2, a destination narrower than a lane and the 2047 limit of the
+map word; tests/test_rectify_host.py asserts that each case reaches its branch. The same cases run through the kernel text
+compiled for the host in tests/test_rectify_kernel_emulation.py: a case that fails here and passes there is a difference in
+the device's arithmetic, one that fails in both is an indexing bug."""
 import os
 import sys
 
@@ -150,6 +157,115 @@ def test_points_equal_the_restatement(aria, torch_cuda, work):
         assert d_in.cpu().numpy().tobytes() == RC.ref_points(1, kp, bad).tobytes()
     finally:
         r.close()
+
+
+# ---- the read forms, the frame groups and the limits (rectify_cases.EDGE_CASES) ---------------------------------------------
+@pytest.fixture(scope="module", params=RC.DEVICE_CASES)
+def edge(request, aria, work):
+    case = RC.EDGE_CASES[request.param]
+    r = aria.HipRectifier(cameras=case.cam, new_K=case.new_K, src_size=case.src, dst_size=case.dst, fill=case.fill,
+                          stream=work.cuda_stream)
+    yield case, r
+    r.close()
+
+
+def _case_batch(torch, work, case, r, frames):
+    """The batch form on the case's layouts -> (images, True when no padding byte changed)."""
+    n = len(frames)
+    d_src = _dev(torch, work, case.src_buffer(frames))
+    d_dst = _full(torch, work, n * case.dst_stride, 0x5A)
+    r.remap_batch_device(d_src, n, d_dst, 0, case.src_stride, case.src_pitch, case.dst_stride, case.dst_pitch)
+    assert r.status() == 0
+    return case.images(d_dst.cpu().numpy(), n)
+
+
+def test_edge_case_map_equals_the_restatement(edge):
+    """k3 != 0, quarter turns and a camera that looks away (Z <= 0), 8x8 and 2x2 sources, ix = iy = 2045 with bit 31 set."""
+    case, r = edge
+    got = r.map(0)
+    print("%s: %d of %d words differ" % (case.name, int((got != case.map).sum()), got.size))
+    assert got.tobytes() == case.map.tobytes()
+    assert r.status() == 0
+
+
+def test_edge_case_remap_equals_the_restatement(torch_cuda, work, edge):
+    """Every frame of the case in one call (17 frames: blockIdx.z = 0, 1, 2 and a last group of one), then frame 8 and frame
+    16 -- the first of the second group and the lone one of the third -- in calls of their own, the blocking host form on the
+    last frame, and a call without frames."""
+    case, r = edge
+    img, pad_kept = _case_batch(torch_cuda, work, case, r, case.frames)
+    print("%s: %d of %d pixels differ" % (case.name, int((img != case.want).sum()), case.want.size))
+    assert img.tobytes() == case.want.tobytes()
+    assert pad_kept, "padding was written"
+    for f in sorted({8, 16} & set(range(case.n_frames))):
+        one, pad_kept = _case_batch(torch_cuda, work, case, r, case.frames[f:f + 1])
+        assert one.tobytes() == img[f:f + 1].tobytes() and pad_kept, f
+    last = case.n_frames - 1
+    assert r.remap(case.frames[last], 0).tobytes() == img[last].tobytes()
+    d_src = _dev(torch_cuda, work, case.src_buffer(case.frames[:1]))
+    d_dst = _full(torch_cuda, work, case.dst_stride, 0x5A)
+    r.remap_batch_device(d_src, 0, d_dst, 0, case.src_stride, case.src_pitch, case.dst_stride, case.dst_pitch)
+    assert r.status() == 0 and bool((d_dst == 0x5A).all()), "a call without frames wrote"
+
+
+def test_edge_case_refuses_bad_layouts_before_a_launch(aria, torch_cuda, work, edge):
+    """ARIA_E_INVALID, nothing enqueued and the destination untouched: a source or destination pitch below the width, a source
+    pitch above 2^19, a stride that lets two frames overlap, a camera the handle does not have."""
+    case, r = edge
+    (sw, sh), (dw, dh) = case.src, case.dst
+    d_src = _dev(torch_cuda, work, case.src_buffer(case.frames[:2] if case.n_frames > 1 else np.repeat(case.frames, 2, axis=0)))
+    d_dst = _full(torch_cuda, work, 2 * case.dst_stride, 0x5A)
+    good = dict(cam=0, src_stride=case.src_stride, src_pitch=case.src_pitch, dst_stride=case.dst_stride, dst_pitch=case.dst_pitch)
+    bad = [dict(src_pitch=sw - 1), dict(src_pitch=(1 << 19) + 1), dict(dst_pitch=dw - 1),
+           dict(src_stride=case.src_pitch * (sh - 1) + sw - 1), dict(dst_stride=case.dst_pitch * (dh - 1) + dw - 1),
+           dict(cam=1), dict(cam=-1)]
+    for kw in bad:
+        with pytest.raises(aria.AriaError) as e:
+            r.remap_batch_device(d_src, 2, d_dst, **dict(good, **kw))
+        assert e.value.status == -1, kw
+    with pytest.raises(aria.AriaError) as e:
+        r.remap_batch_device(d_src, -1, d_dst, **good)
+    assert e.value.status == -1
+    with pytest.raises(aria.AriaError) as e:
+        r.remap(case.frames[0], 1)
+    assert e.value.status == -1
+    assert r.status() == 0 and bool((d_dst == 0x5A).all()), "a refused call wrote"
+
+
+def test_edge_points_equal_the_restatement(aria, torch_cuda, work):
+    """NaN, infinite and huge keypoints and keypoints far outside the image, through an identity camera and two that look away
+    (Ry(75), Ry(-100): Z <= 0 for about half the records): (-1, -1) wherever the restatement says so and nowhere else, out of
+    place and in place, the host form; counts of (-1, 300) skip frame 0, leave its records as they are and report once."""
+    torch = torch_cuda
+    kp, counts = RC.edge_keypoints(), RC.POINT_COUNTS
+    for name, cam in RC.point_cameras():
+        want = RC.ref_edge_points_all()[name][0]
+        r = aria.HipRectifier(cameras=cam, new_K=cam["K"], src_size=RC.SIZE, stream=work.cuda_stream)
+        try:
+            d_in, d_n = _dev(torch, work, kp), _dev(torch, work, counts)
+            d_out = _full(torch, work, kp.nbytes, 0x5A)
+            r.points_batch_device(d_in, d_n, RC.KP_STRIDE, 2, d_out)
+            assert r.status() == 0
+            out = d_out.cpu().numpy().view(kp.dtype).reshape(kp.shape)
+            for f, n in enumerate(counts):
+                gone = (want[f, :n]["x"] == -1) & (want[f, :n]["y"] == -1)
+                print("%s frame %d: %d of %d at (-1, -1), %d records differ" % (name, f, int(gone.sum()), n, int((out[f, :n] != want[f, :n]).sum())))
+                assert out[f, :n].tobytes() == want[f, :n].tobytes(), (name, f)
+                assert (out[f, n:].view(np.uint8) == 0x5A).all(), "records beyond the count were written"
+            r.points_batch_device(d_in, d_n, RC.KP_STRIDE, 2)                        # in place
+            assert r.status() == 0
+            assert d_in.cpu().numpy().tobytes() == want.tobytes(), name
+            assert r.points(kp[1]).tobytes() == want[1].tobytes(), name               # the host form
+            bad = np.array([-1, RC.KP_STRIDE], np.int32)
+            d_in, d_n = _dev(torch, work, kp), _dev(torch, work, bad)
+            r.points_batch_device(d_in, d_n, RC.KP_STRIDE, 2)
+            assert r.status() == -1                                                   # ARIA_E_INVALID, once
+            assert r.status() == 0
+            got = d_in.cpu().numpy().view(kp.dtype).reshape(kp.shape)
+            assert got[0].tobytes() == kp[0].tobytes(), "the skipped frame was written"
+            assert got.tobytes() == RC.ref_edge_points(cam, kp, bad).tobytes(), name
+        finally:
+            r.close()
 
 
 def test_chain_raw_pair_to_stereo_observations(aria, torch_cuda, work):

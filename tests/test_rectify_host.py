@@ -214,6 +214,85 @@ def test_small_shape_is_a_real_test_of_the_map():
         assert len(np.unique(m[ok] & 31)) == 32 and len(np.unique((m[ok] >> 16) & 31)) == 32
 
 
+def test_read_forms_on_hand_made_lanes():
+    """read_forms against lanes written by hand: the span bounds (x-span 6 and y-span 1 are the last of the rows form), the
+    right-edge term, the padded tail lane, a lane without a valid pixel."""
+    from aria_slam_amd import rectify_ref as R
+    w = lambda ix, iy: np.uint32((ix << 5) | (iy << 21) | 9)   # noqa: E731
+    X = np.uint32(R.INVALID)
+    m = np.array([[w(10, 5), w(12, 5), w(14, 6), w(16, 5),   w(10, 5), w(12, 5), w(14, 5), w(17, 5),   w(3, 7), X],
+                  [w(10, 5), w(10, 6), w(10, 7), w(10, 5),   X, X, X, X,                               w(25, 0), w(24, 1)],
+                  [w(24, 9), X, w(30, 9), X,                 w(25, 9), w(31, 9), w(25, 9), w(25, 9),   X, X]], np.uint32)
+    f = RC.read_forms(m, 32)
+    assert f["form"].tolist() == [[RC.ROWS, RC.TAPS, RC.ROWS], [RC.TAPS, RC.NONE, RC.ROWS], [RC.ROWS, RC.TAPS, RC.NONE]]
+    assert f["xspan"].tolist() == [[6, 7, 0], [0, -1, 1], [6, 6, -1]] and f["yspan"].tolist() == [[1, 0, 0], [2, -1, 1], [0, 0, -1]]
+    assert f["edge_only"].tolist() == [[False, False, False], [False, False, False], [False, True, False]]
+    assert f["mixed"].tolist() == [[False, False, True], [False, False, True], [True, False, False]]   # the padded tail counts
+    assert f["x0"][0, 0] == 10 and f["y0"][0, 0] == 5 and f["x0"][1, 2] == 24 and f["y0"][1, 2] == 0
+    assert RC.read_forms(m, 33)["form"][2, 1] == RC.ROWS                  # one more source column: x0 + 7 is inside
+
+
+def test_edge_cases_reach_their_branches():
+    """What each case of rectify_cases.EDGE_CASES is for, asserted on the restatement's map with slack, so that a change of
+    the inputs cannot silently empty a branch. The figures seen are in DESIGN.md section 19."""
+    from aria_slam_amd import rectify_ref as R
+    n = {name: RC.form_counts(c) for name, c in RC.EDGE_CASES.items()}
+    for name, c in n.items():
+        print(name, c)
+    c = n["zoom45"]                                                        # both sides of the x-span bound
+    assert c["xspan6"] >= 20 and c["xspan7"] >= 10 and c["rows"] >= 100 and c["mixed"] >= 10 and c["edge_only"] >= 10
+    c = n["zoom20"]
+    assert c["xspan_max"] >= 12 and c["yspan2"] >= 1 and c["rows"] >= 20 and c["taps"] >= 20
+    c = n["roll20"]                                                        # both sides of the y-span bound, the + 64 shift
+    assert c["yspan1"] >= 100 and c["yspan2"] >= 50 and c["low_pair"] >= 100
+    c = n["roll90"]
+    assert c["rows"] == 0 and c["taps"] == c["lanes"] and c["yspan_max"] >= 2 and c["invalid_share"] < 0.02
+    c = n["yaw75"]
+    Z = R.source_coords(RC.EDGE_CASES["yaw75"].cam, RC.EDGE_CASES["yaw75"].new_K, 41, 33)[2]
+    assert (Z <= 0).sum() >= 100 and c["rows"] >= 20 and c["taps"] >= 20
+    c = n["src8"]
+    assert c["taps"] >= 1 and c["rows"] == 0 and c["edge_only"] == c["taps"]
+    c = n["src2"]
+    assert (RC.EDGE_CASES["src2"].map != R.INVALID).sum() >= 1 and c["lanes"] == 1 and RC.EDGE_CASES["src2"].dst[0] < 4
+    assert sum(n[k]["mixed_rows"] for k in RC.DEVICE_CASES) >= 50          # valid and invalid pixels in one rows-form lane
+    # the lower-row clamp: a rows-form lane whose taps all lie in row src_h - 2, so that row y0 + 2 would be below the image
+    assert n["zoom45"]["last_row"] + n["roll20"]["last_row"] >= 5 and n["limits"]["last_row"] >= 100
+    # the limits of the 11 + 5 bit packing
+    m = RC.EDGE_CASES["limits"].map
+    ok = m != R.INVALID
+    ix, iy = (m & 0xFFFF) >> 5, m >> 21
+    assert RC.EDGE_CASES["limits"].src == (R.MAX_DIM, R.MAX_DIM) == (2047, 2047)
+    assert (ix[ok] == 2045).any() and (iy[ok] == 2045).any() and ((m[ok] >> 31) == 1).any()
+    assert ok[:23, :2046].all() and not ok[:, 2046].any() and not ok[23].any()   # one pixel further is invalid
+    assert n["limits"]["rows"] >= 1000 and n["limits"]["edge_only"] >= 20
+    # the variants' LDS form: tiles that are staged and tiles that are not
+    box = RC.tile_box_bytes(RC.EDGE_CASES["zoom20_big"].map)
+    assert (box > RC.LDS_BYTES).any() and ((box > 0) & (box <= RC.LDS_BYTES)).any()
+    # the layouts: one tight case whose every row is stored by dwords, fill = 255 once, 17 frames = groups of 8, 8 and 1
+    tight = [c for c in RC.EDGE_CASES.values() if c.dst_pitch == c.dst[0]]
+    assert [c.name for c in tight] == ["roll90"] and tight[0].dst[0] % 4 == 0 and tight[0].src_pitch == tight[0].src[0]
+    assert sorted(c.fill for c in RC.EDGE_CASES.values()).count(255) == 1
+    assert all(c.dst_pitch % 2 == 1 and c.src_pitch > c.src[0] for c in RC.EDGE_CASES.values() if c not in tight)
+    assert all(RC.EDGE_CASES[k].n_frames == 17 for k in RC.DEVICE_CASES if k != "limits")
+    for c in RC.EDGE_CASES.values():                                       # noise: a wrong tap shows
+        assert len(np.unique(c.frames)) == 256 or c.frames.size < 4096
+
+
+def test_edge_points_reach_both_outcomes():
+    """The points cases: the four non-finite records give (-1, -1) on the identity camera and nothing else does; each rotated
+    camera has at least 50 records at (-1, -1) by Z <= 0 and at least 50 finite ones. Nothing written is NaN or infinite."""
+    n = RC.POINT_COUNTS[0]
+    for name, (want, behind) in RC.ref_edge_points_all().items():
+        gone = (want[0, :n]["x"] == -1) & (want[0, :n]["y"] == -1)
+        print(name, int(gone.sum()), "at (-1, -1),", int((gone & behind).sum()), "by Z <= 0")
+        assert np.isfinite(want["x"]).all() and np.isfinite(want["y"]).all()
+        assert gone[RC.POINT_NONFINITE].all() and (gone | ~behind).all()
+        if name == "identity":
+            assert np.nonzero(gone)[0].tolist() == RC.POINT_NONFINITE
+        else:
+            assert (gone & behind).sum() >= 50 and (~gone).sum() >= 50
+
+
 def test_load_sensor_yaml(aria, tmp_path):
     p = str(tmp_path / "sensor.yaml")
     RC.write_sensor_yaml(p, RC.K_R, RC.D_R, RC.T_BS_R)

@@ -11,6 +11,9 @@ in the same process and alternating, each checked bitwise against the shipped fo
   read form     the shipped three 8-byte row loads per lane against two unaligned 16-bit global loads per pixel
                 (ARIA_RECT_READ=taps) and against the LDS-staged bounding box (ARIA_RECT_READ=lds)
 
+This comparison is against the shipped form's output on this tool's own shapes; that every form equals the restatement on the
+cases that reach each read form, frame group and limit is tools/rect_check.py (tests/test_gpu_rectify_variants.py).
+
 Usage: rect_rate.py [--images 4096] [--shapes 752x480,640x480] [--reps 10] [--groups 1] [--no-ab]"""
 import argparse
 import json
