@@ -91,6 +91,9 @@ EXPORTS = [
     "aria_alert_default_config", "aria_alert_create", "aria_alert_destroy", "aria_alert_stream", "aria_alert_check",
     "aria_alert_dets_seen", "aria_alert_measure_batch_device", "aria_alert_arbitrate_batch_device", "aria_alert_run_batch_device",
     "aria_alert_measure", "aria_alert_arbitrate", "aria_alert_run", "aria_alert_zone_bounds", "aria_alert_algorithmic_bytes",
+    # absolute pose from the point map (6-point DLT RANSAC + Gauss-Newton, map association), additive to ABI 4
+    "aria_pnp_default_config", "aria_pnp_create", "aria_pnp_destroy", "aria_pnp_stream", "aria_pnp_check",
+    "aria_pnp_estimate", "aria_pnp_estimate_batch_device", "aria_pnp_debug_hypotheses", "aria_pnp_associate_batch_device",
 ]
 
 
@@ -115,6 +118,18 @@ class PoseConfig(C.Structure):
 POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,)), ("n_matches", "<i4"),
                               ("n_inliers", "<i4"), ("n_pose_inliers", "<i4"), ("best_hypothesis", "<i4"),
                               ("refined", "<i4"), ("valid", "<i4")])
+
+
+class PnpConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("hypotheses", C.c_int),
+                ("refine_iters", C.c_int), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("threshold_px", C.c_double), ("seed", C.c_uint64)]
+
+
+# aria_pnp_corr (32 bytes) and aria_pnp_result (128 bytes)
+PNP_CORR_DTYPE = np.dtype([("X", "<f8", (3,)), ("u", "<f4"), ("v", "<f4")])
+PNP_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("rms_px", "<f8"), ("n_corr", "<i4"), ("n_inliers", "<i4"),
+                             ("best_hypothesis", "<i4"), ("iterations", "<i4"), ("refined", "<i4"), ("valid", "<i4")])
 
 
 class FundConfig(C.Structure):
@@ -498,6 +513,8 @@ def load_library():
         _bind_nav(L)
     if hasattr(L, "aria_alert_create"):
         _bind_alert(L)
+    if hasattr(L, "aria_pnp_create"):
+        _bind_pnp(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -682,6 +699,15 @@ def _bind_alert(L):
     L.aria_alert_zone_bounds.argtypes = [i, p]
     L.aria_alert_algorithmic_bytes.restype = i64
     L.aria_alert_algorithmic_bytes.argtypes = [i, i, i, i]
+
+
+def _bind_pnp(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "pnp")
+    L.aria_pnp_estimate.argtypes = [p, p, i, i, p, p]
+    L.aria_pnp_estimate_batch_device.argtypes = [p, p, p, i, i, i, p, p]
+    L.aria_pnp_debug_hypotheses.argtypes = [p, p, i, i, p, p, p, p]
+    L.aria_pnp_associate_batch_device.argtypes = [p, p, i, i, p, p, i64, p, p, i, i, p, p, p]
 
 
 def status_string(status):

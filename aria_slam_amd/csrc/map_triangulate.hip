@@ -753,3 +753,13 @@ int aria_map_filter_distance(aria_map_t h, double max_distance) {
 }
 
 }  // extern "C"
+
+// Internal (stage_handle.h): what aria_pnp_associate_batch_device reads of the map without a host round trip.
+namespace aria {
+void map_device_view(aria_map_t h, const aria_map_point** arena, const long long** d_size, int64_t* capacity, int* device) {
+    *arena = h->d_arena;
+    *d_size = h->d_meta + META_SIZE;
+    *capacity = h->capacity;
+    *device = h->device;
+}
+}  // namespace aria

@@ -1,5 +1,5 @@
-// Host side of what the thirteen stage handles (aria_pose_t, aria_fund_t, aria_map_t, aria_graph_t, aria_fuse_t, aria_eval_t,
-// aria_det_t, aria_stereo_t, aria_rect_t, aria_dense_t, aria_tsdf_t, aria_nav_t, aria_alert_t) share: the lifecycle of device, stream and deferred-error words, grow-only device buffers, and
+// Host side of what the fourteen stage handles (aria_pose_t, aria_fund_t, aria_map_t, aria_graph_t, aria_fuse_t, aria_eval_t,
+// aria_det_t, aria_stereo_t, aria_rect_t, aria_dense_t, aria_tsdf_t, aria_nav_t, aria_alert_t, aria_pnp_t) share: the lifecycle of device, stream and deferred-error words, grow-only device buffers, and
 // the single-pair staging of the blocking host forms that take a match list. Header-only; not part of the public interface.
 #pragma once
 #include <algorithm>
@@ -145,5 +145,10 @@ struct PairStaging {
         return rc != ARIA_OK ? rc : copy(st, kq, nq, kt, nt, matches, n);
     }
 };
+
+// The map handle's arena, the device word that holds its size, its capacity and its device (map_triangulate.hip): the
+// association kernels of the absolute pose stage read the map where it lies. The arena pointer is the one current at the
+// call: a reserve, a growth or a filter of the map after it moves the points elsewhere.
+void map_device_view(aria_map_t h, const aria_map_point** arena, const long long** d_size, int64_t* capacity, int* device);
 
 }  // namespace aria

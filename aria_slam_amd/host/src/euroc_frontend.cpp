@@ -1,5 +1,5 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
-//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply]
+//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
 //                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--alerts FILE]
 //
@@ -33,6 +33,12 @@
 // current_pose as world-to-camera extrinsics and the previous image for colour; at the end filterOutliers, then the PLY
 // export, and "map N points -> FILE" is printed. The composition current_pose * delta is the reference's and is not
 // geometrically consistent after the first pair; the batch form with pose records is.
+// --track-map FILE2 (needs --pose): the trajectory and a map of its own in one frame and one scale (aria_hip/MapTracker.hpp,
+// DESIGN.md section 24). The first accepted pair is bootstrapped by the pose stage at unit baseline and triangulated; each
+// later frame is placed by PnP on the device against the points of the previous pair; a frame for which PnP finds no pose, or
+// one with n_inliers <= 10, falls back to the pose stage's delta; the new pair is triangulated with the two extrinsics.
+// FILE2 gets one TUM line per frame (world-to-camera poses), and "track pnp A fallback B bootstrap C held D map N -> FILE2"
+// is printed. --pose FILE, --map and the CSV are byte-identical with and without it.
 //
 // --loop-verify reference (needs --loop): a loop candidate is accepted as LoopClosureDetector accepts it -- F-RANSAC on its
 // ratio-0.7 list, then E-RANSAC + recoverPose on the F inliers with computeRelativePose's K (aria_hip/
@@ -143,6 +149,7 @@
 #include "aria_hip/HipFundamentalEstimator.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
+#include "aria_hip/MapTracker.hpp"
 #include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/HipPathPlanner.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
@@ -184,7 +191,7 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--alerts file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--alerts file]\n"
                              "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
                              "  --plan file: a path over the --volume map from the cell under the first camera of the --pose chain to the cell under the last\n"
                              "               (needs --volume): one x y z line per path cell\n"
@@ -203,7 +210,7 @@ int main(int argc, char** argv) {
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
-    std::string csv, pose_file, map_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
+    std::string csv, pose_file, map_file, track_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
@@ -219,6 +226,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--decode-threads") && i + 1 < argc) decode_threads = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--pose") && i + 1 < argc) pose_file = argv[++i];
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--track-map") && i + 1 < argc) track_file = argv[++i];
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
         else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
         else if (!std::strcmp(argv[i], "--fuse") && i + 1 < argc) fuse_file = argv[++i];
@@ -256,6 +264,10 @@ int main(int argc, char** argv) {
                           : eval_align == "sim3" ? ARIA_EVAL_ALIGN_SIM3 : -1;
     if (!eval_file.empty() && (pose_file.empty() || eval_mode < 0 || rpe_delta < 1)) {
         std::fprintf(stderr, "--eval needs --pose, --eval-align none|se3|sim3 and --rpe-delta >= 1\n");
+        return 1;
+    }
+    if (!track_file.empty() && pose_file.empty()) {
+        std::fprintf(stderr, "--track-map needs --pose (it bootstraps from, and falls back to, the pose stage)\n");
         return 1;
     }
     if (!map_file.empty() && pose_file.empty()) {
@@ -353,6 +365,10 @@ int main(int argc, char** argv) {
     // --fuse: the visual record of every frame (euroc_eval.cpp:209), filled where the pose is accepted
     std::vector<aria_fuse_visual> fuse_visual(fuse_file.empty() ? 0 : N);
     std::size_t map_points = 0;
+    // --track-map: world-to-camera pose per frame, and how each step was made (TrackStep::Source)
+    std::vector<std::array<double, 16>> track_traj(track_file.empty() ? 0 : N);
+    long long track_steps[4] = {0, 0, 0, 0};
+    std::size_t track_points = 0;
     long long volume_points = 0, volume_observed = 0;   // --volume
     long long alert_events = 0, alert_frames = 0;       // --alerts
     std::vector<std::string> alert_lines;
@@ -442,6 +458,13 @@ int main(int argc, char** argv) {
                 mc.device = fc.hip_device;
                 if (rectifier) mc.K = new_K;
                 mapper = std::make_unique<adapters::hip::HipMapper>(mc);
+            }
+            std::unique_ptr<adapters::hip::MapTracker> tracker;         // --track-map
+            if (!track_file.empty()) {
+                adapters::hip::MapperConfig mc;
+                mc.device = fc.hip_device;
+                if (rectifier) mc.K = new_K;
+                tracker = std::make_unique<adapters::hip::MapTracker>(mc);
             }
             // --stereo: the right image has an extractor of its own; the observations of the previous frame stay for the scale
             std::unique_ptr<adapters::hip::OrbHipExtractor> right_extractor;
@@ -568,6 +591,10 @@ int main(int argc, char** argv) {
                     traj[i] = current_pose;
                     if (graph && last_vertex[i] < 0 && i > 0) last_vertex[i] = last_vertex[i - 1];
                 }
+                if (tracker) {                                             // view 1 = previous frame: the query side in the legacy order
+                    if (r.previous) track_steps[tracker->track(*r.previous, *r.frame, r.matches, fc.frontend.legacy_order, r.pose).source]++;
+                    track_traj[i] = tracker->pose();
+                }
                 if (mapper) { prev_gray.swap(gray); pw = fw; ph = fh; }
                 FrameRecord& o = rec[i];
                 o.keypoints = r.frame->numKeypoints();
@@ -590,6 +617,7 @@ int main(int argc, char** argv) {
                 mapper->exportPLY(map_file);
                 map_points = mapper->size();
             }
+            if (tracker) track_points = tracker->mapper().size();
             if (volume) {
                 volume_points = (long long)volume->exportPLY(volume_file);
                 volume_observed = (long long)volume->observedVoxels();
@@ -788,6 +816,11 @@ int main(int argc, char** argv) {
                     gr.pcg_iterations, optimize_file.c_str());
     }
     if (!map_file.empty()) std::printf("map %zu points -> %s\n", map_points, map_file.c_str());
+    if (!track_file.empty()) {
+        write_tum(track_file, [&](std::size_t i) { return track_traj[i]; });
+        std::printf("track pnp %lld fallback %lld bootstrap %lld held %lld map %zu -> %s\n", track_steps[2], track_steps[3],
+                    track_steps[1], track_steps[0], track_points, track_file.c_str());
+    }
     if (stereo) {
         std::ofstream sf;
         if (!stereo_file.empty()) sf.open(stereo_file);

@@ -1690,6 +1690,109 @@ int   aria_alert_zone_bounds(int width, int out[2]);
 /* Algorithmic bytes of one measurement call: the band's pixels read once (4 B) plus 16 B per source slot, per frame. */
 int64_t aria_alert_algorithmic_bytes(int width, int zone_top, int zone_bottom, int n_frames);
 
+/* ---- absolute pose from the point map: a camera pose from 3D-2D correspondences (PnP RANSAC), the step that places a
+ * frame in the frame and scale of the map that aria_map_* keeps in HBM -- the two-view stage above fixes |t| = 1 per pair,
+ * so chained deltas agree with the map only for the first pair. The reference has no PnP code (its notes name the method:
+ * docs/milestones/H04_POSE_ESTIMATION_AUDIT.md section 8); aria_slam_amd/pnp_ref.py is the definition, and parity with
+ * OpenCV's solvePnPRansac is not claimed. Batched over pairs; additive to ABI 4.
+ *
+ * Pose. x_cam = R X + t, world to camera, the map stage's convention; R row-major.
+ * Points. x = (u - cx) / fx, y = (v - cy) / fy in fp64. For scoring a pair's points are taken relative to its first
+ *   correspondence's X0: d = X - X0 in fp64, rounded to fp32, and (x, y) rounded to fp32 -- a map far from the origin
+ *   loses nothing in fp32. A pose is scored as (R, t0 = R X0 + t) rounded to fp32. A correspondence with a scoring value
+ *   that is not finite or beyond 1e15 in magnitude never scores; a pose with |t0| beyond 1e15 is invalid (so that every
+ *   square of the test below stays finite).
+ * Hypotheses. `hypotheses` per pair; the hash of the two-view stage with 6 distinct indices per hypothesis (slots
+ *   j = 0..5, at most 256 draws per slot). Results depend on (seed, pair id, correspondences) only.
+ * Minimal solver. 6-point DLT, one model per sample, fp64. Conditioning in sample order: c = mean of the six X, s = mean
+ *   of |X - c| (invalid when s is 0 or not finite), Xh = ((X - c) / s, 1). Rows [Xh, 0, -x Xh] and [0, Xh, -y Xh]; 11 of
+ *   the 12 are taken: both rows of sample points 0..4 and the x-row of point 5. Gaussian elimination with partial pivoting
+ *   (first row of largest |a|); a pivot with |pivot| <= 1e-9 * max|A_ij| marks the sample invalid. Back substitution with
+ *   p11 = 1: after the conditioning p11 is proportional to the depth of the sample's centroid, positive for points in
+ *   front of the camera. P = [M | m]; invalid when det M <= 0. M = U S V^T (V from the 3x3 Jacobi of the two-view stage
+ *   on M^T M, u_i = M v_i / sigma_i, third columns as cross products); invalid when sigma3 <= 1e-9 sigma1. R = U V^T,
+ *   lambda = (s1 + s2 + s3) / 3, t' = m / lambda, t = s t' - R c.
+ * Inliers. In fp32 and division-free: Xc = R d + t0, each component ((r0 dx + r1 dy) + r2 dz) + t0; a point is an inlier
+ *   when Xc.z > 0 and (Xc.x - x Xc.z)^2 + (Xc.y - y Xc.z)^2 <= thr2 * Xc.z^2, thr2 = (threshold_px / ((fx + fy) / 2))^2.
+ * Winner. Most inliers; ties to the lowest h; an invalid hypothesis scores -1. Integer counts, fixed reduction order.
+ * Refinement. When the winner has >= 6 inliers and refine_iters > 0: up to refine_iters Gauss-Newton steps in fp64 on the
+ *   normalised reprojection residuals (Xc.x / Xc.z - x, Xc.y / Xc.z - y), Xc = R (X - X0) + t0, over the winner's inlier
+ *   set, which is not re-evaluated between steps. It starts from the winner as scored, R replaced by the nearest rotation
+ *   (the same U V^T). The update is left-multiplicative: R <- Exp(w) R, t0 <- Exp(w) t0 + v. The 21 + 6 entries of the
+ *   normal equations are summed in a fixed order (per thread over its strided share of the correspondences, then a fixed
+ *   tree); the 6x6 system is solved by Cholesky in one lane; a pivot that is not positive, or a step that is not finite,
+ *   ends the refinement with the last good pose. It stops early when |(w, v)| <= 1e-12. `iterations` is the number of steps
+ *   taken. The refined pose is rescored in fp32 and kept (refined = 1) when its count is >= the winner's; otherwise the
+ *   result is the winner as scored.
+ * Outputs. The mask and n_inliers are those of the kept pose; t = t0 - R X0; rms_px is the RMS of the residuals above
+ *   over them, in fp64 in a fixed order, times (fx + fy) / 2.
+ * Validity. valid = 0 with fewer than 6 correspondences, with no valid hypothesis, or when a result field would not be
+ *   finite: R = I, t = 0, counts 0, best_hypothesis = -1, zero mask. No field is ever NaN or Inf.
+ * Determinism. No float atomics; bitwise reproducible run to run and independent of how pairs are split into calls.
+ * Known limit. A 6-point DLT is degenerate on a planar sample: every pivot test fails on a planar scene, which yields
+ *   valid = 0. A P3P minimal solver is the follow-up. */
+typedef struct aria_pnp_s* aria_pnp_t;
+typedef struct {
+    double X[3];               /* world point                                                                    */
+    float  u, v;               /* pixel                                                                          */
+} aria_pnp_corr;               /* 32 bytes                                                                       */
+typedef struct {
+    double R[9], t[3];         /* x_cam = R X + t                                                                */
+    double rms_px;             /* RMS reprojection error of the final inliers                                    */
+    int    n_corr, n_inliers, best_hypothesis, iterations, refined, valid;
+} aria_pnp_result;             /* 128 bytes                                                                      */
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_pnp_config)                                                     */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle owns one (non-blocking: NOT ordered against
+                                * the legacy default stream, see aria_pose_config)                               */
+    int      hypotheses;       /* per pair: multiple of 64, 64..16384 (default 1024)                            */
+    int      refine_iters;     /* 0..16 (default 5)                                                              */
+    double   fx, fy, cx, cy;   /* intrinsics (default EuRoC cam0)                                                */
+    double   threshold_px;     /* default 2.0: the map stage's max_reproj_px, the error a map point was admitted with */
+    uint64_t seed;             /* sample hash seed (default 0)                                                   */
+} aria_pnp_config;
+
+void  aria_pnp_default_config(aria_pnp_config* cfg);
+int   aria_pnp_create(const aria_pnp_config* cfg, aria_pnp_t* out);
+void  aria_pnp_destroy(aria_pnp_t h);
+void* aria_pnp_stream(aria_pnp_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check:
+ * ARIA_E_INVALID when some pair's count was outside [0, corr_cap] (estimate) or its counts or match indices were out of
+ * range (associate). Such a pair is detected before any of its data is read and skipped (n_corr = 0, valid = 0, zero
+ * mask; no correspondences); the other pairs are unaffected. */
+int   aria_pnp_check(aria_pnp_t h);
+/* One pair, host buffers; blocks. pair_base is the pair id the sample hash uses. mask (optional): n bytes. */
+int   aria_pnp_estimate(aria_pnp_t h, const aria_pnp_corr* corr, int n, int pair_base, aria_pnp_result* out, uint8_t* mask);
+/* Device-resident batch form: pair p reads d_ncorr[p] correspondences at d_corr + p*corr_cap, writes d_out[p] and, if
+ * d_mask is not NULL, corr_cap bytes at d_mask + p*corr_cap (zero beyond the pair's correspondences). The sample hash
+ * sees pair id pair_base + p. Enqueued on the handle's stream; nothing is synchronised, except when the workspace grows. */
+int   aria_pnp_estimate_batch_device(aria_pnp_t h, const aria_pnp_corr* d_corr, const int* d_ncorr, int n_pairs, int corr_cap,
+                                     int pair_base, aria_pnp_result* d_out, uint8_t* d_mask);
+/* Test hook: for one pair (host buffers), every hypothesis's 6 sample indices (sample_idx[h*6 + j]; -1 when n < 6), R
+ * (R[h*9 + k]) and t0 (t0[h*3 + k]) in fp32 as scored (zero when invalid) and inlier count (counts[h], -1 when invalid). */
+int   aria_pnp_debug_hypotheses(aria_pnp_t h, const aria_pnp_corr* corr, int n, int pair_base, int* sample_idx, float* R,
+                                float* t0, int* counts);
+/* The join that keeps the chain device-resident: correspondences of n_pairs tracked pairs against the map's arena, read
+ * with its device-resident size, no host round trip. For pair p the map points used are those with pair == anchor_base + p;
+ * anchor_view (1 or 2) says whether their idx1 or idx2 indexes the anchor frame, the train side of pair p's matches
+ * (d_matches + p*match_cap, d_nmatches[p] of them; the query keypoints at d_kp_query + p*kp_stride, d_nq[p] of them).
+ * Match m yields a correspondence -- X of the map point, the pixel of kp_query[m.query_idx] -- when such a point has that
+ * index equal to m.train_idx; of several such points the one at the lowest arena position is taken. Correspondences are
+ * written in match order, stably compacted, at d_corr + p*match_cap, their number at d_ncorr[p]; d_corr_match (optional)
+ * receives each correspondence's match index at d_corr_match + p*match_cap, so a mask can be carried back. The result
+ * is the input of aria_pnp_estimate_batch_device with corr_cap = match_cap. A count outside [0, match_cap] or
+ * [0, kp_stride], a query_idx outside [0, d_nq[p]) or a train_idx outside [0, kp_stride) is a deferred error of the pair
+ * (d_ncorr[p] = 0). Enqueued on the handle's stream, which must be ordered after the work that filled the map: the call takes
+ * the arena's address as it is when called, so a reserve, a growth or a filter of the map between this call and its
+ * completion is the caller's error (create both handles on one stream, or check the map first). A map on another device
+ * than the handle's: ARIA_E_INVALID. Cost: the call clears and fills a table of n_pairs * kp_stride ints, so kp_stride
+ * should be the keypoint capacity, not a generous bound (at most 2^24). */
+int   aria_pnp_associate_batch_device(aria_pnp_t h, aria_map_t map, int anchor_base, int anchor_view,
+                                      const aria_keypoint* d_kp_query, const int* d_nq, int64_t kp_stride,
+                                      const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
+                                      aria_pnp_corr* d_corr, int* d_ncorr, int* d_corr_match);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
