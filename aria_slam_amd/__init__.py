@@ -17,6 +17,7 @@ from .fundamental import HipFundamentalEstimator, verify_loop_candidates
 from .mapper import HipMapper
 from .nav import HipPathPlanner
 from .pnp import HipPnPEstimator
+from .bundle import HipBundleAdjuster
 from .pose import HipPoseEstimator
 from .posegraph import HipPoseGraphOptimizer
 from .rectify import HipRectifier, load_sensor_yaml
@@ -27,4 +28,4 @@ __all__ = ["KP_DTYPE", "MATCH_DTYPE", "AriaError", "abi_version", "build_library
            "status_string", "level_info", "resize_table", "algorithmic_bytes", "synth_frame_pair", "synth_sequence", "HipMatcher", "OrbHipExtractor", "flag_keypoints_device",
            "HipPoseEstimator", "HipMapper", "HipFundamentalEstimator", "verify_loop_candidates", "HipPoseGraphOptimizer",
            "HipSensorFusion", "HipImuPreintegrator", "HipTrajectoryEvaluator", "load_ground_truth_csv", "HipObjectDetector",
-           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner", "HipObstacleAlerter", "HipPnPEstimator"]
+           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner", "HipObstacleAlerter", "HipPnPEstimator", "HipBundleAdjuster"]

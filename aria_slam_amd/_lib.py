@@ -94,6 +94,9 @@ EXPORTS = [
     # absolute pose from the point map (6-point DLT RANSAC + Gauss-Newton, map association), additive to ABI 4
     "aria_pnp_default_config", "aria_pnp_create", "aria_pnp_destroy", "aria_pnp_stream", "aria_pnp_check",
     "aria_pnp_estimate", "aria_pnp_estimate_batch_device", "aria_pnp_debug_hypotheses", "aria_pnp_associate_batch_device",
+    # local bundle adjustment (batched windows, Schur-complement LM over poses and points), additive to ABI 4
+    "aria_ba_default_config", "aria_ba_create", "aria_ba_destroy", "aria_ba_stream", "aria_ba_check",
+    "aria_ba_optimize", "aria_ba_optimize_batch_device", "aria_ba_debug_linearize", "aria_ba_window_from_chain_device",
 ]
 
 
@@ -130,6 +133,19 @@ class PnpConfig(C.Structure):
 PNP_CORR_DTYPE = np.dtype([("X", "<f8", (3,)), ("u", "<f4"), ("v", "<f4")])
 PNP_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("rms_px", "<f8"), ("n_corr", "<i4"), ("n_inliers", "<i4"),
                              ("best_hypothesis", "<i4"), ("iterations", "<i4"), ("refined", "<i4"), ("valid", "<i4")])
+
+
+class BaConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("huber_px", C.c_double), ("min_depth", C.c_double),
+                ("max_iterations", C.c_int), ("max_windows", C.c_int)]
+
+
+# aria_ba_obs (16 bytes) and aria_ba_result (56 bytes)
+BA_OBS_DTYPE = np.dtype([("point", "<i4"), ("pose", "<i4"), ("u", "<f4"), ("v", "<f4")])
+BA_RESULT_DTYPE = np.dtype([("chi2_initial", "<f8"), ("chi2_final", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8"),
+                            ("n_obs_used", "<i4"), ("iterations_done", "<i4"), ("trials", "<i4"), ("stop_reason", "<i4"),
+                            ("valid", "<i4"), ("reserved", "<i4")])
 
 
 class FundConfig(C.Structure):
@@ -515,6 +531,8 @@ def load_library():
         _bind_alert(L)
     if hasattr(L, "aria_pnp_create"):
         _bind_pnp(L)
+    if hasattr(L, "aria_ba_create"):
+        _bind_ba(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -699,6 +717,15 @@ def _bind_alert(L):
     L.aria_alert_zone_bounds.argtypes = [i, p]
     L.aria_alert_algorithmic_bytes.restype = i64
     L.aria_alert_algorithmic_bytes.argtypes = [i, i, i, i]
+
+
+def _bind_ba(L):
+    p, i, d = C.c_void_p, C.c_int, C.c_double
+    _bind_handle(L, "ba")
+    L.aria_ba_optimize.argtypes = [p, p, p, i, p, p, i, p, i, i, p, p]
+    L.aria_ba_optimize_batch_device.argtypes = [p, p, p, p, p, p, p, p, p, i, i, i, i, i, p, p]
+    L.aria_ba_debug_linearize.argtypes = [p, p, p, i, p, p, i, p, i, d, C.POINTER(d), C.POINTER(i), p, p, p, p]
+    L.aria_ba_window_from_chain_device.argtypes = [p, p, p, p, i, i, i, p, p, p, p, C.c_int64, p, p, i, i, i, i, p, p, p, p, p]
 
 
 def _bind_pnp(L):

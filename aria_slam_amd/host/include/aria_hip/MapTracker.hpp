@@ -10,6 +10,7 @@
 #include <optional>
 #include <vector>
 
+#include "aria_hip/HipBundleAdjuster.hpp"
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipPnPEstimator.hpp"
 #include "aria_hip/HipPoseEstimator.hpp"
@@ -36,6 +37,9 @@ public:
                     int width = 0, int height = 0);
     const std::array<double, 16>& pose() const { return pose_; }   // world to camera of the last frame, 4x4 row-major
     HipMapper& mapper() { return mapper_; }
+    // Every later step is also recorded in `builder` (nullptr: none): the frames, their poses, and which keypoint of the new
+    // frame continues which point, for the windows of HipBundleAdjuster. The builder must outlive the tracking.
+    void setWindowBuilder(WindowBuilder* builder) { builder_ = builder; }
 
 private:
     HipMapper mapper_;
@@ -45,6 +49,7 @@ private:
     bool bootstrapped_ = false;
     int anchor_pair_ = -1;              // pair id of the points whose view 2 is the last frame; -1: none
     int steps_ = 0;
+    WindowBuilder* builder_ = nullptr;
 };
 
 }  // namespace aria::adapters::hip

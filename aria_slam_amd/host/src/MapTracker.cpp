@@ -36,6 +36,8 @@ TrackStep MapTracker::track(const core::Frame& previous, const core::Frame& curr
         step.source = bootstrapped_ ? TrackStep::FALLBACK : TrackStep::BOOTSTRAP;
     }
     anchor_pair_ = -1;
+    std::vector<aria_map_point> appended;
+    if (builder_ && builder_->frames() == 0) builder_->addFrame(previous, before.data());
     if (step.source != TrackStep::HELD) {
         bootstrapped_ = true;
         std::int64_t size0 = 0;
@@ -47,8 +49,14 @@ TrackStep MapTracker::track(const core::Frame& previous, const core::Frame& curr
             aria_map_point first{};
             if ((rc = aria_map_read(mapper_.handle(), size0, 1, &first)) != ARIA_OK) throw std::runtime_error("MapTracker: aria_map_read failed");
             anchor_pair_ = first.pair;
+            if (builder_) {
+                appended.resize((std::size_t)step.added);
+                if ((rc = aria_map_read(mapper_.handle(), size0, step.added, appended.data())) != ARIA_OK)
+                    throw std::runtime_error("MapTracker: aria_map_read failed");
+            }
         }
     }
+    if (builder_) builder_->addStep(current, now.data(), matches, previous_is_query, appended);
     pose_ = now;
     return step;
 }

@@ -1,5 +1,5 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
-//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2]
+//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--bundle FILE3] [--bundle-window N]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
 //                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--alerts FILE]
 //
@@ -46,6 +46,12 @@
 // The loop step then runs over the merged stream as in the sharded mode, keeping the keypoints of the keyframes the
 // database holds. Keyframes are the default run's; the loops are a subset of its. Without the flag nothing changes.
 //
+// --bundle FILE3 [--bundle-window N] (needs --track-map): local bundle adjustment of the tracked trajectory, post hoc as
+// --optimize is (aria_hip/HipBundleAdjuster.hpp; the reference names the step, README.md:1162, and has no code for it). The
+// tracker's steps are recorded in a WindowBuilder; windows of N frames (default 10, at most 16) with stride N - 2 are adjusted
+// in order with their first two poses fixed -- two fixed poses remove the monocular gauge, scale included -- and a window's
+// refined poses and points seed the next. FILE3 gets one TUM line per frame and one trailing comment line per window with
+// chi2_initial, chi2_final and rms_px.
 // --optimize FILE (needs --pose, --loop and --loop-verify reference, so that accepted candidates carry relative_pose): the
 // pose graph of euroc_eval.cpp through aria_hip/HipPoseGraphOptimizer.hpp -- setInitialPose(frame, current_pose) and
 // addOdometryEdge(frame - 1, frame, delta) exactly where :211-215 adds them (after every accepted pose update; the first
@@ -149,6 +155,7 @@
 #include "aria_hip/HipFundamentalEstimator.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipMapper.hpp"
+#include "aria_hip/HipBundleAdjuster.hpp"
 #include "aria_hip/MapTracker.hpp"
 #include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/HipPathPlanner.hpp"
@@ -191,7 +198,7 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--alerts file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--alerts file]\n"
                              "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
                              "  --plan file: a path over the --volume map from the cell under the first camera of the --pose chain to the cell under the last\n"
                              "               (needs --volume): one x y z line per path cell\n"
@@ -204,12 +211,16 @@ int main(int argc, char** argv) {
                              "                       relative translations take the metric scale\n"
                              "  --eval file: ATE / RPE of the --pose (and --optimize, --fuse) trajectories against the sequence's ground truth (needs --pose)\n"
                              "  --fuse file: EKF visual-inertial fusion over imu0 and the --pose stage's relative poses (needs --pose), one TUM line per frame\n"
+                             "  --bundle file: local bundle adjustment of the --track-map trajectory in windows of --bundle-window N frames (default 10, at most 16),\n"
+                             "                 stride N - 2, the first two poses of a window fixed (needs --track-map)\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
                              "                   the per-loop optimize(10) and reset of current_pose of the reference are not reproduced (the loop step is post hoc)\n", argv[0]);
         return -1;                                                        // euroc_eval.cpp:64-70
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
     bool legacy = false, loop = false;
+    std::string bundle_file;
+    int bundle_window = 10;
     std::string csv, pose_file, map_file, track_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
@@ -227,6 +238,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pose") && i + 1 < argc) pose_file = argv[++i];
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
         else if (!std::strcmp(argv[i], "--track-map") && i + 1 < argc) track_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--bundle") && i + 1 < argc) bundle_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--bundle-window") && i + 1 < argc) bundle_window = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
         else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
         else if (!std::strcmp(argv[i], "--fuse") && i + 1 < argc) fuse_file = argv[++i];
@@ -268,6 +281,10 @@ int main(int argc, char** argv) {
     }
     if (!track_file.empty() && pose_file.empty()) {
         std::fprintf(stderr, "--track-map needs --pose (it bootstraps from, and falls back to, the pose stage)\n");
+        return 1;
+    }
+    if (!bundle_file.empty() && (track_file.empty() || bundle_window < 3 || bundle_window > ARIA_BA_MAX_POSES)) {
+        std::fprintf(stderr, "--bundle needs --track-map and --bundle-window 3..16\n");
         return 1;
     }
     if (!map_file.empty() && pose_file.empty()) {
@@ -369,6 +386,10 @@ int main(int argc, char** argv) {
     std::vector<std::array<double, 16>> track_traj(track_file.empty() ? 0 : N);
     long long track_steps[4] = {0, 0, 0, 0};
     std::size_t track_points = 0;
+    // --bundle: what the tracker did, step by step, and the sequence frame its first frame is
+    adapters::hip::WindowBuilder bundle_builder;
+    adapters::hip::PoseIntrinsics bundle_K;
+    long long bundle_first = -1;
     long long volume_points = 0, volume_observed = 0;   // --volume
     long long alert_events = 0, alert_frames = 0;       // --alerts
     std::vector<std::string> alert_lines;
@@ -465,6 +486,10 @@ int main(int argc, char** argv) {
                 mc.device = fc.hip_device;
                 if (rectifier) mc.K = new_K;
                 tracker = std::make_unique<adapters::hip::MapTracker>(mc);
+                if (!bundle_file.empty()) {
+                    tracker->setWindowBuilder(&bundle_builder);
+                    bundle_K = mc.K;
+                }
             }
             // --stereo: the right image has an extractor of its own; the observations of the previous frame stay for the scale
             std::unique_ptr<adapters::hip::OrbHipExtractor> right_extractor;
@@ -592,6 +617,7 @@ int main(int argc, char** argv) {
                     if (graph && last_vertex[i] < 0 && i > 0) last_vertex[i] = last_vertex[i - 1];
                 }
                 if (tracker) {                                             // view 1 = previous frame: the query side in the legacy order
+                    if (r.previous && bundle_first < 0) bundle_first = (long long)i - 1;
                     if (r.previous) track_steps[tracker->track(*r.previous, *r.frame, r.matches, fc.frontend.legacy_order, r.pose).source]++;
                     track_traj[i] = tracker->pose();
                 }
@@ -820,6 +846,36 @@ int main(int argc, char** argv) {
         write_tum(track_file, [&](std::size_t i) { return track_traj[i]; });
         std::printf("track pnp %lld fallback %lld bootstrap %lld held %lld map %zu -> %s\n", track_steps[2], track_steps[3],
                     track_steps[1], track_steps[0], track_points, track_file.c_str());
+    }
+    if (!bundle_file.empty()) {
+        // windows in order; a window's refined poses and points seed the next (WindowBuilder::store)
+        std::vector<std::string> lines;
+        const int frames = bundle_builder.frames();
+        if (frames >= 3) {
+            adapters::hip::HipBundleAdjuster adjuster(bundle_K, -1.0, 1e-6, 10, 1);        // post hoc on device 0, as --optimize is
+            for (int first = 0; first + 2 < frames; first += bundle_window - 2) {
+                const int n = std::min(bundle_window, frames - first);
+                adapters::hip::BundleWindow w = bundle_builder.window(first, n);
+                const adapters::hip::BundleResult r = adjuster.optimize(w, 0);
+                bundle_builder.store(w);
+                char buf[256];
+                std::snprintf(buf, sizeof(buf), "# window %d %d points %d observations %zu chi2_initial %.9g chi2_final %.9g rms_px %.6f",
+                              first, n, w.nPoints(), w.obs.size(), r.record.chi2_initial, r.record.chi2_final, r.record.rms_px);
+                lines.push_back(buf);
+            }
+        }
+        write_tum(bundle_file, [&](std::size_t i) {
+            const long long k = (long long)i - bundle_first;
+            if (bundle_first < 0 || k < 0 || k >= frames) return track_traj[i];
+            std::array<double, 16> T{};
+            const std::array<double, 12>& p = bundle_builder.pose((int)k);
+            for (int c = 0; c < 12; c++) T[(std::size_t)c] = p[(std::size_t)c];
+            T[15] = 1.0;
+            return T;
+        });
+        std::ofstream bf(bundle_file, std::ios::app);
+        for (const std::string& l : lines) bf << l << '\n';
+        std::printf("bundle %d frames %zu windows of %d -> %s\n", frames, lines.size(), bundle_window, bundle_file.c_str());
     }
     if (stereo) {
         std::ofstream sf;

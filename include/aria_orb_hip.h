@@ -1793,6 +1793,120 @@ int   aria_pnp_associate_batch_device(aria_pnp_t h, aria_map_t map, int anchor_b
                                       const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
                                       aria_pnp_corr* d_corr, int* d_ncorr, int* d_corr_match);
 
+/* ---- local bundle adjustment: the poses and points of one sliding window refined together against every pixel that saw
+ * them -- the step that ties the chain's stages to each other (two-view pose fixes |t| = 1 per pair, the mapper triangulates
+ * each pair alone, PnP holds the points fixed, the pose graph never looks at a pixel). The reference has no code for it (its
+ * notes name the step: README.md:1162, docs/milestones/H10_POSE_GRAPH_AUDIT.md:501-540); aria_slam_amd/ba_ref.py is the
+ * definition, and parity with g2o or Ceres is not claimed. Batched over windows; additive to ABI 4.
+ *
+ * Window. n_poses <= 16 (ARIA_BA_MAX_POSES) world-to-camera poses [R t], 12 doubles row-major, a fixed byte each; n_points
+ *   points X[3] in fp64, a fixed byte each; n_obs records aria_ba_obs sorted strictly ascending by (point, pose): a point's
+ *   observations are contiguous, at most 16, without duplicates. Intrinsics fx, fy, cx, cy from the config, fp64.
+ * Validity. A window is invalid when a count is negative or beyond its capacity, n_poses > 16, an index is out of range,
+ *   the order is not strictly ascending, or a pose, point or pixel is not finite: valid = 0, stop_reason = 2, the other
+ *   fields 0, the used mask 0, nothing beyond the records is read, poses and points are left bitwise untouched, and
+ *   aria_ba_check reports ARIA_E_INVALID once. The other windows of the batch are unaffected.
+ * Residual. Xc = R X + t, r = (fx Xc.x / Xc.z + cx - u, fy Xc.y / Xc.z + cy - v) in pixels, e = |r|. An observation with
+ *   Xc.z <= min_depth at the initial state is dropped for the whole call (its byte of the used mask is 0). A trial state at
+ *   which a used observation has Xc.z <= min_depth, or whose chi2 is not finite, is rejected.
+ * Robust weight. Huber with huber_px = delta (0 = off): w = 1 and the cost e^2 when e <= delta, else w = delta / e and the
+ *   cost 2 delta e - delta^2. chi2 = the sum of the costs over the used observations.
+ * Updates. Pose: R <- Exp(w) R, t <- Exp(w) t + v, Exp as in the absolute-pose refinement, parameters ordered (w, v).
+ *   Point: X <- X + dX. A fixed pose or point gets no update and keeps its bits. A point with fewer than two used
+ *   observations is treated as fixed for the call; its observations still constrain their poses.
+ * Step. U_i = sum w Jc^T Jc, V_j = sum w Jp^T Jp, W_o = w Jc^T Jp, bc_i = -sum w Jc^T r, bp_j = -sum w Jp^T r; damping
+ *   H + lambda I; Vd_j = V_j + lambda I inverted through its 3x3 Cholesky factor; over the free poses
+ *   S_ik = [i == k](U_i + lambda I) - sum_j W_ij Vd_j^-1 W_kj^T, g_i = bc_i - sum_j W_ij Vd_j^-1 bp_j, solved by dense
+ *   Cholesky of at most 96 x 96; dX_j = Vd_j^-1 (bp_j - sum_i W_ij^T dc_i). A pivot that is not positive rejects the trial.
+ * LM control. That of the pose-graph stage above, constants unchanged: lambda0 = 1e-5 * the largest diagonal entry of U over
+ *   the free poses and V over the free points, the gain ratio with the denominator dx.(lambda dx + b) + 1e-3, accepted
+ *   when rho > 0, the 1/3 clamp, lambda *= ni, ni *= 2 on a rejection, ten rejected trials end the call (stop_reason 1).
+ *   rho uses the robust chi2. The LM state restarts per call.
+ * Determinism. No float atomics; every sum has a fixed order that depends on the window alone: results are bitwise
+ *   reproducible run to run and independent of the window's place in a batch, of the batch's split into calls and of the
+ *   number of scratch slots. The summation order is not ba_ref's: the device is held to it by measured tolerances.
+ * Out of scope: windows of more than 16 poses or a reduced system outside the LDS; intrinsics or distortion as parameters;
+ *   stereo or depth observations; merging duplicate points; writing refined points back into the map arena;
+ *   marginalisation and priors; global BA; IMU factors; parity with g2o or Ceres. */
+#define ARIA_BA_MAX_POSES 16
+typedef struct aria_ba_s* aria_ba_t;
+typedef struct {
+    int   point, pose;         /* indices into the window's points and poses                                      */
+    float u, v;                /* pixel                                                                          */
+} aria_ba_obs;                 /* 16 bytes                                                                       */
+typedef struct {
+    double chi2_initial, chi2_final, lambda;
+    double rms_px;             /* over the used observations at the final state, unweighted                      */
+    int    n_obs_used, iterations_done, trials;
+    int    stop_reason;        /* 0 = iterations done, 1 = ten rejected trials, 2 = invalid window               */
+    int    valid, reserved;
+} aria_ba_result;              /* 56 bytes; no field is ever NaN or Inf for a valid window                       */
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_ba_config)                                                      */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle owns one (non-blocking, see aria_pose_config) */
+    double   fx, fy, cx, cy;   /* intrinsics (default EuRoC cam0)                                                */
+    double   huber_px;         /* default sqrt(5.991); 0 = no robust weight                                      */
+    double   min_depth;        /* default 1e-6                                                                   */
+    int      max_iterations;   /* 1..100 (default 10): what a call with iterations = 0 runs                      */
+    int      max_windows;      /* scratch slots = windows per launch, 1..65535 (default 256); more windows run as
+                                * consecutive launches, and the slot count changes no bit of a result            */
+} aria_ba_config;
+
+void  aria_ba_default_config(aria_ba_config* cfg);
+int   aria_ba_create(const aria_ba_config* cfg, aria_ba_t* out);
+void  aria_ba_destroy(aria_ba_t h);
+void* aria_ba_stream(aria_ba_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check: ARIA_E_INVALID
+ * when some window was invalid (above) or the track builder refused one, else ARIA_E_OUTPUT_TOO_SMALL when the track
+ * builder found more points or observations than its capacities. */
+int   aria_ba_check(aria_ba_t h);
+/* One window, host buffers; blocks. poses_inout: n_poses * 12 doubles, points_inout: n_points * 3, both updated in place.
+ * iterations: 1..100, or 0 for the config's. used (optional): n_obs bytes. An invalid window returns ARIA_E_INVALID with
+ * *result filled as above. */
+int   aria_ba_optimize(aria_ba_t h, double* poses_inout, const uint8_t* pose_fixed, int n_poses, double* points_inout,
+                       const uint8_t* point_fixed, int n_points, const aria_ba_obs* obs, int n_obs, int iterations,
+                       aria_ba_result* result, uint8_t* used);
+/* Device-resident batch form: window b reads d_n_poses[b] poses at d_poses + b*pose_cap*12 with their fixed bytes at
+ * d_pose_fixed + b*pose_cap, d_n_points[b] points at d_points + b*point_cap*3 with d_point_fixed + b*point_cap, and
+ * d_n_obs[b] observations at d_obs + b*obs_cap; updates poses and points in place; writes d_out[b] and, if d_used is not
+ * NULL, obs_cap bytes at d_used + b*obs_cap (zero beyond the window's observations). Enqueued on the handle's stream;
+ * nothing is synchronised, except when the workspace grows (it is sized by max_windows, point_cap and obs_cap). */
+int   aria_ba_optimize_batch_device(aria_ba_t h, double* d_poses, const uint8_t* d_pose_fixed, double* d_points,
+                                    const uint8_t* d_point_fixed, const aria_ba_obs* d_obs, const int* d_n_poses,
+                                    const int* d_n_points, const int* d_n_obs, int n_windows, int pose_cap, int point_cap,
+                                    int obs_cap, int iterations, aria_ba_result* d_out, uint8_t* d_used);
+/* Test hook: one window (host buffers) linearised at its state and damped with `lambda`. chi2, n_obs_used; with F free
+ * poses in pose order, S (6F x 6F, row-major, both triangles) and g (6F); V (n_points * 9) and bp (n_points * 3) of every
+ * point over its used observations. */
+int   aria_ba_debug_linearize(aria_ba_t h, const double* poses, const uint8_t* pose_fixed, int n_poses, const double* points,
+                              const uint8_t* point_fixed, int n_points, const aria_ba_obs* obs, int n_obs, double lambda,
+                              double* chi2, int* n_obs_used, double* S, double* g, double* V, double* bp);
+
+/* The track builder: windows of points and observations from what the batch chain leaves in HBM, equal to
+ * ba_ref.window_from_chain bit for bit (integers and copies only). The chain is n_chain_pairs pairs with ids pair_base + q,
+ * their keypoints at d_kp1 + q*kp_stride (view 1, d_n1[q] of them) and d_kp2 + q*kp_stride (view 2), their matches at
+ * d_matches + q*match_cap (d_nmatches[q]; query_is_first says which side of a match indexes view 1), as
+ * aria_map_triangulate_batch_device took them. Precondition: view 2 of pair q is the same extraction as view 1 of pair
+ * q + 1. Window b covers the pairs d_pair_first[b] .. + d_n_pairs[b] - 1 (1..15 pairs, inside the chain): frame f is view 1
+ * of pair d_pair_first[b] + f, the last frame view 2 of the last pair. Its points are the arena's points whose pair lies in
+ * the window, in arena order; a point of pair p yields the observations (f, pixel of view-1 keypoint idx1), (f + 1, pixel of
+ * view-2 keypoint idx2) and then, for each later pair of the window, the match whose view-1 index equals the index carried
+ * so far -- the lowest match index of several -- which adds that pair's view-2 pixel and carries its view-2 index on; the
+ * first pair without such a match ends the track. Observations come out sorted. Written: X at d_points + b*point_cap*3,
+ * observations at d_obs + b*obs_cap, each point's arena position at d_point_src + b*point_cap, d_n_points[b], d_n_obs[b].
+ * A window outside the chain, a count out of range or an index out of range is a deferred ARIA_E_INVALID of the window, more
+ * points or observations than the capacities a deferred ARIA_E_OUTPUT_TOO_SMALL; either way its counts are 0. Enqueued on
+ * the handle's stream, which must be ordered after the work that filled the map (the rule of
+ * aria_pnp_associate_batch_device); a map on another device than the handle's: ARIA_E_INVALID. The same physical point
+ * triangulated in two pairs stays two points. */
+int   aria_ba_window_from_chain_device(aria_ba_t h, aria_map_t map, const int* d_pair_first, const int* d_n_pairs, int n_windows,
+                                       int pair_base, int n_chain_pairs, const aria_keypoint* d_kp1, const int* d_n1,
+                                       const aria_keypoint* d_kp2, const int* d_n2, int64_t kp_stride,
+                                       const aria_match* d_matches, const int* d_nmatches, int match_cap, int query_is_first,
+                                       int point_cap, int obs_cap, double* d_points, aria_ba_obs* d_obs, int* d_point_src,
+                                       int* d_n_points, int* d_n_obs);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
