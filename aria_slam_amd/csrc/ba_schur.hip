@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "common.h"
+#include "solver_device.h"
 #include "stage_handle.h"
 
 using namespace aria;
@@ -39,10 +40,8 @@ constexpr int BA_WAVES = BA_BLOCK / 64;
 constexpr int BA_P = ARIA_BA_MAX_POSES;
 constexpr int BA_N = 6 * BA_P;            // rows of the reduced system
 constexpr int BA_LD = BA_N + 1;           // padded row: a column read touches every bank once
-constexpr int BA_MAX_TRIALS = 10;
 constexpr int ERRBIT_BA_INPUT = 1;
 constexpr int ERRBIT_BA_CAPACITY = 2;     // track builder: more points or observations than the caller's capacity
-constexpr int STOP_ITERATIONS = 0, STOP_TRIALS = 1, STOP_INVALID = 2;
 
 struct BaArgs {
     double* poses;
@@ -100,44 +99,6 @@ __device__ inline int tid_here() {
     return t;
 }
 
-// ---- reductions: per-lane partial, wave butterfly, fixed 8-way sum through LDS (k_graph_lm's) ---------------------------
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ inline void block_sum2(Lds& L, int& phase, double& a, double& b) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-    double* slot = L.red + phase * 2 * BA_WAVES;
-    if ((threadIdx.x & 63) == 0) {
-        slot[threadIdx.x >> 6] = a;
-        slot[BA_WAVES + (threadIdx.x >> 6)] = b;
-    }
-    __syncthreads();
-    double sa = 0.0, sb = 0.0;
-#pragma unroll
-    for (int w = 0; w < BA_WAVES; w++) { sa += slot[w]; sb += slot[BA_WAVES + w]; }
-    a = sa;
-    b = sb;
-    phase ^= 1;      // the next reduction uses the other slot: one barrier per reduction is enough
-}
-
-__device__ inline double block_max(Lds& L, int& phase, double a) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) a = fmax(a, __shfl_xor(a, m, 64));
-    double* slot = L.red + phase * 2 * BA_WAVES;
-    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = a;
-    __syncthreads();
-    double s = slot[0];
-#pragma unroll
-    for (int w = 1; w < BA_WAVES; w++) s = fmax(s, slot[w]);
-    phase ^= 1;
-    return s;
-}
-
-__device__ constexpr int tri6(int a, int c) { return a <= c ? 6 * a - a * (a - 1) / 2 + (c - a) : 6 * c - c * (c - 1) / 2 + (a - c); }
 __device__ constexpr int tri3(int a, int c) { return a <= c ? 3 * a - a * (a - 1) / 2 + (c - a) : 3 * c - c * (c - 1) / 2 + (a - c); }
 
 // ---- one observation ------------------------------------------------------------------------------------------------------
@@ -417,25 +378,8 @@ __device__ inline void solve_lds(Lds& L, int n) {
 
 // R <- Exp(w) R, t <- Exp(w) t + v on the 12 doubles of [R t]
 __device__ inline void pose_update(double* P, const double* x) {
-    const double th2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    double a, b;
-    if (th2 < 1e-16) {
-        a = 1.0 - th2 / 6.0;
-        b = 0.5 - th2 / 24.0;
-    } else {
-        const double th = sqrt(th2);
-        a = sin(th) / th;
-        b = (1.0 - cos(th)) / th2;
-    }
-    const double Kx[9] = {0.0, -x[2], x[1], x[2], 0.0, -x[0], -x[1], x[0], 0.0};
     double E[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const double k2 = Kx[r * 3] * Kx[c] + Kx[r * 3 + 1] * Kx[3 + c] + Kx[r * 3 + 2] * Kx[6 + c];
-            E[r * 3 + c] = ((r == c) ? 1.0 : 0.0) + a * Kx[r * 3 + c] + b * k2;
-        }
+    exp_so3(x, E);
     double Q[12];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
@@ -464,7 +408,7 @@ __device__ inline void chi2_pass(Lds& L, int& phase, const double* points, const
         c2 += cost;
         es += e2;
     }
-    block_sum2(L, phase, c2, es);
+    block_sum2<BA_WAVES>(L.red, phase, c2, es);
     bad = __syncthreads_or(b);
     chi2 = c2;
     e2sum = es;
@@ -613,7 +557,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_lm(const BaArgs A) {
     chi2_pass(L, phase, points, obs, nobs, S, K, chi2, e2sum, behind);
     double mx = point_pass(L, A, points, obs, npts, S, K);
     mx = fmax(mx, pose_pass(L, points, obs, nposes, S, K));
-    const double maxdiag = block_max(L, phase, mx);       // its barrier publishes V, bp, W, U and bc
+    const double maxdiag = block_max<BA_WAVES>(L.red, phase, mx);   // its barrier publishes V, bp, W, U and bc
     res.chi2_initial = res.chi2_final = chi2;
     const int n = 6 * L.nfree;
     if (A.mode == 1) {
@@ -629,16 +573,17 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_lm(const BaArgs A) {
         if (tid == 0) A.out[win] = res;
         return;
     }
-    double lambda = 1e-5 * maxdiag, ni = 2.0;
+    LmDamping lm;
+    lm.start(maxdiag);
 
     for (int it = 0; it < A.iterations; it++) {
         bool accepted = false;
-        for (int trial = 0; trial < BA_MAX_TRIALS; trial++) {
+        for (int trial = 0; trial < LM_MAX_TRIALS; trial++) {
             res.trials++;
             const int tid = tid_here();
-            bool solved = !__syncthreads_or(point_trial(npts, lambda, S));     // barrier: Vd^-1 and E are visible
+            bool solved = !__syncthreads_or(point_trial(npts, lm.lambda, S));     // barrier: Vd^-1 and E are visible
             if (solved) {
-                build_reduced(L, obs, lambda, S);
+                build_reduced(L, obs, lm.lambda, S);
                 __syncthreads();
                 solved = cholesky_lds(L, n);
             }
@@ -655,7 +600,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_lm(const BaArgs A) {
 #pragma unroll
                     for (int c = 0; c < 6; c++) {
                         d[c] = L.dc[6 * L.fidx[tid] + c];
-                        den += d[c] * (lambda * d[c] + L.bc[6 * tid + c]);
+                        den += d[c] * (lm.lambda * d[c] + L.bc[6 * tid + c]);
                     }
                     pose_update(Pn, d);
 #pragma unroll
@@ -686,11 +631,11 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_lm(const BaArgs A) {
                         const double x = points[3 * (size_t)j + c];
                         S.xbak[3 * (size_t)j + c] = x;
                         points[3 * (size_t)j + c] = x + dx;
-                        den += dx * (lambda * dx + bpj[c]);
+                        den += dx * (lm.lambda * dx + bpj[c]);
                     }
                 }
                 double zero = 0.0;
-                block_sum2(L, phase, den, zero);            // barrier: the new state is visible
+                block_sum2<BA_WAVES>(L.red, phase, den, zero);   // barrier: the new state is visible
                 den += 1e-3;
                 int bh;
                 chi2_pass(L, phase, points, obs, nobs, S, K, chi2_new, e2_new, bh);
@@ -703,9 +648,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_lm(const BaArgs A) {
                 point_pass(L, A, points, obs, npts, S, K);
                 pose_pass(L, points, obs, nposes, S, K);
                 __syncthreads();
-                const double a = 2.0 * rho - 1.0;
-                lambda *= fmax(1.0 / 3.0, 1.0 - a * a * a);
-                ni = 2.0;
+                lm.accept(rho);
                 accepted = true;
                 break;
             }
@@ -721,8 +664,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_lm(const BaArgs A) {
                 }
                 __syncthreads();
             }
-            lambda *= ni;
-            ni *= 2.0;
+            lm.reject();
         }
         if (!accepted) {
             res.stop_reason = STOP_TRIALS;
@@ -736,7 +678,7 @@ __global__ __launch_bounds__(BA_BLOCK) void k_ba_lm(const BaArgs A) {
         for (int c = 0; c < 12; c++) poses[12 * (size_t)tid + c] = L.P[12 * tid + c];
     }
     res.chi2_final = chi2;
-    res.lambda = lambda;
+    res.lambda = lm.lambda;
     res.rms_px = res.n_obs_used > 0 ? sqrt(e2sum / (double)res.n_obs_used) : 0.0;
     if (tid == 0) A.out[win] = res;
 }

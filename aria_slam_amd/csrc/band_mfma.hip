@@ -48,7 +48,6 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef short short2v __attribute__((ext_vector_type(2)));
 typedef unsigned short us2v __attribute__((ext_vector_type(2)));
 
 // ---- constant operand tables of the two matrix passes, one row of 24 dwords per lane ----
@@ -118,18 +117,6 @@ static Band2Cfg band2_cfg(const Plan& P, int w, int level, int w_next) {
     return Band2Cfg{lpr, nthr, qcap, nblk, pix + 4 * (size_t)qcap + 4 * (size_t)(w_next + 48)};
 }
 
-__device__ __forceinline__ uint32_t b2_pk_min(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
-}
-__device__ __forceinline__ uint32_t b2_pk_max(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
-}
-__device__ __forceinline__ uint32_t b2_pk_sub(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) - __builtin_bit_cast(short2v, b));
-}
-__device__ __forceinline__ uint32_t b2_pk_add(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) + __builtin_bit_cast(short2v, b));
-}
 __device__ __forceinline__ uint32_t b2_umad24(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t r;
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -148,17 +135,17 @@ __device__ __forceinline__ int b2_fast_score(const uint8_t* c, int pitch) {
                          rm3[0], rm3[-1], rm2[-2], rm1[-3], c[-3], rp1[-3], rp2[-2], rp3[-1]};
     uint32_t P[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) P[k] = b2_pk_sub(v | (ring[k] << 16), ring[k] | vhi);
+    for (int k = 0; k < 16; k++) P[k] = pk_sub_i16(v | (ring[k] << 16), ring[k] | vhi);
     uint32_t M2[16], M4[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) M2[k] = b2_pk_min(P[k], P[(k + 1) & 15]);
+    for (int k = 0; k < 16; k++) M2[k] = pk_min_i16(P[k], P[(k + 1) & 15]);
 #pragma unroll
-    for (int k = 0; k < 16; k++) M4[k] = b2_pk_min(M2[k], M2[(k + 2) & 15]);
+    for (int k = 0; k < 16; k++) M4[k] = pk_min_i16(M2[k], M2[(k + 2) & 15]);
     uint32_t Q = 0x80008000u;   // (-32768, -32768)
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-        const uint32_t m9 = b2_pk_min(b2_pk_min(M4[k], M4[(k + 4) & 15]), P[(k + 8) & 15]);
-        Q = b2_pk_max(Q, m9);
+        const uint32_t m9 = pk_min_i16(pk_min_i16(M4[k], M4[(k + 4) & 15]), P[(k + 8) & 15]);
+        Q = pk_max_i16(Q, m9);
     }
     const int q0 = (int)(short)(Q & 0xFFFFu), q1 = (int)(short)(Q >> 16);
     return max(q0, q1) - 1;
@@ -446,10 +433,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))) void 
                         for (int pr = 0; pr < 2; pr++) {
                             const uint32_t c2 = RC2[sC][pr], n2 = RC2[sM3][pr], s2 = RC2[sP3][pr];
                             const uint32_t w2p = EW[sC][pr], e2 = EW[sC][2 + pr];
-                            const uint32_t lo = b2_pk_sub(c2, T2), hi = b2_pk_add(c2, T2);
+                            const uint32_t lo = pk_sub_i16(c2, T2), hi = pk_add_i16(c2, T2);
                             // sign bit set <=> darker than c - t / brighter than c + t
-                            const uint32_t dk = b2_pk_sub(b2_pk_max(b2_pk_min(n2, s2), b2_pk_min(e2, w2p)), lo);
-                            const uint32_t br = b2_pk_sub(hi, b2_pk_min(b2_pk_max(n2, s2), b2_pk_max(e2, w2p)));
+                            const uint32_t dk = pk_sub_i16(pk_max_i16(pk_min_i16(n2, s2), pk_min_i16(e2, w2p)), lo);
+                            const uint32_t br = pk_sub_i16(hi, pk_min_i16(pk_max_i16(n2, s2), pk_max_i16(e2, w2p)));
                             pass[pr] = (dk | br) & (pr ? xm1 : xm0);
                         }
                         accw |= (pass[0] | (pass[1] >> 1)) >> (2 * u);

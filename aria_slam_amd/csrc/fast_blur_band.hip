@@ -99,20 +99,7 @@ __device__ __forceinline__ uint32_t umad24(uint32_t a, uint32_t b, uint32_t c) {
     return r;
 }
 
-typedef short short2v __attribute__((ext_vector_type(2)));
 typedef unsigned short us2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_min_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
-}
-__device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
-}
-__device__ __forceinline__ uint32_t pk_sub_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) - __builtin_bit_cast(short2v, b));
-}
-__device__ __forceinline__ uint32_t pk_add_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) + __builtin_bit_cast(short2v, b));
-}
 
 // fast_score.cpp cornerScore<16> for the pixel at LDS address c (row pitch `pitch`):
 // max over the 16 nine-arcs of min(v - ring) and of min(ring - v), minus 1; both polarities ride in one register as

@@ -75,25 +75,11 @@ typedef uint32_t qent_t;
 static_assert(kOut >= 128 && kQ1 >= 64 && kQ2 >= 64, "emit() appends up to 64 entries behind a 64-entry batch; the lists are filled 64 lanes at a time");
 constexpr int kOwned = 62;                        // productive lanes per wave (lanes 1..62)
 
-typedef short short2v __attribute__((ext_vector_type(2)));
 typedef unsigned short us2v __attribute__((ext_vector_type(2)));
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// (gload_sv / gstore_sv: wave-uniform 64-bit base in SGPRs + the lane's 32-bit offset -- orb_device.h)
-__device__ __forceinline__ uint32_t pk_min_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
-}
-__device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
-}
-__device__ __forceinline__ uint32_t pk_sub_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) - __builtin_bit_cast(short2v, b));
-}
-__device__ __forceinline__ uint32_t pk_add_i16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) + __builtin_bit_cast(short2v, b));
-}
-
+// (gload_sv / gstore_sv: wave-uniform 64-bit base in SGPRs + the lane's 32-bit offset; pk_*_i16 -- orb_device.h)
 // inclusive prefix sum over the 64 lanes of the wave (DPP: Hillis-Steele inside the 16-lane rows, then the row carries)
 __device__ __forceinline__ int wave_scan_incl(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);     // row_shr:1

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "solver_device.h"
 #include "stage_handle.h"
 
 using namespace aria;
@@ -37,10 +38,8 @@ namespace {
 
 constexpr int GRAPH_BLOCK = 512;          // 8 waves: 2 per SIMD, 256 VGPRs each
 constexpr int GRAPH_WAVES = GRAPH_BLOCK / 64;
-constexpr int GRAPH_MAX_TRIALS = 10;
 constexpr int ERRBIT_GRAPH_INPUT = 1;     // counts, fixed index or an edge out of range (graph skipped)
 constexpr int ERRBIT_GRAPH_LARGE = 2;     // more vertices or edges than the handle was created for (graph skipped)
-constexpr int STOP_ITERATIONS = 0, STOP_TRIALS = 1, STOP_INVALID = 2;
 constexpr int GRAPH_LDS_EDGES = 544;      // edges whose W fits the LDS beside p: 27 * 544 * 8 + 6 * 512 * 8 = 142080 bytes of 160 KiB
 constexpr int EDGE_DOUBLES = 36 * 4 + 12; // A, B, W[2], gi, gj per edge
 constexpr int VERT_DOUBLES = 12 + 36 + 36 + 6 * 5;   // backup, D, Minv, b, x, r, p, Ap per vertex
@@ -72,53 +71,11 @@ __device__ inline Scratch scratch_of(double* vbase, double* ebase, int* ibase, i
     return s;
 }
 
-// ---- reductions: per-lane partial (vertex order), wave butterfly, fixed 8-way sum through LDS -----------------------------
+// ---- reductions: per-lane partial (vertex order), then block_sum2 / block_sum / block_max<GRAPH_WAVES> of solver_device.h
 struct Red {
     double* lds;      // [2][2][GRAPH_WAVES]
     int phase;
 };
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ inline void block_sum2(Red& R, double& a, double& b) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-    double* slot = R.lds + R.phase * 2 * GRAPH_WAVES;
-    if ((threadIdx.x & 63) == 0) {
-        slot[threadIdx.x >> 6] = a;
-        slot[GRAPH_WAVES + (threadIdx.x >> 6)] = b;
-    }
-    __syncthreads();
-    double sa = 0.0, sb = 0.0;
-#pragma unroll
-    for (int w = 0; w < GRAPH_WAVES; w++) { sa += slot[w]; sb += slot[GRAPH_WAVES + w]; }
-    a = sa;
-    b = sb;
-    R.phase ^= 1;    // the next reduction uses the other slot: one barrier per reduction is enough
-}
-
-__device__ inline double block_sum(Red& R, double a) {
-    double b = 0.0;
-    block_sum2(R, a, b);
-    return a;
-}
-
-__device__ inline double block_max(Red& R, double a) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) a = fmax(a, __shfl_xor(a, m, 64));
-    double* slot = R.lds + R.phase * 2 * GRAPH_WAVES;
-    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = a;
-    __syncthreads();
-    double s = slot[0];
-#pragma unroll
-    for (int w = 1; w < GRAPH_WAVES; w++) s = fmax(s, slot[w]);
-    R.phase ^= 1;
-    return s;
-}
 
 // ---- SE(3) pieces (graph_ref.py: quat_from_rot, rot_from_quat, oplus) ---------------------------------------------------
 // q = (x, y, z, w), unit, w >= 0
@@ -251,7 +208,7 @@ __device__ inline double edge_pass(Red& R, const double* poses, const aria_graph
                                    const Scratch& S, double* W) {
     double part = 0.0;
     for (int k = threadIdx.x; k < ne; k += GRAPH_BLOCK) part += edge_blocks(poses, edges[k], S, W, k);
-    return block_sum(R, part);      // its barrier also publishes the blocks to the workgroup
+    return block_sum<GRAPH_WAVES>(R.lds, R.phase, part);   // its barrier also publishes the blocks to the workgroup
 }
 
 // every vertex gathers D and b over its incident edges in adjacency order; returns max diag(D) over the free vertices
@@ -284,7 +241,7 @@ __device__ inline double vertex_gather(Red& R, int nv, int fixed, const Scratch&
             for (int c = 0; c < 6; c++) mx = fmax(mx, D[7 * c]);
         }
     }
-    return block_max(R, mx);
+    return block_max<GRAPH_WAVES>(R.lds, R.phase, mx);
 }
 
 // ---- preconditioner: inverse of the damped diagonal blocks (the separable step: swap this and precond_apply) ------------
@@ -344,7 +301,6 @@ __device__ inline void precond_build(int nv, double lambda, const Scratch& S) {
 // D and Minv are symmetric bit for bit (each entry is the same sum of commuting products), so the solver reads their upper
 // triangles only: 21 of 36 entries
 __device__ constexpr int sym6(int a, int c) { return a <= c ? 6 * a + c : 6 * c + a; }
-__device__ constexpr int tri6(int a, int c) { return a <= c ? 6 * a - a * (a - 1) / 2 + (c - a) : 6 * c - c * (c - 1) / 2 + (a - c); }
 // W = s Ji^T Jj has a zero block: rows 0..2 x columns 3..5 (Ji's lower-left and Jj's off-diagonal blocks are zero)
 __device__ constexpr bool w_zero(int r, int c) { return r < 3 && c >= 3; }
 __device__ constexpr int w27(int r, int c) { return r < 3 ? 3 * r + c : 9 + 6 * (r - 3) + c; }    // index among the 27 others
@@ -380,7 +336,7 @@ __device__ inline int pcg_solve(Red& R, int nv, int fixed, double lambda, const 
             bb += r[c] * r[c];
         }
     }
-    block_sum2(R, rz, bb);          // barrier: p is visible to the workgroup
+    block_sum2<GRAPH_WAVES>(R.lds, R.phase, rz, bb);   // barrier: p is visible to the workgroup
     if (!(bb > 0.0)) return 0;
     const double stop = rel_tol * rel_tol * bb;
     int iters = 0;
@@ -427,7 +383,7 @@ __device__ inline int pcg_solve(Red& R, int nv, int fixed, double lambda, const 
                 pAp += p[c] * y[c];
             }
         }
-        pAp = block_sum(R, pAp);
+        pAp = block_sum<GRAPH_WAVES>(R.lds, R.phase, pAp);
         if (!(pAp > 0.0)) break;
         const double alpha = rz / pAp;
         double rr = 0.0, rzn = 0.0;
@@ -448,7 +404,7 @@ __device__ inline int pcg_solve(Red& R, int nv, int fixed, double lambda, const 
                 rzn += r[c] * z[c];
             }
         }
-        block_sum2(R, rr, rzn);
+        block_sum2<GRAPH_WAVES>(R.lds, R.phase, rr, rzn);
         iters = it;
         if (rr <= stop) break;
         const double beta = rzn / rz;
@@ -515,7 +471,7 @@ __device__ inline int pcg_small(Red& R, int nv, int ne, int fixed, double lambda
         rz += r[c] * z[c];
         bb += r[c] * r[c];
     }
-    block_sum2(R, rz, bb);
+    block_sum2<GRAPH_WAVES>(R.lds, R.phase, rz, bb);
     int iters = 0;
     if (bb > 0.0) {
         const double stop = rel_tol * rel_tol * bb;
@@ -553,7 +509,7 @@ __device__ inline int pcg_small(Red& R, int nv, int ne, int fixed, double lambda
             }
 #pragma unroll
             for (int c = 0; c < 6; c++) pAp += p[c] * y[c];
-            pAp = block_sum(R, pAp);                 // barrier: every lane has read its neighbours' p
+            pAp = block_sum<GRAPH_WAVES>(R.lds, R.phase, pAp);   // barrier: every lane has read its neighbours' p
             if (!(pAp > 0.0)) break;
             const double alpha = rz / pAp;
             double rr = 0.0, rzn = 0.0;
@@ -574,7 +530,7 @@ __device__ inline int pcg_small(Red& R, int nv, int ne, int fixed, double lambda
                 rr += r[c] * r[c];
                 rzn += r[c] * z[c];
             }
-            block_sum2(R, rr, rzn);
+            block_sum2<GRAPH_WAVES>(R.lds, R.phase, rr, rzn);
             iters = it;
             if (rr <= stop) break;
             const double beta = rzn / rz;
@@ -734,22 +690,23 @@ __global__ __launch_bounds__(GRAPH_BLOCK) void k_graph_lm(double* poses_all, con
         if (tid == 0) results[g] = res;
         return;
     }
-    double lambda = 1e-5 * maxdiag, ni = 2.0;
+    LmDamping lm;
+    lm.start(maxdiag);
 
     for (int it = 0; it < iterations; it++) {
         bool accepted = false;
-        for (int trial = 0; trial < GRAPH_MAX_TRIALS; trial++) {
+        for (int trial = 0; trial < LM_MAX_TRIALS; trial++) {
             res.trials++;
             double* Wc = curW ? S.W1 : S.W0;
             double* Wn = curW ? S.W0 : S.W1;
-            precond_build(nv, lambda, S);           // each lane builds and later reads its own vertices' blocks
+            precond_build(nv, lm.lambda, S);           // each lane builds and later reads its own vertices' blocks
             // three forms of one solve, the same arithmetic in the same order (the choice changes no bit of the result)
             if (nv <= GRAPH_BLOCK && ne <= wlds_edges)
-                res.pcg_iterations += pcg_small<true>(R, nv, ne, fixed, lambda, Wc, S, pcg_max_iters, pcg_rel_tol, wlds, wlds_edges);
+                res.pcg_iterations += pcg_small<true>(R, nv, ne, fixed, lm.lambda, Wc, S, pcg_max_iters, pcg_rel_tol, wlds, wlds_edges);
             else if (nv <= GRAPH_BLOCK)
-                res.pcg_iterations += pcg_small<false>(R, nv, ne, fixed, lambda, Wc, S, pcg_max_iters, pcg_rel_tol, wlds, 0);
+                res.pcg_iterations += pcg_small<false>(R, nv, ne, fixed, lm.lambda, Wc, S, pcg_max_iters, pcg_rel_tol, wlds, 0);
             else
-                res.pcg_iterations += pcg_solve(R, nv, fixed, lambda, Wc, S, pcg_max_iters, pcg_rel_tol);
+                res.pcg_iterations += pcg_solve(R, nv, fixed, lm.lambda, Wc, S, pcg_max_iters, pcg_rel_tol);
             // update (with a backup) and the gain's denominator dx.(lambda dx + b)
             double den = 0.0;
             const size_t Vc = (size_t)S.Vc;
@@ -764,22 +721,20 @@ __global__ __launch_bounds__(GRAPH_BLOCK) void k_graph_lm(double* poses_all, con
 #pragma unroll
                 for (int c = 0; c < 6; c++) {
                     d[c] = S.x[c * Vc + v];
-                    den += d[c] * (lambda * d[c] + S.b[c * Vc + v]);
+                    den += d[c] * (lm.lambda * d[c] + S.b[c * Vc + v]);
                 }
                 pose_update(P, d);
 #pragma unroll
                 for (int c = 0; c < 12; c++) poses[12 * (size_t)v + c] = P[c];
             }
-            den = block_sum(R, den) + 1e-3;         // barrier: the new poses are visible
+            den = block_sum<GRAPH_WAVES>(R.lds, R.phase, den) + 1e-3;   // barrier: the new poses are visible
             const double chi2_new = edge_pass(R, poses, edges, ne, S, Wn);
             const double rho = (chi2 - chi2_new) / den;
             if (rho > 0.0 && chi2_new < INFINITY && chi2_new == chi2_new) {
                 curW ^= 1;
                 vertex_gather(R, nv, fixed, S);
                 chi2 = chi2_new;
-                const double a = 2.0 * rho - 1.0;
-                lambda *= fmax(1.0 / 3.0, 1.0 - a * a * a);
-                ni = 2.0;
+                lm.accept(rho);
                 accepted = true;
                 break;
             }
@@ -789,8 +744,7 @@ __global__ __launch_bounds__(GRAPH_BLOCK) void k_graph_lm(double* poses_all, con
                 for (int c = 0; c < 12; c++) poses[12 * (size_t)v + c] = S.bak[c * Vc + v];
             }
             __syncthreads();
-            lambda *= ni;
-            ni *= 2.0;
+            lm.reject();
         }
         if (!accepted) {
             res.stop_reason = STOP_TRIALS;
@@ -799,7 +753,7 @@ __global__ __launch_bounds__(GRAPH_BLOCK) void k_graph_lm(double* poses_all, con
         res.iterations_done++;
     }
     res.chi2_final = chi2;
-    res.lambda = lambda;
+    res.lambda = lm.lambda;
     if (tid == 0) results[g] = res;
 }
 

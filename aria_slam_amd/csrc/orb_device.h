@@ -50,6 +50,21 @@ __device__ __forceinline__ void gstore_sv(uint8_t* base, uint32_t off, T v) {
     *reinterpret_cast<gp>(b + off) = v;
 }
 
+// two int16 in one register: v_pk_min_i16, v_pk_max_i16, v_pk_sub_i16, v_pk_add_u16
+typedef short short2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_min_i16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
+}
+__device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b)));
+}
+__device__ __forceinline__ uint32_t pk_sub_i16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) - __builtin_bit_cast(short2v, b));
+}
+__device__ __forceinline__ uint32_t pk_add_i16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, a) + __builtin_bit_cast(short2v, b));
+}
+
 __device__ __forceinline__ int reflect101(int i, int n) {
     // BORDER_REFLECT_101; inputs here never lie more than one period outside, clamp guards tiny levels
     if (i < 0) i = -i;

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "ransac_device.h"
+#include "solver_device.h"
 #include "stage_handle.h"
 
 using namespace aria;
@@ -56,44 +57,6 @@ __device__ __forceinline__ int pnp_inlier(const float r[9], const float t[3], fl
     const float Z = ((r[6] * a.x + r[7] * a.y) + r[8] * a.z) + t[2];
     const float ex = X - a.w * Z, ey = Y - y * Z;
     return (Z > 0.0f && ex * ex + ey * ey <= thr2 * (Z * Z)) ? 1 : 0;
-}
-
-// The 3x3 Jacobi of the two-view stage (pose_ransac.hip jacobi_rotate / jacobi3), restated here so that that file's kernels
-// keep the instructions they have.
-template <int N, typename P>
-__device__ __forceinline__ void jacobi_rotate(P A, P V, int p, int q) {
-    const double apq = A[p * N + q];
-    if (apq == 0.0) return;
-    const double theta = (A[q * N + q] - A[p * N + p]) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    for (int k = 0; k < N; k++) {            // A <- A J
-        const double akp = A[k * N + p], akq = A[k * N + q];
-        A[k * N + p] = c * akp - s * akq;
-        A[k * N + q] = s * akp + c * akq;
-    }
-    for (int k = 0; k < N; k++) {            // A <- J^T A
-        const double apk = A[p * N + k], aqk = A[q * N + k];
-        A[p * N + k] = c * apk - s * aqk;
-        A[q * N + k] = s * apk + c * aqk;
-    }
-    A[p * N + q] = 0.0;
-    A[q * N + p] = 0.0;
-    for (int k = 0; k < N; k++) {            // V <- V J
-        const double vkp = V[k * N + p], vkq = V[k * N + q];
-        V[k * N + p] = c * vkp - s * vkq;
-        V[k * N + q] = s * vkp + c * vkq;
-    }
-}
-
-__device__ __forceinline__ void jacobi3(double A[9], double V[9]) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 10; sweep++) {
-        jacobi_rotate<3>(A, V, 0, 1);
-        jacobi_rotate<3>(A, V, 0, 2);
-        jacobi_rotate<3>(A, V, 1, 2);
-    }
 }
 
 // R = U V^T of M = U S V^T (row-major), sig = the singular values, descending: V from the eigenvectors of M^T M,
@@ -429,24 +392,8 @@ __device__ int pnp_gn_step(const double* S, double* L, double* R, double* t) {
     double nrm = 0.0;
     for (int i = 0; i < 6; i++) nrm = nrm + x[i] * x[i];
     if (!isfinite(nrm)) return 0;
-    // Exp(w) = I + a K + b K^2
-    const double th2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    double a, b;
-    if (th2 < 1e-16) {
-        a = 1.0 - th2 / 6.0;
-        b = 0.5 - th2 / 24.0;
-    } else {
-        const double th = sqrt(th2);
-        a = sin(th) / th;
-        b = (1.0 - cos(th)) / th2;
-    }
-    const double K[9] = {0.0, -x[2], x[1], x[2], 0.0, -x[0], -x[1], x[0], 0.0};
     double E[9];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            const double k2 = K[r * 3] * K[c] + K[r * 3 + 1] * K[3 + c] + K[r * 3 + 2] * K[6 + c];
-            E[r * 3 + c] = ((r == c) ? 1.0 : 0.0) + a * K[r * 3 + c] + b * k2;
-        }
+    exp_so3(x, E);
     double Rn[9], tn[3];
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) Rn[r * 3 + c] = E[r * 3] * R[c] + E[r * 3 + 1] * R[3 + c] + E[r * 3 + 2] * R[6 + c];

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "ransac_device.h"
+#include "solver_device.h"
 #include "stage_handle.h"
 
 using namespace aria;
@@ -48,44 +49,6 @@ __device__ __forceinline__ int pose_inlier(const float e[9], float4 q, float thr
     const float r = q.z * ex0 + q.w * ex1 + ex2;
     const float d = ex0 * ex0 + ex1 * ex1 + et0 * et0 + et1 * et1;
     return (d > 0.0f && r * r <= thr2 * d) ? 1 : 0;
-}
-
-// One Jacobi rotation zeroing A[p][q] of a symmetric N x N matrix (row-major), accumulated into V's columns.
-template <int N, typename P>
-__device__ __forceinline__ void jacobi_rotate(P A, P V, int p, int q) {
-    const double apq = A[p * N + q];
-    if (apq == 0.0) return;
-    const double theta = (A[q * N + q] - A[p * N + p]) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    for (int k = 0; k < N; k++) {            // A <- A J
-        const double akp = A[k * N + p], akq = A[k * N + q];
-        A[k * N + p] = c * akp - s * akq;
-        A[k * N + q] = s * akp + c * akq;
-    }
-    for (int k = 0; k < N; k++) {            // A <- J^T A
-        const double apk = A[p * N + k], aqk = A[q * N + k];
-        A[p * N + k] = c * apk - s * aqk;
-        A[q * N + k] = s * apk + c * aqk;
-    }
-    A[p * N + q] = 0.0;
-    A[q * N + p] = 0.0;
-    for (int k = 0; k < N; k++) {            // V <- V J
-        const double vkp = V[k * N + p], vkq = V[k * N + q];
-        V[k * N + p] = c * vkp - s * vkq;
-        V[k * N + q] = s * vkp + c * vkq;
-    }
-}
-
-// 3 x 3 symmetric eigen-decomposition in registers: eigenvalues on A's diagonal, eigenvectors in V's columns
-__device__ __forceinline__ void jacobi3(double A[9], double V[9]) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 10; sweep++) {
-        jacobi_rotate<3>(A, V, 0, 1);
-        jacobi_rotate<3>(A, V, 0, 2);
-        jacobi_rotate<3>(A, V, 1, 2);
-    }
 }
 
 // Closest essential matrix (singular values (s, s, 0)) of e, scaled to unit Frobenius norm: (u1 v1^T + u2 v2^T) / sqrt(2),

@@ -272,7 +272,7 @@ def test_ba_schur_is_in_the_product_build_and_has_no_float_atomics():
     src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
     assert "ba_schur.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "ba_schur.hip")).read()
-    src += open(os.path.join(ROOT, "aria_slam_amd", "csrc", "stage_handle.h")).read()
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "solver_device.h"))
     assert "getenv" not in src
     # the only atomics are integer ones: the count of the used observations, the track builder's lowest match index
     # (a minimum) and the error word

@@ -257,7 +257,9 @@ def test_the_table_covers_the_rejected_trial_path():
     from aria_slam_amd import graph_ref as G
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "graph_optimize.hip")).read()
     lanes = int(re.search(r"GRAPH_BLOCK\s*=\s*(\d+)", src).group(1))
-    assert lanes == 512 and int(re.search(r"GRAPH_MAX_TRIALS\s*=\s*(\d+)", src).group(1)) == G.MAX_TRIALS == 10
+    shared = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "solver_device.h")).read()      # the trial cap of both LM kernels
+    assert "trial < LM_MAX_TRIALS" in src
+    assert lanes == 512 and int(re.search(r"LM_MAX_TRIALS\s*=\s*(\d+)", shared).group(1)) == G.MAX_TRIALS == 10
     on_chip_edges = 544                      # the on-chip form of the one-vertex-per-lane solver holds this many
     seen = set()
     for c in GC.CASES:
@@ -362,7 +364,7 @@ def test_graph_optimize_is_in_the_product_build_and_has_no_float_atomics():
     assert "graph_optimize.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "graph_optimize.hip")).read()
     # the rules below follow the code into the shared headers this file includes
-    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h") if '#include "%s"' % h in src)
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h", "solver_device.h") if '#include "%s"' % h in src)
     assert "getenv" not in src
     # the only atomics are the integer ones of the adjacency build (counts and fill cursors) and the error word
     atomics = re.findall(r"atomic\w+\(&?\s*([\w.\[\]>-]+)", src)

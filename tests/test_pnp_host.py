@@ -222,7 +222,7 @@ def test_pnp_ransac_is_in_the_product_build_and_reads_no_environment():
     src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
     assert "pnp_ransac.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "pnp_ransac.hip")).read()
-    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h"))
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h", "solver_device.h"))
     assert "getenv" not in src
     assert "atomicAdd(float" not in src and "atomicAdd(double" not in src
 
@@ -240,15 +240,46 @@ def test_host_adapters_build_with_the_pnp_estimator(aria):
     assert os.path.exists(os.path.join(pkg, "euroc_frontend"))
 
 
-def test_the_3x3_jacobi_is_the_two_view_stage_s():
-    """pnp_ransac.hip carries its own copy of jacobi_rotate / jacobi3 (moving them into a shared header would have to be
-    shown not to change the two-view kernels' instructions): the two texts must stay equal."""
-    def text(name):
-        s = open(os.path.join(ROOT, "aria_slam_amd", "csrc", name)).read()
-        a = s.index("template <int N, typename P>\n__device__ __forceinline__ void jacobi_rotate")
-        b = s.index("jacobi_rotate<3>(A, V, 1, 2);", a)
-        return s[a:s.index("}\n}", b) + 3]
-    a, b = text("pose_ransac.hip"), text("pnp_ransac.hip")
-    assert "jacobi3" in a and a.count("\n") > 30
-    strip = lambda t: "\n".join(l for l in t.splitlines() if not l.lstrip().startswith("//"))   # noqa: E731
-    assert strip(a) == strip(b)
+# functions elsewhere in csrc that share a name with a shared helper and are another function: other arguments, another
+# summation order (merging them would change bits). Keyed by their parameter list, so a copy of the shared form still counts.
+OTHER_FORMS = {
+    ("block_sum", "pnp_ransac.hip", "double (&acc)[N], double (*wave)[N], double* out"),
+    ("block_sum", "traj_eval.hip", "T (&v)[N], T* lds"),
+    ("wave_sum", "orb_kernels.hip", "int v"),
+}
+
+
+def _definitions(code):
+    """[(name, parameter list or None)] of the functions, constants, structs and vector typedefs a source text defines."""
+    out = [(m.group(1), " ".join(m.group(2).split()))
+           for m in re.finditer(r"^[ \t]*__(?:device|host)__[^\n;(]*?\b(\w+)\(([^)]*(?:\([^)]*\)[^)]*)*)\)\s*\{", code, re.M)]
+    for stmt in re.findall(r"^[ \t]*constexpr\s+\w+\s+(\w+\s*=[^;(]*);", code, re.M):
+        out += [(n, None) for n in re.findall(r"(\w+)\s*=", stmt)]
+    out += [(n, None) for n in re.findall(r"^[ \t]*struct\s+(\w+)\s*\{", code, re.M)]
+    out += [(n, None) for n in re.findall(r"^[ \t]*typedef\s[^;]*?\b(\w+)\s+__attribute__\(\(ext_vector_type", code, re.M)]
+    return out
+
+
+def test_shared_device_helpers_have_one_definition():
+    """Every helper of solver_device.h, and the packed-int16 helpers of orb_device.h, is defined once among csrc/*.hip and
+    csrc/*.h, in its shared header, and every .hip that uses it includes that header: no second copy to drift from the first."""
+    csrc = os.path.join(ROOT, "aria_slam_amd", "csrc")
+    strip = lambda t: re.sub(r"//[^\n]*", "", t)   # noqa: E731
+    code = {f: strip(open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    # the names at file scope of solver_device.h (LmDamping's members are indented and belong to it)
+    unindented = "\n".join(ln for ln in code["solver_device.h"].splitlines() if not ln.startswith((" ", "\t")))
+    solver = sorted({n for n, _ in _definitions(unindented)})
+    assert set(solver) >= {"jacobi_rotate", "jacobi3", "wave_sum", "block_sum2", "block_sum", "block_max", "tri6", "exp_so3",
+                           "LmDamping", "LM_MAX_TRIALS", "STOP_ITERATIONS", "STOP_TRIALS", "STOP_INVALID"}, solver
+    shared = [(n, "solver_device.h") for n in solver]
+    shared += [(n, "orb_device.h") for n in ("short2v", "pk_min_i16", "pk_max_i16", "pk_sub_i16", "pk_add_i16")]
+    for name, header in shared:
+        where = [f for f, text in code.items() for n, params in _definitions(text)
+                 if n == name and (name, f, params) not in OTHER_FORMS]
+        assert where == [header], (name, where)
+        own = {f for n, f, _ in OTHER_FORMS if n == name}        # these may use their own function of that name
+        for f, text in code.items():
+            if f.endswith(".hip") and f not in own and re.search(r"\b%s\b" % name, text):
+                assert '#include "%s"' % header in text, (name, f)
+    found = {(n, f, p) for f, text in code.items() for n, p in _definitions(text)}
+    assert OTHER_FORMS <= found, OTHER_FORMS - found            # no stale exception

@@ -167,7 +167,7 @@ def test_pose_ransac_is_in_the_product_build_and_reads_no_environment():
     assert "pose_ransac.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "pose_ransac.hip")).read()
     # the rules below follow the code into the shared headers this file includes
-    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h") if '#include "%s"' % h in src)
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h", "solver_device.h") if '#include "%s"' % h in src)
     assert "getenv" not in src
 
 
