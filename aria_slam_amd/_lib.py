@@ -97,6 +97,9 @@ EXPORTS = [
     # local bundle adjustment (batched windows, Schur-complement LM over poses and points), additive to ABI 4
     "aria_ba_default_config", "aria_ba_create", "aria_ba_destroy", "aria_ba_stream", "aria_ba_check",
     "aria_ba_optimize", "aria_ba_optimize_batch_device", "aria_ba_debug_linearize", "aria_ba_window_from_chain_device",
+    # ray casting of the TSDF volume (depth, normal, gray and shaded views at a batch of poses), additive to ABI 4
+    "aria_ray_default_config", "aria_ray_create", "aria_ray_destroy", "aria_ray_stream", "aria_ray_check",
+    "aria_ray_update_from_volume_device", "aria_ray_cast_batch_device", "aria_ray_cast", "aria_ray_algorithmic_bytes",
 ]
 
 
@@ -324,6 +327,18 @@ TSDF_VOXEL_DTYPE = np.dtype([("tsdf", "<f4"), ("weight", "<u2"), ("gray", "u1"),
 TSDF_POINT_DTYPE = np.dtype([("X", "<f4", (3,)), ("gray", "u1"), ("axis", "u1"), ("weight", "<u2")])
 
 
+class RayConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int),
+                ("nz", C.c_int), ("min_weight", C.c_int), ("skip", C.c_int), ("voxel", C.c_float), ("origin", C.c_float * 3),
+                ("near", C.c_float), ("far", C.c_float), ("step", C.c_float), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double)]
+
+
+# aria_ray_view (16 bytes) and the ARIA_RAY_* plane bits of aria_ray_algorithmic_bytes
+RAY_VIEW_DTYPE = np.dtype([("n_hit", "<i4"), ("n_ended", "<i4"), ("nearest", "<f4"), ("valid", "<i4")])
+RAY_DEPTH, RAY_NORMAL, RAY_GRAY, RAY_SHADE = 1, 2, 4, 8
+
+
 class NavConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int),
                 ("nz", C.c_int), ("up_axis", C.c_int), ("band0", C.c_int), ("band1", C.c_int), ("min_weight", C.c_int),
@@ -533,6 +548,8 @@ def load_library():
         _bind_pnp(L)
     if hasattr(L, "aria_ba_create"):
         _bind_ba(L)
+    if hasattr(L, "aria_ray_create"):
+        _bind_ray(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -682,6 +699,16 @@ def _bind_tsdf(L):
     L.aria_tsdf_volume_bytes.argtypes = [i, i, i]
     L.aria_tsdf_algorithmic_bytes.restype = i64
     L.aria_tsdf_algorithmic_bytes.argtypes = [i, i, i, i, i, i]
+
+
+def _bind_ray(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "ray")
+    L.aria_ray_update_from_volume_device.argtypes = [p, p]
+    L.aria_ray_cast_batch_device.argtypes = [p, p, p, i, i, i, p, i64, i, p, i64, i, p, i64, i, p, i64, i, p]
+    L.aria_ray_cast.argtypes = [p, p, i, i, p, p, p, p, p]
+    L.aria_ray_algorithmic_bytes.restype = i64
+    L.aria_ray_algorithmic_bytes.argtypes = [i, i, i, i]
 
 
 def _bind_nav(L):

@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--bundle FILE3] [--bundle-window N]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--alerts FILE]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -120,6 +120,14 @@
 // middle of the band, and exactly one line "plan <status> <cost> <cells>" is printed (status 0 OK, 1 UNREACHABLE, 2 OUT_OF_GRID;
 // FILE is then empty). Without the flag nothing of this runs and every output is byte-identical.
 //
+// --render PREFIX [--render-every N] (needs --volume): ray casting of the volume on the device (include/aria_orb_hip.h, "ray
+// casting of the volume"; aria_hip/HipVolumeRenderer.hpp). After the volume is built it is cast at every N-th (default 10) of
+// the poses a frame was integrated at, in batches of at most 64 views (one batch up to that), at the frame's size and the volume's intrinsics, with the stage's defaults
+// (0.3 to 10 m, step = the voxel). Per view PREFIX_<frame>_depth.pgm (16-bit, millimetres, most significant byte first, 0 = no
+// hit) and PREFIX_<frame>_shade.pgm (8-bit, the head-light shade) are written, <frame> being the frame's index in the
+// sequence, and exactly one line "render <views> <hit pixels>" is printed. Without the flag nothing of this runs and every
+// other output is byte-identical.
+//
 // --alerts FILE (needs --dense): obstacle alerts on the device (include/aria_orb_hip.h, "obstacle alerts"; aria_hip/
 // HipObstacleAlerter.hpp). Every frame's dense depth map goes through a HipObstacleAlerter of the frame's size with the stage's
 // defaults (the band is the lower three quarters of the image; nobody has tuned them on a recording), at the timestamp
@@ -159,6 +167,7 @@
 #include "aria_hip/MapTracker.hpp"
 #include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/HipPathPlanner.hpp"
+#include "aria_hip/HipVolumeRenderer.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
 #include "aria_hip/HipDenseStereo.hpp"
 #include "aria_hip/HipRectifier.hpp"
@@ -198,8 +207,10 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--alerts file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
                              "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
+                             "  --render prefix: the --volume map cast at every n-th integrated pose (--render-every n, default 10; needs --volume):\n"
+                             "                   prefix_<frame>_depth.pgm (16-bit mm) and prefix_<frame>_shade.pgm per view\n"
                              "  --plan file: a path over the --volume map from the cell under the first camera of the --pose chain to the cell under the last\n"
                              "               (needs --volume): one x y z line per path cell\n"
                              "  --volume file.ply: dense depth fusion of the --dense depth maps along the --pose chain (needs --pose, --stereo, --dense): the surface\n"
@@ -225,7 +236,8 @@ int main(int argc, char** argv) {
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
-    std::string stereo_file, dense_file, volume_file, plan_file, alerts_file;
+    std::string stereo_file, dense_file, volume_file, plan_file, alerts_file, render_prefix;
+    int render_every = 10;
     double voxel = 0.05;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--legacy-order")) legacy = true;
@@ -254,6 +266,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--voxel") && i + 1 < argc) voxel = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--plan") && i + 1 < argc) plan_file = argv[++i];
         else if (!std::strcmp(argv[i], "--alerts") && i + 1 < argc) alerts_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--render") && i + 1 < argc) render_prefix = argv[++i];
+        else if (!std::strcmp(argv[i], "--render-every") && i + 1 < argc) render_every = std::atoi(argv[++i]);
         else max_features = std::atoi(argv[i]);
     }
     if (devices < 1) devices = 1;
@@ -310,6 +324,10 @@ int main(int argc, char** argv) {
     }
     if (!plan_file.empty() && volume_file.empty()) {
         std::fprintf(stderr, "--plan needs --volume file.ply (the map it plans over)\n");
+        return 1;
+    }
+    if (!render_prefix.empty() && (volume_file.empty() || render_every < 1)) {
+        std::fprintf(stderr, "--render needs --volume file.ply (the map it casts) and --render-every >= 1\n");
         return 1;
     }
     if (!alerts_file.empty() && dense_file.empty()) {
@@ -393,6 +411,7 @@ int main(int argc, char** argv) {
     long long volume_points = 0, volume_observed = 0;   // --volume
     long long alert_events = 0, alert_frames = 0;       // --alerts
     std::vector<std::string> alert_lines;
+    long long render_views = 0, render_hits = 0;        // --render
     aria_nav_record plan_record{ARIA_NAV_INF, 0, 0, ARIA_NAV_OUT_OF_GRID};   // --plan: a sequence without frames has no start
     // --optimize: the reference's PoseGraphOptimizer over the device (euroc_eval.cpp:211-215, 235, 282-288)
     std::unique_ptr<adapters::hip::HipPoseGraphOptimizer> graph;
@@ -500,6 +519,8 @@ int main(int argc, char** argv) {
             std::unique_ptr<adapters::hip::HipDenseStereo> dense_stereo;   // --dense: made at the first pair, for its size
             std::unique_ptr<adapters::hip::HipTsdfVolume> volume;          // --volume: centred on the first camera, the world origin
             adapters::hip::DenseDepth dense_map;
+            std::vector<std::pair<std::size_t, std::array<double, 12>>> integrated;   // --render: frame index and [R|t] of each integration
+            int render_w = 0, render_h = 0;
             adapters::hip::RecordingAudioFeedback alert_audio;             // --alerts: made at the first pair, for its size
             std::unique_ptr<adapters::hip::HipObstacleAlerter> alerter;
             if (!volume_file.empty()) {
@@ -607,8 +628,13 @@ int main(int argc, char** argv) {
                             last_vertex[i] = (long long)i;
                         }
                         // --volume: this frame's depth map at the updated pose, when the translation carries a metric scale
-                        if (volume && stereo_lines[i].scale_valid)
-                            volume->integrate(dense_map.depth.data(), fw, fh, current_pose.data(), gray.data());
+                        if (volume && stereo_lines[i].scale_valid &&
+                            volume->integrate(dense_map.depth.data(), fw, fh, current_pose.data(), gray.data()) && !render_prefix.empty()) {
+                            std::array<double, 12> e;
+                            std::copy(current_pose.begin(), current_pose.begin() + 12, e.begin());
+                            integrated.emplace_back(i, e);
+                            render_w = fw; render_h = fh;
+                        }
                         if (mapper && r.previous)                          // euroc_eval.cpp:218-222: view 1 = previous frame
                             mapper->triangulateExtrinsics(*r.previous, *r.frame, r.matches, c.data(), current_pose.data(),
                                                           prev_gray.data(), pw, ph, fc.frontend.legacy_order);
@@ -647,6 +673,29 @@ int main(int argc, char** argv) {
             if (volume) {
                 volume_points = (long long)volume->exportPLY(volume_file);
                 volume_observed = (long long)volume->observedVoxels();
+            }
+            if (volume && !render_prefix.empty() && !integrated.empty()) {
+                adapters::hip::HipVolumeRenderer renderer(adapters::hip::VolumeRendererConfig::fromVolume(*volume));
+                renderer.update(*volume);
+                std::vector<std::size_t> frames;
+                std::vector<std::array<double, 12>> views;
+                for (std::size_t k = 0; k < integrated.size(); k += (std::size_t)render_every) {
+                    frames.push_back(integrated[k].first);
+                    views.push_back(integrated[k].second);
+                }
+                const std::size_t px = (std::size_t)render_w * render_h, chunk = 64;   // one batch up to 64 views: bounded memory on a long sequence
+                for (std::size_t c0 = 0; c0 < frames.size(); c0 += chunk) {
+                    const std::size_t n = std::min(chunk, frames.size() - c0);
+                    const std::vector<std::array<double, 12>> part(views.begin() + (std::ptrdiff_t)c0, views.begin() + (std::ptrdiff_t)(c0 + n));
+                    const adapters::hip::RenderedViews rv = renderer.castBatch(part, render_w, render_h);
+                    for (std::size_t k = 0; k < n; k++) {
+                        const std::string base = render_prefix + "_" + std::to_string(frames[c0 + k]);
+                        adapters::hip::HipVolumeRenderer::writeDepthPGM(base + "_depth.pgm", rv.depth.data() + k * px, render_w, render_h);
+                        adapters::hip::HipVolumeRenderer::writeGrayPGM(base + "_shade.pgm", rv.shade.data() + k * px, render_w, render_h);
+                    }
+                    render_hits += rv.hitPixels();
+                }
+                render_views = (long long)frames.size();
             }
             std::ofstream pf;
             if (!plan_file.empty()) pf.open(plan_file);                    // created even when there is nothing to plan
@@ -909,6 +958,7 @@ int main(int argc, char** argv) {
     }
     if (!volume_file.empty()) std::printf("volume %lld %lld\n", volume_points, volume_observed);
     if (!plan_file.empty()) std::printf("plan %d %d %d\n", plan_record.status, plan_record.cost, plan_record.n_cells);
+    if (!render_prefix.empty()) std::printf("render %lld %lld\n", render_views, render_hits);
     if (!alerts_file.empty()) {
         std::ofstream af(alerts_file);
         for (const std::string& l : alert_lines) af << l << '\n';

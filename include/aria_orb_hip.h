@@ -1314,8 +1314,9 @@ int64_t aria_dense_algorithmic_bytes(int width, int height);
 /* ---- dense depth fusion: the fp32 depth maps of aria_dense_* integrated along the trajectory into one truncated signed
  * distance volume in HBM, and the surface points read back out of it. The reference has no code for it (its roadmap items
  * H17, H20 and H22 sit on such a map), so the NumPy restatement aria_slam_amd/tsdf_ref.py is the definition and the device
- * equals it bit for bit. Out of scope: normals, marching-cubes meshes, ray casting, bilinear depth lookup, volume shifting
- * or hashing, and any alert logic (path planning is the stage below). Additive to ABI 4.
+ * equals it bit for bit. Out of scope: marching-cubes meshes, bilinear depth lookup, volume shifting or hashing,
+ * and any alert logic (path planning is the stage below; normals and ray casting are the stage "ray casting of the
+ * volume"). Additive to ABI 4.
  *
  * Unless stated otherwise the arithmetic is fp32, one rounding per operation, no contraction, in exactly the order written.
  * 1. Volume. nx, ny, nz voxels, each a multiple of 8 in 8..1024; `voxel` the edge in metres (> 0); origin[3] the world
@@ -1906,6 +1907,121 @@ int   aria_ba_window_from_chain_device(aria_ba_t h, aria_map_t map, const int* d
                                        const aria_match* d_matches, const int* d_nmatches, int match_cap, int query_is_first,
                                        int point_cap, int obs_cap, double* d_points, aria_ba_obs* d_obs, int* d_point_src,
                                        int* d_n_points, int* d_n_obs);
+
+/* ---- ray casting of the volume: a ray per pixel marched through the aria_tsdf_voxel records of the dense depth fusion, the
+ * zero crossing refined on the trilinear interpolant and that interpolant differentiated: a predicted fp32 depth map at a
+ * pose (what aria_alert_measure_batch_device and aria_tsdf_integrate_batch_device read), world-frame normals, the fused gray
+ * and a head-light shade, batched over views. The reference has no code for it (its roadmap item H21 is a 3-D viewer), so the
+ * NumPy restatement aria_slam_amd/ray_ref.py is the definition and the device equals it bit for bit. The stage owns no
+ * volume: it is handed the records in HBM with their geometry. Out of scope: meshes, adaptive step lengths, colour, shadows
+ * or any second light, frame-to-model ICP (this stage makes it possible; it is the follow-up), and a volume that changes
+ * between aria_ray_update_from_volume_device and a cast. Additive to ABI 4.
+ *
+ * All arithmetic is fp32, one rounding per operation, no contraction, in exactly the order written. A NaN fails every
+ * comparison. lerp(a, b, w) means a + w * (b - a).
+ * 1. Geometry and configuration. nx, ny, nz, voxel, origin[3], min_weight as in rule 1 of the dense depth fusion, with the
+ *   same validity ranges. The records' tsdf values must not be infinite (the fusion writes values in [-1, 1]): with an
+ *   infinite tsdf the depth of a hit can be a NaN, whose bits are not defined, and `nearest` of its view is then not defined
+ *   either. inv_voxel = 1.0f / voxel. fx, fy, cx, cy are doubles converted once with (float); inv_fx = 1.0f / fx,
+ *   inv_fy = 1.0f / fy. near > 0, far >= near, step > 0, all finite. n_steps = (int)floorf((far - near) / step) + 1 must lie
+ *   in 1..8192.
+ * 2. View. World-to-camera [R|t], 12 doubles row-major, each converted with (float) once (the record
+ *   aria_tsdf_integrate_batch_device reads). The camera centre per world axis a, with r0a, r1a, r2a column a of R:
+ *   o_a = -((r0a*t0 + r1a*t1) + r2a*t2); in grid units og_a = (o_a - origin_a) * inv_voxel - 0.5f. Views may carry a byte
+ *   mask: a view whose byte is 0 is skipped, and nothing of it is written, its record included. An unmasked view with a
+ *   non-finite extrinsic writes zeros to every requested output and valid = 0 to its record, and defers ARIA_E_INVALID; the
+ *   other views are unaffected.
+ * 3. Pixel (u, v), integers in [0, W) x [0, H): a = ((float)u - cx) * inv_fx; b = ((float)v - cy) * inv_fy;
+ *   d_a = (r0a*a + r1a*b) + r2a; dg_a = d_a * inv_voxel. The ray is parameterised by the camera depth z, what the depth maps
+ *   of aria_dense_* hold and what the integration compares against.
+ * 4. Sample k. z_k = near + (float)k * step, formed from k, never accumulated. g_a = og_a + z_k * dg_a; r_a = rintf(g_a),
+ *   half-even. The sample is inside when 0 <= r_a <= n_a - 1 on all three axes, compared in float; its voxel is then
+ *   ((int)r_x, (int)r_y, (int)r_z). It is seen when inside and weight >= min_weight.
+ * 5. Walk. k runs from 0 to n_steps - 1, ascending. The first k whose sample is seen with tsdf < 0 ends the walk. It is a
+ *   hit when k >= 1 and sample k-1 is seen with tsdf >= 0; otherwise a miss (a back face, or a start inside a surface). No
+ *   such k is also a miss. A miss writes depth 0.0f, normal (0, 0, 0), gray 0, shade 0.
+ * 6. Trilinear value T(z). g as in rule 4; b_a = floorf(g_a); f_a = g_a - b_a. T is defined when 0 <= b_a and
+ *   b_a + 1.0f <= n_a - 1 on all three axes and all eight voxels b + {0,1}^3 have weight >= min_weight; t_xyz are their tsdf
+ *   values. c00 = lerp(t000, t100, f_x), c10 = lerp(t010, t110, f_x), c01 = lerp(t001, t101, f_x), c11 = lerp(t011, t111, f_x);
+ *   c0 = lerp(c00, c10, f_y), c1 = lerp(c01, c11, f_y); T = lerp(c0, c1, f_z).
+ * 7. Refinement of a hit at k. F0 = T(z_{k-1}), F1 = T(z_k). If both are defined and F0 >= 0 && F1 <= 0 && F0 > F1 then
+ *   A = F0, B = F1; otherwise A = tsdf_{k-1}, B = tsdf_k, the nearest-voxel values of rule 5, for which A - B > 0 always
+ *   holds. alpha = A / (A - B); depth = z_{k-1} + alpha * step.
+ * 8. Gray. alpha < 0.5f ? gray_{k-1} : gray_k, of the nearest voxels of rule 5 (the extraction's rule).
+ * 9. Normal, in the world frame, pointing to the free side. Take the cell of rule 6 at z = depth with its f and c**; if that
+ *   cell is not defined the normal is 0. Gx = lerp(lerp(t100 - t000, t110 - t010, f_y), lerp(t101 - t001, t111 - t011, f_y),
+ *   f_z); Gy = lerp(c10 - c00, c11 - c01, f_z); Gz = c1 - c0; len = sqrtf((Gx*Gx + Gy*Gy) + Gz*Gz). If len > 0,
+ *   n = (Gx/len, Gy/len, Gz/len), else n = 0. The gradient is that of ONE cell's interpolant and therefore discontinuous
+ *   across cells: neighbouring pixels on either side of a cell face can differ by the jump of the one-sided differences.
+ * 10. Shade, a head-light Lambert term. With a non-zero normal dl = sqrtf((d_x*d_x + d_y*d_y) + d_z*d_z),
+ *   c = fabsf((n_x*d_x + n_y*d_y) + n_z*d_z) / dl, shade = (uint8_t)rintf(fminf(255.0f, 255.0f * c)); otherwise 0.
+ * 11. View record aria_ray_view: n_hit; n_ended, the walks that ended at a seen negative sample, hit or not; nearest, the
+ *   least hit depth, 0.0f without a hit; valid. The counts and the minimum are taken with integer operations (the minimum on
+ *   the bit pattern of the positive float); no float atomics.
+ * Outputs per view, each pointer NULL = that plane is not written, each with its own stride per view and pitch per row, in
+ *   elements: fp32 depth; fp32 normals, three floats per pixel interleaved (stride in floats, pitch in pixels); uint8 gray;
+ *   uint8 shade. Elements outside W x H are never written.
+ * Determinism. One writer per pixel. The result is bitwise independent of batch position, of the split into calls, of
+ *   `skip` and of the run.
+ * Known limit. Where the trilinear pair of rule 7 does not bracket the crossing that the nearest-voxel walk found -- in a
+ *   grid-aligned view whose samples fall on the crossing itself this is the common case -- rule 7 falls back to the
+ *   nearest-voxel values, which costs up to about half a step of depth error (DESIGN.md section 26 has the measured
+ *   figures). */
+typedef struct aria_ray_s* aria_ray_t;
+typedef struct {
+    int32_t  n_hit;
+    int32_t  n_ended;           /* walks that ended at a seen negative sample, hit or not                          */
+    float    nearest;           /* the least hit depth, 0.0f without a hit                                         */
+    int32_t  valid;             /* 0: a non-finite extrinsic                                                       */
+} aria_ray_view;                /* 16 bytes                                                                        */
+#define ARIA_RAY_DEPTH 1
+#define ARIA_RAY_NORMAL 2
+#define ARIA_RAY_GRAY 4
+#define ARIA_RAY_SHADE 8
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_ray_config)                                                      */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    int      nx, ny, nz;        /* the volume's geometry; default 256 x 256 x 128                                  */
+    int      min_weight;        /* default 2, 1..65535                                                             */
+    int      skip;              /* default 1: no record load in a brick of 8 x 8 x 8 voxels that cannot end a walk; */
+                                /* 0 = every sample loads its record. The same bytes either way.                   */
+    float    voxel;             /* default 0.05 m                                                                  */
+    float    origin[3];         /* default (-6.4, -6.4, 0)                                                         */
+    float    near, far, step;   /* default 0.3, 10, 0.05 (= voxel): 195 samples                                    */
+    double   fx, fy, cx, cy;    /* intrinsics of the views (default EuRoC cam0)                                    */
+} aria_ray_config;              /* 96 bytes                                                                        */
+
+void  aria_ray_default_config(aria_ray_config* cfg);
+/* ARIA_E_INVALID for a bad field (n_steps outside 1..8192 included), before any device is touched. */
+int   aria_ray_create(const aria_ray_config* cfg, aria_ray_t* out);
+void  aria_ray_destroy(aria_ray_t h);
+void* aria_ray_stream(aria_ray_t h);
+/* Synchronises the handle's stream and returns, once, the deferred ARIA_E_INVALID of an unmasked view with a non-finite
+ * extrinsic since the last check. */
+int   aria_ray_check(aria_ray_t h);
+/* Remembers d_voxels (nx*ny*nz records in the layout of rule 1 of the dense depth fusion, aria_tsdf_device_voxels of a volume
+ * of this geometry) and builds the skip words from them: one bit per brick of 8 x 8 x 8 voxels, set when the brick holds a
+ * voxel with weight >= min_weight && tsdf < 0. The records must stay where they are, and unchanged, until the casts that
+ * follow have run; after the volume changed, update again. Enqueued on the handle's stream, no synchronisation. */
+int   aria_ray_update_from_volume_device(aria_ray_t h, const aria_tsdf_voxel* d_voxels);
+/* Rules 2-11 for n_views views of width x height. View f reads its 12 doubles at d_extrinsics + 12*f and its byte at
+ * d_view_mask + f (NULL = every view), and writes depth at d_depth + f*depth_stride + v*depth_pitch + u, its normal at
+ * d_normal + f*normal_stride + 3*(v*normal_pitch + u), gray and shade like depth, and its record at d_views + f; every
+ * output pointer, d_views included, may be NULL. width, height in 1..16384, n_views in 0..65535, a pitch at least the width
+ * and, for n_views > 1, a stride that holds a view. A cast before the first update is ARIA_E_INVALID, refused before
+ * anything is enqueued. Enqueued on the handle's stream, no synchronisation. */
+int   aria_ray_cast_batch_device(aria_ray_t h, const double* d_extrinsics, const uint8_t* d_view_mask, int n_views, int width,
+                                 int height, float* d_depth, int64_t depth_stride, int depth_pitch, float* d_normal,
+                                 int64_t normal_stride, int normal_pitch, uint8_t* d_gray, int64_t gray_stride, int gray_pitch,
+                                 uint8_t* d_shade, int64_t shade_stride, int shade_pitch, aria_ray_view* d_views);
+/* One view into dense host buffers (width*height elements each, 3*width*height for the normals; any may be NULL); blocks.
+ * A non-finite extrinsic returns ARIA_E_INVALID, with zeros in the outputs. */
+int   aria_ray_cast(aria_ray_t h, const double* extrinsics, int width, int height, float* depth, float* normal, uint8_t* gray,
+                    uint8_t* shade, aria_ray_view* view);
+/* The bytes one cast writes: (4, 12, 1, 1 per pixel for the planes of the ARIA_RAY_* bit set `planes`) * width * height
+ * + 16, times n_views; ARIA_E_INVALID for sizes the cast refuses. Host only, no handle. */
+int64_t aria_ray_algorithmic_bytes(int width, int height, int n_views, int planes);
 
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
