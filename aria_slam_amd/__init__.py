@@ -12,6 +12,7 @@ from .dense import HipDenseStereo
 from .detect import HipObjectDetector
 from .evaluate import HipTrajectoryEvaluator, load_ground_truth_csv
 from .frontend import HipMatcher, OrbHipExtractor, flag_keypoints_device
+from .icp import HipDenseTracker
 from .fusion import HipImuPreintegrator, HipSensorFusion
 from .fundamental import HipFundamentalEstimator, verify_loop_candidates
 from .mapper import HipMapper
@@ -29,4 +30,4 @@ __all__ = ["KP_DTYPE", "MATCH_DTYPE", "AriaError", "abi_version", "build_library
            "status_string", "level_info", "resize_table", "algorithmic_bytes", "synth_frame_pair", "synth_sequence", "HipMatcher", "OrbHipExtractor", "flag_keypoints_device",
            "HipPoseEstimator", "HipMapper", "HipFundamentalEstimator", "verify_loop_candidates", "HipPoseGraphOptimizer",
            "HipSensorFusion", "HipImuPreintegrator", "HipTrajectoryEvaluator", "load_ground_truth_csv", "HipObjectDetector",
-           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner", "HipObstacleAlerter", "HipPnPEstimator", "HipBundleAdjuster", "HipVolumeRenderer"]
+           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner", "HipObstacleAlerter", "HipPnPEstimator", "HipBundleAdjuster", "HipVolumeRenderer", "HipDenseTracker"]

@@ -100,6 +100,9 @@ EXPORTS = [
     # ray casting of the TSDF volume (depth, normal, gray and shaded views at a batch of poses), additive to ABI 4
     "aria_ray_default_config", "aria_ray_create", "aria_ray_destroy", "aria_ray_stream", "aria_ray_check",
     "aria_ray_update_from_volume_device", "aria_ray_cast_batch_device", "aria_ray_cast", "aria_ray_algorithmic_bytes",
+    # frame-to-model tracking (batched point-to-plane ICP against the ray-cast model view), additive to ABI 4
+    "aria_icp_default_config", "aria_icp_create", "aria_icp_destroy", "aria_icp_stream", "aria_icp_check",
+    "aria_icp_track_batch_device", "aria_icp_track", "aria_icp_debug_system_device", "aria_icp_algorithmic_bytes",
 ]
 
 
@@ -334,6 +337,19 @@ class RayConfig(C.Structure):
                 ("cx", C.c_double), ("cy", C.c_double)]
 
 
+class IcpConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("min_depth", C.c_float), ("max_depth", C.c_float), ("dist_max", C.c_float),
+                ("reach", C.c_float), ("min_corr", C.c_int), ("n_levels", C.c_int), ("min_pivot", C.c_double), ("eps", C.c_double),
+                ("stride", C.c_int * 4), ("iterations", C.c_int * 4)]
+
+
+# aria_icp_result (32 bytes)
+ICP_RESULT_DTYPE = np.dtype([("valid", "<i4"), ("iterations_run", "<i4"), ("n_corr", "<i4"), ("level", "<i4"), ("rms", "<f8"),
+                             ("delta", "<f8")])
+ICP_TERMS = 29
+
+
 # aria_ray_view (16 bytes) and the ARIA_RAY_* plane bits of aria_ray_algorithmic_bytes
 RAY_VIEW_DTYPE = np.dtype([("n_hit", "<i4"), ("n_ended", "<i4"), ("nearest", "<f4"), ("valid", "<i4")])
 RAY_DEPTH, RAY_NORMAL, RAY_GRAY, RAY_SHADE = 1, 2, 4, 8
@@ -550,6 +566,8 @@ def load_library():
         _bind_ba(L)
     if hasattr(L, "aria_ray_create"):
         _bind_ray(L)
+    if hasattr(L, "aria_icp_create"):
+        _bind_icp(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -699,6 +717,16 @@ def _bind_tsdf(L):
     L.aria_tsdf_volume_bytes.argtypes = [i, i, i]
     L.aria_tsdf_algorithmic_bytes.restype = i64
     L.aria_tsdf_algorithmic_bytes.argtypes = [i, i, i, i, i, i]
+
+
+def _bind_icp(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "icp")
+    L.aria_icp_track_batch_device.argtypes = [p, p, i64, i, p, i64, i, p, i64, i, p, p, p, i, i, i, p, p]
+    L.aria_icp_track.argtypes = [p, p, p, p, p, p, i, i, p, p]
+    L.aria_icp_debug_system_device.argtypes = [p, p, i64, i, p, i64, i, p, i64, i, p, p, i, i, i, i, p]
+    L.aria_icp_algorithmic_bytes.restype = i64
+    L.aria_icp_algorithmic_bytes.argtypes = [p, i, i, i]
 
 
 def _bind_ray(L):

@@ -1,0 +1,584 @@
+// Frame-to-model tracking: batched point-to-plane ICP of a live depth map against the depth map and normals that the ray
+// casting stage predicted from the volume. Semantics in include/aria_orb_hip.h ("frame-to-model tracking");
+// aria_slam_amd/icp_ref.py is the definition and this file equals it bit for bit.
+//
+// k_icp_prepare     a lane per frame: the non-finite check (deferred-error OR), Trel = Tm o T0^-1 in fp64, its fp32 copy and
+//                   the fp32 Rm into the 128-byte record the hot path reads, the start values of the state.
+// k_icp_accumulate  the hot path. Grid (tiles of the level, frames). A wave owns 16 x 4 level pixels PPL times over (a
+//                   workgroup of four waves 16 x 16 PPL): a lane gathers its strided live pixels, projects them, gathers
+//                   the model depth and normal at (vm, um) and keeps the 28 partial sums in fp64 REGISTERS: each term is an
+//                   integer below 2^38.6 (rule 4), so a lane's and a wave's sums stay below 2^53 and are exact, hence the
+//                   same integers in any order. The wave pays ONE reduction (icp_commit, above the pasted text) and one
+//                   int64 atomic per term into one of the frame's ICP_ROWS accumulator rows. The frame record comes through
+//                   scalar loads; the workgroups of a finished, lost or level-skipping frame exit wave-uniformly. No float
+//                   atomics, no LDS, no barrier, no scratch.
+// k_icp_solve       a lane per frame: rule 5 on the summed rows (which it zeroes for the next iteration), and on the call's
+//                   last iteration rule 6.
+// k_icp_set / k_icp_export  aria_icp_debug_system_device: the caller's Trel into the frame records; the rows summed out.
+// Plain HIP C++. The text from "namespace {" to the C-ABI section also compiles for the host
+// (tests/test_icp_kernel_emulation.py); the one cross-lane step, icp_commit, sits above it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "common.h"
+#include "solver_device.h"
+#include "stage_handle.h"
+
+using namespace aria;
+
+static_assert(sizeof(aria_icp_result) == 32, "aria_icp_result is 32 bytes");
+static_assert(sizeof(aria_icp_config) == 120, "aria_icp_config is 120 bytes");
+
+// Rule 4 for one wave: the 28 fp64 partial sums (integers below 2^53, so every order gives the same value) and the count
+// by a butterfly, then one int64 atomic per non-zero term from lane 0. Every lane of the wave calls it. The host emulation
+// replaces it by its lane-serial form.
+__device__ __forceinline__ void icp_commit(long long* row, double (&s)[28], int count) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) count += __shfl_xor(count, d, 64);
+    if (count == 0) return;                                            // wave-uniform: no correspondence, every term is zero
+#pragma unroll
+    for (int k = 0; k < 28; k++) s[k] = wave_sum(s[k]);
+    if ((threadIdx.x & 63) != 0) return;
+#pragma unroll
+    for (int k = 0; k < 28; k++)
+        if (s[k] != 0.0) atomicAdd(reinterpret_cast<unsigned long long*>(row + k), (unsigned long long)(long long)s[k]);
+    atomicAdd(reinterpret_cast<unsigned long long*>(row + 28), (unsigned long long)count);
+}
+
+namespace {
+
+constexpr int ICP_BLOCK = 256;
+constexpr int ICP_TILE_W = 16, ICP_TILE_H = 16;                      // level pixels of a workgroup per pass: a wave is 16 x 4
+constexpr int ICP_PPL = 4;                                           // passes, i.e. pixels per lane, of the shipped schedule
+constexpr int ICP_ROWS = 8, ICP_ROW = 32;                            // accumulator rows per frame, int64 words per row (29 used)
+constexpr int ICP_MAX_IMAGE = 16384, ICP_MAX_PIXELS = 1 << 24, ICP_MAX_FRAMES = 4096, ICP_MAX_ITERATIONS = 64;
+constexpr int ERRBIT_ICP_INPUT = 1;
+constexpr int ICP_MASKED = 0, ICP_ACTIVE = 1, ICP_LOST = 2, ICP_BAD = 3;
+
+// What the kernels take by value.
+struct IcpParams {
+    float fx, fy, cx, cy, inv_fx, inv_fy;
+    float min_depth, max_depth, dist2, reach2;
+    int min_corr, pad;
+    double min_pivot, eps;
+};
+
+// Host side, inside the text the host emulation compiles, so that it runs on the constants the library uses.
+inline IcpParams icp_params(const double K[4], float min_depth, float max_depth, float dist_max, float reach, int min_corr,
+                            double min_pivot, double eps) {
+    IcpParams P{};
+    P.fx = (float)K[0]; P.fy = (float)K[1]; P.cx = (float)K[2]; P.cy = (float)K[3];
+    P.inv_fx = 1.0f / P.fx; P.inv_fy = 1.0f / P.fy;
+    P.min_depth = min_depth; P.max_depth = max_depth;
+    P.dist2 = dist_max * dist_max; P.reach2 = reach * reach;
+    P.min_corr = min_corr; P.min_pivot = min_pivot; P.eps = eps;
+    return P;
+}
+
+// One frame as the hot path reads it: 32 words at a workgroup-uniform address.
+struct IcpFrame {
+    float T[12];                    // Trel as fp32, [R|t] row-major
+    float Rm[9];
+    int state;                      // ICP_MASKED, ICP_ACTIVE, ICP_LOST, ICP_BAD
+    int skip_level;                 // the level whose rest this frame skips (rule 5), -1: none
+    int pad[9];
+};
+static_assert(sizeof(IcpFrame) == 128, "IcpFrame is 128 bytes");
+
+// One frame as the solve keeps it.
+struct IcpState {
+    double Trel[12];
+    aria_icp_result rec;
+};
+
+__device__ __forceinline__ bool icp_finite(double v) { return fabs(v) <= DBL_MAX; }
+
+__device__ __forceinline__ void icp_publish(const double* Trel, IcpFrame& F) {
+    for (int k = 0; k < 12; k++) F.T[k] = (float)Trel[k];
+}
+
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_prepare(const double* __restrict__ model_ext, const double* __restrict__ guess,
+                                                           const uint8_t* __restrict__ mask, int n_frames, IcpFrame* __restrict__ frames,
+                                                           IcpState* __restrict__ states, int* err) {
+    const int f = (int)(blockIdx.x * ICP_BLOCK + threadIdx.x);
+    if (f >= n_frames) return;
+    const double* Tm = model_ext + 12 * (int64_t)f;
+    const double* T0 = guess + 12 * (int64_t)f;
+    const bool wanted = !mask || mask[f] != 0;
+    bool fin = true;
+    for (int k = 0; k < 12; k++) fin = fin && icp_finite(Tm[k]) && icp_finite(T0[k]);
+    if (wanted && !fin) atomicOr(err, ERRBIT_ICP_INPUT);
+    IcpFrame F{};
+    IcpState S{};
+    for (int i = 0; i < 3; i++)                                       // rule 1
+        for (int j = 0; j < 3; j++) S.Trel[4 * i + j] = (Tm[4 * i] * T0[4 * j] + Tm[4 * i + 1] * T0[4 * j + 1]) + Tm[4 * i + 2] * T0[4 * j + 2];
+    for (int i = 0; i < 3; i++)
+        S.Trel[4 * i + 3] = Tm[4 * i + 3] - ((S.Trel[4 * i] * T0[3] + S.Trel[4 * i + 1] * T0[7]) + S.Trel[4 * i + 2] * T0[11]);
+    icp_publish(S.Trel, F);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) F.Rm[3 * i + j] = (float)Tm[4 * i + j];
+    F.state = !wanted ? ICP_MASKED : fin ? ICP_ACTIVE : ICP_BAD;
+    F.skip_level = -1;
+    frames[f] = F;
+    states[f] = S;
+}
+
+// aria_icp_debug_system_device: the caller's Trel instead of rule 1.
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_set(const double* __restrict__ model_ext, const double* __restrict__ trel, int n_frames,
+                                                       IcpFrame* __restrict__ frames) {
+    const int f = (int)(blockIdx.x * ICP_BLOCK + threadIdx.x);
+    if (f >= n_frames) return;
+    IcpFrame F{};
+    icp_publish(trel + 12 * (int64_t)f, F);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) F.Rm[3 * i + j] = (float)model_ext[12 * (int64_t)f + 4 * i + j];
+    F.state = ICP_ACTIVE;
+    F.skip_level = -1;
+    frames[f] = F;
+}
+
+// The three maps of a call.
+struct IcpMaps {
+    const float* live; const float* depth; const float* normal;
+    int64_t live_stride, depth_stride, normal_stride;
+    int live_pitch, depth_pitch, normal_pitch;
+    int W, H;
+};
+
+// Rule 3 for the live pixel (u, v) of frame f: false when it is rejected, else J[6] and r.
+__device__ __forceinline__ bool icp_pixel(const IcpParams& P, const IcpFrame& F, const IcpMaps& m, int64_t f, int u, int v, float J[6], float& r) {
+    const float D = m.live[f * m.live_stride + (int64_t)v * m.live_pitch + u];
+    if (!(D >= P.min_depth && D <= P.max_depth)) return false;
+    const float px = (((float)u - P.cx) * P.inv_fx) * D, py = (((float)v - P.cy) * P.inv_fy) * D;
+    const float qx = ((F.T[0] * px + F.T[1] * py) + F.T[2] * D) + F.T[3];
+    const float qy = ((F.T[4] * px + F.T[5] * py) + F.T[6] * D) + F.T[7];
+    const float qz = ((F.T[8] * px + F.T[9] * py) + F.T[10] * D) + F.T[11];
+    if (!(qz > 0.0f)) return false;
+    const float iz = 1.0f / qz;
+    const float um = rintf((P.fx * qx) * iz + P.cx), vm = rintf((P.fy * qy) * iz + P.cy);
+    if (!(um >= 0.0f && um <= (float)(m.W - 1) && vm >= 0.0f && vm <= (float)(m.H - 1))) return false;
+    const int ui = (int)um, vi = (int)vm;
+    const float Mz = m.depth[f * m.depth_stride + (int64_t)vi * m.depth_pitch + ui];
+    const float* Nw = m.normal + f * m.normal_stride + 3 * ((int64_t)vi * m.normal_pitch + ui);
+    const float N0 = Nw[0], N1 = Nw[1], N2 = Nw[2];
+    if (!(Mz > 0.0f) || !(N0 != 0.0f || N1 != 0.0f || N2 != 0.0f)) return false;
+    const float n0 = (F.Rm[0] * N0 + F.Rm[1] * N1) + F.Rm[2] * N2;
+    const float n1 = (F.Rm[3] * N0 + F.Rm[4] * N1) + F.Rm[5] * N2;
+    const float n2 = (F.Rm[6] * N0 + F.Rm[7] * N1) + F.Rm[8] * N2;
+    if (!((n0 * n0 + n1 * n1) + n2 * n2 <= 1.5f)) return false;
+    const float e0 = qx - ((um - P.cx) * P.inv_fx) * Mz, e1 = qy - ((vm - P.cy) * P.inv_fy) * Mz, e2 = qz - Mz;
+    if (!((e0 * e0 + e1 * e1) + e2 * e2 <= P.dist2)) return false;
+    if (!((qx * qx + qy * qy) + qz * qz <= P.reach2)) return false;
+    r = (n0 * e0 + n1 * e1) + n2 * e2;
+    J[0] = qy * n2 - qz * n1;
+    J[1] = qz * n0 - qx * n2;
+    J[2] = qx * n1 - qy * n0;
+    J[3] = n0; J[4] = n1; J[5] = n2;
+    return true;
+}
+
+// grid: (ceil(Wl / 16), ceil(Hl / (16 PPL)), frames) for the level's Wl x Hl pixels. Rule 4: J * 2^12 and r * 2^18 are exact in
+// fp64 and so are their products, which ARE the scaled products of the rule; rint rounds them half-even.
+template <int PPL>
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_accumulate(IcpParams P, const IcpFrame* __restrict__ frames, IcpMaps m, int stride, int level,
+                                                              long long* __restrict__ acc) {
+    const int64_t f = (int64_t)blockIdx.z;
+    const IcpFrame& F = frames[f];                                    // workgroup-uniform
+    if (F.state != ICP_ACTIVE || F.skip_level == level) return;
+    const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int u = ((int)blockIdx.x * ICP_TILE_W + (lane & 15)) * stride;
+    double s[28];
+#pragma unroll
+    for (int k = 0; k < 28; k++) s[k] = 0.0;
+    int count = 0;
+#pragma unroll
+    for (int pass = 0; pass < PPL; pass++) {
+        const int v = ((((int)blockIdx.y * PPL + pass) * 4 + wave) * 4 + (lane >> 4)) * stride;
+        float J[6], r;
+        if (u < m.W && v < m.H && icp_pixel(P, F, m, f, u, v, J, r)) {
+            double j[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) j[i] = ldexp((double)J[i], 12);
+            const double rs = ldexp((double)r, 18);
+            int k = 0;
+#pragma unroll
+            for (int a = 0; a < 6; a++)
+#pragma unroll
+                for (int b = a; b < 6; b++) s[k++] += rint(j[a] * j[b]);
+#pragma unroll
+            for (int a = 0; a < 6; a++) s[21 + a] += rint(j[a] * rs);
+            s[27] += rint(rs * rs);
+            count++;
+        }
+    }
+    const int row = (int)((blockIdx.x + blockIdx.y * 3u + (unsigned)wave) & (ICP_ROWS - 1));
+    icp_commit(acc + (f * ICP_ROWS + row) * ICP_ROW, s, count);
+}
+
+// aria_icp_debug_system_device: a lane per frame sums the rows out and zeroes them.
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_export(int n_frames, long long* __restrict__ acc, long long* __restrict__ out) {
+    const int f = (int)(blockIdx.x * ICP_BLOCK + threadIdx.x);
+    if (f >= n_frames) return;
+    long long* a = acc + (int64_t)f * ICP_ROWS * ICP_ROW;
+    for (int k = 0; k < 29; k++) {
+        long long S = 0;
+        for (int r = 0; r < ICP_ROWS; r++) {
+            S += a[r * ICP_ROW + k];
+            a[r * ICP_ROW + k] = 0;
+        }
+        out[29 * (int64_t)f + k] = S;
+    }
+}
+
+// Rule 5 on the 29 integers: false when the frame is lost. x: delta.
+__device__ __forceinline__ bool icp_cholesky(const IcpParams& P, const long long S[29], double x[6]) {
+    double A[21], b[6], L[36], y[6];
+#pragma unroll
+    for (int k = 0; k < 21; k++) A[k] = (double)S[k] / 16777216.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) b[k] = (double)S[21 + k] / 1073741824.0;
+    const double thr = P.min_pivot * (double)S[28];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double s = A[tri6(j, j)];
+#pragma unroll
+        for (int q = 0; q < j; q++) s = s - L[6 * j + q] * L[6 * j + q];
+        if (!(s > thr)) return false;
+        L[6 * j + j] = sqrt(s);
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            s = A[tri6(j, i)];
+#pragma unroll
+            for (int q = 0; q < j; q++) s = s - L[6 * i + q] * L[6 * j + q];
+            L[6 * i + j] = s / L[6 * j + j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double s = -b[i];
+#pragma unroll
+        for (int q = 0; q < i; q++) s = s - L[6 * i + q] * y[q];
+        y[i] = s / L[6 * i + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double s = y[i];
+#pragma unroll
+        for (int q = i + 1; q < 6; q++) s = s - L[6 * q + i] * x[q];
+        x[i] = s / L[6 * i + i];
+    }
+    return true;
+}
+
+// Trel <- [Cayley(delta[0:3]) | delta[3:6]] o Trel.
+__device__ __forceinline__ void icp_advance(double T[12], const double x[6]) {
+    const double a[3] = {0.5 * x[0], 0.5 * x[1], 0.5 * x[2]};
+    const double s = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+    const double den = 1.0 + s, one = 1.0 - s;
+    const double K[9] = {0.0, -a[2], a[1], a[2], 0.0, -a[0], -a[1], a[0], 0.0};
+    double R[9], out[12];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            R[3 * i + j] = i == j ? (one + 2.0 * (a[i] * a[i])) / den : (2.0 * (a[i] * a[j]) + 2.0 * K[3 * i + j]) / den;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[4 * i + j] = (R[3 * i] * T[j] + R[3 * i + 1] * T[4 + j]) + R[3 * i + 2] * T[8 + j];
+        out[4 * i + 3] = ((R[3 * i] * T[3] + R[3 * i + 1] * T[7]) + R[3 * i + 2] * T[11]) + x[3 + i];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) T[k] = out[k];
+}
+
+// grid: ceil(n_frames / 256). level: of the accumulation that just ran; last: the call's final iteration, rule 6 is due.
+__global__ __launch_bounds__(ICP_BLOCK) void k_icp_solve(IcpParams P, int n_frames, int level, int last, IcpFrame* __restrict__ frames,
+                                                         IcpState* __restrict__ states, long long* __restrict__ acc,
+                                                         const double* __restrict__ model_ext, const double* __restrict__ guess,
+                                                         double* __restrict__ out, aria_icp_result* __restrict__ results) {
+    const int f = (int)(blockIdx.x * ICP_BLOCK + threadIdx.x);
+    if (f >= n_frames) return;
+    int state = frames[f].state;
+    if (state == ICP_MASKED) return;
+    IcpState* st = states + f;
+    if (state == ICP_ACTIVE && frames[f].skip_level != level) {
+        long long* a = acc + (int64_t)f * ICP_ROWS * ICP_ROW;
+        long long S[29];
+#pragma unroll
+        for (int k = 0; k < 29; k++) {
+            long long sum = 0;
+#pragma unroll
+            for (int r = 0; r < ICP_ROWS; r++) {
+                sum += a[r * ICP_ROW + k];
+                a[r * ICP_ROW + k] = 0;
+            }
+            S[k] = sum;
+        }
+        const int count = (int)S[28];
+        aria_icp_result rec = st->rec;
+        rec.iterations_run += 1;
+        rec.n_corr = count;
+        rec.level = level;
+        rec.rms = count > 0 ? sqrt(((double)S[27] / 68719476736.0) / (double)count) : 0.0;
+        rec.delta = 0.0;
+        double x[6];
+        if (count < P.min_corr || !icp_cholesky(P, S, x)) {
+            state = ICP_LOST;
+            frames[f].state = ICP_LOST;
+        } else {
+            rec.delta = sqrt(((((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) + x[3] * x[3]) + x[4] * x[4]) + x[5] * x[5]);
+            double T[12];
+#pragma unroll
+            for (int k = 0; k < 12; k++) T[k] = st->Trel[k];
+            icp_advance(T, x);
+#pragma unroll
+            for (int k = 0; k < 12; k++) {
+                st->Trel[k] = T[k];
+                frames[f].T[k] = (float)T[k];
+            }
+            if (rec.delta < P.eps) frames[f].skip_level = level;
+        }
+        st->rec = rec;
+    }
+    if (!last) return;
+    const double* Tm = model_ext + 12 * (int64_t)f;
+    aria_icp_result rec = st->rec;                                     // zero for ICP_BAD
+    rec.valid = state == ICP_ACTIVE ? 1 : 0;
+    if (results) results[f] = rec;
+    if (!out || state == ICP_BAD) return;
+    double* o = out + 12 * (int64_t)f;
+    if (state == ICP_LOST) {
+        for (int k = 0; k < 12; k++) o[k] = guess[12 * (int64_t)f + k];
+        return;
+    }
+    const double* T = st->Trel;                                        // rule 6
+    const double d[3] = {Tm[3] - T[3], Tm[7] - T[7], Tm[11] - T[11]};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) o[4 * i + j] = (T[i] * Tm[j] + T[4 + i] * Tm[4 + j]) + T[8 + i] * Tm[8 + j];
+        o[4 * i + 3] = (T[i] * d[0] + T[4 + i] * d[1]) + T[8 + i] * d[2];
+    }
+}
+
+}  // namespace
+
+// ---- C-ABI --------------------------------------------------------------------------------------------------------------
+struct aria_icp_s : StageHandle {
+    aria_icp_config cfg{};
+    IcpParams P{};
+    bool plain = false;                                        // variants build: one pixel per lane, one atomic set per wave
+    DeviceBuffer<IcpFrame> d_frames;
+    DeviceBuffer<IcpState> d_states;
+    DeviceBuffer<long long> d_acc;
+    // host-form staging (grow-only)
+    DeviceBuffer<float> d_live, d_depth, d_normal;
+    double* d_pose = nullptr;                                  // Tm, T0, T: 36 doubles
+    aria_icp_result* d_rec = nullptr;
+};
+
+namespace {
+
+bool icp_bad_config(const aria_icp_config* c) {
+    if (!c || c->struct_size != (int)sizeof(aria_icp_config)) return true;
+    for (double v : {c->fx, c->fy, c->cx, c->cy})
+        if (!std::isfinite(v)) return true;
+    if (c->fx == 0 || c->fy == 0) return true;
+    if (!std::isfinite(c->min_depth) || !std::isfinite(c->max_depth) || !(c->min_depth > 0) || !(c->min_depth <= c->max_depth)) return true;
+    if (!(c->dist_max > 0) || !(c->dist_max <= 1.0f) || !(c->reach > 0) || !(c->reach <= 128.0f)) return true;
+    if (c->min_corr < 1 || c->min_corr > ICP_MAX_PIXELS) return true;
+    if (!std::isfinite(c->min_pivot) || !(c->min_pivot >= 0) || !std::isfinite(c->eps) || !(c->eps >= 0)) return true;
+    if (c->n_levels < 1 || c->n_levels > ARIA_ICP_MAX_LEVELS) return true;
+    int total = 0;
+    for (int l = 0; l < c->n_levels; l++) {
+        const int s = c->stride[l];
+        if (s < 1 || s > 16 || (s & (s - 1))) return true;
+        if (c->iterations[l] < 0 || c->iterations[l] > ICP_MAX_ITERATIONS) return true;
+        total += c->iterations[l];
+    }
+    return total < 1;
+}
+
+bool icp_bad_size(int width, int height, int n_frames) {
+    return n_frames < 0 || n_frames > ICP_MAX_FRAMES || width < 1 || height < 1 || width > ICP_MAX_IMAGE || height > ICP_MAX_IMAGE ||
+           (int64_t)width * height > ICP_MAX_PIXELS;
+}
+
+bool icp_bad_plane(const void* p, int64_t stride, int pitch, int width, int height, int n_frames, int per_pixel) {
+    return !p || pitch < width || (n_frames > 1 && stride < per_pixel * ((int64_t)pitch * (height - 1) + width));
+}
+
+int icp_reserve(aria_icp_s* h, int n_frames) {
+    int rc;
+    if ((rc = h->d_frames.reserve(h->stream, (size_t)n_frames)) != ARIA_OK) return rc;
+    if ((rc = h->d_states.reserve(h->stream, (size_t)n_frames)) != ARIA_OK) return rc;
+    return h->d_acc.reserve(h->stream, (size_t)n_frames * ICP_ROWS * ICP_ROW);
+}
+
+void icp_launch_accumulate(aria_icp_s* h, const IcpMaps& m, int n_frames, int stride, int level) {
+    const int wl = (m.W + stride - 1) / stride, hl = (m.H + stride - 1) / stride;
+    const int ppl = h->plain ? 1 : ICP_PPL;
+    const dim3 grid((unsigned)((wl + ICP_TILE_W - 1) / ICP_TILE_W), (unsigned)((hl + ICP_TILE_H * ppl - 1) / (ICP_TILE_H * ppl)), (unsigned)n_frames);
+    if (h->plain)
+        hipLaunchKernelGGL(k_icp_accumulate<1>, grid, dim3(ICP_BLOCK), 0, h->stream, h->P, (const IcpFrame*)h->d_frames, m, stride, level,
+                           (long long*)h->d_acc);
+    else
+        hipLaunchKernelGGL(k_icp_accumulate<ICP_PPL>, grid, dim3(ICP_BLOCK), 0, h->stream, h->P, (const IcpFrame*)h->d_frames, m, stride,
+                           level, (long long*)h->d_acc);
+}
+
+}  // namespace
+
+extern "C" {
+
+void aria_icp_default_config(aria_icp_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->struct_size = (int)sizeof(aria_icp_config);
+    c->fx = 458.654; c->fy = 457.296; c->cx = 367.215; c->cy = 248.375;   // EuRoC cam0
+    c->min_depth = 0.3f; c->max_depth = 10.0f; c->dist_max = 0.1f; c->reach = 64.0f;
+    c->min_corr = 64; c->min_pivot = 5e-6; c->eps = 1e-6;
+    c->n_levels = 3;
+    c->stride[0] = 4; c->stride[1] = 2; c->stride[2] = 1;
+    c->iterations[0] = 4; c->iterations[1] = 5; c->iterations[2] = 10;
+}
+
+int64_t aria_icp_algorithmic_bytes(const aria_icp_config* c, int width, int height, int n_frames) {
+    if (icp_bad_config(c) || icp_bad_size(width, height, n_frames)) return ARIA_E_INVALID;
+    int64_t px = 0;
+    for (int l = 0; l < c->n_levels; l++) {
+        const int s = c->stride[l];
+        px += (int64_t)c->iterations[l] * ((width + s - 1) / s) * ((height + s - 1) / s);
+    }
+    return (20 * px + 320) * n_frames;
+}
+
+int aria_icp_create(const aria_icp_config* c, aria_icp_t* out) {
+    if (!out || icp_bad_config(c)) return ARIA_E_INVALID;
+    *out = nullptr;
+    aria_icp_s* h = new (std::nothrow) aria_icp_s();
+    if (!h) return ARIA_E_OOM;
+    h->cfg = *c;
+    const double K[4] = {c->fx, c->fy, c->cx, c->cy};
+    h->P = icp_params(K, c->min_depth, c->max_depth, c->dist_max, c->reach, c->min_corr, c->min_pivot, c->eps);
+    if (const char* s = aria_getenv("ARIA_ICP_SCHEDULE")) h->plain = !std::strcmp(s, "plain");   // variants build: A/B
+    int rc = stage_open(h, c->device, c->stream, 1, "aria_icp_create");
+    if (rc == ARIA_OK) {
+        hipError_t e = hipMalloc((void**)&h->d_pose, 36 * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_rec, sizeof(aria_icp_result));
+        if (e != hipSuccess) rc = hip_fail(e, "aria_icp_create", __FILE__, __LINE__);
+    }
+    if (rc != ARIA_OK) {
+        aria_icp_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return ARIA_OK;
+}
+
+void aria_icp_destroy(aria_icp_t h) {
+    if (!h) return;
+    stage_close(h, {h->d_pose, h->d_rec});
+    delete h;
+}
+
+void* aria_icp_stream(aria_icp_t h) { return h ? (void*)h->stream : nullptr; }
+
+int aria_icp_check(aria_icp_t h) {
+    if (!h) return ARIA_E_INVALID;
+    int bits = 0;
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
+    return (bits & ERRBIT_ICP_INPUT) ? ARIA_E_INVALID : ARIA_OK;
+}
+
+int aria_icp_track_batch_device(aria_icp_t h, const float* d_depth, int64_t depth_stride, int depth_pitch, const float* d_model_depth,
+                                int64_t model_depth_stride, int model_depth_pitch, const float* d_model_normal, int64_t normal_stride,
+                                int normal_pitch, const double* d_model_extrinsics, const double* d_guess, const uint8_t* d_mask,
+                                int n_frames, int width, int height, double* d_extrinsics_out, aria_icp_result* d_results) {
+    if (!h || icp_bad_size(width, height, n_frames)) return ARIA_E_INVALID;
+    if (n_frames == 0) return ARIA_OK;
+    if (!d_model_extrinsics || !d_guess || icp_bad_plane(d_depth, depth_stride, depth_pitch, width, height, n_frames, 1) ||
+        icp_bad_plane(d_model_depth, model_depth_stride, model_depth_pitch, width, height, n_frames, 1) ||
+        icp_bad_plane(d_model_normal, normal_stride, normal_pitch, width, height, n_frames, 3))
+        return ARIA_E_INVALID;
+    ARIA_HIP(hipSetDevice(h->device));
+    int rc;
+    if ((rc = icp_reserve(h, n_frames)) != ARIA_OK) return rc;
+    ARIA_HIP(hipMemsetAsync(h->d_acc, 0, (size_t)n_frames * ICP_ROWS * ICP_ROW * sizeof(long long), h->stream));
+    const dim3 per_frame((unsigned)((n_frames + ICP_BLOCK - 1) / ICP_BLOCK));
+    hipLaunchKernelGGL(k_icp_prepare, per_frame, dim3(ICP_BLOCK), 0, h->stream, d_model_extrinsics, d_guess, d_mask, n_frames,
+                       (IcpFrame*)h->d_frames, (IcpState*)h->d_states, h->d_err);
+    ARIA_HIP(hipGetLastError());
+    const IcpMaps m{d_depth, d_model_depth, d_model_normal, depth_stride, model_depth_stride, normal_stride,
+                    depth_pitch, model_depth_pitch, normal_pitch, width, height};
+    int total = 0, done = 0;
+    for (int l = 0; l < h->cfg.n_levels; l++) total += h->cfg.iterations[l];
+    for (int l = 0; l < h->cfg.n_levels; l++)
+        for (int it = 0; it < h->cfg.iterations[l]; it++) {
+            icp_launch_accumulate(h, m, n_frames, h->cfg.stride[l], l);
+            ARIA_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_icp_solve, per_frame, dim3(ICP_BLOCK), 0, h->stream, h->P, n_frames, l, ++done == total ? 1 : 0,
+                               (IcpFrame*)h->d_frames, (IcpState*)h->d_states, (long long*)h->d_acc, d_model_extrinsics, d_guess,
+                               d_extrinsics_out, d_results);
+            ARIA_HIP(hipGetLastError());
+        }
+    return ARIA_OK;
+}
+
+int aria_icp_debug_system_device(aria_icp_t h, const float* d_depth, int64_t depth_stride, int depth_pitch, const float* d_model_depth,
+                                 int64_t model_depth_stride, int model_depth_pitch, const float* d_model_normal, int64_t normal_stride,
+                                 int normal_pitch, const double* d_model_extrinsics, const double* d_trel, int n_frames, int width,
+                                 int height, int stride, int64_t* d_system) {
+    if (!h || icp_bad_size(width, height, n_frames) || stride < 1 || stride > 16 || (stride & (stride - 1))) return ARIA_E_INVALID;
+    if (n_frames == 0) return ARIA_OK;
+    if (!d_model_extrinsics || !d_trel || !d_system || icp_bad_plane(d_depth, depth_stride, depth_pitch, width, height, n_frames, 1) ||
+        icp_bad_plane(d_model_depth, model_depth_stride, model_depth_pitch, width, height, n_frames, 1) ||
+        icp_bad_plane(d_model_normal, normal_stride, normal_pitch, width, height, n_frames, 3))
+        return ARIA_E_INVALID;
+    ARIA_HIP(hipSetDevice(h->device));
+    int rc;
+    if ((rc = icp_reserve(h, n_frames)) != ARIA_OK) return rc;
+    ARIA_HIP(hipMemsetAsync(h->d_acc, 0, (size_t)n_frames * ICP_ROWS * ICP_ROW * sizeof(long long), h->stream));
+    const dim3 per_frame((unsigned)((n_frames + ICP_BLOCK - 1) / ICP_BLOCK));
+    hipLaunchKernelGGL(k_icp_set, per_frame, dim3(ICP_BLOCK), 0, h->stream, d_model_extrinsics, d_trel, n_frames, (IcpFrame*)h->d_frames);
+    ARIA_HIP(hipGetLastError());
+    const IcpMaps m{d_depth, d_model_depth, d_model_normal, depth_stride, model_depth_stride, normal_stride,
+                    depth_pitch, model_depth_pitch, normal_pitch, width, height};
+    icp_launch_accumulate(h, m, n_frames, stride, 0);
+    ARIA_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_icp_export, per_frame, dim3(ICP_BLOCK), 0, h->stream, n_frames, (long long*)h->d_acc, (long long*)d_system);
+    ARIA_HIP(hipGetLastError());
+    return ARIA_OK;
+}
+
+int aria_icp_track(aria_icp_t h, const float* depth, const float* model_depth, const float* model_normal, const double* model_extrinsics,
+                   const double* guess, int width, int height, double* extrinsics_out, aria_icp_result* result) {
+    if (!h || !depth || !model_depth || !model_normal || !model_extrinsics || !guess || icp_bad_size(width, height, 1)) return ARIA_E_INVALID;
+    ARIA_HIP(hipSetDevice(h->device));
+    const size_t n = (size_t)width * height;
+    int rc;
+    if ((rc = h->d_live.reserve(h->stream, n)) != ARIA_OK) return rc;
+    if ((rc = h->d_depth.reserve(h->stream, n)) != ARIA_OK) return rc;
+    if ((rc = h->d_normal.reserve(h->stream, 3 * n)) != ARIA_OK) return rc;
+    ARIA_HIP(hipMemcpyAsync(h->d_live, depth, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    ARIA_HIP(hipMemcpyAsync(h->d_depth, model_depth, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    ARIA_HIP(hipMemcpyAsync(h->d_normal, model_normal, 3 * n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    ARIA_HIP(hipMemcpyAsync(h->d_pose, model_extrinsics, 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    ARIA_HIP(memcpy_on(h->stream, h->d_pose + 12, guess, 12 * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = aria_icp_track_batch_device(h, h->d_live, 0, width, h->d_depth, 0, width, h->d_normal, 0, width, h->d_pose, h->d_pose + 12,
+                                          nullptr, 1, width, height, h->d_pose + 24, h->d_rec)) != ARIA_OK)
+        return rc;
+    if ((rc = aria_icp_check(h)) != ARIA_OK) return rc;
+    if (extrinsics_out) ARIA_HIP(memcpy_on(h->stream, extrinsics_out, h->d_pose + 24, 12 * sizeof(double), hipMemcpyDeviceToHost));
+    if (result) ARIA_HIP(memcpy_on(h->stream, result, h->d_rec, sizeof(aria_icp_result), hipMemcpyDeviceToHost));
+    return ARIA_OK;
+}
+
+}  // extern "C"

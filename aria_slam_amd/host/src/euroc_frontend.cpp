@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--bundle FILE3] [--bundle-window N]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE] [--track-dense FILE2]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -128,6 +128,13 @@
 // sequence, and exactly one line "render <views> <hit pixels>" is printed. Without the flag nothing of this runs and every
 // other output is byte-identical.
 //
+// --track-dense FILE2 (needs --volume): frame-to-model tracking on the device (include/aria_orb_hip.h, "frame-to-model tracking";
+// aria_hip/DenseTracker.hpp). A DenseTracker with a volume of its own (the --volume geometry) takes every frame's dense depth
+// map: it predicts the pose from the --pose chain's step, casts its volume there, tracks the depth map against that view, falls
+// back to the prediction where the tracker reports valid = 0, and integrates the frame at the result. FILE2 gets one TUM line
+// per frame, "track-dense tracked A lost B -> FILE2" is printed and the count of lost frames goes to stderr; with --eval the
+// trajectory is scored as "track-dense". Without the flag nothing of this runs and every other output is byte-identical.
+//
 // --alerts FILE (needs --dense): obstacle alerts on the device (include/aria_orb_hip.h, "obstacle alerts"; aria_hip/
 // HipObstacleAlerter.hpp). Every frame's dense depth map goes through a HipObstacleAlerter of the frame's size with the stage's
 // defaults (the band is the lower three quarters of the image; nobody has tuned them on a recording), at the timestamp
@@ -168,6 +175,7 @@
 #include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/HipPathPlanner.hpp"
 #include "aria_hip/HipVolumeRenderer.hpp"
+#include "aria_hip/DenseTracker.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
 #include "aria_hip/HipDenseStereo.hpp"
 #include "aria_hip/HipRectifier.hpp"
@@ -208,6 +216,7 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
+                             "  --track-dense file2: frame-to-model tracking of the --dense depth maps against a volume of its own (needs --volume): one TUM line per frame\n"
                              "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
                              "  --render prefix: the --volume map cast at every n-th integrated pose (--render-every n, default 10; needs --volume):\n"
                              "                   prefix_<frame>_depth.pgm (16-bit mm) and prefix_<frame>_shade.pgm per view\n"
@@ -236,7 +245,7 @@ int main(int argc, char** argv) {
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
-    std::string stereo_file, dense_file, volume_file, plan_file, alerts_file, render_prefix;
+    std::string stereo_file, dense_file, volume_file, plan_file, alerts_file, render_prefix, dense_track_file;
     int render_every = 10;
     double voxel = 0.05;
     for (int i = 2; i < argc; i++) {
@@ -267,6 +276,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--plan") && i + 1 < argc) plan_file = argv[++i];
         else if (!std::strcmp(argv[i], "--alerts") && i + 1 < argc) alerts_file = argv[++i];
         else if (!std::strcmp(argv[i], "--render") && i + 1 < argc) render_prefix = argv[++i];
+        else if (!std::strcmp(argv[i], "--track-dense") && i + 1 < argc) dense_track_file = argv[++i];
         else if (!std::strcmp(argv[i], "--render-every") && i + 1 < argc) render_every = std::atoi(argv[++i]);
         else max_features = std::atoi(argv[i]);
     }
@@ -328,6 +338,10 @@ int main(int argc, char** argv) {
     }
     if (!render_prefix.empty() && (volume_file.empty() || render_every < 1)) {
         std::fprintf(stderr, "--render needs --volume file.ply (the map it casts) and --render-every >= 1\n");
+        return 1;
+    }
+    if (!dense_track_file.empty() && volume_file.empty()) {
+        std::fprintf(stderr, "--track-dense needs --volume file.ply (the geometry of the map it tracks against)\n");
         return 1;
     }
     if (!alerts_file.empty() && dense_file.empty()) {
@@ -412,6 +426,8 @@ int main(int argc, char** argv) {
     long long alert_events = 0, alert_frames = 0;       // --alerts
     std::vector<std::string> alert_lines;
     long long render_views = 0, render_hits = 0;        // --render
+    std::vector<std::array<double, 16>> dense_traj(dense_track_file.empty() ? 0 : N);   // --track-dense
+    long long dense_tracked = 0, dense_lost = 0;
     aria_nav_record plan_record{ARIA_NAV_INF, 0, 0, ARIA_NAV_OUT_OF_GRID};   // --plan: a sequence without frames has no start
     // --optimize: the reference's PoseGraphOptimizer over the device (euroc_eval.cpp:211-215, 235, 282-288)
     std::unique_ptr<adapters::hip::HipPoseGraphOptimizer> graph;
@@ -518,6 +534,7 @@ int main(int argc, char** argv) {
             core::Frame right_frame;
             std::unique_ptr<adapters::hip::HipDenseStereo> dense_stereo;   // --dense: made at the first pair, for its size
             std::unique_ptr<adapters::hip::HipTsdfVolume> volume;          // --volume: centred on the first camera, the world origin
+            std::unique_ptr<adapters::hip::DenseTracker> dense_tracker;    // --track-dense: the same geometry, its own volume
             adapters::hip::DenseDepth dense_map;
             std::vector<std::pair<std::size_t, std::array<double, 12>>> integrated;   // --render: frame index and [R|t] of each integration
             int render_w = 0, render_h = 0;
@@ -531,6 +548,7 @@ int main(int argc, char** argv) {
                 vc.device = fc.hip_device;
                 vc.centreOn(0.0f, 0.0f, 0.0f);
                 volume = std::make_unique<adapters::hip::HipTsdfVolume>(vc);
+                if (!dense_track_file.empty()) dense_tracker = std::make_unique<adapters::hip::DenseTracker>(vc);
             }
             if (stereo) {
                 adapters::hip::StereoConfig sc;
@@ -595,6 +613,8 @@ int main(int argc, char** argv) {
                     }
                 }
                 if (!traj.empty()) {
+                    std::array<double, 16> chain_step{};                   // --track-dense: this frame's step of the chain, if any
+                    bool stepped = false;
                     if (r.pose && r.pose->n_pose_inliers > 10) {           // euroc_eval.cpp:191
                         std::array<double, 16> d = adapters::hip::poseMatrix(*r.pose);
                         const std::array<double, 16> c = current_pose;
@@ -614,6 +634,8 @@ int main(int argc, char** argv) {
                                 current_pose[(size_t)(a * 4 + b)] = v;     // current_pose = current_pose * delta (:206)
                             }
                         n_pose_updates++;
+                        chain_step = d;
+                        stepped = true;
                         if (!fuse_visual.empty()) {                        // euroc_eval.cpp:209: the relative R, t
                             aria_fuse_visual& v = fuse_visual[i];
                             for (int a = 0; a < 3; a++) {
@@ -640,6 +662,10 @@ int main(int argc, char** argv) {
                                                           prev_gray.data(), pw, ph, fc.frontend.legacy_order);
                     }
                     traj[i] = current_pose;
+                    if (dense_tracker) {
+                        dense_tracker->step(dense_map.depth.data(), fw, fh, stepped ? chain_step.data() : nullptr, gray.data());
+                        dense_traj[i] = dense_tracker->pose();
+                    }
                     if (graph && last_vertex[i] < 0 && i > 0) last_vertex[i] = last_vertex[i - 1];
                 }
                 if (tracker) {                                             // view 1 = previous frame: the query side in the legacy order
@@ -670,6 +696,10 @@ int main(int argc, char** argv) {
                 map_points = mapper->size();
             }
             if (tracker) track_points = tracker->mapper().size();
+            if (dense_tracker) {
+                dense_tracked = dense_tracker->framesTracked();
+                dense_lost = dense_tracker->framesLost();
+            }
             if (volume) {
                 volume_points = (long long)volume->exportPLY(volume_file);
                 volume_observed = (long long)volume->observedVoxels();
@@ -959,6 +989,11 @@ int main(int argc, char** argv) {
     if (!volume_file.empty()) std::printf("volume %lld %lld\n", volume_points, volume_observed);
     if (!plan_file.empty()) std::printf("plan %d %d %d\n", plan_record.status, plan_record.cost, plan_record.n_cells);
     if (!render_prefix.empty()) std::printf("render %lld %lld\n", render_views, render_hits);
+    if (!dense_track_file.empty()) {
+        write_tum(dense_track_file, [&](std::size_t i) { return dense_traj[i]; });
+        std::printf("track-dense tracked %lld lost %lld -> %s\n", dense_tracked, dense_lost, dense_track_file.c_str());
+        std::fprintf(stderr, "track-dense: %lld of %lld tracked frames lost\n", dense_lost, dense_tracked);
+    }
     if (!alerts_file.empty()) {
         std::ofstream af(alerts_file);
         for (const std::string& l : alert_lines) af << l << '\n';
@@ -1002,6 +1037,12 @@ int main(int argc, char** argv) {
             report = score("pose", pose_xyz.data(), ARIA_EVAL_EST_XYZ);
             if (!optimized_xyz.empty()) report = score("optimize", optimized_xyz.data(), ARIA_EVAL_EST_XYZ);
             if (!fused_states.empty()) score("fuse", fused_states.data(), ARIA_EVAL_EST_FUSE_STATE);
+            if (!dense_traj.empty()) {
+                std::vector<double> dense_xyz;
+                for (std::size_t i = 0; i < N; i++)
+                    for (int a = 0; a < 3; a++) dense_xyz.push_back(dense_traj[i][(size_t)(a * 4 + 3)]);
+                score("track-dense", dense_xyz.data(), ARIA_EVAL_EST_XYZ);
+            }
             std::printf("\nTrajectory Error:\n  ATE (RMSE): %.4f m\n  RPE (RMSE): %.4f m\n", report.ate_raw, report.rpe_raw);   // :303-305
         } catch (const std::exception& e) {
             std::fprintf(stderr, "--eval: %s\n", e.what());

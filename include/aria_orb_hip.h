@@ -2023,6 +2023,127 @@ int   aria_ray_cast(aria_ray_t h, const double* extrinsics, int width, int heigh
  * + 16, times n_views; ARIA_E_INVALID for sizes the cast refuses. Host only, no handle. */
 int64_t aria_ray_algorithmic_bytes(int width, int height, int n_views, int planes);
 
+/* ---- frame-to-model tracking: batched point-to-plane ICP of a live fp32 depth map (what aria_dense_compute_batch_device
+ * writes) against the depth map and world-frame normals aria_ray_cast_batch_device predicted from the volume, which corrects
+ * the pose the frame is then integrated at. The reference has no code for it (KinectFusion's tracking step, under its roadmap
+ * items H17 and H21), so the NumPy restatement aria_slam_amd/icp_ref.py is the definition and the device equals it bit for
+ * bit. Out of scope: a live-normal or angle compatibility test, Huber or any other weights, colour / photometric terms, depth
+ * pyramids (levels are strides on the full-resolution maps) and a motion model. Additive to ABI 4.
+ *
+ * Unless stated otherwise all arithmetic is fp32, one rounding per operation, no contraction, in exactly the order written. A
+ * NaN fails every comparison.
+ * Inputs per frame f: the live depth map D of W x H; the model view as the ray casting stage wrote it: depth M (0 = miss),
+ *   interleaved normals N in the world frame (zero = none) and the 12 doubles Tm (world to model camera) it was cast at; a
+ *   guess T0, 12 doubles, world to live camera (usually Tm itself); an optional byte mask. fx, fy, cx, cy are doubles converted
+ *   once with (float); inv_fx = 1.0f / fx, inv_fy = 1.0f / fy.
+ * 1. State. Trel = Tm o T0^-1, live camera to model camera, formed once in fp64: Rrel_ij = (Rm_i0*R0_j0 + Rm_i1*R0_j1) +
+ *   Rm_i2*R0_j2; trel_i = tm_i - ((Rrel_i0*t0_0 + Rrel_i1*t0_1) + Rrel_i2*t0_2). Its 12 doubles are converted with (float)
+ *   for the per-pixel work of each iteration, and Rm with (float) once. No world coordinate appears per pixel: a map 1 km from
+ *   the origin loses nothing.
+ * 2. Levels. Level l uses the live pixels with u % s == 0 && v % s == 0, s = stride[l], a power of two <= 16; it runs
+ *   iterations[l] in 0..64 iterations; at most 4 levels, at least one iteration in all (default strides 4, 2, 1 with 4, 5,
+ *   10 iterations). The model maps are always read at full resolution.
+ * 3. Correspondence of the live pixel (u, v) with depth D, valid when min_depth <= D <= max_depth.
+ *   p = ((((float)u - cx) * inv_fx) * D, (((float)v - cy) * inv_fy) * D, D); q_i = ((r_i0*p_x + r_i1*p_y) + r_i2*p_z) + t_i
+ *   with the fp32 Trel. Reject unless q_z > 0. iz = 1.0f / q_z; um = rintf((fx*q_x)*iz + cx), vm = rintf((fy*q_y)*iz + cy),
+ *   half-even; reject unless 0 <= um <= W - 1 and 0 <= vm <= H - 1, compared in float. Mz = M[vm, um], Nw = N[vm, um]: reject
+ *   unless Mz > 0 and some component of Nw != 0. n_i = (Rm_i0*Nw_0 + Rm_i1*Nw_1) + Rm_i2*Nw_2; reject unless
+ *   (n_0*n_0 + n_1*n_1) + n_2*n_2 <= 1.5f (the normals of the ray casting stage have length 1; the bound is what makes the
+ *   proof of rule 4 hold for any input). pm = (((um - cx) * inv_fx) * Mz, ((vm - cy) * inv_fy) * Mz, Mz); e = q - pm; reject
+ *   unless (e_0*e_0 + e_1*e_1) + e_2*e_2 <= dist_max*dist_max and (q_0*q_0 + q_1*q_1) + q_2*q_2 <= reach*reach. Residual
+ *   r = (n_0*e_0 + n_1*e_1) + n_2*e_2. J = (q x n, n): c_0 = q_1*n_2 - q_2*n_1, c_1 = q_2*n_0 - q_0*n_2,
+ *   c_2 = q_0*n_1 - q_1*n_0, each two products and one difference.
+ * 4. The system, in integers. Per frame and iteration 29 int64 sums over the correspondences: [0..20] J_i*J_j for i <= j, row
+ *   by row; [21..26] J_i*r; [27] r*r; [28] the count. Each product is formed in fp64, where the product of two fp32 values is
+ *   exact, multiplied by 2^24, 2^30 and 2^36 for the three groups (exact), rounded half-even to int64 and added. Integer
+ *   addition is associative: the sums do not depend on schedule, grid, wave order or atomics.
+ *   No overflow: a component of q x n is at most |q| |n| <= reach * sqrt(1.5) * (1 + 2^-20) <= 156.8 for reach <= 128, and
+ *   those of n are smaller, so |J_i*J_j| * 2^24 < 2^38.6; |r| <= |n| |e| <= 1.225 (1 + 2^-20) for dist_max <= 1, so
+ *   |J_i*r| * 2^30 < 2^37.6 and r*r * 2^36 < 2^36.6. With W*H <= 2^24 terms every sum stays below 2^62.6 < 2^63. Hence the
+ *   validity ranges dist_max <= 1, reach <= 128, W*H <= 2^24. (A term is also an integer below 2^53 in fp64, so a kernel may
+ *   add up to 2^14 of them exactly in fp64 before it converts: aria_slam_amd/csrc/icp_track.hip does.)
+ * 5. Solve, fp64, scalar operations in this order. A_ij = (double)S / 2^24, b_i = (double)S / 2^30 (the conversion rounds to
+ *   nearest even above 2^53); count = S[28]; rms = sqrt(((double)S[27] / 2^36) / (double)count), 0 for count 0. The frame is
+ *   LOST when count < min_corr, or at the first Cholesky pivot that is not > min_pivot * (double)count. Cholesky by columns
+ *   j = 0..5: s = A_jj, then s = s - L_jm*L_jm for m = 0..j-1; the pivot is s; L_jj = sqrt(s); for i = j+1..5: s = A_ji, then
+ *   s = s - L_im*L_jm for m = 0..j-1; L_ij = s / L_jj. Forward: s = -b_i, s = s - L_im*y_m for m = 0..i-1, y_i = s / L_ii.
+ *   Back, i = 5..0: s = y_i, s = s - L_mi*x_m for m = i+1..5, x_i = s / L_ii. delta = x;
+ *   |delta| = sqrt(((((x0*x0 + x1*x1) + x2*x2) + x3*x3) + x4*x4) + x5*x5). The rotation increment is the Cayley map of
+ *   w = delta[0:3], rational, so that the solve uses only + - * / sqrt: a = 0.5 * w, s = (a0*a0 + a1*a1) + a2*a2,
+ *   Rinc_ii = ((1 - s) + 2*(a_i*a_i)) / (1 + s), Rinc_ij = (2*(a_i*a_j) + 2*K_ij) / (1 + s) with K = [a]x. Then
+ *   Trel <- [Rinc | delta[3:6]] o Trel: R_ij = (Rinc_i0*R_0j + Rinc_i1*R_1j) + Rinc_i2*R_2j, t_i = ((Rinc_i0*t_0 + Rinc_i1*t_1)
+ *   + Rinc_i2*t_2) + delta_{3+i}. A frame whose |delta| < eps after its update skips the rest of its level. A lost frame keeps
+ *   T0 and stops.
+ * 6. Output per frame: T = Trel^-1 o Tm, 12 doubles: R_ij = (Rrel_0i*Rm_0j + Rrel_1i*Rm_1j) + Rrel_2i*Rm_2j,
+ *   t_i = (Rrel_0i*d_0 + Rrel_1i*d_1) + Rrel_2i*d_2 with d = tm - trel; a lost frame's T is T0. The record aria_icp_result:
+ *   valid; iterations_run, the accumulations solved, a losing one included; n_corr, rms and delta = |delta| (0 when lost) of
+ *   the last of them, and the level it belonged to. A frame whose mask byte is 0 writes nothing. An unmasked frame with a
+ *   non-finite Tm or T0 writes a zero record (valid = 0), no pose, and defers ARIA_E_INVALID; the other frames are unaffected.
+ * Determinism. The result is bitwise independent of batch position, of the split into calls, of the schedule and of the run. */
+typedef struct aria_icp_s* aria_icp_t;
+typedef struct {
+    int32_t  valid;             /* 0: lost (rule 5) or a non-finite pose                                           */
+    int32_t  iterations_run;
+    int32_t  n_corr;            /* correspondences of the last accumulation                                        */
+    int32_t  level;             /* the level the last accumulation belonged to                                     */
+    double   rms;               /* sqrt(sum r^2 / n_corr) of the last accumulation, in metres                      */
+    double   delta;             /* |delta| of the last solve, 0 when it lost the frame                             */
+} aria_icp_result;              /* 32 bytes                                                                        */
+#define ARIA_ICP_MAX_LEVELS 4
+#define ARIA_ICP_TERMS 29
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_icp_config)                                                      */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    double   fx, fy, cx, cy;    /* intrinsics of the live and the model maps (default EuRoC cam0)                  */
+    float    min_depth, max_depth;   /* default 0.3, 10; 0 < min_depth <= max_depth                                */
+    float    dist_max;          /* default 0.1 m, in (0, 1]                                                        */
+    float    reach;             /* default 64 m, in (0, 128]                                                       */
+    int      min_corr;          /* default 64, 1..2^24                                                             */
+    int      n_levels;          /* default 3, 1..4                                                                 */
+    double   min_pivot;         /* default 5e-6, >= 0: measured, DESIGN.md section 27                              */
+    double   eps;               /* default 1e-6, >= 0                                                              */
+    int      stride[ARIA_ICP_MAX_LEVELS];       /* default 4, 2, 1                                                 */
+    int      iterations[ARIA_ICP_MAX_LEVELS];   /* default 4, 5, 10                                                */
+} aria_icp_config;              /* 120 bytes                                                                       */
+
+void  aria_icp_default_config(aria_icp_config* cfg);
+/* ARIA_E_INVALID for a bad field, before any device is touched. */
+int   aria_icp_create(const aria_icp_config* cfg, aria_icp_t* out);
+void  aria_icp_destroy(aria_icp_t h);
+void* aria_icp_stream(aria_icp_t h);
+/* Synchronises the handle's stream and returns, once, the deferred ARIA_E_INVALID of an unmasked frame with a non-finite
+ * pose since the last check. */
+int   aria_icp_check(aria_icp_t h);
+/* Rules 1-6 for n_frames frames of width x height. Frame f reads its live depth at d_depth + f*depth_stride + v*depth_pitch + u,
+ * the model depth likewise, the model normal at d_model_normal + f*normal_stride + 3*(v*normal_pitch + u) (strides and pitches
+ * in elements; the normals: stride in floats, pitch in pixels), its 12 doubles at d_model_extrinsics + 12*f and d_guess + 12*f
+ * and its byte at d_mask + f (NULL = every frame); it writes 12 doubles at d_extrinsics_out + 12*f and its record at
+ * d_results + f, either of which may be NULL. width, height in 1..16384 with width*height <= 2^24, n_frames in 0..4096, a
+ * pitch at least the width and, for n_frames > 1, a stride that holds a frame: anything else is ARIA_E_INVALID, refused before
+ * anything is enqueued. The call enqueues sum(iterations) x (accumulate, solve) on the handle's stream: no graph, no host
+ * synchronisation, no grid-wide barrier. */
+int   aria_icp_track_batch_device(aria_icp_t h, const float* d_depth, int64_t depth_stride, int depth_pitch,
+                                  const float* d_model_depth, int64_t model_depth_stride, int model_depth_pitch,
+                                  const float* d_model_normal, int64_t normal_stride, int normal_pitch,
+                                  const double* d_model_extrinsics, const double* d_guess, const uint8_t* d_mask, int n_frames,
+                                  int width, int height, double* d_extrinsics_out, aria_icp_result* d_results);
+/* One frame from dense host buffers (width*height floats each, 3*width*height for the normals); blocks. extrinsics_out and
+ * result may be NULL. A non-finite pose returns ARIA_E_INVALID. */
+int   aria_icp_track(aria_icp_t h, const float* depth, const float* model_depth, const float* model_normal,
+                     const double* model_extrinsics, const double* guess, int width, int height, double* extrinsics_out,
+                     aria_icp_result* result);
+/* The 29 integers of rule 4 of one accumulation per frame, at the Trel given as 12 doubles at d_trel + 12*f (live camera to
+ * model camera) on the level pixels of `stride` (1, 2, 4, 8 or 16), with no solve: d_system + 29*f. The maps as above. */
+int   aria_icp_debug_system_device(aria_icp_t h, const float* d_depth, int64_t depth_stride, int depth_pitch,
+                                   const float* d_model_depth, int64_t model_depth_stride, int model_depth_pitch,
+                                   const float* d_model_normal, int64_t normal_stride, int normal_pitch,
+                                   const double* d_model_extrinsics, const double* d_trel, int n_frames, int width, int height,
+                                   int stride, int64_t* d_system);
+/* The bytes a call must move: per iteration and level pixel 4 of live depth and 4 + 12 of the model, and 320 per frame (two
+ * poses read, one written, the record); ARIA_E_INVALID for a configuration or sizes the call refuses. Host only, no handle. */
+int64_t aria_icp_algorithmic_bytes(const aria_icp_config* cfg, int width, int height, int n_frames);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
