@@ -94,6 +94,7 @@ EXPORTS = [
     # absolute pose from the point map (6-point DLT RANSAC + Gauss-Newton, map association), additive to ABI 4
     "aria_pnp_default_config", "aria_pnp_create", "aria_pnp_destroy", "aria_pnp_stream", "aria_pnp_check",
     "aria_pnp_estimate", "aria_pnp_estimate_batch_device", "aria_pnp_debug_hypotheses", "aria_pnp_associate_batch_device",
+    "aria_pnp_set_solver", "aria_pnp_get_solver",
     # local bundle adjustment (batched windows, Schur-complement LM over poses and points), additive to ABI 4
     "aria_ba_default_config", "aria_ba_create", "aria_ba_destroy", "aria_ba_stream", "aria_ba_check",
     "aria_ba_optimize", "aria_ba_optimize_batch_device", "aria_ba_debug_linearize", "aria_ba_window_from_chain_device",
@@ -790,6 +791,8 @@ def _bind_pnp(L):
     L.aria_pnp_estimate_batch_device.argtypes = [p, p, p, i, i, i, p, p]
     L.aria_pnp_debug_hypotheses.argtypes = [p, p, i, i, p, p, p, p]
     L.aria_pnp_associate_batch_device.argtypes = [p, p, i, i, p, p, i64, p, p, i, i, p, p, p]
+    L.aria_pnp_set_solver.argtypes = [p, i]
+    L.aria_pnp_get_solver.argtypes = [p]
 
 
 def status_string(status):

@@ -1,4 +1,4 @@
-// Absolute pose from 3D-2D correspondences on the device: PnP RANSAC (6-point DLT minimal solver, fp32 reprojection scoring,
+// Absolute pose from 3D-2D correspondences on the device: PnP RANSAC (6-point DLT or P3P minimal solver, fp32 reprojection scoring,
 // Gauss-Newton refinement over the winner's inliers), batched over pairs, and the join of a match list with the point map
 // that feeds it. Semantics in include/aria_orb_hip.h ("absolute pose from the point map"); aria_slam_amd/pnp_ref.py restates
 // every step in NumPy and is the definition.
@@ -10,6 +10,10 @@
 //                 system in 264 VGPRs): the pivot search and the pivot-row broadcast are cross-lane moves inside the 16-lane
 //                 row, the back substitution broadcasts one unknown per step; then every lane of the row holds P and lane
 //                 0 writes (R, t0) in fp32 or "invalid". No scratch (tests/test_pnp_host.py)
+//   k_pnp_hyp_p3p the other solver (aria_pnp_set_solver), in k_pnp_hyp's place: a lane per hypothesis, 256 hypotheses of one
+//                 pair per workgroup -- the three-point system is a few dozen live fp64 values, all 3x3 code is written out
+//                 with constant indices, "the largest of three" and "the best of four" are selects. No LDS, no scratch
+//                 (tests/test_p3p_host.py)
 //   k_pnp_score   one lane per hypothesis, the pair's points staged in LDS tiles (20 B per point) and read as a broadcast:
 //                 inlier count per hypothesis (the hot loop: 27 fp32 ops per evaluation, no scratch)
 //   k_pnp_finish  one workgroup per pair: argmax over (count, -h), Gauss-Newton on the winner's inliers (21 + 6 sums in
@@ -41,7 +45,12 @@ constexpr int PNP_FINISH_BLOCK = 256;
 constexpr int PNP_HYP_BLOCK = 256;         // 16 hypotheses of one pair
 constexpr int PNP_ROW = 16;                // lanes per hypothesis in k_pnp_hyp
 constexpr int PNP_MAX_RETRY = 256;
-constexpr int PNP_MIN = 6;                 // correspondences of a sample, and the least a pair or a refinement needs
+constexpr int PNP_MIN = 6;                 // correspondences of a DLT sample, and the least a refinement needs
+constexpr int PNP_MIN_P3P = 4;             // correspondences of a P3P sample: three for the solver, one to pick its root
+constexpr int PNP_P3P_BLOCK = 256;         // hypotheses of one pair per workgroup of k_pnp_hyp_p3p
+constexpr double P3P_AREA_TOL = 1e-12;     // |(X1 - X2) x (X1 - X3)|^2 <= tol * max(a_ij)^2: collinear or coincident sample
+constexpr int P3P_CUBIC_STEPS = 30;
+constexpr int P3P_POLISH_STEPS = 5;
 constexpr double PNP_PIVOT_TOL = 1e-9;     // |pivot| <= tol * max|A_ij|: degenerate sample
 constexpr double PNP_RANK_TOL = 1e-9;      // sigma3 <= tol * sigma1: M is no scaled rotation
 constexpr double PNP_RANGE = 1e15;         // scoring values and |t0| beyond this never score (header, "Points")
@@ -104,6 +113,25 @@ __device__ __forceinline__ bool finite9(const double* v, int n) {
     return ok;
 }
 
+// The hand-over of both hypothesis kernels, component k: t0[k] = (R X0)[k] + t; false when t is not finite or |t0[k]| is
+// beyond PNP_RANGE. The caller adds finite9(R, 9).
+__device__ __forceinline__ bool pnp_hand_over(const double R[9], double t, const double X0[3], int k, double t0[3]) {
+    t0[k] = ((R[3 * k] * X0[0] + R[3 * k + 1] * X0[1]) + R[3 * k + 2] * X0[2]) + t;
+    return isfinite(t) && fabs(t0[k]) <= PNP_RANGE;
+}
+
+// (R, t0) in fp32, structure-of-arrays per pair: Ps[(p * 12 + k) * H + h], k = 0..8 R, 9..11 t0; cnt[p * H + h] = 0 (valid,
+// to be scored) or -1.
+__device__ __forceinline__ void pnp_store_model(float* Ps, int* cnt, int p, int H, int h, bool ok,
+                                                const double R[9], const double t0[3]) {
+    float* Pp = Ps + (int64_t)p * 12 * H;
+#pragma unroll
+    for (int k = 0; k < 9; k++) Pp[(int64_t)k * H + h] = ok ? (float)R[k] : 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) Pp[(int64_t)(9 + k) * H + h] = ok ? (float)t0[k] : 0.0f;
+    cnt[(int64_t)p * H + h] = ok ? 0 : -1;
+}
+
 // ---- stage: count check, normalisation, centring on X0 ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pnp_stage(const aria_pnp_corr* __restrict__ corr, const int* __restrict__ ncorr,
                                                    int corr_cap, double fx, double fy, double cx, double cy,
@@ -144,8 +172,6 @@ __global__ __launch_bounds__(256) void k_pnp_stage(const aria_pnp_corr* __restri
 // ---- hypotheses: sample + 6-point DLT, a row of the system per lane -------------------------------------------------------
 __device__ __forceinline__ double nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
 
-// (R, t0) is stored structure-of-arrays per pair: Ps[(p * 12 + k) * H + h], k = 0..8 R, 9..11 t0; cnt[p * H + h] = 0
-// (valid, to be scored) or -1.
 __global__ __launch_bounds__(PNP_HYP_BLOCK) void k_pnp_hyp(const aria_pnp_corr* __restrict__ corr, const int* __restrict__ npts,
                                                            int corr_cap, int H, uint64_t seed, int pair_base, double fx,
                                                            double fy, double cx, double cy, float* __restrict__ Ps,
@@ -270,20 +296,210 @@ __global__ __launch_bounds__(PNP_HYP_BLOCK) void k_pnp_hyp(const aria_pnp_corr* 
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 const double t = sd * (m[k] / lam) - ((R[3 * k] * c[0] + R[3 * k + 1] * c[1]) + R[3 * k + 2] * c[2]);
-                t0[k] = ((R[3 * k] * X0[0] + R[3 * k + 1] * X0[1]) + R[3 * k + 2] * X0[2]) + t;
-                ok &= isfinite(t) && fabs(t0[k]) <= PNP_RANGE;
+                ok &= pnp_hand_over(R, t, X0, k, t0);
             }
             ok &= finite9(R, 9);
         }
     }
-    if (row == 0) {
-        float* Pp = Ps + (int64_t)p * 12 * H;
+    if (row == 0) pnp_store_model(Ps, cnt, p, H, h, ok, R, t0);
+}
+
+// ---- hypotheses, the other solver: sample of 4 + P3P, a lane per hypothesis ---------------------------------------------------
+// pnp_ref.solve_p3p line by line (the header's "Minimal solver, P3P"): every sum in its order, no contraction.
+struct P3 {
+    double x, y, z;
+};
+__device__ __forceinline__ P3 p3_sub(P3 a, P3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ P3 p3_cross(P3 a, P3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double p3_dot(P3 a, P3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ double p3_det(P3 a, P3 b, P3 c) { return p3_dot(a, p3_cross(b, c)); }
+__device__ __forceinline__ P3 p3_sel(bool c, P3 a, P3 b) { return {c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z}; }
+
+// unit null vector of D0 - lam I, D0 symmetric with entries d00 d01 d02 d11 d12 d22: the largest row cross product, ties to
+// the earliest
+__device__ __forceinline__ P3 p3_rank2_vector(double d00, double d01, double d02, double d11, double d12, double d22, double lam) {
+    const P3 r0 = {d00 - lam, d01, d02}, r1 = {d01, d11 - lam, d12}, r2 = {d02, d12, d22 - lam};
+    P3 v = p3_cross(r0, r1);
+    double n = p3_dot(v, v);
+    const P3 c1 = p3_cross(r0, r2);
+    const double n1 = p3_dot(c1, c1);
+    bool take = n1 > n;
+    v = p3_sel(take, c1, v);
+    n = take ? n1 : n;
+    const P3 c2 = p3_cross(r1, r2);
+    const double n2 = p3_dot(c2, c2);
+    take = n2 > n;
+    v = p3_sel(take, c2, v);
+    n = take ? n2 : n;
+    const double nn = sqrt(n);
+    return {v.x / nn, v.y / nn, v.z / nn};
+}
+
+__global__ __launch_bounds__(PNP_P3P_BLOCK) void k_pnp_hyp_p3p(const aria_pnp_corr* __restrict__ corr, const int* __restrict__ npts,
+                                                               int corr_cap, int H, uint64_t seed, int pair_base, double fx,
+                                                               double fy, double cx, double cy, float* __restrict__ Ps,
+                                                               int* __restrict__ cnt, int* __restrict__ dbg_idx) {
+    const int p = blockIdx.x;
+    const int h = blockIdx.y * PNP_P3P_BLOCK + threadIdx.x;
+    if (h >= H) return;
+    const int n = npts[p];
+    bool ok = n >= PNP_MIN_P3P;
+    int idx[4] = {-1, -1, -1, -1};
+    if (ok) ok = draw_sample<4, PNP_MAX_RETRY>(seed, (uint32_t)(pair_base + p), h, n, idx);
+    if (dbg_idx) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) Pp[(int64_t)k * H + h] = ok ? (float)R[k] : 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) Pp[(int64_t)(9 + k) * H + h] = ok ? (float)t0[k] : 0.0f;
-        cnt[(int64_t)p * H + h] = ok ? 0 : -1;
+        for (int j = 0; j < 4; j++) dbg_idx[h * 6 + j] = idx[j];
+        dbg_idx[h * 6 + 4] = -1;
+        dbg_idx[h * 6 + 5] = -1;
     }
+    double Rb[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tb[3] = {0, 0, 0}, t0[3] = {0, 0, 0};
+    int slot = -1;
+    if (ok) {
+        const aria_pnp_corr* cp = corr + (int64_t)p * corr_cap;
+        const aria_pnp_corr q0 = cp[idx[0]], q1 = cp[idx[1]], q2 = cp[idx[2]], q3 = cp[idx[3]];
+        const P3 X1 = {q0.X[0], q0.X[1], q0.X[2]}, X2 = {q1.X[0], q1.X[1], q1.X[2]}, X3 = {q2.X[0], q2.X[1], q2.X[2]};
+        const P3 X4 = {q3.X[0], q3.X[1], q3.X[2]};
+        // 1. unit bearings, squared distances from differences, cosines
+        P3 y1, y2, y3;
+        {
+            double x = ((double)q0.u - cx) / fx, y = ((double)q0.v - cy) / fy, nr = sqrt((x * x + y * y) + 1.0);
+            y1 = {x / nr, y / nr, 1.0 / nr};
+            x = ((double)q1.u - cx) / fx; y = ((double)q1.v - cy) / fy; nr = sqrt((x * x + y * y) + 1.0);
+            y2 = {x / nr, y / nr, 1.0 / nr};
+            x = ((double)q2.u - cx) / fx; y = ((double)q2.v - cy) / fy; nr = sqrt((x * x + y * y) + 1.0);
+            y3 = {x / nr, y / nr, 1.0 / nr};
+        }
+        const double x4 = ((double)q3.u - cx) / fx, y4 = ((double)q3.v - cy) / fy;
+        const P3 v1 = p3_sub(X1, X2), v2 = p3_sub(X1, X3), d23 = p3_sub(X2, X3);
+        const double a12 = p3_dot(v1, v1), a13 = p3_dot(v2, v2), a23 = p3_dot(d23, d23);
+        const double b12 = p3_dot(y1, y2), b13 = p3_dot(y1, y3), b23 = p3_dot(y2, y3);
+        const P3 v3 = p3_cross(v1, v2);
+        const double area2 = p3_dot(v3, v3);
+        const double amax = fmax(fmax(a12, a13), a23);
+        ok = area2 > P3P_AREA_TOL * (amax * amax);
+        // 2. the cubic det(D1 + g D2) = 0, D1 = a23 M12 - a12 M23, D2 = a23 M13 - a13 M23 (columns; both symmetric)
+        const P3 D1a = {a23, -(a23 * b12), 0.0}, D1b = {-(a23 * b12), a23 - a12, a12 * b23}, D1c = {0.0, a12 * b23, -a12};
+        const P3 D2a = {a23, 0.0, -(a23 * b13)}, D2b = {0.0, -a13, a13 * b23}, D2c = {-(a23 * b13), a13 * b23, a23 - a13};
+        const double c3 = p3_det(D2a, D2b, D2c);
+        const double c2 = (p3_det(D1a, D2b, D2c) + p3_det(D2a, D1b, D2c)) + p3_det(D2a, D2b, D1c);
+        const double c1 = (p3_det(D2a, D1b, D1c) + p3_det(D1a, D2b, D1c)) + p3_det(D1a, D1b, D2c);
+        const double c0 = p3_det(D1a, D1b, D1c);
+        ok &= c3 != 0.0;
+        const double ca = c2 / c3, cb = c1 / c3, cc = c0 / c3;
+        const double xi = -ca / 3.0;
+        const double disc = ca * ca - 3.0 * cb;
+        const double fi = ((xi + ca) * xi + cb) * xi + cc;
+        const double rr = 2.0 * sqrt(disc > 0.0 ? disc : 0.0) / 3.0;
+        double g = disc > 0.0 ? (fi > 0.0 ? xi - rr : xi + rr) : xi;
+#pragma unroll 1
+        for (int it = 0; it < P3P_CUBIC_STEPS; it++) {
+            const double f = ((g + ca) * g + cb) * g + cc;
+            const double fp = (3.0 * g + 2.0 * ca) * g + cb;
+            g = fp != 0.0 ? g - f / fp : g;
+        }
+        // 3. the rank-2 form D0 = D1 + g D2 and its two eigenpairs
+        const double d00 = D1a.x + g * D2a.x, d01 = D1a.y + g * D2a.y, d02 = D1a.z + g * D2a.z;
+        const double d11 = D1b.y + g * D2b.y, d12 = D1b.z + g * D2b.z, d22 = D1c.z + g * D2c.z;
+        const double tr = (d00 + d11) + d22;
+        const double mm = ((d00 * d11 - d01 * d01) + (d00 * d22 - d02 * d02)) + (d11 * d22 - d12 * d12);
+        const double dq = tr * tr - 4.0 * mm;
+        const double sq = sqrt(dq > 0.0 ? dq : 0.0);
+        const double la = (tr + (tr >= 0.0 ? sq : -sq)) / 2.0;
+        const double lb = mm / la;
+        const bool pos = la > 0.0;
+        ok &= (pos && lb < 0.0) || (la < 0.0 && lb > 0.0);
+        if (ok) {
+            const P3 ea = p3_rank2_vector(d00, d01, d02, d11, d12, d22, la), eb = p3_rank2_vector(d00, d01, d02, d11, d12, d22, lb);
+            const P3 e1 = p3_sel(pos, ea, eb), e2 = p3_sel(pos, eb, ea);
+            const double lpos = pos ? la : lb, lneg = pos ? lb : la;
+            const double s = sqrt(-lneg / lpos);
+            const double iw = 1.0 / area2;
+            const P3 wa = p3_cross(v2, v3), wb = p3_cross(v3, v1);
+            const P3 w1v = {wa.x * iw, wa.y * iw, wa.z * iw}, w2v = {wb.x * iw, wb.y * iw, wb.z * iw}, w3v = {v3.x * iw, v3.y * iw, v3.z * iw};
+            double best = __builtin_inf();
+            // 4. - 7. the four candidate slots in their order: (+s, -s) x (q / A, C / q); a fixed trip count, predicated
+#pragma unroll 1
+            for (int sign = 0; sign < 2; sign++) {
+                const double ss = sign ? -s : s;
+                const double p0 = e1.x - ss * e2.x, p1 = e1.y - ss * e2.y, p2 = e1.z - ss * e2.z;
+                const double w0 = -p1 / p0, w1 = -p2 / p0;
+                const double A = a23 * (w1 * w1) - a12;
+                const double B = a23 * (2.0 * (w0 * w1) - 2.0 * (b12 * w1)) + 2.0 * (a12 * b23);
+                const double C = a23 * ((w0 * w0 + 1.0) - 2.0 * (b12 * w0)) - a12;
+                const double qd = B * B - 4.0 * (A * C);
+                const double sqd = sqrt(qd >= 0.0 ? qd : 0.0);
+                const double q = -(B + (B >= 0.0 ? sqd : -sqd)) / 2.0;
+#pragma unroll 1
+                for (int root = 0; root < 2; root++) {
+                    const double tau = root ? C / q : q / A;
+                    const double den = (1.0 + tau * tau) - (2.0 * b23) * tau;
+                    double l2 = sqrt(a23 / (den > 0.0 ? den : 1.0));
+                    double l3 = tau * l2;
+                    double l1 = w0 * l2 + w1 * l3;
+                    const bool alive = qd >= 0.0 && tau > 0.0 && den > 0.0 && l1 > 0.0;
+                    // 5. polish: Newton on the three distance equations, the 3x3 solve by the adjugate
+#pragma unroll 1
+                    for (int it = 0; it < P3P_POLISH_STEPS; it++) {
+                        const double r1 = ((l1 * l1 + l2 * l2) - (2.0 * b12) * (l1 * l2)) - a12;
+                        const double r2 = ((l1 * l1 + l3 * l3) - (2.0 * b13) * (l1 * l3)) - a13;
+                        const double r3 = ((l2 * l2 + l3 * l3) - (2.0 * b23) * (l2 * l3)) - a23;
+                        const double j00 = 2.0 * (l1 - b12 * l2), j01 = 2.0 * (l2 - b12 * l1);
+                        const double j10 = 2.0 * (l1 - b13 * l3), j12 = 2.0 * (l3 - b13 * l1);
+                        const double j21 = 2.0 * (l2 - b23 * l3), j22 = 2.0 * (l3 - b23 * l2);
+                        const double dj = -(j00 * (j12 * j21)) - j01 * (j10 * j22);
+                        const bool go = dj != 0.0;
+                        const double g1 = (-(j12 * j21) * r1 - (j01 * j22) * r2) + (j01 * j12) * r3;
+                        const double g2 = (-(j10 * j22) * r1 + (j00 * j22) * r2) - (j00 * j12) * r3;
+                        const double g3 = ((j10 * j21) * r1 - (j00 * j21) * r2) - (j01 * j10) * r3;
+                        l1 = go ? l1 - g1 / dj : l1;
+                        l2 = go ? l2 - g2 / dj : l2;
+                        l3 = go ? l3 - g3 / dj : l3;
+                    }
+                    // 6. pose from the two triangles
+                    const P3 Y1 = {l1 * y1.x, l1 * y1.y, l1 * y1.z}, Y2 = {l2 * y2.x, l2 * y2.y, l2 * y2.z}, Y3 = {l3 * y3.x, l3 * y3.y, l3 * y3.z};
+                    const P3 u1 = p3_sub(Y1, Y2), u2 = p3_sub(Y1, Y3);
+                    const P3 u3 = p3_cross(u1, u2);
+                    double R[9], t[3];
+                    R[0] = (u1.x * w1v.x + u2.x * w2v.x) + u3.x * w3v.x;
+                    R[1] = (u1.x * w1v.y + u2.x * w2v.y) + u3.x * w3v.y;
+                    R[2] = (u1.x * w1v.z + u2.x * w2v.z) + u3.x * w3v.z;
+                    R[3] = (u1.y * w1v.x + u2.y * w2v.x) + u3.y * w3v.x;
+                    R[4] = (u1.y * w1v.y + u2.y * w2v.y) + u3.y * w3v.y;
+                    R[5] = (u1.y * w1v.z + u2.y * w2v.z) + u3.y * w3v.z;
+                    R[6] = (u1.z * w1v.x + u2.z * w2v.x) + u3.z * w3v.x;
+                    R[7] = (u1.z * w1v.y + u2.z * w2v.y) + u3.z * w3v.y;
+                    R[8] = (u1.z * w1v.z + u2.z * w2v.z) + u3.z * w3v.z;
+                    t[0] = Y1.x - ((R[0] * X1.x + R[1] * X1.y) + R[2] * X1.z);
+                    t[1] = Y1.y - ((R[3] * X1.x + R[4] * X1.y) + R[5] * X1.z);
+                    t[2] = Y1.z - ((R[6] * X1.x + R[7] * X1.y) + R[8] * X1.z);
+                    // 7. the fourth point picks: least error, ties to the earliest slot
+                    const double cx4 = ((R[0] * X4.x + R[1] * X4.y) + R[2] * X4.z) + t[0];
+                    const double cy4 = ((R[3] * X4.x + R[4] * X4.y) + R[5] * X4.z) + t[1];
+                    const double cz4 = ((R[6] * X4.x + R[7] * X4.y) + R[8] * X4.z) + t[2];
+                    const double zz = cz4 > 0.0 ? cz4 : 1.0;
+                    const double ex = cx4 / zz - x4, ey = cy4 / zz - y4;
+                    const double err = ex * ex + ey * ey;
+                    const bool fin = isfinite(err) && finite9(R, 9) && finite9(t, 3);
+                    const bool take = alive && fin && cz4 > 0.0 && err < best;
+                    best = take ? err : best;
+                    slot = take ? 2 * sign + root : slot;
+#pragma unroll
+                    for (int k = 0; k < 9; k++) Rb[k] = take ? R[k] : Rb[k];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) tb[k] = take ? t[k] : tb[k];
+                }
+            }
+        }
+        ok = slot >= 0;
+        // 8. hand-over
+        if (ok) {
+            const double X0[3] = {cp[0].X[0], cp[0].X[1], cp[0].X[2]};
+#pragma unroll
+            for (int k = 0; k < 3; k++) ok &= pnp_hand_over(Rb, tb[k], X0, k, t0);
+            ok &= finite9(Rb, 9);
+        }
+    }
+    pnp_store_model(Ps, cnt, p, H, h, ok, Rb, t0);
 }
 
 // ---- scoring: the hot loop ----------------------------------------------------------------------------------------------
@@ -415,8 +631,9 @@ __global__ __launch_bounds__(PNP_FINISH_BLOCK) void k_pnp_finish(const aria_pnp_
                                                                  const float* __restrict__ pb, const int* __restrict__ npts,
                                                                  int corr_cap, int H, const float* __restrict__ Ps,
                                                                  const int* __restrict__ cnt, float thr2, double fx, double fy,
-                                                                 double cx, double cy, int refine_iters, uint8_t* __restrict__ ws,
-                                                                 uint8_t* __restrict__ mask, aria_pnp_result* __restrict__ out) {
+                                                                 double cx, double cy, int refine_iters, int min_corr,
+                                                                 uint8_t* __restrict__ ws, uint8_t* __restrict__ mask,
+                                                                 aria_pnp_result* __restrict__ out) {
     __shared__ int red_c[PNP_FINISH_BLOCK], red_h[PNP_FINISH_BLOCK];
     __shared__ double Sw[PNP_FINISH_BLOCK / 64][27], S[27], L[36];
     __shared__ double Rc[9], tc[3], X0[3];
@@ -448,7 +665,7 @@ __global__ __launch_bounds__(PNP_FINISH_BLOCK) void k_pnp_finish(const aria_pnp_
     const int win_c = red_c[0], win_h = red_h[0];
     aria_pnp_result* o = out + p;
     uint8_t* mk = mask ? mask + (int64_t)p * corr_cap : nullptr;
-    if (n < PNP_MIN || win_c < 0) {
+    if (n < min_corr || win_c < 0) {             // min_corr: the solver's sample size
         if (mk)
             for (int i = tid; i < corr_cap; i += PNP_FINISH_BLOCK) mk[i] = 0;
         if (tid == 0) pnp_write_invalid(o, n);
@@ -671,6 +888,7 @@ __global__ __launch_bounds__(256) void k_pnp_assoc_gather(const aria_map_point* 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
 struct aria_pnp_s : StageHandle {
     aria_pnp_config cfg{};
+    int solver = ARIA_PNP_SOLVER_DLT6;    // a launch parameter: read when a call is issued (aria_pnp_set_solver)
     // grow-only workspace of the batch path
     DeviceBuffer<float4> d_pa;            // [n_pairs][corr_cap] (dx, dy, dz, x)
     DeviceBuffer<float> d_pb;             // [n_pairs][corr_cap] y
@@ -707,13 +925,19 @@ int enqueue(aria_pnp_t h, const aria_pnp_corr* d_corr, const int* d_ncorr, int n
     const aria_pnp_config& c = h->cfg;
     hipLaunchKernelGGL(k_pnp_stage, dim3(n_pairs), dim3(256), 0, h->stream, d_corr, d_ncorr, corr_cap, c.fx, c.fy, c.cx, c.cy,
                        h->d_pa, h->d_pb, h->d_npts, h->d_err);
-    hipLaunchKernelGGL(k_pnp_hyp, dim3(n_pairs, H / (PNP_HYP_BLOCK / PNP_ROW)), dim3(PNP_HYP_BLOCK), 0, h->stream, d_corr, h->d_npts,
-                       corr_cap, H, (uint64_t)c.seed, pair_base, c.fx, c.fy, c.cx, c.cy, h->d_P, h->d_cnt, d_dbg);
+    const bool p3p = h->solver == ARIA_PNP_SOLVER_P3P;
+    if (p3p)
+        hipLaunchKernelGGL(k_pnp_hyp_p3p, dim3(n_pairs, (H + PNP_P3P_BLOCK - 1) / PNP_P3P_BLOCK), dim3(PNP_P3P_BLOCK), 0, h->stream,
+                           d_corr, h->d_npts, corr_cap, H, (uint64_t)c.seed, pair_base, c.fx, c.fy, c.cx, c.cy, h->d_P, h->d_cnt, d_dbg);
+    else
+        hipLaunchKernelGGL(k_pnp_hyp, dim3(n_pairs, H / (PNP_HYP_BLOCK / PNP_ROW)), dim3(PNP_HYP_BLOCK), 0, h->stream, d_corr, h->d_npts,
+                           corr_cap, H, (uint64_t)c.seed, pair_base, c.fx, c.fy, c.cx, c.cy, h->d_P, h->d_cnt, d_dbg);
     hipLaunchKernelGGL(k_pnp_score, dim3(n_pairs, (H + PNP_SCORE_BLOCK - 1) / PNP_SCORE_BLOCK), dim3(PNP_SCORE_BLOCK), 0, h->stream,
                        h->d_pa, h->d_pb, h->d_npts, corr_cap, H, h->d_P, h->d_cnt, pnp_thr2(c));
     if (finish)
         hipLaunchKernelGGL(k_pnp_finish, dim3(n_pairs), dim3(PNP_FINISH_BLOCK), 0, h->stream, d_corr, h->d_pa, h->d_pb, h->d_npts,
-                           corr_cap, H, h->d_P, h->d_cnt, pnp_thr2(c), c.fx, c.fy, c.cx, c.cy, c.refine_iters, h->d_ws, d_mask, d_out);
+                           corr_cap, H, h->d_P, h->d_cnt, pnp_thr2(c), c.fx, c.fy, c.cx, c.cy, c.refine_iters,
+                           p3p ? PNP_MIN_P3P : PNP_MIN, h->d_ws, d_mask, d_out);
     ARIA_HIP(hipGetLastError());
     return ARIA_OK;
 }
@@ -779,6 +1003,14 @@ void aria_pnp_destroy(aria_pnp_t h) {
 }
 
 void* aria_pnp_stream(aria_pnp_t h) { return h ? (void*)h->stream : nullptr; }
+
+int aria_pnp_set_solver(aria_pnp_t h, int solver) {
+    if (!h || (solver != ARIA_PNP_SOLVER_DLT6 && solver != ARIA_PNP_SOLVER_P3P)) return ARIA_E_INVALID;
+    h->solver = solver;
+    return ARIA_OK;
+}
+
+int aria_pnp_get_solver(aria_pnp_t h) { return h ? h->solver : ARIA_E_INVALID; }
 
 int aria_pnp_check(aria_pnp_t h) {
     if (!h) return ARIA_E_INVALID;

@@ -32,7 +32,13 @@ public:
     HipPnPEstimator(const HipPnPEstimator&) = delete;
     HipPnPEstimator& operator=(const HipPnPEstimator&) = delete;
 
-    // std::nullopt when the stage finds no pose (fewer than 6 correspondences, no valid hypothesis, a planar scene).
+    // The minimal solver of the calls that follow: ARIA_PNP_SOLVER_DLT6 (the default; a planar scene yields no pose) or
+    // ARIA_PNP_SOLVER_P3P (four correspondences are enough, planar scenes included). Throws on an unknown value.
+    void setSolver(int solver);
+    int solver() const { return aria_pnp_get_solver(h_); }
+
+    // std::nullopt when the stage finds no pose (fewer correspondences than the solver needs, 6 or 4; no valid hypothesis; with
+    // the DLT a planar scene).
     std::optional<AbsolutePose> estimate(const std::vector<aria_pnp_corr>& corr, int pair_id = 0);
 
     // One tracked frame against the map, joined on the device (aria_pnp_associate_batch_device, then

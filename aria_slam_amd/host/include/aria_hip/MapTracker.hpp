@@ -27,7 +27,9 @@ struct TrackStep {
 
 class MapTracker {
 public:
-    explicit MapTracker(const MapperConfig& map_cfg = {}, int min_pose_inliers = 10, int hypotheses = 1024);
+    // pnp_solver: the minimal solver of the PnP step (ARIA_PNP_SOLVER_DLT6 or ARIA_PNP_SOLVER_P3P; HipPnPEstimator::setSolver).
+    explicit MapTracker(const MapperConfig& map_cfg = {}, int min_pose_inliers = 10, int hypotheses = 1024,
+                        int pnp_solver = ARIA_PNP_SOLVER_DLT6);
 
     // One step previous -> current. `matches` pair the two frames; previous_is_query: match.query_idx indexes `previous`.
     // two_view: the two-view stage's previous -> current pose, if it found one (accepted when n_pose_inliers >

@@ -35,6 +35,11 @@ void HipPnPEstimator::fail(const char* where, int status) {
     throw std::runtime_error(msg);
 }
 
+void HipPnPEstimator::setSolver(int solver) {
+    const int rc = aria_pnp_set_solver(h_, solver);
+    if (rc != ARIA_OK) fail("aria_pnp_set_solver", rc);
+}
+
 std::optional<AbsolutePose> HipPnPEstimator::estimate(const std::vector<aria_pnp_corr>& corr, int pair_id) {
     aria_pnp_result r{};
     AbsolutePose out;

@@ -5,9 +5,11 @@
 
 namespace aria::adapters::hip {
 
-MapTracker::MapTracker(const MapperConfig& map_cfg, int min_pose_inliers, int hypotheses)
+MapTracker::MapTracker(const MapperConfig& map_cfg, int min_pose_inliers, int hypotheses, int pnp_solver)
     : mapper_(map_cfg), pnp_(map_cfg.K, hypotheses, map_cfg.max_reproj_px, 5, 0, nullptr, map_cfg.device),
-      min_pose_inliers_(min_pose_inliers), pose_{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1} {}
+      min_pose_inliers_(min_pose_inliers), pose_{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1} {
+    if (pnp_solver != ARIA_PNP_SOLVER_DLT6) pnp_.setSolver(pnp_solver);
+}
 
 TrackStep MapTracker::track(const core::Frame& previous, const core::Frame& current, const std::vector<core::Match>& matches,
                             bool previous_is_query, const std::optional<TwoViewPose>& two_view, const std::uint8_t* previous_image,

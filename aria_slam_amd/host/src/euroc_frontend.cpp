@@ -1,5 +1,5 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
-//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--bundle FILE3] [--bundle-window N]
+//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--pnp-solver dlt|p3p] [--bundle FILE3] [--bundle-window N]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
 //                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE] [--track-dense FILE2]
 //
@@ -38,7 +38,8 @@
 // later frame is placed by PnP on the device against the points of the previous pair; a frame for which PnP finds no pose, or
 // one with n_inliers <= 10, falls back to the pose stage's delta; the new pair is triangulated with the two extrinsics.
 // FILE2 gets one TUM line per frame (world-to-camera poses), and "track pnp A fallback B bootstrap C held D map N -> FILE2"
-// is printed. --pose FILE, --map and the CSV are byte-identical with and without it.
+// is printed. --pose FILE, --map and the CSV are byte-identical with and without it. --pnp-solver dlt|p3p chooses the PnP
+// step's minimal solver (default dlt; p3p places a frame against a planar map, where the DLT finds no pose).
 //
 // --loop-verify reference (needs --loop): a loop candidate is accepted as LoopClosureDetector accepts it -- F-RANSAC on its
 // ratio-0.7 list, then E-RANSAC + recoverPose on the F inliers with computeRelativePose's K (aria_hip/
@@ -231,6 +232,8 @@ int main(int argc, char** argv) {
                              "                       relative translations take the metric scale\n"
                              "  --eval file: ATE / RPE of the --pose (and --optimize, --fuse) trajectories against the sequence's ground truth (needs --pose)\n"
                              "  --fuse file: EKF visual-inertial fusion over imu0 and the --pose stage's relative poses (needs --pose), one TUM line per frame\n"
+                             "  --pnp-solver dlt|p3p: the minimal solver of --track-map's PnP step (default dlt: the 6-point DLT, which places no frame on a\n"
+                             "                        planar scene; p3p needs four map points and handles planes)\n"
                              "  --bundle file: local bundle adjustment of the --track-map trajectory in windows of --bundle-window N frames (default 10, at most 16),\n"
                              "                 stride N - 2, the first two poses of a window fixed (needs --track-map)\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
@@ -241,6 +244,7 @@ int main(int argc, char** argv) {
     bool legacy = false, loop = false;
     std::string bundle_file;
     int bundle_window = 10;
+    std::string pnp_solver_name = "dlt";
     std::string csv, pose_file, map_file, track_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
@@ -259,6 +263,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pose") && i + 1 < argc) pose_file = argv[++i];
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
         else if (!std::strcmp(argv[i], "--track-map") && i + 1 < argc) track_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--pnp-solver") && i + 1 < argc) pnp_solver_name = argv[++i];
         else if (!std::strcmp(argv[i], "--bundle") && i + 1 < argc) bundle_file = argv[++i];
         else if (!std::strcmp(argv[i], "--bundle-window") && i + 1 < argc) bundle_window = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
@@ -301,6 +306,11 @@ int main(int argc, char** argv) {
                           : eval_align == "sim3" ? ARIA_EVAL_ALIGN_SIM3 : -1;
     if (!eval_file.empty() && (pose_file.empty() || eval_mode < 0 || rpe_delta < 1)) {
         std::fprintf(stderr, "--eval needs --pose, --eval-align none|se3|sim3 and --rpe-delta >= 1\n");
+        return 1;
+    }
+    const int pnp_solver = pnp_solver_name == "dlt" ? ARIA_PNP_SOLVER_DLT6 : pnp_solver_name == "p3p" ? ARIA_PNP_SOLVER_P3P : -1;
+    if (pnp_solver < 0) {
+        std::fprintf(stderr, "--pnp-solver takes dlt or p3p\n");
         return 1;
     }
     if (!track_file.empty() && pose_file.empty()) {
@@ -520,7 +530,7 @@ int main(int argc, char** argv) {
                 adapters::hip::MapperConfig mc;
                 mc.device = fc.hip_device;
                 if (rectifier) mc.K = new_K;
-                tracker = std::make_unique<adapters::hip::MapTracker>(mc);
+                tracker = std::make_unique<adapters::hip::MapTracker>(mc, 10, 1024, pnp_solver);
                 if (!bundle_file.empty()) {
                     tracker->setWindowBuilder(&bundle_builder);
                     bundle_K = mc.K;

@@ -1,5 +1,5 @@
 """Absolute pose from the point map on the device (include/aria_orb_hip.h, "absolute pose from the point map"): PnP RANSAC over
-3D-2D correspondences -- a 6-point DLT minimal solver, fp32 reprojection scoring, Gauss-Newton refinement -- and the join of
+3D-2D correspondences -- a 6-point DLT or a P3P minimal solver, fp32 reprojection scoring, Gauss-Newton refinement -- and the join of
 a match list with the map that produces the correspondences. aria_slam_amd.pnp_ref restates the stage in NumPy and is its
 definition; the reference project has no PnP code.
 
@@ -32,12 +32,19 @@ def _corr(corr):
     return c.reshape(-1)
 
 
+SOLVERS = {"dlt": 0, "p3p": 1}           # ARIA_PNP_SOLVER_DLT6, ARIA_PNP_SOLVER_P3P
+
+
 class HipPnPEstimator(StageHandle):
-    """Binding of aria_pnp_t. K = (fx, fy, cx, cy); the defaults are EuRoC cam0 and the map stage's 2 px."""
+    """Binding of aria_pnp_t. K = (fx, fy, cx, cy); the defaults are EuRoC cam0 and the map stage's 2 px. solver: "dlt" (the
+    6-point DLT, which yields valid = 0 on a planar scene) or "p3p" (four correspondences are enough, planar scenes
+    included); it can be changed between calls through the `solver` property."""
 
     _prefix, _config = "pnp", _lib.PnpConfig
 
-    def __init__(self, K=None, hypotheses=1024, threshold_px=2.0, refine_iters=5, seed=0, stream=None, device=0):
+    def __init__(self, K=None, hypotheses=1024, threshold_px=2.0, refine_iters=5, seed=0, stream=None, device=0, solver="dlt"):
+        if solver not in SOLVERS:
+            raise ValueError("solver must be one of %r" % (sorted(SOLVERS),))
         cfg = self._default_config(device, stream)
         cfg.hypotheses = hypotheses
         if K is not None:
@@ -46,6 +53,24 @@ class HipPnPEstimator(StageHandle):
         cfg.refine_iters = refine_iters
         cfg.seed = seed
         self._create(cfg)
+        if solver != "dlt":
+            self.solver = solver
+
+    @property
+    def solver(self):
+        """The minimal solver of the calls issued from now on: "dlt" or "p3p" (aria_pnp_set_solver; nothing is synchronised)."""
+        code = self._L.aria_pnp_get_solver(self._h)
+        return [k for k, v in SOLVERS.items() if v == code][0]
+
+    @solver.setter
+    def solver(self, name):
+        if name not in SOLVERS:
+            raise ValueError("solver must be one of %r" % (sorted(SOLVERS),))
+        check(self._L.aria_pnp_set_solver(self._h, SOLVERS[name]), "aria_pnp_set_solver")
+
+    def set_solver_code(self, code):
+        """aria_pnp_set_solver with a raw value; returns the status (an unknown value: ARIA_E_INVALID, nothing changes)."""
+        return int(self._L.aria_pnp_set_solver(self._h, int(code)))
 
     @property
     def K(self):
@@ -77,7 +102,8 @@ class HipPnPEstimator(StageHandle):
               "aria_pnp_associate_batch_device")
 
     def debug_hypotheses(self, corr, pair_base=0):
-        """(sample_idx (H, 6) int32, R (H, 9) float32, t0 (H, 3) float32, counts (H,) int32) of one pair -- the test hook."""
+        """(sample_idx (H, 6) int32, R (H, 9) float32, t0 (H, 3) float32, counts (H,) int32) of one pair -- the test hook.
+        With the P3P solver slots 4 and 5 of sample_idx are -1."""
         c = _corr(corr)
         H = self.config.hypotheses
         idx = np.zeros((H, 6), np.int32)

@@ -7,7 +7,20 @@ device's order of operations; the solver and the refinement run in fp64 (3x3 SVD
 
 estimate(dtype=np.longdouble) is the yardstick that rounding is measured against (tools/pnp_gap.py): the refinement, the
 nearest rotation it starts from and the outputs in extended precision; the hypotheses and every inlier test are the same
-in both runs."""
+in both runs.
+
+Two minimal solvers. solver="dlt" (the default) is the 6-point DLT above. solver="p3p" is a three-point solver with a fourth
+point that picks among its roots (solve_p3p; MIN_CORR_P3P = 4 correspondences): the elimination of Persson and Nordberg
+("Lambda Twist", ECCV 2018) restated with + - * / and sqrt alone -- one real root of the cubic by 30 Newton steps from a
+start on the monotone side, the rank-2 form's eigenpairs from a quadratic and row cross products, up to four candidates in a
+fixed order, five Newton steps on the distance equations each, the pose from the two triangles. No cbrt, acos or cos: their
+results cannot be held between host and device. Parity with OpenCV's SOLVEPNP_P3P is not claimed. A plane through the
+sample is no degeneracy of this solver, so a planar scene, where every DLT sample is invalid, yields a pose.
+
+One model per hypothesis: the candidate that reprojects the sample's fourth point best. Scoring all roots would quadruple
+the scoring loop; the price is that an outlier in slot 3 can pick the wrong root of an otherwise clean sample, and such a
+hypothesis is lost. From the hand-over on -- scoring, winner, refinement (from 6 inliers), outputs -- the definition is the
+one above; only the "fewer than 6 correspondences" gate becomes the solver's minimum."""
 import numpy as np
 
 from ._lib import KP_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, PNP_CORR_DTYPE
@@ -19,11 +32,22 @@ RANK_TOL = 1e-9
 RANGE = 1e15          # |X - X0|, |x|, |y| and |t0| beyond this never score: squares stay finite in fp32
 MIN_CORR = 6
 STEP_TOL = 1e-12
+MIN_CORR_P3P = 4      # three points for the solver, the fourth picks among its roots
+P3P_AREA_TOL = 1e-12  # |(X1 - X2) x (X1 - X3)|^2 <= tol * max(a_ij)^2: collinear or coincident sample points
+P3P_CUBIC_STEPS = 30
+P3P_POLISH_STEPS = 5
+SOLVERS = ("dlt", "p3p")
 
 
-def sample_indices(seed, pair, hypotheses, n):
-    """(hypotheses, 6) sample indices: the pose stage's hash with six slots."""
-    return P.sample_indices(seed, pair, hypotheses, n, k=6)
+def min_corr(solver="dlt"):
+    if solver not in SOLVERS:
+        raise ValueError("solver must be one of %r" % (SOLVERS,))
+    return MIN_CORR if solver == "dlt" else MIN_CORR_P3P
+
+
+def sample_indices(seed, pair, hypotheses, n, k=6):
+    """(hypotheses, k) sample indices: the pose stage's hash with k slots (6 for the DLT, 4 for P3P)."""
+    return P.sample_indices(seed, pair, hypotheses, n, k=k)
 
 
 def threshold2(threshold_px=2.0, K=EUROC_K):
@@ -140,6 +164,193 @@ def solve_minimal(X, xy):
     return R, t, ok
 
 
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _det3(c0, c1, c2):
+    return _dot(c0, _cross(c1, c2))
+
+
+def _rank2_vector(d, lam):
+    """The null vector of D0 - lam I (d = the six entries d00 d01 d02 d11 d12 d22): the largest of the three row cross
+    products (ties to the earliest), normalised."""
+    r0 = (d[0] - lam, d[1], d[2])
+    r1 = (d[1], d[3] - lam, d[4])
+    r2 = (d[2], d[4], d[5] - lam)
+    v, n = None, None
+    for c in (_cross(r0, r1), _cross(r0, r2), _cross(r1, r2)):
+        cn = _dot(c, c)
+        if v is None:
+            v, n = c, cn
+        else:
+            take = cn > n
+            v = tuple(np.where(take, c[k], v[k]) for k in range(3))
+            n = np.where(take, cn, n)
+    nn = np.sqrt(n)
+    return (v[0] / nn, v[1] / nn, v[2] / nn)
+
+
+def solve_p3p(X, xy, dtype=np.float64, detail=False):
+    """The P3P minimal solver on (H, 4, 3) world points and (H, 4, 2) normalised pixels, in `dtype` and in the device's
+    order of operations: points 0..2 are solved, point 3 picks the candidate. Returns (R (H, 3, 3), t (H, 3), valid (H,),
+    slot (H,)): x_cam = R X + t; slot = the chosen candidate, 2 * (sign of s: 0 = +s, 1 = -s) + (root of the tau quadratic:
+    0 = q / A, 1 = C / q), -1 when invalid. detail=True appends a dict: `alive` (H, 4) the candidates that passed step 4,
+    `usable` (H, 4) those that also passed step 7's tests, `lengths` (H, 4, 3) after the polish, `poses` (R (H, 4, 3, 3),
+    t (H, 4, 3)), `a` (a12, a13, a23), `b` (b12, b13, b23), `bearings` (H, 3, 3), `err` (H, 4) the fourth point's error, `area2` and `amax`
+    (the degeneracy test's two sides), `degenerate` (H,)."""
+    dt = dtype
+    X = np.asarray(X, dt)
+    xy = np.asarray(xy, dt)
+    H = X.shape[0]
+    c = lambda v: dt(v)   # noqa: E731
+    with np.errstate(all="ignore"):
+        # 1. setup
+        yb = []
+        for i in range(3):
+            x, y = xy[:, i, 0], xy[:, i, 1]
+            nrm = np.sqrt((x * x + y * y) + c(1))
+            yb.append((x / nrm, y / nrm, c(1) / nrm))
+        Xs = [tuple(X[:, i, k] for k in range(3)) for i in range(4)]
+        sub = lambda p, q: (p[0] - q[0], p[1] - q[1], p[2] - q[2])   # noqa: E731
+        v1, v2, d23 = sub(Xs[0], Xs[1]), sub(Xs[0], Xs[2]), sub(Xs[1], Xs[2])
+        a12, a13, a23 = _dot(v1, v1), _dot(v2, v2), _dot(d23, d23)
+        b12, b13, b23 = _dot(yb[0], yb[1]), _dot(yb[0], yb[2]), _dot(yb[1], yb[2])
+        # 6's degeneracy test, first: collinear or coincident sample points
+        v3 = _cross(v1, v2)
+        area2 = _dot(v3, v3)
+        amax = np.maximum(np.maximum(a12, a13), a23)
+        ok = area2 > c(P3P_AREA_TOL) * (amax * amax)
+        # 2. the cubic det(D1 + g D2) = 0
+        z = np.zeros(H, dt)
+        D1 = ((a23, -(a23 * b12), z), (-(a23 * b12), a23 - a12, a12 * b23), (z, a12 * b23, -a12))       # columns (symmetric)
+        D2 = ((a23, z, -(a23 * b13)), (z, -a13, a13 * b23), (-(a23 * b13), a13 * b23, a23 - a13))
+        c3 = _det3(D2[0], D2[1], D2[2])
+        c2 = (_det3(D1[0], D2[1], D2[2]) + _det3(D2[0], D1[1], D2[2])) + _det3(D2[0], D2[1], D1[2])
+        c1 = (_det3(D2[0], D1[1], D1[2]) + _det3(D1[0], D2[1], D1[2])) + _det3(D1[0], D1[1], D2[2])
+        c0 = _det3(D1[0], D1[1], D1[2])
+        ok &= c3 != 0
+        ca, cb, cc = c2 / c3, c1 / c3, c0 / c3
+        xi = -ca / c(3)
+        disc = ca * ca - c(3) * cb
+        fi = ((xi + ca) * xi + cb) * xi + cc
+        r = c(2) * np.sqrt(np.where(disc > 0, disc, c(0))) / c(3)
+        g = np.where(disc > 0, np.where(fi > 0, xi - r, xi + r), xi)
+        for _ in range(P3P_CUBIC_STEPS):
+            f = ((g + ca) * g + cb) * g + cc
+            fp = (c(3) * g + c(2) * ca) * g + cb
+            g = np.where(fp != 0, g - f / np.where(fp != 0, fp, c(1)), g)
+        # 3. the rank-2 form D0 = D1 + g D2
+        d = (D1[0][0] + g * D2[0][0], D1[0][1] + g * D2[0][1], D1[0][2] + g * D2[0][2],
+             D1[1][1] + g * D2[1][1], D1[1][2] + g * D2[1][2], D1[2][2] + g * D2[2][2])
+        tr = (d[0] + d[3]) + d[5]
+        mm = ((d[0] * d[3] - d[1] * d[1]) + (d[0] * d[5] - d[2] * d[2])) + (d[3] * d[5] - d[4] * d[4])
+        dq = tr * tr - c(4) * mm
+        sq = np.sqrt(np.where(dq > 0, dq, c(0)))
+        la = (tr + np.where(tr >= 0, sq, -sq)) / c(2)
+        lb = mm / la
+        pos = la > 0
+        ok &= (pos & (lb < 0)) | ((la < 0) & (lb > 0))
+        ea, eb = _rank2_vector(d, la), _rank2_vector(d, lb)
+        e1 = tuple(np.where(pos, ea[k], eb[k]) for k in range(3))
+        e2 = tuple(np.where(pos, eb[k], ea[k]) for k in range(3))
+        lpos, lneg = np.where(pos, la, lb), np.where(pos, lb, la)
+        s = np.sqrt(np.where(ok, -lneg / lpos, c(0)))
+        # 4. - 7. the four candidate slots, in order
+        best_err = np.full(H, np.inf, dt)
+        slot = np.full(H, -1, np.int64)
+        Rb = [[np.zeros(H, dt) for _ in range(3)] for _ in range(3)]
+        tb = [np.zeros(H, dt) for _ in range(3)]
+        det = {k: [] for k in ("alive", "usable", "lengths", "R", "t", "err")}
+        x4, y4 = xy[:, 3, 0], xy[:, 3, 1]
+        for sign in range(2):
+            ss = s if sign == 0 else -s
+            p0, p1, p2 = e1[0] - ss * e2[0], e1[1] - ss * e2[1], e1[2] - ss * e2[2]
+            w0, w1 = -p1 / p0, -p2 / p0
+            A = a23 * (w1 * w1) - a12
+            B = a23 * (c(2) * (w0 * w1) - c(2) * (b12 * w1)) + c(2) * (a12 * b23)
+            C = a23 * ((w0 * w0 + c(1)) - c(2) * (b12 * w0)) - a12
+            qd = B * B - c(4) * (A * C)
+            sqd = np.sqrt(np.where(qd >= 0, qd, c(0)))
+            q = -(B + np.where(B >= 0, sqd, -sqd)) / c(2)
+            for root in range(2):
+                tau = q / A if root == 0 else C / q
+                den = (c(1) + tau * tau) - (c(2) * b23) * tau
+                l2 = np.sqrt(a23 / np.where(den > 0, den, c(1)))
+                l3 = tau * l2
+                l1 = w0 * l2 + w1 * l3
+                alive = ok & (qd >= 0) & (tau > 0) & (den > 0) & (l1 > 0)
+                # 5. polish
+                for _ in range(P3P_POLISH_STEPS):
+                    r1 = ((l1 * l1 + l2 * l2) - (c(2) * b12) * (l1 * l2)) - a12
+                    r2 = ((l1 * l1 + l3 * l3) - (c(2) * b13) * (l1 * l3)) - a13
+                    r3 = ((l2 * l2 + l3 * l3) - (c(2) * b23) * (l2 * l3)) - a23
+                    j00, j01 = c(2) * (l1 - b12 * l2), c(2) * (l2 - b12 * l1)
+                    j10, j12 = c(2) * (l1 - b13 * l3), c(2) * (l3 - b13 * l1)
+                    j21, j22 = c(2) * (l2 - b23 * l3), c(2) * (l3 - b23 * l2)
+                    dj = -(j00 * (j12 * j21)) - j01 * (j10 * j22)
+                    go = dj != 0
+                    dd = np.where(go, dj, c(1))
+                    # adj(J) r, J = [[j00 j01 0] [j10 0 j12] [0 j21 j22]]
+                    e1_ = (-(j12 * j21) * r1 - (j01 * j22) * r2) + (j01 * j12) * r3
+                    e2_ = (-(j10 * j22) * r1 + (j00 * j22) * r2) - (j00 * j12) * r3
+                    e3_ = ((j10 * j21) * r1 - (j00 * j21) * r2) - (j01 * j10) * r3
+                    l1 = np.where(go, l1 - e1_ / dd, l1)
+                    l2 = np.where(go, l2 - e2_ / dd, l2)
+                    l3 = np.where(go, l3 - e3_ / dd, l3)
+                # 6. pose
+                Y = [tuple(l * yb[i][k] for k in range(3)) for i, l in enumerate((l1, l2, l3))]
+                u1, u2 = sub(Y[0], Y[1]), sub(Y[0], Y[2])
+                u3 = _cross(u1, u2)
+                iw = c(1) / np.where(ok, area2, c(1))
+                wa, wb = _cross(v2, v3), _cross(v3, v1)
+                w = [tuple(wa[k] * iw for k in range(3)), tuple(wb[k] * iw for k in range(3)), tuple(v3[k] * iw for k in range(3))]
+                R = [[(u1[r_] * w[0][k] + u2[r_] * w[1][k]) + u3[r_] * w[2][k] for k in range(3)] for r_ in range(3)]
+                t = [Y[0][r_] - ((R[r_][0] * Xs[0][0] + R[r_][1] * Xs[0][1]) + R[r_][2] * Xs[0][2]) for r_ in range(3)]
+                # 7. choice by the fourth point
+                Xc = [((R[r_][0] * Xs[3][0] + R[r_][1] * Xs[3][1]) + R[r_][2] * Xs[3][2]) + t[r_] for r_ in range(3)]
+                zz = np.where(Xc[2] > 0, Xc[2], c(1))
+                ex, ey = Xc[0] / zz - x4, Xc[1] / zz - y4
+                err = ex * ex + ey * ey
+                fin = np.isfinite(err)
+                for r_ in range(3):
+                    fin &= np.isfinite(t[r_])
+                    for k in range(3):
+                        fin &= np.isfinite(R[r_][k])
+                usable = alive & fin & (Xc[2] > 0)
+                take = usable & (err < best_err)
+                best_err = np.where(take, err, best_err)
+                slot = np.where(take, 2 * sign + root, slot)
+                for r_ in range(3):
+                    tb[r_] = np.where(take, t[r_], tb[r_])
+                    for k in range(3):
+                        Rb[r_][k] = np.where(take, R[r_][k], Rb[r_][k])
+                if detail:
+                    det["alive"].append(alive)
+                    det["usable"].append(usable)
+                    det["lengths"].append(np.stack([l1, l2, l3], axis=1))
+                    det["R"].append(np.stack([np.stack(row, axis=1) for row in R], axis=1))
+                    det["t"].append(np.stack(t, axis=1))
+                    det["err"].append(err)
+        valid = slot >= 0
+        Rout = np.stack([np.stack(row, axis=1) for row in Rb], axis=1)
+        tout = np.stack(tb, axis=1)
+    Rout[~valid] = 0
+    tout[~valid] = 0
+    if not detail:
+        return Rout, tout, valid, slot
+    info = dict(alive=np.stack(det["alive"], axis=1), usable=np.stack(det["usable"], axis=1),
+                lengths=np.stack(det["lengths"], axis=1), poses=(np.stack(det["R"], axis=1), np.stack(det["t"], axis=1)),
+                err=np.stack(det["err"], axis=1), a=(a12, a13, a23), b=(b12, b13, b23),
+                bearings=np.stack([np.stack(v, axis=1) for v in yb], axis=1), area2=area2, amax=amax,
+                degenerate=~(area2 > c(P3P_AREA_TOL) * (amax * amax)))
+    return Rout, tout, valid, slot, info
+
+
 def scored_pose(R, t, X0):
     """(R32 (H, 9), t032 (H, 3), ok): the pose as scored, t0 = R X0 + t, rounded to fp32; ok = finite and |t0| <= RANGE."""
     R = np.asarray(R, np.float64).reshape(-1, 3, 3)
@@ -185,18 +396,26 @@ def error_ratio(R32, t032, d32, xy32, thr2):
     return np.where((Z > 0) & np.isfinite(r), r, np.inf)
 
 
-def hypotheses(corr, seed=0, pair=0, n_hyp=1024, threshold_px=2.0, K=EUROC_K, staged=None):
-    """What aria_pnp_debug_hypotheses returns: (sample_idx (H, 6), R (H, 9) fp32, t0 (H, 3) fp32, counts (H,), -1 = invalid)."""
+def hypotheses(corr, seed=0, pair=0, n_hyp=1024, threshold_px=2.0, K=EUROC_K, staged=None, solver="dlt", branches=None):
+    """What aria_pnp_debug_hypotheses returns: (sample_idx (H, 6), R (H, 9) fp32, t0 (H, 3) fp32, counts (H,), -1 = invalid).
+    solver="p3p": slots 4 and 5 of sample_idx are -1; `branches`, a list, receives the (H,) chosen candidate slots of
+    solve_p3p (-1 where the hypothesis is invalid)."""
     st = staged if staged is not None else stage(corr, K)
     n = len(st["X"])
-    idx = sample_indices(seed, pair, n_hyp, n)
+    k = min_corr(solver)
+    idx = sample_indices(seed, pair, n_hyp, n, k=k)
     valid = (idx >= 0).all(axis=1)
+    slots = np.full(n_hyp, -1, np.int64)
     R32 = np.zeros((n_hyp, 9), np.float32)
     t032 = np.zeros((n_hyp, 3), np.float32)
     counts = np.full(n_hyp, -1, np.int64)
     if valid.any():
         rows = np.flatnonzero(valid)
-        R, t, ok = solve_minimal(st["X"][idx[rows]], st["xy"][idx[rows]])
+        if solver == "dlt":
+            R, t, ok = solve_minimal(st["X"][idx[rows]], st["xy"][idx[rows]])
+        else:
+            R, t, ok, sl = solve_p3p(st["X"][idx[rows]], st["xy"][idx[rows]])
+            slots[rows] = sl
         r32, t32, ok2 = scored_pose(R, t, st["X0"])
         ok &= ok2
         R32[rows[ok]] = r32[ok]
@@ -208,6 +427,11 @@ def hypotheses(corr, seed=0, pair=0, n_hyp=1024, threshold_px=2.0, K=EUROC_K, st
         for a in range(0, len(live), 256):
             sel = live[a:a + 256]
             counts[sel] = inliers32(R32[sel], t032[sel], st["d32"], st["xy32"], thr2).sum(axis=1)
+    if k < 6:
+        idx = np.concatenate([idx, np.full((n_hyp, 6 - k), -1, np.int64)], axis=1)
+        slots[~valid] = -1
+    if branches is not None:
+        branches.append(slots)
     return idx, R32, t032, counts
 
 
@@ -292,17 +516,18 @@ def _invalid(n):
                 n_refit=0)
 
 
-def estimate(corr, seed=0, pair=0, n_hyp=1024, threshold_px=2.0, refine_iters=5, K=EUROC_K, dtype=None, hyp=None, staged=None):
+def estimate(corr, seed=0, pair=0, n_hyp=1024, threshold_px=2.0, refine_iters=5, K=EUROC_K, dtype=None, hyp=None, staged=None,
+             solver="dlt"):
     """aria_pnp_estimate on the CPU: a dict of the aria_pnp_result fields and the mask, plus what the tests need to judge a
     case: winner_R / winner_t0 (the winning pose as scored, fp32), refit_R / refit_t0 (the refined pose as rescored, fp32,
     whether or not it was kept; None without a refinement) and n_winner / n_refit. dtype=np.longdouble: the refinement and
-    the outputs in extended precision."""
+    the outputs in extended precision. solver: the minimal solver of the hypotheses, and the least count a pair needs."""
     st = staged if staged is not None else stage(corr, K)
     n = len(st["X"])
     res = _invalid(n)
-    if n < MIN_CORR:
+    if n < min_corr(solver):
         return res
-    _idx, R32, t032, counts = hyp if hyp is not None else hypotheses(corr, seed, pair, n_hyp, threshold_px, K, st)
+    _idx, R32, t032, counts = hyp if hyp is not None else hypotheses(corr, seed, pair, n_hyp, threshold_px, K, st, solver)
     best = int(np.argmax(counts))
     if counts[best] < 0:
         return res

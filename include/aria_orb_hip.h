@@ -1704,8 +1704,11 @@ int64_t aria_alert_algorithmic_bytes(int width, int zone_top, int zone_bottom, i
  *   that is not finite or beyond 1e15 in magnitude never scores; a pose with |t0| beyond 1e15 is invalid (so that every
  *   square of the test below stays finite).
  * Hypotheses. `hypotheses` per pair; the hash of the two-view stage with 6 distinct indices per hypothesis (slots
- *   j = 0..5, at most 256 draws per slot). Results depend on (seed, pair id, correspondences) only.
- * Minimal solver. 6-point DLT, one model per sample, fp64. Conditioning in sample order: c = mean of the six X, s = mean
+ *   j = 0..5, at most 256 draws per slot), 4 (slots j = 0..3) with the P3P solver. Results depend on (seed, pair id,
+ *   correspondences, solver) only.
+ * Solvers. Two minimal solvers, chosen per handle by aria_pnp_set_solver; the default is the 6-point DLT. Each yields one
+ *   model and one validity bit per hypothesis; everything from "Inliers" on is the same for both.
+ * Minimal solver, DLT. 6-point DLT, one model per sample, fp64. Conditioning in sample order: c = mean of the six X, s = mean
  *   of |X - c| (invalid when s is 0 or not finite), Xh = ((X - c) / s, 1). Rows [Xh, 0, -x Xh] and [0, Xh, -y Xh]; 11 of
  *   the 12 are taken: both rows of sample points 0..4 and the x-row of point 5. Gaussian elimination with partial pivoting
  *   (first row of largest |a|); a pivot with |pivot| <= 1e-9 * max|A_ij| marks the sample invalid. Back substitution with
@@ -1713,6 +1716,33 @@ int64_t aria_alert_algorithmic_bytes(int width, int zone_top, int zone_bottom, i
  *   front of the camera. P = [M | m]; invalid when det M <= 0. M = U S V^T (V from the 3x3 Jacobi of the two-view stage
  *   on M^T M, u_i = M v_i / sigma_i, third columns as cross products); invalid when sigma3 <= 1e-9 sigma1. R = U V^T,
  *   lambda = (s1 + s2 + s3) / 3, t' = m / lambda, t = s t' - R c.
+ * Minimal solver, P3P. Sample points 1..3 are solved, point 4 picks among the roots; fp64, and only + - * / and sqrt (no
+ *   cbrt, acos or cos: their results cannot be held between host and device); the elimination of Persson and Nordberg's
+ *   "Lambda Twist" with fixed iteration counts and a fixed order of candidates.
+ *   Setup: unit bearings y_i = (x_i, y_i, 1) / |.|, a_ij = |X_i - X_j|^2 from the differences, b_ij = y_i . y_j; the
+ *   unknowns are the distances l_i > 0 with l_i^2 + l_j^2 - 2 b_ij l_i l_j = a_ij. Invalid when
+ *   |(X1 - X2) x (X1 - X3)|^2 <= 1e-12 * max(a_ij)^2: collinear or coincident sample points.
+ *   Cubic: with M12, M13, M23 the symmetric forms of the three equations, D1 = a23 M12 - a12 M23, D2 = a23 M13 - a13 M23;
+ *   det(D1 + g D2) = 0, coefficients from 3x3 determinants (columns of D1 and D2 mixed), invalid when c3 = 0. One real root
+ *   of the monic cubic by 30 Newton steps from the inflection point x_i, or, when the derivative's discriminant
+ *   D = a^2 - 3 b is positive, from x_i - (2/3) sqrt(D) if f(x_i) > 0 and x_i + (2/3) sqrt(D) otherwise; a step whose
+ *   derivative is 0 is not taken.
+ *   Rank-2 form: D0 = D1 + g D2; its non-zero eigenvalues from l^2 - tr l + m (m = the sum of the principal 2x2 minors),
+ *   the root of larger magnitude as (tr + sign(tr) sqrt(tr^2 - 4 m)) / 2, the other as m / l; each eigenvector the largest
+ *   of the three row cross products of D0 - l I (ties to the earliest), normalised. Invalid unless the eigenvalues have
+ *   opposite signs; s = sqrt(-l_neg / l_pos), e1 and e2 the eigenvectors of l_pos and l_neg.
+ *   Candidates, four slots in this order: (+s, -s) x (first, second root of tau). The plane (e1 - s e2) . l = 0 gives
+ *   l1 = w0 l2 + w1 l3; with l3 = tau l2 the first two equations give A tau^2 + B tau + C = 0, solved as
+ *   q = -(B + sign(B) sqrt(B^2 - 4 A C)) / 2, tau = q / A, then C / q. A slot is kept when the discriminant is >= 0,
+ *   tau > 0, 1 + tau^2 - 2 b23 tau > 0 and l1 > 0, with l2 = sqrt(a23 / (1 + tau^2 - 2 b23 tau)).
+ *   Polish: five Newton steps on the three distance equations per slot, the 3x3 system by its adjugate; a step with a zero
+ *   determinant is not taken.
+ *   Pose: Y_i = l_i y_i; R = [Y1-Y2, Y1-Y3, (Y1-Y2) x (Y1-Y3)] [X1-X2, X1-X3, (X1-X2) x (X1-X3)]^-1 (the inverse from cross
+ *   products over |(X1-X2) x (X1-X3)|^2), t = Y1 - R X1.
+ *   Choice: Xc = R X4 + t per slot; a slot that is not finite or has Xc.z <= 0 is dropped; the model is the slot with the
+ *   least (Xc.x / Xc.z - x4)^2 + (Xc.y / Xc.z - y4)^2, ties to the earliest; no slot left: invalid. One model per
+ *   hypothesis is a decision: scoring every root would quadruple the scoring loop. The price: an outlier in slot 4 can
+ *   pick the wrong root of an otherwise clean sample.
  * Inliers. In fp32 and division-free: Xc = R d + t0, each component ((r0 dx + r1 dy) + r2 dz) + t0; a point is an inlier
  *   when Xc.z > 0 and (Xc.x - x Xc.z)^2 + (Xc.y - y Xc.z)^2 <= thr2 * Xc.z^2, thr2 = (threshold_px / ((fx + fy) / 2))^2.
  * Winner. Most inliers; ties to the lowest h; an invalid hypothesis scores -1. Integer counts, fixed reduction order.
@@ -1727,11 +1757,16 @@ int64_t aria_alert_algorithmic_bytes(int width, int zone_top, int zone_bottom, i
  *   result is the winner as scored.
  * Outputs. The mask and n_inliers are those of the kept pose; t = t0 - R X0; rms_px is the RMS of the residuals above
  *   over them, in fp64 in a fixed order, times (fx + fy) / 2.
- * Validity. valid = 0 with fewer than 6 correspondences, with no valid hypothesis, or when a result field would not be
+ * Validity. valid = 0 with fewer than 6 correspondences (4 with P3P), with no valid hypothesis, or when a result field would not be
  *   finite: R = I, t = 0, counts 0, best_hypothesis = -1, zero mask. No field is ever NaN or Inf.
  * Determinism. No float atomics; bitwise reproducible run to run and independent of how pairs are split into calls.
- * Known limit. A 6-point DLT is degenerate on a planar sample: every pivot test fails on a planar scene, which yields
- *   valid = 0. A P3P minimal solver is the follow-up. */
+ * Planar scenes. A 6-point DLT is degenerate on a planar sample: every pivot test fails on a planar scene, which yields
+ *   valid = 0 with the default solver. A plane is no degeneracy of P3P: select it (aria_pnp_set_solver) where the view
+ *   may be a wall, a floor or a table top. It also needs fewer hypotheses: a clean 4-sample at 50 % outliers is a 1 in 16
+ *   draw, a clean 6-sample 1 in 64. The refinement still needs 6 inliers, so a pair of 4 or 5 correspondences yields the
+ *   winner as scored. */
+#define ARIA_PNP_SOLVER_DLT6 0
+#define ARIA_PNP_SOLVER_P3P  1
 typedef struct aria_pnp_s* aria_pnp_t;
 typedef struct {
     double X[3];               /* world point                                                                    */
@@ -1758,6 +1793,11 @@ void  aria_pnp_default_config(aria_pnp_config* cfg);
 int   aria_pnp_create(const aria_pnp_config* cfg, aria_pnp_t* out);
 void  aria_pnp_destroy(aria_pnp_t h);
 void* aria_pnp_stream(aria_pnp_t h);
+/* The minimal solver of the calls issued after this one (aria_pnp_estimate, _estimate_batch_device, _debug_hypotheses; the
+ * association does not depend on it). A launch parameter: nothing is synchronised, work already enqueued keeps the solver
+ * it was issued with. An unknown value: ARIA_E_INVALID, the handle unchanged. A new handle has ARIA_PNP_SOLVER_DLT6. */
+int   aria_pnp_set_solver(aria_pnp_t h, int solver);
+int   aria_pnp_get_solver(aria_pnp_t h);
 /* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check:
  * ARIA_E_INVALID when some pair's count was outside [0, corr_cap] (estimate) or its counts or match indices were out of
  * range (associate). Such a pair is detected before any of its data is read and skipped (n_corr = 0, valid = 0, zero
@@ -1770,7 +1810,8 @@ int   aria_pnp_estimate(aria_pnp_t h, const aria_pnp_corr* corr, int n, int pair
  * sees pair id pair_base + p. Enqueued on the handle's stream; nothing is synchronised, except when the workspace grows. */
 int   aria_pnp_estimate_batch_device(aria_pnp_t h, const aria_pnp_corr* d_corr, const int* d_ncorr, int n_pairs, int corr_cap,
                                      int pair_base, aria_pnp_result* d_out, uint8_t* d_mask);
-/* Test hook: for one pair (host buffers), every hypothesis's 6 sample indices (sample_idx[h*6 + j]; -1 when n < 6), R
+/* Test hook: for one pair (host buffers), every hypothesis's 6 sample indices (sample_idx[h*6 + j]; -1 when n < 6; with
+ * P3P slots 0..3 hold the sample and slots 4 and 5 are -1), R
  * (R[h*9 + k]) and t0 (t0[h*3 + k]) in fp32 as scored (zero when invalid) and inlier count (counts[h], -1 when invalid). */
 int   aria_pnp_debug_hypotheses(aria_pnp_t h, const aria_pnp_corr* corr, int n, int pair_base, int* sample_idx, float* R,
                                 float* t0, int* counts);
