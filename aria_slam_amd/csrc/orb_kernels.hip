@@ -10,8 +10,9 @@
 //   k_describe    a6.6  intensity-centroid angle (one keypoint per 16-lane DPP row, integer moments, fastAtan2)
 //                 a6.8  256-bit rBRIEF: lane l16 of a row evaluates tests 16*it + l16; one 64-bit ballot per iteration
 //                       carries 16 descriptor bits for each of the wave's four keypoints (LSB-first bytes)
-//                 batch path (Q4 levels): 16 keypoints per wave in four such rounds, the angle and sincos once (describe16)
-// All of it is HBM/LDS/VALU-integer work; nothing here is a dense contraction, so no MFMA.
+//                 batch path (Q4 levels): 16 keypoints per wave, the angle and sincos once (describe16); the moments of the
+//                       16 are one [16 x 1024] x [1024 x 2] int8 contraction on the matrix cores (v_mfma_i32_16x16x64_i8)
+// The rest is HBM/LDS/VALU-integer work.
 // Float stages are compiled with -ffp-contract=off so that they round exactly like the SSE3-baseline
 // OpenCV build the CPU reference path uses (no FMA).
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "ic_moment_weights.h"
 #include "orb_device.h"
 #include "orb_kernels.h"
 
@@ -45,9 +47,15 @@ constexpr PatternLaneMajor make_pattern_lane_major() {
 }
 __device__ __attribute__((aligned(16))) const PatternLaneMajor kPattern31 = make_pattern_lane_major();
 
-// end-of-row table of the radius-15 disc (orb.cpp computeKeyPoints umax; verified against the host
-// computation in tests/test_host_logic.py)
-#define ARIA_UMAX_LIST {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3}
+// (the end-of-row table of the radius-15 disc, ARIA_UMAX_LIST: ic_moment_weights.h)
+
+// The IC moment weights of the batch k_describe's matrix-core phase (describe16<0>): [role][piece][16] int8, 2 KB, copied
+// into LDS by every wave. -DARIA_DESC_MOMENTS_LDS=1 (tools/build_ab.sh, the A side of A/B measurements) builds the four
+// LDS moment rounds for MODE 0 as well; the library reads no switch at run time.
+#ifndef ARIA_DESC_MOMENTS_LDS
+#define ARIA_DESC_MOMENTS_LDS 0
+#endif
+__device__ __attribute__((aligned(16))) const IcMomentWeights kIcMomentW = make_ic_moment_weights();
 
 // Byte masks of the radius-15 disc for k_describe's dword-wise IC moments, laid out like the pattern: lane
 // (hp = l16 >> 3, j = l16 & 7) owns patch columns u = 4j-15 .. 4j-12 of the rows v = 2k + hp - 15, k = 0..15, and
@@ -816,17 +824,31 @@ __device__ __forceinline__ void describe16(const Plan& P, const FrameSrc& S, con
     const int grp = lane >> 4, l16 = lane & 15;
     const int rs = l16 & 3;                                   // the round whose keypoint (4 rs + grp) this lane's record is
     uint8_t* const win = s_patch[wv * 4 + grp];
+#if ARIA_DESC_MOMENTS_LDS
+    constexpr bool MOM_MFMA = false;
+#else
+    constexpr bool MOM_MFMA = !ARENA;                         // the moments on the matrix cores (the arena keeps the LDS rounds)
+#endif
+    // the moment weights, [role][piece][16] int8: a copy per wave (two 16-byte pieces per lane), so that no wave waits for
+    // another one
+    static_assert(sizeof(IcMomentWeights) == 2 * 16 * 64, "two 16-byte pieces of the weight table per lane");
+    __shared__ __attribute__((aligned(16))) int8_t s_icw[kDescWaves][sizeof(IcMomentWeights)];
 
     // ---- bookkeeping once per 16 keypoints ----
     int frame = 0, l = 0, base = 0;                           // MODE 0: the wave's; MODE 1: per round (below)
     uint4 sv;
     bool valid;                                               // this lane's record is a keypoint to describe (l16 < 4)
     uint32_t act = 0;                                         // wave-uniform: bit r = round r has work
+    uint4 wq0 = make_uint4(0u, 0u, 0u, 0u), wq1 = wq0;        // this lane's pieces of the moment weights
     if constexpr (!ARENA) {
         const int blk = __builtin_amdgcn_readfirstlane(blk_in);
         const int xcd = blk & 7, j = blk >> 3;                // XCD-aware block -> frame map (as in the 4-keypoint form)
         frame = __builtin_amdgcn_readfirstlane((j / blocks_per_frame) * 8 + xcd);
         if (frame >= n_frames) return;
+        if constexpr (MOM_MFMA) {                             // (in flight during the bookkeeping; stored behind the window requests)
+            wq0 = reinterpret_cast<const uint4*>(&kIcMomentW.w[0][0][0])[lane];
+            wq1 = reinterpret_cast<const uint4*>(&kIcMomentW.w[1][0][0])[lane];
+        }
         const int w = __builtin_amdgcn_readfirstlane((j % blocks_per_frame) * kDescWaves + wv);   // wave of the frame
         const int* cnt = sel_cnt + frame * kLevels;
         int total = 0, wl = 0, i0 = -1;
@@ -883,6 +905,104 @@ __device__ __forceinline__ void describe16(const Plan& P, const FrameSrc& S, con
     if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
     DSTAMP16(1);
 
+    // request round r's blurred Q4 window: 10 x 10 pieces of 16 bytes, 7 per lane (the last lanes repeat piece 99)
+    constexpr int kPv = 7;
+    DwordQuad pv[kPv];
+    int pq[kPv], pc[kPv];
+#pragma unroll
+    for (int k = 0; k < kPv; k++) {
+        const int p = min(16 * k + l16, kDescQ * kDescQ - 1);
+        pq[k] = (p * 205) >> 11;                            // p / 10 for p < 1024
+        pc[k] = p - kDescQ * pq[k];
+    }
+    auto blur_issue = [&](int r) {
+        int fr, lr;
+        round_fl(r, fr, lr);
+        const uint8_t* bl = blur + (int64_t)fr * P.blur_frame_bytes + P.lv[lr].blur_off;
+        const int qp = P.lv[lr].pitch * 4;
+        const int xy = row_pick((int)sv.x, row_src(r));
+        const int x = xy & 0xFFFF, y = (int)((uint32_t)xy >> 16);
+        const uint32_t o = (uint32_t)(((y - kDescR) >> 2) * qp + ((x - kDescR) >> 2) * 16);
+#pragma unroll
+        for (int k = 0; k < kPv; k++)
+            pv[k] = *reinterpret_cast<const DwordQuad*>(bl + (o + (uint32_t)(pq[k] * qp + pc[k] * 16)));
+    };
+
+    int m10_s = 0, m01_s = 0;                               // parked moments: lane (g, r) <- keypoint 4r + g
+    const int nr = 32 - __builtin_clz(act);                 // rounds with work (a prefix)
+    if constexpr (MOM_MFMA) {
+    // ---- the moments of the 16 keypoints as one int8 matrix product (ic_moment_weights.h) ----
+    //   D[m][n] = sum_k A[m][k] * B[k][n]: m = the keypoint's row, k = the 1024 bytes of its 64 window pieces, n = the role
+    // A: lane (kb = lane >> 4, m = lane & 15) supplies piece 4 * step + kb of keypoint-row m in step 0..15: the 16 bytes at
+    //    (x - 15, y - 15) + (row, 16 * half), straight from memory into the operand registers, no realignment in LDS.
+    //    Byte-exact 16-byte loads are served far slower than dword-aligned ones, so the lane loads the four
+    //    dwords from the dword-aligned start and cuts the piece out of them and a fifth dword (below) with v_alignbyte
+    //    (sh = the start's byte in its dword). Only a level-0 image that is not dword-aligned takes the byte-exact load
+    //    (sh = 0, the fifth dword unused). Every read stays inside its image row: x + 20 < w for a keypoint 31 px from
+    //    the edge.
+    //    Pixel bytes XOR 0x80 = I - 128.
+    // B: lane (kb, n) supplies the same piece of role (n >> 2) & 1 from the LDS copy of the table: columns 0..3 = m10,
+    //    4..7 = m01 (the columns above repeat them, unused). A and B use one k numbering, so its order inside the
+    //    instruction does not matter.
+    // D: lane (g, n) holds rows 4g .. 4g + 3 of column n in its four registers. Row 4g + r = keypoint 4r + g, so lane (g, n)
+    //    finds keypoint 4 * (n & 3) + g in register n & 3: its own m10 for n < 4, and its m01 four lanes up (row_shl:4).
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    typedef v4i __attribute__((aligned(1))) v4i_unaligned;
+    typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+    int pitch;
+    const uint8_t* img = raw_level_ptr(P, S, raw, frame, l, pitch);
+    const bool exact = __builtin_amdgcn_readfirstlane((l == 0) && !S.aligned4) != 0;
+    const int xy = row_pick((int)sv.x, ((l16 >> 2) * 16 + (l16 & 3)) << 2);   // row m = l16: the record of lane (m >> 2, m & 3)
+    const int x = xy & 0xFFFF, y = (int)((uint32_t)xy >> 16);
+    const int prow = grp >> 1, phalf = grp & 1;             // piece 4k + grp = row 2k + prow, half phalf
+    const uint32_t sh = exact ? 0u : (uint32_t)(x - kHalfPatch) & 3u;
+    const uint32_t o = (uint32_t)((y - kHalfPatch + prow) * pitch + (x - kHalfPatch) + 16 * phalf) - sh;
+    struct Piece { v4i q; uint32_t e; };
+    auto piece = [&](int k) -> Piece {                      // (pieces 62, 63: row 30 again, their weights are zero)
+        const uint32_t off = k < 15 ? o + (uint32_t)(2 * k * pitch) : o + (uint32_t)((30 - prow) * pitch);
+        Piece t;
+        t.q = *reinterpret_cast<const v4i_unaligned*>(img + off);
+        t.e = 0u;
+        if (k >= kIcTailStepLo && k <= kIcTailStepHi) t.e = *reinterpret_cast<const u32_unaligned*>(img + off + 16);
+        return t;
+    };
+    // The fifth dword of a piece: for half 0 it is the first dword of the row's half 1, which the lane 16 up has loaded
+    // (ds_bpermute, no second load). For half 1 it holds the columns u >= 13 - sh of the row at most, which lie inside
+    // the disc only in the rows of the steps kIcTailStepLo..Hi (ic_moment_weights.h): those steps load it, in the
+    // others whatever the bpermute brings meets zero weights.
+    const int up16 = ((lane + 16) & 63) << 2;
+    auto operand = [&](const Piece& t, int k) -> v4i {
+        v4i r;
+        uint32_t e = (uint32_t)__builtin_amdgcn_ds_bpermute(up16, t.q[0]);
+        if (k >= kIcTailStepLo && k <= kIcTailStepHi) e = phalf ? t.e : e;
+        r[0] = (int)__builtin_amdgcn_alignbyte((uint32_t)t.q[1], (uint32_t)t.q[0], sh);
+        r[1] = (int)__builtin_amdgcn_alignbyte((uint32_t)t.q[2], (uint32_t)t.q[1], sh);
+        r[2] = (int)__builtin_amdgcn_alignbyte((uint32_t)t.q[3], (uint32_t)t.q[2], sh);
+        r[3] = (int)__builtin_amdgcn_alignbyte(e, (uint32_t)t.q[3], sh);
+        return r ^ (int)0x80808080;
+    };
+    const int8_t* wb = s_icw[wv] + ((l16 >> 2) & 1) * (kIcPieces * kIcPieceBytes) + grp * kIcPieceBytes;
+    Piece a[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) a[k] = piece(k);
+    reinterpret_cast<uint4*>(s_icw[wv])[lane] = wq0;         // (requested first: here long before the windows)
+    reinterpret_cast<uint4*>(s_icw[wv])[64 + lane] = wq1;
+    __builtin_amdgcn_wave_barrier();
+    v4i acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        if (k == 8) blur_issue(0);                          // behind the second half: the first blurred windows fly
+        const v4i av = operand(a[k & 7], k);
+        const v4i bv = *reinterpret_cast<const v4i*>(wb + 4 * kIcPieceBytes * k);
+        if (k & 1) acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bv, acc1, 0, 0, 0);
+        else acc0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bv, acc0, 0, 0, 0);
+        if (k < 8) a[k] = piece(k + 8);                     // the second half is requested while the first is consumed
+    }
+    const v4i acc = acc0 + acc1;
+    const int sel = (l16 & 2) ? ((l16 & 1) ? acc[3] : acc[2]) : ((l16 & 1) ? acc[1] : acc[0]);
+    m10_s = sel;
+    m01_s = __builtin_amdgcn_update_dpp(0, sel, 0x104, 0xF, 0xF, true);       // row_shl:4: lane (g, n) <- lane (g, n + 4)
+    } else {
     // ---- moment rounds ----
     uint32_t icm[16];
 #pragma unroll
@@ -927,32 +1047,8 @@ __device__ __forceinline__ void describe16(const Plan& P, const FrameSrc& S, con
             }
         }
     };
-    // request round r's blurred Q4 window: 10 x 10 pieces of 16 bytes, 7 per lane (the last lanes repeat piece 99)
-    constexpr int kPv = 7;
-    DwordQuad pv[kPv];
-    int pq[kPv], pc[kPv];
-#pragma unroll
-    for (int k = 0; k < kPv; k++) {
-        const int p = min(16 * k + l16, kDescQ * kDescQ - 1);
-        pq[k] = (p * 205) >> 11;                            // p / 10 for p < 1024
-        pc[k] = p - kDescQ * pq[k];
-    }
-    auto blur_issue = [&](int r) {
-        int fr, lr;
-        round_fl(r, fr, lr);
-        const uint8_t* bl = blur + (int64_t)fr * P.blur_frame_bytes + P.lv[lr].blur_off;
-        const int qp = P.lv[lr].pitch * 4;
-        const int xy = row_pick((int)sv.x, row_src(r));
-        const int x = xy & 0xFFFF, y = (int)((uint32_t)xy >> 16);
-        const uint32_t o = (uint32_t)(((y - kDescR) >> 2) * qp + ((x - kDescR) >> 2) * 16);
-#pragma unroll
-        for (int k = 0; k < kPv; k++)
-            pv[k] = *reinterpret_cast<const DwordQuad*>(bl + (o + (uint32_t)(pq[k] * qp + pc[k] * 16)));
-    };
-
-    int m10_s = 0, m01_s = 0;                               // parked moments: lane (g, r) <- round r, row g
-    const int nr = 32 - __builtin_clz(act);                 // rounds with work (a prefix)
-    // one moment round: raw window -> LDS, then the next request (`next`) flies while this round reduces
+    // one moment round: raw window -> LDS, then the next request (`next`) flies while this round reduces (the moments are
+    // parked into lane (g, r) <- round r, row g)
     auto moment_round = [&](int r, auto next) {
         const int sh = sh_n;
         {
@@ -993,6 +1089,7 @@ __device__ __forceinline__ void describe16(const Plan& P, const FrameSrc& S, con
 #pragma unroll 1
     for (int r = 0; r < nr - 1; r++) moment_round(r, [&] { raw_issue(r + 1); });
     moment_round(nr - 1, [&] { blur_issue(0); });         // the last round: the first blurred windows fly instead
+    }
     if (stamps) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
     DSTAMP16(2);
 
