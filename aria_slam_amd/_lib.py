@@ -104,6 +104,10 @@ EXPORTS = [
     # frame-to-model tracking (batched point-to-plane ICP against the ray-cast model view), additive to ABI 4
     "aria_icp_default_config", "aria_icp_create", "aria_icp_destroy", "aria_icp_stream", "aria_icp_check",
     "aria_icp_track_batch_device", "aria_icp_track", "aria_icp_debug_system_device", "aria_icp_algorithmic_bytes",
+    # mesh of the TSDF volume (watertight marching tetrahedra: vertices and triangles), additive to ABI 4
+    "aria_mesh_default_config", "aria_mesh_create", "aria_mesh_destroy", "aria_mesh_stream", "aria_mesh_check",
+    "aria_mesh_update_from_volume_device", "aria_mesh_extract_device", "aria_mesh_extract", "aria_mesh_scratch_bytes",
+    "aria_mesh_algorithmic_bytes",
 ]
 
 
@@ -329,6 +333,16 @@ class TsdfConfig(C.Structure):
 # aria_tsdf_voxel (8 bytes) and aria_tsdf_point (16 bytes)
 TSDF_VOXEL_DTYPE = np.dtype([("tsdf", "<f4"), ("weight", "<u2"), ("gray", "u1"), ("reserved", "u1")])
 TSDF_POINT_DTYPE = np.dtype([("X", "<f4", (3,)), ("gray", "u1"), ("axis", "u1"), ("weight", "<u2")])
+
+
+class MeshConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int),
+                ("nz", C.c_int), ("min_weight", C.c_int), ("voxel", C.c_float), ("origin", C.c_float * 3)]
+
+
+# aria_mesh_vertex (16 bytes) and aria_mesh_triangle (12 bytes)
+MESH_VERTEX_DTYPE = np.dtype([("X", "<f4", (3,)), ("gray", "u1"), ("dir", "u1"), ("weight", "<u2")])
+MESH_TRIANGLE_DTYPE = np.dtype([("v", "<u4", (3,))])
 
 
 class RayConfig(C.Structure):
@@ -569,6 +583,8 @@ def load_library():
         _bind_ray(L)
     if hasattr(L, "aria_icp_create"):
         _bind_icp(L)
+    if hasattr(L, "aria_mesh_create"):
+        _bind_mesh(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -738,6 +754,18 @@ def _bind_ray(L):
     L.aria_ray_cast.argtypes = [p, p, i, i, p, p, p, p, p]
     L.aria_ray_algorithmic_bytes.restype = i64
     L.aria_ray_algorithmic_bytes.argtypes = [i, i, i, i]
+
+
+def _bind_mesh(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "mesh")
+    L.aria_mesh_update_from_volume_device.argtypes = [p, p]
+    L.aria_mesh_extract_device.argtypes = [p, p, i64, p, i64, p]
+    L.aria_mesh_extract.argtypes = [p, p, i64, p, i64, p]
+    L.aria_mesh_scratch_bytes.restype = i64
+    L.aria_mesh_scratch_bytes.argtypes = [i, i, i]
+    L.aria_mesh_algorithmic_bytes.restype = i64
+    L.aria_mesh_algorithmic_bytes.argtypes = [i, i, i, i64, i64]
 
 
 def _bind_nav(L):

@@ -1,7 +1,7 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--pnp-solver dlt|p3p] [--bundle FILE3] [--bundle-window N]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
-//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE] [--track-dense FILE2]
+//                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--mesh FILE2.ply] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE] [--track-dense FILE2]
 //
 // The feature front-end of the reference's only end-to-end harness, src/euroc_eval.cpp:128-176, driven through the
 // ports instead of cv::cuda::ORB / cv::cuda::DescriptorMatcher: for every image of an ASL/EuRoC sequence
@@ -113,6 +113,12 @@
 // surface points are written as PLY (the --map header and vertex format) and "volume <points> <observed voxels>" is printed.
 // Without the flag nothing of this runs and every output is byte-identical.
 //
+// --mesh FILE2.ply (needs --volume): the mesh of the volume on the device (include/aria_orb_hip.h, "mesh of the volume"; aria_hip/
+// HipVolumeMesher.hpp). After the volume is built and its points are written, its records are contoured by marching tetrahedra
+// and FILE2 gets the triangle mesh as PLY: the --volume header and vertex lines plus "element face" / "property list uchar int
+// vertex_indices". Exactly one line "mesh <vertices> <triangles>" is printed. Without the flag nothing of this runs and every
+// output is byte-identical.
+//
 // --plan FILE (needs --volume): path planning on the device (include/aria_orb_hip.h, "path planning"; aria_hip/
 // HipPathPlanner.hpp). After the volume is built its band [ny/2 - 8, ny/2 + 16) around the first camera's height is collapsed into
 // the traversability grid of the x-z plane (up_axis 1, the stage's default radii and penalties, which nobody has tuned on a
@@ -175,6 +181,7 @@
 #include "aria_hip/MapTracker.hpp"
 #include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/HipPathPlanner.hpp"
+#include "aria_hip/HipVolumeMesher.hpp"
 #include "aria_hip/HipVolumeRenderer.hpp"
 #include "aria_hip/DenseTracker.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
@@ -216,11 +223,12 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--mesh file2.ply] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
                              "  --track-dense file2: frame-to-model tracking of the --dense depth maps against a volume of its own (needs --volume): one TUM line per frame\n"
                              "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
                              "  --render prefix: the --volume map cast at every n-th integrated pose (--render-every n, default 10; needs --volume):\n"
                              "                   prefix_<frame>_depth.pgm (16-bit mm) and prefix_<frame>_shade.pgm per view\n"
+                             "  --mesh file2.ply: the --volume map as a triangle mesh (watertight marching tetrahedra; needs --volume)\n"
                              "  --plan file: a path over the --volume map from the cell under the first camera of the --pose chain to the cell under the last\n"
                              "               (needs --volume): one x y z line per path cell\n"
                              "  --volume file.ply: dense depth fusion of the --dense depth maps along the --pose chain (needs --pose, --stereo, --dense): the surface\n"
@@ -249,7 +257,7 @@ int main(int argc, char** argv) {
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
     bool stereo = false, rectify = false;
-    std::string stereo_file, dense_file, volume_file, plan_file, alerts_file, render_prefix, dense_track_file;
+    std::string stereo_file, dense_file, volume_file, mesh_file, plan_file, alerts_file, render_prefix, dense_track_file;
     int render_every = 10;
     double voxel = 0.05;
     for (int i = 2; i < argc; i++) {
@@ -277,6 +285,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rectify")) rectify = true;
         else if (!std::strcmp(argv[i], "--dense") && i + 1 < argc) dense_file = argv[++i];
         else if (!std::strcmp(argv[i], "--volume") && i + 1 < argc) volume_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh_file = argv[++i];
         else if (!std::strcmp(argv[i], "--voxel") && i + 1 < argc) voxel = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--plan") && i + 1 < argc) plan_file = argv[++i];
         else if (!std::strcmp(argv[i], "--alerts") && i + 1 < argc) alerts_file = argv[++i];
@@ -340,6 +349,10 @@ int main(int argc, char** argv) {
     }
     if (!volume_file.empty() && (pose_file.empty() || !stereo || dense_file.empty() || !(voxel > 0))) {
         std::fprintf(stderr, "--volume needs --pose (the trajectory), --stereo baseline_m (its metric scale), --dense file (the depth maps) and --voxel > 0\n");
+        return 1;
+    }
+    if (!mesh_file.empty() && volume_file.empty()) {
+        std::fprintf(stderr, "--mesh needs --volume file.ply (the map it contours)\n");
         return 1;
     }
     if (!plan_file.empty() && volume_file.empty()) {
@@ -433,6 +446,7 @@ int main(int argc, char** argv) {
     adapters::hip::PoseIntrinsics bundle_K;
     long long bundle_first = -1;
     long long volume_points = 0, volume_observed = 0;   // --volume
+    long long mesh_vertices = 0, mesh_triangles = 0;    // --mesh
     long long alert_events = 0, alert_frames = 0;       // --alerts
     std::vector<std::string> alert_lines;
     long long render_views = 0, render_hits = 0;        // --render
@@ -713,6 +727,13 @@ int main(int argc, char** argv) {
             if (volume) {
                 volume_points = (long long)volume->exportPLY(volume_file);
                 volume_observed = (long long)volume->observedVoxels();
+            }
+            if (volume && !mesh_file.empty()) {
+                adapters::hip::HipVolumeMesher mesher(adapters::hip::VolumeMesherConfig::fromVolume(*volume));
+                mesher.update(*volume);
+                const auto counts = mesher.exportPLY(mesh_file);
+                mesh_vertices = (long long)counts.first;
+                mesh_triangles = (long long)counts.second;
             }
             if (volume && !render_prefix.empty() && !integrated.empty()) {
                 adapters::hip::HipVolumeRenderer renderer(adapters::hip::VolumeRendererConfig::fromVolume(*volume));
@@ -997,6 +1018,7 @@ int main(int argc, char** argv) {
         std::printf("dense 64 disparities | mean valid share %.4f -> %s\n", N ? share / N : 0.0, dense_file.c_str());
     }
     if (!volume_file.empty()) std::printf("volume %lld %lld\n", volume_points, volume_observed);
+    if (!mesh_file.empty()) std::printf("mesh %lld %lld\n", mesh_vertices, mesh_triangles);
     if (!plan_file.empty()) std::printf("plan %d %d %d\n", plan_record.status, plan_record.cost, plan_record.n_cells);
     if (!render_prefix.empty()) std::printf("render %lld %lld\n", render_views, render_hits);
     if (!dense_track_file.empty()) {

@@ -1314,9 +1314,9 @@ int64_t aria_dense_algorithmic_bytes(int width, int height);
 /* ---- dense depth fusion: the fp32 depth maps of aria_dense_* integrated along the trajectory into one truncated signed
  * distance volume in HBM, and the surface points read back out of it. The reference has no code for it (its roadmap items
  * H17, H20 and H22 sit on such a map), so the NumPy restatement aria_slam_amd/tsdf_ref.py is the definition and the device
- * equals it bit for bit. Out of scope: marching-cubes meshes, bilinear depth lookup, volume shifting or hashing,
+ * equals it bit for bit. Out of scope: bilinear depth lookup, volume shifting or hashing,
  * and any alert logic (path planning is the stage below; normals and ray casting are the stage "ray casting of the
- * volume"). Additive to ABI 4.
+ * volume"; triangle meshes are the stage "mesh of the volume"). Additive to ABI 4.
  *
  * Unless stated otherwise the arithmetic is fp32, one rounding per operation, no contraction, in exactly the order written.
  * 1. Volume. nx, ny, nz voxels, each a multiple of 8 in 8..1024; `voxel` the edge in metres (> 0); origin[3] the world
@@ -1954,7 +1954,7 @@ int   aria_ba_window_from_chain_device(aria_ba_t h, aria_map_t map, const int* d
  * pose (what aria_alert_measure_batch_device and aria_tsdf_integrate_batch_device read), world-frame normals, the fused gray
  * and a head-light shade, batched over views. The reference has no code for it (its roadmap item H21 is a 3-D viewer), so the
  * NumPy restatement aria_slam_amd/ray_ref.py is the definition and the device equals it bit for bit. The stage owns no
- * volume: it is handed the records in HBM with their geometry. Out of scope: meshes, adaptive step lengths, colour, shadows
+ * volume: it is handed the records in HBM with their geometry. Out of scope: meshes (the stage "mesh of the volume"), adaptive step lengths, colour, shadows
  * or any second light, frame-to-model ICP (this stage makes it possible; it is the follow-up), and a volume that changes
  * between aria_ray_update_from_volume_device and a cast. Additive to ABI 4.
  *
@@ -2184,6 +2184,103 @@ int   aria_icp_debug_system_device(aria_icp_t h, const float* d_depth, int64_t d
 /* The bytes a call must move: per iteration and level pixel 4 of live depth and 4 + 12 of the model, and 320 per frame (two
  * poses read, one written, the record); ARIA_E_INVALID for a configuration or sizes the call refuses. Host only, no handle. */
 int64_t aria_icp_algorithmic_bytes(const aria_icp_config* cfg, int width, int height, int n_frames);
+
+/* ---- mesh of the volume: the aria_tsdf_voxel records of the dense depth fusion contoured into a triangle mesh, the one
+ * output of the dense chain a consumer can use as a surface (a map viewer, a mesh tool, a later collision or visibility
+ * query). The reference has no code for it (its roadmap item H21 is a 3-D map viewer), so the NumPy restatement
+ * aria_slam_amd/mesh_ref.py is the definition and the device equals it byte for byte. The stage owns no volume: it is handed
+ * the records in HBM with their geometry. Every cell is cut into the six tetrahedra of the Kuhn (Freudenthal) split around
+ * its body diagonal and each tetrahedron is contoured on its own: the split is translation invariant, so neighbouring cells
+ * agree on every shared face, and the 16-case table is derived from one orientation rule. Out of scope: the 256-case
+ * marching-cubes table, vertex normals, welding or decimation, colour beyond gray, meshing a sub-box, re-meshing only the
+ * bricks that changed, and a volume that changes between aria_mesh_update_from_volume_device and an extract. Additive to
+ * ABI 4.
+ *
+ * All arithmetic is fp32, one rounding per operation, no contraction, in exactly the order written. A NaN fails every
+ * comparison. The records' tsdf values must be finite, as in the ray casting stage.
+ * 1. Geometry. nx, ny, nz, voxel, origin[3], min_weight as in rule 1 of the dense depth fusion, with the same validity
+ *   ranges. Records lie at the linear index (k*ny + j)*nx + i. The centre of voxel (i, j, k) is
+ *   c = origin + ((float)i + 0.5f) * voxel per axis. A voxel is seen when weight >= min_weight. It is inside when tsdf < 0;
+ *   zero and -0.0f are outside, as in rule 4 of the fusion.
+ * 2. Edges and vertices. Voxel a owns seven edges (a, d), d = 1..7: the bits of d name the axes stepped by +1 (1 = x, 2 = y,
+ *   4 = z), so 3, 5 and 6 are face diagonals and 7 is the body diagonal of the cell at a. The far end b must lie inside the
+ *   volume. The edge carries a vertex when a and b are both seen and exactly one of them is inside; the rule is edge local
+ *   and does not ask whether a live cell uses the vertex. alpha = tsdf_a / (tsdf_a - tsdf_b); X = c_a with alpha * voxel
+ *   added on every axis of d, the same product on each; gray = alpha < 0.5f ? gray_a : gray_b;
+ *   weight = min(weight_a, weight_b); dir = d. Vertices are numbered in ascending (linear index of a, d). For d in {1, 2, 4}
+ *   this is rule 4 of the fusion word for word: those vertices, in order, are the records of aria_tsdf_extract_points with
+ *   axis = log2(d).
+ * 3. Cells and tetrahedra. Cell (i, j, k) exists for i < nx-1, j < ny-1, k < nz-1; its corners are q = bx + 2 by + 4 bz, the
+ *   voxels (i+bx, j+by, k+bz). It is live when all eight corners are seen. Tetrahedron p = 0..5 belongs to the axis
+ *   permutations pi in the order xyz, xzy, yxz, yzx, zxy, zyx; its corners are (0, 2^pi0, 2^pi0 + 2^pi1, 7). Every edge of
+ *   a tetrahedron joins a corner to a corner whose bit set contains it, so it is the edge (lower corner's voxel, difference
+ *   of the bit sets) of rule 2, owned by one of the cell's corners 0..6.
+ * 4. Table. By the tetrahedron's 4-bit inside mask (bit t = its corner t inside): 0 or 4 inside, nothing. 1 inside (corner a)
+ *   the triangle through the edges from a to the outside corners in ascending order; 3 inside (corner c outside), through
+ *   the edges from the inside corners, ascending, to c. 2 inside (a < b inside, c < d outside): the quad (a,c), (a,d), (b,d),
+ *   (b,c), split as (0,1,2), (0,2,3). Orientation: with every vertex at its edge midpoint, (v1 - v0) x (v2 - v0) has a
+ *   positive dot product with (mean of the outside corners - mean of the inside corners); otherwise the last two vertices
+ *   of each triangle are swapped. This depends only on p and the mask: a table of 6 x 16 entries, with
+ *   0,1,1,2,1,2,2,1,1,2,2,1,2,1,1,0 triangles by mask.
+ * 5. Triangles. The live cells in ascending linear index of corner 0, then tetrahedra 0..5, then table order. A triangle is
+ *   three uint32 vertex numbers of rule 2. At most 12 per cell.
+ * 6. Capacities. The first min(total, cap) vertices and the first min(total, cap) triangles are written; triangles carry the
+ *   full numbering whatever the vertex capacity. The two int64 count words receive the totals (vertices, triangles). A total
+ *   above its capacity defers ARIA_E_OUTPUT_TOO_SMALL. A vertex total above 2^32 - 1 defers ARIA_E_OVERFLOW, and the
+ *   triangles are then not valid. Records beyond the written ones are never touched.
+ * 7. Properties that follow. No directed edge (v0 -> v1, v1 -> v2, v2 -> v0 of a triangle) occurs twice. Inside any block of
+ *   live cells every directed edge is met by its reverse exactly once: the mesh is a closed oriented manifold wherever the
+ *   data is complete, and its boundary runs along faces between a live cell and a cell that is not. An exact zero gives
+ *   alpha = 0, hence coincident vertices and zero-area triangles; they are kept, so the topology stays intact.
+ * Determinism. No float atomics, one writer per record: the result is bitwise independent of run, handle and stream. */
+typedef struct aria_mesh_s* aria_mesh_t;
+typedef struct {
+    float    X[3];              /* world coordinates in metres                                                     */
+    uint8_t  gray;
+    uint8_t  dir;               /* d of rule 2: 1, 2, 4 axis edges, 3, 5, 6 face diagonals, 7 the body diagonal     */
+    uint16_t weight;            /* min of the two voxels' weights                                                  */
+} aria_mesh_vertex;             /* 16 bytes                                                                        */
+typedef struct {
+    uint32_t v[3];              /* vertex numbers of rule 2                                                        */
+} aria_mesh_triangle;           /* 12 bytes                                                                        */
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_mesh_config)                                                     */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking)  */
+    int      nx, ny, nz;        /* the volume's geometry; default 256 x 256 x 128                                  */
+    int      min_weight;        /* default 2, 1..65535                                                             */
+    float    voxel;             /* default 0.05 m                                                                  */
+    float    origin[3];         /* default (-6.4, -6.4, 0)                                                         */
+} aria_mesh_config;             /* 48 bytes                                                                        */
+
+void  aria_mesh_default_config(aria_mesh_config* cfg);
+/* ARIA_E_INVALID for a bad field, before any device is touched. The handle keeps aria_mesh_scratch_bytes on the device. */
+int   aria_mesh_create(const aria_mesh_config* cfg, aria_mesh_t* out);
+void  aria_mesh_destroy(aria_mesh_t h);
+void* aria_mesh_stream(aria_mesh_t h);
+/* Synchronises the handle's stream and returns, once, what the extracts since the last check deferred: ARIA_E_OVERFLOW
+ * before ARIA_E_OUTPUT_TOO_SMALL. */
+int   aria_mesh_check(aria_mesh_t h);
+/* Remembers d_voxels (nx*ny*nz records in the layout of rule 1, aria_tsdf_device_voxels of a volume of this geometry) and
+ * runs rules 2 and 3 over them: a word per voxel (its edges that carry a vertex, its cell's corner signs and triangle count)
+ * and two counts per 256 voxels. The records must stay where they are, and unchanged, until the extracts that follow have
+ * run; after the volume changed, update again. Enqueued on the handle's stream, no synchronisation. */
+int   aria_mesh_update_from_volume_device(aria_mesh_t h, const aria_tsdf_voxel* d_voxels);
+/* Rules 2-6 into device memory: vertices at d_vertices (vcap records), triangles at d_triangles (tcap records), the totals at
+ * d_counts[0] (vertices) and d_counts[1] (triangles). A pointer may be NULL with its capacity 0; d_counts may not. An
+ * extract before the first update is ARIA_E_INVALID, refused before anything is enqueued. Enqueued on the handle's stream,
+ * no synchronisation. */
+int   aria_mesh_extract_device(aria_mesh_t h, aria_mesh_vertex* d_vertices, int64_t vcap, aria_mesh_triangle* d_triangles,
+                               int64_t tcap, int64_t* d_counts);
+/* The same into host arrays; blocks, and returns what aria_mesh_check would. counts: two int64. */
+int   aria_mesh_extract(aria_mesh_t h, aria_mesh_vertex* vertices, int64_t vcap, aria_mesh_triangle* triangles, int64_t tcap,
+                        int64_t* counts);
+/* What a handle of this geometry keeps on the device: 4 bytes per voxel and 24 per 256 voxels; ARIA_E_INVALID for dims the
+ * create refuses. Host only, no handle. */
+int64_t aria_mesh_scratch_bytes(int nx, int ny, int nz);
+/* The bytes one update + extract must move: every record read once (8), its word written once and read once (8), 16 per
+ * vertex and 12 per triangle written. Host only, no handle. */
+int64_t aria_mesh_algorithmic_bytes(int nx, int ny, int nz, int64_t n_vertices, int64_t n_triangles);
 
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
