@@ -313,7 +313,10 @@ class RectConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("src_width", C.c_int),
                 ("src_height", C.c_int), ("dst_width", C.c_int), ("dst_height", C.c_int), ("n_cameras", C.c_int),
                 ("cam", RectCamera * 2), ("new_fx", C.c_double), ("new_fy", C.c_double), ("new_cx", C.c_double),
-                ("new_cy", C.c_double), ("fill", C.c_int), ("reserved", C.c_int)]
+                ("new_cy", C.c_double), ("fill", C.c_int), ("model", C.c_int)]
+
+
+RECT_MODEL_RADTAN, RECT_MODEL_KB4 = 0, 1
 
 
 class DenseConfig(C.Structure):

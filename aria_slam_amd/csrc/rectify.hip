@@ -15,6 +15,9 @@
 //                   dword store per lane; tail columns and unaligned destination rows take a byte path. Padding is never
 //                   written.
 // k_rect_points     a lane per keypoint: 20 fixed-point iterations of the inverse distortion in fp64, rotation, projection.
+// k_rect_build_map_kb4, k_rect_points_kb4   the same two jobs for the fisheye model KB4 (aria_rect_config::model): atan and
+//                   tan from + - * / and sqrt (rect_atan, rect_tan), ten Newton steps per keypoint. k_rect_remap reads a map
+//                   of either model.
 // No atomics but the deferred-error OR. Plain HIP C++: the anonymous namespace below, up to the C-ABI, also compiles for the
 // host (tests/test_rectify_kernel_emulation.py).
 // The variants build (-DARIA_VARIANTS) adds k_rect_remap_lds, the measured and rejected read form (the tile's source bounding
@@ -312,6 +315,102 @@ __global__ __launch_bounds__(RECT_BLOCK) void k_rect_points(RectCam c, const Rec
     kp_out[(int64_t)f * kp_stride + i] = k;
 }
 
+// ---- the fisheye model KB4 (the header's steps 2k and 4k). A RectCam of a KB4 handle holds k1, k2, k3, k4 in the fields
+// k1, k2, p1, p2 (dist[0..3] in both models) and 0 in k3. atan and tan are built from + - * / and sqrt with fixed loop counts,
+// so every lane does the same work and the host computes the same bits.
+constexpr int RECT_KB4_POINT_ITERS = 10;
+constexpr double RECT_KB4_RESIDUAL = 1e-9;
+constexpr double RECT_HALF_PI = 1.5707963267948966;
+
+// atan(r), r >= 0: three half-angle steps, the Taylor series to t^25 in Horner form, times 8
+__device__ __forceinline__ double rect_atan(double r) {
+    double t = r;
+    for (int i = 0; i < 3; i++) t = t / (1.0 + sqrt(1.0 + t * t));
+    const double s = t * t;
+    double p = 1.0 / 25.0;
+    for (int k = 11; k >= 0; k--) p = 1.0 / (double)(2 * k + 1) - s * p;
+    return 8.0 * (t * p);
+}
+
+// tan(a), 0 <= a < pi / 2: sin / cos of a / 8 by their Taylor series, three double-angle steps
+__device__ __forceinline__ double rect_tan(double a) {
+    const double h = a * 0.125, s = h * h;
+    double ps = 1.0, pc = 1.0;
+    for (int k = 8; k >= 1; k--) {
+        ps = 1.0 - s / (double)((2 * k) * (2 * k + 1)) * ps;
+        pc = 1.0 - s / (double)((2 * k - 1) * (2 * k)) * pc;
+    }
+    double t = (h * ps) / pc;
+    for (int i = 0; i < 3; i++) t = (2.0 * t) / (1.0 - t * t);
+    return t;
+}
+
+__device__ __forceinline__ double rect_kb4_P(const RectCam& c, double a) {
+    const double q = a * a;
+    return (((c.p2 * q + c.p1) * q + c.k2) * q + c.k1) * q + 1.0;
+}
+
+// d/da (a P(a)); <= 0 beyond the angle at which the polynomial folds back
+__device__ __forceinline__ double rect_kb4_D(const RectCam& c, double a) {
+    const double q = a * a;
+    return (((9.0 * c.p2 * q + 7.0 * c.p1) * q + 5.0 * c.k2) * q + 3.0 * c.k1) * q + 1.0;
+}
+
+__global__ __launch_bounds__(RECT_BLOCK) void k_rect_build_map_kb4(RectCam c, int src_w, int src_h, int dst_w, int dst_h,
+                                                                   int map_pitch, uint32_t* __restrict__ map) {
+    const int64_t i = (int64_t)blockIdx.x * RECT_BLOCK + threadIdx.x;
+    if (i >= (int64_t)map_pitch * dst_h) return;
+    const int v = (int)(i / map_pitch), u = (int)(i % map_pitch);
+    uint32_t word = RECT_INVALID;
+    if (u < dst_w) {
+        const double x = ((double)u - c.ncx) / c.nfx, y = ((double)v - c.ncy) / c.nfy;
+        const double X = c.R[0] * x + c.R[3] * y + c.R[6];
+        const double Y = c.R[1] * x + c.R[4] * y + c.R[7];
+        const double Z = c.R[2] * x + c.R[5] * y + c.R[8];
+        const double xn = X / Z, yn = Y / Z;
+        const double r = sqrt(xn * xn + yn * yn);
+        const double a = rect_atan(r);
+        const double sc = r == 0.0 ? 1.0 : (a * rect_kb4_P(c, a)) / r;
+        const double xd = xn * sc, yd = yn * sc;
+        const double su = c.fx * xd + c.cx, sv = c.fy * yd + c.cy;
+        const double qx = floor(su * 32.0 + 0.5), qy = floor(sv * 32.0 + 0.5);
+        const bool ok = rect_kb4_D(c, a) > 0.0 && Z > 0.0 && rect_finite(su) && rect_finite(sv) && qx >= 0.0 && qy >= 0.0 &&
+                        qx < (double)(src_w - 1) * 32.0 && qy < (double)(src_h - 1) * 32.0;
+        if (ok) word = (uint32_t)(int)qx | ((uint32_t)(int)qy << 16);
+    }
+    map[i] = word;
+}
+
+// grid, deferred error and the in-place rule as k_rect_points
+__global__ __launch_bounds__(RECT_BLOCK) void k_rect_points_kb4(RectCam c, const RectKp* kp_in, const int* __restrict__ counts,
+                                                                int64_t kp_stride, RectKp* kp_out, int* __restrict__ err) {
+    const int f = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * RECT_BLOCK + threadIdx.x;
+    const int n = counts[f];
+    if (n < 0 || n > kp_stride) {                        // uniform over the frame: it is skipped
+        if (i == 0) atomicOr(err, ERRBIT_RECT_INPUT);
+        return;
+    }
+    if (i >= n) return;
+    RectKp k = kp_in[(int64_t)f * kp_stride + i];
+    const double xd = ((double)k.x - c.cx) / c.fx, yd = ((double)k.y - c.cy) / c.fy;
+    const double td = sqrt(xd * xd + yd * yd);
+    double a = td;
+    for (int it = 0; it < RECT_KB4_POINT_ITERS; it++) a = a - (a * rect_kb4_P(c, a) - td) / rect_kb4_D(c, a);
+    const bool conv = rect_finite(a) && a >= 0.0 && a < RECT_HALF_PI && rect_kb4_D(c, a) > 0.0 &&
+                      fabs(a * rect_kb4_P(c, a) - td) <= RECT_KB4_RESIDUAL;
+    const double sc = td == 0.0 ? 1.0 : rect_tan(a) / td;
+    const double x = xd * sc, y = yd * sc;
+    const double X = c.R[0] * x + c.R[1] * y + c.R[2];
+    const double Y = c.R[3] * x + c.R[4] * y + c.R[5];
+    const double Z = c.R[6] * x + c.R[7] * y + c.R[8];
+    const float u = (float)(c.nfx * X / Z + c.ncx), v = (float)(c.nfy * Y / Z + c.ncy);
+    const bool ok = conv && Z > 0.0 && fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX;
+    k.x = ok ? u : -1.0f;
+    k.y = ok ? v : -1.0f;
+    kp_out[(int64_t)f * kp_stride + i] = k;
+}
+
 }  // namespace
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
@@ -348,8 +447,9 @@ bool bad_config(const aria_rect_config* c) {
         c->fill < 0 || c->fill > 255)
         return true;
     if (!(c->new_fx > 0) || !(c->new_fy > 0) || !fin(c->new_fx) || !fin(c->new_fy) || !fin(c->new_cx) || !fin(c->new_cy)) return true;
+    if (c->model != ARIA_RECT_MODEL_RADTAN && c->model != ARIA_RECT_MODEL_KB4) return true;
     for (int k = 0; k < c->n_cameras; k++)
-        if (bad_camera(c->cam[k])) return true;
+        if (bad_camera(c->cam[k]) || (c->model == ARIA_RECT_MODEL_KB4 && c->cam[k].dist[4] != 0.0)) return true;
     return false;
 }
 
@@ -464,8 +564,9 @@ int aria_rect_create(const aria_rect_config* c, aria_rect_t* out) {
         hipError_t e = hipMalloc((void**)&h->d_map, words * c->n_cameras * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&h->d_count, sizeof(int));
         if (e == hipSuccess) {
+            const auto build = c->model == ARIA_RECT_MODEL_KB4 ? k_rect_build_map_kb4 : k_rect_build_map;
             for (int k = 0; k < c->n_cameras; k++)
-                hipLaunchKernelGGL(k_rect_build_map, dim3((unsigned)((words + RECT_BLOCK - 1) / RECT_BLOCK)), dim3(RECT_BLOCK), 0,
+                hipLaunchKernelGGL(build, dim3((unsigned)((words + RECT_BLOCK - 1) / RECT_BLOCK)), dim3(RECT_BLOCK), 0,
                                    h->stream, h->cam[k], c->src_width, c->src_height, c->dst_width, c->dst_height, h->map_pitch,
                                    h->d_map + k * words);
             e = hipGetLastError();
@@ -550,7 +651,7 @@ int aria_rect_points_batch_device(aria_rect_t h, int cam, const aria_keypoint* d
         return ARIA_E_INVALID;
     if (n_frames == 0) return ARIA_OK;
     ARIA_HIP(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_rect_points, dim3((unsigned)((kp_stride + RECT_BLOCK - 1) / RECT_BLOCK), n_frames), dim3(RECT_BLOCK), 0,
+    hipLaunchKernelGGL(h->cfg.model == ARIA_RECT_MODEL_KB4 ? k_rect_points_kb4 : k_rect_points, dim3((unsigned)((kp_stride + RECT_BLOCK - 1) / RECT_BLOCK), n_frames), dim3(RECT_BLOCK), 0,
                        h->stream, h->cam[cam], reinterpret_cast<const RectKp*>(d_kp_in), d_n, kp_stride,
                        reinterpret_cast<RectKp*>(d_kp_out), h->d_err);
     ARIA_HIP(hipGetLastError());

@@ -54,10 +54,18 @@ struct AslGroundTruth {              // the 17 doubles of aria_eval_truth, in it
 
 struct AslCalibration {             // one camera's sensor.yaml
     double intrinsics[4] = {0, 0, 0, 0};     // fx, fy, cx, cy
-    double distortion[5] = {0, 0, 0, 0, 0};  // radtan k1, k2, p1, p2, k3 (k3 = 0 when the file has four)
+    double distortion[5] = {0, 0, 0, 0, 0};  // radtan k1, k2, p1, p2, k3 (k3 = 0 when the file has four); KB4 k1, k2, k3, k4, 0
     double T_BS[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // sensor to body, row-major
     int width = 0, height = 0;               // resolution, 0 when the file has none
     std::string distortion_model;            // "radial-tangential" in EuRoC; empty when the file has none
+    // The model as aria_rect_config::model takes it: 0 (ARIA_RECT_MODEL_RADTAN) for "radial-tangential", "radtan", "plumb_bob"
+    // and a file without the key, 1 (ARIA_RECT_MODEL_KB4) for "equidistant", "fisheye" and "kb4", -1 for any other name.
+    int rectModel() const {
+        const std::string& m = distortion_model;
+        if (m.empty() || m == "radial-tangential" || m == "radtan" || m == "plumb_bob") return 0;
+        if (m == "equidistant" || m == "fisheye" || m == "kb4") return 1;
+        return -1;
+    }
 };
 
 class AslSequence {

@@ -1,8 +1,11 @@
 // aria::adapters::hip::HipRectifier -- undistortion and stereo rectification over the C-ABI (include/aria_orb_hip.h,
-// "rectification"): the maps of one radtan camera (plain undistortion) or of the two cameras of a rig (the rectifying rotations
+// "rectification"): the maps of one camera (plain undistortion) or of the two cameras of a rig (the rectifying rotations
 // from their T_BS) built on the device, images warped into the frame the extractor and the stereo stage read, keypoints moved
 // into it. The reference parses the distortion coefficients and never uses them; the definition is the NumPy restatement
-// aria_slam_amd/rectify_ref.py, which the device equals bit for bit. Fisheye (KB4) models are out of scope.
+// aria_slam_amd/rectify_ref.py, which the device equals bit for bit. RectifierConfig::model picks radtan or the fisheye model
+// KB4 (OpenCV's "fisheye", Kalibr's "equidistant") for all cameras of the handle. Out of scope: Aria's FISHEYE624, KB3, rays at
+// or beyond 90 degrees from the axis, cylindrical and equirectangular destinations; parity with OpenCV's fisheye:: functions
+// is not pinned.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -15,11 +18,12 @@ namespace aria::adapters::hip {
 
 struct RectCalibration {                 // one camera as its sensor.yaml states it (EuRoC cam0 by default)
     PoseIntrinsics K{};
-    double dist[5] = {-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.0};   // radtan k1, k2, p1, p2, k3
+    double dist[5] = {-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.0};   // radtan k1, k2, p1, p2, k3; KB4 k1..k4, 0
     double T_BS[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};             // sensor to body, row-major
 };
 
 struct RectifierConfig {
+    int model = ARIA_RECT_MODEL_RADTAN;  // ARIA_RECT_MODEL_*, of every camera (AslCalibration::rectModel() of a sensor.yaml)
     int n_cameras = 1;                   // 1: plain undistortion of cam[0]; 2: stereo rectification of cam[0] (left), cam[1]
     RectCalibration cam[2];
     int src_width = 752, src_height = 480;

@@ -25,6 +25,7 @@ HipRectifier::HipRectifier(const RectifierConfig& cfg) {
     cfg_.dst_height = cfg.dst_height > 0 ? cfg.dst_height : cfg.src_height;
     cfg_.n_cameras = cfg.n_cameras;
     cfg_.fill = cfg.fill;
+    cfg_.model = cfg.model;
     if (cfg.n_cameras < 1 || cfg.n_cameras > 2) fail("HipRectifier", ARIA_E_INVALID);
     for (int k = 0; k < cfg.n_cameras; k++) {
         aria_rect_camera& c = cfg_.cam[k];

@@ -94,7 +94,7 @@
 // scale" (0 1 for a frame without an accepted pose). Without --stereo nothing of this runs and every output is byte-identical.
 //
 // --rectify (frame-at-a-time path; the sequence needs mav0/cam0/sensor.yaml, and mav0/cam1/sensor.yaml with --stereo): the
-// radtan distortion the reference parses and never applies is removed on the device (include/aria_orb_hip.h, "rectification";
+// distortion the reference parses and never applies (radial-tangential, or equidistant = fisheye = kb4) is removed on the device (include/aria_orb_hip.h, "rectification";
 // aria_hip/HipRectifier.hpp). Without --stereo every cam0 image is undistorted before extraction (new K = cam0's K) and the
 // pose and map stages take that K. With --stereo both images of a frame are rectified with the rotations built from the two
 // T_BS, and the stereo, pose and map stages take the rectified K; a BASELINE_M of 0 then means the calibration's baseline. A
@@ -408,10 +408,16 @@ int main(int argc, char** argv) {
                 return 1;
             }
             const std::string& model = seq.calibration(c).distortion_model;
-            if (!model.empty() && model != "radial-tangential" && model != "radtan") {
-                std::fprintf(stderr, "--rectify: cam%d's distortion model '%s' is not radial-tangential\n", c, model.c_str());
+            if (seq.calibration(c).rectModel() < 0) {
+                std::fprintf(stderr, "--rectify: cam%d's distortion model '%s' is neither radial-tangential nor equidistant (fisheye, kb4)\n", c,
+                             model.c_str());
                 return 1;
             }
+        }
+        if (stereo && seq.calibration(0).rectModel() != seq.calibration(1).rectModel()) {
+            std::fprintf(stderr, "--rectify: cam0's distortion model '%s' and cam1's '%s' differ: the cameras of a rig share one model\n",
+                         seq.calibration(0).distortion_model.c_str(), seq.calibration(1).distortion_model.c_str());
+            return 1;
         }
     }
     double stereo_baseline_used = stereo_baseline;
@@ -505,6 +511,7 @@ int main(int argc, char** argv) {
             if (rectify) {
                 adapters::hip::RectifierConfig rc;
                 rc.n_cameras = stereo ? 2 : 1;
+                rc.model = seq.calibration(0).rectModel();
                 rc.device = fc.hip_device;
                 for (int c = 0; c < rc.n_cameras; c++) {
                     const io::AslCalibration& cal = seq.calibration(c);

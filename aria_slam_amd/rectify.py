@@ -1,7 +1,10 @@
 """Undistortion and stereo rectification on the device (include/aria_orb_hip.h, "rectification"): the maps of one or two
-radtan cameras built at creation, image batches warped in HBM into the layout the batch extractor and the stereo stage
-read, keypoints moved into the undistorted / rectified frame. The reference never applies its distortion coefficients;
-aria_slam_amd.rectify_ref is the definition and the device equals it bit for bit. Fisheye (KB4) models are out of scope.
+cameras built at creation, image batches warped in HBM into the layout the batch extractor and the stereo stage read,
+keypoints moved into the undistorted / rectified frame. The reference never applies its distortion coefficients;
+aria_slam_amd.rectify_ref is the definition and the device equals it bit for bit. A handle's cameras are radtan or, with
+model = "kb4", the fisheye model KB4 (OpenCV's "fisheye", Kalibr's "equidistant": k1..k4). Out of scope: Aria's FISHEYE624,
+KB3, rays at or beyond 90 degrees from the axis, cylindrical and equirectangular destinations; parity with OpenCV's
+fisheye:: functions is not pinned.
 
 As with the other stages, the handle's own stream is non-blocking: device buffers filled on torch's default stream must be
 synchronised before a *_batch_device call, or the rectifier must be created on the caller's stream."""
@@ -9,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, rectify_ref
 from ._handle import StageHandle
 from ._lib import KP_DTYPE, check
 from .frontend import _ptr
@@ -24,12 +27,14 @@ def _numbers(line):
     return [float(t) for t in body.replace(",", " ").split()]
 
 
-def load_sensor_yaml(path):
+def load_sensor_yaml(path, fisheye=False):
     """A camera's mav0/camN/sensor.yaml, read key by key and line by line as the reference's reader does (EuRoCReader
     loadCameraParams): `intrinsics: [fx, fy, cx, cy]`, `distortion_coefficients: [k1, k2, p1, p2(, k3)]`,
     `resolution: [w, h]`, and T_BS's 16-value `data: [...]` (which may run over several lines). Returns dict(K, dist
-    (5 values), T_BS (4x4), resolution (w, h) or None, model)."""
+    (5 values), T_BS (4x4), resolution (w, h) or None, model). With fisheye = True the models `equidistant`, `fisheye` and
+    `kb4` are accepted too: exactly four coefficients k1..k4 (dist = k1, k2, k3, k4, 0) and model = "kb4" in the dict."""
     out = dict(K=None, dist=None, T_BS=np.eye(4), resolution=None, model="radial-tangential")
+    n_dist = 0
     with open(path) as f:
         lines = f.read().splitlines()
     in_tbs = False
@@ -39,6 +44,7 @@ def load_sensor_yaml(path):
         if "intrinsics:" in line:
             out["K"] = tuple(_numbers(line)[:4])
         elif "distortion_coefficients:" in line:
+            n_dist = len(_numbers(line))
             d = _numbers(line)[:5]
             out["dist"] = tuple(d + [0.0] * (5 - len(d)))
         elif "distortion_model:" in line:
@@ -60,23 +66,38 @@ def load_sensor_yaml(path):
         raise ValueError("%s: no intrinsics: [fx, fy, cx, cy]" % path)
     if out["dist"] is None:
         out["dist"] = (0.0,) * 5
+    if fisheye and out["model"] in ("equidistant", "fisheye", "kb4"):
+        if n_dist != 4:
+            raise ValueError("%s: the %s model takes exactly 4 coefficients, the file has %d" % (path, out["model"], n_dist))
+        out["model"] = "kb4"
+        return out
     if out["model"] not in ("radial-tangential", "radtan", "plumb_bob"):
         raise ValueError("%s: distortion model %r is not radtan" % (path, out["model"]))
     return out
 
 
 class HipRectifier(StageHandle):
-    """Binding of aria_rect_t. cameras: one or two rectify_ref.camera dicts (K, dist, R); new_K: intrinsics of the
-    destination images (default: the first camera's K); src_size / dst_size: (width, height)."""
+    """Binding of aria_rect_t. cameras: one or two rectify_ref.camera dicts (K, dist, R, and model = "kb4" for a fisheye
+    camera); new_K: intrinsics of the destination images (default: the first camera's K); src_size / dst_size: (width,
+    height); model: "radtan" or "kb4" for camera dicts that do not say (default radtan). All cameras of a handle share one
+    model: mixed models raise ValueError."""
 
     _prefix, _config = "rect", _lib.RectConfig
 
     def __init__(self, cameras=None, new_K=None, src_size=(752, 480), dst_size=None, fill=0, baseline=None, stream=None,
-                 device=0):
+                 device=0, model=None):
+        if isinstance(cameras, dict):
+            cameras = [cameras]
+        if model is not None and model not in rectify_ref.MODEL_NAMES:
+            raise ValueError("model %r is neither 'radtan' nor 'kb4'" % (model,))
+        # the keyword, then what the camera dicts say themselves: all of it must name one model
+        models = {rectify_ref.MODEL_NAMES[model]} if model is not None else set()
+        models |= {rectify_ref.model_of(cam) for cam in (cameras or []) if "model" in cam or model is None}
+        if len(models) > 1:
+            raise ValueError("the cameras of one rectifier share one distortion model, not %s" % " and ".join(sorted(models)))
         cfg = self._default_config(device, stream)
+        cfg.model = rectify_ref.MODELS.index(models.pop() if models else "radtan")
         if cameras is not None:
-            if isinstance(cameras, dict):
-                cameras = [cameras]
             cfg.n_cameras = len(cameras)
             for k, cam in enumerate(cameras[:2]):
                 c = cfg.cam[k]
@@ -107,6 +128,8 @@ class HipRectifier(StageHandle):
               "aria_rect_stereo_geometry")
         pad = lambda d: tuple(float(v) for v in d) + (0.0,) * (5 - len(d))   # noqa: E731
         cams = [dict(K=tuple(kl), dist=pad(D_l), R=tuple(cfg.cam[0].R)), dict(K=tuple(kr), dist=pad(D_r), R=tuple(cfg.cam[1].R))]
+        if kw.get("model") is not None and rectify_ref.MODEL_NAMES.get(kw["model"]) == "kb4" and (len(D_l) != 4 or len(D_r) != 4):
+            raise ValueError("kb4 takes exactly k1, k2, k3, k4")
         return cls(cams, (cfg.new_fx, cfg.new_fy, cfg.new_cx, cfg.new_cy), src_size, dst_size, baseline=b.value, **kw)
 
     @property
@@ -129,7 +152,15 @@ class HipRectifier(StageHandle):
 
     def camera(self, cam):
         c = self.config.cam[cam]
-        return dict(K=(c.fx, c.fy, c.cx, c.cy), dist=tuple(c.dist), R=tuple(c.R))
+        out = dict(K=(c.fx, c.fy, c.cx, c.cy), dist=tuple(c.dist), R=tuple(c.R))
+        if self.model == "kb4":
+            out["model"] = "kb4"
+        return out
+
+    @property
+    def model(self):
+        """"radtan" or "kb4"."""
+        return rectify_ref.MODELS[self.config.model]
 
     def map(self, cam=0):
         """The camera's map as a (dst_height, dst_width) uint32 array: qx | qy << 16 in 1/32 px, 0xFFFFFFFF = invalid."""

@@ -3,8 +3,12 @@ The reference parses the radtan coefficients of cam0/sensor.yaml and never uses 
 this file IS the definition: the device is held to it bit for bit. Every fp64 step below uses only + - * / and sqrt in the
 header's order with every sum taken left to right (no contraction); the pixel step is integer.
 
-Parity with OpenCV's stereoRectify / initUndistortRectifyMap / remap is not pinned and not claimed. The model is radtan
-(k1, k2, p1, p2, k3); the fisheye (KB4) model needs atan and is out of scope.
+Parity with OpenCV's stereoRectify / initUndistortRectifyMap / remap (and its fisheye:: functions) is not pinned and not
+claimed. Two models: radtan (k1, k2, p1, p2, k3) and the fisheye model KB4 (Kannala-Brandt k1..k4: OpenCV's "fisheye",
+Kalibr's "equidistant"), the header's steps 2k and 4k. KB4 needs atan and tan; rect_atan and rect_tan below build them from
++ - * / and sqrt alone, so the bitwise rule holds for KB4 as it does for radtan. Out of scope: Aria's FISHEYE624 (its 12
+coefficients do not fit the camera record), KB3, rays at or beyond 90 degrees from the axis (a pinhole destination cannot
+hold them), cylindrical and equirectangular destinations.
 
 Also raw_stereo_pair, the synthetic raw (distorted, rotated) pair of the tests and tools."""
 import math
@@ -30,16 +34,39 @@ EUROC_MH = dict(
 INVALID = 0xFFFFFFFF
 MAX_DIM = 2047
 POINT_ITERATIONS = 20
+FISHEYE_POINT_ITERATIONS = 10                                   # Newton steps of step 4k (OpenCV's count)
+FISHEYE_RESIDUAL = 1e-9                                         # |a P(a) - td| of a Newton run that converged
+HALF_PI = 1.5707963267948966
 IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+MODELS = ("radtan", "kb4")                                      # ARIA_RECT_MODEL_RADTAN = 0, ARIA_RECT_MODEL_KB4 = 1
+MODEL_NAMES = {"radtan": "radtan", "radial-tangential": "radtan", "plumb_bob": "radtan",
+               "kb4": "kb4", "equidistant": "kb4", "fisheye": "kb4"}
 
 
-def camera(K, dist=(), R=IDENTITY):
-    """A camera as the stage takes it: dict(K = (fx, fy, cx, cy), dist = (k1, k2, p1, p2, k3), R = 9 row-major)."""
+def camera(K, dist=(), R=IDENTITY, model="radtan"):
+    """A camera as the stage takes it: dict(K = (fx, fy, cx, cy), dist = (k1, k2, p1, p2, k3), R = 9 row-major). With
+    model = "kb4" dist is exactly (k1, k2, k3, k4), stored as (k1, k2, k3, k4, 0.0), and the dict says model = "kb4"; a
+    radtan dict carries no model key."""
     d = [float(v) for v in np.asarray(dist, np.float64).reshape(-1)]
-    if len(d) > 5:
+    out = dict(K=tuple(float(v) for v in K), dist=tuple(d + [0.0] * (5 - len(d))),
+               R=tuple(float(v) for v in np.asarray(R, np.float64).reshape(9)))
+    if model == "kb4":
+        if len(d) != 4:
+            raise ValueError("kb4 takes exactly k1, k2, k3, k4")
+        out["model"] = "kb4"
+    elif model != "radtan":
+        raise ValueError("model %r is neither 'radtan' nor 'kb4'" % (model,))
+    elif len(d) > 5:
         raise ValueError("radtan takes k1, k2, p1, p2 and an optional k3")
-    return dict(K=tuple(float(v) for v in K), dist=tuple(d + [0.0] * (5 - len(d))),
-                R=tuple(float(v) for v in np.asarray(R, np.float64).reshape(9)))
+    return out
+
+
+def model_of(cam):
+    """"radtan" or "kb4": the model key of a camera dict (absent = radtan)."""
+    m = cam.get("model", "radtan")
+    if m not in MODELS:
+        raise ValueError("model %r is neither 'radtan' nor 'kb4'" % (m,))
+    return m
 
 
 def _cross(a, b):
@@ -92,8 +119,67 @@ def _distort_terms(x, y, d):
     return rad, dx, dy
 
 
-def source_coords(cam, new_K, dst_w, dst_h):
-    """Step 2 up to (su, sv, Z) for every destination pixel, fp64 arrays of shape (dst_h, dst_w)."""
+_ATAN_C = tuple(np.float64(1.0) / np.float64(2 * k + 1) for k in range(13))             # 1 / (2k + 1), k = 0 .. 12
+_TAN_S = tuple(np.float64((2 * k) * (2 * k + 1)) for k in range(9))                     # (2k)(2k + 1), k = 1 .. 8 used
+_TAN_C = tuple(np.float64((2 * k - 1) * (2 * k)) for k in range(9))                     # (2k - 1)(2k)
+
+
+def rect_atan(r):
+    """atan(r) for r >= 0 from + - * / and sqrt: three half-angle steps t <- t / (1 + sqrt(1 + t t)) bring the argument
+    under tan(pi / 16), then the Taylor series to t^25 in Horner form, times 8. Non-finite in, non-finite out; a finite r
+    above 1.3e154, where t t overflows, gives 0 (on the device too): no ray of a finite calibration gets there."""
+    t = np.asarray(r, np.float64)
+    with np.errstate(all="ignore"):
+        for _ in range(3):
+            t = t / (1.0 + np.sqrt(1.0 + t * t))
+        s = t * t
+        p = _ATAN_C[12]
+        for k in range(11, -1, -1):
+            p = _ATAN_C[k] - s * p
+        return 8.0 * (t * p)
+
+
+def rect_tan(a):
+    """tan(a) for 0 <= a < pi / 2 from + - * /: sin and cos of a / 8 by their Taylor series to h^17 and h^16 in Horner
+    form, their quotient, three double-angle steps t <- 2 t / (1 - t t)."""
+    a = np.asarray(a, np.float64)
+    with np.errstate(all="ignore"):
+        h = a * 0.125
+        s = h * h
+        ps = pc = np.float64(1.0)
+        for k in range(8, 0, -1):
+            ps = 1.0 - s / _TAN_S[k] * ps
+            pc = 1.0 - s / _TAN_C[k] * pc
+        t = (h * ps) / pc
+        for _ in range(3):
+            t = (2.0 * t) / (1.0 - t * t)
+        return t
+
+
+def kb4_P(a, d):
+    """P(a) = 1 + k1 a^2 + k2 a^4 + k3 a^6 + k4 a^8: the distorted angle is a P(a)."""
+    k1, k2, k3, k4 = d[:4]
+    q = a * a
+    return (((k4 * q + k3) * q + k2) * q + k1) * q + 1.0
+
+
+def kb4_D(a, d):
+    """D(a) = d/da (a P(a)). D <= 0: the polynomial has folded back, the angle is beyond the lens's field."""
+    k1, k2, k3, k4 = d[:4]
+    q = a * a
+    return (((9.0 * k4 * q + 7.0 * k3) * q + 5.0 * k2) * q + 3.0 * k1) * q + 1.0
+
+
+def _kb4_scale(xn, yn, d):
+    """Step 2k at normalised (xn, yn): (sc, D(a)) with xd = xn sc, yd = yn sc."""
+    r = np.sqrt(xn * xn + yn * yn)
+    a = rect_atan(r)
+    sc = np.where(r == 0.0, 1.0, (a * kb4_P(a, d)) / r)
+    return sc, kb4_D(a, d)
+
+
+def _source_coords(cam, new_K, dst_w, dst_h):
+    """Step 2 (2k) up to (su, sv, Z, model's own validity) for every destination pixel."""
     fx, fy, cx, cy = (np.float64(v) for v in cam["K"])
     nfx, nfy, ncx, ncy = (np.float64(v) for v in new_K)
     d = [np.float64(v) for v in cam["dist"]]
@@ -106,18 +192,34 @@ def source_coords(cam, new_K, dst_w, dst_h):
         Y = R[1] * x + R[4] * y + R[7]
         Z = R[2] * x + R[5] * y + R[8]
         xn, yn = X / Z, Y / Z
-        rad, dx, dy = _distort_terms(xn, yn, d)
-        xd, yd = xn * rad + dx, yn * rad + dy
+        if model_of(cam) == "kb4":
+            sc, D = _kb4_scale(xn, yn, d)
+            xd, yd = xn * sc, yn * sc
+            ok = D > 0.0
+        else:
+            rad, dx, dy = _distort_terms(xn, yn, d)
+            xd, yd = xn * rad + dx, yn * rad + dy
+            ok = np.ones(Z.shape, bool)
         su, sv = fx * xd + cx, fy * yd + cy
-    return su, sv, Z
+    return su, sv, Z, ok
+
+
+def source_coords(cam, new_K, dst_w, dst_h):
+    """Step 2 (2k for a kb4 camera) up to (su, sv, Z) for every destination pixel, fp64 arrays of shape (dst_h, dst_w)."""
+    return _source_coords(cam, new_K, dst_w, dst_h)[:3]
+
+
+def fold_invalid(cam, new_K, dst_w, dst_h):
+    """The destination pixels of a kb4 camera that step 2k's fold rule (D(a) <= 0) makes invalid, (dst_h, dst_w) bool."""
+    return ~_source_coords(cam, new_K, dst_w, dst_h)[3]
 
 
 def build_map(cam, new_K, src_w, src_h, dst_w, dst_h):
-    """Step 2: the uint32 map (dst_h, dst_w): qx | qy << 16 in 1/32 px, or 0xFFFFFFFF."""
-    su, sv, Z = source_coords(cam, new_K, dst_w, dst_h)
+    """Step 2 (2k): the uint32 map (dst_h, dst_w): qx | qy << 16 in 1/32 px, or 0xFFFFFFFF."""
+    su, sv, Z, ok_model = _source_coords(cam, new_K, dst_w, dst_h)
     with np.errstate(all="ignore"):
         qx, qy = np.floor(su * 32.0 + 0.5), np.floor(sv * 32.0 + 0.5)
-        ok = (Z > 0) & np.isfinite(su) & np.isfinite(sv)
+        ok = ok_model & (Z > 0) & np.isfinite(su) & np.isfinite(sv)
         # ix >= 0 and ix + 1 <= Wsrc - 1 on the exact fp64 integers, before the conversion
         ok &= (qx >= 0) & (qy >= 0) & (qx < (src_w - 1) * 32.0) & (qy < (src_h - 1) * 32.0)
     q = np.where(ok, qx, 0).astype(np.int64) | (np.where(ok, qy, 0).astype(np.int64) << 16)
@@ -144,22 +246,37 @@ def distort(pts, cam):
     p = np.asarray(pts, np.float64).reshape(-1, 2)
     fx, fy, cx, cy = cam["K"]
     x, y = (p[:, 0] - cx) / fx, (p[:, 1] - cy) / fy
+    if model_of(cam) == "kb4":
+        with np.errstate(all="ignore"):
+            sc = _kb4_scale(x, y, [np.float64(v) for v in cam["dist"]])[0]
+        return np.stack([fx * (x * sc) + cx, fy * (y * sc) + cy], axis=1)
     rad, dx, dy = _distort_terms(x, y, cam["dist"])
     return np.stack([fx * (x * rad + dx) + cx, fy * (y * rad + dy) + cy], axis=1)
 
 
 def undistort_xy(xs, ys, cam, new_K):
-    """Step 4 on fp64 raw pixel coordinates: (u', v', Z) as fp64, before the fp32 store and the validity rule."""
+    """Step 4 (4k) on fp64 raw pixel coordinates: (u', v', Z) as fp64, before the fp32 store and the validity rule. Under
+    kb4 a point that step 4k's own rule rejects (the Newton run, the angle, the fold) has u' = v' = NaN."""
     fx, fy, cx, cy = (np.float64(v) for v in cam["K"])
     nfx, nfy, ncx, ncy = (np.float64(v) for v in new_K)
     d = [np.float64(v) for v in cam["dist"]]
     R = [np.float64(v) for v in cam["R"]]
     with np.errstate(all="ignore"):
         xd, yd = (np.asarray(xs, np.float64) - cx) / fx, (np.asarray(ys, np.float64) - cy) / fy
-        x, y = xd, yd
-        for _ in range(POINT_ITERATIONS):
-            rad, dx, dy = _distort_terms(x, y, d)
-            x, y = (xd - dx) / rad, (yd - dy) / rad
+        if model_of(cam) == "kb4":
+            td = np.sqrt(xd * xd + yd * yd)
+            a = td
+            for _ in range(FISHEYE_POINT_ITERATIONS):
+                a = a - (a * kb4_P(a, d) - td) / kb4_D(a, d)
+            ok = (np.isfinite(a) & (a >= 0.0) & (a < HALF_PI) & (kb4_D(a, d) > 0.0) &
+                  (np.abs(a * kb4_P(a, d) - td) <= FISHEYE_RESIDUAL))
+            sc = np.where(td == 0.0, 1.0, rect_tan(a) / td)
+            x, y = np.where(ok, xd * sc, np.nan), np.where(ok, yd * sc, np.nan)
+        else:
+            x, y = xd, yd
+            for _ in range(POINT_ITERATIONS):
+                rad, dx, dy = _distort_terms(x, y, d)
+                x, y = (xd - dx) / rad, (yd - dy) / rad
         X = R[0] * x + R[1] * y + R[2]
         Y = R[3] * x + R[4] * y + R[5]
         Z = R[6] * x + R[7] * y + R[8]
@@ -200,9 +317,11 @@ def scaled_calibration(W, H, full):
 
 
 def rectified_cameras(calib, new_K=None):
-    """(left camera, right camera, new_K, baseline) of a calibration dict: stereo_geometry's rotations attached."""
+    """(left camera, right camera, new_K, baseline) of a calibration dict: stereo_geometry's rotations attached. The dict
+    may carry model ("radtan", the default, or "kb4"), which holds for both cameras."""
     g = stereo_geometry(calib["K_l"], calib["K_r"], calib["T_BS_l"], calib["T_BS_r"], new_K)
-    return (camera(calib["K_l"], calib["D_l"], g["R1"]), camera(calib["K_r"], calib["D_r"], g["R2"]), g["new_K"],
+    m = calib.get("model", "radtan")
+    return (camera(calib["K_l"], calib["D_l"], g["R1"], m), camera(calib["K_r"], calib["D_r"], g["R2"], m), g["new_K"],
             g["baseline"])
 
 

@@ -1144,9 +1144,13 @@ int   aria_stereo_scale_pose(aria_stereo_t h, const aria_pose_result* pose, cons
 /* ---- rectification: undistortion and stereo rectification of image batches in HBM, and of keypoints. The reference parses
  * the radtan coefficients of cam0/sensor.yaml and never uses them, and has no stereo rectification, so the NumPy restatement
  * aria_slam_amd/rectify_ref.py is the definition and the device equals it bit for bit. Parity with OpenCV's stereoRectify,
- * initUndistortRectifyMap and remap is not pinned and not claimed. Distortion model: radtan only, dist = k1, k2, p1, p2, k3
- * (k3 optional, 0). The fisheye model (KB4) needs atan, which cannot be held bitwise between device and host: out of scope.
- * Additive to ABI 4.
+ * initUndistortRectifyMap, remap and fisheye:: functions is not pinned and not claimed. Two distortion models, one per handle
+ * (aria_rect_config::model): radtan, dist = k1, k2, p1, p2, k3 (k3 optional, 0), steps 2 and 4; and the fisheye model KB4
+ * (Kannala-Brandt with four coefficients: OpenCV's "fisheye", Kalibr's "equidistant"), dist = k1, k2, k3, k4, 0, steps 2k and
+ * 4k. KB4 needs atan and tan; rect_atan and rect_tan below build them from + - * / and sqrt, so the bitwise rule holds for both
+ * models. Out of scope: Aria's FISHEYE624 (6 radial, 2 tangential and 4 thin-prism coefficients do not fit the 144-byte camera
+ * record), KB3, rays at or beyond 90 degrees from the axis (a pinhole destination cannot hold them), cylindrical and
+ * equirectangular destinations. Additive to ABI 4.
  *
  * Steps 1, 2 and 4 are fp64 without contraction, use only + - * / and sqrt, and sum left to right. Step 3 is integer.
  * 1. Stereo geometry (host only, aria_rect_stereo_geometry). Inputs: K_l, K_r = (fx, fy, cx, cy) and the row-major 4x4 T_BS
@@ -1171,11 +1175,27 @@ int   aria_stereo_scale_pose(aria_stereo_t h, const aria_pose_result* pose, cons
  *   iterations of x <- (xd - dx) / rad, y <- (yd - dy) / rad with rad, dx, dy the expressions of step 2 at the current
  *   (x, y); (X, Y, Z) = R_c (x, y, 1); u' = fx' X / Z + cx', v' = fy' Y / Z + cy', both stored as fp32; every other field of
  *   the record is copied. Z <= 0 or a stored value that is not finite: (-1, -1). No NaN or Inf is ever written.
+ * KB4. fp64 without contraction, every expression in the order written, fixed loop counts.
+ *   rect_atan(r), r >= 0: t = r; three times t = t / (1 + sqrt(1 + t t)); s = t t; p = 1/25; for k = 11 .. 0:
+ *   p = 1/(2k+1) - s p (the constants are the fp64 quotients 1.0 / (2k+1)); the result is 8 (t p). A non-finite r gives a
+ *   non-finite result. |rect_atan - atan| <= 1e-13 on [0, 1000].
+ *   rect_tan(a), 0 <= a < pi/2: h = a 0.125, s = h h; ps = pc = 1; for k = 8 .. 1: ps = 1 - (s / ((2k)(2k+1))) ps and
+ *   pc = 1 - (s / ((2k-1)(2k))) pc; t = (h ps) / pc; three times t = (2 t) / (1 - t t). Relative error <= 1e-12 on [0, 1.5].
+ *   With q = a a: P(a) = (((k4 q + k3) q + k2) q + k1) q + 1 and D(a) = (((9 k4 q + 7 k3) q + 5 k2) q + 3 k1) q + 1, the
+ *   derivative of a P(a).
+ * 2k. Map. Step 2 up to xn = X / Z, yn = Y / Z; r = sqrt(xn xn + yn yn), a = rect_atan(r); sc = 1 when r == 0, else
+ *   (a P(a)) / r; xd = xn sc, yd = yn sc; su, sv, qx, qy, the bounds and the word as in step 2. The pixel is also invalid when
+ *   D(a) <= 0: beyond that angle the polynomial folds back and pixels outside the lens's field would read from inside the image.
+ * 4k. Points. xd = (x - cx) / fx, yd = (y - cy) / fy, td = sqrt(xd xd + yd yd); from a = td exactly 10 Newton steps
+ *   a = a - (a P(a) - td) / D(a). The point is valid when a is finite, 0 <= a, a < 1.5707963267948966, D(a) > 0 and
+ *   |a P(a) - td| <= 1e-9. Then sc = 1 when td == 0, else rect_tan(a) / td; x = xd sc, y = yd sc; rotation, projection, the
+ *   fp32 store and the (-1, -1) rule as in step 4. An invalid point is (-1, -1).
  * Determinism. No float atomics; bitwise reproducible and independent of the batch split. */
 typedef struct aria_rect_s* aria_rect_t;
+enum { ARIA_RECT_MODEL_RADTAN = 0, ARIA_RECT_MODEL_KB4 = 1 };
 typedef struct {
     double fx, fy, cx, cy;      /* intrinsics of the raw camera                                                    */
-    double dist[5];             /* radtan k1, k2, p1, p2, k3                                                       */
+    double dist[5];             /* radtan k1, k2, p1, p2, k3; KB4 k1, k2, k3, k4, 0                                */
     double R[9];                /* rectifying rotation, row-major: x_rect = R x_cam; identity = plain undistortion */
 } aria_rect_camera;             /* 144 bytes                                                                       */
 typedef struct {
@@ -1188,13 +1208,13 @@ typedef struct {
     aria_rect_camera cam[2];
     double   new_fx, new_fy, new_cx, new_cy;   /* intrinsics of the destination images, shared by the cameras      */
     int      fill;              /* byte of an invalid pixel, 0..255 (default 0)                                    */
-    int      reserved;
+    int      model;             /* ARIA_RECT_MODEL_*, of every camera of the handle (default radtan)               */
 } aria_rect_config;             /* 368 bytes                                                                       */
 
 /* EuRoC cam0 at 752x480, plain undistortion (R = I), new K = K, one camera. */
 void  aria_rect_default_config(aria_rect_config* cfg);
 /* Builds the maps of the cameras on the device. ARIA_E_INVALID for sizes out of range, non-positive or non-finite focal
- * lengths, n_cameras outside 1..2, fill outside 0..255. */
+ * lengths, n_cameras outside 1..2, fill outside 0..255, a model that is neither ARIA_RECT_MODEL_*, KB4 with dist[4] != 0. */
 int   aria_rect_create(const aria_rect_config* cfg, aria_rect_t* out);
 void  aria_rect_destroy(aria_rect_t h);
 void* aria_rect_stream(aria_rect_t h);

@@ -11,14 +11,22 @@ in the same process and alternating, each checked bitwise against the shipped fo
   read form     the shipped three 8-byte row loads per lane against two unaligned 16-bit global loads per pixel
                 (ARIA_RECT_READ=taps) and against the LDS-staged bounding box (ARIA_RECT_READ=lds)
 
+--model kb4 runs all of it through the fisheye model: the EuRoC rig's two T_BS with the intrinsics and k1..k4 of a 190-degree
+lens (TUM-VI's cam0, 512x512) scaled to the shape. The remap kernel does not know the model; the two figures that do are
+printed for either model, per shape, from the product form alone:
+  map build     wall-clock time of creating the handle (both cameras' maps built on the device, synchronised), median of 7
+  points        aria_rect_points_batch_device over 4096 frames x 2000 keypoints uniform over the raw image, HIP events
+
 This comparison is against the shipped form's output on this tool's own shapes; that every form equals the restatement on the
 cases that reach each read form, frame group and limit is tools/rect_check.py (tests/test_gpu_rectify_variants.py).
 
-Usage: rect_rate.py [--images 4096] [--shapes 752x480,640x480] [--reps 10] [--groups 1] [--no-ab]"""
+Usage: rect_rate.py [--images 4096] [--shapes 752x480,640x480] [--reps 10] [--groups 1] [--no-ab] [--model radtan|kb4]
+                    [--point-frames 4096] [--keypoints 2000]"""
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -28,20 +36,78 @@ sys.path.insert(0, ROOT)
 PEAK = 8.0e12   # B/s, the MI355X's HBM3E specification
 
 
-def make_rectifier(A, W, H, stream, env=None):
+# TUM-VI cam0 (512x512, equidistant): the intrinsics of --model kb4, on the EuRoC rig's extrinsics
+KB4_K, KB4_D, KB4_SIZE = (190.978, 190.973, 254.931, 256.897), (0.0034823894, 0.0007150348, -0.0020532361, 0.00020293673), (512, 512)
+
+
+def calibration(W, H, model):
     from aria_slam_amd import rectify_ref as R
-    cal = R.scaled_calibration(W, H, R.EUROC_MH)
+    if model == "kb4":
+        return R.scaled_calibration(W, H, dict(R.EUROC_MH, K_l=KB4_K, K_r=KB4_K, D_l=KB4_D, D_r=KB4_D, size=KB4_SIZE))
+    return R.scaled_calibration(W, H, R.EUROC_MH)
+
+
+def make_rectifier(A, W, H, stream, env=None, model="radtan"):
+    cal = calibration(W, H, model)
     for k in ("ARIA_RECT_GROUP", "ARIA_RECT_READ"):
         os.environ.pop(k, None)
     os.environ.update(env or {})                                  # read by aria_rect_create in the variants build only
     r = A.HipRectifier.from_stereo_calibration(cal["K_l"], cal["D_l"], cal["T_BS_l"], cal["K_r"], cal["D_r"], cal["T_BS_r"], (W, H),
-                                               stream=stream.cuda_stream)
+                                               stream=stream.cuda_stream, model=model)
     for k in (env or {}):
         os.environ.pop(k, None)
     return r
 
 
-def measure(A, torch, W, H, B, reps, warmup, ab, groups=(1,)):
+def measure_model_stages(A, torch, W, H, model, frames, keypoints, reps, warmup):
+    """The two figures that depend on the distortion model: handle creation (the map build) and the points batch."""
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    create = []
+    for _ in range(7 + 1):                                        # the first creation loads the code object: dropped
+        t = time.perf_counter()
+        r = make_rectifier(A, W, H, stream, model=model)
+        create.append((time.perf_counter() - t) * 1e3)
+        r.close()
+    create = create[1:]
+    r = make_rectifier(A, W, H, stream, model=model)
+    with torch.cuda.stream(stream):
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(8)
+        kp = torch.zeros((frames, keypoints, 6), dtype=torch.float32, device=dev)
+        kp[:, :, 0] = torch.rand((frames, keypoints), device=dev, generator=gen) * (W - 1)
+        kp[:, :, 1] = torch.rand((frames, keypoints), device=dev, generator=gen) * (H - 1)
+        out = torch.zeros_like(kp)
+        counts = torch.full((frames,), keypoints, dtype=torch.int32, device=dev)
+    stream.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for k in range(warmup + reps):
+        t0.record(stream)
+        r.points_batch_device(kp, counts, keypoints, frames, out)
+        t1.record(stream)
+        t1.synchronize()
+        if k >= warmup:
+            times.append(t0.elapsed_time(t1))
+    r.check()
+    with torch.cuda.stream(stream):
+        moved = float(((out[:, :, 0] != -1) | (out[:, :, 1] != -1)).float().mean())
+    stream.synchronize()
+    r.close()
+    ms = float(np.median(times))
+    res = dict(model=model, width=W, height=H, create_ms_median=float(np.median(create)), create_ms_min=float(np.min(create)),
+               create_ms_max=float(np.max(create)), point_frames=frames, keypoints=keypoints, points_ms_median=ms,
+               points_ms_min=float(np.min(times)), points_ms_max=float(np.max(times)),
+               points_ns_per_keypoint=ms * 1e6 / (frames * keypoints), points_valid_share=moved)
+    print("%dx%d, %s: handle creation (two maps built) %.3f ms (median of %d, min %.3f max %.3f); points, %d frames x %d keypoints: "
+          "%.3f ms (median of %d, min %.3f max %.3f) = %.3f ns/keypoint, %.1f %% valid"
+          % (W, H, model, res["create_ms_median"], len(create), res["create_ms_min"], res["create_ms_max"], frames, keypoints, ms, reps,
+             res["points_ms_min"], res["points_ms_max"], res["points_ns_per_keypoint"], 100 * moved))
+    print(json.dumps(res))
+    return res
+
+
+def measure(A, torch, W, H, B, reps, warmup, ab, groups=(1,), model="radtan"):
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
@@ -55,7 +121,7 @@ def measure(A, torch, W, H, B, reps, warmup, ab, groups=(1,)):
     if ab:
         forms += [("G=%d" % g, {"ARIA_RECT_GROUP": str(g)}) for g in groups]
         forms += [("taps", {"ARIA_RECT_READ": "taps"}), ("lds", {"ARIA_RECT_READ": "lds"})]
-    rect = [(name, make_rectifier(A, W, H, stream, env)) for name, env in forms]
+    rect = [(name, make_rectifier(A, W, H, stream, env, model)) for name, env in forms]
     times = {name: [] for name, _ in rect}
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for name, r in rect:                                          # warm-up, and every form against the shipped one's bytes
@@ -76,7 +142,7 @@ def measure(A, torch, W, H, B, reps, warmup, ab, groups=(1,)):
             t1.synchronize()
             times[name].append(t0.elapsed_time(t1))
     invalid = float((rect[0][1].map(0) == 0xFFFFFFFF).mean())
-    res = dict(width=W, height=H, images=B, reps=reps, invalid_share=invalid, algorithmic_bytes_per_image=2 * W * H)
+    res = dict(model=model, width=W, height=H, images=B, reps=reps, invalid_share=invalid, algorithmic_bytes_per_image=2 * W * H)
     for name, r in rect:
         ms = float(np.median(times[name]))
         us = ms * 1e3 / B
@@ -99,6 +165,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--groups", default="1", help="frame-group sizes of the A/B beside the shipped one")
     ap.add_argument("--no-ab", action="store_true", help="the product library alone: no frame-group and read-form A/B")
+    ap.add_argument("--model", choices=("radtan", "kb4"), default="radtan")
+    ap.add_argument("--point-frames", type=int, default=4096)
+    ap.add_argument("--keypoints", type=int, default=2000)
+    ap.add_argument("--no-remap", action="store_true", help="map build and points only")
     a = ap.parse_args()
     if not a.no_ab and not os.environ.get("ARIA_ORB_HIP_LIBRARY"):
         variants = os.path.join(ROOT, "aria_slam_amd", "libaria_orb_hip_variants.so")
@@ -111,7 +181,9 @@ def main():
     assert torch.cuda.is_available(), "rect_rate.py measures on the GPU; there is no CPU fallback"
     for shape in a.shapes.split(","):
         W, H = (int(v) for v in shape.split("x"))
-        measure(A, torch, W, H, a.images, a.reps, a.warmup, not a.no_ab, [int(g) for g in a.groups.split(",")])
+        if not a.no_remap:
+            measure(A, torch, W, H, a.images, a.reps, a.warmup, not a.no_ab, [int(g) for g in a.groups.split(",")], a.model)
+        measure_model_stages(A, torch, W, H, a.model, a.point_frames, a.keypoints, a.reps, a.warmup)
 
 
 if __name__ == "__main__":
