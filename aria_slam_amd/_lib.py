@@ -108,6 +108,9 @@ EXPORTS = [
     "aria_mesh_default_config", "aria_mesh_create", "aria_mesh_destroy", "aria_mesh_stream", "aria_mesh_check",
     "aria_mesh_update_from_volume_device", "aria_mesh_extract_device", "aria_mesh_extract", "aria_mesh_scratch_bytes",
     "aria_mesh_algorithmic_bytes",
+    # guided matching (landmarks projected by a predicted pose, window search, local-map PnP input), additive to ABI 4
+    "aria_proj_default_config", "aria_proj_create", "aria_proj_destroy", "aria_proj_stream", "aria_proj_check",
+    "aria_proj_search_batch_device", "aria_proj_search", "aria_proj_landmarks_from_map_device",
 ]
 
 
@@ -296,6 +299,18 @@ class StereoConfig(C.Structure):
                 ("max_disparity", C.c_double), ("band_factor", C.c_double), ("median_factor", C.c_double),
                 ("th_hamming", C.c_int), ("sad_half_window", C.c_int), ("sad_slide", C.c_int), ("max_octave_diff", C.c_int),
                 ("min_scale_matches", C.c_int), ("reserved", C.c_int)]
+
+
+class ProjConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("min_depth", C.c_double), ("radius_px", C.c_double), ("ratio", C.c_float),
+                ("th_hamming", C.c_int), ("max_octave_diff", C.c_int), ("reserved", C.c_int)]
+
+
+# aria_proj_landmark (64 bytes), aria_proj_obs (24 bytes) and aria_proj_pair (8 bytes)
+PROJ_LANDMARK_DTYPE = np.dtype([("X", "<f8", (3,)), ("desc", "u1", (32,)), ("octave", "<i4"), ("source", "<i4")])
+PROJ_OBS_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("kp_idx", "<i4"), ("hamming", "<i4"), ("second", "<i4"), ("flags", "<i4")])
+PROJ_PAIR_DTYPE = np.dtype([("landmark", "<i4"), ("keypoint", "<i4")])
 
 
 # aria_stereo_obs (32 bytes) and aria_stereo_scale (16 bytes)
@@ -588,6 +603,8 @@ def load_library():
         _bind_icp(L)
     if hasattr(L, "aria_mesh_create"):
         _bind_mesh(L)
+    if hasattr(L, "aria_proj_create"):
+        _bind_proj(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -824,6 +841,14 @@ def _bind_pnp(L):
     L.aria_pnp_associate_batch_device.argtypes = [p, p, i, i, p, p, i64, p, p, i, i, p, p, p]
     L.aria_pnp_set_solver.argtypes = [p, i]
     L.aria_pnp_get_solver.argtypes = [p]
+
+
+def _bind_proj(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "proj")
+    L.aria_proj_search_batch_device.argtypes = [p, p, p, p, p, i64, i, i, p, i, p, i, i, p, p, p, p]
+    L.aria_proj_search.argtypes = [p, p, p, p, i, i, i, p, i, p, p, p, C.POINTER(C.c_int)]
+    L.aria_proj_landmarks_from_map_device.argtypes = [p, p, i64, i64, i, i, p, p, p, i64, i, p, p]
 
 
 def status_string(status):

@@ -1,5 +1,5 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
-//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--pnp-solver dlt|p3p] [--bundle FILE3] [--bundle-window N]
+//                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--pnp-solver dlt|p3p] [--local-map K] [--local-radius PX] [--bundle FILE3] [--bundle-window N]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
 //                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--mesh FILE2.ply] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE] [--track-dense FILE2]
 //
@@ -40,6 +40,10 @@
 // FILE2 gets one TUM line per frame (world-to-camera poses), and "track pnp A fallback B bootstrap C held D map N -> FILE2"
 // is printed. --pose FILE, --map and the CSV are byte-identical with and without it. --pnp-solver dlt|p3p chooses the PnP
 // step's minimal solver (default dlt; p3p places a frame against a planar map, where the DLT finds no pose).
+// --local-map K [--local-radius PX] (needs --track-map; default 0 = off): every step first tries guided matching (aria_hip/
+// HipProjectionMatcher.hpp) -- the landmarks of the last K triangulated pairs projected by the predicted
+// pose, searched in a window of PX px at octave 0, PnP on the result -- and goes down the path above only when that places no
+// pose. "track local L of the last K pairs, radius PX px" is printed after the track line. Without the flag nothing changes.
 //
 // --loop-verify reference (needs --loop): a loop candidate is accepted as LoopClosureDetector accepts it -- F-RANSAC on its
 // ratio-0.7 list, then E-RANSAC + recoverPose on the F inliers with computeRelativePose's K (aria_hip/
@@ -223,7 +227,7 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--mesh file2.ply] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--local-map K] [--local-radius PX] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--mesh file2.ply] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
                              "  --track-dense file2: frame-to-model tracking of the --dense depth maps against a volume of its own (needs --volume): one TUM line per frame\n"
                              "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
                              "  --render prefix: the --volume map cast at every n-th integrated pose (--render-every n, default 10; needs --volume):\n"
@@ -242,6 +246,9 @@ int main(int argc, char** argv) {
                              "  --fuse file: EKF visual-inertial fusion over imu0 and the --pose stage's relative poses (needs --pose), one TUM line per frame\n"
                              "  --pnp-solver dlt|p3p: the minimal solver of --track-map's PnP step (default dlt: the 6-point DLT, which places no frame on a\n"
                              "                        planar scene; p3p needs four map points and handles planes)\n"
+                             "  --local-map K [--local-radius PX]: --track-map first places a frame by guided matching against the landmarks of the last K\n"
+                             "                        pairs (projection by the predicted pose, window of PX px at octave 0, default 15), so a frame\n"
+                             "                        after a blank one keeps the map's frame and scale (default 0: off)\n"
                              "  --bundle file: local bundle adjustment of the --track-map trajectory in windows of --bundle-window N frames (default 10, at most 16),\n"
                              "                 stride N - 2, the first two poses of a window fixed (needs --track-map)\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
@@ -253,6 +260,8 @@ int main(int argc, char** argv) {
     std::string bundle_file;
     int bundle_window = 10;
     std::string pnp_solver_name = "dlt";
+    int local_map = 0;
+    double local_radius = 15.0;
     std::string csv, pose_file, map_file, track_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
@@ -272,6 +281,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map_file = argv[++i];
         else if (!std::strcmp(argv[i], "--track-map") && i + 1 < argc) track_file = argv[++i];
         else if (!std::strcmp(argv[i], "--pnp-solver") && i + 1 < argc) pnp_solver_name = argv[++i];
+        else if (!std::strcmp(argv[i], "--local-map") && i + 1 < argc) local_map = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--local-radius") && i + 1 < argc) local_radius = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--bundle") && i + 1 < argc) bundle_file = argv[++i];
         else if (!std::strcmp(argv[i], "--bundle-window") && i + 1 < argc) bundle_window = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
@@ -324,6 +335,10 @@ int main(int argc, char** argv) {
     }
     if (!track_file.empty() && pose_file.empty()) {
         std::fprintf(stderr, "--track-map needs --pose (it bootstraps from, and falls back to, the pose stage)\n");
+        return 1;
+    }
+    if (local_map < 0 || (local_map > 0 && track_file.empty()) || !(local_radius >= 0.0 && local_radius <= 1024.0)) {
+        std::fprintf(stderr, "--local-map K >= 0 needs --track-map; --local-radius 0..1024\n");
         return 1;
     }
     if (!bundle_file.empty() && (track_file.empty() || bundle_window < 3 || bundle_window > ARIA_BA_MAX_POSES)) {
@@ -445,7 +460,7 @@ int main(int argc, char** argv) {
     std::size_t map_points = 0;
     // --track-map: world-to-camera pose per frame, and how each step was made (TrackStep::Source)
     std::vector<std::array<double, 16>> track_traj(track_file.empty() ? 0 : N);
-    long long track_steps[4] = {0, 0, 0, 0};
+    long long track_steps[5] = {0, 0, 0, 0, 0};   // indexed by TrackStep::Source
     std::size_t track_points = 0;
     // --bundle: what the tracker did, step by step, and the sequence frame its first frame is
     adapters::hip::WindowBuilder bundle_builder;
@@ -552,6 +567,7 @@ int main(int argc, char** argv) {
                 mc.device = fc.hip_device;
                 if (rectifier) mc.K = new_K;
                 tracker = std::make_unique<adapters::hip::MapTracker>(mc, 10, 1024, pnp_solver);
+                if (local_map > 0) tracker->setLocalMap(local_map, (float)local_radius);
                 if (!bundle_file.empty()) {
                     tracker->setWindowBuilder(&bundle_builder);
                     bundle_K = mc.K;
@@ -963,6 +979,7 @@ int main(int argc, char** argv) {
         write_tum(track_file, [&](std::size_t i) { return track_traj[i]; });
         std::printf("track pnp %lld fallback %lld bootstrap %lld held %lld map %zu -> %s\n", track_steps[2], track_steps[3],
                     track_steps[1], track_steps[0], track_points, track_file.c_str());
+        if (local_map > 0) std::printf("track local %lld of the last %d pairs, radius %.1f px\n", track_steps[4], local_map, local_radius);
     }
     if (!bundle_file.empty()) {
         // windows in order; a window's refined poses and points seed the next (WindowBuilder::store)

@@ -2302,6 +2302,110 @@ int64_t aria_mesh_scratch_bytes(int nx, int ny, int nz);
  * vertex and 12 per triangle written. Host only, no handle. */
 int64_t aria_mesh_algorithmic_bytes(int nx, int ny, int nz, int64_t n_vertices, int64_t n_triangles);
 
+/* ---- guided matching: landmarks projected into a frame by a predicted pose, the keypoints searched in a small window
+ * around each projection, the best descriptor match kept (the step ORB-SLAM calls SearchByProjection) -- correspondences for
+ * aria_pnp_estimate_batch_device against landmarks of ANY earlier pair, where aria_pnp_associate_batch_device reaches only
+ * the points of the previous one. The reference has no code for it, so the NumPy restatement aria_slam_amd/proj_ref.py is
+ * the definition and the device equals it bit for bit. Additive to ABI 4.
+ *
+ * Inputs per frame f of a batch: a predicted world-to-camera pose at d_pose + 12 f (12 doubles [R|t], row-major: rows of
+ *   (r0 r1 r2 t)); the extractor's batch outputs, keypoints at d_kp + f*kp_stride (d_n[f] of them), descriptors at
+ *   d_desc + f*kp_stride*32, kp_stride <= 8192; the image size width x height (<= 4096 each); and a range
+ *   (first, count) = d_range[2f], d_range[2f+1] into ONE array of n_landmarks aria_proj_landmark records, count <= land_cap
+ *   <= 2^20. A map appends in pair order, so "the landmarks of the last K pairs" is one range and the frames of a batch share
+ *   one array; ranges may overlap.
+ * Rules per landmark i of the frame's range (array index first + i), in this order. radius_px and ratio are used as fp32;
+ *   scale[o] is the fp32 level scale of aria_orb_level_info.
+ * 1. Projection in fp64, no contraction. Xc = R X + t, each component ((r0 X0 + r1 X1) + r2 X2) + t. The landmark is visible
+ *   when octave >= 0, Xc.z > min_depth, and u = (float)(fx * Xc.x / Xc.z + cx), v = (float)(fy * Xc.y / Xc.z + cy) satisfy
+ *   0 <= u < width and 0 <= v < height in fp32 (a NaN fails every test). A landmark that is not visible has u = v = 0,
+ *   kp_idx = hamming = second = -1, flags = 0. octave < 0 marks a dead landmark, which is never visible.
+ * 2. Candidates. Keypoint k < d_n[f] is a candidate when, in fp32 as written, |octave_k - octave_i| <= max_octave_diff with
+ *   both octaves clamped to 0..7, fabsf(x_k - u) <= r and fabsf(y_k - v) <= r, r = radius_px * scale[octave_i]: a square
+ *   window with inclusive edges.
+ * 3. Best and second. hamming = the least 256-bit Hamming distance over the candidates, ties to the lowest k; second = the
+ *   least distance over the OTHER candidates (it may equal hamming), -1 with a single candidate. No candidate:
+ *   hamming = second = -1.
+ * 4. Acceptance. Rejected when hamming >= th_hamming; rejected when second >= 0 and not
+ *   (float)hamming < ratio * (float)second. A single candidate passes the ratio test.
+ * 5. Uniqueness. An accepted landmark claims its best keypoint; a keypoint goes to the claim of least hamming, ties to the
+ *   lowest i. The losers are unmatched: they do not fall back to their second candidate.
+ * 6. Record. flags: bit 0 visible, bit 1 had candidates, bit 2 accepted, bit 3 won its keypoint. kp_idx = the keypoint when
+ *   bit 3 is set, else -1. hamming and second keep their values whenever bit 1 is set; u and v whenever bit 0 is.
+ * Outputs per frame. land_cap records aria_proj_obs at d_obs + f*land_cap (records at and beyond count are written as not
+ *   visible). And the matched landmarks in ascending i, stably compacted: aria_pnp_corr at d_corr + f*land_cap (the
+ *   landmark's X and the matched keypoint's stored fp32 pixel), aria_proj_pair at d_pairs + f*land_cap (the array index
+ *   first + i and kp_idx), their number at d_ncorr[f] -- the input of aria_pnp_estimate_batch_device with
+ *   corr_cap = land_cap; d_pairs carries an inlier mask back to landmarks and keypoints. No NaN or Inf is ever written.
+ * Invalid frames. d_n[f] outside [0, kp_stride], first < 0, count outside [0, land_cap], first + count > n_landmarks, or a
+ *   non-finite pose entry: detected before any keypoint, descriptor or landmark of the frame is read; every record of the
+ *   frame is not visible, d_ncorr[f] = 0, and aria_proj_check reports ARIA_E_INVALID once. The other frames are unaffected.
+ * Determinism. Integer atomics only; bitwise reproducible; independent of the batch split, of the frame's place in the
+ *   batch, of how landmarks are chunked over workgroups and of the cell size of the keypoint binning.
+ * Defaults. min_depth 0.1 (the map stage's), radius_px 15, ratio 0.9, th_hamming 100, max_octave_diff 1: ORB-SLAM's
+ *   published tracking constants. Nobody has tuned them on a recording here.
+ * Out of scope: a predicted scale level from the landmark's distance; the viewing-angle test; ORB-SLAM's rotation-histogram
+ *   check; fusing duplicate map points; updating a landmark's descriptor; relocalisation. */
+typedef struct aria_proj_s* aria_proj_t;
+typedef struct {
+    int      struct_size;       /* = sizeof(aria_proj_config)                                                     */
+    int      device;
+    void*    stream;            /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking, as in
+                                 * aria_pose_config)                                                              */
+    double   fx, fy, cx, cy;    /* intrinsics (default EuRoC cam0)                                                */
+    double   min_depth;         /* default 0.1, finite                                                            */
+    double   radius_px;         /* default 15, used as fp32, 0..1024                                              */
+    float    ratio;             /* default 0.9, 0..1                                                              */
+    int      th_hamming;        /* default 100, 0..257                                                            */
+    int      max_octave_diff;   /* default 1, 0..8                                                                */
+    int      reserved;
+} aria_proj_config;             /* 80 bytes                                                                       */
+typedef struct {
+    double  X[3];               /* world point                                                                    */
+    uint8_t desc[32];           /* the descriptor the landmark is recognised by                                   */
+    int     octave;             /* of the keypoint it was made from; < 0: dead, never visible                     */
+    int     source;             /* carried, never interpreted (the join below: the arena position)                */
+} aria_proj_landmark;           /* 64 bytes                                                                       */
+typedef struct {
+    float u, v;
+    int   kp_idx, hamming, second, flags;
+} aria_proj_obs;                /* 24 bytes                                                                       */
+typedef struct {
+    int landmark, keypoint;
+} aria_proj_pair;               /* 8 bytes                                                                        */
+
+void  aria_proj_default_config(aria_proj_config* cfg);
+int   aria_proj_create(const aria_proj_config* cfg, aria_proj_t* out);
+void  aria_proj_destroy(aria_proj_t h);
+void* aria_proj_stream(aria_proj_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when a frame of a search was invalid (above) or a map point of the join was out of range (below). */
+int   aria_proj_check(aria_proj_t h);
+/* Device-resident batch form (layout above). Enqueued on the handle's stream; nothing is synchronised, except when the
+ * handle's workspace grows: 20 bytes per keypoint slot and 4 per 32 x 32 pixel cell of every frame of the batch. */
+int   aria_proj_search_batch_device(aria_proj_t h, const double* d_pose, const aria_keypoint* d_kp, const uint8_t* d_desc,
+                                    const int* d_n, int64_t kp_stride, int width, int height,
+                                    const aria_proj_landmark* d_land, int n_landmarks, const int* d_range, int land_cap,
+                                    int n_frames, aria_proj_obs* d_obs, aria_pnp_corr* d_corr, aria_proj_pair* d_pairs,
+                                    int* d_ncorr);
+/* One frame from host arrays, every landmark searched (first = 0, count = land_cap = n_landmarks); blocks, and returns what
+ * aria_proj_check would. obs, corr, pairs: n_landmarks records each (corr and pairs filled up to *n_corr). */
+int   aria_proj_search(aria_proj_t h, const double* pose, const aria_keypoint* kp, const uint8_t* desc, int n, int width,
+                       int height, const aria_proj_landmark* land, int n_landmarks, aria_proj_obs* obs, aria_pnp_corr* corr,
+                       aria_proj_pair* pairs, int* n_corr);
+/* The join with the map: arena positions [first, min(first + max_count, size)) become landmarks at d_land[0..), their number
+ * at d_nland[0]; the arena is read with its device-resident size, as aria_pnp_associate_batch_device reads it, and the
+ * stream-ordering caveats written there hold here. For a point of pair p, slot s = p - pair_base must lie in [0, n_slots)
+ * and idx = idx1 (view 1) or idx2 (view 2) in [0, d_n[s]) with d_n[s] <= kp_stride: the landmark is the point's X, the
+ * descriptor row and the octave of keypoint idx of slot s (d_kp + s*kp_stride, d_desc + s*kp_stride*32), and source = the
+ * arena position. A point out of range becomes a dead landmark (octave -1, zero X and descriptor, source = its position)
+ * and a deferred ARIA_E_INVALID. Records at and beyond the number written are dead with source -1, so all max_count
+ * records are defined. Integer copies only. first >= 0, 0 <= max_count, first + max_count < 2^31; a map on another device
+ * than the handle's: ARIA_E_INVALID. */
+int   aria_proj_landmarks_from_map_device(aria_proj_t h, aria_map_t map, int64_t first, int64_t max_count, int pair_base,
+                                          int view, const aria_keypoint* d_kp, const uint8_t* d_desc, const int* d_n,
+                                          int64_t kp_stride, int n_slots, aria_proj_landmark* d_land, int* d_nland);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
