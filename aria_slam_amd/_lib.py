@@ -111,6 +111,11 @@ EXPORTS = [
     # guided matching (landmarks projected by a predicted pose, window search, local-map PnP input), additive to ABI 4
     "aria_proj_default_config", "aria_proj_create", "aria_proj_destroy", "aria_proj_stream", "aria_proj_check",
     "aria_proj_search_batch_device", "aria_proj_search", "aria_proj_landmarks_from_map_device",
+    # place recognition (flat binary bag-of-words vocabulary, ring database of bags, scored top-K), additive to ABI 4
+    "aria_bow_default_config", "aria_bow_create", "aria_bow_destroy", "aria_bow_stream", "aria_bow_check", "aria_bow_words",
+    "aria_bow_train_device", "aria_bow_train", "aria_bow_set_vocabulary", "aria_bow_get_vocabulary", "aria_bow_save", "aria_bow_load",
+    "aria_bow_transform_batch_device", "aria_bow_add_batch_device", "aria_bow_add", "aria_bow_add_device", "aria_bow_size",
+    "aria_bow_info", "aria_bow_query_batch_device", "aria_bow_query", "aria_bow_query_device",
 ]
 
 
@@ -311,6 +316,15 @@ class ProjConfig(C.Structure):
 PROJ_LANDMARK_DTYPE = np.dtype([("X", "<f8", (3,)), ("desc", "u1", (32,)), ("octave", "<i4"), ("source", "<i4")])
 PROJ_OBS_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("kp_idx", "<i4"), ("hamming", "<i4"), ("second", "<i4"), ("flags", "<i4")])
 PROJ_PAIR_DTYPE = np.dtype([("landmark", "<i4"), ("keypoint", "<i4")])
+
+
+class BowConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("words", C.c_int), ("rows", C.c_int),
+                ("capacity", C.c_int), ("top_k", C.c_int), ("min_frames_between", C.c_int), ("train_iters", C.c_int)]
+
+
+# aria_bow_hit (32 bytes)
+BOW_HIT_DTYPE = np.dtype([("index", "<i4"), ("reserved", "<i4"), ("id", "<i8"), ("S", "<i8"), ("score", "<f8")])
 
 
 # aria_stereo_obs (32 bytes) and aria_stereo_scale (16 bytes)
@@ -605,6 +619,8 @@ def load_library():
         _bind_mesh(L)
     if hasattr(L, "aria_proj_create"):
         _bind_proj(L)
+    if hasattr(L, "aria_bow_create"):
+        _bind_bow(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -841,6 +857,27 @@ def _bind_pnp(L):
     L.aria_pnp_associate_batch_device.argtypes = [p, p, i, i, p, p, i64, p, p, i, i, p, p, p]
     L.aria_pnp_set_solver.argtypes = [p, i]
     L.aria_pnp_get_solver.argtypes = [p]
+
+
+def _bind_bow(L):
+    p, i, i64, ll, ip = C.c_void_p, C.c_int, C.c_int64, C.c_longlong, C.POINTER(C.c_int)
+    _bind_handle(L, "bow")
+    L.aria_bow_words.argtypes = [p]
+    L.aria_bow_train_device.argtypes = [p, p, p, i, i64, ip]
+    L.aria_bow_train.argtypes = [p, p, p, i, i64, ip]
+    L.aria_bow_set_vocabulary.argtypes = [p, p, p, i]
+    L.aria_bow_get_vocabulary.argtypes = [p, p, p, ip]
+    L.aria_bow_save.argtypes = [p, C.c_char_p]
+    L.aria_bow_load.argtypes = [p, C.c_char_p]
+    L.aria_bow_transform_batch_device.argtypes = [p, p, p, i, i64, p, p]
+    L.aria_bow_add_batch_device.argtypes = [p, p, p, p, i]
+    L.aria_bow_add.argtypes = [p, ll, p, i]
+    L.aria_bow_add_device.argtypes = [p, ll, p, i]
+    L.aria_bow_size.argtypes = [p]
+    L.aria_bow_info.argtypes = [p, i, C.POINTER(ll), ip]
+    L.aria_bow_query_batch_device.argtypes = [p, p, p, p, i, p, p]
+    L.aria_bow_query.argtypes = [p, ll, p, i, p, ip]
+    L.aria_bow_query_device.argtypes = [p, ll, p, i, p, ip]
 
 
 def _bind_proj(L):

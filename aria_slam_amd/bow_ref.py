@@ -1,0 +1,201 @@
+"""Place recognition by a binary bag of words: the definition (include/aria_orb_hip.h, "place recognition"). The reference has
+no such code, so this NumPy restatement IS the definition and aria_slam_amd/csrc/bow_index.hip equals it bit for bit. Everything
+is integer arithmetic except one correctly rounded fp64 division per score.
+
+  vocabulary  V words of 32 bytes (bit b of a descriptor = bit b & 7 of byte b >> 3, the matcher's order), 1 <= V <= 4096, and a
+              weight idf_q[w] (uint16, < 4096) per word.
+  quantise    the word at the least Hamming distance, ties to the lowest word.
+  train       k-majority clustering (train below), weights from the integer logarithm ilog2_q8.
+  bag         tf[w] = descriptors of the frame on word w (uint16); v[w] = tf[w] * idf_q[w]; N = sum v[w] < 2^24; N = 0: empty.
+  score       S = sum_w min(v[w] * Nd, u[w] * Nq) (exact, <= Nq * Nd < 2^48); score = double(S) / double(Nq * Nd).
+  database    a deque of at most `capacity` entries (id, tf, N), oldest first; adding beyond capacity drops the oldest.
+  query       the non-empty entries with query_id - id >= min_frames_between and score > 0; best K by score descending, ties to
+              the lower index."""
+import collections
+
+import numpy as np
+
+MAX_WORDS = 4096
+MAX_ROWS = 4096
+MAX_FRAMES = 65535
+MAX_TOP_K = 32
+DEFAULT_ITERS = 10
+DEFAULT_CAPACITY = 65536
+FILE_MAGIC = b"ARIABOW\x00"
+FILE_VERSION = 1
+
+# aria_bow_hit (32 bytes)
+HIT_DTYPE = np.dtype([("index", "<i4"), ("reserved", "<i4"), ("id", "<i8"), ("S", "<i8"), ("score", "<f8")])
+
+
+def bits_of(desc):
+    """[n, 32] uint8 -> [n, 256] uint8 of 0 / 1, bit b = bit b & 7 of byte b >> 3."""
+    return np.unpackbits(np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), axis=1, bitorder="little")
+
+
+def pack_bits(bits):
+    return np.packbits(np.asarray(bits, np.uint8).reshape(-1, 256), axis=1, bitorder="little")
+
+
+def distances(desc, words):
+    """[n, V] Hamming distances (exact: every term is an integer <= 256, far inside fp32)."""
+    a, w = bits_of(desc).astype(np.float32), bits_of(words).astype(np.float32)
+    d = a.sum(1)[:, None] + w.sum(1)[None, :] - 2.0 * (a @ w.T)
+    return d.astype(np.int32)
+
+
+def quantise(desc, words):
+    """Rule 2: the index of the nearest word of each descriptor, ties to the lowest index. [n] int32."""
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    if len(desc) == 0:
+        return np.zeros(0, np.int32)
+    out = np.empty(len(desc), np.int32)
+    for s in range(0, len(desc), 4096):
+        out[s:s + 4096] = np.argmin(distances(desc[s:s + 4096], words), axis=1)    # argmin keeps the first of equals
+    return out
+
+
+def ilog2_q8(num, den):
+    """floor-like log2(num / den) in Q8 for integers 1 <= den <= num < 2^16, by shift and square on 64-bit integers. This
+    function is the definition, truncations included: e = the integer part; the mantissa num / (den << e) as a truncated Q30
+    number in [1, 2); eight times: square (truncated to Q30), take the bit that says whether the square reached 2."""
+    num, den = int(num), int(den)
+    assert 1 <= den <= num < 65536
+    e = 0
+    while (den << (e + 1)) <= num:
+        e += 1
+    m = (num << 30) // (den << e)
+    r = e
+    for _ in range(8):
+        m = (m * m) >> 30
+        r <<= 1
+        if m >= (1 << 31):
+            r |= 1
+            m >>= 1
+    return r
+
+
+def idf_weight(n_frames, n_w):
+    """Rule 4: 0 when the word is in no frame or in every frame, else log2(F / n_w) in Q8."""
+    return 0 if n_w <= 0 or n_w >= n_frames else ilog2_q8(n_frames, n_w)
+
+
+def majority(desc, idx, words):
+    """One update of rule 3: bit = 1 iff 2 * ones > members; a word without members keeps its bits."""
+    V = len(words)
+    ones = np.zeros((V, 256), np.int64)
+    np.add.at(ones, idx, bits_of(desc).astype(np.int64))
+    members = np.bincount(idx, minlength=V).astype(np.int64)
+    new = pack_bits((2 * ones > members[:, None]).astype(np.uint8))
+    keep = members == 0
+    new[keep] = words[keep]
+    return new
+
+
+def train(frames, V, iters=DEFAULT_ITERS):
+    """Rules 3 and 4. frames: a list of [n_f, 32] uint8 arrays. Returns (words [V, 32] uint8, idf_q [V] uint16, iterations
+    run). Raises ValueError for what the library answers with ARIA_E_INVALID."""
+    frames = [np.ascontiguousarray(f, np.uint8).reshape(-1, 32) for f in frames]
+    F = len(frames)
+    D = np.concatenate(frames) if F else np.zeros((0, 32), np.uint8)
+    n = len(D)
+    if not 1 <= V <= MAX_WORDS or n < V or F > MAX_FRAMES or iters < 0:
+        raise ValueError("training set refused")
+    words = D[[(j * n) // V for j in range(V)]].copy()
+    run = 0
+    while run < iters:
+        new = majority(D, quantise(D, words), words)
+        run += 1
+        changed = not np.array_equal(new, words)
+        words = new
+        if not changed:
+            break
+    n_w = np.zeros(V, np.int64)
+    for f in frames:
+        n_w[np.unique(quantise(f, words))] += 1
+    idf = np.array([idf_weight(F, int(c)) for c in n_w], np.uint16)
+    return words, idf, run
+
+
+def transform(desc, words, idf_q):
+    """Rule 5: (tf [V] uint16, N)."""
+    tf = np.bincount(quantise(desc, words), minlength=len(words)).astype(np.uint16)
+    return tf, norm_of(tf, idf_q)
+
+
+def norm_of(tf, idf_q):
+    return int((np.asarray(tf).astype(np.int64) * np.asarray(idf_q).astype(np.int64)).sum())
+
+
+def score(tf_q, n_q, tf_d, n_d, idf_q):
+    """Rule 6: (S, score). Python integers, one IEEE division."""
+    if n_q <= 0 or n_d <= 0:
+        return 0, 0.0
+    idf = np.asarray(idf_q).astype(np.int64)
+    v, u = np.asarray(tf_q).astype(np.int64) * idf, np.asarray(tf_d).astype(np.int64) * idf
+    S = int(np.minimum(v * int(n_d), u * int(n_q)).sum())
+    return S, float(S) / float(int(n_q) * int(n_d))
+
+
+class BowIndexRef:
+    """Rules 7 and 8."""
+
+    def __init__(self, words, idf_q, capacity=DEFAULT_CAPACITY, top_k=10, min_frames_between=0):
+        self.words = np.ascontiguousarray(words, np.uint8).reshape(-1, 32)
+        self.idf = np.ascontiguousarray(idf_q, np.uint16).reshape(-1)
+        assert len(self.words) == len(self.idf) and 1 <= top_k <= MAX_TOP_K and capacity >= 1
+        self.top_k, self.mfb = int(top_k), int(min_frames_between)
+        self.db = collections.deque(maxlen=int(capacity))
+
+    def transform(self, desc):
+        return transform(desc, self.words, self.idf)
+
+    def add_bag(self, kf_id, tf, norm):
+        self.db.append((int(kf_id), np.array(tf, np.uint16), int(norm)))
+
+    def add(self, kf_id, desc):
+        self.add_bag(kf_id, *self.transform(desc))
+
+    def size(self):
+        return len(self.db)
+
+    def info(self, index):
+        return self.db[index][0], self.db[index][2]
+
+    def query_bag(self, query_id, tf, norm):
+        """(hits [top_k] HIT_DTYPE, count)."""
+        cand = []
+        for i, (kid, tf_d, n_d) in enumerate(self.db):
+            if norm <= 0 or n_d <= 0 or int(query_id) - kid < self.mfb:
+                continue
+            S, sc = score(tf, norm, tf_d, n_d, self.idf)
+            if sc > 0.0:
+                cand.append((i, kid, S, sc))
+        cand.sort(key=lambda c: (-c[3], c[0]))
+        hits = np.zeros(self.top_k, HIT_DTYPE)
+        hits["index"], hits["id"] = -1, -1
+        for k, (i, kid, S, sc) in enumerate(cand[:self.top_k]):
+            hits[k] = (i, 0, kid, S, sc)
+        return hits, min(len(cand), self.top_k)
+
+    def query(self, query_id, desc):
+        return self.query_bag(query_id, *self.transform(desc))
+
+
+def vocabulary_bytes(words, idf_q):
+    """The project's vocabulary file: magic, version (u32), V (u32), words, idf_q, little-endian."""
+    words = np.ascontiguousarray(words, np.uint8).reshape(-1, 32)
+    idf = np.ascontiguousarray(idf_q, "<u2").reshape(-1)
+    return FILE_MAGIC + np.array([FILE_VERSION, len(words)], "<u4").tobytes() + words.tobytes() + idf.tobytes()
+
+
+def bow_subset_candidates(hits, count, good, nq, query_id, kf_ids, kf_counts, min_frames_between):
+    """The host rules of KeyframeDB.find_candidates_bow: the reference's scoring (loopdb.score_candidates) applied to the
+    database indices the index returned. good[k]: ratio-test matches of the query against hit k. Returns [(db_index, score)]."""
+    from .loopdb import score_candidates
+    idx = [int(h) for h in np.asarray(hits["index"])[:count] if h >= 0]
+    sub = score_candidates([good[k] for k in range(len(idx))], nq, query_id, [kf_ids[i] for i in idx], [kf_counts[i] for i in idx],
+                           min_frames_between)
+    out = [(idx[k], s) for k, s in sub]
+    out.sort(key=lambda t: (-t[1], t[0]))
+    return out

@@ -16,6 +16,7 @@
 // (aria_hip/HipPoseEstimator.hpp) is an E-RANSAC-only variant with the caller's K.
 #pragma once
 #include <functional>
+#include <memory>
 #include <optional>
 #include <utility>
 #include <vector>
@@ -26,6 +27,8 @@
 struct aria_kfdb_s;
 
 namespace aria::adapters::hip {
+
+class HipPlaceIndex;
 
 class HipLoopDetector : public interfaces::ILoopDetector {
 public:
@@ -55,6 +58,17 @@ public:
     using Verifier = std::function<bool(const core::KeyFrame& query, std::uint64_t match_id, core::LoopCandidate& candidate)>;
     void setVerifier(Verifier v) { verifier_ = std::move(v); }
 
+    // Place recognition in front of the exact check (aria_hip/HipPlaceIndex.hpp; off by default, and with none set every
+    // method is what it was, to the bit). With an index set, addKeyFrame also adds the keyframe's bag, and findCandidates asks
+    // the index for its best top_k entries, runs the ratio-0.7 match (aria_kfdb_match) against those keyframes only and
+    // applies the reference's rules (good / max(1, |query|), > 0.1, best five) to that subset. The index must hold a
+    // vocabulary, be fed by this detector alone and keep at least as many entries as the keyframe database; the database's
+    // `capacity` may then be raised well past the reference's 500 (a slot costs slot_rows * 32 bytes of HBM).
+    void setPlaceIndex(std::shared_ptr<HipPlaceIndex> index, int top_k = 10);
+    // what the index has been asked and has answered since it was set: queries, and candidates passed to the exact check
+    long long placeQueries() const { return place_queries_; }
+    long long placeCandidates() const { return place_candidates_; }
+
 private:
     aria_kfdb_s* db_ = nullptr;
     HipMatcher matcher_;
@@ -66,6 +80,9 @@ private:
     Verifier verifier_;
     std::vector<int> good_;
     std::vector<core::Match> match_buf_;
+    std::shared_ptr<HipPlaceIndex> place_;
+    int place_top_k_ = 10;
+    long long place_queries_ = 0, place_candidates_ = 0;
 };
 
 }  // namespace aria::adapters::hip

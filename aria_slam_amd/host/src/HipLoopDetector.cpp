@@ -5,6 +5,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "aria_hip/HipPlaceIndex.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -43,6 +44,17 @@ void HipLoopDetector::addKeyFrame(const core::KeyFrame& kf) {
     if ((size_t)n * 32 > kf.frame.descriptors.size()) fail("addKeyFrame: descriptors shorter than numKeypoints()*32", ARIA_E_INVALID);
     int rc = aria_kfdb_add(db_, (long long)kf.id, kf.frame.descriptors.data(), n);       // push_back + pop_front beyond 500
     if (rc != ARIA_OK) fail("aria_kfdb_add", rc);
+    if (place_) {                                                                          // the C-ABI directly: this file links without HipPlaceIndex.cpp
+        rc = aria_bow_add(place_->handle(), (long long)kf.id, n ? kf.frame.descriptors.data() : nullptr, n);
+        if (rc != ARIA_OK) fail("aria_bow_add", rc);
+    }
+}
+
+void HipLoopDetector::setPlaceIndex(std::shared_ptr<HipPlaceIndex> index, int top_k) {
+    if (index && (aria_bow_words(index->handle()) == 0 || aria_bow_size(index->handle()) != size() || top_k < 1))
+        fail("setPlaceIndex: the index needs a vocabulary and as many entries as the database", ARIA_E_INVALID);
+    place_ = std::move(index);
+    place_top_k_ = top_k;
 }
 
 std::vector<std::pair<int, double>> HipLoopDetector::findCandidates(const core::KeyFrame& query) {
@@ -51,6 +63,38 @@ std::vector<std::pair<int, double>> HipLoopDetector::findCandidates(const core::
     const int nq = (int)query.frame.numKeypoints();
     if ((size_t)nq * 32 > query.frame.descriptors.size()) fail("findCandidates: descriptors shorter than numKeypoints()*32", ARIA_E_INVALID);
     matcher_.reserve(nq, slot_rows_);
+    if (place_) {
+        // the index names at most top_k keyframes; only they are matched exactly. Its deque may be longer than the
+        // database's: the same keyframe lies `shift` positions later there
+        const int shift = aria_bow_size(place_->handle()) - size();
+        std::vector<aria_bow_hit> hits((size_t)place_->topK());
+        int n_hits = 0;
+        int rc = aria_bow_query(place_->handle(), (long long)query.id, query.frame.descriptors.data(), nq, hits.data(), &n_hits);
+        if (rc != ARIA_OK) fail("aria_bow_query", rc);
+        place_queries_++;
+        hits.resize((size_t)std::max(0, std::min(n_hits, std::min(place_top_k_, place_->topK()))));
+        match_buf_.resize((size_t)std::max(nq, 1));
+        for (const aria_bow_hit& h : hits) {
+            const int i = h.index - shift;
+            long long id = 0;
+            int cnt = 0;
+            if (i < 0 || aria_kfdb_info(db_, i, &id, &cnt) != ARIA_OK || id != (long long)h.id) continue;
+            if ((long long)query.id - id < (long long)min_frames_between_) continue;   // :81
+            if (cnt <= 0) continue;                                                     // :83
+            int good = 0;
+            place_candidates_++;
+            rc = aria_kfdb_match(db_, matcher_.handle(), i, query.frame.descriptors.data(), nq, 0.7f,
+                                 reinterpret_cast<aria_match*>(match_buf_.data()), (int)match_buf_.size(), &good);
+            if (rc != ARIA_OK) fail("aria_kfdb_match", rc);
+            const double score = (double)good / std::max(1, nq);                       // :98
+            if (score > 0.1) candidates.push_back({i, score});                          // :99
+        }
+        std::sort(candidates.begin(), candidates.end(), [](const auto& a, const auto& b) {
+            return a.second > b.second || (a.second == b.second && a.first < b.first);  // :105-106, ties in database order
+        });
+        if (candidates.size() > 5) candidates.resize(5);                                // :109-111
+        return candidates;
+    }
     int n_kf = 0;
     int rc = aria_kfdb_scan(db_, matcher_.handle(), query.frame.descriptors.data(), nq, 0.7, good_.data(), (int)good_.size(), &n_kf);
     if (rc != ARIA_OK) fail("aria_kfdb_scan", rc);

@@ -1,5 +1,6 @@
 // euroc_frontend <dataset_path> [max_features=2000] [--legacy-order] [--csv out.csv] [--loop] [--loop-verify reference]
 //                [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose FILE] [--map FILE.ply] [--track-map FILE2] [--pnp-solver dlt|p3p] [--local-map K] [--local-radius PX] [--bundle FILE3] [--bundle-window N]
+//                [--loop-bow V] [--loop-bow-top K] [--loop-bow-vocab FILE] [--loop-capacity N]
 //                [--optimize FILE] [--fuse FILE] [--eval FILE] [--eval-align none|se3|sim3] [--rpe-delta N]
 //                [--stereo BASELINE_M] [--stereo-out FILE] [--rectify] [--dense FILE] [--volume FILE.ply] [--voxel M] [--mesh FILE2.ply] [--plan FILE] [--render PREFIX] [--render-every N] [--alerts FILE] [--track-dense FILE2]
 //
@@ -44,6 +45,13 @@
 // HipProjectionMatcher.hpp) -- the landmarks of the last K triangulated pairs projected by the predicted
 // pose, searched in a window of PX px at octave 0, PnP on the result -- and goes down the path above only when that places no
 // pose. "track local L of the last K pairs, radius PX px" is printed after the track line. Without the flag nothing changes.
+//
+// --loop-bow V [--loop-bow-top K] [--loop-bow-vocab FILE] [--loop-capacity N] (needs --loop; default 0 = off): place recognition
+// in front of the exact loop check (aria_hip/HipPlaceIndex.hpp, HipLoopDetector::setPlaceIndex). The loop step then runs over the
+// merged stream as in the sharded mode. The vocabulary of V words is loaded from FILE when it exists; otherwise it is trained, in
+// a pre-pass over that stream, on at most 256 of the frames that can be keyframes, sampled evenly, and written to FILE when one
+// is named. The keyframe database holds N keyframes (default 500, the reference's), the index as many bags. One line
+// "loop bow words V iterations I entries E queries Q candidates C" is printed (I = 0: loaded).
 //
 // --loop-verify reference (needs --loop): a loop candidate is accepted as LoopClosureDetector accepts it -- F-RANSAC on its
 // ratio-0.7 list, then E-RANSAC + recoverPose on the F inliers with computeRelativePose's K (aria_hip/
@@ -180,6 +188,7 @@
 #include "aria_hip/HipFactory.hpp"
 #include "aria_hip/HipFundamentalEstimator.hpp"
 #include "aria_hip/HipLoopDetector.hpp"
+#include "aria_hip/HipPlaceIndex.hpp"
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipBundleAdjuster.hpp"
 #include "aria_hip/MapTracker.hpp"
@@ -249,6 +258,9 @@ int main(int argc, char** argv) {
                              "  --local-map K [--local-radius PX]: --track-map first places a frame by guided matching against the landmarks of the last K\n"
                              "                        pairs (projection by the predicted pose, window of PX px at octave 0, default 15), so a frame\n"
                              "                        after a blank one keeps the map's frame and scale (default 0: off)\n"
+                             "  --loop-bow V [--loop-bow-top K] [--loop-bow-vocab file] [--loop-capacity N]: place recognition in front of the loop check (needs --loop):\n"
+                             "                 a bag-of-words index of V words names the K (default 10) keyframes that are matched exactly; the vocabulary is\n"
+                             "                 loaded from the file, or trained on at most 256 frames of the run and written there; N keyframes are kept (default 500)\n"
                              "  --bundle file: local bundle adjustment of the --track-map trajectory in windows of --bundle-window N frames (default 10, at most 16),\n"
                              "                 stride N - 2, the first two poses of a window fixed (needs --track-map)\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
@@ -262,6 +274,9 @@ int main(int argc, char** argv) {
     std::string pnp_solver_name = "dlt";
     int local_map = 0;
     double local_radius = 15.0;
+    int loop_bow = 0, loop_bow_top = 10, loop_capacity = 500;
+    bool loop_bow_given = false;
+    std::string loop_bow_vocab;
     std::string csv, pose_file, map_file, track_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
@@ -286,6 +301,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--bundle") && i + 1 < argc) bundle_file = argv[++i];
         else if (!std::strcmp(argv[i], "--bundle-window") && i + 1 < argc) bundle_window = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--loop-verify") && i + 1 < argc) loop_verify = argv[++i];
+        else if (!std::strcmp(argv[i], "--loop-bow") && i + 1 < argc) { loop_bow = std::atoi(argv[++i]); loop_bow_given = true; }
+        else if (!std::strcmp(argv[i], "--loop-bow-top") && i + 1 < argc) { loop_bow_top = std::atoi(argv[++i]); loop_bow_given = true; }
+        else if (!std::strcmp(argv[i], "--loop-bow-vocab") && i + 1 < argc) { loop_bow_vocab = argv[++i]; loop_bow_given = true; }
+        else if (!std::strcmp(argv[i], "--loop-capacity") && i + 1 < argc) loop_capacity = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
         else if (!std::strcmp(argv[i], "--fuse") && i + 1 < argc) fuse_file = argv[++i];
         else if (!std::strcmp(argv[i], "--eval") && i + 1 < argc) eval_file = argv[++i];
@@ -314,6 +333,14 @@ int main(int argc, char** argv) {
         return -1;
     }
     const bool verify_reference = !loop_verify.empty();
+    if (loop_bow_given && (!loop || loop_bow < 1 || loop_bow > 4096 || loop_bow_top < 1 || loop_bow_top > 32)) {
+        std::fprintf(stderr, "--loop-bow V (1..4096), --loop-bow-top K (1..32) and --loop-bow-vocab need --loop\n");
+        return 1;
+    }
+    if (loop_capacity < 1 || (loop_capacity != 500 && !loop)) {
+        std::fprintf(stderr, "--loop-capacity N >= 1 needs --loop\n");
+        return 1;
+    }
     if (!optimize_file.empty() && (pose_file.empty() || !verify_reference)) {
         std::fprintf(stderr, "--optimize needs --pose, --loop and --loop-verify reference (loop edges carry the verified relative pose)\n");
         return -1;
@@ -450,7 +477,7 @@ int main(int argc, char** argv) {
     int w = 0, h = 0;
     const bool sharded = shards > 1;
     // the loop step over the merged stream, after the shards (--loop-verify: it needs the keyframes' keypoints)
-    const bool posthoc_loop = loop && (sharded || batch > 0 || verify_reference);
+    const bool posthoc_loop = loop && (sharded || batch > 0 || verify_reference || loop_bow > 0 || loop_capacity != 500);
     std::vector<pipeline::BatchStats> bstats((size_t)shards);
     // --pose: current_pose per frame (4x4 row-major), chained as euroc_eval.cpp:202-206 does
     std::vector<std::array<double, 16>> traj(pose_file.empty() ? 0 : N);
@@ -821,7 +848,45 @@ int main(int argc, char** argv) {
         factory::HipFactoryConfig fc;
         fc.max_features = max_features;
         adapters::hip::HipLoopDetector ld(fc.loop_min_frames_between, fc.loop_min_score, fc.loop_min_matches,
-                                          ((max_features + 8 * 64 + 63) / 64) * 64, 500, nullptr, 0);
+                                          ((max_features + 8 * 64 + 63) / 64) * 64, loop_capacity, nullptr, 0);
+        std::shared_ptr<adapters::hip::HipPlaceIndex> place;
+        int place_iters = 0;
+        if (loop_bow > 0) {
+            adapters::hip::PlaceIndexConfig pc;
+            pc.words = loop_bow;
+            pc.rows = std::min(((max_features + 8 * 64 + 63) / 64) * 64, 4096);
+            pc.capacity = loop_capacity;
+            pc.top_k = loop_bow_top;
+            pc.min_frames_between = fc.loop_min_frames_between;
+            place = std::make_shared<adapters::hip::HipPlaceIndex>(pc);
+            const bool have_file = !loop_bow_vocab.empty() && std::ifstream(loop_bow_vocab).good();
+            if (have_file) {
+                place->load(loop_bow_vocab);
+                if (place->words() != loop_bow) {
+                    std::fprintf(stderr, "--loop-bow-vocab %s holds %d words, --loop-bow asks for %d\n", loop_bow_vocab.c_str(), place->words(), loop_bow);
+                    return 1;
+                }
+            } else {
+                // the pre-pass: at most 256 of the frames that can be keyframes, sampled evenly over the sequence
+                std::vector<const core::Frame*> cand, pick;
+                for (std::size_t i = 1; i < N; i++)
+                    if ((int)rec[i].matches >= fc.frontend.keyframe_min_matches && rec[i].frame) cand.push_back(rec[i].frame.get());
+                const std::size_t want = std::min<std::size_t>(cand.size(), 256);
+                std::size_t rows = 0;
+                for (std::size_t k = 0; k < want; k++) {
+                    pick.push_back(cand[k * cand.size() / want]);
+                    rows += pick.back()->numKeypoints();
+                }
+                if (rows < (std::size_t)loop_bow) {
+                    std::fprintf(stderr, "--loop-bow %d: the %zu training frames hold %zu descriptors, fewer than the words asked for\n", loop_bow,
+                                 pick.size(), rows);
+                    return 1;
+                }
+                place_iters = place->train(pick);
+                if (!loop_bow_vocab.empty()) place->save(loop_bow_vocab);
+            }
+            ld.setPlaceIndex(place, loop_bow_top);
+        }
         std::unique_ptr<adapters::hip::HipFundamentalEstimator> fund;
         std::unique_ptr<adapters::hip::HipPoseEstimator> pose;
         std::deque<std::size_t> held;                                  // keyframes in the database, oldest first
@@ -845,12 +910,15 @@ int main(int argc, char** argv) {
             o.is_keyframe = true;
             if (verify_reference) {                                    // keep the keypoints of the 500 keyframes held
                 held.push_back(i);
-                if (held.size() > 500) { rec[held.front()].frame.reset(); held.pop_front(); }
+                if (held.size() > (std::size_t)loop_capacity) { rec[held.front()].frame.reset(); held.pop_front(); }
             }
             if (lp) { o.loop_match_id = (long long)lp->match_id; o.loop_score = lp->score; }
             if (lp && graph)                                               // euroc_eval.cpp:235
                 graph->addLoopEdge((int)lp->query_id, (int)lp->match_id, adapters::hip::loopRelativePose(*lp));
         }
+        if (place)
+            std::printf("loop bow words %d iterations %d entries %d queries %lld candidates %lld\n", place->words(), place_iters, place->size(),
+                        ld.placeQueries(), ld.placeCandidates());
     }
 
     long long total_kp = 0, total_matches = 0, n_keyframes = 0, n_loops = 0;

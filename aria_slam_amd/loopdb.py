@@ -85,3 +85,23 @@ class KeyframeDB:
         matcher.sync()
         return score_candidates(good.cpu().numpy(), nq, query_id, self.ids.cpu().numpy(), self.counts.cpu().numpy(),
                                 min_frames_between)
+
+    def find_candidates_bow(self, matcher, bow, d_query, nq, query_id, min_frames_between, ratio=0.7):
+        """The place index (a HipBowIndex fed with the same keyframes in the same order, so index-aligned) names its top-K;
+        only those slots go through the exact scan, and the reference's rules are applied to that subset. Returns
+        [(db_index, score)] as find_candidates does: a subset of what the full scan would pass."""
+        import torch
+        from .bow_ref import bow_subset_candidates
+        hits, count = bow.query_device(query_id, d_query, int(nq))
+        idx = [int(i) for i in hits["index"][:count] if i >= 0]                  # the helper below reads the hits the same way
+        if not idx:
+            return []
+        sel = torch.tensor(idx, dtype=torch.int64, device=self.desc.device)
+        block = self.desc.index_select(0, sel).contiguous()                      # [K, rows, 32]
+        counts = self.counts.index_select(0, sel).contiguous()
+        good = torch.zeros((len(idx),), dtype=torch.int32, device=self.desc.device)
+        torch.cuda.current_stream(self.desc.device).synchronize()              # the gather is torch's; the matcher has its own stream
+        matcher.match_db_device(d_query, int(nq), block, counts, len(idx), self.rows * 32, ratio, good)
+        matcher.sync()
+        return bow_subset_candidates(hits, count, good.cpu().numpy(), nq, query_id, self.ids.cpu().numpy(), self.counts.cpu().numpy(),
+                                     min_frames_between)

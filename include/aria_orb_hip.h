@@ -2406,6 +2406,101 @@ int   aria_proj_landmarks_from_map_device(aria_proj_t h, aria_map_t map, int64_t
                                           int view, const aria_keypoint* d_kp, const uint8_t* d_desc, const int* d_n,
                                           int64_t kp_stride, int n_slots, aria_proj_landmark* d_land, int* d_nland);
 
+/* ---- place recognition: a binary bag-of-words keyframe index that does not forget -------------------------------------
+ * The brute-force keyframe scan (aria_kfdb_scan, LoopClosure.cpp:72-114) scores a query against every stored keyframe and
+ * keeps 500 of them; this stage scores a query against the bags of up to `capacity` keyframes and names the best K, which
+ * alone go through the exact check. The reference names the cure (docs/milestones/H09_LOOP_CLOSURE_AUDIT.md 2.1, 6.3) and
+ * has no code for it: aria_slam_amd/bow_ref.py is the definition and the device equals it bit for bit. Everything is integer
+ * arithmetic except one correctly rounded fp64 division per score. The vocabulary is flat: the nearest word of a descriptor
+ * is found by the matcher's kNN-2 kernel against all V words. Additive to ABI 4.
+ *
+ * 1. Vocabulary. V words, 1 <= V <= 4096, 32 bytes each, and a weight idf_q[w] (uint16, < 4096) per word. Bit b of a
+ *    descriptor is bit b & 7 of byte b >> 3, the matcher's order.
+ * 2. Quantise. A descriptor's word is the word at the least Hamming distance, ties to the lowest word index.
+ * 3. Train. k-majority clustering from F frames holding n descriptors in all, in frame order. n < V, F > 65535 or a count
+ *    outside [0, desc_stride]: ARIA_E_INVALID. Initial word j is training descriptor floor(j * n / V). An iteration quantises
+ *    every descriptor, then sets each bit of a word to 1 iff 2 * ones > members (a tie gives 0; a word without members keeps
+ *    its bits). Training stops after train_iters iterations or after the first that changes no word.
+ * 4. Weights. The training set is quantised once more; n_w = training frames holding word w. idf_q[w] = 0 when n_w is 0 or
+ *    F, else log2(F / n_w) in Q8 by a shift-and-square logarithm on 64-bit integers (bow_ref.ilog2_q8 is its definition,
+ *    truncations included; no libm call anywhere).
+ * 5. Bag of a frame. tf[w] = the frame's descriptors on word w (uint16; at most `rows` <= 4096 descriptors), v[w] =
+ *    tf[w] * idf_q[w], the norm N = sum v[w] < 2^24. N = 0: the bag is empty, scores 0 against everything, is never returned.
+ * 6. Score. S = sum_w min(v[w] * Nd, u[w] * Nq) for a query (v, Nq) and an entry (u, Nd): an exact integer <= Nq * Nd < 2^48;
+ *    score = (double)S / (double)(Nq * Nd), one IEEE division: DBoW2's L1 score 1 - |a - b|_1 / 2 of the L1-normalised bags.
+ *    Identical bags score exactly 1.0, disjoint bags 0.0.
+ * 7. Database. A deque of at most `capacity` entries (id, tf, N); adding beyond capacity drops the oldest; index i = the
+ *    position, oldest first: aria_kfdb's semantics, so the two stay index-aligned when fed together. A ring in HBM:
+ *    capacity * 2 * roundup(V, 8) bytes, allocated when a vocabulary is set; nothing is copied on a drop. A new vocabulary
+ *    (train, set, load) empties the database.
+ * 8. Query. Candidates: non-empty entries with query_id - id >= min_frames_between and score > 0. Result: the best
+ *    K = top_k <= 32 by score descending, ties to the lower index, as K records aria_bow_hit per query (index -1, id -1, S 0,
+ *    score 0 where there is none) and their number. Every query of a batch sees the database as it was at the call.
+ * Determinism: integer sums and integer atomics only; training, bags and hits are bitwise reproducible and independent of how
+ * frames and queries are batched. */
+typedef struct aria_bow_s* aria_bow_t;
+typedef struct {
+    int      struct_size;          /* = sizeof(aria_bow_config)                                                   */
+    int      device;
+    void*    stream;               /* borrowed hipStream_t, or NULL = the handle creates and owns one (non-blocking) */
+    int      words;                /* V that training makes, 1..4096 (default 4096)                               */
+    int      rows;                 /* most descriptors of a frame, 1..4096 (default 4096)                         */
+    int      capacity;             /* entries (default 65536)                                                     */
+    int      top_k;                /* 1..32 (default 10)                                                          */
+    int      min_frames_between;   /* default 30 (HipLoopDetector's)                                              */
+    int      train_iters;          /* default 10                                                                  */
+} aria_bow_config;                 /* 40 bytes                                                                    */
+typedef struct {
+    int32_t index;                 /* position in the database, oldest first; -1 = none                           */
+    int32_t reserved;              /* 0                                                                           */
+    int64_t id;
+    int64_t S;                     /* the numerator of the score                                                  */
+    double  score;
+} aria_bow_hit;                    /* 32 bytes                                                                    */
+
+void  aria_bow_default_config(aria_bow_config* cfg);
+int   aria_bow_create(const aria_bow_config* cfg, aria_bow_t* out);
+void  aria_bow_destroy(aria_bow_t h);
+void* aria_bow_stream(aria_bow_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when a frame's count was outside [0, min(desc_stride, rows)] (that frame alone got an empty bag) or the norm
+ * of an added or queried bag was not the sum of its weighted counts, or not below 2^24 (that entry alone is stored empty, that
+ * query alone is asked as an empty one). */
+int   aria_bow_check(aria_bow_t h);
+/* V of the vocabulary in use, 0 before there is one. Every call below that needs a vocabulary returns ARIA_E_INVALID then. */
+int   aria_bow_words(aria_bow_t h);
+/* Training (rules 3 and 4) of cfg.words words. Frame f's descriptors lie at d_desc + f * desc_stride * 32, d_counts[f] of
+ * them. Blocks: the host reads the counts first and one changed flag per iteration. *iters_run = iterations run. */
+int   aria_bow_train_device(aria_bow_t h, const uint8_t* d_desc, const int* d_counts, int n_frames, int64_t desc_stride,
+                            int* iters_run);
+int   aria_bow_train(aria_bow_t h, const uint8_t* desc, const int* counts, int n_frames, int64_t desc_stride, int* iters_run);
+/* Host arrays: V * 32 bytes and V weights (each < 4096). get: words and idf_q may be NULL; *V is always written. */
+int   aria_bow_set_vocabulary(aria_bow_t h, const uint8_t* words, const uint16_t* idf_q, int V);
+int   aria_bow_get_vocabulary(aria_bow_t h, uint8_t* words, uint16_t* idf_q, int* V);
+/* The vocabulary file, little-endian: "ARIABOW\0", version (u32 = 1), V (u32), V * 32 bytes of words, V * u16 weights. A file
+ * that cannot be read, is truncated, is longer, or holds a bad magic, version, V or weight: ARIA_E_INVALID. */
+int   aria_bow_save(aria_bow_t h, const char* path);
+int   aria_bow_load(aria_bow_t h, const char* path);
+/* Bags of a batch of frames (layout as in training): n_frames rows of V uint16 at d_tf and n_frames norms at d_norm. A count
+ * above min(desc_stride, rows) or below 0 defers ARIA_E_INVALID for that frame alone and writes an empty bag. Enqueued. */
+int   aria_bow_transform_batch_device(aria_bow_t h, const uint8_t* d_desc, const int* d_counts, int n_frames, int64_t desc_stride,
+                                      uint16_t* d_tf, int32_t* d_norm);
+/* n bags (as the transform writes them) appended in order with the ids of a HOST array, read before the call returns. Enqueued. */
+int   aria_bow_add_batch_device(aria_bow_t h, const uint16_t* d_tf, const int32_t* d_norm, const long long* ids, int n);
+/* Transform and add of one frame, 0 <= n <= rows. The host form blocks for its upload only. */
+int   aria_bow_add(aria_bow_t h, long long id, const uint8_t* desc_host, int n);
+int   aria_bow_add_device(aria_bow_t h, long long id, const uint8_t* d_desc, int n);
+int   aria_bow_size(aria_bow_t h);
+int   aria_bow_info(aria_bow_t h, int index, long long* id, int* norm);
+/* n_queries bags against the database: top_k records per query at d_hits, the number of real ones at d_counts. query_ids: a
+ * HOST array, read before the call returns. Enqueued, except when the workspace grows (16 bytes per entry and query of a
+ * chunk of at most 256 queries and 2^25 pairs). */
+int   aria_bow_query_batch_device(aria_bow_t h, const uint16_t* d_tf, const int32_t* d_norm, const long long* query_ids,
+                                  int n_queries, aria_bow_hit* d_hits, int* d_counts);
+/* Transform and query of one frame; hits: top_k records on the HOST. Blocks, and returns what aria_bow_check would. */
+int   aria_bow_query(aria_bow_t h, long long query_id, const uint8_t* desc_host, int n, aria_bow_hit* hits, int* n_out);
+int   aria_bow_query_device(aria_bow_t h, long long query_id, const uint8_t* d_desc, int n, aria_bow_hit* hits, int* n_out);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
