@@ -1,7 +1,9 @@
-"""The case table of frame-to-model tracking, shared by tests/test_icp_host.py, test_icp_kernel_emulation.py and
-test_gpu_icp.py. Scenes are rendered analytically in NumPy: three mutually orthogonal planes and a sphere, giving camera
-depth and exact world-frame normals. Every shape is the smallest at which that part of the kernel can still go wrong; the
-references are computed once per process and handed out read-only.
+"""The case table of frame-to-model tracking, shared by tests/test_icp_host.py, test_icp_rules_host.py,
+test_icp_kernel_emulation.py, test_gpu_icp.py and test_gpu_icp_rules.py. Scenes are rendered analytically in NumPy: three
+mutually orthogonal planes and a sphere, giving camera depth and exact world-frame normals. Every shape is the smallest at
+which that part of the kernel can still go wrong; the references are computed once per process and handed out read-only.
+What the scenes cannot ask -- a rule of the correspondence test that never fires on them, a limit at equality, a tie of
+rintf, a given pivot index, frame 256 of a batch, a map 16384 wide -- is written by hand in the second half of this file.
 
 Measured with aria_slam_amd/icp_ref.py over the eight seeded perturbations of perturbations() (tests/test_icp_host.py prints
 and asserts them; the bound is twice the measured worst):
@@ -287,3 +289,302 @@ def bound_case():
     N = rng.normal(size=(4, 4, 3))
     N = (N / np.linalg.norm(N, axis=-1, keepdims=True) * math.sqrt(1.4999)).astype(np.float32)
     return cfg, D, M, N, list(IDENTITY), IR.model_rotation(IDENTITY)
+
+
+# ---- the rule table: rule 3, test by test ------------------------------------------------------------------------------------------
+# The rendered scenes above are three planes and a sphere at 1-2 m with unit normals under the default configuration: of the
+# twelve tests of rule 3 they can fail only the depth range (0 = no hit), the projection bounds, Mz > 0, the zero normal and
+# dist_max. The table below is written by hand from powers of two, so that every decision is exact in fp32 and each test is the
+# FIRST to reject some pixel, each inclusive limit is met at equality and one ulp beyond, and rintf meets exact ties.
+RULES = ("depth_low", "depth_high", "qz", "left", "right", "top", "bottom", "model_depth", "normal_zero", "normal_long", "dist", "reach")
+ACCEPTED = len(RULES)
+Census = namedtuple("Census", "code um vm nn ee qq")
+
+
+def rule_values(cfg, D, M, N, Trel, Rm, stride):
+    """Rule 3 of the header restated test by test, in the order the rule states them: Census(code, um, vm, nn, ee, qq), each
+    [Hl, Wl] over the level pixels of `stride`. code is the index into RULES of the first test that rejects the pixel, or
+    ACCEPTED. The arithmetic is that of icp_ref.jacobians; tests/test_icp_rules_host.py holds code == ACCEPTED to its `ok`."""
+    f32 = np.float32
+    H, W = D.shape
+    with np.errstate(all="ignore"):
+        T = np.asarray(Trel, np.float64).astype(f32)
+        fx, fy, cx, cy = (f32(v) for v in cfg.K)
+        inv_fx, inv_fy = f32(1.0) / fx, f32(1.0) / fy
+        uu, vv = np.meshgrid(np.arange(0, W, stride), np.arange(0, H, stride))
+        shape = uu.shape
+        uu, vv = uu.reshape(-1), vv.reshape(-1)
+        d = np.asarray(D, f32)[vv, uu]
+        p = [((uu.astype(f32) - cx) * inv_fx) * d, ((vv.astype(f32) - cy) * inv_fy) * d, d]
+        q = [((T[4 * i] * p[0] + T[4 * i + 1] * p[1]) + T[4 * i + 2] * p[2]) + T[4 * i + 3] for i in range(3)]
+        iz = f32(1.0) / q[2]
+        um, vm = np.rint((fx * q[0]) * iz + cx), np.rint((fy * q[1]) * iz + cy)
+        sides = [um >= f32(0), um <= f32(W - 1), vm >= f32(0), vm <= f32(H - 1)]
+        inside = sides[0] & sides[1] & sides[2] & sides[3]
+        ui, vi = np.where(inside, um, f32(0)).astype(np.int64), np.where(inside, vm, f32(0)).astype(np.int64)
+        Mz, Nw = np.asarray(M, f32)[vi, ui], np.asarray(N, f32)[vi, ui]
+        n = [(Rm[3 * i] * Nw[:, 0] + Rm[3 * i + 1] * Nw[:, 1]) + Rm[3 * i + 2] * Nw[:, 2] for i in range(3)]
+        nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]
+        pm = [((ui.astype(f32) - cx) * inv_fx) * Mz, ((vi.astype(f32) - cy) * inv_fy) * Mz, Mz]
+        e = [q[i] - pm[i] for i in range(3)]
+        ee = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]
+        qq = (q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]
+        tests = [d >= cfg.min_depth, d <= cfg.max_depth, q[2] > f32(0)] + sides + [
+            Mz > f32(0), (Nw[:, 0] != 0) | (Nw[:, 1] != 0) | (Nw[:, 2] != 0), nn <= f32(IR.NORMAL_MAX),
+            ee <= cfg.dist_max * cfg.dist_max, qq <= cfg.reach * cfg.reach]
+        code = np.full(uu.shape, ACCEPTED, np.int64)
+        for k in range(len(tests) - 1, -1, -1):
+            code[~tests[k]] = k
+    return Census(*(a.reshape(shape) for a in (code, um, vm, nn, ee, qq)))
+
+
+def rule_census(cfg, D, M, N, Trel, Rm, stride=1):
+    """Per level pixel the index into RULES of the first rejecting test of rule 3, or ACCEPTED."""
+    return rule_values(cfg, D, M, N, Trel, Rm, stride).code
+
+
+# One hand-written pixel: frame index, live pixel (v, u), the census code it must get, what it is there for ("first": the
+# first rule to reject, "eq": an inclusive limit at equality, "beyond": one ulp past it, "tie": an exact rintf tie,
+# "nonfinite"), and where they matter the rounded position (um, vm; -0.0 is told from 0.0) and the compared quantity
+# (`at`: (field of Census, the exact value it must have)).
+Expect = namedtuple("Expect", "frame v u code kind um vm at")
+# cfg; batch (frames of one shape, T0 unused); trels [n][12], the Trel of each frame for debug_system; expect: the list above.
+RuleGroup = namedtuple("RuleGroup", "name cfg batch trels expect")
+
+RULE_K = (2.0, 2.0, 2.0, 2.0)                                        # p = ((u - 2) / 2, (v - 2) / 2, 1) D: pixel (2, 2) looks along the axis
+RULE_KO = (2.0, 4.0, 0.5, 1.5)
+RULE_CFG = dict(min_depth=0.5, max_depth=4.0, dist_max=1.0, reach=8.0, min_corr=1)
+RZ90 = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+
+
+def _rule_normals(w, h):
+    """A different normal at every model pixel (eighths, so products are exact): a wrong (vm, um) changes J."""
+    u, v = np.meshgrid(np.arange(w), np.arange(h))
+    return np.stack([((3 * u + v) % 5 - 2) / 8.0, ((u + 2 * v) % 7 - 3) / 8.0, -np.ones((h, w))], -1).astype(np.float32)
+
+
+class _RuleFrames:
+    """The frames of one RuleGroup under construction. Every frame starts as a frontal plane at 1 m seen from the model's
+    own pose (every pixel accepted at Trel = identity) and is then edited pixel by pixel."""
+
+    def __init__(self, name, w, h, k, Rm=None):
+        self.name, self.w, self.h, self.k = name, w, h, k
+        self.Tm = ext(np.eye(3) if Rm is None else Rm, np.zeros(3))
+        self.frames, self.trels, self.expect = [], [], []
+
+    def frame(self, name, t=(0.0, 0.0, 0.0), R=None, D=1.0, M=1.0):
+        self.cur = dict(name=name, D=np.full((self.h, self.w), D, np.float32), M=np.full((self.h, self.w), M, np.float32),
+                        N=_rule_normals(self.w, self.h))
+        self.frames.append(self.cur)
+        self.trels.append(list(ext(np.eye(3) if R is None else R, t)))
+        return self
+
+    def px(self, v, u, code, kind, D=None, M=None, N=None, um=None, vm=None, at=None):
+        """Edit the live pixel (v, u) and the model pixel at the same place (where the frames that use M and N project it)
+        and note what must become of the live pixel."""
+        if D is not None:
+            self.cur["D"][v, u] = D
+        if M is not None:
+            self.cur["M"][v, u] = M
+        if N is not None:
+            self.cur["N"][v, u] = N
+        self.expect.append(Expect(len(self.frames) - 1, v, u, RULES.index(code) if code != "accepted" else ACCEPTED, kind, um, vm, at))
+        return self
+
+    def group(self, cfg):
+        fr = [Frame(self.name + "." + f["name"], _ro(f["D"]), _ro(f["M"]), _ro(f["N"]), _ro(self.Tm), _ro(self.Tm), _ro(self.Tm), self.w,
+                    self.h, self.k) for f in self.frames]
+        return RuleGroup(self.name, cfg, Batch(fr, None, self.w, self.h, self.k), self.trels, tuple(self.expect))
+
+
+def rule_cases():
+    """The rule table: two RuleGroups, `even` (8 x 8) and `odd` (7 x 5, other intrinsics, Rm a quarter turn about z)."""
+    def build():
+        f32, nan, inf = np.float32, np.nan, np.inf
+        up, down = (lambda x: np.nextafter(f32(x), f32(inf))), (lambda x: np.nextafter(f32(x), f32(-inf)))
+        g = _RuleFrames("even", 8, 8, RULE_K)
+        # live depth: the inclusive range at equality and one ulp beyond, and everything that is no depth. The hand-written
+        # pixels sit on even rows and columns where they can, so that the level of stride 2 keeps them
+        g.frame("depth")
+        g.px(0, 0, "accepted", "eq", D=0.5, M=0.5).px(0, 2, "depth_low", "beyond", D=down(0.5), M=0.5)
+        g.px(4, 2, "accepted", "eq", D=4.0, M=4.0).px(4, 4, "depth_high", "beyond", D=up(4.0), M=4.0)
+        for u, (d, code) in enumerate(((nan, "depth_low"), (inf, "depth_high"), (-inf, "depth_low"), (-1.0, "depth_low"),
+                                       (1e-40, "depth_low"), (0.0, "depth_low"), (-0.0, "depth_low"))):
+            g.px(6, u, code, "nonfinite", D=d)
+        g.px(5, 7, "accepted", "eq", um=7.0, vm=5.0).px(7, 5, "accepted", "eq", um=5.0, vm=7.0)       # um == W - 1, vm == H - 1
+        g.px(5, 0, "accepted", "eq", um=0.0, vm=5.0).px(0, 5, "accepted", "eq", um=5.0, vm=0.0)
+        # the model: depth and normal. (2, 2) and (2, 4) are near enough to the axis to be accepted once Mz > 0 is dropped or
+        # made inclusive; at (2, 0) vm == cy, so pm_y = 0 * Inf and e.e is NaN, where (0, 4) has e.e = Inf
+        g.frame("model")
+        g.px(0, 0, "model_depth", "nonfinite", M=nan).px(0, 2, "model_depth", "first", M=-1.0).px(0, 4, "dist", "nonfinite", M=inf)
+        g.px(0, 6, "dist", "first", M=1e-40).px(0, 1, "model_depth", "first", M=-0.0)
+        g.px(2, 2, "model_depth", "first", D=0.5, M=-0.25).px(2, 4, "model_depth", "first", D=0.5, M=0.0)
+        g.px(2, 0, "dist", "nonfinite", M=inf)
+        g.px(4, 0, "normal_zero", "first", N=(0.0, 0.0, 0.0)).px(4, 2, "normal_zero", "first", N=(-0.0, -0.0, -0.0))
+        g.px(4, 4, "accepted", "eq", N=(1.0, 0.5, 0.5), at=("nn", f32(1.5)))
+        g.px(4, 6, "normal_long", "beyond", N=(1.0, 0.5, 0.5 + 2.0 ** -23), at=("nn", up(1.5)))
+        g.px(6, 0, "normal_long", "nonfinite", N=(nan, 0.0, -1.0)).px(6, 2, "normal_long", "nonfinite", N=(0.0, nan, 0.0))
+        g.px(6, 4, "normal_long", "first", N=(0.0, 0.0, 2.0)).px(6, 6, "normal_long", "nonfinite", N=(inf, 0.0, 0.0))
+        # dist_max: e = (0, 0, 1) and e = (2^-12, 2^-12, 1)
+        g.frame("dist").px(2, 2, "accepted", "eq", D=2.0, at=("ee", f32(1.0)))
+        g.frame("dist_beyond", t=(2.0 ** -12, 2.0 ** -12, 0.0)).px(2, 2, "dist", "beyond", D=2.0, at=("ee", up(1.0)))
+        # reach: q = (0, 0, 8) and q = (2^-9, 2^-9, 8); the even pixels around (2, 2) have e = 0 and are rejected by reach first
+        g.frame("reach", t=(0.0, 0.0, 4.0), D=4.0, M=8.0).px(2, 2, "accepted", "eq", at=("qq", f32(64.0)))
+        g.px(2, 4, "reach", "first").px(4, 2, "reach", "first")
+        g.frame("reach_beyond", t=(2.0 ** -9, 2.0 ** -9, 4.0), D=4.0, M=8.0).px(2, 2, "reach", "beyond", at=("qq", up(64.0)))
+        # q_z: 0 for the plane at 1 m, negative at (2, 2) with a model that would accept it, positive where D = 2
+        g.frame("qz", t=(0.0, 0.0, -1.0)).px(0, 0, "qz", "first").px(2, 2, "qz", "first", D=0.5, M=0.25)
+        g.px(2, 4, "accepted", "first", D=2.0, um=6.0, vm=2.0).px(4, 4, "accepted", "first", D=2.0, um=6.0, vm=6.0)
+        # the four sides
+        g.frame("sides_lt", t=(-1.0, -1.0, 0.0)).px(0, 0, "left", "first", um=-2.0).px(4, 1, "left", "beyond", um=-1.0)
+        g.px(0, 2, "top", "first", um=0.0, vm=-2.0).px(1, 4, "top", "beyond", vm=-1.0).px(2, 2, "accepted", "eq", um=0.0, vm=0.0)
+        g.frame("sides_rb", t=(1.0, 1.0, 0.0)).px(0, 7, "right", "first", um=9.0).px(3, 6, "right", "beyond", um=8.0)
+        g.px(7, 0, "bottom", "first", vm=9.0).px(6, 3, "bottom", "beyond", vm=8.0).px(5, 5, "accepted", "eq", um=7.0, vm=7.0)
+        # ties: um = u + 0.5 and vm = v + 0.5 go to the even neighbour, downwards from an even u and upwards from an odd one;
+        # 7.5 = W - 0.5 goes up to W = 8 and is outside
+        g.frame("ties", t=(0.25, 0.25, 0.0))
+        for i in range(7):
+            g.px(i, 6 - i, "accepted", "tie", um=float(6 - i + ((6 - i) & 1)), vm=float(i + (i & 1)))
+        g.px(2, 7, "right", "tie", um=8.0).px(7, 2, "bottom", "tie", vm=8.0)
+        # um = u - 0.5: -0.5 rounds to -0.0, which is >= 0: column 0 and row 0 are accepted
+        g.frame("ties_neg", t=(-0.25, -0.25, 0.0)).px(0, 0, "accepted", "tie", um=-0.0, vm=-0.0)
+        g.px(3, 0, "accepted", "tie", um=-0.0, vm=2.0).px(0, 3, "accepted", "tie", um=2.0, vm=-0.0).px(1, 2, "accepted", "tie", um=2.0, vm=0.0)
+        # a positive subnormal q_z: iz overflows, um is -Inf, NaN (0 * Inf) or +Inf
+        g.frame("tiny_qz", R=np.diag([1.0, 1.0, 2.0 ** -140])).px(4, 0, "left", "nonfinite", um=-inf)
+        g.px(4, 2, "left", "nonfinite").px(4, 6, "right", "nonfinite", um=inf)
+        even = g.group(config(RULE_K, **RULE_CFG))
+        # odd width and height: W - 0.5 = 6.5 and H - 0.5 = 4.5 go DOWN to W - 1 and H - 1 and are inside
+        g = _RuleFrames("odd", 7, 5, RULE_KO, Rm=RZ90)
+        g.frame("plain").px(4, 6, "accepted", "eq", um=6.0, vm=4.0).px(0, 0, "accepted", "eq", um=0.0, vm=0.0)
+        g.frame("ties", t=(0.25, 0.125, 0.0)).px(4, 6, "accepted", "tie", um=6.0, vm=4.0).px(3, 5, "accepted", "tie", um=6.0, vm=4.0)
+        g.px(0, 0, "accepted", "tie", um=0.0, vm=0.0).px(1, 1, "accepted", "tie", um=2.0, vm=2.0)
+        g.frame("ties_neg", t=(-0.25, -0.125, 0.0)).px(0, 0, "accepted", "tie", um=-0.0, vm=-0.0).px(4, 6, "accepted", "tie", um=6.0, vm=4.0)
+        g.px(2, 1, "accepted", "tie", um=0.0, vm=2.0)
+        return even, g.group(config(RULE_KO, **RULE_CFG))
+    return _cached("rule_cases", build)
+
+
+def rule_systems(group, stride):
+    """The 29 integers of every frame of a RuleGroup on the level of `stride`: int64 [n, 29]."""
+    return _cached(("rule_systems", group.name, stride), lambda: _ro(np.stack([
+        IR.system(group.cfg, f.D, f.M, f.N, trel, IR.model_rotation(f.Tm), stride) for f, trel in zip(group.batch.frames, group.trels)])))
+
+
+# ---- the solve table: rule 5 through track ------------------------------------------------------------------------------------
+SOLVE_W = SOLVE_H = 16
+SOLVE_K = (16.0, 16.0, 7.5, 7.5)
+SOLVE_T0 = ext(rodrigues(np.array([0.002, -0.001, 0.003])), [0.003, -0.002, 0.001])
+SolveCase = namedtuple("SolveCase", "name frame cfg")
+
+
+def solve_frame(kind, T0=None, D=None):
+    """A 16 x 16 frame whose 256 pixels are all accepted at Trel = identity: a plane at 1 m with a depth pattern in 1/256 m, the
+    live map 1/64 m off it in a pattern of three, and a normal field `kind`: `bumpy` has full rank; `least0` too, with normals that
+    nearly pass through the x axis, so that pivot 0 is the least of the six (0.25 for 2.4 .. 256) and is alone in deciding
+    whether the frame is lost; `col1` .. `col5` make the named column of J zero at every pixel, so that pivot is exactly 0
+    while those before it are positive."""
+    u, v = np.meshgrid(np.arange(SOLVE_W), np.arange(SOLVE_H))
+    M = (1.0 + ((u * 7 + v * 13) % 11 - 5) / 256.0).astype(np.float32)
+    live = (M + ((u + v) % 3 - 1) / 64.0).astype(np.float32) if D is None else np.asarray(D, np.float32)
+    a, b, c = ((3 * u + v) % 5 - 2) / 8.0, ((u + 2 * v) % 7 - 3) / 8.0, ((2 * u + 3 * v) % 5 + 4) / 8.0
+    z, one = np.zeros(u.shape), np.ones(u.shape)
+    N = dict(bumpy=(a, b, -one), least0=(a, -(v - 7.5) / 16.0 + b / 8.0, -one), col1=(z, one, z), col2=(z, z, -one), col3=(z, b, -c), col4=(a, z, -c), col5=(c, b, z))[kind]
+    T0 = IDENTITY if T0 is None else T0
+    return Frame("solve." + kind, _ro(live), _ro(M), _ro(np.stack(N, -1).astype(np.float32)), IDENTITY, _ro(T0), IDENTITY, SOLVE_W, SOLVE_H,
+                 SOLVE_K)
+
+
+def first_step(frame, **cfg_kw):
+    """The Step of the restatement's first accumulation."""
+    trace = []
+    IR.track(config(frame.K, **cfg_kw), frame.D, frame.M, frame.N, frame.Tm, frame.T0, trace)
+    return trace[0][2]
+
+
+def solve_cases():
+    """The solve table, a tuple of SolveCase. The first accumulation of `pivot<j>...` is lost at pivot index j."""
+    def build():
+        one = dict(strides=(1,), iterations=(3,))
+        bumpy = solve_frame("bumpy")
+        st = first_step(bumpy, min_pivot=0.0, **one)
+        assert st.count == 256 and not st.lost
+        piv = st.pivots
+        out = [SolveCase("pivot%d_zero" % j, solve_frame("col%d" % j), config(SOLVE_K, min_pivot=0.0, **one)) for j in range(1, 6)]
+        # s == thr: 256 correspondences, so thr = (pivot / 256) * 256.0 is the pivot itself and `s > thr` is false. Pivot 0 of
+        # `least0` is the least, so one ulp less leaves the frame valid: the two cases differ in every output
+        single = dict(strides=(1,), iterations=(1,))
+        least0 = solve_frame("least0")
+        st0 = first_step(least0, min_pivot=0.0, **single)
+        assert st0.count == 256 and st0.pivots[0] == min(st0.pivots)
+        out.append(SolveCase("pivot0_equal", least0, config(SOLVE_K, min_pivot=st0.pivots[0] / 256.0, **single)))
+        out.append(SolveCase("pivot0_below", least0, config(SOLVE_K, min_pivot=float(np.nextafter(st0.pivots[0] / 256.0, 0.0)), **single)))
+        # a pivot that is not zero, lost between two others: the threshold is the geometric mean of that pivot and the least before it
+        for j in range(1, 6):
+            if piv[j] < min(piv[:j]):
+                out.append(SolveCase("pivot%d_between" % j, bumpy, config(SOLVE_K, min_pivot=math.sqrt(piv[j] * min(piv[:j])) / 256.0, **one)))
+        out.append(SolveCase("min_corr_equal", bumpy, config(SOLVE_K, min_corr=256, **single)))
+        out.append(SolveCase("min_corr_over", bumpy, config(SOLVE_K, min_corr=257, **single)))
+        D = np.zeros((SOLVE_H, SOLVE_W), np.float32)
+        D[::2, 1::2] = np.nan
+        D[1::2, ::2] = np.nan
+        out.append(SolveCase("blind", solve_frame("bumpy", SOLVE_T0, D), config(SOLVE_K)))
+        moved = solve_frame("bumpy", SOLVE_T0)
+        out.append(SolveCase("zero_thresholds", moved, config(SOLVE_K, min_pivot=0.0, eps=0.0, strides=(2, 1), iterations=(0, 64))))
+        out.append(SolveCase("skipped_level", moved, config(SOLVE_K, strides=(2, 1), iterations=(0, 64))))
+        return tuple(out)
+    return _cached("solve_cases", build)
+
+
+def solve_ref(case):
+    """(Track, trace) of the restatement on a SolveCase."""
+    def build():
+        f, trace = case.frame, []
+        return IR.track(case.cfg, f.D, f.M, f.N, f.Tm, f.T0, trace), trace
+    return _cached(("solve_ref", case.name), build)
+
+
+# ---- a batch of 300 and the strips ---------------------------------------------------------------------------------------------
+BIG_N, BIG_NAN = 300, 270
+BIG_MASKED = (5, 254, 255, 257, 280, 299)                             # zeros on both sides of index 256, the second workgroup's first lane
+
+
+def batch300():
+    """300 guesses for one 16 x 12 frame of the rendered scene: (cfg, Batch). Every tenth guess is half a metre off and loses the
+    frame, frame BIG_NAN has a NaN in T0, the frames of BIG_MASKED are masked."""
+    def build():
+        w, h, k = 16, 12, (6.0, 6.0, 7.7, 5.6)
+        cfg = config(k, min_corr=24, strides=(2, 1), iterations=(2, 3))
+        M, N = analytic_model(w, h, k)
+        D = _ro(render(perturbations(0.002, 0.004)[0], w, h, k)[0])
+        rng = np.random.default_rng(17)
+        frames = []
+        for i in range(BIG_N):
+            wv, tv = rng.normal(size=3), rng.normal(size=3)
+            T0 = ext(rodrigues(wv * (0.0002 * (1 + i % 30) / np.linalg.norm(wv))), tv * ((0.5 if i % 10 == 9 else 0.0004 * (1 + i % 23)) / np.linalg.norm(tv)))
+            if i == BIG_NAN:
+                T0[7] = np.nan
+            frames.append(Frame("big%d" % i, D, M, N, IDENTITY, _ro(T0), IDENTITY, w, h, k))
+        mask = np.ones(BIG_N, np.uint8)
+        mask[list(BIG_MASKED)] = 0
+        return cfg, Batch(frames, _ro(mask), w, h, k)
+    return _cached("batch300", build)
+
+
+STRIP = 16384
+
+
+def strip_case(w, h):
+    """A strip of 16384 x 1 or 1 x 16384, the size limit of the stage: a frontal plane at 1.5 m with a seeded ripple of 1 cm in
+    both maps and normals a little off the axis; (cfg, Frame, Trel). Trel moves the projection 1.6 pixels along the strip."""
+    def build():
+        rng = np.random.default_rng(23)
+        k = (8192.0, 8192.0, (w - 1) / 2.0, (h - 1) / 2.0)
+        M = (1.5 + rng.uniform(-0.01, 0.01, (h, w))).astype(np.float32)
+        D = (1.5 + rng.uniform(-0.01, 0.01, (h, w))).astype(np.float32)
+        N = np.concatenate([rng.uniform(-0.2, 0.2, (h, w, 2)), -np.ones((h, w, 1))], -1).astype(np.float32)
+        along, across = (3e-4, 2e-5) if w > h else (2e-5, 3e-4)
+        T0 = ext(np.eye(3), [-along, -across, -1e-3])                  # a rotation of 1e-4 would move a pixel off a strip one pixel wide
+        f = Frame("strip%dx%d" % (w, h), _ro(D), _ro(M), _ro(N), IDENTITY, _ro(T0), IDENTITY, w, h, k)
+        # a strip leaves the solve nearly singular: min_pivot = 0 lets the first step through, and the next accumulations lose the frame
+        return config(k, min_pivot=0.0, strides=(1,), iterations=(3,)), f, list(ext(np.eye(3), [along, across, 1e-3]))
+    return _cached(("strip", w, h), build)

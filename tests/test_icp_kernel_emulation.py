@@ -20,7 +20,17 @@ Mutants, each put into the pasted text by hand and run once against this file (n
   * a partial-tile lane not masked (u < m.W dropped): passes every case of the table -- the pixel just outside a dense map
     projects outside it, and the guard bytes of `pitched` read as 1.5e16 m, no valid depth -- and fails `edge` at strides
     2 and 1 (2623 correspondences for 2537 at stride 1; at stride 4 the 16 level columns are one whole tile), which is
-    why test_partial_tile_lanes_are_masked exists."""
+    why test_partial_tile_lanes_are_masked exists.
+A second round of mutants, for the hand-written tables of icp_cases (rule_cases, solve_cases, batch300); none of them is
+seen by any case above:
+  * roundf for rintf: fails the four `ties` frames of the rule table;
+  * (n.n) < 1.5f, the test dropped, or written as `> 1.5f rejects` (a NaN passes): fail even.model;
+  * e.e < dist2 fails even.dist; written as `> dist2 rejects` it fails even.model (e.e is NaN under a model depth of +Inf
+    on the row of cy); q.q < reach2 fails even.reach; Mz >= 0 fails even.model;
+  * `s >= thr` in icp_cholesky fails pivot0_equal and pivot5_zero; `count <= min_corr` fails min_corr_equal;
+  * k_icp_prepare stopping at lane 256 fails batch300.
+  Not seen by anything, because a later test of rule 3 rejects what these let through: the depth range, q_z > 0 or the
+  reach test letting a NaN pass, q_z >= 0, um > -1 for um >= 0, and the zero normal written as N == 0 on all three."""
 import ctypes as C
 import os
 import subprocess
@@ -182,3 +192,46 @@ def test_track_kernel_source_batch_of_five_masked_and_nonfinite(emu):
     assert err == 1 and want[2]
     assert recs.tobytes() == want[1].tobytes() and poses.tobytes() == want[0].tobytes()
     assert recs[1:2].tobytes() == bytes(32) and poses[1].tobytes() == IC.guarded_outputs(1)[0].tobytes()
+
+
+@pytest.mark.parametrize("plain", (0, 1))
+@pytest.mark.parametrize("group", (0, 1), ids=("even", "odd"))
+def test_rule_table_kernel_source_is_the_restatements_integers(emu, group, plain):
+    """The hand-written pixels of icp_cases.rule_cases(): every frame of a group in one call, each at its own Trel, dense and
+    with valid depths in the live map's padding, at strides 1 and 2."""
+    g = IC.rule_cases()[group]
+    for padded in (False, True):
+        lay = IC.layout(g.batch.W, g.batch.H, padded)
+        for stride in (1, 2):
+            got, _ = system(emu, g.cfg, g.batch, lay, g.trels, stride, plain, live_fill=1.0 if padded else None)
+            want = IC.rule_systems(g, stride)
+            bad = [g.batch.frames[i].name for i in range(len(want)) if (got[i] != want[i]).any()]
+            assert not bad, (padded, stride, bad)
+
+
+@pytest.mark.parametrize("plain", (0, 1))
+def test_solve_table_kernel_source_is_bitwise_the_restatement(emu, plain):
+    for c in IC.solve_cases():
+        b = IC.Batch([c.frame], None, c.frame.W, c.frame.H, c.frame.K)
+        poses, recs, err, _ = track(emu, c.cfg, b, IC.layout(b.W, b.H), plain)
+        want = IC.solve_ref(c)[0]
+        assert err == 0 and recs[0].tobytes() == want.result.tobytes(), (c.name, recs[0], want.result)
+        assert poses[0].tobytes() == want.T.tobytes(), c.name
+
+
+def test_batch_of_300_kernel_source_second_block_of_the_per_frame_kernels(emu):
+    """Frames 256 .. 299 belong to the second block of k_icp_prepare and k_icp_solve; masked, lost and non-finite frames on both
+    sides of it."""
+    cfg, b = IC.batch300()
+    poses, recs, err, _ = track(emu, cfg, b, IC.layout(b.W, b.H))
+    want = IC.expected(b, cfg)
+    assert err == 1 and want[2]
+    assert recs.tobytes() == want[1].tobytes() and poses.tobytes() == want[0].tobytes()
+
+
+def test_bound_case_kernel_source_is_the_restatements_integers(emu):
+    cfg, D, M, N, trel, Rm = IC.bound_case()
+    f = IC.Frame("bound", D, M, N, IC.IDENTITY, IC.IDENTITY, IC.IDENTITY, 4, 4, cfg.K)
+    got, _ = system(emu, cfg, IC.Batch([f], None, 4, 4, cfg.K), IC.layout(4, 4), [trel], 1)
+    want = IR.system(cfg, D, M, N, trel, Rm, 1)
+    assert (got[0] == want).all() and np.abs(want[:21]).max() > 2.0 ** 37
