@@ -1,5 +1,6 @@
 """The kernel source of aria_slam_amd/csrc/proj_search.hip, compiled for the HOST and held bitwise to the restatement
-(aria_slam_amd/proj_ref.py) on the case table tests/test_gpu_proj.py runs on the device.
+(aria_slam_amd/proj_ref.py) on the case table tests/test_gpu_proj.py runs on the device, and on every limit and size of
+edge_groups() (tests/test_gpu_proj_edges.py) under each group's own configuration.
 
 Three pieces of the file's text are pasted between tests/cpp/proj_kernel_emu_head.inc (a shim: the lanes of a workgroup one after
 the other) and proj_kernel_emu_tail.inc and compiled with the clang++ that hipcc drives: the plain per-landmark arithmetic between
@@ -91,6 +92,23 @@ def test_plain_arithmetic_and_resolve_are_bitwise_the_restatement(emu, f):
                               t["width"], t["height"])[0]
     assert outside == 0
     assert got.tobytes() == want.tobytes() == PC.expected(f, t["landmarks"])[0].tobytes(), f["name"]
+
+
+def _edge_frames():
+    return [pytest.param(g, f, id="%s / %s" % (g["name"], f["name"])) for g in PC.edge_groups() for f in g["frames"] if f["valid"]]
+
+
+@pytest.mark.parametrize("g,f", _edge_frames())
+def test_plain_arithmetic_on_every_limit_and_size(emu, g, f):
+    """Every valid frame of edge_groups() under its group's configuration, image size, kp_stride and land_cap. claim_bits passes
+    its whole range of 2^20 landmarks (the dead ones return at the first test, so the range costs a fraction of a second).
+    outside == 0 is the check that one pixel of slack around the window suffices: for the differences of the fp32 group that
+    round ONTO r, and for the radius_px = 1024 windows, whose edges lie a thousand pixels outside the image."""
+    kp, desc = PC.edge_frame_arrays(g, f)
+    got, outside = _search(emu, f["pose"], kp, desc, f["n"], g["kp_stride"], g["width"], g["height"], g["landmarks"], f["first"], f["count"],
+                           g["land_cap"], g["cfg"])
+    assert outside == 0
+    assert got.tobytes() == PC.edge_restatement(g, f)[0].tobytes() == PC.edge_expected(g, f)[0].tobytes(), (g["name"], f["name"])
 
 
 def test_crowded_random_scene_in_large_coordinates(emu):
