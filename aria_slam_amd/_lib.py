@@ -116,6 +116,9 @@ EXPORTS = [
     "aria_bow_train_device", "aria_bow_train", "aria_bow_set_vocabulary", "aria_bow_get_vocabulary", "aria_bow_save", "aria_bow_load",
     "aria_bow_transform_batch_device", "aria_bow_add_batch_device", "aria_bow_add", "aria_bow_add_device", "aria_bow_size",
     "aria_bow_info", "aria_bow_query_batch_device", "aria_bow_query", "aria_bow_query_device",
+    # loop alignment (batched Sim(3) RANSAC of the landmarks two keyframes own, join with the point map), additive to ABI 4
+    "aria_sim3_default_config", "aria_sim3_create", "aria_sim3_destroy", "aria_sim3_stream", "aria_sim3_check",
+    "aria_sim3_estimate", "aria_sim3_estimate_batch_device", "aria_sim3_debug_hypotheses", "aria_sim3_associate_batch_device",
 ]
 
 
@@ -152,6 +155,20 @@ class PnpConfig(C.Structure):
 PNP_CORR_DTYPE = np.dtype([("X", "<f8", (3,)), ("u", "<f4"), ("v", "<f4")])
 PNP_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("rms_px", "<f8"), ("n_corr", "<i4"), ("n_inliers", "<i4"),
                              ("best_hypothesis", "<i4"), ("iterations", "<i4"), ("refined", "<i4"), ("valid", "<i4")])
+
+
+class Sim3Config(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("stream", C.c_void_p), ("hypotheses", C.c_int),
+                ("refine_iters", C.c_int), ("fix_scale", C.c_int), ("reserved", C.c_int), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("threshold_px", C.c_double), ("min_scale", C.c_double),
+                ("max_scale", C.c_double), ("seed", C.c_uint64)]
+
+
+# aria_sim3_corr (64 bytes) and aria_sim3_result (136 bytes)
+SIM3_CORR_DTYPE = np.dtype([("X1", "<f8", (3,)), ("X2", "<f8", (3,)), ("u1", "<f4"), ("v1", "<f4"), ("u2", "<f4"), ("v2", "<f4")])
+SIM3_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("s", "<f8"), ("rms_px", "<f8"), ("n_corr", "<i4"),
+                              ("n_inliers", "<i4"), ("best_hypothesis", "<i4"), ("iterations", "<i4"), ("refined", "<i4"),
+                              ("valid", "<i4")])
 
 
 class BaConfig(C.Structure):
@@ -621,6 +638,8 @@ def load_library():
         _bind_proj(L)
     if hasattr(L, "aria_bow_create"):
         _bind_bow(L)
+    if hasattr(L, "aria_sim3_create"):
+        _bind_sim3(L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
@@ -846,6 +865,15 @@ def _bind_ba(L):
     L.aria_ba_optimize_batch_device.argtypes = [p, p, p, p, p, p, p, p, p, i, i, i, i, i, p, p]
     L.aria_ba_debug_linearize.argtypes = [p, p, p, i, p, p, i, p, i, d, C.POINTER(d), C.POINTER(i), p, p, p, p]
     L.aria_ba_window_from_chain_device.argtypes = [p, p, p, p, i, i, i, p, p, p, p, C.c_int64, p, p, i, i, i, i, p, p, p, p, p]
+
+
+def _bind_sim3(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "sim3")
+    L.aria_sim3_estimate.argtypes = [p, p, i, i, p, p]
+    L.aria_sim3_estimate_batch_device.argtypes = [p, p, p, i, i, i, p, p]
+    L.aria_sim3_debug_hypotheses.argtypes = [p, p, i, i, p, p, p, p, p]
+    L.aria_sim3_associate_batch_device.argtypes = [p, p, p, p, i, i, p, p, p, p, p, p, i64, p, p, i, i, p, p, p]
 
 
 def _bind_pnp(L):

@@ -1,5 +1,5 @@
-// Host side of what the twenty stage handles (aria_pose_t, aria_fund_t, aria_map_t, aria_graph_t, aria_fuse_t, aria_eval_t,
-// aria_det_t, aria_stereo_t, aria_rect_t, aria_dense_t, aria_tsdf_t, aria_nav_t, aria_alert_t, aria_pnp_t, aria_ba_t, aria_ray_t, aria_icp_t, aria_mesh_t, aria_proj_t, aria_bow_t) share: the lifecycle of device, stream and deferred-error words, grow-only device buffers, and
+// Host side of what the twenty-one stage handles (aria_pose_t, aria_fund_t, aria_map_t, aria_graph_t, aria_fuse_t, aria_eval_t,
+// aria_det_t, aria_stereo_t, aria_rect_t, aria_dense_t, aria_tsdf_t, aria_nav_t, aria_alert_t, aria_pnp_t, aria_ba_t, aria_ray_t, aria_icp_t, aria_mesh_t, aria_proj_t, aria_bow_t, aria_sim3_t) share: the lifecycle of device, stream and deferred-error words, grow-only device buffers, and
 // the single-pair staging of the blocking host forms that take a match list. Header-only; not part of the public interface.
 #pragma once
 #include <algorithm>

@@ -47,6 +47,9 @@ public:
                     bool previous_is_query, const std::optional<TwoViewPose>& two_view, const std::uint8_t* previous_image = nullptr,
                     int width = 0, int height = 0);
     const std::array<double, 16>& pose() const { return pose_; }   // world to camera of the last frame, 4x4 row-major
+    // Pair id of the map points whose view 2 is the last frame (-1: it owns none). With pose(), read after a step, this is what
+    // the loop alignment needs to know about a keyframe (aria_hip/HipSim3Aligner.hpp, KeyframeInMap).
+    int anchorPair() const { return anchor_pair_; }
     HipMapper& mapper() { return mapper_; }
     // Every later step is also recorded in `builder` (nullptr: none): the frames, their poses, and which keypoint of the new
     // frame continues which point, for the windows of HipBundleAdjuster. The builder must outlive the tracking.

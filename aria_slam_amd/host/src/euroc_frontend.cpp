@@ -59,6 +59,14 @@
 // The loop step then runs over the merged stream as in the sharded mode, keeping the keypoints of the keyframes the
 // database holds. Keyframes are the default run's; the loops are a subset of its. Without the flag nothing changes.
 //
+// --loop-align sim3 [--loop-align-out FILE] (needs --loop, --loop-verify reference and --track-map; unsharded): after the
+// reference verification has accepted a candidate, the landmarks the two keyframes own in the tracker's map are joined through
+// the candidate's match list and aligned (aria_hip/HipSim3Aligner.hpp, makeSim3Verifier). A valid alignment with at least 20
+// inliers (ORB-SLAM's constant, untuned) replaces the candidate's unit-length relative pose by [R t] in map units, which is
+// what --optimize then hands the pose graph; otherwise the candidate stays as it was. s is only reported. FILE gets one line
+// per accepted loop: query id, match id, s, n_corr, n_inliers, rms_px, replaced (0 or 1); one line "loop align sim3
+// candidates C replaced R" is printed. Off by default; without the flag every output is what it was, byte for byte.
+//
 // --bundle FILE3 [--bundle-window N] (needs --track-map): local bundle adjustment of the tracked trajectory, post hoc as
 // --optimize is (aria_hip/HipBundleAdjuster.hpp; the reference names the step, README.md:1162, and has no code for it). The
 // tracker's steps are recorded in a WindowBuilder; windows of N frames (default 10, at most 16) with stride N - 2 are adjusted
@@ -191,6 +199,7 @@
 #include "aria_hip/HipPlaceIndex.hpp"
 #include "aria_hip/HipMapper.hpp"
 #include "aria_hip/HipBundleAdjuster.hpp"
+#include "aria_hip/HipSim3Aligner.hpp"
 #include "aria_hip/MapTracker.hpp"
 #include "aria_hip/HipObstacleAlerter.hpp"
 #include "aria_hip/HipPathPlanner.hpp"
@@ -277,6 +286,7 @@ int main(int argc, char** argv) {
     int loop_bow = 0, loop_bow_top = 10, loop_capacity = 500;
     bool loop_bow_given = false;
     std::string loop_bow_vocab;
+    std::string loop_align, loop_align_out;
     std::string csv, pose_file, map_file, track_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
@@ -305,6 +315,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--loop-bow-top") && i + 1 < argc) { loop_bow_top = std::atoi(argv[++i]); loop_bow_given = true; }
         else if (!std::strcmp(argv[i], "--loop-bow-vocab") && i + 1 < argc) { loop_bow_vocab = argv[++i]; loop_bow_given = true; }
         else if (!std::strcmp(argv[i], "--loop-capacity") && i + 1 < argc) loop_capacity = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--loop-align") && i + 1 < argc) loop_align = argv[++i];
+        else if (!std::strcmp(argv[i], "--loop-align-out") && i + 1 < argc) loop_align_out = argv[++i];
         else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
         else if (!std::strcmp(argv[i], "--fuse") && i + 1 < argc) fuse_file = argv[++i];
         else if (!std::strcmp(argv[i], "--eval") && i + 1 < argc) eval_file = argv[++i];
@@ -333,6 +345,12 @@ int main(int argc, char** argv) {
         return -1;
     }
     const bool verify_reference = !loop_verify.empty();
+    if ((!loop_align.empty() || !loop_align_out.empty()) && (loop_align != "sim3" || !verify_reference || track_file.empty() || shards > 1 || batch > 0)) {
+        std::fprintf(stderr, "--loop-align sim3 [--loop-align-out FILE] needs --loop, --loop-verify reference and --track-map, unsharded "
+                             "(the only alignment mode is 'sim3')\n");
+        return 1;
+    }
+    const bool align_sim3 = !loop_align.empty();
     if (loop_bow_given && (!loop || loop_bow < 1 || loop_bow > 4096 || loop_bow_top < 1 || loop_bow_top > 32)) {
         std::fprintf(stderr, "--loop-bow V (1..4096), --loop-bow-top K (1..32) and --loop-bow-vocab need --loop\n");
         return 1;
@@ -489,6 +507,10 @@ int main(int argc, char** argv) {
     std::vector<std::array<double, 16>> track_traj(track_file.empty() ? 0 : N);
     long long track_steps[5] = {0, 0, 0, 0, 0};   // indexed by TrackStep::Source
     std::size_t track_points = 0;
+    // --loop-align sim3: the anchor pair of every tracked frame, and the tracker (its map) kept for the loop step
+    std::vector<int> track_anchor(align_sim3 ? N : 0, -1);
+    std::unique_ptr<adapters::hip::MapTracker> kept_tracker;
+    adapters::hip::PoseIntrinsics track_K;
     // --bundle: what the tracker did, step by step, and the sequence frame its first frame is
     adapters::hip::WindowBuilder bundle_builder;
     adapters::hip::PoseIntrinsics bundle_K;
@@ -594,6 +616,7 @@ int main(int argc, char** argv) {
                 mc.device = fc.hip_device;
                 if (rectifier) mc.K = new_K;
                 tracker = std::make_unique<adapters::hip::MapTracker>(mc, 10, 1024, pnp_solver);
+                track_K = mc.K;
                 if (local_map > 0) tracker->setLocalMap(local_map, (float)local_radius);
                 if (!bundle_file.empty()) {
                     tracker->setWindowBuilder(&bundle_builder);
@@ -746,6 +769,7 @@ int main(int argc, char** argv) {
                     if (r.previous && bundle_first < 0) bundle_first = (long long)i - 1;
                     if (r.previous) track_steps[tracker->track(*r.previous, *r.frame, r.matches, fc.frontend.legacy_order, r.pose).source]++;
                     track_traj[i] = tracker->pose();
+                    if (align_sim3) track_anchor[i] = tracker->anchorPair();
                 }
                 if (mapper) { prev_gray.swap(gray); pw = fw; ph = fh; }
                 FrameRecord& o = rec[i];
@@ -770,6 +794,7 @@ int main(int argc, char** argv) {
                 map_points = mapper->size();
             }
             if (tracker) track_points = tracker->mapper().size();
+            if (tracker && align_sim3) kept_tracker = std::move(tracker);
             if (dense_tracker) {
                 dense_tracked = dense_tracker->framesTracked();
                 dense_lost = dense_tracker->framesLost();
@@ -890,12 +915,41 @@ int main(int argc, char** argv) {
         std::unique_ptr<adapters::hip::HipFundamentalEstimator> fund;
         std::unique_ptr<adapters::hip::HipPoseEstimator> pose;
         std::deque<std::size_t> held;                                  // keyframes in the database, oldest first
+        std::unique_ptr<adapters::hip::HipSim3Aligner> aligner;        // --loop-align sim3
+        std::ofstream align_out;
+        long long align_candidates = 0, align_replaced = 0;
         if (verify_reference) {
             fund = std::make_unique<adapters::hip::HipFundamentalEstimator>();
             pose = std::make_unique<adapters::hip::HipPoseEstimator>(adapters::hip::referenceLoopIntrinsics());
-            ld.setVerifier(adapters::hip::makeReferenceVerifier(*fund, *pose, fc.loop_min_matches, [&](std::uint64_t id) {
-                return id < N && rec[(size_t)id].frame ? rec[(size_t)id].frame.get() : nullptr;
-            }));
+            adapters::hip::HipLoopDetector::Verifier reference =
+                adapters::hip::makeReferenceVerifier(*fund, *pose, fc.loop_min_matches, [&](std::uint64_t id) {
+                    return id < N && rec[(size_t)id].frame ? rec[(size_t)id].frame.get() : nullptr;
+                });
+            if (align_sim3 && kept_tracker) {
+                // after the reference verification has accepted a candidate: the two keyframes' landmarks, joined through its
+                // match list and aligned; a valid alignment with >= 20 inliers replaces the unit-length edge by [R t] in map units
+                aligner = std::make_unique<adapters::hip::HipSim3Aligner>(track_K);
+                if (!loop_align_out.empty()) { align_out.open(loop_align_out); align_out << std::setprecision(17); }
+                auto lookup = [&](std::uint64_t id) -> std::optional<adapters::hip::KeyframeInMap> {
+                    if (id >= N || !rec[(size_t)id].frame || track_anchor[(size_t)id] < 0) return std::nullopt;
+                    adapters::hip::KeyframeInMap k;
+                    k.anchor_pair = track_anchor[(size_t)id];
+                    k.anchor_view = 2;                                     // the tracker's points index the last frame as view 2
+                    for (int q = 0; q < 12; q++) k.pose[(size_t)q] = track_traj[(size_t)id][(size_t)q];
+                    k.frame = rec[(size_t)id].frame.get();
+                    return k;
+                };
+                auto report = [&](const adapters::hip::Sim3Report& r) {
+                    align_candidates++;
+                    align_replaced += r.replaced ? 1 : 0;
+                    if (align_out.is_open())
+                        align_out << r.query_id << ' ' << r.match_id << ' ' << r.s << ' ' << r.n_corr << ' ' << r.n_inliers << ' ' << r.rms_px
+                                  << ' ' << (r.replaced ? 1 : 0) << '\n';
+                };
+                ld.setVerifier(adapters::hip::makeSim3Verifier(*aligner, kept_tracker->mapper().handle(), lookup, reference, 20, report));
+            } else {
+                ld.setVerifier(reference);
+            }
         }
         for (std::size_t i = 1; i < N; i++) {
             FrameRecord& o = rec[i];
@@ -916,6 +970,9 @@ int main(int argc, char** argv) {
             if (lp && graph)                                               // euroc_eval.cpp:235
                 graph->addLoopEdge((int)lp->query_id, (int)lp->match_id, adapters::hip::loopRelativePose(*lp));
         }
+        if (aligner)
+            std::printf("loop align sim3 candidates %lld replaced %lld%s%s\n", align_candidates, align_replaced,
+                        loop_align_out.empty() ? "" : " -> ", loop_align_out.c_str());
         if (place)
             std::printf("loop bow words %d iterations %d entries %d queries %lld candidates %lld\n", place->words(), place_iters, place->size(),
                         ld.placeQueries(), ld.placeCandidates());

@@ -2501,6 +2501,133 @@ int   aria_bow_query_batch_device(aria_bow_t h, const uint16_t* d_tf, const int3
 int   aria_bow_query(aria_bow_t h, long long query_id, const uint8_t* desc_host, int n, aria_bow_hit* hits, int* n_out);
 int   aria_bow_query_device(aria_bow_t h, long long query_id, const uint8_t* d_desc, int n, aria_bow_hit* hits, int* n_out);
 
+/* ---- loop alignment: the similarity X2 = s R X1 + t between the landmarks two keyframes of a loop own (batched Sim(3)
+ * RANSAC). Place recognition (aria_bow_*) and the two-view verification (aria_fund_*, aria_pose_*) yield a loop edge whose
+ * translation has length 1 by construction, while every odometry edge of a map-tracked run is in the map's units; both
+ * keyframes own triangulated landmarks in the map's arena, so a match between them is a pair of 3-D points, and the
+ * similarity that aligns them gives the edge's translation in map units, the scale drift s around the loop, and a
+ * verification stronger than the epipolar one. This is the role of ORB-SLAM's ComputeSim3. The reference has no code for it
+ * (its H09 and H10 audits name the loop edge's unknown scale as the open problem); aria_slam_amd/sim3_ref.py is the
+ * definition, and parity with ORB-SLAM's Sim3Solver is not claimed. Batched over pairs; additive to ABI 4.
+ *
+ * Correspondences. aria_sim3_corr holds the landmark of keyframe 1 in CAMERA 1's coordinates, the landmark of keyframe 2 in
+ *   CAMERA 2's coordinates and the pixels of the two matched keypoints. Camera coordinates on purpose: they are near the
+ *   origin, so the fp32 scoring needs no centring, and a map 1 km from the origin loses nothing, because the join
+ *   (aria_sim3_associate_batch_device) does the move to camera coordinates in fp64.
+ * Model. X2 = s R X1 + t; R row-major. With fix_scale = 1, s = 1 everywhere (a metric stereo map).
+ * Points. x_j = ((u_j - cx) / fx, (v_j - cy) / fy) in fp64. For scoring X1, X2, x1, x2 are rounded to fp32. A correspondence
+ *   with a scoring value beyond 1e15 in magnitude never scores; a model with |t| beyond 1e15 is invalid (every square of the
+ *   test below stays finite).
+ * Hypotheses. `hypotheses` per pair; the hash of the two-view stage with 3 distinct indices per hypothesis (slots j = 0..2,
+ *   at most 256 draws per slot), keyed by (seed, pair id, h). A sample is invalid when a slot stays -1; when in either frame
+ *   |(Xb - Xa) x (Xc - Xa)|^2 <= 1e-12 * max(|Xb - Xa|^2, |Xc - Xa|^2, |Xc - Xb|^2)^2 (the P3P solver's collinearity test);
+ *   or when the model is not finite.
+ * Closed form. fp64, + - * / and sqrt only. Centroids c1, c2 (((Xa + Xb) + Xc) / 3); M = sum (X2_i - c2)(X1_i - c1)^T, rank 2
+ *   because three points are coplanar. V and the eigenvalues of M^T M from the 3x3 Jacobi of the two-view stage, sorted
+ *   descending with its select network; sigma_k = sqrt(max(lambda_k, 0)); u_k = M v_k / sigma_k for the two largest,
+ *   u3 = u1 x u2, v3 = v1 x v2, R = sum u_k v_k^T (a rotation, never a reflection). s = (sigma_1 + sigma_2) / sum |X1_i - c1|^2,
+ *   Umeyama's least-squares scale, invalid outside [min_scale, max_scale]; s = 1 with fix_scale. t = c2 - s R c1.
+ * Inliers. fp32, division-free and two-sided, because a triangulated monocular point is uncertain along its ray and certain
+ *   in the image: Y2 = s R X1 + t, each component s ((r0 X + r1 Y) + r2 Z) + t_k, against x2; Y1 = R^T (X2 - t), each
+ *   component (r_0k d0 + r_1k d1) + r_2k d2 with d = X2 - t, against x1 -- no 1 / s: the test is invariant to a positive scale
+ *   of Y1. Inlier when for both: Y.z > 0 and (Y.x - x Y.z)^2 + (Y.y - y Y.z)^2 <= thr2 * Y.z^2,
+ *   thr2 = (threshold_px / ((fx + fy) / 2))^2.
+ * Winner. Most inliers; ties to the lowest h; an invalid hypothesis scores -1. Integer counts, fixed reduction order.
+ * Refinement. When the winner has >= 4 inliers and refine_iters > 0: up to refine_iters Gauss-Newton steps in fp64 on the four
+ *   normalised reprojection residuals per inlier (Y2 against x2, Y1 against x1), over the winner's inlier set, which is not
+ *   re-evaluated between steps. It starts from the winner's closed form in fp64 (what was scored is its fp32 rounding). Seven
+ *   parameters (w, v, sigma), six with fix_scale, and a left-multiplicative update: R <- Exp(w) R, t <- E(sigma) (Exp(w) t) + v,
+ *   s <- E(sigma) s. E is NOT libm's exp: it is the fixed polynomial 1 + x (1 + x/2 (1 + x/3 ( ... (1 + x/12)))), + * / only, so
+ *   host and device compute the same bits; E(0) = E'(0) = 1 is all a Gauss-Newton step needs, and at the fixed point sigma = 0.
+ *   The 28 + 7 entries of the normal equations are summed in a fixed order (per thread over its strided share, then a fixed
+ *   tree); Cholesky in one lane; a pivot that is not positive, a step that is not finite, or an s outside
+ *   [min_scale, max_scale] ends the refinement with the last good model. It stops early at |dx| <= 1e-12. The refined model is
+ *   rescored in fp32 and kept (refined = 1) when its count is >= the winner's; otherwise the result is the winner's closed form.
+ *   Two cameras at one centre (t = 0) cannot see s in the image: the sigma column vanishes, the pivot test ends the
+ *   refinement, and s is the closed form's.
+ * Outputs. The mask and n_inliers are those of the kept model; rms_px is the RMS over both directions of the kept inliers
+ *   (sqrt(sum of the four squared residuals / (2 n_inliers))), in fp64 in a fixed order, times (fx + fy) / 2. n_corr is the
+ *   number of correspondences read (0 for a pair refused by the checks below).
+ * Validity. valid = 0 with fewer than 3 correspondences, with no valid hypothesis, or when a result field would not be finite:
+ *   R = I, t = 0, s = 1, n_inliers = 0, best_hypothesis = -1, zero mask. No field is ever NaN or Inf. valid = 1 says a model
+ *   was found; whether it is a loop is the caller's gate on n_inliers (ORB-SLAM's constant is 20, untuned here). A count
+ *   outside [0, corr_cap], or an X or a pixel that is not finite, is found before any arithmetic: the pair is invalid with
+ *   n_corr = 0, aria_sim3_check reports ARIA_E_INVALID once, the other pairs of the launch are unaffected.
+ * Determinism. No float atomics; bitwise reproducible run to run, independent of how pairs are split into calls and of a
+ *   pair's place in a launch.
+ * threshold_px = 3.0 is sqrt(9.21) rounded, ORB-SLAM's chi-square bound at octave 0; min_inliers = 20 likewise. Both are
+ *   assumptions nobody has tuned on a recording.
+ * Not built: a Sim(3) pose graph that distributes s around the loop (the SE(3) graph takes [R t]; s is only reported),
+ *   correcting the map's points after a loop, fusing duplicate landmarks, guided re-matching after the first alignment
+ *   (ORB-SLAM's SearchBySim3), per-octave thresholds, relocalisation. */
+typedef struct aria_sim3_s* aria_sim3_t;
+typedef struct {
+    double X1[3];              /* landmark of keyframe 1, camera 1's coordinates                                 */
+    double X2[3];              /* landmark of keyframe 2, camera 2's coordinates                                 */
+    float  u1, v1, u2, v2;     /* pixels of the two matched keypoints                                            */
+} aria_sim3_corr;              /* 64 bytes                                                                       */
+typedef struct {
+    double R[9], t[3], s;      /* X2 = s R X1 + t                                                                */
+    double rms_px;             /* RMS reprojection error of the final inliers, both directions                   */
+    int    n_corr, n_inliers, best_hypothesis, iterations, refined, valid;
+} aria_sim3_result;            /* 136 bytes                                                                      */
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_sim3_config)                                                    */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle owns one (non-blocking: NOT ordered against
+                                * the legacy default stream, see aria_pose_config)                               */
+    int      hypotheses;       /* per pair: multiple of 64, 64..16384 (default 1024)                            */
+    int      refine_iters;     /* 0..16 (default 5)                                                              */
+    int      fix_scale;        /* 0 or 1 (default 0); 1: s = 1 everywhere                                        */
+    int      reserved;         /* 0                                                                              */
+    double   fx, fy, cx, cy;   /* intrinsics (default EuRoC cam0)                                                */
+    double   threshold_px;     /* default 3.0 = sqrt(9.21) rounded; untuned                                      */
+    double   min_scale, max_scale; /* defaults 0.05 and 20: a model outside them is invalid                      */
+    uint64_t seed;             /* sample hash seed (default 0)                                                   */
+} aria_sim3_config;
+
+void  aria_sim3_default_config(aria_sim3_config* cfg);
+int   aria_sim3_create(const aria_sim3_config* cfg, aria_sim3_t* out);
+void  aria_sim3_destroy(aria_sim3_t h);
+void* aria_sim3_stream(aria_sim3_t h);
+/* Synchronises the handle's stream and returns the deferred error of the batch calls since the last check: ARIA_E_INVALID
+ * when some pair's count was outside [0, corr_cap] or one of its values was not finite (estimate), or its counts or match
+ * indices were out of range (associate). Such a pair is skipped; the other pairs are unaffected. */
+int   aria_sim3_check(aria_sim3_t h);
+/* One pair, host buffers; blocks. pair_base is the pair id the sample hash uses. mask (optional): n bytes. */
+int   aria_sim3_estimate(aria_sim3_t h, const aria_sim3_corr* corr, int n, int pair_base, aria_sim3_result* out, uint8_t* mask);
+/* Device-resident batch form, with the meaning of aria_pnp_estimate_batch_device: pair p reads d_ncorr[p] correspondences at
+ * d_corr + p*corr_cap, writes d_out[p] and, if d_mask is not NULL, corr_cap bytes at d_mask + p*corr_cap (zero beyond the
+ * pair's correspondences). The sample hash sees pair id pair_base + p. Enqueued; nothing is synchronised, except when the
+ * workspace grows. */
+int   aria_sim3_estimate_batch_device(aria_sim3_t h, const aria_sim3_corr* d_corr, const int* d_ncorr, int n_pairs, int corr_cap,
+                                      int pair_base, aria_sim3_result* d_out, uint8_t* d_mask);
+/* Test hook: for one pair (host buffers), every hypothesis's 3 sample indices (sample_idx[h*3 + j]; -1 when n < 3), R
+ * (R[h*9 + k]), t (t[h*3 + k]) and s (s[h]) in fp32 as scored (zero when invalid) and inlier count (counts[h], -1 when
+ * invalid). */
+int   aria_sim3_debug_hypotheses(aria_sim3_t h, const aria_sim3_corr* corr, int n, int pair_base, int* sample_idx, float* R,
+                                 float* t, float* s, int* counts);
+/* The join that keeps the chain device-resident; aria_pnp_associate_batch_device twice over. Pair p's keyframe 1 is the
+ * query side of its matches (d_matches + p*match_cap, d_nmatches[p] of them; keypoints at d_kp1 + p*kp_stride, d_n1[p] of
+ * them) and keyframe 2 the train side (d_kp2, d_n2). Keyframe j owns the arena points with pair == d_anchorJ[p] (a device
+ * array of n_pairs ints), indexed by their idx{viewJ} (viewJ = 1 or 2). A match yields a correspondence when both sides have
+ * such a point; of several points the one at the lowest arena position is taken, per side. Xj = Rj X + tj with the 12-double
+ * world-to-camera rows [R t] at d_poseJ + 12 p, in fp64, each component ((r0 X + r1 Y) + r2 Z) + t; the pixels are the
+ * keypoints'. Correspondences are written in match order, stably compacted, at d_corr + p*match_cap, their number at
+ * d_ncorr[p], each one's match index (optional) at d_corr_match + p*match_cap: the input of
+ * aria_sim3_estimate_batch_device with corr_cap = match_cap. Integers and copies only, plus the one rigid move. A count
+ * outside [0, match_cap] or [0, kp_stride], a query_idx outside [0, d_n1[p]) or a train_idx outside [0, d_n2[p]) is a
+ * deferred error of the pair (d_ncorr[p] = 0). The stream order, the arena-address caveat and the other-device refusal are
+ * those of aria_pnp_associate_batch_device. Cost: the call clears and fills two tables of n_pairs * kp_stride ints (kp_stride
+ * at most 2^24), and, unlike the PnP join, whose pairs are anchor_base + p, the fill compares every arena point with every
+ * pair's anchor: n_pairs * arena integer compares per table. That is nothing for the handful of candidates a loop detector
+ * hands over and 47 times the PnP join at 4096 pairs against 2.4 M points; a sorted anchor list or a hash is not built. */
+int   aria_sim3_associate_batch_device(aria_sim3_t h, aria_map_t map, const int* d_anchor1, const int* d_anchor2, int view1,
+                                       int view2, const double* d_pose1, const double* d_pose2, const aria_keypoint* d_kp1,
+                                       const int* d_n1, const aria_keypoint* d_kp2, const int* d_n2, int64_t kp_stride,
+                                       const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
+                                       aria_sim3_corr* d_corr, int* d_ncorr, int* d_corr_match);
+
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);
 int aria_synth_sequence(uint64_t seed0, int n_pairs, int width, int height, uint8_t* out, int n_threads);
