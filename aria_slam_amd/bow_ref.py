@@ -127,6 +127,17 @@ def norm_of(tf, idf_q):
     return int((np.asarray(tf).astype(np.int64) * np.asarray(idf_q).astype(np.int64)).sum())
 
 
+MAX_NORM = 1 << 24
+
+
+def held_norm(tf, norm, idf_q):
+    """The door of the database and of a query (aria_bow_check in the header): a caller's norm is trusted only when it is the sum
+    of the bag's weighted counts and below 2^24. Returns (the norm the index uses, accepted); a refused bag is an empty one
+    (norm 0) and a deferred error, and nothing else changes."""
+    ok = 0 <= int(norm) == norm_of(tf, idf_q) < MAX_NORM
+    return (int(norm) if ok else 0), ok
+
+
 def score(tf_q, n_q, tf_d, n_d, idf_q):
     """Rule 6: (S, score). Python integers, one IEEE division."""
     if n_q <= 0 or n_d <= 0:

@@ -1,7 +1,11 @@
 """Place recognition on the MI355X (aria_bow_*, kernels in aria_slam_amd/csrc/bow_index.hip) against its definition, the NumPy
 restatement aria_slam_amd/bow_ref.py, bit for bit: words, weights, iterations run, bags, norms, hits with the numerator S and the
 bit pattern of the score, counts and deferred errors; on the case table (tests/bow_cases.py) equal to the answers written down
-from the construction as well."""
+from the construction as well.
+
+This file holds the rules at small sizes: at most 40 entries, 40 bags in a call and top_k 4, queries at V = 4, 256 and 4096, the
+ring wrapping at capacity 4. More than one tile of k_bow_score, more than one wave or trip of k_bow_topk, a second chunk of an add or
+a query call, the other row strides, the bound on the norm and training and transform at size are tests/test_gpu_bow_edges.py."""
 import os
 import sys
 
