@@ -1,6 +1,5 @@
-"""What the bindings of the twenty-one stage handles share (aria_pose_t, aria_fund_t, aria_map_t, aria_graph_t, aria_fuse_t,
-aria_eval_t, aria_det_t, aria_stereo_t, aria_rect_t, aria_dense_t, aria_tsdf_t, aria_nav_t, aria_alert_t, aria_pnp_t, aria_ba_t, aria_ray_t, aria_icp_t, aria_mesh_t, aria_proj_t, aria_bow_t, aria_sim3_t): creation from the stage's config structure, the handle's lifetime, and the
-check / status / stream calls, all found from the stage's C prefix."""
+"""What the bindings of every stage handle share (_lib.STAGES lists them): creation from the stage's config structure, the
+handle's lifetime, and the check / status / stream calls, all found from the stage's C prefix."""
 import ctypes as C
 
 from . import _lib

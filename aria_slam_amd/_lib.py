@@ -598,52 +598,18 @@ def load_library():
                                            C.POINTER(C.c_int64)]
     L.aria_matcher_stream.argtypes = [C.c_void_p]
     L.aria_matcher_sync.argtypes = [C.c_void_p]
-    if hasattr(L, "aria_pose_create"):   # absent from A/B builds of the extractor sources alone (tools/build_ab.sh)
-        _bind_pose(L)
-    if hasattr(L, "aria_map_create"):
-        _bind_map(L)
-    if hasattr(L, "aria_fund_create"):
-        _bind_fund(L)
-    if hasattr(L, "aria_graph_create"):
-        _bind_graph(L)
-    if hasattr(L, "aria_fuse_create"):
-        _bind_fuse(L)
-    if hasattr(L, "aria_eval_create"):
-        _bind_eval(L)
-    if hasattr(L, "aria_det_create"):
-        _bind_det(L)
-    if hasattr(L, "aria_stereo_create"):
-        _bind_stereo(L)
-    if hasattr(L, "aria_rect_create"):
-        _bind_rect(L)
-    if hasattr(L, "aria_dense_create"):
-        _bind_dense(L)
-    if hasattr(L, "aria_tsdf_create"):
-        _bind_tsdf(L)
-    if hasattr(L, "aria_nav_create"):
-        _bind_nav(L)
-    if hasattr(L, "aria_alert_create"):
-        _bind_alert(L)
-    if hasattr(L, "aria_pnp_create"):
-        _bind_pnp(L)
-    if hasattr(L, "aria_ba_create"):
-        _bind_ba(L)
-    if hasattr(L, "aria_ray_create"):
-        _bind_ray(L)
-    if hasattr(L, "aria_icp_create"):
-        _bind_icp(L)
-    if hasattr(L, "aria_mesh_create"):
-        _bind_mesh(L)
-    if hasattr(L, "aria_proj_create"):
-        _bind_proj(L)
-    if hasattr(L, "aria_bow_create"):
-        _bind_bow(L)
-    if hasattr(L, "aria_sim3_create"):
-        _bind_sim3(L)
+    for prefix in STAGES:
+        if hasattr(L, "aria_%s_create" % prefix):   # absent from A/B builds of the extractor sources alone (tools/build_ab.sh)
+            globals()["_bind_" + prefix](L)
     L.aria_synth_frame_pair.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.aria_synth_sequence.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     _lib = L
     return L
+
+
+# Every stage handle, by the prefix of its C entry points (aria_<prefix>_create, ...), in the order the stages were added.
+STAGES = ("pose", "map", "fund", "graph", "fuse", "eval", "det", "stereo", "rect", "dense", "tsdf", "nav", "alert", "pnp", "ba", "ray",
+          "icp", "mesh", "proj", "bow", "sim3")
 
 
 def _bind_handle(L, prefix):

@@ -504,40 +504,29 @@ void aria_alert_default_config(aria_alert_config* c) {
 
 int aria_alert_create(const aria_alert_config* c, aria_alert_t* out) {
     if (!out || alert_bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_alert_s* h = new (std::nothrow) aria_alert_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    AlertParams& P = h->P;
-    P.width = c->width; P.height = c->height; P.zone_top = c->zone_top; P.zone_bottom = c->zone_bottom;
-    int b[2];
-    (void)aria_alert_zone_bounds(c->width, b);
-    P.bound0 = b[0]; P.bound1 = b[1];
-    P.max_dets = c->max_dets; P.min_valid = c->min_valid; P.min_depth = c->min_depth; P.max_depth = c->max_depth;
-    P.zone_num = c->zone_pct_num; P.zone_den = c->zone_pct_den; P.det_num = c->det_pct_num; P.det_den = c->det_pct_den;
-    P.zone_alert_m = c->zone_alert_m; P.default_depth = c->default_depth; P.crit_m = c->crit_m; P.high_m = c->high_m;
-    P.medium_m = c->medium_m; P.beep_m = c->beep_m;
-    P.obstacle_dangerous = c->obstacle_dangerous; P.n_dangerous = c->n_dangerous;
-    for (int i = 0; i < 32; i++) P.dangerous[i] = c->dangerous[i];
-    P.max_events = c->max_events_per_frame;
-    for (int i = 0; i < 4; i++) P.cooldown_ns[i] = c->cooldown_ns[i];
-    if (const char* s = aria_getenv("ARIA_ALERT_SELECT")) h->plain = !std::strcmp(s, "plain");   // variants build: A/B
-    const int rc = stage_open(h, c->device, c->stream, 2, "aria_alert_create");
-    if (rc != ARIA_OK) {
-        aria_alert_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 2, "aria_alert_create", [](aria_alert_s* h) {
+        const aria_alert_config& c = h->cfg;
+        AlertParams& P = h->P;
+        P.width = c.width; P.height = c.height; P.zone_top = c.zone_top; P.zone_bottom = c.zone_bottom;
+        int b[2];
+        (void)aria_alert_zone_bounds(c.width, b);
+        P.bound0 = b[0]; P.bound1 = b[1];
+        P.max_dets = c.max_dets; P.min_valid = c.min_valid; P.min_depth = c.min_depth; P.max_depth = c.max_depth;
+        P.zone_num = c.zone_pct_num; P.zone_den = c.zone_pct_den; P.det_num = c.det_pct_num; P.det_den = c.det_pct_den;
+        P.zone_alert_m = c.zone_alert_m; P.default_depth = c.default_depth; P.crit_m = c.crit_m; P.high_m = c.high_m;
+        P.medium_m = c.medium_m; P.beep_m = c.beep_m;
+        P.obstacle_dangerous = c.obstacle_dangerous; P.n_dangerous = c.n_dangerous;
+        for (int i = 0; i < 32; i++) P.dangerous[i] = c.dangerous[i];
+        P.max_events = c.max_events_per_frame;
+        for (int i = 0; i < 4; i++) P.cooldown_ns[i] = c.cooldown_ns[i];
+        if (const char* s = aria_getenv("ARIA_ALERT_SELECT")) h->plain = !std::strcmp(s, "plain");   // variants build: A/B
+        return (int)ARIA_OK;
+    });
 }
 
-void aria_alert_destroy(aria_alert_t h) {
-    if (!h) return;
-    stage_close(h);
-    delete h;
-}
+void aria_alert_destroy(aria_alert_t h) { stage_destroy(h); }
 
-void* aria_alert_stream(aria_alert_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_alert_stream(aria_alert_t h) { return stage_stream(h); }
 
 int aria_alert_check(aria_alert_t h) {
     if (!h) return ARIA_E_INVALID;

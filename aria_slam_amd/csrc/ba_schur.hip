@@ -781,37 +781,21 @@ int aria_ba_create(const aria_ba_config* c, aria_ba_t* out) {
         !std::isfinite(c->fx) || !std::isfinite(c->fy) || !std::isfinite(c->cx) || !std::isfinite(c->cy) || c->fx == 0 ||
         c->fy == 0)
         return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_ba_s* h = new (std::nothrow) aria_ba_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_ba_create");
-    if (rc == ARIA_OK) rc = h->d_counts.reserve(h->stream, 4);
-    if (rc == ARIA_OK) rc = h->d_res.reserve(h->stream, 1);
-    if (rc == ARIA_OK) rc = h->d_dbg.reserve(h->stream, (size_t)BA_N * BA_N + BA_N);
-    if (rc != ARIA_OK) {
-        aria_ba_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_ba_create", [](aria_ba_s* h) {
+        const char* what = "aria_ba_create";
+        int rc;
+        if ((rc = h->d_counts.reserve(h->stream, 4, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_res.reserve(h->stream, 1, what)) != ARIA_OK) return rc;
+        return h->d_dbg.reserve(h->stream, (size_t)BA_N * BA_N + BA_N, what);
+    });
 }
 
-void aria_ba_destroy(aria_ba_t h) {
-    if (!h) return;
-    stage_close(h);
-    delete h;
-}
+void aria_ba_destroy(aria_ba_t h) { stage_destroy(h); }
 
-void* aria_ba_stream(aria_ba_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_ba_stream(aria_ba_t h) { return stage_stream(h); }
 
 int aria_ba_check(aria_ba_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    if (bits & ERRBIT_BA_INPUT) return ARIA_E_INVALID;
-    return (bits & ERRBIT_BA_CAPACITY) ? ARIA_E_OUTPUT_TOO_SMALL : ARIA_OK;
+    return stage_check(h, {{ERRBIT_BA_INPUT, ARIA_E_INVALID}, {ERRBIT_BA_CAPACITY, ARIA_E_OUTPUT_TOO_SMALL}});
 }
 
 int aria_ba_optimize_batch_device(aria_ba_t h, double* d_poses, const uint8_t* d_pose_fixed, double* d_points,

@@ -460,12 +460,12 @@ int score_lds_bytes(int Vp) { return BW_QT * Vp * 4 + Vp * 2; }
 struct aria_bow_s : StageHandle {
     aria_bow_config cfg{};
     int V = 0, Vp = 0;                       // words of the vocabulary (0: none yet) and the ring's row stride
-    uint32_t* d_words = nullptr;             // [BW_MAX_WORDS][8]
-    uint16_t* d_idf = nullptr;               // [BW_MAX_WORDS]
+    DeviceBuffer<uint32_t> d_words;          // [BW_MAX_WORDS][8]
+    DeviceBuffer<uint16_t> d_idf;            // [BW_MAX_WORDS]
     // the database: a ring of `capacity` slots, oldest at head
     DeviceBuffer<uint16_t> d_db_tf;          // [capacity][Vp]
-    int* d_db_norm = nullptr;                // [capacity]
-    long long* d_db_ids = nullptr;           // [capacity]
+    DeviceBuffer<int> d_db_norm;             // [capacity]
+    DeviceBuffer<long long> d_db_ids;        // [capacity]
     std::vector<long long> ids;              // the ids again, by slot, for aria_bow_info
     long long head = 0;
     int size = 0;
@@ -480,12 +480,12 @@ struct aria_bow_s : StageHandle {
     DeviceBuffer<long long> d_src;
     DeviceBuffer<uint8_t> d_train_desc;      // host-buffer training
     DeviceBuffer<int> d_train_counts;
-    int* d_flag = nullptr;                   // the changed flag of an iteration
+    DeviceBuffer<int> d_flag;                // the changed flag of an iteration
     // single-frame staging of the host forms
-    uint8_t* d_desc1 = nullptr;              // [rows][32]
-    uint16_t* d_tf1 = nullptr;               // [BW_MAX_WORDS]
-    int* d_norm1 = nullptr;                  // norm, count
-    aria_bow_hit* d_hits1 = nullptr;         // [BW_MAX_K]
+    DeviceBuffer<uint8_t> d_desc1;           // [rows][32]
+    DeviceBuffer<uint16_t> d_tf1;            // [BW_MAX_WORDS]
+    DeviceBuffer<int> d_norm1;               // norm, count
+    DeviceBuffer<aria_bow_hit> d_hits1;      // [BW_MAX_K]
 };
 
 namespace {
@@ -518,7 +518,7 @@ int quantise_frames(aria_bow_s* h, const uint8_t* d_desc, const int* d_counts, i
     if ((rc = h->d_cnt.reserve(h->stream, (size_t)n_frames)) != ARIA_OK) return rc;
     hipLaunchKernelGGL(k_bow_counts, dim3((n_frames + BW_BLOCK - 1) / BW_BLOCK), dim3(BW_BLOCK), 0, h->stream, d_counts, fixed, n_frames,
                        limit, h->d_cnt.p, h->d_err);
-    launch_knn2_mfma(0, maxq, n_frames, h->stream, d_desc, h->d_cnt.p, 0, reinterpret_cast<const uint8_t*>(h->d_words), nullptr, h->V,
+    launch_knn2_mfma(0, maxq, n_frames, h->stream, d_desc, h->d_cnt.p, 0, reinterpret_cast<const uint8_t*>(h->d_words.p), nullptr, h->V,
                      desc_stride * 32, 0, h->d_keys.p, maxq, 0.0, nullptr, h->V, nullptr);
     return ARIA_OK;
 }
@@ -559,50 +559,31 @@ void aria_bow_default_config(aria_bow_config* c) {
 
 int aria_bow_create(const aria_bow_config* c, aria_bow_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_bow_s* h = new (std::nothrow) aria_bow_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_bow_create");
-    if (rc == ARIA_OK) {
-        h->ids.assign((size_t)c->capacity, -1);
-        hipError_t e = hipMalloc((void**)&h->d_words, BW_MAX_WORDS * 32);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_idf, BW_MAX_WORDS * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_db_norm, (size_t)c->capacity * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_db_ids, (size_t)c->capacity * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_flag, sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_desc1, (size_t)c->rows * 32);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_tf1, BW_MAX_WORDS * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_norm1, 2 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_hits1, BW_MAX_K * sizeof(aria_bow_hit));
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_score), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    score_lds_bytes(BW_MAX_WORDS));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_bow_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_bow_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_bow_create", [](aria_bow_s* h) {
+        const char* what = "aria_bow_create";
+        const size_t capacity = (size_t)h->cfg.capacity;
+        h->ids.assign(capacity, -1);
+        int rc;
+        if ((rc = h->d_words.reserve(h->stream, BW_MAX_WORDS * 8, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_idf.reserve(h->stream, BW_MAX_WORDS, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_db_norm.reserve(h->stream, capacity, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_db_ids.reserve(h->stream, capacity, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_flag.reserve(h->stream, 1, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_desc1.reserve(h->stream, (size_t)h->cfg.rows * 32, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_tf1.reserve(h->stream, BW_MAX_WORDS, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_norm1.reserve(h->stream, 2, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_hits1.reserve(h->stream, BW_MAX_K, what)) != ARIA_OK) return rc;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_score), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 score_lds_bytes(BW_MAX_WORDS));
+        return e == hipSuccess ? (int)ARIA_OK : hip_fail(e, what, __FILE__, __LINE__);
+    });
 }
 
-void aria_bow_destroy(aria_bow_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_words, h->d_idf, h->d_db_norm, h->d_db_ids, h->d_flag, h->d_desc1, h->d_tf1, h->d_norm1, h->d_hits1});
-    delete h;
-}
+void aria_bow_destroy(aria_bow_t h) { stage_destroy(h); }
 
-void* aria_bow_stream(aria_bow_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_bow_stream(aria_bow_t h) { return stage_stream(h); }
 
-int aria_bow_check(aria_bow_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_BOW_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_bow_check(aria_bow_t h) { return stage_check(h, {{ERRBIT_BOW_INPUT, ARIA_E_INVALID}}); }
 
 int aria_bow_words(aria_bow_t h) { return h ? h->V : 0; }
 
@@ -801,7 +782,7 @@ int aria_bow_add_batch_device(aria_bow_t h, const uint16_t* d_tf, const int32_t*
 int aria_bow_add_device(aria_bow_t h, long long id, const uint8_t* d_desc, int n) {
     if (!h || h->V == 0 || n < 0 || n > h->cfg.rows || (n && !d_desc)) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    const int rc = transform_impl(h, n ? d_desc : h->d_desc1, nullptr, n, 1, h->cfg.rows, h->d_tf1, h->d_norm1);
+    const int rc = transform_impl(h, n ? d_desc : h->d_desc1.p, nullptr, n, 1, h->cfg.rows, h->d_tf1, h->d_norm1);
     return rc != ARIA_OK ? rc : aria_bow_add_batch_device(h, h->d_tf1, h->d_norm1, &id, 1);
 }
 
@@ -859,7 +840,7 @@ int aria_bow_query_device(aria_bow_t h, long long query_id, const uint8_t* d_des
     if (n_out) *n_out = 0;
     if (!h || h->V == 0 || n < 0 || n > h->cfg.rows || (n && !d_desc) || !hits) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int rc = transform_impl(h, n ? d_desc : h->d_desc1, nullptr, n, 1, h->cfg.rows, h->d_tf1, h->d_norm1);
+    int rc = transform_impl(h, n ? d_desc : h->d_desc1.p, nullptr, n, 1, h->cfg.rows, h->d_tf1, h->d_norm1);
     if (rc != ARIA_OK) return rc;
     if ((rc = aria_bow_query_batch_device(h, h->d_tf1, h->d_norm1, &query_id, 1, h->d_hits1, h->d_norm1 + 1)) != ARIA_OK) return rc;
     int count = 0;

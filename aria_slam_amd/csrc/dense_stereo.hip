@@ -305,12 +305,10 @@ struct aria_dense_s : StageHandle {
     DeviceBuffer<float> d_depth;
     DeviceBuffer<aria_keypoint> d_kp;
     DeviceBuffer<aria_stereo_obs> d_obs;
-    int* d_count = nullptr;
+    DeviceBuffer<int> d_count;
 };
 
 namespace {
-
-bool fin(double v) { return std::isfinite(v); }
 
 int64_t pairs_for(const aria_dense_config* c) {
     const int64_t per_pair = DN_BYTES_PER_PIXEL * c->max_width * c->max_height;
@@ -318,8 +316,8 @@ int64_t pairs_for(const aria_dense_config* c) {
 }
 
 bool bad_config(const aria_dense_config* c) {
-    return !c || c->struct_size != (int)sizeof(aria_dense_config) || !(c->fx > 0) || !(c->fy > 0) || !fin(c->fx) || !fin(c->fy) ||
-           !fin(c->cx) || !fin(c->cy) || !(c->baseline > 0) || !fin(c->baseline) || c->num_disparities != DN_D || c->P1 < 1 ||
+    return !c || c->struct_size != (int)sizeof(aria_dense_config) || bad_pinhole(c->fx, c->fy, c->cx, c->cy) ||
+           !(c->baseline > 0) || !std::isfinite(c->baseline) || c->num_disparities != DN_D || c->P1 < 1 ||
            c->P1 > c->P2 || c->P2 > 127 || c->uniqueness < 0 || c->uniqueness > 99 || c->lr_max_diff > DN_D - 1 ||
            c->max_width < 1 || c->max_width > DN_MAX_DIM || c->max_height < 1 || c->max_height > DN_MAX_DIM ||
            c->scratch_bytes < 1 || pairs_for(c) < 1;
@@ -347,34 +345,19 @@ void aria_dense_default_config(aria_dense_config* c) {
 
 int aria_dense_create(const aria_dense_config* c, aria_dense_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_dense_s* h = new (std::nothrow) aria_dense_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    h->prm.fx = (float)c->fx; h->prm.fy = (float)c->fy; h->prm.cx = (float)c->cx; h->prm.cy = (float)c->cy;
-    h->prm.fb = h->prm.fx * (float)c->baseline;          // the product formed once, in fp32
-    h->prm.P1 = c->P1; h->prm.P2 = c->P2; h->prm.uniq = c->uniqueness; h->prm.lr = c->lr_max_diff;
-    h->in_flight = (int)pairs_for(c);
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_dense_create");
-    if (rc == ARIA_OK) {
-        const hipError_t e = hipMalloc((void**)&h->d_count, sizeof(int));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_dense_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_dense_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_dense_create", [](aria_dense_s* h) {
+        const aria_dense_config& c = h->cfg;
+        h->prm.fx = (float)c.fx; h->prm.fy = (float)c.fy; h->prm.cx = (float)c.cx; h->prm.cy = (float)c.cy;
+        h->prm.fb = h->prm.fx * (float)c.baseline;           // the product formed once, in fp32
+        h->prm.P1 = c.P1; h->prm.P2 = c.P2; h->prm.uniq = c.uniqueness; h->prm.lr = c.lr_max_diff;
+        h->in_flight = (int)pairs_for(&c);
+        return h->d_count.reserve(h->stream, 1, "aria_dense_create");
+    });
 }
 
-void aria_dense_destroy(aria_dense_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_count});
-    delete h;
-}
+void aria_dense_destroy(aria_dense_t h) { stage_destroy(h); }
 
-void* aria_dense_stream(aria_dense_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_dense_stream(aria_dense_t h) { return stage_stream(h); }
 
 int aria_dense_pairs_in_flight(aria_dense_t h) { return h ? h->in_flight : ARIA_E_INVALID; }
 
@@ -388,13 +371,7 @@ int64_t aria_dense_algorithmic_bytes(int width, int height) {
     return (int64_t)width * height * (2 + 2 + 4);        // both images read, int16 disparity and fp32 depth written
 }
 
-int aria_dense_check(aria_dense_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_DENSE_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_dense_check(aria_dense_t h) { return stage_check(h, {{ERRBIT_DENSE_INPUT, ARIA_E_INVALID}}); }
 
 int aria_dense_compute_batch_device(aria_dense_t h, const uint8_t* d_left, const uint8_t* d_right, int64_t img_stride, int width,
                                     int height, int pitch, int n_pairs, int16_t* d_disp, int64_t disp_stride, int disp_pitch,

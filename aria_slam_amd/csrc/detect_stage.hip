@@ -274,15 +274,15 @@ void det_build_table(int src, int dst, uint32_t* out) {
 // ---- C-ABI ------------------------------------------------------------------------------------------------------------------
 struct aria_det_s : StageHandle {          // d_err: [0] bits, [1] det rows needed, [2] box rows needed
     aria_det_config cfg{};
-    uint32_t* d_tab = nullptr;             // x table at 0, y table at DET_MAX_DIM
+    DeviceBuffer<uint32_t> d_tab;          // x table at 0, y table at DET_MAX_DIM
     std::vector<uint32_t> h_tab;           // host copy (kept while the upload may be in flight)
     int tab_key[4] = {0, 0, 0, 0};         // W, H, in_w, in_h of the tables on the device
     // the handle's own buffers (aria_det_device_buffers, host forms), allocated on first use
-    void* d_input = nullptr;
-    float* d_raw = nullptr;
-    aria_detection* d_dets = nullptr;
-    aria_box* d_boxes = nullptr;
-    int* d_counts = nullptr;               // ndets at 0, nboxes at max_batch
+    DeviceBuffer<uint8_t> d_input;         // bytes: floats or halves, cfg.out_half
+    DeviceBuffer<float> d_raw;
+    DeviceBuffer<aria_detection> d_dets;
+    DeviceBuffer<aria_box> d_boxes;
+    DeviceBuffer<int> d_counts;            // ndets at 0, nboxes at max_batch
     DeviceBuffer<uint8_t> d_img;           // staging of aria_det_preprocess
 };
 
@@ -291,14 +291,13 @@ namespace {
 size_t det_elem(const aria_det_s* h) { return h->cfg.out_half ? 2 : 4; }
 
 int det_ensure_buffers(aria_det_t h) {
-    if (h->d_counts) return ARIA_OK;
     const size_t B = (size_t)h->cfg.max_batch, NC = (size_t)h->cfg.max_candidates;
-    ARIA_HIP(hipMalloc(&h->d_input, B * 3 * (size_t)h->cfg.input_w * h->cfg.input_h * det_elem(h)));
-    ARIA_HIP(hipMalloc((void**)&h->d_raw, B * NC * 6 * sizeof(float)));
-    ARIA_HIP(hipMalloc((void**)&h->d_dets, B * NC * sizeof(aria_detection)));
-    ARIA_HIP(hipMalloc((void**)&h->d_boxes, B * NC * sizeof(aria_box)));
-    ARIA_HIP(hipMalloc((void**)&h->d_counts, 2 * B * sizeof(int)));
-    return ARIA_OK;
+    int rc;
+    if ((rc = h->d_input.reserve(h->stream, B * 3 * (size_t)h->cfg.input_w * h->cfg.input_h * det_elem(h))) != ARIA_OK) return rc;
+    if ((rc = h->d_raw.reserve(h->stream, B * NC * 6)) != ARIA_OK) return rc;
+    if ((rc = h->d_dets.reserve(h->stream, B * NC)) != ARIA_OK) return rc;
+    if ((rc = h->d_boxes.reserve(h->stream, B * NC)) != ARIA_OK) return rc;
+    return h->d_counts.reserve(h->stream, 2 * B);
 }
 
 int det_tables(aria_det_t h, int W, int H) {
@@ -354,29 +353,13 @@ int aria_det_create(const aria_det_config* c, aria_det_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_det_config)) return ARIA_E_INVALID;
     *out = nullptr;
     if (!det_config_ok(c)) return ARIA_E_INVALID;
-    aria_det_s* h = new (std::nothrow) aria_det_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 4, "aria_det_create");
-    if (rc == ARIA_OK) {
-        const hipError_t e = hipMalloc((void**)&h->d_tab, 2 * DET_MAX_DIM * sizeof(uint32_t));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_det_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_det_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 4, "aria_det_create",
+                        [](aria_det_s* h) { return h->d_tab.reserve(h->stream, 2 * DET_MAX_DIM, "aria_det_create"); });
 }
 
-void aria_det_destroy(aria_det_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_tab, h->d_input, h->d_raw, h->d_dets, h->d_boxes, h->d_counts});
-    delete h;
-}
+void aria_det_destroy(aria_det_t h) { stage_destroy(h); }
 
-void* aria_det_stream(aria_det_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_det_stream(aria_det_t h) { return stage_stream(h); }
 
 int aria_det_check(aria_det_t h, int* det_rows_needed, int* box_rows_needed) {
     if (!h) return ARIA_E_INVALID;

@@ -543,7 +543,7 @@ struct aria_fund_s : StageHandle {
     DeviceBuffer<int> d_nmod;             // [n_pairs][H]
     DeviceBuffer<int> d_cnt;              // [n_pairs][H][3]
     PairStaging pair;                     // aria_fund_estimate, aria_fund_debug_hypotheses
-    aria_fund_result* d_res = nullptr;
+    DeviceBuffer<aria_fund_result> d_res;
     DeviceBuffer<int> d_dbg;
 };
 
@@ -584,7 +584,7 @@ int fund_enqueue(aria_fund_t h, const aria_keypoint* d_kq, const int* d_nq, cons
 int fund_enqueue_staged(aria_fund_t h, int query_is_first, int pair_base, int* d_dbg, bool finish) {
     const PairStaging& s = h->pair;
     return fund_enqueue(h, s.d_kq, s.d_counts, s.d_kt, s.d_counts + 1, s.kp_stride, s.d_m, s.d_counts + 2, 1, s.match_cap,
-                        query_is_first, pair_base, finish ? h->d_res : nullptr, finish ? s.d_mask.p : nullptr, nullptr, nullptr,
+                        query_is_first, pair_base, finish ? h->d_res.p : nullptr, finish ? s.d_mask.p : nullptr, nullptr, nullptr,
                         d_dbg, finish);
 }
 
@@ -607,39 +607,17 @@ int aria_fund_create(const aria_fund_config* c, aria_fund_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_fund_config)) return ARIA_E_INVALID;
     if (c->hypotheses < 64 || c->hypotheses > 16384 || (c->hypotheses % 64)) return ARIA_E_INVALID;
     if (!(c->threshold_px > 0) || !std::isfinite(c->threshold_px)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_fund_s* h = new (std::nothrow) aria_fund_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_fund_create");
-    if (rc == ARIA_OK) rc = h->pair.create(h->stream);
-    if (rc == ARIA_OK) {
-        const hipError_t e = hipMalloc((void**)&h->d_res, sizeof(aria_fund_result));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_fund_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_fund_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_fund_create", [](aria_fund_s* h) {
+        const int rc = h->pair.create(h->stream);
+        return rc != ARIA_OK ? rc : h->d_res.reserve(h->stream, 1, "aria_fund_create");
+    });
 }
 
-void aria_fund_destroy(aria_fund_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_res});
-    delete h;
-}
+void aria_fund_destroy(aria_fund_t h) { stage_destroy(h); }
 
-void* aria_fund_stream(aria_fund_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_fund_stream(aria_fund_t h) { return stage_stream(h); }
 
-int aria_fund_check(aria_fund_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_FUND_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_fund_check(aria_fund_t h) { return stage_check(h, {{ERRBIT_FUND_INPUT, ARIA_E_INVALID}}); }
 
 int aria_fund_estimate_batch_device(aria_fund_t h, const aria_keypoint* d_kp_query, const int* d_nq,
                                     const aria_keypoint* d_kp_train, const int* d_nt, int64_t kp_stride,
@@ -685,8 +663,7 @@ int aria_fund_debug_hypotheses(aria_fund_t h, const aria_keypoint* kp_query, int
     ARIA_HIP(hipMemcpyAsync(soa.data(), h->d_F, sizeof(double) * 27 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(counts, h->d_cnt, sizeof(int) * 3 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < H; i++)
-        for (int k = 0; k < 27; k++) F[(size_t)i * 27 + k] = soa[(size_t)k * H + i];
+    unpack_models(soa.data(), H, 0, 27, F);
     return aria_fund_check(h);
 }
 

@@ -762,14 +762,14 @@ __global__ __launch_bounds__(GRAPH_BLOCK) void k_graph_lm(double* poses_all, con
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
 struct aria_graph_s : StageHandle {
     aria_graph_config cfg{};
-    double* d_v = nullptr;     // [max_graphs] vertex scratch
-    double* d_e = nullptr;     // [max_graphs] edge scratch
-    int* d_i = nullptr;        // [max_graphs] adjacency
+    DeviceBuffer<double> d_v;  // [max_graphs] vertex scratch
+    DeviceBuffer<double> d_e;  // [max_graphs] edge scratch
+    DeviceBuffer<int> d_i;     // [max_graphs] adjacency
     // single-graph staging (aria_graph_optimize, aria_graph_debug_linearize)
-    double* d_poses = nullptr;
-    aria_graph_edge* d_edges = nullptr;
-    int* d_off = nullptr;      // [0..1] vertex offsets, [2..3] edge offsets, [4] fixed
-    aria_graph_result* d_res = nullptr;
+    DeviceBuffer<double> d_poses;
+    DeviceBuffer<aria_graph_edge> d_edges;
+    DeviceBuffer<int> d_off;   // [0..1] vertex offsets, [2..3] edge offsets, [4] fixed
+    DeviceBuffer<aria_graph_result> d_res;
     int wlds_edges = 0;        // edges of the on-chip solve (0: the device refused the LDS size, W and p stay in HBM)
 };
 
@@ -827,52 +827,34 @@ int aria_graph_create(const aria_graph_config* c, aria_graph_t* out) {
         c->max_edges > (1 << 22) || c->pcg_max_iters < 1 || c->pcg_max_iters > 100000 || !(c->pcg_rel_tol > 0) ||
         !(c->pcg_rel_tol < 1))
         return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_graph_s* h = new (std::nothrow) aria_graph_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_graph_create");
-    if (rc == ARIA_OK) {
+    return stage_create(c, out, 1, "aria_graph_create", [](aria_graph_s* h) {
+        const aria_graph_config& c = h->cfg;
         // more than 64 KiB of dynamic LDS has to be asked for; where that is refused the solve keeps W and p in HBM
-        h->wlds_edges = std::min(c->max_edges, GRAPH_LDS_EDGES);
+        h->wlds_edges = std::min(c.max_edges, GRAPH_LDS_EDGES);
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_graph_lm), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)graph_lds_bytes(h->wlds_edges)) != hipSuccess) {
             (void)hipGetLastError();
             h->wlds_edges = 0;
         }
-        const size_t G = (size_t)c->max_graphs, V = (size_t)c->max_vertices, E = (size_t)c->max_edges;
-        hipError_t e = hipMalloc((void**)&h->d_v, G * V * VERT_DOUBLES * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_e, G * E * EDGE_DOUBLES * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_i, G * graph_int_words(c->max_vertices, c->max_edges) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_poses, V * 12 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_edges, E * sizeof(aria_graph_edge));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_off, 8 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_res, sizeof(aria_graph_result));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_graph_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_graph_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+        const size_t G = (size_t)c.max_graphs, V = (size_t)c.max_vertices, E = (size_t)c.max_edges;
+        const char* what = "aria_graph_create";
+        int rc;
+        if ((rc = h->d_v.reserve(h->stream, G * V * VERT_DOUBLES, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_e.reserve(h->stream, G * E * EDGE_DOUBLES, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_i.reserve(h->stream, G * graph_int_words(c.max_vertices, c.max_edges), what)) != ARIA_OK) return rc;
+        if ((rc = h->d_poses.reserve(h->stream, V * 12, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_edges.reserve(h->stream, E, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_off.reserve(h->stream, 8, what)) != ARIA_OK) return rc;
+        return h->d_res.reserve(h->stream, 1, what);
+    });
 }
 
-void aria_graph_destroy(aria_graph_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_v, h->d_e, h->d_i, h->d_poses, h->d_edges, h->d_off, h->d_res});
-    delete h;
-}
+void aria_graph_destroy(aria_graph_t h) { stage_destroy(h); }
 
-void* aria_graph_stream(aria_graph_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_graph_stream(aria_graph_t h) { return stage_stream(h); }
 
 int aria_graph_check(aria_graph_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    if (bits & ERRBIT_GRAPH_INPUT) return ARIA_E_INVALID;
-    return (bits & ERRBIT_GRAPH_LARGE) ? ARIA_E_TOO_LARGE : ARIA_OK;
+    return stage_check(h, {{ERRBIT_GRAPH_INPUT, ARIA_E_INVALID}, {ERRBIT_GRAPH_LARGE, ARIA_E_TOO_LARGE}});
 }
 
 int aria_graph_optimize_batch_device(aria_graph_t h, double* d_poses, const int* d_vertex_offset, const aria_graph_edge* d_edges,

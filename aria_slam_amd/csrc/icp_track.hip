@@ -379,8 +379,8 @@ struct aria_icp_s : StageHandle {
     DeviceBuffer<long long> d_acc;
     // host-form staging (grow-only)
     DeviceBuffer<float> d_live, d_depth, d_normal;
-    double* d_pose = nullptr;                                  // Tm, T0, T: 36 doubles
-    aria_icp_result* d_rec = nullptr;
+    DeviceBuffer<double> d_pose;                               // Tm, T0, T: 36 doubles
+    DeviceBuffer<aria_icp_result> d_rec;
 };
 
 namespace {
@@ -461,42 +461,21 @@ int64_t aria_icp_algorithmic_bytes(const aria_icp_config* c, int width, int heig
 
 int aria_icp_create(const aria_icp_config* c, aria_icp_t* out) {
     if (!out || icp_bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_icp_s* h = new (std::nothrow) aria_icp_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    const double K[4] = {c->fx, c->fy, c->cx, c->cy};
-    h->P = icp_params(K, c->min_depth, c->max_depth, c->dist_max, c->reach, c->min_corr, c->min_pivot, c->eps);
-    if (const char* s = aria_getenv("ARIA_ICP_SCHEDULE")) h->plain = !std::strcmp(s, "plain");   // variants build: A/B
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_icp_create");
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_pose, 36 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_rec, sizeof(aria_icp_result));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_icp_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_icp_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_icp_create", [](aria_icp_s* h) {
+        const aria_icp_config& c = h->cfg;
+        const double K[4] = {c.fx, c.fy, c.cx, c.cy};
+        h->P = icp_params(K, c.min_depth, c.max_depth, c.dist_max, c.reach, c.min_corr, c.min_pivot, c.eps);
+        if (const char* s = aria_getenv("ARIA_ICP_SCHEDULE")) h->plain = !std::strcmp(s, "plain");   // variants build: A/B
+        const int rc = h->d_pose.reserve(h->stream, 36, "aria_icp_create");
+        return rc != ARIA_OK ? rc : h->d_rec.reserve(h->stream, 1, "aria_icp_create");
+    });
 }
 
-void aria_icp_destroy(aria_icp_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_pose, h->d_rec});
-    delete h;
-}
+void aria_icp_destroy(aria_icp_t h) { stage_destroy(h); }
 
-void* aria_icp_stream(aria_icp_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_icp_stream(aria_icp_t h) { return stage_stream(h); }
 
-int aria_icp_check(aria_icp_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_ICP_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_icp_check(aria_icp_t h) { return stage_check(h, {{ERRBIT_ICP_INPUT, ARIA_E_INVALID}}); }
 
 int aria_icp_track_batch_device(aria_icp_t h, const float* d_depth, int64_t depth_stride, int depth_pitch, const float* d_model_depth,
                                 int64_t model_depth_stride, int model_depth_pitch, const float* d_model_normal, int64_t normal_stride,

@@ -635,27 +635,13 @@ __global__ void k_visual_from_pose(const aria_pose_result* __restrict__ res, con
 struct aria_fuse_s : StageHandle {
     aria_fuse_config cfg{};
     // staging of the host forms (aria_fuse_run, aria_fuse_preintegrate), grown on demand
-    void* d_buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[6] = {0, 0, 0, 0, 0, 0};
+    DeviceBuffer<uint8_t> d_buf[6];   // bytes: each host form lays its own arrays over the slots
 };
 
 namespace {
 
 // staging slot `k` of at least `bytes` bytes (never empty); the stream is idle whenever a host form grows one
-hipError_t fuse_reserve(aria_fuse_t h, int k, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 64);
-    if (h->cap[k] >= bytes) return hipSuccess;
-    if (h->d_buf[k]) {
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return e;
-        (void)hipFree(h->d_buf[k]);
-        h->d_buf[k] = nullptr;
-        h->cap[k] = 0;
-    }
-    hipError_t e = hipMalloc(&h->d_buf[k], bytes);
-    if (e == hipSuccess) h->cap[k] = bytes;
-    return e;
-}
+int fuse_reserve(aria_fuse_t h, int k, size_t bytes) { return h->d_buf[k].reserve(h->stream, std::max<size_t>(bytes, 64)); }
 
 }  // namespace
 
@@ -701,34 +687,14 @@ int aria_fuse_filter_init(aria_fuse_filter* f, const aria_fuse_config* cfg) {
 
 int aria_fuse_create(const aria_fuse_config* c, aria_fuse_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_fuse_config)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_fuse_s* h = new (std::nothrow) aria_fuse_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    const int rc = stage_open(h, c->device, c->stream, 1, "aria_fuse_create");
-    if (rc != ARIA_OK) {
-        aria_fuse_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_fuse_create", [](aria_fuse_s*) { return (int)ARIA_OK; });
 }
 
-void aria_fuse_destroy(aria_fuse_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_buf[0], h->d_buf[1], h->d_buf[2], h->d_buf[3], h->d_buf[4], h->d_buf[5]});
-    delete h;
-}
+void aria_fuse_destroy(aria_fuse_t h) { stage_destroy(h); }
 
-void* aria_fuse_stream(aria_fuse_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_fuse_stream(aria_fuse_t h) { return stage_stream(h); }
 
-int aria_fuse_check(aria_fuse_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_FUSE_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_fuse_check(aria_fuse_t h) { return stage_check(h, {{ERRBIT_FUSE_INPUT, ARIA_E_INVALID}}); }
 
 int aria_fuse_run_batch_device(aria_fuse_t h, aria_fuse_filter* d_filters, const aria_imu_sample* d_imu, const int* d_imu_offset,
                                int n_imu_total, const int* d_imu_end, const aria_fuse_visual* d_visual,
@@ -752,12 +718,13 @@ int aria_fuse_run(aria_fuse_t h, aria_fuse_filter* filter, const aria_imu_sample
         return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
     const size_t NI = (size_t)n_imu, NF = (size_t)n_frames;
-    ARIA_HIP(fuse_reserve(h, 0, sizeof(aria_fuse_filter)));
-    ARIA_HIP(fuse_reserve(h, 1, NI * sizeof(aria_imu_sample)));
-    ARIA_HIP(fuse_reserve(h, 2, NF * sizeof(int)));
-    ARIA_HIP(fuse_reserve(h, 3, NF * sizeof(aria_fuse_visual)));
-    ARIA_HIP(fuse_reserve(h, 4, NF * sizeof(aria_fuse_state)));
-    ARIA_HIP(fuse_reserve(h, 5, 4 * sizeof(int)));
+    int rc;
+    if ((rc = fuse_reserve(h, 0, sizeof(aria_fuse_filter))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 1, NI * sizeof(aria_imu_sample))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 2, NF * sizeof(int))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 3, NF * sizeof(aria_fuse_visual))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 4, NF * sizeof(aria_fuse_state))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 5, 4 * sizeof(int))) != ARIA_OK) return rc;
     const int off[4] = {0, n_imu, 0, n_frames};
     hipStream_t st = h->stream;
     ARIA_HIP(hipMemcpyAsync(h->d_buf[0], filter, sizeof(aria_fuse_filter), hipMemcpyHostToDevice, st));
@@ -765,10 +732,10 @@ int aria_fuse_run(aria_fuse_t h, aria_fuse_filter* filter, const aria_imu_sample
     if (NF) ARIA_HIP(hipMemcpyAsync(h->d_buf[2], imu_end, NF * sizeof(int), hipMemcpyHostToDevice, st));
     if (NF) ARIA_HIP(hipMemcpyAsync(h->d_buf[3], visual, NF * sizeof(aria_fuse_visual), hipMemcpyHostToDevice, st));
     ARIA_HIP(memcpy_on(st, h->d_buf[5], off, sizeof(off), hipMemcpyHostToDevice));
-    const int* d_off = (const int*)h->d_buf[5];
-    int rc = aria_fuse_run_batch_device(h, (aria_fuse_filter*)h->d_buf[0], (const aria_imu_sample*)h->d_buf[1], d_off, n_imu,
-                                        (const int*)h->d_buf[2], (const aria_fuse_visual*)h->d_buf[3], d_off + 2, n_frames, 1,
-                                        (aria_fuse_state*)h->d_buf[4]);
+    const int* d_off = (const int*)h->d_buf[5].p;
+    rc = aria_fuse_run_batch_device(h, (aria_fuse_filter*)h->d_buf[0].p, (const aria_imu_sample*)h->d_buf[1].p, d_off, n_imu,
+                                    (const int*)h->d_buf[2].p, (const aria_fuse_visual*)h->d_buf[3].p, d_off + 2, n_frames, 1,
+                                    (aria_fuse_state*)h->d_buf[4].p);
     if (rc != ARIA_OK) return rc;
     ARIA_HIP(hipMemcpyAsync(filter, h->d_buf[0], sizeof(aria_fuse_filter), hipMemcpyDeviceToHost, st));
     if (NF) ARIA_HIP(hipMemcpyAsync(states, h->d_buf[4], NF * sizeof(aria_fuse_state), hipMemcpyDeviceToHost, st));
@@ -804,19 +771,20 @@ int aria_fuse_preintegrate(aria_fuse_t h, const aria_imu_sample* imu, int n_imu,
     if (n_intervals == 0) return ARIA_OK;
     ARIA_HIP(hipSetDevice(h->device));
     const size_t NI = (size_t)n_imu, N = (size_t)n_intervals;
-    ARIA_HIP(fuse_reserve(h, 0, 6 * sizeof(double)));
-    ARIA_HIP(fuse_reserve(h, 1, NI * sizeof(aria_imu_sample)));
-    ARIA_HIP(fuse_reserve(h, 2, N * sizeof(int)));
-    ARIA_HIP(fuse_reserve(h, 3, N * sizeof(int)));
-    ARIA_HIP(fuse_reserve(h, 4, N * sizeof(aria_preint_result)));
+    int rc;
+    if ((rc = fuse_reserve(h, 0, 6 * sizeof(double))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 1, NI * sizeof(aria_imu_sample))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 2, N * sizeof(int))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 3, N * sizeof(int))) != ARIA_OK) return rc;
+    if ((rc = fuse_reserve(h, 4, N * sizeof(aria_preint_result))) != ARIA_OK) return rc;
     hipStream_t st = h->stream;
     if (bias) ARIA_HIP(hipMemcpyAsync(h->d_buf[0], bias, 6 * sizeof(double), hipMemcpyHostToDevice, st));
     if (NI) ARIA_HIP(hipMemcpyAsync(h->d_buf[1], imu, NI * sizeof(aria_imu_sample), hipMemcpyHostToDevice, st));
     ARIA_HIP(hipMemcpyAsync(h->d_buf[2], begin, N * sizeof(int), hipMemcpyHostToDevice, st));
     ARIA_HIP(memcpy_on(st, h->d_buf[3], end, N * sizeof(int), hipMemcpyHostToDevice));
-    int rc = aria_fuse_preintegrate_batch_device(h, (const aria_imu_sample*)h->d_buf[1], n_imu, (const int*)h->d_buf[2],
-                                                 (const int*)h->d_buf[3], n_intervals, bias ? (const double*)h->d_buf[0] : nullptr,
-                                                 (aria_preint_result*)h->d_buf[4]);
+    rc = aria_fuse_preintegrate_batch_device(h, (const aria_imu_sample*)h->d_buf[1].p, n_imu, (const int*)h->d_buf[2].p,
+                                             (const int*)h->d_buf[3].p, n_intervals, bias ? (const double*)h->d_buf[0].p : nullptr,
+                                             (aria_preint_result*)h->d_buf[4].p);
     if (rc != ARIA_OK) return rc;
     ARIA_HIP(memcpy_on(st, out, h->d_buf[4], N * sizeof(aria_preint_result), hipMemcpyDeviceToHost));
     return aria_fuse_check(h);

@@ -467,8 +467,8 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_fscatter(const aria_map_point
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------
 struct aria_map_s : StageHandle {
     aria_map_config cfg{};
-    long long* d_meta = nullptr;                         // META_* slots
-    double* d_stats = nullptr;                           // mean[3], threshold
+    DeviceBuffer<long long> d_meta;                      // META_* slots
+    DeviceBuffer<double> d_stats;                        // mean[3], threshold
     // the arena and its ping-pong twin (the filters scatter into the other one), `capacity` points each
     aria_map_point* d_arena = nullptr;
     aria_map_point* d_arena2 = nullptr;
@@ -485,7 +485,7 @@ struct aria_map_s : StageHandle {
     // single-pair staging (aria_map_triangulate): the pair, view 1's image, the two extrinsics
     PairStaging pair;
     DeviceBuffer<uint8_t> d_img;
-    double* d_ext = nullptr;                             // 24 doubles
+    DeviceBuffer<double> d_ext;                          // 24 doubles
 };
 
 namespace {
@@ -576,9 +576,8 @@ int reserve(aria_map_t h, int64_t n) {
 }
 
 bool bad_config(const aria_map_config* c) {
-    return !c || c->struct_size != (int)sizeof(aria_map_config) || !(c->fx > 0) || !(c->fy > 0) || !std::isfinite(c->fx) ||
-           !std::isfinite(c->fy) || !std::isfinite(c->cx) || !std::isfinite(c->cy) || !std::isfinite(c->min_depth) ||
-           !std::isfinite(c->max_depth) || !(c->max_depth >= c->min_depth) || !std::isfinite(c->min_parallax_deg) ||
+    return !c || c->struct_size != (int)sizeof(aria_map_config) || bad_pinhole(c->fx, c->fy, c->cx, c->cy) ||
+           !std::isfinite(c->min_depth) || !std::isfinite(c->max_depth) || !(c->max_depth >= c->min_depth) || !std::isfinite(c->min_parallax_deg) ||
            !(c->max_reproj_px >= 0) || !std::isfinite(c->max_reproj_px) || c->capacity < 0 || c->capacity > ((int64_t)1 << 31);
 }
 
@@ -603,45 +602,30 @@ void aria_map_default_config(aria_map_config* c) {
 
 int aria_map_create(const aria_map_config* c, aria_map_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_map_s* h = new (std::nothrow) aria_map_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_map_create");
-    if (rc == ARIA_OK) rc = h->pair.create(h->stream);
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_meta, META_SLOTS * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_stats, 4 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_ext, 24 * sizeof(double));
-        if (e == hipSuccess) e = memset_on(h->stream, h->d_meta, 0, META_SLOTS * sizeof(long long));
+    // reserve() comes last: it alone sets the arenas, so a create that fails has none for stage_create to free
+    return stage_create(c, out, 1, "aria_map_create", [](aria_map_s* h) {
+        const char* what = "aria_map_create";
+        int rc;
+        if ((rc = h->pair.create(h->stream)) != ARIA_OK) return rc;
+        if ((rc = h->d_meta.reserve(h->stream, META_SLOTS, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_stats.reserve(h->stream, 4, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_ext.reserve(h->stream, 24, what)) != ARIA_OK) return rc;
+        hipError_t e = memset_on(h->stream, h->d_meta, 0, META_SLOTS * sizeof(long long));
         if (e == hipSuccess) e = memset_on(h->stream, h->d_stats, 0, 4 * sizeof(double));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_map_create", __FILE__, __LINE__);
-    }
-    if (rc == ARIA_OK) rc = reserve(h, std::max<int64_t>(c->capacity, 1));
-    if (rc != ARIA_OK) {
-        aria_map_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+        if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
+        return reserve(h, std::max<int64_t>(h->cfg.capacity, 1));
+    });
 }
 
 void aria_map_destroy(aria_map_t h) {
     if (!h) return;
-    stage_close(h, {h->d_meta, h->d_stats, h->d_arena, h->d_arena2, h->d_ext});
-    delete h;
+    stage_destroy(h, {h->d_arena, h->d_arena2});   // plain pointers: the filters swap them and reserve() replaces both
 }
 
-void* aria_map_stream(aria_map_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_map_stream(aria_map_t h) { return stage_stream(h); }
 
 int aria_map_check(aria_map_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    if (bits & ERRBIT_MAP_INPUT) return ARIA_E_INVALID;
-    if (bits & ERRBIT_MAP_FULL) return ARIA_E_OUTPUT_TOO_SMALL;
-    return ARIA_OK;
+    return stage_check(h, {{ERRBIT_MAP_INPUT, ARIA_E_INVALID}, {ERRBIT_MAP_FULL, ARIA_E_OUTPUT_TOO_SMALL}});
 }
 
 int aria_map_triangulate(aria_map_t h, const aria_keypoint* kp_query, int nq, const aria_keypoint* kp_train, int nt,

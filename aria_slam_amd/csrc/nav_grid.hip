@@ -303,15 +303,13 @@ struct aria_nav_s : StageHandle {
     int plain = 0;                                             // variants build: ARIA_NAV_SCHEDULE=plain
     bool stale = true;                                         // the map changed since the last solve (or there was none)
     int n_goals = 0;
-    uint8_t* d_cells = nullptr;
-    uint8_t* d_span = nullptr;
-    uint16_t* d_d2 = nullptr;
-    uint16_t* d_cost = nullptr;
-    uint32_t* d_cm = nullptr;
-    int32_t* d_fields = nullptr;                               // max_goals x nv x nu
-    int32_t* d_goals = nullptr;                                // 2 x max_goals: the goals of the last solve
-    int* d_rounds = nullptr;                                   // max_goals
-    int* d_bad = nullptr;                                      // the refusal word of a set_cells call
+    DeviceBuffer<uint8_t> d_cells, d_span;
+    DeviceBuffer<uint16_t> d_d2, d_cost;
+    DeviceBuffer<uint32_t> d_cm;
+    DeviceBuffer<int32_t> d_fields;                            // max_goals x nv x nu
+    DeviceBuffer<int32_t> d_goals;                             // 2 x max_goals: the goals of the last solve
+    DeviceBuffer<int> d_rounds;                                // max_goals
+    DeviceBuffer<int> d_bad;                                   // the refusal word of a set_cells call
     // host-form staging (grow-only)
     DeviceBuffer<uint8_t> d_in;
     DeviceBuffer<int32_t> d_queries, d_paths;
@@ -393,68 +391,51 @@ int64_t aria_nav_field_bytes(int nu, int nv, int max_goals) {
 
 int aria_nav_create(const aria_nav_config* c, aria_nav_t* out) {
     if (!out || nav_bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_nav_s* h = new (std::nothrow) aria_nav_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    NavParams& P = h->P;
-    P.nx = c->nx; P.ny = c->ny; P.nz = c->nz; P.up_axis = c->up_axis; P.band0 = c->band0; P.band1 = c->band1;
-    P.nu = c->up_axis == 0 ? c->ny : c->nx;
-    P.nv = c->up_axis == 2 ? c->ny : c->nz;
-    P.min_weight = c->min_weight; P.occ_count = c->occ_count; P.free_count = c->free_count; P.occ_tsdf = c->occ_tsdf;
-    P.radius = c->clear_radius; P.block_d2 = c->block_d2; P.soft_d2 = c->soft_d2; P.penalty = c->penalty;
-    P.unknown_penalty = c->unknown_penalty; P.allow_unknown = c->allow_unknown;
-    h->n = P.nu * P.nv;
-    h->lds_bytes = (size_t)4 * (P.nu + 1) * P.nv;
-    h->lds = h->lds_bytes + 64 <= (size_t)NAV_LDS_BYTES;                 // 64: the changed words and alignment
-    if (const char* s = aria_getenv("ARIA_NAV_SCHEDULE")) h->plain = !std::strcmp(s, "plain");   // variants build: A/B
-    if (h->plain) h->lds = false;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_nav_create");
-    if (rc == ARIA_OK) {
-        const size_t n = (size_t)h->n;
-        hipError_t e = hipMalloc((void**)&h->d_cells, n);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_span, n);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_d2, n * 2);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_cost, n * 2);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_cm, n * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_fields, n * 4 * (size_t)c->max_goals);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_goals, sizeof(int32_t) * 2 * (size_t)c->max_goals);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_rounds, sizeof(int) * (size_t)c->max_goals);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_bad, sizeof(int));
+    return stage_create(c, out, 1, "aria_nav_create", [](aria_nav_s* h) {
+        const aria_nav_config& c = h->cfg;
+        const char* what = "aria_nav_create";
+        NavParams& P = h->P;
+        P.nx = c.nx; P.ny = c.ny; P.nz = c.nz; P.up_axis = c.up_axis; P.band0 = c.band0; P.band1 = c.band1;
+        P.nu = c.up_axis == 0 ? c.ny : c.nx;
+        P.nv = c.up_axis == 2 ? c.ny : c.nz;
+        P.min_weight = c.min_weight; P.occ_count = c.occ_count; P.free_count = c.free_count; P.occ_tsdf = c.occ_tsdf;
+        P.radius = c.clear_radius; P.block_d2 = c.block_d2; P.soft_d2 = c.soft_d2; P.penalty = c.penalty;
+        P.unknown_penalty = c.unknown_penalty; P.allow_unknown = c.allow_unknown;
+        h->n = P.nu * P.nv;
+        h->lds_bytes = (size_t)4 * (P.nu + 1) * P.nv;
+        h->lds = h->lds_bytes + 64 <= (size_t)NAV_LDS_BYTES;             // 64: the changed words and alignment
+        if (const char* s = aria_getenv("ARIA_NAV_SCHEDULE")) h->plain = !std::strcmp(s, "plain");   // variants build: A/B
+        if (h->plain) h->lds = false;
+        const size_t n = (size_t)h->n, goals = (size_t)c.max_goals;
+        int rc;
+        if ((rc = h->d_cells.reserve(h->stream, n, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_span.reserve(h->stream, n, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_d2.reserve(h->stream, n, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_cost.reserve(h->stream, n, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_cm.reserve(h->stream, n, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_fields.reserve(h->stream, n * goals, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_goals.reserve(h->stream, 2 * goals, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_rounds.reserve(h->stream, goals, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_bad.reserve(h->stream, 1, what)) != ARIA_OK) return rc;
         // a property of the function, not of the handle: always the most the stage uses, so that handles of different planes
         // cannot lower it under one another
-        if (e == hipSuccess && h->lds)
+        hipError_t e = hipSuccess;
+        if (h->lds)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nav_field<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     NAV_LDS_BYTES - 64);
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_cells, 2, n, h->stream);            // a new handle: every cell UNKNOWN
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_rounds, 0, sizeof(int) * (size_t)c->max_goals, h->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "aria_nav_create", __FILE__, __LINE__);
-        if (rc == ARIA_OK) rc = nav_rebuild(h);
-    }
-    if (rc != ARIA_OK) {
-        aria_nav_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_cells, 2, n, h->stream);                // a new handle: every cell UNKNOWN
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_rounds, 0, sizeof(int) * goals, h->stream);
+        if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
+        return nav_rebuild(h);
+    });
 }
 
-void aria_nav_destroy(aria_nav_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_cells, h->d_span, h->d_d2, h->d_cost, h->d_cm, h->d_fields, h->d_goals, h->d_rounds, h->d_bad});
-    delete h;
-}
+void aria_nav_destroy(aria_nav_t h) { stage_destroy(h); }
 
-void* aria_nav_stream(aria_nav_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_nav_stream(aria_nav_t h) { return stage_stream(h); }
 
 int aria_nav_check(aria_nav_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    if (bits & ERRBIT_NAV_INPUT) return ARIA_E_INVALID;
-    if (bits & ERRBIT_NAV_FIELD) return ARIA_E_OVERFLOW;
-    return (bits & ERRBIT_NAV_CAP) ? ARIA_E_OUTPUT_TOO_SMALL : ARIA_OK;
+    return stage_check(h, {{ERRBIT_NAV_INPUT, ARIA_E_INVALID}, {ERRBIT_NAV_FIELD, ARIA_E_OVERFLOW}, {ERRBIT_NAV_CAP, ARIA_E_OUTPUT_TOO_SMALL}});
 }
 
 int aria_nav_update_from_volume_device(aria_nav_t h, const aria_tsdf_voxel* d_voxels) {
@@ -489,9 +470,9 @@ int aria_nav_set_cells(aria_nav_t h, const uint8_t* cells) {
     return aria_nav_check(h);
 }
 
-int aria_nav_read_cells(aria_nav_t h, uint8_t* out) { return nav_read(h, out, h ? h->d_cells : nullptr, h ? (size_t)h->n : 0); }
-int aria_nav_read_clearance(aria_nav_t h, uint16_t* out) { return nav_read(h, out, h ? h->d_d2 : nullptr, h ? (size_t)h->n * 2 : 0); }
-int aria_nav_read_costs(aria_nav_t h, uint16_t* out) { return nav_read(h, out, h ? h->d_cost : nullptr, h ? (size_t)h->n * 2 : 0); }
+int aria_nav_read_cells(aria_nav_t h, uint8_t* out) { return nav_read(h, out, h ? h->d_cells.p : nullptr, h ? (size_t)h->n : 0); }
+int aria_nav_read_clearance(aria_nav_t h, uint16_t* out) { return nav_read(h, out, h ? h->d_d2.p : nullptr, h ? (size_t)h->n * 2 : 0); }
+int aria_nav_read_costs(aria_nav_t h, uint16_t* out) { return nav_read(h, out, h ? h->d_cost.p : nullptr, h ? (size_t)h->n * 2 : 0); }
 
 int aria_nav_solve_device(aria_nav_t h, const int32_t* d_goals, int n_goals) {
     if (!h || n_goals < 0 || n_goals > h->cfg.max_goals || (n_goals > 0 && !d_goals)) return ARIA_E_INVALID;
@@ -550,7 +531,7 @@ int aria_nav_plan(aria_nav_t h, const int32_t* goals, int n_goals, const int32_t
     return aria_nav_check(h);
 }
 
-int32_t* aria_nav_device_fields(aria_nav_t h) { return h ? h->d_fields : nullptr; }
+int32_t* aria_nav_device_fields(aria_nav_t h) { return h ? h->d_fields.p : nullptr; }
 
 int aria_nav_read_field(aria_nav_t h, int g, int32_t* out) {
     if (!h || !out || h->stale || g < 0 || g >= h->n_goals) return ARIA_E_INVALID;

@@ -898,19 +898,14 @@ struct aria_pnp_s : StageHandle {
     DeviceBuffer<uint8_t> d_ws;           // [n_pairs][corr_cap] inlier flags
     DeviceBuffer<int> d_table;            // [n_pairs][kp_stride] association table
     // single-pair staging of the host forms
-    DeviceBuffer<aria_pnp_corr> d_corr1;
-    DeviceBuffer<uint8_t> d_mask1;
+    CorrStaging<aria_pnp_corr> one;
+    DeviceBuffer<aria_pnp_result> d_res;
     DeviceBuffer<int> d_dbg;
-    int* d_n1 = nullptr;
-    aria_pnp_result* d_res = nullptr;
 };
 
 namespace {
 
-float pnp_thr2(const aria_pnp_config& c) {
-    const double t = c.threshold_px / ((c.fx + c.fy) * 0.5);
-    return (float)(t * t);
-}
+float pnp_thr2(const aria_pnp_config& c) { return normalized_thr2(c.threshold_px, c.fx, c.fy); }
 
 int enqueue(aria_pnp_t h, const aria_pnp_corr* d_corr, const int* d_ncorr, int n_pairs, int corr_cap, int pair_base,
             aria_pnp_result* d_out, uint8_t* d_mask, int* d_dbg, bool finish) {
@@ -942,18 +937,6 @@ int enqueue(aria_pnp_t h, const aria_pnp_corr* d_corr, const int* d_ncorr, int n
     return ARIA_OK;
 }
 
-// uploads one pair for the host forms; *cap = what the batch form is told
-int stage_one(aria_pnp_t h, const aria_pnp_corr* corr, int n, int* cap) {
-    if (n < 0 || n > (1 << 20) || (n && !corr)) return ARIA_E_INVALID;
-    *cap = std::max(n, 1);
-    int rc;
-    if ((rc = h->d_corr1.reserve(h->stream, (size_t)*cap)) != ARIA_OK) return rc;
-    if ((rc = h->d_mask1.reserve(h->stream, (size_t)*cap)) != ARIA_OK) return rc;
-    if (n) ARIA_HIP(hipMemcpyAsync(h->d_corr1, corr, sizeof(aria_pnp_corr) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    ARIA_HIP(memcpy_on(h->stream, h->d_n1, &n, sizeof(int), hipMemcpyHostToDevice));
-    return ARIA_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -975,34 +958,16 @@ int aria_pnp_create(const aria_pnp_config* c, aria_pnp_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_pnp_config)) return ARIA_E_INVALID;
     if (c->hypotheses < 64 || c->hypotheses > 16384 || (c->hypotheses % 64)) return ARIA_E_INVALID;
     if (c->refine_iters < 0 || c->refine_iters > 16) return ARIA_E_INVALID;
-    if (!(c->fx > 0) || !(c->fy > 0) || !std::isfinite(c->cx) || !std::isfinite(c->cy) || !(c->threshold_px > 0) ||
-        !std::isfinite(c->fx) || !std::isfinite(c->fy) || !std::isfinite(c->threshold_px))
-        return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_pnp_s* h = new (std::nothrow) aria_pnp_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_pnp_create");
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_res, sizeof(aria_pnp_result));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_n1, sizeof(int));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_pnp_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_pnp_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    if (bad_pinhole(c->fx, c->fy, c->cx, c->cy) || !(c->threshold_px > 0) || !std::isfinite(c->threshold_px)) return ARIA_E_INVALID;
+    return stage_create(c, out, 1, "aria_pnp_create", [](aria_pnp_s* h) {
+        const int rc = h->d_res.reserve(h->stream, 1, "aria_pnp_create");
+        return rc != ARIA_OK ? rc : h->one.create(h->stream, "aria_pnp_create");
+    });
 }
 
-void aria_pnp_destroy(aria_pnp_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_res, h->d_n1});
-    delete h;
-}
+void aria_pnp_destroy(aria_pnp_t h) { stage_destroy(h); }
 
-void* aria_pnp_stream(aria_pnp_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_pnp_stream(aria_pnp_t h) { return stage_stream(h); }
 
 int aria_pnp_set_solver(aria_pnp_t h, int solver) {
     if (!h || (solver != ARIA_PNP_SOLVER_DLT6 && solver != ARIA_PNP_SOLVER_P3P)) return ARIA_E_INVALID;
@@ -1012,13 +977,7 @@ int aria_pnp_set_solver(aria_pnp_t h, int solver) {
 
 int aria_pnp_get_solver(aria_pnp_t h) { return h ? h->solver : ARIA_E_INVALID; }
 
-int aria_pnp_check(aria_pnp_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_PNP_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_pnp_check(aria_pnp_t h) { return stage_check(h, {{ERRBIT_PNP_INPUT, ARIA_E_INVALID}}); }
 
 int aria_pnp_estimate_batch_device(aria_pnp_t h, const aria_pnp_corr* d_corr, const int* d_ncorr, int n_pairs, int corr_cap,
                                    int pair_base, aria_pnp_result* d_out, uint8_t* d_mask) {
@@ -1032,12 +991,12 @@ int aria_pnp_estimate_batch_device(aria_pnp_t h, const aria_pnp_corr* d_corr, co
 int aria_pnp_estimate(aria_pnp_t h, const aria_pnp_corr* corr, int n, int pair_base, aria_pnp_result* out, uint8_t* mask) {
     if (!h || !out || pair_base < 0) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int cap = 1;
-    int rc = stage_one(h, corr, n, &cap);
+    CorrStaging<aria_pnp_corr>& s = h->one;
+    int rc = s.upload(h->stream, corr, n);
     if (rc != ARIA_OK) return rc;
-    if ((rc = enqueue(h, h->d_corr1, h->d_n1, 1, cap, pair_base, h->d_res, h->d_mask1, nullptr, true)) != ARIA_OK) return rc;
+    if ((rc = enqueue(h, s.d_corr, s.d_n, 1, s.cap, pair_base, h->d_res, s.d_mask, nullptr, true)) != ARIA_OK) return rc;
     ARIA_HIP(hipMemcpyAsync(out, h->d_res, sizeof(aria_pnp_result), hipMemcpyDeviceToHost, h->stream));
-    if (mask && n) ARIA_HIP(hipMemcpyAsync(mask, h->d_mask1, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (mask && n) ARIA_HIP(hipMemcpyAsync(mask, s.d_mask, (size_t)n, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
     return aria_pnp_check(h);
 }
@@ -1046,21 +1005,18 @@ int aria_pnp_debug_hypotheses(aria_pnp_t h, const aria_pnp_corr* corr, int n, in
                               int* counts) {
     if (!h || !sample_idx || !R || !t0 || !counts || pair_base < 0) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int cap = 1;
-    int rc = stage_one(h, corr, n, &cap);
+    int rc = h->one.upload(h->stream, corr, n);
     if (rc != ARIA_OK) return rc;
     const int H = h->cfg.hypotheses;
     if ((rc = h->d_dbg.reserve(h->stream, (size_t)H * 6)) != ARIA_OK) return rc;
-    if ((rc = enqueue(h, h->d_corr1, h->d_n1, 1, cap, pair_base, nullptr, nullptr, h->d_dbg, false)) != ARIA_OK) return rc;
+    if ((rc = enqueue(h, h->one.d_corr, h->one.d_n, 1, h->one.cap, pair_base, nullptr, nullptr, h->d_dbg, false)) != ARIA_OK) return rc;
     std::vector<float> soa((size_t)12 * H);
     ARIA_HIP(hipMemcpyAsync(sample_idx, h->d_dbg, sizeof(int) * 6 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(soa.data(), h->d_P, sizeof(float) * 12 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(counts, h->d_cnt, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < H; i++) {
-        for (int k = 0; k < 9; k++) R[(size_t)i * 9 + k] = soa[(size_t)k * H + i];
-        for (int k = 0; k < 3; k++) t0[(size_t)i * 3 + k] = soa[(size_t)(9 + k) * H + i];
-    }
+    unpack_models(soa.data(), H, 0, 9, R);
+    unpack_models(soa.data(), H, 9, 3, t0);
     return aria_pnp_check(h);
 }
 

@@ -471,16 +471,13 @@ struct aria_pose_s : StageHandle {
     DeviceBuffer<int> d_cnt;              // [n_pairs][H]
     DeviceBuffer<uint8_t> d_ws;           // [n_pairs][match_cap] inlier flags
     PairStaging pair;                     // aria_pose_estimate, aria_pose_debug_hypotheses
-    aria_pose_result* d_res = nullptr;
+    DeviceBuffer<aria_pose_result> d_res;
     DeviceBuffer<int> d_dbg;
 };
 
 namespace {
 
-float pose_thr2(const aria_pose_config& c) {
-    const double t = c.threshold_px / ((c.fx + c.fy) * 0.5);
-    return (float)(t * t);
-}
+float pose_thr2(const aria_pose_config& c) { return normalized_thr2(c.threshold_px, c.fx, c.fy); }
 
 int enqueue(aria_pose_t h, const aria_keypoint* d_kq, const int* d_nq, const aria_keypoint* d_kt, const int* d_nt,
             int64_t kp_stride, const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap, int query_is_first,
@@ -510,7 +507,7 @@ int enqueue(aria_pose_t h, const aria_keypoint* d_kq, const int* d_nq, const ari
 int enqueue_staged(aria_pose_t h, int query_is_first, int pair_base, int* d_dbg, bool finish) {
     const PairStaging& s = h->pair;
     return enqueue(h, s.d_kq, s.d_counts, s.d_kt, s.d_counts + 1, s.kp_stride, s.d_m, s.d_counts + 2, 1, s.match_cap, query_is_first,
-                   pair_base, finish ? h->d_res : nullptr, finish ? s.d_mask.p : nullptr, d_dbg, finish);
+                   pair_base, finish ? h->d_res.p : nullptr, finish ? s.d_mask.p : nullptr, d_dbg, finish);
 }
 
 }  // namespace
@@ -533,42 +530,18 @@ void aria_pose_default_config(aria_pose_config* c) {
 int aria_pose_create(const aria_pose_config* c, aria_pose_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_pose_config)) return ARIA_E_INVALID;
     if (c->hypotheses < 64 || c->hypotheses > 16384 || (c->hypotheses % 64)) return ARIA_E_INVALID;
-    if (!(c->fx > 0) || !(c->fy > 0) || !std::isfinite(c->cx) || !std::isfinite(c->cy) || !(c->threshold_px > 0) ||
-        !(c->distance_thresh > 0) || !std::isfinite(c->fx) || !std::isfinite(c->fy))
-        return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_pose_s* h = new (std::nothrow) aria_pose_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_pose_create");
-    if (rc == ARIA_OK) rc = h->pair.create(h->stream);
-    if (rc == ARIA_OK) {
-        const hipError_t e = hipMalloc((void**)&h->d_res, sizeof(aria_pose_result));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_pose_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_pose_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    if (bad_pinhole(c->fx, c->fy, c->cx, c->cy) || !(c->threshold_px > 0) || !(c->distance_thresh > 0)) return ARIA_E_INVALID;
+    return stage_create(c, out, 1, "aria_pose_create", [](aria_pose_s* h) {
+        const int rc = h->pair.create(h->stream);
+        return rc != ARIA_OK ? rc : h->d_res.reserve(h->stream, 1, "aria_pose_create");
+    });
 }
 
-void aria_pose_destroy(aria_pose_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_res});
-    delete h;
-}
+void aria_pose_destroy(aria_pose_t h) { stage_destroy(h); }
 
-void* aria_pose_stream(aria_pose_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_pose_stream(aria_pose_t h) { return stage_stream(h); }
 
-int aria_pose_check(aria_pose_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_POSE_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_pose_check(aria_pose_t h) { return stage_check(h, {{ERRBIT_POSE_INPUT, ARIA_E_INVALID}}); }
 
 int aria_pose_estimate_batch_device(aria_pose_t h, const aria_keypoint* d_kp_query, const int* d_nq,
                                     const aria_keypoint* d_kp_train, const int* d_nt, int64_t kp_stride,
@@ -612,8 +585,7 @@ int aria_pose_debug_hypotheses(aria_pose_t h, const aria_keypoint* kp_query, int
     ARIA_HIP(hipMemcpyAsync(soa.data(), h->d_E, sizeof(float) * 9 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(counts, h->d_cnt, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < H; i++)
-        for (int k = 0; k < 9; k++) E[(size_t)i * 9 + k] = soa[(size_t)k * H + i];
+    unpack_models(soa.data(), H, 0, 9, E);
     return aria_pose_check(h);
 }
 

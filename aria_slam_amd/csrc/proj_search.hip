@@ -409,8 +409,8 @@ struct aria_proj_s : StageHandle {
     DeviceBuffer<aria_proj_obs> d_obs;
     DeviceBuffer<aria_pnp_corr> d_corr;
     DeviceBuffer<aria_proj_pair> d_pairs;
-    double* d_pose = nullptr;              // 12 doubles
-    int* d_counts = nullptr;               // n, first, count, n_corr
+    DeviceBuffer<double> d_pose;           // 12 doubles
+    DeviceBuffer<int> d_counts;            // n, first, count, n_corr
 };
 
 namespace {
@@ -418,8 +418,7 @@ namespace {
 bool fin(double v) { return std::isfinite(v); }
 
 bool bad_config(const aria_proj_config* c) {
-    return !c || c->struct_size != (int)sizeof(aria_proj_config) || !(c->fx > 0) || !(c->fy > 0) || !fin(c->fx) || !fin(c->fy) ||
-           !fin(c->cx) || !fin(c->cy) || !fin(c->min_depth) || !(c->radius_px >= 0) || !(c->radius_px <= 1024) ||
+    return !c || c->struct_size != (int)sizeof(aria_proj_config) || bad_pinhole(c->fx, c->fy, c->cx, c->cy) || !fin(c->min_depth) || !(c->radius_px >= 0) || !(c->radius_px <= 1024) ||
            !(c->ratio >= 0) || !(c->ratio <= 1) || c->th_hamming < 0 || c->th_hamming > 257 || c->max_octave_diff < 0 ||
            c->max_octave_diff > kLevels;
 }
@@ -453,43 +452,23 @@ void aria_proj_default_config(aria_proj_config* c) {
 
 int aria_proj_create(const aria_proj_config* c, aria_proj_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_proj_s* h = new (std::nothrow) aria_proj_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    h->prm = make_params(*c);
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_proj_create");
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_pose, 12 * sizeof(double));
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_bin), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    PJ_MAX_CELLS * (int)sizeof(int));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_proj_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_proj_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_proj_create", [](aria_proj_s* h) {
+        const char* what = "aria_proj_create";
+        h->prm = make_params(h->cfg);
+        int rc;
+        if ((rc = h->d_counts.reserve(h->stream, 4, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_pose.reserve(h->stream, 12, what)) != ARIA_OK) return rc;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_bin), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 PJ_MAX_CELLS * (int)sizeof(int));
+        return e == hipSuccess ? (int)ARIA_OK : hip_fail(e, what, __FILE__, __LINE__);
+    });
 }
 
-void aria_proj_destroy(aria_proj_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_counts, h->d_pose});
-    delete h;
-}
+void aria_proj_destroy(aria_proj_t h) { stage_destroy(h); }
 
-void* aria_proj_stream(aria_proj_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_proj_stream(aria_proj_t h) { return stage_stream(h); }
 
-int aria_proj_check(aria_proj_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_PROJ_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_proj_check(aria_proj_t h) { return stage_check(h, {{ERRBIT_PROJ_INPUT, ARIA_E_INVALID}}); }
 
 int aria_proj_search_batch_device(aria_proj_t h, const double* d_pose, const aria_keypoint* d_kp, const uint8_t* d_desc,
                                   const int* d_n, int64_t kp_stride, int width, int height, const aria_proj_landmark* d_land,

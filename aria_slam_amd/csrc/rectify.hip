@@ -422,11 +422,11 @@ struct aria_rect_s : StageHandle {
     int map_pitch = 0;
     int group = RECT_GROUP;
     bool read_lds = false, read_taps = false;                  // variants build only
-    uint32_t* d_map = nullptr;                                 // n_cameras * map_pitch * dst_height
+    DeviceBuffer<uint32_t> d_map;                              // n_cameras * map_pitch * dst_height
     // single-image staging of the blocking host forms (grow-only)
     DeviceBuffer<uint8_t> d_img;                               // source then destination
     DeviceBuffer<aria_keypoint> d_kp;
-    int* d_count = nullptr;
+    DeviceBuffer<int> d_count;
 };
 
 namespace {
@@ -434,7 +434,7 @@ namespace {
 bool fin(double v) { return std::isfinite(v); }
 
 bool bad_camera(const aria_rect_camera& c) {
-    bool bad = !(c.fx > 0) || !(c.fy > 0) || !fin(c.fx) || !fin(c.fy) || !fin(c.cx) || !fin(c.cy);
+    bool bad = bad_pinhole(c.fx, c.fy, c.cx, c.cy);
     for (double v : c.dist) bad |= !fin(v);
     for (double v : c.R) bad |= !fin(v);
     return bad;
@@ -446,7 +446,7 @@ bool bad_config(const aria_rect_config* c) {
         c->dst_height < 1 || c->dst_width > RECT_MAX_DIM || c->dst_height > RECT_MAX_DIM || c->n_cameras < 1 || c->n_cameras > 2 ||
         c->fill < 0 || c->fill > 255)
         return true;
-    if (!(c->new_fx > 0) || !(c->new_fy > 0) || !fin(c->new_fx) || !fin(c->new_fy) || !fin(c->new_cx) || !fin(c->new_cy)) return true;
+    if (bad_pinhole(c->new_fx, c->new_fy, c->new_cx, c->new_cy)) return true;
     if (c->model != ARIA_RECT_MODEL_RADTAN && c->model != ARIA_RECT_MODEL_KB4) return true;
     for (int k = 0; k < c->n_cameras; k++)
         if (bad_camera(c->cam[k]) || (c->model == ARIA_RECT_MODEL_KB4 && c->cam[k].dist[4] != 0.0)) return true;
@@ -547,56 +547,35 @@ int aria_rect_stereo_geometry(const double* K_l, const double* K_r, const double
 
 int aria_rect_create(const aria_rect_config* c, aria_rect_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_rect_s* h = new (std::nothrow) aria_rect_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    h->map_pitch = (c->dst_width + 3) & ~3;
-    if (const char* g = aria_getenv("ARIA_RECT_GROUP")) h->group = std::min(std::max(std::atoi(g), 1), 64);   // variants build: A/B
-    if (const char* r = aria_getenv("ARIA_RECT_READ")) {
-        h->read_lds = !std::strcmp(r, "lds");
-        h->read_taps = !std::strcmp(r, "taps");
-    }
-    for (int k = 0; k < c->n_cameras; k++) h->cam[k] = make_cam(*c, k);
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_rect_create");
-    if (rc == ARIA_OK) {
-        const size_t words = (size_t)h->map_pitch * c->dst_height;
-        hipError_t e = hipMalloc((void**)&h->d_map, words * c->n_cameras * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_count, sizeof(int));
-        if (e == hipSuccess) {
-            const auto build = c->model == ARIA_RECT_MODEL_KB4 ? k_rect_build_map_kb4 : k_rect_build_map;
-            for (int k = 0; k < c->n_cameras; k++)
-                hipLaunchKernelGGL(build, dim3((unsigned)((words + RECT_BLOCK - 1) / RECT_BLOCK)), dim3(RECT_BLOCK), 0,
-                                   h->stream, h->cam[k], c->src_width, c->src_height, c->dst_width, c->dst_height, h->map_pitch,
-                                   h->d_map + k * words);
-            e = hipGetLastError();
+    return stage_create(c, out, 1, "aria_rect_create", [](aria_rect_s* h) {
+        const aria_rect_config& c = h->cfg;
+        const char* what = "aria_rect_create";
+        h->map_pitch = (c.dst_width + 3) & ~3;
+        if (const char* g = aria_getenv("ARIA_RECT_GROUP")) h->group = std::min(std::max(std::atoi(g), 1), 64);   // variants build: A/B
+        if (const char* r = aria_getenv("ARIA_RECT_READ")) {
+            h->read_lds = !std::strcmp(r, "lds");
+            h->read_taps = !std::strcmp(r, "taps");
         }
+        for (int k = 0; k < c.n_cameras; k++) h->cam[k] = make_cam(c, k);
+        const size_t words = (size_t)h->map_pitch * c.dst_height;
+        int rc;
+        if ((rc = h->d_map.reserve(h->stream, words * c.n_cameras, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_count.reserve(h->stream, 1, what)) != ARIA_OK) return rc;
+        const auto build = c.model == ARIA_RECT_MODEL_KB4 ? k_rect_build_map_kb4 : k_rect_build_map;
+        for (int k = 0; k < c.n_cameras; k++)
+            hipLaunchKernelGGL(build, dim3((unsigned)((words + RECT_BLOCK - 1) / RECT_BLOCK)), dim3(RECT_BLOCK), 0, h->stream,
+                               h->cam[k], c.src_width, c.src_height, c.dst_width, c.dst_height, h->map_pitch, h->d_map + k * words);
+        hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "aria_rect_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_rect_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+        return e == hipSuccess ? (int)ARIA_OK : hip_fail(e, what, __FILE__, __LINE__);
+    });
 }
 
-void aria_rect_destroy(aria_rect_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_map, h->d_count});
-    delete h;
-}
+void aria_rect_destroy(aria_rect_t h) { stage_destroy(h); }
 
-void* aria_rect_stream(aria_rect_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_rect_stream(aria_rect_t h) { return stage_stream(h); }
 
-int aria_rect_check(aria_rect_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_RECT_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_rect_check(aria_rect_t h) { return stage_check(h, {{ERRBIT_RECT_INPUT, ARIA_E_INVALID}}); }
 
 int aria_rect_remap_batch_device(aria_rect_t h, int cam, const uint8_t* d_src, int64_t src_stride, int src_pitch, int n_frames,
                                  uint8_t* d_dst, int64_t dst_stride, int dst_pitch) {

@@ -705,19 +705,14 @@ struct aria_sim3_s : StageHandle {
     DeviceBuffer<uint8_t> d_ws;           // [n_pairs][corr_cap] inlier flags
     DeviceBuffer<int> d_table;            // [2][n_pairs][kp_stride] association tables
     // single-pair staging of the host forms
-    DeviceBuffer<aria_sim3_corr> d_corr1;
-    DeviceBuffer<uint8_t> d_mask1;
+    CorrStaging<aria_sim3_corr> one;
+    DeviceBuffer<aria_sim3_result> d_res;
     DeviceBuffer<int> d_dbg;
-    int* d_n1 = nullptr;
-    aria_sim3_result* d_res = nullptr;
 };
 
 namespace {
 
-float sim3_thr2(const aria_sim3_config& c) {
-    const double t = c.threshold_px / ((c.fx + c.fy) * 0.5);
-    return (float)(t * t);
-}
+float sim3_thr2(const aria_sim3_config& c) { return normalized_thr2(c.threshold_px, c.fx, c.fy); }
 
 int enqueue(aria_sim3_t h, const aria_sim3_corr* d_corr, const int* d_ncorr, int n_pairs, int corr_cap, int pair_base,
             aria_sim3_result* d_out, uint8_t* d_mask, int* d_dbg, bool finish) {
@@ -746,18 +741,6 @@ int enqueue(aria_sim3_t h, const aria_sim3_corr* d_corr, const int* d_ncorr, int
     return ARIA_OK;
 }
 
-// uploads one pair for the host forms; *cap = what the batch form is told
-int stage_one(aria_sim3_t h, const aria_sim3_corr* corr, int n, int* cap) {
-    if (n < 0 || n > (1 << 20) || (n && !corr)) return ARIA_E_INVALID;
-    *cap = std::max(n, 1);
-    int rc;
-    if ((rc = h->d_corr1.reserve(h->stream, (size_t)*cap)) != ARIA_OK) return rc;
-    if ((rc = h->d_mask1.reserve(h->stream, (size_t)*cap)) != ARIA_OK) return rc;
-    if (n) ARIA_HIP(hipMemcpyAsync(h->d_corr1, corr, sizeof(aria_sim3_corr) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    ARIA_HIP(memcpy_on(h->stream, h->d_n1, &n, sizeof(int), hipMemcpyHostToDevice));
-    return ARIA_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -782,43 +765,19 @@ int aria_sim3_create(const aria_sim3_config* c, aria_sim3_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_sim3_config)) return ARIA_E_INVALID;
     if (c->hypotheses < 64 || c->hypotheses > 16384 || (c->hypotheses % 64)) return ARIA_E_INVALID;
     if (c->refine_iters < 0 || c->refine_iters > 16 || (c->fix_scale != 0 && c->fix_scale != 1)) return ARIA_E_INVALID;
-    if (!(c->fx > 0) || !(c->fy > 0) || !std::isfinite(c->cx) || !std::isfinite(c->cy) || !(c->threshold_px > 0) ||
-        !std::isfinite(c->fx) || !std::isfinite(c->fy) || !std::isfinite(c->threshold_px))
-        return ARIA_E_INVALID;
+    if (bad_pinhole(c->fx, c->fy, c->cx, c->cy) || !(c->threshold_px > 0) || !std::isfinite(c->threshold_px)) return ARIA_E_INVALID;
     if (!(c->min_scale > 0) || !(c->max_scale >= c->min_scale) || !std::isfinite(c->max_scale)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_sim3_s* h = new (std::nothrow) aria_sim3_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_sim3_create");
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_res, sizeof(aria_sim3_result));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_n1, sizeof(int));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_sim3_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_sim3_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_sim3_create", [](aria_sim3_s* h) {
+        const int rc = h->d_res.reserve(h->stream, 1, "aria_sim3_create");
+        return rc != ARIA_OK ? rc : h->one.create(h->stream, "aria_sim3_create");
+    });
 }
 
-void aria_sim3_destroy(aria_sim3_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_res, h->d_n1});
-    delete h;
-}
+void aria_sim3_destroy(aria_sim3_t h) { stage_destroy(h); }
 
-void* aria_sim3_stream(aria_sim3_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_sim3_stream(aria_sim3_t h) { return stage_stream(h); }
 
-int aria_sim3_check(aria_sim3_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_SIM3_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_sim3_check(aria_sim3_t h) { return stage_check(h, {{ERRBIT_SIM3_INPUT, ARIA_E_INVALID}}); }
 
 int aria_sim3_estimate_batch_device(aria_sim3_t h, const aria_sim3_corr* d_corr, const int* d_ncorr, int n_pairs, int corr_cap,
                                     int pair_base, aria_sim3_result* d_out, uint8_t* d_mask) {
@@ -832,12 +791,12 @@ int aria_sim3_estimate_batch_device(aria_sim3_t h, const aria_sim3_corr* d_corr,
 int aria_sim3_estimate(aria_sim3_t h, const aria_sim3_corr* corr, int n, int pair_base, aria_sim3_result* out, uint8_t* mask) {
     if (!h || !out || pair_base < 0) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int cap = 1;
-    int rc = stage_one(h, corr, n, &cap);
+    CorrStaging<aria_sim3_corr>& s = h->one;
+    int rc = s.upload(h->stream, corr, n);
     if (rc != ARIA_OK) return rc;
-    if ((rc = enqueue(h, h->d_corr1, h->d_n1, 1, cap, pair_base, h->d_res, h->d_mask1, nullptr, true)) != ARIA_OK) return rc;
+    if ((rc = enqueue(h, s.d_corr, s.d_n, 1, s.cap, pair_base, h->d_res, s.d_mask, nullptr, true)) != ARIA_OK) return rc;
     ARIA_HIP(hipMemcpyAsync(out, h->d_res, sizeof(aria_sim3_result), hipMemcpyDeviceToHost, h->stream));
-    if (mask && n) ARIA_HIP(hipMemcpyAsync(mask, h->d_mask1, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (mask && n) ARIA_HIP(hipMemcpyAsync(mask, s.d_mask, (size_t)n, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
     return aria_sim3_check(h);
 }
@@ -846,22 +805,19 @@ int aria_sim3_debug_hypotheses(aria_sim3_t h, const aria_sim3_corr* corr, int n,
                                float* s, int* counts) {
     if (!h || !sample_idx || !R || !t || !s || !counts || pair_base < 0) return ARIA_E_INVALID;
     ARIA_HIP(hipSetDevice(h->device));
-    int cap = 1;
-    int rc = stage_one(h, corr, n, &cap);
+    int rc = h->one.upload(h->stream, corr, n);
     if (rc != ARIA_OK) return rc;
     const int H = h->cfg.hypotheses;
     if ((rc = h->d_dbg.reserve(h->stream, (size_t)H * 3)) != ARIA_OK) return rc;
-    if ((rc = enqueue(h, h->d_corr1, h->d_n1, 1, cap, pair_base, nullptr, nullptr, h->d_dbg, false)) != ARIA_OK) return rc;
+    if ((rc = enqueue(h, h->one.d_corr, h->one.d_n, 1, h->one.cap, pair_base, nullptr, nullptr, h->d_dbg, false)) != ARIA_OK) return rc;
     std::vector<float> soa((size_t)SIM3_MODEL * H);
     ARIA_HIP(hipMemcpyAsync(sample_idx, h->d_dbg, sizeof(int) * 3 * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(soa.data(), h->d_M, sizeof(float) * SIM3_MODEL * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipMemcpyAsync(counts, h->d_cnt, sizeof(int) * (size_t)H, hipMemcpyDeviceToHost, h->stream));
     ARIA_HIP(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < H; i++) {
-        for (int k = 0; k < 9; k++) R[(size_t)i * 9 + k] = soa[(size_t)k * H + i];
-        for (int k = 0; k < 3; k++) t[(size_t)i * 3 + k] = soa[(size_t)(9 + k) * H + i];
-        s[i] = soa[(size_t)12 * H + i];
-    }
+    unpack_models(soa.data(), H, 0, 9, R);
+    unpack_models(soa.data(), H, 9, 3, t);
+    unpack_models(soa.data(), H, 12, 1, s);
     return aria_sim3_check(h);
 }
 

@@ -1,6 +1,6 @@
-// Host side of what the twenty-one stage handles (aria_pose_t, aria_fund_t, aria_map_t, aria_graph_t, aria_fuse_t, aria_eval_t,
-// aria_det_t, aria_stereo_t, aria_rect_t, aria_dense_t, aria_tsdf_t, aria_nav_t, aria_alert_t, aria_pnp_t, aria_ba_t, aria_ray_t, aria_icp_t, aria_mesh_t, aria_proj_t, aria_bow_t, aria_sim3_t) share: the lifecycle of device, stream and deferred-error words, grow-only device buffers, and
-// the single-pair staging of the blocking host forms that take a match list. Header-only; not part of the public interface.
+// Host side of what every stage handle shares (aria_slam_amd/_lib.py lists them, STAGES): the lifecycle of device, stream and
+// deferred-error words, create / destroy / check over it, grow-only device buffers, the pinhole and threshold forms of the
+// RANSAC stages, and the single-pair staging of the blocking host forms. Header-only; not part of the public interface.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -19,7 +19,7 @@ struct StageHandle {
 };
 
 // Device-range check, hipSetDevice, the caller's stream or a new non-blocking one, d_err allocated and zeroed. `what` names
-// the entry point in aria_last_hip_error(). On failure the caller runs its destroy, which ends in stage_close.
+// the entry point in aria_last_hip_error(). On failure stage_create runs stage_destroy, which starts with stage_close.
 inline int stage_open(StageHandle* h, int device, void* stream, int err_words, const char* what) {
     int ndev = 0;
     ARIA_HIP(hipGetDeviceCount(&ndev));
@@ -41,8 +41,9 @@ inline int stage_open(StageHandle* h, int device, void* stream, int err_words, c
     return e == hipSuccess ? ARIA_OK : hip_fail(e, what, __FILE__, __LINE__);
 }
 
-// Every destroy: the device made current, the stream drained, d_err and the stage's plain device pointers freed, the stream
-// destroyed if the handle made it (a borrowed stream stays the caller's). DeviceBuffer members free themselves with the handle.
+// Every destroy: the device made current, the stream drained, d_err freed, the stream destroyed if the handle made it (a
+// borrowed stream stays the caller's). DeviceBuffer members free themselves with the handle, right after, on this thread and
+// so with the same device current. `bufs` is for plain pointers whose ownership moves between members.
 inline void stage_close(StageHandle* h, std::initializer_list<void*> bufs = {}) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
@@ -52,8 +53,8 @@ inline void stage_close(StageHandle* h, std::initializer_list<void*> bufs = {}) 
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
 }
 
-// Synchronises, reads the first n deferred-error words and clears them when any is set. Each aria_<stage>_check maps the
-// bits to its own status on top of this.
+// Synchronises, reads the first n deferred-error words and clears them when any is set. The checks that read more than
+// one word map the bits themselves on top of this; the others are a stage_check.
 inline int stage_read_errors(StageHandle* h, int* words, int n) {
     ARIA_HIP(hipSetDevice(h->device));
     ARIA_HIP(hipStreamSynchronize(h->stream));
@@ -61,6 +62,48 @@ inline int stage_read_errors(StageHandle* h, int* words, int n) {
     bool any = false;
     for (int k = 0; k < n; k++) any |= words[k] != 0;
     if (any) ARIA_HIP(memset_on(h->stream, h->d_err, 0, n * sizeof(int)));
+    return ARIA_OK;
+}
+
+// aria_<stage>_check of a stage with one error word: the status of the first bit of the list that is set.
+struct ErrStatus {
+    int bit, status;
+};
+inline int stage_check(StageHandle* h, std::initializer_list<ErrStatus> in_priority_order) {
+    if (!h) return ARIA_E_INVALID;
+    int bits = 0;
+    const int rc = stage_read_errors(h, &bits, 1);
+    if (rc != ARIA_OK) return rc;
+    for (const ErrStatus& e : in_priority_order)
+        if (bits & e.bit) return e.status;
+    return ARIA_OK;
+}
+
+inline void* stage_stream(const StageHandle* h) { return h ? (void*)h->stream : nullptr; }
+
+// aria_<stage>_destroy: stage_close, then the handle and with it its DeviceBuffer members.
+template <class S>
+void stage_destroy(S* h, std::initializer_list<void*> bufs = {}) {
+    if (!h) return;
+    stage_close(h, bufs);
+    delete h;
+}
+
+// aria_<stage>_create past the stage's own validation of *c: the handle, its copy of the config, stage_open, then init(h) --
+// the stage's allocations, kernel attributes and derived parameters, returning a status. Any failure destroys the handle.
+template <class S, class Cfg, class Init>
+int stage_create(const Cfg* c, S** out, int err_words, const char* what, Init init) {
+    *out = nullptr;
+    S* h = new (std::nothrow) S();
+    if (!h) return ARIA_E_OOM;
+    h->cfg = *c;
+    int rc = stage_open(h, c->device, c->stream, err_words, what);
+    if (rc == ARIA_OK) rc = init(h);
+    if (rc != ARIA_OK) {
+        stage_destroy(h);
+        return rc;
+    }
+    *out = h;
     return ARIA_OK;
 }
 
@@ -77,7 +120,8 @@ struct DeviceBuffer {
     ~DeviceBuffer() { release(); }
     operator T*() const { return p; }
 
-    int reserve(hipStream_t st, size_t n) {
+    // `what` names the caller in aria_last_hip_error() when the allocation fails: a create passes its own name.
+    int reserve(hipStream_t st, size_t n, const char* what = "hipMalloc") {
         if (n <= cap) return ARIA_OK;
         ARIA_HIP(hipStreamSynchronize(st));   // earlier work on the stream may still read the old block
         T* old = p;
@@ -87,7 +131,7 @@ struct DeviceBuffer {
         const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
         if (e != hipSuccess) {
             p = nullptr;
-            return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+            return hip_fail(e, what, __FILE__, __LINE__);
         }
         cap = n;
         return ARIA_OK;
@@ -145,6 +189,49 @@ struct PairStaging {
         return rc != ARIA_OK ? rc : copy(st, kq, nq, kt, nt, matches, n);
     }
 };
+
+// Single-pair staging of the blocking host forms that take a correspondence list (absolute pose, loop alignment): one pair's
+// records, mask and count in the layout of the batch entry points, n_pairs = 1.
+template <class Corr>
+struct CorrStaging {
+    DeviceBuffer<Corr> d_corr;
+    DeviceBuffer<uint8_t> d_mask;
+    DeviceBuffer<int> d_n;
+    int cap = 1;                          // of the last upload: max(n, 1), what the batch form is told
+
+    int create(hipStream_t st, const char* what) { return d_n.reserve(st, 1, what); }
+
+    int upload(hipStream_t st, const Corr* corr, int n) {
+        if (n < 0 || n > (1 << 20) || (n && !corr)) return ARIA_E_INVALID;
+        cap = std::max(n, 1);
+        int rc;
+        if ((rc = d_corr.reserve(st, (size_t)cap)) != ARIA_OK) return rc;
+        if ((rc = d_mask.reserve(st, (size_t)cap)) != ARIA_OK) return rc;
+        if (n) ARIA_HIP(hipMemcpyAsync(d_corr, corr, sizeof(Corr) * (size_t)n, hipMemcpyHostToDevice, st));
+        ARIA_HIP(memcpy_on(st, d_n, &n, sizeof(int), hipMemcpyHostToDevice));
+        return ARIA_OK;
+    }
+};
+
+// Rows [row0, row0 + rows) of the hypothesis models as the kernels keep them, soa[row][H], to one record per hypothesis,
+// out[H][rows]: what the aria_<stage>_debug_hypotheses forms return.
+template <class T>
+void unpack_models(const T* soa, int H, int row0, int rows, T* out) {
+    for (int i = 0; i < H; i++)
+        for (int k = 0; k < rows; k++) out[(size_t)i * rows + k] = soa[(size_t)(row0 + k) * H + i];
+}
+
+// Squared inlier threshold in normalised image coordinates, as the essential, absolute-pose and Sim(3) kernels take it.
+inline float normalized_thr2(double threshold_px, double fx, double fy) {
+    const double t = threshold_px / ((fx + fy) * 0.5);
+    return (float)(t * t);
+}
+
+// The part of the intrinsics test that every stage with a pinhole camera shares: positive finite focal lengths and a finite
+// principal point. Each create adds its own conditions.
+inline bool bad_pinhole(double fx, double fy, double cx, double cy) {
+    return !(fx > 0) || !(fy > 0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy);
+}
 
 // The map handle's arena, the device word that holds its size, its capacity and its device (map_triangulate.hip): the
 // association kernels of the absolute pose stage read the map where it lies. The arena pointer is the one current at the

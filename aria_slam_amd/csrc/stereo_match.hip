@@ -481,9 +481,9 @@ struct aria_stereo_s : StageHandle {
     DeviceBuffer<aria_stereo_obs> d_obs;                       // match: cap; scale: query + train
     DeviceBuffer<aria_match> d_m;
     DeviceBuffer<uint8_t> d_mask;
-    int* d_counts = nullptr;                                   // 4 ints
-    aria_pose_result* d_pose = nullptr;
-    aria_stereo_scale* d_scale = nullptr;
+    DeviceBuffer<int> d_counts;                                // 4 ints
+    DeviceBuffer<aria_pose_result> d_pose;
+    DeviceBuffer<aria_stereo_scale> d_scale;
 };
 
 namespace {
@@ -491,8 +491,7 @@ namespace {
 bool fin(double v) { return std::isfinite(v); }
 
 bool bad_config(const aria_stereo_config* c) {
-    return !c || c->struct_size != (int)sizeof(aria_stereo_config) || !(c->fx > 0) || !(c->fy > 0) || !fin(c->fx) || !fin(c->fy) ||
-           !fin(c->cx) || !fin(c->cy) || !(c->baseline > 0) || !fin(c->baseline) || !fin(c->min_disparity) ||
+    return !c || c->struct_size != (int)sizeof(aria_stereo_config) || bad_pinhole(c->fx, c->fy, c->cx, c->cy) || !(c->baseline > 0) || !fin(c->baseline) || !fin(c->min_disparity) ||
            !fin(c->max_disparity) || !(c->max_disparity > c->min_disparity) || !(c->band_factor >= 0) || !fin(c->band_factor) ||
            !(c->median_factor >= 0) || !fin(c->median_factor) || c->th_hamming < 0 || c->th_hamming > 257 ||
            c->sad_half_window < 1 || c->sad_half_window > ST_MAX_W || c->sad_slide < 1 || c->sad_slide > ST_MAX_L ||
@@ -536,47 +535,27 @@ void aria_stereo_default_config(aria_stereo_config* c) {
 
 int aria_stereo_create(const aria_stereo_config* c, aria_stereo_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_stereo_s* h = new (std::nothrow) aria_stereo_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    h->prm = make_params(*c);
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_stereo_create");
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_counts, 4 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_pose, sizeof(aria_pose_result));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_scale, sizeof(aria_stereo_scale));
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_match), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)match_lds_bytes(ST_MAX_DIM, ST_MAX_KP));
+    return stage_create(c, out, 1, "aria_stereo_create", [](aria_stereo_s* h) {
+        const char* what = "aria_stereo_create";
+        h->prm = make_params(h->cfg);
+        int rc;
+        if ((rc = h->d_counts.reserve(h->stream, 4, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_pose.reserve(h->stream, 1, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_scale.reserve(h->stream, 1, what)) != ARIA_OK) return rc;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_match), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)match_lds_bytes(ST_MAX_DIM, ST_MAX_KP));
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_scale), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     ST_MAX_KP * (int)sizeof(unsigned long long));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_stereo_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_stereo_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+        return e == hipSuccess ? (int)ARIA_OK : hip_fail(e, what, __FILE__, __LINE__);
+    });
 }
 
-void aria_stereo_destroy(aria_stereo_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_counts, h->d_pose, h->d_scale});
-    delete h;
-}
+void aria_stereo_destroy(aria_stereo_t h) { stage_destroy(h); }
 
-void* aria_stereo_stream(aria_stereo_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_stereo_stream(aria_stereo_t h) { return stage_stream(h); }
 
-int aria_stereo_check(aria_stereo_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_STEREO_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_stereo_check(aria_stereo_t h) { return stage_check(h, {{ERRBIT_STEREO_INPUT, ARIA_E_INVALID}}); }
 
 int aria_stereo_match_batch_device(aria_stereo_t h, const uint8_t* d_img_left, const uint8_t* d_img_right, int64_t img_stride,
                                    int width, int height, int pitch, const aria_keypoint* d_kp_left,

@@ -422,26 +422,12 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_traj_eval(const void* __restrict
 struct aria_eval_s : StageHandle {   // d_err: [0] deferred error bits, [1] the sampler's scan flag
     aria_eval_config cfg{};
     // staging of the host forms, grown on demand
-    void* d_buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[7] = {0, 0, 0, 0, 0, 0, 0};
+    DeviceBuffer<uint8_t> d_buf[6];   // bytes: each host form lays its own arrays over the slots
 };
 
 namespace {
 
-hipError_t eval_reserve(aria_eval_t h, int k, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 64);
-    if (h->cap[k] >= bytes) return hipSuccess;
-    if (h->d_buf[k]) {
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return e;
-        (void)hipFree(h->d_buf[k]);
-        h->d_buf[k] = nullptr;
-        h->cap[k] = 0;
-    }
-    hipError_t e = hipMalloc(&h->d_buf[k], bytes);
-    if (e == hipSuccess) h->cap[k] = bytes;
-    return e;
-}
+int eval_reserve(aria_eval_t h, int k, size_t bytes) { return h->d_buf[k].reserve(h->stream, std::max<size_t>(bytes, 64)); }
 
 size_t est_stride(int kind) {
     return kind == ARIA_EVAL_EST_POSE12 ? 12 * sizeof(double) : kind == ARIA_EVAL_EST_FUSE_STATE ? sizeof(aria_fuse_state) : 3 * sizeof(double);
@@ -463,34 +449,14 @@ void aria_eval_default_config(aria_eval_config* c) {
 
 int aria_eval_create(const aria_eval_config* c, aria_eval_t* out) {
     if (!c || !out || c->struct_size != (int)sizeof(aria_eval_config)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_eval_s* h = new (std::nothrow) aria_eval_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    const int rc = stage_open(h, c->device, c->stream, 2, "aria_eval_create");
-    if (rc != ARIA_OK) {
-        aria_eval_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 2, "aria_eval_create", [](aria_eval_s*) { return (int)ARIA_OK; });
 }
 
-void aria_eval_destroy(aria_eval_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_buf[0], h->d_buf[1], h->d_buf[2], h->d_buf[3], h->d_buf[4], h->d_buf[5], h->d_buf[6]});
-    delete h;
-}
+void aria_eval_destroy(aria_eval_t h) { stage_destroy(h); }
 
-void* aria_eval_stream(aria_eval_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_eval_stream(aria_eval_t h) { return stage_stream(h); }
 
-int aria_eval_check(aria_eval_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_EVAL_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_eval_check(aria_eval_t h) { return stage_check(h, {{ERRBIT_EVAL_INPUT, ARIA_E_INVALID}}); }
 
 int aria_eval_sample_truth_device(aria_eval_t h, const aria_eval_truth* d_gt, int n_gt, const double* d_ts, int n,
                                   aria_eval_truth* d_out, int* d_valid) {
@@ -516,15 +482,16 @@ int aria_eval_sample_truth(aria_eval_t h, const aria_eval_truth* gt, int n_gt, c
     if (n == 0) return ARIA_OK;
     ARIA_HIP(hipSetDevice(h->device));
     const size_t M = (size_t)n_gt, N = (size_t)n;
-    ARIA_HIP(eval_reserve(h, 0, M * sizeof(aria_eval_truth)));
-    ARIA_HIP(eval_reserve(h, 1, N * sizeof(double)));
-    ARIA_HIP(eval_reserve(h, 2, N * sizeof(aria_eval_truth)));
-    ARIA_HIP(eval_reserve(h, 3, N * sizeof(int)));
+    int rc;
+    if ((rc = eval_reserve(h, 0, M * sizeof(aria_eval_truth))) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 1, N * sizeof(double))) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 2, N * sizeof(aria_eval_truth))) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 3, N * sizeof(int))) != ARIA_OK) return rc;
     hipStream_t st = h->stream;
     if (M) ARIA_HIP(hipMemcpyAsync(h->d_buf[0], gt, M * sizeof(aria_eval_truth), hipMemcpyHostToDevice, st));
     ARIA_HIP(memcpy_on(st, h->d_buf[1], ts, N * sizeof(double), hipMemcpyHostToDevice));
-    int rc = aria_eval_sample_truth_device(h, (const aria_eval_truth*)h->d_buf[0], n_gt, (const double*)h->d_buf[1], n,
-                                           (aria_eval_truth*)h->d_buf[2], (int*)h->d_buf[3]);
+    rc = aria_eval_sample_truth_device(h, (const aria_eval_truth*)h->d_buf[0].p, n_gt, (const double*)h->d_buf[1].p, n,
+                                       (aria_eval_truth*)h->d_buf[2].p, (int*)h->d_buf[3].p);
     if (rc != ARIA_OK) return rc;
     ARIA_HIP(hipMemcpyAsync(out, h->d_buf[2], N * sizeof(aria_eval_truth), hipMemcpyDeviceToHost, st));
     if (valid) ARIA_HIP(hipMemcpyAsync(valid, h->d_buf[3], N * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -558,22 +525,22 @@ int aria_eval_batch(aria_eval_t h, const void* est, int est_kind, const int* off
     if (n_traj == 0) return ARIA_OK;
     ARIA_HIP(hipSetDevice(h->device));
     const size_t NP = (size_t)n_poses_total, NT = (size_t)n_truth, B = (size_t)n_traj, stride = est_stride(est_kind);
-    ARIA_HIP(eval_reserve(h, 0, NP * stride));
-    ARIA_HIP(eval_reserve(h, 1, (B + 1) * sizeof(int)));
-    ARIA_HIP(eval_reserve(h, 2, NT * sizeof(aria_eval_truth)));
-    ARIA_HIP(eval_reserve(h, 3, NP));
-    ARIA_HIP(eval_reserve(h, 4, NP * sizeof(double)));
-    ARIA_HIP(eval_reserve(h, 5, B * sizeof(aria_eval_result)));
+    int rc;
+    if ((rc = eval_reserve(h, 0, NP * stride)) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 1, (B + 1) * sizeof(int))) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 2, NT * sizeof(aria_eval_truth))) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 3, NP)) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 4, NP * sizeof(double))) != ARIA_OK) return rc;
+    if ((rc = eval_reserve(h, 5, B * sizeof(aria_eval_result))) != ARIA_OK) return rc;
     hipStream_t st = h->stream;
     if (NP) ARIA_HIP(hipMemcpyAsync(h->d_buf[0], est, NP * stride, hipMemcpyHostToDevice, st));
     if (NT) ARIA_HIP(hipMemcpyAsync(h->d_buf[2], truth, NT * sizeof(aria_eval_truth), hipMemcpyHostToDevice, st));
     if (NP && mask) ARIA_HIP(hipMemcpyAsync(h->d_buf[3], mask, NP, hipMemcpyHostToDevice, st));
     if (pose_err) ARIA_HIP(hipMemsetAsync(h->d_buf[4], 0, std::max<size_t>(NP * sizeof(double), 8), st));
     ARIA_HIP(memcpy_on(st, h->d_buf[1], offset, (B + 1) * sizeof(int), hipMemcpyHostToDevice));
-    int rc = aria_eval_batch_device(h, h->d_buf[0], est_kind, (const int*)h->d_buf[1], n_poses_total, n_traj,
-                                    (const aria_eval_truth*)h->d_buf[2], n_truth, truth_shared,
-                                    mask ? (const uint8_t*)h->d_buf[3] : nullptr, align_mode, rpe_delta,
-                                    pose_err ? (double*)h->d_buf[4] : nullptr, (aria_eval_result*)h->d_buf[5]);
+    rc = aria_eval_batch_device(h, h->d_buf[0], est_kind, (const int*)h->d_buf[1].p, n_poses_total, n_traj,
+                                (const aria_eval_truth*)h->d_buf[2].p, n_truth, truth_shared, mask ? h->d_buf[3].p : nullptr, align_mode,
+                                rpe_delta, pose_err ? (double*)h->d_buf[4].p : nullptr, (aria_eval_result*)h->d_buf[5].p);
     if (rc != ARIA_OK) return rc;
     ARIA_HIP(hipMemcpyAsync(results, h->d_buf[5], B * sizeof(aria_eval_result), hipMemcpyDeviceToHost, st));
     if (pose_err && NP) ARIA_HIP(hipMemcpyAsync(pose_err, h->d_buf[4], NP * sizeof(double), hipMemcpyDeviceToHost, st));

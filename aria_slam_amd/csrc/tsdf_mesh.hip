@@ -290,12 +290,10 @@ struct aria_mesh_s : StageHandle {
     size_t n_vox = 0;
     int n_chunks = 0;
     const unsigned long long* d_vol = nullptr;                 // the caller's records, remembered by update
-    uint32_t* d_words = nullptr;                               // the parked word per voxel
-    int* d_vcount = nullptr;                                   // per chunk
-    int* d_tcount = nullptr;
-    long long* d_voff = nullptr;
-    long long* d_toff = nullptr;
-    long long* d_counts = nullptr;                             // host form: the two totals
+    DeviceBuffer<uint32_t> d_words;                            // the parked word per voxel
+    DeviceBuffer<int> d_vcount, d_tcount;                      // per chunk
+    DeviceBuffer<long long> d_voff, d_toff;
+    DeviceBuffer<int64_t> d_counts;                            // host form: the two totals
     // host-form staging (grow-only)
     DeviceBuffer<aria_mesh_vertex> d_vertices;
     DeviceBuffer<aria_mesh_triangle> d_triangles;
@@ -349,47 +347,29 @@ int64_t aria_mesh_algorithmic_bytes(int nx, int ny, int nz, int64_t n_vertices, 
 
 int aria_mesh_create(const aria_mesh_config* c, aria_mesh_t* out) {
     if (!out || mesh_bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_mesh_s* h = new (std::nothrow) aria_mesh_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    h->G = MeshGeom{c->nx, c->ny, c->nz, (uint32_t)c->min_weight, c->voxel, c->origin[0], c->origin[1], c->origin[2]};
-    h->n_vox = (size_t)c->nx * c->ny * c->nz;
-    h->n_chunks = (int)(h->n_vox / MESH_BLOCK);
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_mesh_create");
-    if (rc == ARIA_OK) {
+    return stage_create(c, out, 1, "aria_mesh_create", [](aria_mesh_s* h) {
+        const aria_mesh_config& c = h->cfg;
+        h->G = MeshGeom{c.nx, c.ny, c.nz, (uint32_t)c.min_weight, c.voxel, c.origin[0], c.origin[1], c.origin[2]};
+        h->n_vox = (size_t)c.nx * c.ny * c.nz;
+        h->n_chunks = (int)(h->n_vox / MESH_BLOCK);
         const size_t nc = (size_t)h->n_chunks;
-        hipError_t e = hipMalloc((void**)&h->d_words, h->n_vox * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_vcount, nc * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_tcount, nc * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_voff, nc * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_toff, nc * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_counts, 2 * sizeof(long long));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_mesh_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_mesh_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+        const char* what = "aria_mesh_create";
+        int rc;
+        if ((rc = h->d_words.reserve(h->stream, h->n_vox, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_vcount.reserve(h->stream, nc, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_tcount.reserve(h->stream, nc, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_voff.reserve(h->stream, nc, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_toff.reserve(h->stream, nc, what)) != ARIA_OK) return rc;
+        return h->d_counts.reserve(h->stream, 2, what);
+    });
 }
 
-void aria_mesh_destroy(aria_mesh_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_words, h->d_vcount, h->d_tcount, h->d_voff, h->d_toff, h->d_counts});
-    delete h;
-}
+void aria_mesh_destroy(aria_mesh_t h) { stage_destroy(h); }
 
-void* aria_mesh_stream(aria_mesh_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_mesh_stream(aria_mesh_t h) { return stage_stream(h); }
 
 int aria_mesh_check(aria_mesh_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    if (bits & ERRBIT_MESH_OVERFLOW) return ARIA_E_OVERFLOW;
-    return (bits & ERRBIT_MESH_CAP) ? ARIA_E_OUTPUT_TOO_SMALL : ARIA_OK;
+    return stage_check(h, {{ERRBIT_MESH_OVERFLOW, ARIA_E_OVERFLOW}, {ERRBIT_MESH_CAP, ARIA_E_OUTPUT_TOO_SMALL}});
 }
 
 int aria_mesh_update_from_volume_device(aria_mesh_t h, const aria_tsdf_voxel* d_voxels) {
@@ -429,7 +409,7 @@ int aria_mesh_extract(aria_mesh_t h, aria_mesh_vertex* vertices, int64_t vcap, a
     if (vcap > 0 && (rc = h->d_vertices.reserve(h->stream, (size_t)vcap)) != ARIA_OK) return rc;
     if (tcap > 0 && (rc = h->d_triangles.reserve(h->stream, (size_t)tcap)) != ARIA_OK) return rc;
     if ((rc = aria_mesh_extract_device(h, vcap > 0 ? (aria_mesh_vertex*)h->d_vertices : nullptr, vcap,
-                                       tcap > 0 ? (aria_mesh_triangle*)h->d_triangles : nullptr, tcap, (int64_t*)h->d_counts)) != ARIA_OK)
+                                       tcap > 0 ? (aria_mesh_triangle*)h->d_triangles : nullptr, tcap, h->d_counts)) != ARIA_OK)
         return rc;
     long long n[2] = {0, 0};
     ARIA_HIP(memcpy_on(h->stream, n, h->d_counts, sizeof(n), hipMemcpyDeviceToHost));

@@ -353,15 +353,15 @@ struct aria_ray_s : StageHandle {
     RayParams P{};
     size_t n_vox = 0, n_words = 0;
     const unsigned long long* d_vol = nullptr;                 // the caller's records, remembered by update
-    uint32_t* d_words = nullptr;                               // the skip bits
-    uint8_t* d_flags = nullptr;                                // a byte per brick, packed into d_words by update
+    DeviceBuffer<uint32_t> d_words;                            // the skip bits
+    DeviceBuffer<uint8_t> d_flags;                             // a byte per brick, packed into d_words by update
     int n_bricks = 0;
     DeviceBuffer<RayView> d_views;
     // host-form staging (grow-only)
     DeviceBuffer<float> d_depth, d_normal;
     DeviceBuffer<uint8_t> d_gray, d_shade;
-    double* d_ext = nullptr;                                   // 12 doubles
-    aria_ray_view* d_rec = nullptr;
+    DeviceBuffer<double> d_ext;                                // 12 doubles
+    DeviceBuffer<aria_ray_view> d_rec;
 };
 
 namespace {
@@ -420,44 +420,25 @@ int aria_ray_create(const aria_ray_config* c, aria_ray_t* out) {
     *out = nullptr;
     const RayParams P = ray_make_params(*c);
     if (P.n_steps < 1) return ARIA_E_INVALID;
-    aria_ray_s* h = new (std::nothrow) aria_ray_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    h->P = P;
-    h->n_vox = (size_t)c->nx * c->ny * c->nz;
-    h->n_bricks = (int)(h->n_vox / 512);
-    h->n_words = ((size_t)h->n_bricks + 31) / 32;
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_ray_create");
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_words, h->n_words * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_flags, (size_t)h->n_bricks);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_ext, 12 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_rec, sizeof(aria_ray_view));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_ray_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_ray_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_ray_create", [&P](aria_ray_s* h) {
+        const char* what = "aria_ray_create";
+        h->P = P;
+        h->n_vox = (size_t)h->cfg.nx * h->cfg.ny * h->cfg.nz;
+        h->n_bricks = (int)(h->n_vox / 512);
+        h->n_words = ((size_t)h->n_bricks + 31) / 32;
+        int rc;
+        if ((rc = h->d_words.reserve(h->stream, h->n_words, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_flags.reserve(h->stream, (size_t)h->n_bricks, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_ext.reserve(h->stream, 12, what)) != ARIA_OK) return rc;
+        return h->d_rec.reserve(h->stream, 1, what);
+    });
 }
 
-void aria_ray_destroy(aria_ray_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_words, h->d_flags, h->d_ext, h->d_rec});
-    delete h;
-}
+void aria_ray_destroy(aria_ray_t h) { stage_destroy(h); }
 
-void* aria_ray_stream(aria_ray_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_ray_stream(aria_ray_t h) { return stage_stream(h); }
 
-int aria_ray_check(aria_ray_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    return (bits & ERRBIT_RAY_INPUT) ? ARIA_E_INVALID : ARIA_OK;
-}
+int aria_ray_check(aria_ray_t h) { return stage_check(h, {{ERRBIT_RAY_INPUT, ARIA_E_INVALID}}); }
 
 int aria_ray_update_from_volume_device(aria_ray_t h, const aria_tsdf_voxel* d_voxels) {
     if (!h || !d_voxels) return ARIA_E_INVALID;

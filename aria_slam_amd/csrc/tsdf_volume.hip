@@ -333,7 +333,7 @@ struct aria_tsdf_s : StageHandle {
     TsdfParams P{};
     size_t n_vox = 0;
     int cull = 1;
-    unsigned long long* d_vol = nullptr;
+    DeviceBuffer<unsigned long long> d_vol;                    // the records, one word each
     DeviceBuffer<TsdfFrame> d_frames;
     DeviceBuffer<uint32_t> d_mask;                             // tiles x words of one launch
     DeviceBuffer<int> d_counts;                                // extraction: per chunk
@@ -342,8 +342,8 @@ struct aria_tsdf_s : StageHandle {
     DeviceBuffer<float> d_depth;
     DeviceBuffer<uint8_t> d_img;
     DeviceBuffer<aria_tsdf_point> d_points;
-    double* d_ext = nullptr;                                   // 12 doubles
-    long long* d_count = nullptr;
+    DeviceBuffer<double> d_ext;                                // 12 doubles
+    DeviceBuffer<int64_t> d_count;
 };
 
 namespace {
@@ -400,44 +400,27 @@ int64_t aria_tsdf_algorithmic_bytes(int nx, int ny, int nz, int width, int heigh
 
 int aria_tsdf_create(const aria_tsdf_config* c, aria_tsdf_t* out) {
     if (!out || bad_config(c)) return ARIA_E_INVALID;
-    *out = nullptr;
-    aria_tsdf_s* h = new (std::nothrow) aria_tsdf_s();
-    if (!h) return ARIA_E_OOM;
-    h->cfg = *c;
-    h->P = make_params(*c);
-    h->n_vox = (size_t)c->nx * c->ny * c->nz;
-    if (const char* s = aria_getenv("ARIA_TSDF_CULL")) h->cull = std::atoi(s) != 0;   // variants build: A/B
-    int rc = stage_open(h, c->device, c->stream, 1, "aria_tsdf_create");
-    if (rc == ARIA_OK) {
-        hipError_t e = hipMalloc((void**)&h->d_vol, h->n_vox * sizeof(aria_tsdf_voxel));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_ext, 12 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_count, sizeof(long long));
-        if (e == hipSuccess) e = memset_on(h->stream, h->d_vol, 0, h->n_vox * sizeof(aria_tsdf_voxel));
-        if (e != hipSuccess) rc = hip_fail(e, "aria_tsdf_create", __FILE__, __LINE__);
-    }
-    if (rc != ARIA_OK) {
-        aria_tsdf_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return ARIA_OK;
+    return stage_create(c, out, 1, "aria_tsdf_create", [](aria_tsdf_s* h) {
+        const aria_tsdf_config& c = h->cfg;
+        const char* what = "aria_tsdf_create";
+        h->P = make_params(c);
+        h->n_vox = (size_t)c.nx * c.ny * c.nz;
+        if (const char* s = aria_getenv("ARIA_TSDF_CULL")) h->cull = std::atoi(s) != 0;   // variants build: A/B
+        int rc;
+        if ((rc = h->d_vol.reserve(h->stream, h->n_vox, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_ext.reserve(h->stream, 12, what)) != ARIA_OK) return rc;
+        if ((rc = h->d_count.reserve(h->stream, 1, what)) != ARIA_OK) return rc;
+        const hipError_t e = memset_on(h->stream, h->d_vol, 0, h->n_vox * sizeof(aria_tsdf_voxel));
+        return e == hipSuccess ? (int)ARIA_OK : hip_fail(e, what, __FILE__, __LINE__);
+    });
 }
 
-void aria_tsdf_destroy(aria_tsdf_t h) {
-    if (!h) return;
-    stage_close(h, {h->d_vol, h->d_ext, h->d_count});
-    delete h;
-}
+void aria_tsdf_destroy(aria_tsdf_t h) { stage_destroy(h); }
 
-void* aria_tsdf_stream(aria_tsdf_t h) { return h ? (void*)h->stream : nullptr; }
+void* aria_tsdf_stream(aria_tsdf_t h) { return stage_stream(h); }
 
 int aria_tsdf_check(aria_tsdf_t h) {
-    if (!h) return ARIA_E_INVALID;
-    int bits = 0;
-    const int rc = stage_read_errors(h, &bits, 1);
-    if (rc != ARIA_OK) return rc;
-    if (bits & ERRBIT_TSDF_INPUT) return ARIA_E_INVALID;
-    return (bits & ERRBIT_TSDF_CAP) ? ARIA_E_OUTPUT_TOO_SMALL : ARIA_OK;
+    return stage_check(h, {{ERRBIT_TSDF_INPUT, ARIA_E_INVALID}, {ERRBIT_TSDF_CAP, ARIA_E_OUTPUT_TOO_SMALL}});
 }
 
 int aria_tsdf_clear(aria_tsdf_t h) {
@@ -532,7 +515,7 @@ int aria_tsdf_extract_points(aria_tsdf_t h, aria_tsdf_point* points, int64_t cap
     ARIA_HIP(hipSetDevice(h->device));
     int rc;
     if (cap > 0 && (rc = h->d_points.reserve(h->stream, (size_t)cap)) != ARIA_OK) return rc;
-    if ((rc = aria_tsdf_extract_points_device(h, cap > 0 ? (aria_tsdf_point*)h->d_points : nullptr, cap, (int64_t*)h->d_count)) != ARIA_OK)
+    if ((rc = aria_tsdf_extract_points_device(h, cap > 0 ? (aria_tsdf_point*)h->d_points : nullptr, cap, h->d_count)) != ARIA_OK)
         return rc;
     long long n = 0;
     ARIA_HIP(memcpy_on(h->stream, &n, h->d_count, sizeof(n), hipMemcpyDeviceToHost));
@@ -542,7 +525,7 @@ int aria_tsdf_extract_points(aria_tsdf_t h, aria_tsdf_point* points, int64_t cap
     return aria_tsdf_check(h);
 }
 
-aria_tsdf_voxel* aria_tsdf_device_voxels(aria_tsdf_t h) { return h ? reinterpret_cast<aria_tsdf_voxel*>(h->d_vol) : nullptr; }
+aria_tsdf_voxel* aria_tsdf_device_voxels(aria_tsdf_t h) { return h ? reinterpret_cast<aria_tsdf_voxel*>(h->d_vol.p) : nullptr; }
 
 int aria_tsdf_read_box(aria_tsdf_t h, int i0, int j0, int k0, int ni, int nj, int nk, aria_tsdf_voxel* out) {
     if (!h || !out || i0 < 0 || j0 < 0 || k0 < 0 || ni < 1 || nj < 1 || nk < 1 || i0 > h->cfg.nx - ni || j0 > h->cfg.ny - nj ||

@@ -1,7 +1,7 @@
-"""What the eight stage handles (pose, fund, map, graph, fuse, eval, det, stereo) share, on the MI355X: create-time
-rejection, the borrowed stream, the grow-only staging and workspace of the three match-list stages, and the deferred input
-error. Every comparison is byte for byte against a fresh handle: a handle that has grown, or has reported an error, computes
-what a new one computes."""
+"""What every stage handle (aria_slam_amd._lib.STAGES) shares, on the MI355X: create-time rejection, the borrowed stream,
+what the entry points answer to a null handle, the grow-only staging and workspace of the three match-list stages, and the
+deferred input error. Every comparison is byte for byte against a fresh handle: a handle that has grown, or has reported an
+error, computes what a new one computes."""
 import ctypes as C
 
 import numpy as np
@@ -9,7 +9,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-STAGES = ["pose", "fund", "map", "graph", "fuse", "eval", "det", "stereo"]
+STAGES = ["pose", "fund", "map", "graph", "fuse", "eval", "det", "stereo", "rect", "dense", "tsdf", "nav", "alert", "pnp", "ba", "ray",
+          "icp", "mesh", "proj", "bow", "sim3"]
 MATCH_STAGES = ["pose", "fund", "map"]
 ARIA_E_INVALID, ARIA_E_NO_DEVICE = -1, -2
 HYP = 64
@@ -29,17 +30,28 @@ def torch_cuda():
 def _config(aria, prefix):
     L = aria._lib
     return dict(pose=L.PoseConfig, fund=L.FundConfig, map=L.MapConfig, graph=L.GraphConfig, fuse=L.FuseConfig,
-                eval=L.EvalConfig, det=L.DetConfig, stereo=L.StereoConfig)[prefix]()
+                eval=L.EvalConfig, det=L.DetConfig, stereo=L.StereoConfig, rect=L.RectConfig, dense=L.DenseConfig,
+                tsdf=L.TsdfConfig, nav=L.NavConfig, alert=L.AlertConfig, pnp=L.PnpConfig, ba=L.BaConfig, ray=L.RayConfig,
+                icp=L.IcpConfig, mesh=L.MeshConfig, proj=L.ProjConfig, bow=L.BowConfig, sim3=L.Sim3Config)[prefix]()
+
+
+VOL = (16, 16, 16)                # the smallest volumes of whole 8^3 bricks with more than one brick per axis
+SMALL = dict(pose=dict(hypotheses=HYP), fund=dict(hypotheses=HYP), pnp=dict(hypotheses=HYP), sim3=dict(hypotheses=HYP),
+             rect=dict(src_size=(W, H)), dense=dict(max_size=(W, H)), alert=dict(width=W, height=H), ba=dict(max_windows=4),
+             tsdf=dict(dims=VOL), ray=dict(dims=VOL), mesh=dict(dims=VOL), nav=dict(dims=VOL, max_goals=4),
+             bow=dict(words=64, rows=64, capacity=16))
 
 
 def _make(aria, prefix, **kw):
-    if prefix == "pose":
-        return aria.HipPoseEstimator(hypotheses=HYP, **kw)
-    if prefix == "fund":
-        return aria.HipFundamentalEstimator(hypotheses=HYP, **kw)
-    cls = dict(map=aria.HipMapper, graph=aria.HipPoseGraphOptimizer, fuse=aria.HipSensorFusion,
-               eval=aria.HipTrajectoryEvaluator, det=aria.HipObjectDetector, stereo=aria.HipStereoMatcher)[prefix]
-    return cls(**kw)
+    """A handle of the stage at the smallest size it accepts where its create allocates by size (SMALL); every default
+    config is creatable as it stands, rect's included (aria_rect_default_config fills in a camera)."""
+    cls = dict(pose=aria.HipPoseEstimator, fund=aria.HipFundamentalEstimator, map=aria.HipMapper, graph=aria.HipPoseGraphOptimizer,
+               fuse=aria.HipSensorFusion, eval=aria.HipTrajectoryEvaluator, det=aria.HipObjectDetector, stereo=aria.HipStereoMatcher,
+               rect=aria.HipRectifier, dense=aria.HipDenseStereo, tsdf=aria.HipTsdfVolume, nav=aria.HipPathPlanner,
+               alert=aria.HipObstacleAlerter, pnp=aria.HipPnPEstimator, ba=aria.HipBundleAdjuster, ray=aria.HipVolumeRenderer,
+               icp=aria.HipDenseTracker, mesh=aria.HipVolumeMesher, proj=aria.HipProjectionMatcher, bow=aria.HipBowIndex,
+               sim3=aria.HipSim3Aligner)[prefix]
+    return cls(**SMALL.get(prefix, {}), **kw)
 
 
 @pytest.mark.parametrize("prefix", STAGES)
@@ -79,6 +91,15 @@ def test_a_borrowed_stream_is_reported_and_survives_close(aria, torch_cuda, pref
         x = torch.arange(8, device=dev) * 2
     s.synchronize()
     assert int(x.sum()) == 56
+
+
+@pytest.mark.parametrize("prefix", STAGES)
+def test_a_null_handle_is_refused_by_check_and_ignored_by_destroy_and_stream(aria, prefix):
+    L = aria.load_library()
+    fn = lambda name: getattr(L, "aria_%s_%s" % (prefix, name))   # noqa: E731
+    assert fn("destroy")(None) is None
+    assert fn("stream")(None) is None
+    assert (fn("check")(None, None, None) if prefix == "det" else fn("check")(None)) == ARIA_E_INVALID
 
 
 # ---- the three match-list stages: inputs, and one way to run each form ------------------------------------------------------
