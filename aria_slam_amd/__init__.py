@@ -26,6 +26,7 @@ from .proj import HipProjectionMatcher
 from .bow import HipBowIndex
 from .sim3 import HipSim3Aligner
 from .posegraph import HipPoseGraphOptimizer
+from .simgraph import HipSim3GraphOptimizer
 from .rectify import HipRectifier, load_sensor_yaml
 from .stereo import HipStereoMatcher
 from .tsdf import HipTsdfVolume
@@ -34,4 +35,4 @@ __all__ = ["KP_DTYPE", "MATCH_DTYPE", "AriaError", "abi_version", "build_library
            "status_string", "level_info", "resize_table", "algorithmic_bytes", "synth_frame_pair", "synth_sequence", "HipMatcher", "OrbHipExtractor", "flag_keypoints_device",
            "HipPoseEstimator", "HipMapper", "HipFundamentalEstimator", "verify_loop_candidates", "HipPoseGraphOptimizer",
            "HipSensorFusion", "HipImuPreintegrator", "HipTrajectoryEvaluator", "load_ground_truth_csv", "HipObjectDetector",
-           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner", "HipObstacleAlerter", "HipPnPEstimator", "HipBundleAdjuster", "HipVolumeRenderer", "HipDenseTracker", "HipVolumeMesher", "HipProjectionMatcher", "HipBowIndex", "HipSim3Aligner"]
+           "HipStereoMatcher", "HipRectifier", "load_sensor_yaml", "HipDenseStereo", "HipTsdfVolume", "HipPathPlanner", "HipObstacleAlerter", "HipPnPEstimator", "HipBundleAdjuster", "HipVolumeRenderer", "HipDenseTracker", "HipVolumeMesher", "HipProjectionMatcher", "HipBowIndex", "HipSim3Aligner", "HipSim3GraphOptimizer"]

@@ -119,6 +119,11 @@ EXPORTS = [
     # loop alignment (batched Sim(3) RANSAC of the landmarks two keyframes own, join with the point map), additive to ABI 4
     "aria_sim3_default_config", "aria_sim3_create", "aria_sim3_destroy", "aria_sim3_stream", "aria_sim3_check",
     "aria_sim3_estimate", "aria_sim3_estimate_batch_device", "aria_sim3_debug_hypotheses", "aria_sim3_associate_batch_device",
+    # Sim(3) pose-graph optimisation and map correction after a loop (7-DoF LM, the arena moved by anchor keyframe), additive to ABI 4
+    "aria_sgraph_default_config", "aria_sgraph_create", "aria_sgraph_destroy", "aria_sgraph_stream", "aria_sgraph_check",
+    "aria_sgraph_optimize", "aria_sgraph_optimize_batch_device", "aria_sgraph_debug_linearize",
+    "aria_sgraph_vertices_from_pose_device", "aria_sgraph_poses_from_vertices_device", "aria_sgraph_correct_map_device",
+    "aria_sgraph_correct_points_device",
 ]
 
 
@@ -209,6 +214,18 @@ GRAPH_EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("info_scale", "<f8
 GRAPH_RESULT_DTYPE = np.dtype([("chi2_initial", "<f8"), ("chi2_final", "<f8"), ("lambda", "<f8"), ("iterations_done", "<i4"),
                                ("trials", "<i4"), ("pcg_iterations", "<i4"), ("valid", "<i4"), ("stop_reason", "<i4"),
                                ("reserved", "<i4")])
+
+
+class SgraphConfig(C.Structure):
+    _fields_ = GraphConfig._fields_ + [("fix_scale", C.c_int), ("reserved", C.c_int)]
+
+
+# aria_sgraph_vertex (104 bytes), aria_sgraph_edge (120 bytes), aria_sgraph_result (48 bytes: aria_graph_result's layout) and
+# aria_sgraph_correct_stats (16 bytes)
+SGRAPH_VERTEX_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("s", "<f8")])
+SGRAPH_EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("info_scale", "<f8"), ("Z", "<f8", (12,)), ("s", "<f8")])
+SGRAPH_RESULT_DTYPE = np.dtype(GRAPH_RESULT_DTYPE.descr)
+SGRAPH_STATS_DTYPE = np.dtype([("moved", "<i4"), ("left_alone", "<i4"), ("refused", "<i4"), ("reserved", "<i4")])
 
 
 class FuseConfig(C.Structure):
@@ -609,7 +626,7 @@ def load_library():
 
 # Every stage handle, by the prefix of its C entry points (aria_<prefix>_create, ...), in the order the stages were added.
 STAGES = ("pose", "map", "fund", "graph", "fuse", "eval", "det", "stereo", "rect", "dense", "tsdf", "nav", "alert", "pnp", "ba", "ray",
-          "icp", "mesh", "proj", "bow", "sim3")
+          "icp", "mesh", "proj", "bow", "sim3", "sgraph")
 
 
 def _bind_handle(L, prefix):
@@ -840,6 +857,18 @@ def _bind_sim3(L):
     L.aria_sim3_estimate_batch_device.argtypes = [p, p, p, i, i, i, p, p]
     L.aria_sim3_debug_hypotheses.argtypes = [p, p, i, i, p, p, p, p, p]
     L.aria_sim3_associate_batch_device.argtypes = [p, p, p, p, i, i, p, p, p, p, p, p, i64, p, p, i, i, p, p, p]
+
+
+def _bind_sgraph(L):
+    p, i, i64 = C.c_void_p, C.c_int, C.c_int64
+    _bind_handle(L, "sgraph")
+    L.aria_sgraph_optimize.argtypes = [p, p, i, i, p, i, i, p]
+    L.aria_sgraph_optimize_batch_device.argtypes = [p, p, p, p, p, p, i, i, p]
+    L.aria_sgraph_debug_linearize.argtypes = [p, p, i, i, p, i, p, p, p, p]
+    L.aria_sgraph_vertices_from_pose_device.argtypes = [p, p, p, i]
+    L.aria_sgraph_poses_from_vertices_device.argtypes = [p, p, p, i]
+    L.aria_sgraph_correct_map_device.argtypes = [p, p, p, i, i, p, p, i, p]
+    L.aria_sgraph_correct_points_device.argtypes = [p, p, i64, p, i, i, p, p, i, p]
 
 
 def _bind_pnp(L):

@@ -170,7 +170,7 @@ def block_jacobi(D, lam):
     """Inverse of the damped diagonal blocks; zero where the Cholesky factorisation fails."""
     Minv = np.zeros_like(D)
     for v in range(len(D)):
-        A = D[v] + lam * np.eye(6)
+        A = D[v] + lam * np.eye(D.shape[-1])
         try:
             L = np.linalg.cholesky(A)
         except np.linalg.LinAlgError:
@@ -183,7 +183,8 @@ def block_jacobi(D, lam):
 
 
 def pcg(D, W, edges, b, lam, fixed, max_iters=1000, rel_tol=1e-8, precond=block_jacobi):
-    """Preconditioned conjugate gradients on (H + lam I) dx = b with the fixed vertex removed. Returns (dx (V, 6), iters)."""
+    """Preconditioned conjugate gradients on (H + lam I) dx = b with the fixed vertex removed. Returns (dx (V, 6), iters).
+    The block size is that of D (6 here, 7 in sgraph_ref)."""
     V = len(D)
     ei = np.array([e[0] for e in edges], np.int64)
     ej = np.array([e[1] for e in edges], np.int64)
@@ -191,7 +192,7 @@ def pcg(D, W, edges, b, lam, fixed, max_iters=1000, rel_tol=1e-8, precond=block_
     if V:
         free[fixed] = 0
     Minv = precond(D, lam)
-    x = np.zeros((V, 6))
+    x = np.zeros_like(b)
     r = b * free
     bb = float((r * r).sum())
     if bb == 0.0:
@@ -226,22 +227,22 @@ def direct(D, W, edges, b, lam, fixed):
         import scipy.sparse.linalg as spl
     except ImportError:
         sp = spl = None
-    V = len(D)
+    V, nb = len(D), D.shape[-1]                   # nb: the block size, 6 here and 7 in sgraph_ref
     free = [v for v in range(V) if v != fixed]
     pos = {v: k for k, v in enumerate(free)}
-    n = 6 * len(free)
-    x = np.zeros((V, 6))
+    n = nb * len(free)
+    x = np.zeros((V, nb))
     if n == 0 or not np.any(b[free]):
         return x, 0
     rows, cols, vals = [], [], []
 
     def put(a, c, B):
-        r0, c0 = 6 * pos[a], 6 * pos[c]
-        rr, cc = np.meshgrid(np.arange(6) + r0, np.arange(6) + c0, indexing="ij")
+        r0, c0 = nb * pos[a], nb * pos[c]
+        rr, cc = np.meshgrid(np.arange(nb) + r0, np.arange(nb) + c0, indexing="ij")
         rows.append(rr.ravel()), cols.append(cc.ravel()), vals.append(B.ravel())
     for v in free:
-        put(v, v, D[v] + lam * np.eye(6))
-    for k, (i, j, _s, _Z) in enumerate(edges):
+        put(v, v, D[v] + lam * np.eye(nb))
+    for k, (i, j) in enumerate((e[0], e[1]) for e in edges):
         if i in pos and j in pos:
             put(i, j, W[k])
             put(j, i, W[k].T)
@@ -257,7 +258,7 @@ def direct(D, W, edges, b, lam, fixed):
         except (RuntimeError, np.linalg.LinAlgError):          # singular: no damping and a floating component
             return x, 0
     if np.all(np.isfinite(sol)):
-        x[free] = sol.reshape(-1, 6)
+        x[free] = sol.reshape(-1, nb)
     return x, 0
 
 
@@ -274,10 +275,17 @@ def optimize(poses, edges, fixed=0, iterations=10, solver="pcg", pcg_max_iters=1
         return poses, res
     if len(poses) == 0:
         return poses, res
-    chi2, b, D, W = linearize(poses, edges)
+    return lm_control(poses, lambda P: linearize(P, edges), oplus, edges, fixed, iterations, solver, pcg_max_iters, pcg_rel_tol, res)
+
+
+def lm_control(poses, linearize_fn, oplus_fn, edges, fixed, iterations, solver, pcg_max_iters, pcg_rel_tol, res):
+    """The LM control of the header of this file over any vertex type: linearize_fn(vertices) -> (chi2, b, D, W) with square
+    blocks of any one size, oplus_fn(vertex, d) -> vertex. `poses` is an array of vertices, copied per trial; `edges` is read
+    for the vertex indices e[0], e[1] only. optimize() above and sgraph_ref.optimize() are its two callers."""
+    chi2, b, D, W = linearize_fn(poses)
     res["chi2_initial"] = chi2
     free = [v for v in range(len(poses)) if v != fixed]
-    lam = 1e-5 * max([D[v, k, k] for v in free for k in range(6)], default=0.0)
+    lam = 1e-5 * max([D[v, k, k] for v in free for k in range(D.shape[-1])], default=0.0)
     ni = 2.0
     for _it in range(iterations):
         accepted = False
@@ -290,9 +298,9 @@ def optimize(poses, edges, fixed=0, iterations=10, solver="pcg", pcg_max_iters=1
             res["pcg_iterations"] += n
             trial = poses.copy()
             for v in free:
-                trial[v] = oplus(poses[v], dx[v])
+                trial[v] = oplus_fn(poses[v], dx[v])
             scale = float((dx[free] * (lam * dx[free] + b[free])).sum()) + 1e-3
-            lin = linearize(trial, edges)
+            lin = linearize_fn(trial)
             rho = (chi2 - lin[0]) / scale
             ok = bool(rho > 0 and np.isfinite(lin[0]))
             res["trace"].append(dict(iteration=_it, trial=_trial, rho=float(rho), accepted=ok, lambda_=float(lam),

@@ -63,9 +63,20 @@
 // reference verification has accepted a candidate, the landmarks the two keyframes own in the tracker's map are joined through
 // the candidate's match list and aligned (aria_hip/HipSim3Aligner.hpp, makeSim3Verifier). A valid alignment with at least 20
 // inliers (ORB-SLAM's constant, untuned) replaces the candidate's unit-length relative pose by [R t] in map units, which is
-// what --optimize then hands the pose graph; otherwise the candidate stays as it was. s is only reported. FILE gets one line
+// what --optimize then hands the pose graph; otherwise the candidate stays as it was. s is reported, and used by --loop-correct. FILE gets one line
 // per accepted loop: query id, match id, s, n_corr, n_inliers, rms_px, replaced (0 or 1); one line "loop align sim3
 // candidates C replaced R" is printed. Off by default; without the flag every output is what it was, byte for byte.
+//
+// --loop-correct [--loop-correct-map FILE.ply] (needs --optimize and --loop-align sim3): the final optimisation runs the Sim(3)
+// pose graph (aria_hip/HipSim3GraphOptimizer.hpp; include/aria_orb_hip.h, "Sim(3) pose-graph optimisation") instead of the SE(3)
+// one, over the trajectory the map lives in: every frame is a vertex with the camera-to-world inverse (host, fp64) of its
+// --track-map pose, consecutive frames are joined by their relative pose at s = 1, and every loop candidate whose alignment
+// was accepted (replaced = 1) adds the edge match -> query with the aligner's (R, t, s) at 10x; a candidate that was not
+// aligned adds nothing. After optimize(50) the tracker's map is corrected: the points of a pair move with the first frame whose
+// MapTracker::anchorPair() is that pair. --optimize FILE then gets the corrected poses [R_new t_new] of that trajectory
+// (camera-to-world, s dropped), FILE.ply the corrected map, and "loop correct edges E moved M left L refused R" is printed.
+// Without the flag every output is what it was, byte for byte. On the synthetic flat-scene sequence no candidate reaches the
+// aligner, so there the flag is run for its plumbing only; what it is for is tests/cpp/sgraph_selftest.cpp's closed walk.
 //
 // --bundle FILE3 [--bundle-window N] (needs --track-map): local bundle adjustment of the tracked trajectory, post hoc as
 // --optimize is (aria_hip/HipBundleAdjuster.hpp; the reference names the step, README.md:1162, and has no code for it). The
@@ -207,6 +218,7 @@
 #include "aria_hip/HipVolumeRenderer.hpp"
 #include "aria_hip/DenseTracker.hpp"
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
+#include "aria_hip/HipSim3GraphOptimizer.hpp"
 #include "aria_hip/HipDenseStereo.hpp"
 #include "aria_hip/HipRectifier.hpp"
 #include "aria_hip/HipSensorFusion.hpp"
@@ -245,7 +257,7 @@ std::uint64_t frame_hash(const core::Frame& f, const std::vector<core::Match>& m
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--local-map K] [--local-radius PX] [--bundle file] [--bundle-window N] [--optimize file] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--mesh file2.ply] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
+        std::fprintf(stderr, "Usage: %s <dataset_path> [max_features] [--legacy-order] [--csv file] [--loop] [--loop-verify reference] [--devices N] [--shards K] [--batch B] [--decode-threads T] [--pose file] [--map file.ply] [--track-map file] [--local-map K] [--local-radius PX] [--bundle file] [--bundle-window N] [--optimize file] [--loop-correct] [--loop-correct-map file.ply] [--fuse file] [--eval file] [--eval-align none|se3|sim3] [--rpe-delta N] [--stereo baseline_m] [--stereo-out file] [--rectify] [--dense file] [--volume file.ply] [--voxel m] [--mesh file2.ply] [--plan file] [--render prefix] [--render-every n] [--alerts file]\n"
                              "  --track-dense file2: frame-to-model tracking of the --dense depth maps against a volume of its own (needs --volume): one TUM line per frame\n"
                              "  --alerts file: obstacle alerts from the --dense depth maps (zones; needs --dense): one line per announced event\n"
                              "  --render prefix: the --volume map cast at every n-th integrated pose (--render-every n, default 10; needs --volume):\n"
@@ -273,7 +285,10 @@ int main(int argc, char** argv) {
                              "  --bundle file: local bundle adjustment of the --track-map trajectory in windows of --bundle-window N frames (default 10, at most 16),\n"
                              "                 stride N - 2, the first two poses of a window fixed (needs --track-map)\n"
                              "  --optimize file: pose graph over the --pose chain and the verified loops (needs --pose, --loop, --loop-verify reference), final optimize(50);\n"
-                             "                   the per-loop optimize(10) and reset of current_pose of the reference are not reproduced (the loop step is post hoc)\n", argv[0]);
+                             "                   the per-loop optimize(10) and reset of current_pose of the reference are not reproduced (the loop step is post hoc)\n"
+                             "  --loop-correct [--loop-correct-map file.ply]: the final optimisation is the Sim(3) graph over the --track-map trajectory, loop edges\n"
+                             "                   carry the accepted alignments' scale, and the tracker's map is corrected by each pair's anchor frame (needs --optimize\n"
+                             "                   and --loop-align sim3); plumbing only on a sequence without loops\n", argv[0]);
         return -1;                                                        // euroc_eval.cpp:64-70
     }
     int max_features = 2000, devices = 1, shards = 0, batch = 0, decode_threads = 4;
@@ -286,7 +301,8 @@ int main(int argc, char** argv) {
     int loop_bow = 0, loop_bow_top = 10, loop_capacity = 500;
     bool loop_bow_given = false;
     std::string loop_bow_vocab;
-    std::string loop_align, loop_align_out;
+    std::string loop_align, loop_align_out, loop_correct_map;
+    bool loop_correct = false;
     std::string csv, pose_file, map_file, track_file, loop_verify, optimize_file, fuse_file, eval_file, eval_align = "sim3";
     int rpe_delta = 10;
     double stereo_baseline = 0.0;
@@ -317,6 +333,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--loop-capacity") && i + 1 < argc) loop_capacity = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--loop-align") && i + 1 < argc) loop_align = argv[++i];
         else if (!std::strcmp(argv[i], "--loop-align-out") && i + 1 < argc) loop_align_out = argv[++i];
+        else if (!std::strcmp(argv[i], "--loop-correct")) loop_correct = true;
+        else if (!std::strcmp(argv[i], "--loop-correct-map") && i + 1 < argc) loop_correct_map = argv[++i];
         else if (!std::strcmp(argv[i], "--optimize") && i + 1 < argc) optimize_file = argv[++i];
         else if (!std::strcmp(argv[i], "--fuse") && i + 1 < argc) fuse_file = argv[++i];
         else if (!std::strcmp(argv[i], "--eval") && i + 1 < argc) eval_file = argv[++i];
@@ -362,6 +380,10 @@ int main(int argc, char** argv) {
     if (!optimize_file.empty() && (pose_file.empty() || !verify_reference)) {
         std::fprintf(stderr, "--optimize needs --pose, --loop and --loop-verify reference (loop edges carry the verified relative pose)\n");
         return -1;
+    }
+    if ((loop_correct || !loop_correct_map.empty()) && (!loop_correct || optimize_file.empty() || !align_sim3)) {
+        std::fprintf(stderr, "--loop-correct [--loop-correct-map FILE.ply] needs --optimize and --loop-align sim3 (the map it corrects is --track-map's)\n");
+        return 1;
     }
     if (!fuse_file.empty() && pose_file.empty()) {
         std::fprintf(stderr, "--fuse needs --pose (the filter is updated with the pose stage's relative poses)\n");
@@ -510,6 +532,9 @@ int main(int argc, char** argv) {
     // --loop-align sim3: the anchor pair of every tracked frame, and the tracker (its map) kept for the loop step
     std::vector<int> track_anchor(align_sim3 ? N : 0, -1);
     std::unique_ptr<adapters::hip::MapTracker> kept_tracker;
+    // --loop-correct: the Sim(3) loop edges, from = the matched keyframe (keyframe 2 of the alignment), to = the query (keyframe 1)
+    struct CorrectEdge { int from, to; adapters::hip::GraphPose Z; double s; };
+    std::vector<CorrectEdge> correct_edges;
     adapters::hip::PoseIntrinsics track_K;
     // --bundle: what the tracker did, step by step, and the sequence frame its first frame is
     adapters::hip::WindowBuilder bundle_builder;
@@ -918,6 +943,7 @@ int main(int argc, char** argv) {
         std::unique_ptr<adapters::hip::HipSim3Aligner> aligner;        // --loop-align sim3
         std::ofstream align_out;
         long long align_candidates = 0, align_replaced = 0;
+        std::vector<adapters::hip::Sim3Report> detect_reports;        // --loop-correct: what the verifier said during one detect()
         if (verify_reference) {
             fund = std::make_unique<adapters::hip::HipFundamentalEstimator>();
             pose = std::make_unique<adapters::hip::HipPoseEstimator>(adapters::hip::referenceLoopIntrinsics());
@@ -942,6 +968,7 @@ int main(int argc, char** argv) {
                 auto report = [&](const adapters::hip::Sim3Report& r) {
                     align_candidates++;
                     align_replaced += r.replaced ? 1 : 0;
+                    if (loop_correct) detect_reports.push_back(r);
                     if (align_out.is_open())
                         align_out << r.query_id << ' ' << r.match_id << ' ' << r.s << ' ' << r.n_corr << ' ' << r.n_inliers << ' ' << r.rms_px
                                   << ' ' << (r.replaced ? 1 : 0) << '\n';
@@ -959,6 +986,7 @@ int main(int argc, char** argv) {
             kf.timestamp = seq.at(i).timestamp;
             kf.frame = *o.frame;
             kf.frame.id = i;
+            detect_reports.clear();
             auto lp = ld.detect(kf);
             ld.addKeyFrame(kf);
             o.is_keyframe = true;
@@ -969,6 +997,12 @@ int main(int argc, char** argv) {
             if (lp) { o.loop_match_id = (long long)lp->match_id; o.loop_score = lp->score; }
             if (lp && graph)                                               // euroc_eval.cpp:235
                 graph->addLoopEdge((int)lp->query_id, (int)lp->match_id, adapters::hip::loopRelativePose(*lp));
+            if (lp && loop_correct)                                        // the accepted alignment of this candidate, if there is one
+                for (const adapters::hip::Sim3Report& r : detect_reports)
+                    if (r.replaced && r.query_id == lp->query_id && r.match_id == lp->match_id) {
+                        correct_edges.push_back({(int)lp->match_id, (int)lp->query_id, adapters::hip::loopRelativePose(*lp), r.s});
+                        break;
+                    }
         }
         if (aligner)
             std::printf("loop align sim3 candidates %lld replaced %lld%s%s\n", align_candidates, align_replaced,
@@ -1075,7 +1109,66 @@ int main(int argc, char** argv) {
         std::printf("fused %lld updates | imu samples %zu: %lld predicted %lld skipped %lld before the first pose -> %s\n", updates,
                     samples.size(), predicted, skipped, ignored, fuse_file.c_str());
     }
-    if (graph) {                                                           // euroc_eval.cpp:282-288
+    if (graph && loop_correct) {                                           // the Sim(3) graph over the tracker's trajectory
+        if (!kept_tracker) { std::fprintf(stderr, "--loop-correct: no tracker map was kept\n"); return 1; }
+        try {
+            adapters::hip::HipSim3GraphOptimizer sg;
+            auto poseOf = [&](std::size_t i) {
+                adapters::hip::GraphPose T = adapters::hip::GraphPose::Identity();
+                for (int a = 0; a < 4; a++)
+                    for (int b = 0; b < 4; b++) T(a, b) = track_traj[i][(size_t)(a * 4 + b)];
+                return T;
+            };
+            for (std::size_t i = 0; i < N; i++) {
+                const adapters::hip::GraphPose X = adapters::hip::cameraToWorld(poseOf(i));
+                sg.setInitialPose((int)i, X);
+                if (i > 0) {                                               // Z = X_{i-1}^-1 X_i = T_{i-1} T_i^-1
+                    const adapters::hip::GraphPose Tp = poseOf(i - 1);
+                    adapters::hip::GraphPose Z = adapters::hip::GraphPose::Identity();
+                    for (int a = 0; a < 3; a++)
+                        for (int b = 0; b < 4; b++) {
+                            double v = 0.0;
+                            for (int k = 0; k < 4; k++) v += Tp(a, k) * X(k, b);
+                            Z(a, b) = v;
+                        }
+                    sg.addOdometryEdge((int)i - 1, (int)i, Z);
+                }
+            }
+            for (const CorrectEdge& e : correct_edges) sg.addLoopEdge(e.from, e.to, e.Z, e.s);
+            sg.optimize(50);
+            std::vector<int> pair_anchor;                                  // pair id -> the first frame that owns it
+            for (std::size_t i = 0; i < N; i++) {
+                const int p = track_anchor[i];
+                if (p < 0) continue;
+                if ((std::size_t)p >= pair_anchor.size()) pair_anchor.resize((std::size_t)p + 1, -1);
+                if (pair_anchor[(std::size_t)p] < 0) pair_anchor[(std::size_t)p] = (int)i;
+            }
+            const aria_sgraph_correct_stats cs = sg.correctMap(kept_tracker->mapper().handle(), pair_anchor, 0);
+            if (!loop_correct_map.empty()) kept_tracker->mapper().exportPLY(loop_correct_map);
+            auto corrected = [&](std::size_t i) {
+                const adapters::hip::GraphPose m = sg.getOptimizedPose((int)i);
+                std::array<double, 16> T{};
+                for (int a = 0; a < 4; a++)
+                    for (int b = 0; b < 4; b++) T[(size_t)(a * 4 + b)] = m(a, b);
+                return T;
+            };
+            write_tum(optimize_file, corrected);
+            if (!eval_file.empty())
+                for (std::size_t i = 0; i < N; i++) {
+                    const std::array<double, 16> T = corrected(i);
+                    for (int a = 0; a < 3; a++) optimized_xyz.push_back(T[(size_t)(a * 4 + 3)]);
+                }
+            const aria_sgraph_result& gr = sg.lastResult();
+            std::printf("sim3 pose graph %zu vertices %zu edges | chi2 %.6g -> %.6g in %d iterations (%d solves, %d PCG iterations) -> %s\n",
+                        sg.numVertices(), sg.numEdges(), gr.chi2_initial, gr.chi2_final, gr.iterations_done, gr.trials, gr.pcg_iterations,
+                        optimize_file.c_str());
+            std::printf("loop correct edges %zu moved %d left %d refused %d%s%s\n", correct_edges.size(), cs.moved, cs.left_alone, cs.refused,
+                        loop_correct_map.empty() ? "" : " -> ", loop_correct_map.c_str());
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "--loop-correct: %s\n", e.what());
+            return 1;
+        }
+    } else if (graph) {                                                    // euroc_eval.cpp:282-288
         graph->optimize(50);
         write_tum(optimize_file, [&](std::size_t i) {
             if (last_vertex[i] < 0) return traj[i];                        // before the first vertex: current_pose, the identity

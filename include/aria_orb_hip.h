@@ -2557,9 +2557,9 @@ int   aria_bow_query_device(aria_bow_t h, long long query_id, const uint8_t* d_d
  *   pair's place in a launch.
  * threshold_px = 3.0 is sqrt(9.21) rounded, ORB-SLAM's chi-square bound at octave 0; min_inliers = 20 likewise. Both are
  *   assumptions nobody has tuned on a recording.
- * Not built: a Sim(3) pose graph that distributes s around the loop (the SE(3) graph takes [R t]; s is only reported),
- *   correcting the map's points after a loop, fusing duplicate landmarks, guided re-matching after the first alignment
- *   (ORB-SLAM's SearchBySim3), per-octave thresholds, relocalisation. */
+ * Not built: fusing duplicate landmarks, guided re-matching after the first alignment (ORB-SLAM's SearchBySim3), per-octave
+ *   thresholds, relocalisation. (The Sim(3) pose graph that distributes s around the loop and the correction of the map's
+ *   points are aria_sgraph_*, below.) */
 typedef struct aria_sim3_s* aria_sim3_t;
 typedef struct {
     double X1[3];              /* landmark of keyframe 1, camera 1's coordinates                                 */
@@ -2627,6 +2627,111 @@ int   aria_sim3_associate_batch_device(aria_sim3_t h, aria_map_t map, const int*
                                        const int* d_n1, const aria_keypoint* d_kp2, const int* d_n2, int64_t kp_stride,
                                        const aria_match* d_matches, const int* d_nmatches, int n_pairs, int match_cap,
                                        aria_sim3_corr* d_corr, int* d_ncorr, int* d_corr_match);
+
+/* ---- Sim(3) pose-graph optimisation and map correction after a loop: the roles of ORB-SLAM's OptimizeEssentialGraph and
+ * CorrectLoop, batched over graphs. The reference has no code for either (its SE(3) graph, aria_graph_*, takes [R t] and
+ * cannot repair the scale a monocular run drifts in). Additive to ABI 4. aria_slam_amd/sgraph_ref.py restates the stage in
+ * NumPy and is its definition: aria_graph_*'s with a seventh coordinate. fp64, + - * / and sqrt only.
+ *
+ * Vertex. S = (R, t, s), camera-to-world: x_w = s R x_c + t. A B = (sA sB, RA RB, sA RA tB + tA); S^-1 = (1/s, R^T,
+ *   -(R^T t) / s). The record holds R row-major, then t, then s; pose rows [R t] interleave t, and the two copy calls below
+ *   convert (64-bit integer copies).
+ * Edge. Z = (R, t, s) measures S_from^-1 S_to; an odometry edge from SE(3) poses has s = 1; a loop edge from an
+ *   aria_sim3_result with keyframe 1 = `to` and keyframe 2 = `from` is its (R, t, s) as they stand. Information
+ *   info_scale * I7 (ORB-SLAM's identity, not tuned).
+ * Error. E = Z^-1 S_i^-1 S_j; e = (t_E, qv_E, (s_E - 1/s_E) / 2) with qv_E the vector part of R_E's unit quaternion, w >= 0.
+ *   The scale term is sinh(log s_E): odd under inversion, slope 1 at 1, no log. chi2 = sum info_scale * e.e.
+ * Update. S <- S * D(d), d of 7: D = (R(dq), dt, f(d7)) with aria_graph_*'s fromMQT on d[0..5] and f(x) = x + sqrt(x^2 + 1)
+ *   for x >= 0, 1 / (-x + sqrt(x^2 + 1)) for x < 0: the exact inverse of the scale error, always positive. The rotation is
+ *   then replaced by that of its unit quaternion. Analytic 7x7 Jacobians (sgraph_ref.py); with every scale 1 their upper-left
+ *   6x6 are aria_graph_*'s.
+ * LM, solver, determinism. Those of aria_graph_* on 7x7 blocks, lambda0 = 1e-5 max diag(H) over the free vertices. One
+ *   workgroup per graph; one form of the solve (the vectors in the handle's scratch, any size).
+ * fix_scale (per handle, for a metric map). The scale row of the error and the seventh row and column of both Jacobians are
+ *   zero, d7 = 0 exactly, and every vertex's s comes back bit for bit. With every s = 1 the poses are aria_graph_*'s up to
+ *   rounding.
+ * Invalid input. aria_graph_*'s rules, and a vertex s or an edge s that is not finite or <= 0: that graph gets valid = 0,
+ *   stop_reason 2, and none of its vertices is written; the other graphs of the batch are unaffected.
+ * Map correction. A point of pair p with pair_base <= p < pair_base + n_table and v = d_pair_vertex[p - pair_base] >= 0 (the
+ *   pair's anchor keyframe) moves by X' = S_new[v] S_old[v]^-1 X in one fixed operation order, the same bits as the
+ *   restatement: d = X - t_old; c_k = ((Ro[0][k] d0 + Ro[1][k] d1) + Ro[2][k] d2) / s_old;
+ *   X'_k = s_new * ((Rn[k][0] c0 + Rn[k][1] c1) + Rn[k][2] c2) + t_new_k. Every other byte of the record is untouched. A pair
+ *   outside the table, or v = -1, leaves the point alone. A v >= n_vertices, a used vertex whose s (old or new) is not finite
+ *   or <= 0, or an X that is not finite leaves the point alone, counts it as refused and defers ARIA_E_INVALID.
+ * Poses after correction. [R_new t_new] with s dropped: a point at camera coordinates x_c is now at s_new x_c -- the local
+ *   structure is rescaled, the camera is not.
+ * Not built: a multi-workgroup solve of one very large graph; the register and LDS forms of aria_graph_*'s solve; covisibility
+ *   and spanning-tree edge selection (the "essential" of the essential graph); landmark fusion and SearchBySim3; bundle
+ *   adjustment after the correction; correcting the TSDF volume; per-edge 7x7 information; robust kernels; tuning of the
+ *   adapters' x10 loop weight. */
+typedef struct aria_sgraph_s* aria_sgraph_t;
+typedef struct {
+    int      struct_size;      /* = sizeof(aria_sgraph_config)                                                  */
+    int      device;
+    void*    stream;           /* borrowed hipStream_t, or NULL = the handle owns one (non-blocking, see aria_graph_config) */
+    int      max_graphs;       /* as aria_graph_config                                                           */
+    int      max_vertices;
+    int      max_edges;
+    int      pcg_max_iters;
+    double   pcg_rel_tol;
+    int      fix_scale;        /* 0 or 1 (default 0)                                                             */
+    int      reserved;         /* 0                                                                              */
+} aria_sgraph_config;          /* 48 bytes                                                                       */
+typedef struct {
+    double   R[9], t[3], s;    /* x_w = s R x_c + t                                                              */
+} aria_sgraph_vertex;          /* 104 bytes                                                                      */
+typedef struct {
+    int32_t  from, to;         /* vertex indices of the graph                                                    */
+    double   info_scale;       /* information = info_scale * I7                                                  */
+    double   Z[12];            /* rows of [R t] of the measured S_from^-1 S_to                                   */
+    double   s;                /* its scale                                                                      */
+} aria_sgraph_edge;            /* 120 bytes                                                                      */
+typedef struct {
+    double   chi2_initial, chi2_final, lambda;
+    int      iterations_done, trials, pcg_iterations, valid, stop_reason, reserved;   /* as aria_graph_result */
+} aria_sgraph_result;          /* 48 bytes                                                                       */
+typedef struct {
+    int      moved, left_alone, refused, reserved;
+} aria_sgraph_correct_stats;   /* 16 bytes                                                                       */
+
+void  aria_sgraph_default_config(aria_sgraph_config* cfg);
+int   aria_sgraph_create(const aria_sgraph_config* cfg, aria_sgraph_t* out);
+void  aria_sgraph_destroy(aria_sgraph_t h);
+void* aria_sgraph_stream(aria_sgraph_t h);
+/* Synchronises the handle's stream and returns the deferred error of the device calls since the last check, once:
+ * ARIA_E_INVALID when some graph was invalid or some point was refused, else ARIA_E_TOO_LARGE when some graph had more
+ * vertices or edges than the handle was created for (that graph: valid = 0, nothing read, nothing written). */
+int   aria_sgraph_check(aria_sgraph_t h);
+/* One graph, host arrays; blocks. Invalid input: ARIA_E_INVALID, larger than the handle: ARIA_E_TOO_LARGE, in both cases
+ * nothing is written. */
+int   aria_sgraph_optimize(aria_sgraph_t h, aria_sgraph_vertex* vertices_inout, int n_vertices, int fixed_index,
+                           const aria_sgraph_edge* edges, int n_edges, int iterations, aria_sgraph_result* result);
+/* Device-resident batch with the offsets and the meaning of aria_graph_optimize_batch_device: graph g owns the vertices
+ * d_vertex_offset[g] .. d_vertex_offset[g+1] and the edges d_edge_offset[g] .. d_edge_offset[g+1] (indices relative to the
+ * graph), fixed vertex d_fixed[g]. Writes d_vertices in place and d_results[g]. Enqueued; data errors: aria_sgraph_check. */
+int   aria_sgraph_optimize_batch_device(aria_sgraph_t h, aria_sgraph_vertex* d_vertices, const int* d_vertex_offset,
+                                        const aria_sgraph_edge* d_edges, const int* d_edge_offset, const int* d_fixed,
+                                        int n_graphs, int iterations, aria_sgraph_result* d_results);
+/* Test hook: one graph (host arrays) linearised at its vertices. chi2; b (n_vertices * 7); H_diag (n_vertices * 49, row-major
+ * 7x7 diagonal blocks); H_off (n_edges * 49, the block at (from, to) of every edge; its transpose sits at (to, from)).
+ * Nothing of the fixed vertex is removed. Blocks. */
+int   aria_sgraph_debug_linearize(aria_sgraph_t h, const aria_sgraph_vertex* vertices, int n_vertices, int fixed_index,
+                                  const aria_sgraph_edge* edges, int n_edges, double* chi2, double* b, double* H_diag,
+                                  double* H_off);
+/* n vertices from n pose rows (12 doubles each, camera-to-world), s = 1; and n pose rows from n vertices, s dropped. Enqueued. */
+int   aria_sgraph_vertices_from_pose_device(aria_sgraph_t h, const double* d_poses, aria_sgraph_vertex* d_vertices, int n);
+int   aria_sgraph_poses_from_vertices_device(aria_sgraph_t h, const aria_sgraph_vertex* d_vertices, double* d_poses, int n);
+/* The map correction (above) on the map handle's arena, read with its device-resident size. d_stats (optional) is cleared and
+ * then counts the points moved, left alone and refused. Enqueued on this handle's stream; the stream order, the arena-address
+ * caveat and the other-device refusal are those of aria_pnp_associate_batch_device. This call writes the arena of another
+ * handle: nothing else may use the map until it has run. */
+int   aria_sgraph_correct_map_device(aria_sgraph_t h, aria_map_t map, const int* d_pair_vertex, int n_table, int pair_base,
+                                     const aria_sgraph_vertex* d_old, const aria_sgraph_vertex* d_new, int n_vertices,
+                                     aria_sgraph_correct_stats* d_stats);
+/* The same correction on n_points records of the caller's own device array (a map kept elsewhere, a test). */
+int   aria_sgraph_correct_points_device(aria_sgraph_t h, aria_map_point* d_points, int64_t n_points, const int* d_pair_vertex,
+                                        int n_table, int pair_base, const aria_sgraph_vertex* d_old,
+                                        const aria_sgraph_vertex* d_new, int n_vertices, aria_sgraph_correct_stats* d_stats);
 
 /* ---- synthetic workload: integer-only generator, identical bytes everywhere ------------ */
 int aria_synth_frame_pair(uint64_t seed, int width, int height, uint8_t* frame_a, uint8_t* frame_b);

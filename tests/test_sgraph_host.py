@@ -1,0 +1,409 @@
+"""Sim(3) pose-graph optimisation and map correction (include/aria_orb_hip.h, "Sim(3) pose-graph optimisation"): the parts
+that need no GPU -- exports and layouts, the NumPy restatement (aria_slam_amd/sgraph_ref.py: the Jacobians against central
+differences, the scale update against the scale error, the reduction to graph_ref with every scale 1, the closed walk whose
+scale drift only a 7-DoF graph can distribute, the map correction), the case table (tests/sgraph_cases.py) and the kernel's
+compile for gfx950."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sgraph_cases as SC      # noqa: E402
+
+SGRAPH_SYMBOLS = ["aria_sgraph_default_config", "aria_sgraph_create", "aria_sgraph_destroy", "aria_sgraph_stream",
+                  "aria_sgraph_check", "aria_sgraph_optimize", "aria_sgraph_optimize_batch_device", "aria_sgraph_debug_linearize",
+                  "aria_sgraph_vertices_from_pose_device", "aria_sgraph_poses_from_vertices_device",
+                  "aria_sgraph_correct_map_device", "aria_sgraph_correct_points_device"]
+
+# ---- the output of tools/sgraph_walk.py (the exact loop edge), copied
+WALK_REF = (0.038372, 0.056150)    # sgraph_ref: ATE rms, max over the 16 centres
+WALK_SE3 = (0.365084, 0.604557)    # graph_ref with the same [R t]
+SCALE_GAP = 1.787e-03              # largest |s_i - 1.5^(-i/15)|
+
+
+def test_sgraph_symbols_exported_and_listed(aria):
+    from aria_slam_amd import _lib
+    L = aria.load_library()
+    header = open(os.path.join(ROOT, "include", "aria_orb_hip.h")).read()
+    for name in SGRAPH_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % name, header), "%s not declared in the header" % name
+        assert hasattr(L, name), "libaria_orb_hip.so does not export %s" % name
+        assert name in _lib.EXPORTS, "%s missing from _lib.EXPORTS" % name
+    assert aria.abi_version() == 4
+    assert aria.HipSim3GraphOptimizer and "sgraph" in _lib.STAGES
+
+
+def test_sgraph_record_layouts_and_defaults(aria, tmp_path):
+    from aria_slam_amd import _lib
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include "aria_orb_hip.h"\nint main(void) { printf("%zu %zu %zu %zu %zu\\n", '
+                   'sizeof(aria_sgraph_config), sizeof(aria_sgraph_vertex), sizeof(aria_sgraph_edge), sizeof(aria_sgraph_result), '
+                   'sizeof(aria_sgraph_correct_stats)); return 0; }\n')
+    exe = tmp_path / "sz"
+    subprocess.check_call(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    cfg_size, v_size, e_size, r_size, s_size = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True,
+                                                                                 check=True).stdout.split()]
+    assert C.sizeof(_lib.SgraphConfig) == cfg_size == 48
+    assert _lib.SGRAPH_VERTEX_DTYPE.itemsize == v_size == 104
+    assert _lib.SGRAPH_EDGE_DTYPE.itemsize == e_size == 120
+    assert _lib.SGRAPH_RESULT_DTYPE.itemsize == r_size == _lib.GRAPH_RESULT_DTYPE.itemsize == 48
+    assert _lib.SGRAPH_RESULT_DTYPE.names == _lib.GRAPH_RESULT_DTYPE.names
+    assert _lib.SGRAPH_STATS_DTYPE.itemsize == s_size == 16
+    cfg = _lib.SgraphConfig()
+    aria.load_library().aria_sgraph_default_config(C.byref(cfg))
+    assert cfg.struct_size == 48 and cfg.max_graphs == 1 and cfg.pcg_max_iters == 1000 and cfg.pcg_rel_tol == 1e-8
+    assert cfg.max_vertices == 4096 and cfg.max_edges == 8192 and cfg.fix_scale == 0
+
+
+# ---- sgraph_ref: Sim(3) ---------------------------------------------------------------------------------------------------------
+def test_group_laws_and_update():
+    from aria_slam_amd import graph_ref as G
+    from aria_slam_amd import sgraph_ref as S
+    rng = np.random.default_rng(0)
+    for _ in range(20):
+        A, B = (S.vertex_from_pose(G.random_pose(rng, 2.0), rng.uniform(0.3, 3)) for _ in range(2))
+        x = rng.normal(size=3)
+        act = lambda V, p: V[12] * (V[:9].reshape(3, 3) @ p) + V[9:12]      # noqa: E731
+        assert np.abs(act(S.mul(A, B), x) - act(A, act(B, x))).max() < 1e-13
+        assert np.abs(act(S.inv(A), act(A, x)) - x).max() < 1e-13
+        ident = S.mul(A, S.inv(A))
+        assert np.abs(ident - S.make_vertex(np.eye(3), np.zeros(3), 1.0)).max() < 1e-14
+    # the update with d = 0 keeps t and s bit for bit and re-orthonormalises R; d7 alone scales s by f(d7)
+    Y = S.oplus(A, np.zeros(7))
+    assert np.array_equal(Y[9:], A[9:]) and np.abs(Y[:9] - A[:9]).max() < 1e-15
+    Y = S.oplus(A, np.array([0, 0, 0, 0, 0, 0, 0.3]))
+    assert Y[12] == A[12] * S.f(0.3) and np.array_equal(Y[9:12], A[9:12])
+
+
+def test_scale_update_is_the_inverse_of_the_scale_error():
+    """f and the scale error g(s) = (s - 1/s) / 2 are inverse to each other. g subtracts 1/f from f, each rounded at its own
+    size, so the round trip cannot be known closer than one ulp of the larger of the two operands (at x = 1e-9 that is 2e-16
+    absolute, 1e-7 of x: the conditioning of g at s = 1, not an error of f). That ulp is the bound; f(-x) f(x) = 1 to one ulp
+    of 1."""
+    from aria_slam_amd import sgraph_ref as S
+    grid = [0.0] + [sgn * x for x in (1e-9, 1e-6, 1e-3, 0.1, 0.5, 1.0, 2.0, 5.0, 20.0) for sgn in (1.0, -1.0)]
+    for x in grid:
+        fx = S.f(x)
+        assert fx > 0
+        ulp = np.spacing(max(fx, 1.0 / fx))
+        got = S.scale_error(fx)
+        print("x %g: round trip off by %.3g ulp, f(-x) f(x) - 1 = %.3g" % (x, abs(got - x) / ulp, S.f(-x) * fx - 1.0))
+        assert abs(got - x) <= ulp, (x, got)
+        assert abs(S.f(-x) * fx - 1.0) <= np.spacing(1.0), x
+    assert S.f(0.0) == 1.0
+
+
+def _graph_ref_jacobian_gap(h):
+    """graph_ref's own analytic-vs-numeric difference with the sampling of tests/test_graph_host.py."""
+    from aria_slam_amd import graph_ref as G
+    rng = np.random.default_rng(1)
+    worst = 0.0
+    for k in range(40):
+        Xi, Xj = G.random_pose(rng, 3.0), G.random_pose(rng, 3.0)
+        Z = G.inv(Xi) @ Xj @ G.random_pose(rng, 0.1, 0.1) if k % 2 else G.random_pose(rng, 3.0)
+        _e, Ji, Jj = G.edge_jacobians(Xi, Xj, Z)
+        if G.quat_from_rot((G.inv(Z) @ G.inv(Xi) @ Xj)[:3, :3])[3] < 1e-3:
+            continue
+        ni, nj = G.numeric_jacobians(Xi, Xj, Z, h)
+        worst = max(worst, np.abs(Ji - ni).max(), np.abs(Jj - nj).max())
+    return worst
+
+
+def test_analytic_jacobians_against_central_differences():
+    """The bound is graph_ref's own analytic-vs-numeric difference at the same step h = 1e-6, measured here with the sampling of
+    tests/test_graph_host.py (`base`, 2.2e-9 when that test was written), times the margin that test gives it: it allows 1e-7,
+    a factor of 1e-7 / 2.2e-9."""
+    from aria_slam_amd import graph_ref as G
+    from aria_slam_amd import sgraph_ref as S
+    h = 1e-6
+    base = _graph_ref_jacobian_gap(h)
+    bound = base * (1e-7 / 2.2e-9)
+    rng = np.random.default_rng(1)
+    rv = lambda t=3.0, a=np.pi, lo=0.3, hi=3.0: S.vertex_from_pose(G.random_pose(rng, t, a), rng.uniform(lo, hi))   # noqa: E731
+    samples = []
+    for k in range(40):                       # random vertices, scales in [0.3, 3]; Z near the relative similarity, and anywhere
+        Si, Sj = rv(), rv()
+        Zs = S.mul(S.mul(S.inv(Si), Sj), rv(0.1, 0.1, 0.8, 1.25)) if k % 2 else rv()
+        samples.append((Si, Sj, Zs))
+    for w_target in (0.05, 0.01):             # w near 0: a residual rotation just short of a half turn
+        Si, Sj = rv(), rv()
+        turn = S.vertex_from_pose(G.make_pose(G.rot_axis(rng.normal(size=3), 2 * np.arccos(w_target)), rng.normal(size=3)), 1.1)
+        samples.append((Si, Sj, S.mul(S.mul(S.inv(Si), Sj), turn)))
+    for far in (20.0, 0.05):                  # s_E far from 1
+        Si, Sj = rv(), rv()
+        samples.append((Si, Sj, S.mul(S.mul(S.inv(Si), Sj), S.vertex_from_pose(G.random_pose(rng, 0.1, 0.1), 1.0 / far))))
+    worst, used = 0.0, 0
+    for Si, Sj, Zs in samples:
+        Z, sz = S.pose_of(Zs), Zs[12]
+        e, Ji, Jj = S.edge_jacobians(Si, Sj, Z, sz)
+        assert np.array_equal(e, S.edge_error(Si, Sj, Z, sz))
+        E = S.mul(S.inv(Zs), S.mul(S.inv(Si), Sj))
+        if S.quat_from_rot(E[:9].reshape(3, 3))[3] < 1e-3:
+            continue                          # at w = 0 the sign choice makes the error discontinuous
+        ni, nj = S.numeric_jacobians(Si, Sj, Z, sz, h)
+        worst, used = max(worst, np.abs(Ji - ni).max(), np.abs(Jj - nj).max()), used + 1
+    print("graph_ref %.3g, sgraph_ref %.3g over %d samples, bound %.3g" % (base, worst, used, bound))
+    assert used >= 40 and worst < bound, worst
+    # the scale extremes were really reached
+    ses = [S.mul(S.inv(Zs), S.mul(S.inv(Si), Sj))[12] for Si, Sj, Zs in samples[-2:]]
+    assert max(ses) > 10 and min(ses) < 0.1
+
+
+def test_with_every_scale_one_the_6x6_parts_are_graph_refs():
+    from aria_slam_amd import graph_ref as G
+    from aria_slam_amd import sgraph_ref as S
+    poses, edges, V, E = SC.se3_graph()
+    for a, b, _w, Z in edges[:6]:
+        e6, Ji6, Jj6 = G.edge_jacobians(poses[a], poses[b], Z)
+        e, Ji, Jj = S.edge_jacobians(V[a], V[b], Z[:3], 1.0)
+        # the two files order the translation's sum differently (R^T (tj - ti) here, a 4x4 product there): rounding only
+        assert np.abs(e[:6] - e6).max() < 1e-14 and np.abs(Ji[:6, :6] - Ji6).max() < 1e-14 and np.abs(Jj[:6, :6] - Jj6).max() < 1e-14
+        assert e[6] == 0.0 and Jj[6, 6] == 1.0 and Ji[6, 6] == -1.0
+    c6, b6, D6, W6 = G.linearize(poses, edges)
+    c, b, D, W = S.linearize(V, S.norm_edges(E), fix_scale=True)
+    scale = np.abs(D6).max()
+    assert abs(c - c6) <= 1e-13 * c6
+    assert np.abs(b[:, :6] - b6).max() <= 1e-13 * np.abs(b6).max()
+    assert np.abs(D[:, :6, :6] - D6).max() <= 1e-13 * scale and np.abs(W[:, :6, :6] - W6).max() <= 1e-13 * scale
+    # fix_scale: the seventh row and column of every block and of b carry nothing
+    assert not b[:, 6].any() and not D[:, 6, :].any() and not D[:, :, 6].any() and not W[:, 6, :].any() and not W[:, :, 6].any()
+
+
+def test_fix_scale_optimize_is_graph_refs_and_keeps_every_scale():
+    from aria_slam_amd import graph_ref as G
+    from aria_slam_amd import sgraph_ref as S
+    poses, edges, V, E = SC.se3_graph()
+    P, r6 = G.optimize(poses, edges, 0, SC.SE3_ITERATIONS, "pcg")
+    Vo, r7 = S.optimize(V, E, 0, SC.SE3_ITERATIONS, "pcg", fix_scale=True)
+    gap = float(np.abs(S.poses_of(Vo) - P).max())
+    print("fix_scale against graph_ref: %.3g (recorded %.3g)" % (gap, SC.FIX_SCALE_GAP))
+    assert gap <= 10 * SC.FIX_SCALE_GAP
+    assert (r6["trials"], r6["iterations_done"], r6["stop_reason"]) == (r7["trials"], r7["iterations_done"], r7["stop_reason"])
+    assert Vo[:, 12].tobytes() == V[:, 12].tobytes()
+    # scales other than 1 come back bit for bit too, and d7 is exactly 0 in every trial
+    V2, E2 = SC.graph("random40")
+    Vo2, _r = S.optimize(V2, E2, 0, 2, "pcg", fix_scale=True)
+    assert Vo2[:, 12].tobytes() == V2[:, 12].tobytes() and not np.array_equal(Vo2[:, :12], V2[:, :12])
+
+
+def test_invalid_scales_make_the_graph_invalid():
+    from aria_slam_amd import sgraph_ref as S
+    V, E = SC.graph("random40")
+    for bad in (0.0, -1.0, np.nan, np.inf):
+        Vb = V.copy()
+        Vb[5, 12] = bad
+        Vo, r = S.optimize(Vb, E, 0, 3)
+        assert r["valid"] == 0 and r["stop_reason"] == S.STOP_INVALID and Vo.tobytes() == Vb.tobytes()
+        Eb = list(E)
+        Eb[3] = Eb[3][:4] + (bad,)
+        Vo, r = S.optimize(V, Eb, 0, 3)
+        assert r["valid"] == 0 and r["stop_reason"] == S.STOP_INVALID and Vo.tobytes() == V.tobytes()
+    Vo, r = S.optimize(V, [(3, 3, 1.0, np.eye(4), 1.0)], 0, 3)
+    assert r["valid"] == 0
+    Vo, r = S.optimize(V, E, 0, 0)
+    assert r["valid"] == 1 and Vo.tobytes() == V.tobytes() and r["trials"] == 0
+
+
+# ---- the case table ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c.name for c in SC.CASES])
+def test_case_has_its_pattern_under_both_solvers_with_a_margin(name):
+    """A condition on the inputs: no decision of a case is near enough to rho = 0 for another summation order to flip it;
+    and the copied figures are this table's."""
+    from aria_slam_amd import sgraph_ref as S
+    c = SC.BY_NAME[name]
+    V, E = SC.graph(name)
+    (Vd, rd), (Vp, rp) = SC.reference(name, c.iterations, "direct"), SC.reference(name, c.iterations, "pcg")
+    assert SC.pattern(rd) == SC.pattern(rp) == c.pattern
+    rho_d, rho_p = (np.array([t["rho"] for t in r["trace"]]) for r in (rd, rp))
+    for r, P in ((rd, Vd), (rp, Vp)):
+        assert r["iterations_done"] == c.iterations and r["stop_reason"] == S.STOP_ITERATIONS and r["valid"] == 1
+        assert P[c.fixed].tobytes() == V[c.fixed].tobytes()
+        if c.fix_scale:
+            assert P[:, 12].tobytes() == V[:, 12].tobytes()
+    lo = np.minimum(np.abs(rho_d), np.abs(rho_p))
+    assert (lo >= SC.RHO_MIN).all() and (lo >= SC.RHO_MARGIN * np.abs(rho_d - rho_p)).all()
+    assert len(SC.GAPS[name]) == c.iterations and abs(SC.MIN_RHO[name] - lo.min()) <= 1e-3
+    for k in range(1, c.iterations + 1):      # within a factor of two of the record, as tests/test_graph_host.py holds its table
+        for got, want in zip(SC.gap(name, k), SC.GAPS[name][k - 1]):
+            assert 0.5 * want <= got <= 2 * want, (k, SC.gap(name, k), SC.GAPS[name][k - 1])
+    if c.handle:
+        assert c.handle[0] >= len(V) and c.handle[1] >= len(E)
+
+
+def test_the_table_covers_every_path_and_boundary_of_the_kernel():
+    src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "sim3_graph.hip")).read()
+    lanes = int(re.search(r"SG_BLOCK\s*=\s*(\d+)", src).group(1))
+    assert lanes == 512 and "trial < LM_MAX_TRIALS" in src
+    sizes = {c.name: (len(SC.graph(c.name)[0]), len(SC.graph(c.name)[1])) for c in SC.CASES}
+    assert sizes["random40"][0] == 40 and sizes["v513"][0] == lanes + 1 and sizes["e513"][1] == lanes + 1
+    assert re.search(r"r+A", SC.BY_NAME["rejected"].pattern) and SC.BY_NAME["fixed7"].fixed == 7 and SC.BY_NAME["fixscale"].fix_scale
+    lin = {n: (len(SC.lin_graph(n)[0]), len(SC.lin_graph(n)[1])) for n, _a, _f in SC.LIN_GRAPHS}
+    assert lin == {"tiny": (3, 2), "v40e51": (40, 51), "v200e229": (200, 229)}
+    V, E, fixed = SC.lin_graph("tiny")
+    assert fixed == 1 and sorted((e[0], e[1]) for e in E) == [(0, 1), (1, 2)]      # both others hang on the fixed vertex alone
+    for n, _a, _f in SC.LIN_GRAPHS:
+        s = SC.lin_graph(n)[0][:, 12]
+        assert 0.5 <= s.min() and s.max() <= 2.0 and set(SC.LIN_GAPS) == set(lin)
+
+
+# ---- the walk: why the stage exists -------------------------------------------------------------------------------------------------
+def test_scale_drift_is_distributed_on_the_closed_walk():
+    """tools/sim3_walk.py's scene (imported, not copied), scale drifted to 1.5 at the last of 16 keyframes, the exact loop edge:
+    the 7-DoF graph gives every vertex the scale of the drift law 1.5^(-i/15) and an ATE strictly below what the SE(3) graph
+    makes of the same [R t]. SCALE_GAP and WALK_REF are tools/sgraph_walk.py's output; the law is held to twice the recorded
+    gap, the band tests/test_graph_host.py gives its recorded figures on another NumPy build."""
+    import sgraph_walk as SW
+    import sim3_walk as W
+    r = SW.run("exact")
+    law = W.DRIFT ** (-np.arange(W.K_FRAMES) / (W.K_FRAMES - 1.0))
+    print("ATE sim3 %s se3 %s before %s, scale gap %.3e" % (r["sim3"], r["se3"], r["before"], r["scale_gap"]))
+    assert np.abs(r["scales"] - law).max() <= 2 * SCALE_GAP
+    assert r["sim3"][0] < r["se3"][0] and r["sim3"][1] < r["se3"][1]            # the condition: strictly below
+    assert r["se3"][0] > r["before"][0]                                          # the SE(3) graph makes the walk worse
+    for got, want in zip(r["sim3"] + r["se3"], WALK_REF + WALK_SE3):
+        assert abs(got - want) <= 1e-3 * want, (got, want)
+    assert abs(r["scale_gap"] - SCALE_GAP) <= 0.05 * SCALE_GAP
+    # the alignment's own edge (s off by a few percent) still beats the SE(3) graph
+    a = SW.run("aligned")
+    assert a["sim3"][0] < a["se3"][0]
+    # the corrected map: every point has an anchor; pair 0 hangs on the fixed keyframe (its similarity is the identity up to
+    # the rounding of (X - t) + t), pair 1 shrinks about keyframe L - 1 by that keyframe's new scale
+    assert r["stats"] == (len(r["points_before"]), 0, 0)
+    L = W.K_FRAMES - 1
+    sel = r["points_before"]["pair"] == 1
+    c_old = np.linalg.inv(SW.walk()["drifted"][L - 1])[:3, 3]
+    d_old = np.linalg.norm(r["points_before"]["X"][sel] - c_old, axis=1)
+    d_new = np.linalg.norm(r["points_after"]["X"][sel] - r["centres"][L - 1], axis=1)
+    assert sel.any() and np.abs(d_new / d_old - r["scales"][L - 1]).max() < 1e-12
+    assert np.abs(r["points_after"]["X"][~sel] - r["points_before"]["X"][~sel]).max() < 1e-14
+
+
+# ---- correct_points -------------------------------------------------------------------------------------------------------------------
+def _points(n, pairs, seed=0):
+    from aria_slam_amd._lib import MAP_POINT_DTYPE
+    rng = np.random.default_rng(seed)
+    p = np.zeros(n, MAP_POINT_DTYPE)
+    p["id"] = np.arange(n)
+    p["X"] = rng.normal(size=(n, 3)) * 5
+    p["quality"], p["err"] = rng.uniform(size=n), rng.uniform(size=(n, 2))
+    p["pair"] = np.resize(np.asarray(pairs, np.int32), n)
+    p["match"], p["idx1"], p["idx2"] = rng.integers(0, 100, (3, n))
+    p["gray"], p["pad"] = rng.integers(0, 255, n), rng.integers(0, 255, (n, 7))
+    return p
+
+
+def test_correct_points_identity_similarity_and_counts():
+    from aria_slam_amd import graph_ref as G
+    from aria_slam_amd import sgraph_ref as S
+    rng = np.random.default_rng(3)
+    pts = _points(50, [0, 1, 2])
+    # old == new, s_old = 1, identity R, t = 0: every X bit for bit. With t != 0 the fixed operation order computes
+    # (X - t) + t, which rounds twice: X comes back to one ulp of the largest of |X|, |t| and |X - t|, not bit for bit.
+    V = np.array([S.make_vertex(np.eye(3), np.zeros(3), 1.0) for _ in range(3)])
+    out, stats = S.correct_points(pts, [0, 1, 2], 0, V, V)
+    assert out.tobytes() == pts.tobytes() and stats == (50, 0, 0)
+    V = np.array([S.make_vertex(np.eye(3), rng.normal(size=3), 1.0) for _ in range(3)])
+    out, stats = S.correct_points(pts, [0, 1, 2], 0, V, V)
+    t = V[pts["pair"], 9:12]
+    ulp = np.spacing(np.maximum(np.maximum(np.abs(pts["X"]), np.abs(t)), np.abs(pts["X"] - t)))
+    assert (np.abs(out["X"] - pts["X"]) <= ulp).all() and stats == (50, 0, 0)
+    # a known similarity: X' = S_new S_old^-1 X in closed form
+    old = np.array([S.vertex_from_pose(G.random_pose(rng, 2.0), rng.uniform(0.5, 2)) for _ in range(3)])
+    new = np.array([S.vertex_from_pose(G.random_pose(rng, 2.0), rng.uniform(0.5, 2)) for _ in range(3)])
+    out, stats = S.correct_points(pts, [2, 0, 1], 0, old, new)
+    assert stats == (50, 0, 0)
+    for k in range(50):
+        v = [2, 0, 1][pts["pair"][k]]
+        T = S.mul(new[v], S.inv(old[v]))
+        want = T[12] * (T[:9].reshape(3, 3) @ pts["X"][k]) + T[9:12]
+        assert np.abs(out["X"][k] - want).max() < 1e-12
+    other = [n for n in pts.dtype.names if n != "X"]
+    assert all(np.array_equal(out[n], pts[n]) for n in other)
+    # a point at the old camera's coordinates x_c lands at s_new x_c in the new camera: the local structure is rescaled
+    xc = np.array([0.3, -0.2, 4.0])
+    one = _points(1, [0])
+    one["X"][0] = old[0][12] * (old[0][:9].reshape(3, 3) @ xc) + old[0][9:12]
+    got, _s = S.correct_points(one, [0], 0, old, new)
+    assert np.abs(got["X"][0] - (new[0][12] * (new[0][:9].reshape(3, 3) @ xc) + new[0][9:12])).max() < 1e-12
+    # table misses and -1 entries are counted and left alone; pair_base shifts the table
+    pts = _points(60, [3, 4, 5, 6, 7, 9])
+    out, stats = S.correct_points(pts, [0, -1, 1, 2], 4, old, new)      # pairs 4..7 in the table, 5 -> -1; 3 below, 9 beyond
+    assert stats == (30, 30, 0)
+    keep = np.isin(pts["pair"], [3, 5, 9])
+    assert out[keep].tobytes() == pts[keep].tobytes() and not np.array_equal(out["X"][~keep], pts["X"][~keep])
+    # refused: a vertex with s <= 0 or not finite, a vertex index beyond the vertices, an X that is not finite
+    bad = new.copy()
+    bad[1, 12] = 0.0
+    pts = _points(40, [0, 1, 2, 3])
+    pts["X"][0, 1] = np.inf                                              # pair 0, else fine
+    out, stats = S.correct_points(pts, [0, 1, 2, 7], 0, old, bad)       # pair 3 -> vertex 7: beyond
+    assert stats == (19, 0, 21)
+    still = np.isin(pts["pair"], [1, 3])
+    still[0] = True
+    assert out[still].tobytes() == pts[still].tobytes()
+    assert S.correct_points(pts[:0], [0], 0, old, new)[1] == (0, 0, 0)
+
+
+def test_bookkeeping_carries_the_scale():
+    from aria_slam_amd import graph_ref as G
+    from aria_slam_amd import sgraph_ref as S
+    rng = np.random.default_rng(5)
+    g = S.Sim3GraphOptimizer()
+    T = {k: G.random_pose(rng) for k in (7, 3, 5)}
+    for k in (7, 3, 5):
+        g.set_initial_pose(k, T[k])
+    assert g.add_odometry_edge(7, 3, G.inv(T[7]) @ T[3]) and g.add_loop_edge(3, 5, G.inv(T[3]) @ T[5], 0.8, 2.0)
+    assert not g.add_loop_edge(4, 7, np.eye(4), 0.5)
+    assert [e[2] for e in g.edges] == [1.0, 20.0] and [e[4] for e in g.edges] == [1.0, 0.8]
+    assert g.get_optimized_scale(5) == 1.0 and g.get_optimized_scale(99) == 1.0
+    g.optimize(5)
+    assert g.get_optimized_pose(7).tobytes() == T[7].tobytes() and g.get_optimized_scale(7) == 1.0
+    assert abs(g.get_optimized_scale(5) - 0.8) < 1e-6 and g.last_result["chi2_final"] < 1e-10      # s_5 = s_3 * 0.8 on a tree
+    g.clear()
+    assert g.scales == [] and g.edges == []
+
+
+# ---- the kernels' compile ------------------------------------------------------------------------------------------------------------
+def test_sgraph_kernels_cross_compile_without_scratch():
+    import isa_kernel_stats as K
+    csrc = os.path.join(ROOT, "aria_slam_amd", "csrc")
+    out = os.path.join(ROOT, "build", "isa")
+    os.makedirs(out, exist_ok=True)
+    path = os.path.join(out, "sim3_graph.s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                           "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + csrc, "--cuda-device-only", "-S", "-w", "-o", path, os.path.join(csrc, "sim3_graph.hip")])
+    text = open(path).read()
+    for kernel in ("k_sgraph_lm", "k_sgraph_correct", "k_sgraph_from_pose", "k_sgraph_to_pose"):
+        body, meta = K.kernel_body(text, kernel)
+        assert body and meta.get("ScratchSize", -1) == 0, (kernel, meta)
+    _body, meta = K.kernel_body(text, "k_sgraph_lm")
+    assert meta.get("LDSByteSize", 1 << 20) <= 64 * 1024
+    # fresh() keeps the scratch strides from being hoisted: without it this kernel held 1756 scalar spills and 20 bytes of
+    # scratch. 17 scalar spills (to vector lanes) and no vector spill were measured with it; a toolchain that undoes it shows here
+    # before it shows as scratch.
+    block = re.search(r"\.name:\s+\S*k_sgraph_lm\S*\n(.*?)\.wavefront_size", text, re.S).group(1)
+    sgpr_spills = int(re.search(r"\.sgpr_spill_count:\s*(\d+)", block).group(1))
+    vgpr_spills = int(re.search(r"\.vgpr_spill_count:\s*(\d+)", block).group(1))
+    print("k_sgraph_lm: %d scalar spills, %d vector spills" % (sgpr_spills, vgpr_spills))
+    assert vgpr_spills == 0 and sgpr_spills <= 64
+    _body, meta = K.kernel_body(text, "k_sgraph_correct")
+    assert meta.get("LDSByteSize", -1) == 0
+
+
+def test_sim3_graph_is_in_the_product_build_and_has_no_float_atomics():
+    mk = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "Makefile")).read()
+    src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
+    assert "sim3_graph.hip" in src_line and "graph_optimize.hip" in src_line
+    src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "sim3_graph.hip")).read()
+    assert "getenv" not in src
+    atomics = re.findall(r"atomic\w+\(&?\s*([\w.\[\]>-]+)", src)
+    assert atomics and all(a.startswith(("S.aoff", "S.cur", "err", "stats")) for a in atomics), atomics      # integers only
+    assert "cooperative" not in src and "grid.sync" not in src and "hipLaunchCooperativeKernel" not in src

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""LIN_GAPS, GAPS, MIN_RHO and FIX_SCALE_GAP of tests/sgraph_cases.py (CPU only; the method and the format of tools/graph_gap.py).
+  LIN_GAPS  for every graph of LIN_GRAPHS: sgraph_ref.linearize in fp64 against the same formulas in numpy.longdouble (written
+            out below, because graph_ref's quaternion helpers return fp64): chi2 relative, b, H_diag and H_off each as
+            max |difference| / max |entry|. tests/test_gpu_sgraph.py allows the device's debug_linearize ten times each.
+  GAPS      for every case and every iteration count k up to the case's: the largest absolute difference of any vertex entry and
+            the relative differences of lambda and chi2_final between sgraph_ref.optimize(solver="direct") and (solver="pcg");
+            the device is allowed ten times each against the direct solve.
+  MIN_RHO   the smallest |rho| of any trial and the smallest ratio |rho| / |rho_direct - rho_pcg|.
+  FIX_SCALE_GAP  sgraph_ref.optimize(fix_scale) against graph_ref.optimize on one SE(3) graph, both with pcg.
+Usage: tools/sgraph_gap.py"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import sgraph_cases as SC   # noqa: E402
+
+LD = np.longdouble
+
+
+def _quat_ld(R):
+    """graph_ref.quat_from_rot in long double."""
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    one = LD(1)
+    if tr > 0:
+        s = np.sqrt(tr + one) * 2
+        q = [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, s / 4]
+    elif R[0, 0] >= R[1, 1] and R[0, 0] >= R[2, 2]:
+        s = np.sqrt(one + R[0, 0] - R[1, 1] - R[2, 2]) * 2
+        q = [s / 4, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s, (R[2, 1] - R[1, 2]) / s]
+    elif R[1, 1] >= R[2, 2]:
+        s = np.sqrt(one + R[1, 1] - R[0, 0] - R[2, 2]) * 2
+        q = [(R[0, 1] + R[1, 0]) / s, s / 4, (R[1, 2] + R[2, 1]) / s, (R[0, 2] - R[2, 0]) / s]
+    else:
+        s = np.sqrt(one + R[2, 2] - R[0, 0] - R[1, 1]) * 2
+        q = [(R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, s / 4, (R[1, 0] - R[0, 1]) / s]
+    q = np.array(q, LD)
+    q = q / np.sqrt(q @ q)
+    return -q if q[3] < 0 else q
+
+
+def _skew_ld(v):
+    z = LD(0)
+    return np.array([[z, -v[2], v[1]], [v[2], z, -v[0]], [-v[1], v[0], z]], LD)
+
+
+def linearize_ld(vertices, edges):
+    """sgraph_ref.linearize (fix_scale off) with every operand and every operation in long double."""
+    V, E = len(vertices), len(edges)
+    b, D, W = np.zeros((V, 7), LD), np.zeros((V, 7, 7), LD), np.zeros((E, 7, 7), LD)
+    chi2 = LD(0)
+    S = np.asarray(vertices, np.float64).astype(LD)
+    for k, (i, j, w, Z, sz) in enumerate(edges):
+        Ri, ti, si = S[i, :9].reshape(3, 3), S[i, 9:12], S[i, 12]
+        Rj, tj, sj = S[j, :9].reshape(3, 3), S[j, 9:12], S[j, 12]
+        Z, sz, w = np.asarray(Z, np.float64).astype(LD), LD(sz), LD(w)
+        Rz, tz = Z[:3, :3], Z[:3, 3]
+        Rm, tm, sm = Ri.T @ Rj, (Ri.T @ (tj - ti)) / si, sj / si
+        Re, te, se = Rz.T @ Rm, (Rz.T @ (tm - tz)) / sz, sm / sz
+        q = _quat_ld(Re)
+        v, qw = q[:3], q[3]
+        Ji, Jj = np.zeros((7, 7), LD), np.zeros((7, 7), LD)
+        c = (se + 1 / se) / 2
+        Ji[:3, :3] = -Rz.T / sz
+        Ji[:3, 3:6] = (2 * Rz.T @ _skew_ld(tm)) / sz
+        Ji[:3, 6] = -(Rz.T @ tm) / sz
+        Ji[3:6, 3:6] = -(qw * np.eye(3, dtype=LD) - _skew_ld(v)) @ Rz.T
+        Ji[6, 6], Jj[6, 6] = -c, c
+        Jj[:3, :3] = se * Re
+        Jj[3:6, 3:6] = qw * np.eye(3, dtype=LD) + _skew_ld(v)
+        e = np.concatenate([te, v, [(se - 1 / se) / 2]])
+        chi2 += w * (e @ e)
+        D[i] += w * Ji.T @ Ji
+        D[j] += w * Jj.T @ Jj
+        W[k] = w * Ji.T @ Jj
+        b[i] -= w * Ji.T @ e
+        b[j] -= w * Jj.T @ e
+    return chi2, b, D, W
+
+
+def lin_gap(name):
+    from aria_slam_amd import sgraph_ref as S
+    V, E, _fixed = SC.lin_graph(name)
+    E = S.norm_edges(E)
+    c, b, D, W = S.linearize(V, E)
+    cl, bl, Dl, Wl = linearize_ld(V, E)
+    rel = lambda a, x: float(np.abs(a.astype(LD) - x).max() / np.abs(x).max())      # noqa: E731
+    return float(abs(LD(c) - cl) / abs(cl)), rel(b, bl), rel(D, Dl), rel(W, Wl)
+
+
+def fix_scale_gap():
+    from aria_slam_amd import graph_ref as G
+    from aria_slam_amd import sgraph_ref as S
+    poses, edges, V, E = SC.se3_graph()
+    P, _r = G.optimize(poses, edges, 0, SC.SE3_ITERATIONS, "pcg")
+    Vo, _rs = S.optimize(V, E, 0, SC.SE3_ITERATIONS, "pcg", fix_scale=True)
+    return float(np.abs(S.poses_of(Vo) - P).max())
+
+
+def main():
+    if np.finfo(LD).eps >= np.finfo(np.float64).eps:
+        sys.exit("numpy.longdouble is no wider than fp64 on this machine: LIN_GAPS cannot be measured here")
+    print("LIN_GAPS = {    # graph: (chi2, b, H_diag, H_off), fp64 against long double")
+    for name, args, _fixed in SC.LIN_GRAPHS:
+        V, E, _f = SC.lin_graph(name)
+        print('    "%s": (%.2e, %.2e, %.2e, %.2e),    # %d vertices, %d edges' % ((name,) + lin_gap(name) + (len(V), len(E))), flush=True)
+    print("}")
+    rhos = {}
+    print("GAPS = {    # case: per k = 1.., (vertex, lambda, chi2_final)")
+    for c in SC.CASES:
+        _Vd, rd = SC.reference(c.name, c.iterations, "direct")
+        _Vp, rp = SC.reference(c.name, c.iterations, "pcg")
+        d, p = np.array([t["rho"] for t in rd["trace"]]), np.array([t["rho"] for t in rp["trace"]])
+        rhos[c.name] = (min(np.abs(d).min(), np.abs(p).min()),
+                        (np.minimum(np.abs(d), np.abs(p)) / np.maximum(np.abs(d - p), 1e-300)).min())
+        print("    # %s direct %s pcg %s" % (c.name, SC.pattern(rd), SC.pattern(rp)))
+        print("    #   accepted rho %s" % " ".join("%.3f" % t["rho"] for t in rp["trace"] if t["accepted"]))
+        rows = ["(%.2e, %.2e, %.2e)" % SC.gap(c.name, k) for k in range(1, c.iterations + 1)]
+        lines = [", ".join(rows[k:k + 3]) for k in range(0, len(rows), 3)]
+        pad = " " * (9 + len(c.name))
+        print('    "%s": [%s],' % (c.name, (",\n" + pad).join(lines)), flush=True)
+    print("}")
+    print("MIN_RHO = {    # case: smallest |rho| of any trial    (smallest |rho| / |rho_direct - rho_pcg|)")
+    for name, (lo, margin) in rhos.items():
+        print('    "%s": %.3f,    # %.3g' % (name, lo, margin))
+    print("}")
+    print("FIX_SCALE_GAP = %.2e    # largest pose entry difference, sgraph_ref fix_scale against graph_ref" % fix_scale_gap())
+
+
+if __name__ == "__main__":
+    main()
