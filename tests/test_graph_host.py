@@ -364,7 +364,8 @@ def test_graph_optimize_is_in_the_product_build_and_has_no_float_atomics():
     assert "graph_optimize.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "graph_optimize.hip")).read()
     # the rules below follow the code into the shared headers this file includes
-    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h", "solver_device.h") if '#include "%s"' % h in src)
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "ransac_device.h", "solver_device.h", "graph_lm_device.h") if '#include "%s"' % h in src)
+    assert '#include "graph_lm_device.h"' in src      # the adjacency build and the solver live there
     assert "getenv" not in src
     # the only atomics are the integer ones of the adjacency build (counts and fill cursors) and the error word
     atomics = re.findall(r"atomic\w+\(&?\s*([\w.\[\]>-]+)", src)

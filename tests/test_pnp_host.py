@@ -261,8 +261,9 @@ def _definitions(code):
 
 
 def test_shared_device_helpers_have_one_definition():
-    """Every helper of solver_device.h, and the packed-int16 helpers of orb_device.h, is defined once among csrc/*.hip and
-    csrc/*.h, in its shared header, and every .hip that uses it includes that header: no second copy to drift from the first."""
+    """Every helper of solver_device.h and of graph_lm_device.h, and the packed-int16 helpers of orb_device.h, is defined once
+    among csrc/*.hip and csrc/*.h, in its shared header, and every .hip that uses it includes that header: no second copy to
+    drift from the first."""
     csrc = os.path.join(ROOT, "aria_slam_amd", "csrc")
     strip = lambda t: re.sub(r"//[^\n]*", "", t)   # noqa: E731
     code = {f: strip(open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
@@ -273,6 +274,22 @@ def test_shared_device_helpers_have_one_definition():
                            "LmDamping", "LM_MAX_TRIALS", "STOP_ITERATIONS", "STOP_TRIALS", "STOP_INVALID"}, solver
     shared = [(n, "solver_device.h") for n in solver]
     shared += [(n, "orb_device.h") for n in ("short2v", "pk_min_i16", "pk_max_i16", "pk_sub_i16", "pk_add_i16")]
+    # the same for graph_lm_device.h: the pieces k_graph_lm and k_sgraph_lm share (GraphScratch's members belong to it), and
+    # the host templates around the kernels, which carry no __host__ for _definitions to see
+    # (its signatures run over two lines, so the indented lines stay and the indented definitions are masked)
+    file_scope = re.sub(r"(?m)^[ \t]+(?=__device__|__host__|struct\b|constexpr\b|typedef\b)", "    masked ", code["graph_lm_device.h"])
+    graph_lm = sorted({n for n, _ in _definitions(file_scope)})
+    assert set(graph_lm) >= {"GraphScratch", "LmRed", "lm_stride", "sym_idx", "unit_quat_from_rot", "rot_from_quat", "load_pose",
+                             "mul_tn", "mul_nn", "mulv_t", "rotation_update", "edge_pass", "build_adjacency", "vertex_gather",
+                             "precond_build", "precond_apply", "pcg_solve"}, graph_lm
+    shared += [(n, "graph_lm_device.h") for n in graph_lm]
+    host = {f: re.findall(r"^(?:int|void)\s+(graph_lm_\w+)\(", text, re.M) for f, text in code.items()}
+    assert sorted(host.pop("graph_lm_device.h")) == ["graph_lm_debug_linearize", "graph_lm_launch", "graph_lm_optimize",
+                                                     "graph_lm_optimize_batch_device", "graph_lm_reserve",
+                                                     "graph_lm_stage_single"] and not any(host.values()), host
+    for f in ("graph_optimize.hip", "sim3_graph.hip"):            # both stages go through every one of them
+        for n in ("graph_lm_reserve", "graph_lm_optimize", "graph_lm_optimize_batch_device", "graph_lm_debug_linearize"):
+            assert n + "<" in code[f], (f, n)
     for name, header in shared:
         where = [f for f, text in code.items() for n, params in _definitions(text)
                  if n == name and (name, f, params) not in OTHER_FORMS]

@@ -386,7 +386,7 @@ def test_sgraph_kernels_cross_compile_without_scratch():
         assert body and meta.get("ScratchSize", -1) == 0, (kernel, meta)
     _body, meta = K.kernel_body(text, "k_sgraph_lm")
     assert meta.get("LDSByteSize", 1 << 20) <= 64 * 1024
-    # fresh() keeps the scratch strides from being hoisted: without it this kernel held 1756 scalar spills and 20 bytes of
+    # lm_stride<true> (graph_lm_device.h; once fresh()) keeps the scratch strides from being hoisted: without it this kernel held 1756 scalar spills and 20 bytes of
     # scratch. 17 scalar spills (to vector lanes) and no vector spill were measured with it; a toolchain that undoes it shows here
     # before it shows as scratch.
     block = re.search(r"\.name:\s+\S*k_sgraph_lm\S*\n(.*?)\.wavefront_size", text, re.S).group(1)
@@ -403,6 +403,9 @@ def test_sim3_graph_is_in_the_product_build_and_has_no_float_atomics():
     src_line = [ln for ln in mk.splitlines() if ln.startswith("SRC :=")][0]
     assert "sim3_graph.hip" in src_line and "graph_optimize.hip" in src_line
     src = open(os.path.join(ROOT, "aria_slam_amd", "csrc", "sim3_graph.hip")).read()
+    # the rules below follow the code into the shared headers this file includes
+    src += "".join(open(os.path.join(ROOT, "aria_slam_amd", "csrc", h)).read() for h in ("stage_handle.h", "solver_device.h", "graph_lm_device.h") if '#include "%s"' % h in src)
+    assert '#include "graph_lm_device.h"' in src      # the adjacency build and the solver live there
     assert "getenv" not in src
     atomics = re.findall(r"atomic\w+\(&?\s*([\w.\[\]>-]+)", src)
     assert atomics and all(a.startswith(("S.aoff", "S.cur", "err", "stats")) for a in atomics), atomics      # integers only
