@@ -21,6 +21,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <functional>
+#include <memory>
 #include <vector>
 
 #include "aria_hip/AslSequence.hpp"
@@ -72,7 +73,7 @@ public:
 
 private:
     struct Impl;
-    Impl* p_;
+    std::unique_ptr<Impl> p_;
     BatchFrontEndConfig cfg_;
     BatchStats stats_;
     int w_ = 0, h_ = 0;

@@ -9,6 +9,7 @@
 
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -36,8 +37,6 @@ public:
     explicit HipBundleAdjuster(const PoseIntrinsics& K = {}, double huber_px = -1.0, double min_depth = 1e-6, int max_iterations = 10,
                                int max_windows = 256, void* stream = nullptr, int device = 0);   // huber_px < 0: the default
     ~HipBundleAdjuster();
-    HipBundleAdjuster(const HipBundleAdjuster&) = delete;
-    HipBundleAdjuster& operator=(const HipBundleAdjuster&) = delete;
 
     // One window, updated in place; blocks. iterations = 0: the handle's. Throws on an invalid window.
     BundleResult optimize(BundleWindow& window, int iterations = 0);
@@ -47,11 +46,11 @@ public:
                              int pose_cap, int point_cap, int obs_cap, int iterations, aria_ba_result* d_out,
                              std::uint8_t* d_used = nullptr);
     void check();
-    aria_ba_t handle() const { return h_; }
+    aria_ba_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_ba_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipBundleAdjuster", where, rc); }
+    detail::StageOwner<aria_ba_t, aria_ba_destroy> h_;
 };
 
 // The tracks of a sequence, kept on the host as MapTracker goes: a point the mapper triangulated from frames (f, f + 1) is

@@ -9,6 +9,7 @@
 
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -37,20 +38,18 @@ class HipDenseStereo {
 public:
     explicit HipDenseStereo(const DenseStereoConfig& cfg = {});
     ~HipDenseStereo();
-    HipDenseStereo(const HipDenseStereo&) = delete;
-    HipDenseStereo& operator=(const HipDenseStereo&) = delete;
 
     // One rectified pair: the two gray images, width x height bytes, tightly packed.
     DenseDepth compute(const std::uint8_t* image_left, const std::uint8_t* image_right, int width, int height);
     // The stereo observations of `keypoints` on a map of compute(): unmatched where the rounded keypoint is outside the image
     // or on a pixel without a positive disparity.
     std::vector<aria_stereo_obs> sample(const DenseDepth& map, const std::vector<core::KeyPoint>& keypoints);
-    int pairsInFlight() const { return aria_dense_pairs_in_flight(h_); }
-    aria_dense_t handle() const { return h_; }
+    int pairsInFlight() const { return aria_dense_pairs_in_flight(h_.get()); }
+    aria_dense_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_dense_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipDenseStereo", where, rc); }
+    detail::StageOwner<aria_dense_t, aria_dense_destroy> h_;
 };
 
 }  // namespace aria::adapters::hip

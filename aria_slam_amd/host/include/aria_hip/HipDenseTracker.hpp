@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "aria_hip/HipVolumeRenderer.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -36,8 +37,6 @@ class HipDenseTracker {
 public:
     explicit HipDenseTracker(const DenseTrackerConfig& cfg = {});
     ~HipDenseTracker();
-    HipDenseTracker(const HipDenseTracker&) = delete;
-    HipDenseTracker& operator=(const HipDenseTracker&) = delete;
 
     // One frame from dense host buffers (aria_icp_track); blocks. The model view is what a renderer of these intrinsics cast at
     // model_extrinsics; guess = nullptr starts at the model's pose. A non-finite pose throws.
@@ -50,14 +49,15 @@ public:
                           int n_frames, int width, int height, double* d_extrinsics_out, aria_icp_result* d_results);
     // A renderer that casts with other intrinsics than this tracker's is refused, as a volume of another geometry is elsewhere.
     void requireSameIntrinsics(const HipVolumeRenderer& renderer) const;
-    int check() { return aria_icp_check(h_); }
+    int check() { return aria_icp_check(h_.get()); }
     const aria_icp_config& config() const { return cfg_; }
-    aria_icp_t handle() const { return h_; }
+    aria_icp_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipDenseTracker", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipDenseTracker", where, rc); }
     aria_icp_config cfg_{};
-    aria_icp_t h_ = nullptr;
+    detail::StageOwner<aria_icp_t, aria_icp_destroy> h_;
 };
 
 }  // namespace aria::adapters::hip

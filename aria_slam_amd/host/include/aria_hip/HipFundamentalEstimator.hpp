@@ -17,6 +17,7 @@
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -40,12 +41,8 @@ public:
         c.hypotheses = hypotheses;
         c.threshold_px = threshold_px;
         c.seed = seed;
-        const int rc = aria_fund_create(&c, &h_);
-        if (rc != ARIA_OK) fail("aria_fund_create", rc);
+        expect("aria_fund_create", aria_fund_create(&c, h_.out()));
     }
-    ~HipFundamentalEstimator() { aria_fund_destroy(h_); }
-    HipFundamentalEstimator(const HipFundamentalEstimator&) = delete;
-    HipFundamentalEstimator& operator=(const HipFundamentalEstimator&) = delete;
 
     // view 1 = `first`, view 2 = `second`; query_is_first as in HipPoseEstimator::estimate. std::nullopt when the stage
     // finds no F (fewer than 15 matches, no model with 7 inliers).
@@ -58,11 +55,11 @@ public:
         aria_fund_result r{};
         FundamentalResult out;
         out.mask.assign(matches.size(), 0);
-        const int rc = aria_fund_estimate(h_, reinterpret_cast<const aria_keypoint*>(q.keypoints.data()), (int)q.keypoints.size(),
-                                          reinterpret_cast<const aria_keypoint*>(t.keypoints.data()), (int)t.keypoints.size(),
-                                          reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(),
-                                          query_is_first ? 1 : 0, pair_id, &r, out.mask.data());
-        if (rc != ARIA_OK) fail("aria_fund_estimate", rc);
+        expect("aria_fund_estimate",
+               aria_fund_estimate(h_.get(), reinterpret_cast<const aria_keypoint*>(q.keypoints.data()), (int)q.keypoints.size(),
+                                  reinterpret_cast<const aria_keypoint*>(t.keypoints.data()), (int)t.keypoints.size(),
+                                  reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(),
+                                  query_is_first ? 1 : 0, pair_id, &r, out.mask.data()));
         if (!r.valid) return std::nullopt;
         for (int k = 0; k < 9; k++) out.F[(size_t)k] = r.F[k];
         out.n_matches = r.n_matches;
@@ -70,16 +67,11 @@ public:
         out.n_models = r.n_models;
         return out;
     }
-    aria_fund_t handle() const { return h_; }
+    aria_fund_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status) {
-        std::string msg = std::string("HipFundamentalEstimator: ") + where + ": " + aria_status_string(status);
-        const char* hip = aria_last_hip_error();
-        if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-        throw std::runtime_error(msg);
-    }
-    aria_fund_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipFundamentalEstimator", where, rc); }
+    detail::StageOwner<aria_fund_t, aria_fund_destroy> h_;
 };
 
 // computeRelativePose's hard-coded camera (LoopClosure.cpp:171-174): build the HipPoseEstimator of makeReferenceVerifier

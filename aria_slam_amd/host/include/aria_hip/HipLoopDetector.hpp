@@ -23,6 +23,7 @@
 
 #include "aria_hip/HipMatcher.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 
 struct aria_kfdb_s;
 
@@ -37,8 +38,6 @@ public:
     explicit HipLoopDetector(int min_frames_between = 30, double min_score = 0.3, int min_matches = 30, int slot_rows = 4096,
                              int capacity = 500, void* stream = nullptr, int device = 0);
     ~HipLoopDetector() override;
-    HipLoopDetector(const HipLoopDetector&) = delete;
-    HipLoopDetector& operator=(const HipLoopDetector&) = delete;
 
     void addKeyFrame(const core::KeyFrame& kf) override;                                  // LoopClosure.cpp:24-31
     std::optional<core::LoopCandidate> detect(const core::KeyFrame& query) override;      // :33-70
@@ -70,7 +69,6 @@ public:
     long long placeCandidates() const { return place_candidates_; }
 
 private:
-    aria_kfdb_s* db_ = nullptr;
     HipMatcher matcher_;
     int min_frames_between_;
     double min_score_;
@@ -83,6 +81,7 @@ private:
     std::shared_ptr<HipPlaceIndex> place_;
     int place_top_k_ = 10;
     long long place_queries_ = 0, place_candidates_ = 0;
+    detail::StageOwner<aria_kfdb_t, aria_kfdb_destroy> db_;     // the last member: destroyed first, before matcher_, as ever
 };
 
 }  // namespace aria::adapters::hip

@@ -13,6 +13,7 @@
 
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -35,8 +36,6 @@ class HipMapper : public interfaces::IMapper {
 public:
     explicit HipMapper(const MapperConfig& cfg = {});
     ~HipMapper() override;
-    HipMapper(const HipMapper&) = delete;
-    HipMapper& operator=(const HipMapper&) = delete;
 
     // IMapper
     void triangulate(const core::Frame& frame1, const core::Frame& frame2, const core::Pose& pose1, const core::Pose& pose2,
@@ -55,11 +54,11 @@ public:
     void filterOutliers();                                // Mapper::filterOutliers
     void filterByDistance(double max_distance = 100.0);   // Mapper::filterByDistance
     std::vector<aria_map_point> records() const;          // the device records, in map order
-    aria_map_t handle() const { return h_; }
+    aria_map_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_map_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipMapper", where, rc); }
+    detail::StageOwner<aria_map_t, aria_map_destroy> h_;
     MapperConfig cfg_;
     int next_pair_ = 0;
     std::vector<core::MapPoint> made_;                    // every point made since clear(), indexed by id

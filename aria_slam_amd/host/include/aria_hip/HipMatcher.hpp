@@ -5,6 +5,7 @@
 #include <utility>
 
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 
 struct aria_matcher_s;
 
@@ -14,8 +15,6 @@ class HipMatcher : public interfaces::IMatcher {
 public:
     explicit HipMatcher(void* stream = nullptr, int device = 0);   // CudaMatcher.cpp:7-19
     ~HipMatcher() override;
-    HipMatcher(const HipMatcher&) = delete;
-    HipMatcher& operator=(const HipMatcher&) = delete;
 
     // Appends to `matches`, never clears (CudaMatcher.cpp:65); empty input leaves it untouched (:35-37).
     // ratio_threshold 0 = test disabled, as IMatcher.hpp:18 documents (see INTEGRATION.md for the divergence
@@ -50,16 +49,16 @@ public:
     bool matchDeviceAsync(const std::uint8_t* d_new, const int* d_count, int rows_max, bool new_is_query, float ratio_threshold = 0.75f);
     void finishDevice(int n_new, std::vector<core::Match>& matches);
 
-    aria_matcher_s* handle() const { return m_; }
+    aria_matcher_s* handle() const { return m_.get(); }
     void* streamArg() const { return stream_; }
     int device() const { return device_; }
     void reserve(int nq, int nt) { ensure(nq, nt); }       // creates / grows the C handle
     // rows per set the handle accepts as it is; growing it (reserve, or a larger call) drops the resident set
-    bool fits(int nq, int nt) const { return m_ && nq <= cap_q_ && nt <= cap_t_; }
+    bool fits(int nq, int nt) const { return m_.get() && nq <= cap_q_ && nt <= cap_t_; }
 
 private:
     void ensure(int nq, int nt);
-    aria_matcher_s* m_ = nullptr;
+    detail::StageOwner<aria_matcher_t, aria_matcher_destroy> m_;
     void* stream_;
     int device_;
     int cap_q_ = 0, cap_t_ = 0;

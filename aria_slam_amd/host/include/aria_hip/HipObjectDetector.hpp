@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -40,8 +41,6 @@ public:
 
     explicit HipObjectDetector(InferenceHook hook, const ObjectDetectorConfig& cfg = {});
     ~HipObjectDetector() override;
-    HipObjectDetector(const HipObjectDetector&) = delete;
-    HipObjectDetector& operator=(const HipObjectDetector&) = delete;
 
     // IObjectDetector: RGB, row-major, 3 channels (IObjectDetector.hpp:15)
     void detect(const std::uint8_t* image_data, int width, int height, std::vector<core::Detection>& detections,
@@ -76,14 +75,14 @@ public:
     const ObjectDetectorConfig& config() const { return cfg_; }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipObjectDetector", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipObjectDetector", where, rc); }
     void enqueue(const std::uint8_t* image_data, int width, int height, int channels);
     void postprocess(int n_frames, int width, int height, float conf, float nms);
     ObjectDetectorConfig cfg_;
     InferenceHook hook_;
-    aria_det_t h_ = nullptr;
-    void* d_img_ = nullptr;
-    std::size_t img_cap_ = 0;
+    detail::DeviceScratch img_;         // the uploaded host image; before h_ (see Stage.hpp, DECLARATION ORDER)
+    detail::StageOwner<aria_det_t, aria_det_destroy> h_;
     void* d_input_ = nullptr;
     float* d_raw_ = nullptr;
     DeviceBoxes lists_;
@@ -102,14 +101,8 @@ interfaces::ObjectDetectorPtr makeObjectDetector(HipObjectDetector::InferenceHoo
 
 static_assert(sizeof(core::Detection) == sizeof(aria_detection), "core::Detection must be the 24-byte aria_detection");
 
-inline void HipObjectDetector::fail(const char* where, int status) {
-    std::string msg = std::string("HipObjectDetector: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
-inline HipObjectDetector::HipObjectDetector(InferenceHook hook, const ObjectDetectorConfig& cfg) : cfg_(cfg), hook_(std::move(hook)) {
+inline HipObjectDetector::HipObjectDetector(InferenceHook hook, const ObjectDetectorConfig& cfg)
+    : cfg_(cfg), hook_(std::move(hook)), img_("HipObjectDetector", cfg.device) {
     if (!hook_) throw std::invalid_argument("HipObjectDetector: an inference hook is required (there is no built-in network)");
     if (cfg_.dynamic_classes.size() > ARIA_DET_MAX_CLASS_IDS) throw std::invalid_argument("HipObjectDetector: more than 32 dynamic classes");
     aria_det_config c;
@@ -121,56 +114,35 @@ inline HipObjectDetector::HipObjectDetector(InferenceHook hook, const ObjectDete
     c.max_batch = cfg_.max_batch;
     c.max_candidates = cfg_.max_candidates;
     c.out_half = cfg_.half ? 1 : 0;
-    int rc = aria_det_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_det_create", rc);
+    expect("aria_det_create", aria_det_create(&c, h_.out()));
     void* in = nullptr;
-    rc = aria_det_device_buffers(h_, &in, &d_raw_, &d_dets_, &d_ndets_, &d_boxes_, &d_nboxes_);
-    if (rc != ARIA_OK) {
-        aria_det_destroy(h_);
-        h_ = nullptr;
-        fail("aria_det_device_buffers", rc);
-    }
+    expect("aria_det_device_buffers", aria_det_device_buffers(h_.get(), &in, &d_raw_, &d_dets_, &d_ndets_, &d_boxes_, &d_nboxes_));
     d_input_ = in;
 }
 
-inline HipObjectDetector::~HipObjectDetector() {
-    if (h_) (void)aria_stream_synchronize(cfg_.device, aria_det_stream(h_));
-    if (d_img_) (void)aria_device_free(cfg_.device, d_img_);
-    aria_det_destroy(h_);
-}
+inline HipObjectDetector::~HipObjectDetector() = default;
 
-inline void* HipObjectDetector::stream() const { return aria_det_stream(h_); }
+inline void* HipObjectDetector::stream() const { return aria_det_stream(h_.get()); }
 
 inline int HipObjectDetector::check() {
-    const int rc = aria_det_check(h_, nullptr, nullptr);
+    const int rc = aria_det_check(h_.get(), nullptr, nullptr);
     if (rc != ARIA_OK && rc != ARIA_E_OUTPUT_TOO_SMALL) fail("aria_det_check", rc);
     return rc;
 }
 
 inline void HipObjectDetector::sync() {
-    const int rc = aria_stream_synchronize(cfg_.device, stream());
-    if (rc != ARIA_OK) fail("aria_stream_synchronize", rc);
+    expect("aria_stream_synchronize", aria_stream_synchronize(cfg_.device, stream()));
 }
 
 // upload, preprocess and the hook of one host image, all on the handle's stream; nothing is waited for (TRTInference.cpp:171-192)
 inline void HipObjectDetector::enqueue(const std::uint8_t* image_data, int width, int height, int channels) {
     if (!image_data || width < 1 || height < 1) throw std::invalid_argument("HipObjectDetector: bad image");
     const std::size_t bytes = (std::size_t)width * height * channels;
-    int rc;
-    if (img_cap_ < bytes) {
-        sync();
-        if (d_img_) (void)aria_device_free(cfg_.device, d_img_);
-        d_img_ = nullptr;
-        img_cap_ = 0;
-        rc = aria_device_alloc(cfg_.device, bytes, &d_img_);
-        if (rc != ARIA_OK) fail("aria_device_alloc", rc);
-        img_cap_ = bytes;
-    }
-    rc = aria_copy_h2d_async(cfg_.device, stream(), d_img_, image_data, bytes);
-    if (rc != ARIA_OK) fail("aria_copy_h2d_async", rc);
-    rc = aria_det_preprocess_batch_device(h_, (const std::uint8_t*)d_img_, 1, width, height, width * channels, (std::int64_t)bytes, channels,
-                                          cfg_.swap_rb ? 1 : 0, d_input_);
-    if (rc != ARIA_OK) fail("aria_det_preprocess_batch_device", rc);
+    img_.reserve(stream(), bytes);
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(cfg_.device, stream(), img_.data(), image_data, bytes));
+    expect("aria_det_preprocess_batch_device",
+           aria_det_preprocess_batch_device(h_.get(), (const std::uint8_t*)img_.data(), 1, width, height, width * channels, (std::int64_t)bytes,
+                                            channels, cfg_.swap_rb ? 1 : 0, d_input_));
     hook_(d_input_, d_raw_, 1, stream());
     pending_ = true;
     pending_w_ = width;
@@ -181,9 +153,9 @@ inline void HipObjectDetector::postprocess(int n_frames, int width, int height, 
     const int* ids = cfg_.dynamic_classes.empty() ? nullptr : cfg_.dynamic_classes.data();
     const int n_ids = cfg_.all_classes ? -1 : (int)cfg_.dynamic_classes.size();
     const int cap = cfg_.max_candidates;
-    const int rc = aria_det_postprocess_batch_device(h_, d_raw_, n_frames, cap, width, height, conf, nms, ids, n_ids, d_dets_, d_ndets_, cap,
-                                                     d_boxes_, d_nboxes_, cap);
-    if (rc != ARIA_OK) fail("aria_det_postprocess_batch_device", rc);
+    expect("aria_det_postprocess_batch_device",
+           aria_det_postprocess_batch_device(h_.get(), d_raw_, n_frames, cap, width, height, conf, nms, ids, n_ids, d_dets_, d_ndets_, cap,
+                                             d_boxes_, d_nboxes_, cap));
     lists_.boxes = d_boxes_;
     lists_.n_boxes = d_nboxes_;
     lists_.detections = d_dets_;
@@ -201,13 +173,12 @@ inline void HipObjectDetector::getDetections(std::vector<core::Detection>& detec
     pending_ = false;
     postprocess(1, pending_w_, pending_h_, conf_threshold, nms_threshold);
     int n = 0;
-    int rc = aria_copy_d2h_async(cfg_.device, stream(), &n, d_ndets_, sizeof(int));
-    if (rc != ARIA_OK) fail("aria_copy_d2h_async", rc);
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(cfg_.device, stream(), &n, d_ndets_, sizeof(int)));
     sync();
     if (n <= 0) return;
     detections.resize((std::size_t)n);
-    rc = aria_copy_d2h_async(cfg_.device, stream(), detections.data(), d_dets_, (std::size_t)n * sizeof(aria_detection));
-    if (rc != ARIA_OK) fail("aria_copy_d2h_async", rc);
+    expect("aria_copy_d2h_async",
+           aria_copy_d2h_async(cfg_.device, stream(), detections.data(), d_dets_, (std::size_t)n * sizeof(aria_detection)));
     sync();
 }
 
@@ -225,9 +196,9 @@ inline void HipObjectDetector::detectGray(const std::uint8_t* image_data, int wi
 
 inline void HipObjectDetector::detectBatchDevice(const std::uint8_t* d_images, int n_frames, int width, int height, int row_stride,
                                           std::int64_t frame_stride, int channels, float conf_threshold, float nms_threshold) {
-    const int rc = aria_det_preprocess_batch_device(h_, d_images, n_frames, width, height, row_stride, frame_stride, channels,
-                                                    cfg_.swap_rb ? 1 : 0, d_input_);
-    if (rc != ARIA_OK) fail("aria_det_preprocess_batch_device", rc);
+    expect("aria_det_preprocess_batch_device",
+           aria_det_preprocess_batch_device(h_.get(), d_images, n_frames, width, height, row_stride, frame_stride, channels,
+                                            cfg_.swap_rb ? 1 : 0, d_input_));
     hook_(d_input_, d_raw_, n_frames, stream());
     postprocess(n_frames, width, height, conf_threshold, nms_threshold);
 }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -64,8 +65,6 @@ public:
     explicit HipObstacleAlerter(const ObstacleAlerterConfig& cfg = {}, interfaces::IAudioFeedback* audio = nullptr,
                                 std::vector<std::string> class_names = {});
     ~HipObstacleAlerter();
-    HipObstacleAlerter(const HipObstacleAlerter&) = delete;
-    HipObstacleAlerter& operator=(const HipObstacleAlerter&) = delete;
 
     // One frame: depth is width x height floats, tightly packed; timestamp_ns must not decrease (such a frame is refused with
     // std::invalid_argument before anything runs). A call that throws, for that or for any other reason, leaves the state and
@@ -81,16 +80,17 @@ public:
     void reset();                                // a cleared state: every cooldown forgotten
     const aria_alert_state& state() const { return state_; }
     const aria_alert_config& config() const { return cfg_; }
-    aria_alert_t handle() const { return h_; }
+    aria_alert_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status);     // std::invalid_argument for ARIA_E_INVALID
+    static void expect(const char* where, int rc) { if (rc != ARIA_OK) fail(where, rc); }
     std::vector<aria_alert_event> finish(int rc, int n_events, const aria_alert_state& after, std::int64_t timestamp_ns);
     void play(const aria_alert_event& e);
     void accept(std::int64_t timestamp_ns) const;
     void release();
     aria_alert_config cfg_{};
-    aria_alert_t h_ = nullptr;
+    detail::StageOwner<aria_alert_t, aria_alert_destroy> h_;
     interfaces::IAudioFeedback* audio_ = nullptr;
     std::vector<std::string> names_;
     std::string obstacle_name_;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "aria_hip/HipTsdfVolume.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -41,8 +42,6 @@ class HipPathPlanner {
 public:
     explicit HipPathPlanner(const PathPlannerConfig& cfg = {});
     ~HipPathPlanner();
-    HipPathPlanner(const HipPathPlanner&) = delete;
-    HipPathPlanner& operator=(const HipPathPlanner&) = delete;
 
     int nu() const { return nu_; }
     int nv() const { return nv_; }
@@ -60,18 +59,19 @@ public:
     PlanResult plan(const std::vector<std::array<std::int32_t, 2>>& goals, const std::vector<std::array<std::int32_t, 3>>& queries,
                     int path_cap);
     std::vector<std::int32_t> field(int goal);
-    int check() { return aria_nav_check(h_); }
+    int check() { return aria_nav_check(h_.get()); }
     // world helpers, on the host: floor((x - origin) / voxel) in fp32 on the two plane axes, and back to the voxel centre with
     // the up coordinate at the middle of the band
     std::array<std::int32_t, 2> cellOf(float x, float y, float z) const;
     std::array<float, 3> centreOf(std::int32_t u, std::int32_t v) const;
     const aria_nav_config& config() const { return cfg_; }
-    aria_nav_t handle() const { return h_; }
+    aria_nav_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipPathPlanner", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipPathPlanner", where, rc); }
     aria_nav_config cfg_{};
-    aria_nav_t h_ = nullptr;
+    detail::StageOwner<aria_nav_t, aria_nav_destroy> h_;
     int nu_ = 0, nv_ = 0, axis_u_ = 0, axis_v_ = 2;
 };
 

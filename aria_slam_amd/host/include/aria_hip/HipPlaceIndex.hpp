@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -27,8 +28,6 @@ class HipPlaceIndex {
 public:
     explicit HipPlaceIndex(const PlaceIndexConfig& cfg = {});
     ~HipPlaceIndex();
-    HipPlaceIndex(const HipPlaceIndex&) = delete;
-    HipPlaceIndex& operator=(const HipPlaceIndex&) = delete;
 
     // k-majority training from the descriptors (N x 32 each) of a batch of frames; returns the iterations run. A new
     // vocabulary (train, load) empties the database.
@@ -43,11 +42,11 @@ public:
     int size() const;
     std::uint64_t id(int index) const;
     int topK() const { return top_k_; }
-    aria_bow_t handle() const { return h_; }
+    aria_bow_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_bow_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipPlaceIndex", where, rc); }
+    detail::StageOwner<aria_bow_t, aria_bow_destroy> h_;
     int top_k_ = 10;
 };
 

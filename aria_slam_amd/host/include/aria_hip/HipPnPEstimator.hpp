@@ -10,6 +10,7 @@
 
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -29,13 +30,11 @@ public:
     explicit HipPnPEstimator(const PoseIntrinsics& K = {}, int hypotheses = 1024, double threshold_px = 2.0, int refine_iters = 5,
                              std::uint64_t seed = 0, void* stream = nullptr, int device = 0);
     ~HipPnPEstimator();
-    HipPnPEstimator(const HipPnPEstimator&) = delete;
-    HipPnPEstimator& operator=(const HipPnPEstimator&) = delete;
 
     // The minimal solver of the calls that follow: ARIA_PNP_SOLVER_DLT6 (the default; a planar scene yields no pose) or
     // ARIA_PNP_SOLVER_P3P (four correspondences are enough, planar scenes included). Throws on an unknown value.
     void setSolver(int solver);
-    int solver() const { return aria_pnp_get_solver(h_); }
+    int solver() const { return aria_pnp_get_solver(h_.get()); }
 
     // std::nullopt when the stage finds no pose (fewer correspondences than the solver needs, 6 or 4; no valid hypothesis; with
     // the DLT a planar scene).
@@ -50,14 +49,12 @@ public:
     std::optional<AbsolutePose> estimateAgainstMap(aria_map_t map, int anchor_pair, int anchor_view, const core::Frame& tracked,
                                                    const std::vector<core::Match>& matches, bool anchor_is_query, int pair_id = 0,
                                                    int* n_corr = nullptr, std::vector<int>* match_index = nullptr);
-    aria_pnp_t handle() const { return h_; }
+    aria_pnp_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_pnp_t h_ = nullptr;
-    int device_ = 0;
-    void* d_buf_ = nullptr;             // grow-only staging of estimateAgainstMap
-    std::size_t d_cap_ = 0;
+    static void expect(const char* where, int rc) { detail::expect("HipPnPEstimator", where, rc); }
+    detail::DeviceScratch scratch_;     // staging of estimateAgainstMap; before h_ (see Stage.hpp, DECLARATION ORDER)
+    detail::StageOwner<aria_pnp_t, aria_pnp_destroy> h_;
 };
 
 // 4x4 row-major [R t; 0 1] of a pose

@@ -18,6 +18,7 @@
 
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -50,12 +51,8 @@ public:
         c.threshold_px = threshold_px;
         c.distance_thresh = distance_thresh;
         c.seed = seed;
-        const int rc = aria_pose_create(&c, &h_);
-        if (rc != ARIA_OK) fail("aria_pose_create", rc);
+        expect("aria_pose_create", aria_pose_create(&c, h_.out()));
     }
-    ~HipPoseEstimator() { aria_pose_destroy(h_); }
-    HipPoseEstimator(const HipPoseEstimator&) = delete;
-    HipPoseEstimator& operator=(const HipPoseEstimator&) = delete;
 
     // view 1 = `first`, view 2 = `second`; query_is_first says which side of each match `first` is (true: match.query_idx
     // indexes first.keypoints). std::nullopt when the stage finds no pose (fewer than 8 matches, no valid hypothesis).
@@ -67,11 +64,11 @@ public:
         aria_pose_result r{};
         TwoViewPose out;
         out.mask.assign(matches.size(), 0);
-        const int rc = aria_pose_estimate(h_, reinterpret_cast<const aria_keypoint*>(q.keypoints.data()), (int)q.keypoints.size(),
-                                          reinterpret_cast<const aria_keypoint*>(t.keypoints.data()), (int)t.keypoints.size(),
-                                          reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(),
-                                          query_is_first ? 1 : 0, pair_id, &r, out.mask.data());
-        if (rc != ARIA_OK) fail("aria_pose_estimate", rc);
+        expect("aria_pose_estimate",
+               aria_pose_estimate(h_.get(), reinterpret_cast<const aria_keypoint*>(q.keypoints.data()), (int)q.keypoints.size(),
+                                  reinterpret_cast<const aria_keypoint*>(t.keypoints.data()), (int)t.keypoints.size(),
+                                  reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(),
+                                  query_is_first ? 1 : 0, pair_id, &r, out.mask.data()));
         if (!r.valid) return std::nullopt;
         for (int k = 0; k < 9; k++) { out.R[(size_t)k] = r.R[k]; out.E[(size_t)k] = r.E[k]; }
         for (int k = 0; k < 3; k++) out.t[(size_t)k] = r.t[k];
@@ -81,16 +78,11 @@ public:
         out.refined = r.refined != 0;
         return out;
     }
-    aria_pose_t handle() const { return h_; }
+    aria_pose_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status) {
-        std::string msg = std::string("HipPoseEstimator: ") + where + ": " + aria_status_string(status);
-        const char* hip = aria_last_hip_error();
-        if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-        throw std::runtime_error(msg);
-    }
-    aria_pose_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipPoseEstimator", where, rc); }
+    detail::StageOwner<aria_pose_t, aria_pose_destroy> h_;
 };
 
 // 4x4 row-major [R t; 0 1] of a pose

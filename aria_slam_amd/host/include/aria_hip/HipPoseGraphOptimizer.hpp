@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -57,8 +58,6 @@ class HipPoseGraphOptimizer {
 public:
     explicit HipPoseGraphOptimizer(int pcg_max_iters = 1000, double pcg_rel_tol = 1e-8, void* stream = nullptr, int device = 0);
     ~HipPoseGraphOptimizer();
-    HipPoseGraphOptimizer(const HipPoseGraphOptimizer&) = delete;
-    HipPoseGraphOptimizer& operator=(const HipPoseGraphOptimizer&) = delete;
 
     // the reference class's surface
     void addOdometryEdge(int from_id, int to_id, const GraphPose& relative_pose, double info_scale = 1.0);
@@ -74,9 +73,9 @@ public:
     std::size_t numEdges() const { return edges_.size(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    static void expect(const char* where, int rc) { detail::expect("HipPoseGraphOptimizer", where, rc); }
     void addEdge(int from_id, int to_id, const double rows[12], double info_scale);
-    aria_graph_t h_ = nullptr;
+    detail::StageOwner<aria_graph_t, aria_graph_destroy> h_;
     aria_graph_config cfg_{};
     std::map<int, int> index_;               // id -> vertex index, in order of first setInitialPose
     std::vector<double> poses_;              // 12 per vertex, rows of [R t]

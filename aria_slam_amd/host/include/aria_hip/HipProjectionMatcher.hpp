@@ -8,6 +8,7 @@
 
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -31,8 +32,6 @@ class HipProjectionMatcher {
 public:
     explicit HipProjectionMatcher(const ProjectionConfig& cfg = {});
     ~HipProjectionMatcher();
-    HipProjectionMatcher(const HipProjectionMatcher&) = delete;
-    HipProjectionMatcher& operator=(const HipProjectionMatcher&) = delete;
 
     // Host form: `count` landmarks from landmarks[first] on against the keypoints and descriptors of `frame`, under the predicted
     // world-to-camera pose T (4x4 row-major). pairs[].landmark indexes `landmarks`. Blocks; throws on a non-finite pose.
@@ -48,11 +47,11 @@ public:
                                 const aria_keypoint* d_kp, const std::uint8_t* d_desc, const int* d_n, std::int64_t kp_stride, int n_slots,
                                 aria_proj_landmark* d_land, int* d_nland);
     void check();
-    aria_proj_t handle() const { return h_; }
+    aria_proj_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_proj_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipProjectionMatcher", where, rc); }
+    detail::StageOwner<aria_proj_t, aria_proj_destroy> h_;
 };
 
 // The landmark of a map point seen in `frame` as keypoint idx: its X, the keypoint's descriptor row and octave, source = the

@@ -12,6 +12,7 @@
 
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -38,8 +39,6 @@ class HipRectifier {
 public:
     explicit HipRectifier(const RectifierConfig& cfg = {});
     ~HipRectifier();
-    HipRectifier(const HipRectifier&) = delete;
-    HipRectifier& operator=(const HipRectifier&) = delete;
 
     // One gray image of camera cam (src_width x src_height bytes, tightly packed) -> dst_width x dst_height bytes.
     void remap(int cam, const std::uint8_t* src, std::vector<std::uint8_t>& dst);
@@ -51,13 +50,14 @@ public:
     int dstWidth() const { return cfg_.dst_width; }
     int dstHeight() const { return cfg_.dst_height; }
     const aria_rect_config& config() const { return cfg_; }
-    aria_rect_t handle() const { return h_; }
+    aria_rect_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipRectifier", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipRectifier", where, rc); }
     aria_rect_config cfg_{};
     double baseline_ = 0.0;
-    aria_rect_t h_ = nullptr;
+    detail::StageOwner<aria_rect_t, aria_rect_destroy> h_;
 };
 
 }  // namespace aria::adapters::hip

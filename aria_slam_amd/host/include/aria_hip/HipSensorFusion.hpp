@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -30,8 +31,6 @@ class HipSensorFusion : public interfaces::ISensorFusion {
 public:
     explicit HipSensorFusion(const aria_fuse_config* cfg = nullptr);     // nullptr: aria_fuse_default_config
     ~HipSensorFusion() override;
-    HipSensorFusion(const HipSensorFusion&) = delete;
-    HipSensorFusion& operator=(const HipSensorFusion&) = delete;
 
     // the port
     void predictIMU(const core::ImuMeasurement& imu) override;
@@ -53,9 +52,9 @@ public:
              aria_fuse_state* states);
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    static void expect(const char* where, int rc) { detail::expect("HipSensorFusion", where, rc); }
     void flush() const;
-    aria_fuse_t h_ = nullptr;
+    detail::StageOwner<aria_fuse_t, aria_fuse_destroy> h_;
     aria_fuse_config cfg_{};
     mutable aria_fuse_filter filter_{};
     mutable std::vector<aria_imu_sample> imu_;

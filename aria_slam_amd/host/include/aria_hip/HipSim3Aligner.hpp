@@ -18,6 +18,7 @@
 #include "aria_hip/HipLoopDetector.hpp"
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -49,8 +50,6 @@ public:
                             bool fix_scale = false, std::uint64_t seed = 0, void* stream = nullptr, int device = 0,
                             double min_scale = 0.05, double max_scale = 20.0);   // a model with s outside them is invalid
     ~HipSim3Aligner();
-    HipSim3Aligner(const HipSim3Aligner&) = delete;
-    HipSim3Aligner& operator=(const HipSim3Aligner&) = delete;
 
     // std::nullopt when the stage finds no model (fewer than 3 correspondences, no valid hypothesis). A model is not a loop:
     // gate on n_inliers.
@@ -63,14 +62,12 @@ public:
     std::optional<Similarity> estimateAgainstMap(aria_map_t map, const KeyframeInMap& kf1, const KeyframeInMap& kf2,
                                                  const std::vector<core::Match>& matches, int pair_id = 0, int* n_corr = nullptr,
                                                  std::vector<int>* match_index = nullptr);
-    aria_sim3_t handle() const { return h_; }
+    aria_sim3_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_sim3_t h_ = nullptr;
-    int device_ = 0;
-    void* d_buf_ = nullptr;             // grow-only staging of estimateAgainstMap
-    std::size_t d_cap_ = 0;
+    static void expect(const char* where, int rc) { detail::expect("HipSim3Aligner", where, rc); }
+    detail::DeviceScratch scratch_;     // staging of estimateAgainstMap; before h_ (see Stage.hpp, DECLARATION ORDER)
+    detail::StageOwner<aria_sim3_t, aria_sim3_destroy> h_;
 };
 
 // One line of what the verifier did with a candidate

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "aria_hip/HipPoseGraphOptimizer.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -29,8 +30,6 @@ public:
     explicit HipSim3GraphOptimizer(bool fix_scale = false, int pcg_max_iters = 1000, double pcg_rel_tol = 1e-8, void* stream = nullptr,
                                    int device = 0);
     ~HipSim3GraphOptimizer();
-    HipSim3GraphOptimizer(const HipSim3GraphOptimizer&) = delete;
-    HipSim3GraphOptimizer& operator=(const HipSim3GraphOptimizer&) = delete;
 
     // HipPoseGraphOptimizer's surface
     void addOdometryEdge(int from_id, int to_id, const GraphPose& relative_pose, double info_scale = 1.0);
@@ -57,10 +56,11 @@ public:
     const std::vector<aria_sgraph_vertex>& vertices() const { return verts_; }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipSim3GraphOptimizer", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipSim3GraphOptimizer", where, rc); }
     void addEdge(int from_id, int to_id, const GraphPose& rel, double scale, double info_scale);
     void ensureHandle(int nv, int ne);
-    aria_sgraph_t h_ = nullptr;
+    detail::StageOwner<aria_sgraph_t, aria_sgraph_destroy> h_;
     aria_sgraph_config cfg_{};
     std::map<int, int> index_;               // id -> vertex index, in order of first setInitialPose
     std::vector<aria_sgraph_vertex> verts_;  // the estimates

@@ -9,6 +9,7 @@
 
 #include "aria_hip/HipPoseEstimator.hpp"
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -35,8 +36,6 @@ class HipStereoMatcher {
 public:
     explicit HipStereoMatcher(const StereoConfig& cfg = {});
     ~HipStereoMatcher();
-    HipStereoMatcher(const HipStereoMatcher&) = delete;
-    HipStereoMatcher& operator=(const HipStereoMatcher&) = delete;
 
     // One rectified pair: the two gray images (width x height bytes, tightly packed) and the frames extracted from them.
     StereoObservations match(const std::uint8_t* image_left, const std::uint8_t* image_right, int width, int height,
@@ -45,11 +44,11 @@ public:
     // of the matches when query_is_first. pose.mask selects the matches when it has one byte per match.
     aria_stereo_scale scale(const TwoViewPose& pose, const std::vector<core::Match>& matches, bool query_is_first,
                             const std::vector<aria_stereo_obs>& obs_query, const std::vector<aria_stereo_obs>& obs_train);
-    aria_stereo_t handle() const { return h_; }
+    aria_stereo_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_stereo_t h_ = nullptr;
+    static void expect(const char* where, int rc) { detail::expect("HipStereoMatcher", where, rc); }
+    detail::StageOwner<aria_stereo_t, aria_stereo_destroy> h_;
 };
 
 }  // namespace aria::adapters::hip

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -18,8 +19,6 @@ class HipTrajectoryEvaluator {
 public:
     explicit HipTrajectoryEvaluator(const aria_eval_config* cfg = nullptr);     // nullptr: aria_eval_default_config
     ~HipTrajectoryEvaluator();
-    HipTrajectoryEvaluator(const HipTrajectoryEvaluator&) = delete;
-    HipTrajectoryEvaluator& operator=(const HipTrajectoryEvaluator&) = delete;
 
     const aria_eval_config& config() const { return cfg_; }
     void setAlignMode(int mode) { cfg_.align_mode = mode; }
@@ -39,11 +38,12 @@ public:
                              const aria_eval_truth* d_truth, int n_truth, bool truth_shared, const std::uint8_t* d_mask,
                              double* d_pose_err, aria_eval_result* d_results);
     int check();
-    void* stream() const { return aria_eval_stream(h_); }
+    void* stream() const { return aria_eval_stream(h_.get()); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
-    aria_eval_t h_ = nullptr;
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipTrajectoryEvaluator", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipTrajectoryEvaluator", where, rc); }
+    detail::StageOwner<aria_eval_t, aria_eval_destroy> h_;
     aria_eval_config cfg_{};
 };
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "aria_hip/HipPoseEstimator.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -29,8 +30,6 @@ class HipTsdfVolume {
 public:
     explicit HipTsdfVolume(const TsdfVolumeConfig& cfg = {});
     ~HipTsdfVolume();
-    HipTsdfVolume(const HipTsdfVolume&) = delete;
-    HipTsdfVolume& operator=(const HipTsdfVolume&) = delete;
 
     // One frame from host buffers: depth width x height floats, tightly packed; extrinsics 12 doubles [R|t] row-major, world to
     // camera (the first three rows of a 4x4 pose serve); image width x height bytes or null. False when an extrinsic is not
@@ -40,7 +39,7 @@ public:
     void integrateBatchDevice(const float* d_depth, std::int64_t depth_stride, int depth_pitch, int width, int height,
                               const double* d_extrinsics, const std::uint8_t* d_frame_mask, const std::uint8_t* d_image,
                               std::int64_t image_stride, int image_pitch, int n_frames);
-    int check() { return aria_tsdf_check(h_); }
+    int check() { return aria_tsdf_check(h_.get()); }
     void clear();
     std::int64_t countPoints();
     // the surface points in canonical order
@@ -51,12 +50,13 @@ public:
     // the surface points in HipMapper::exportPLY's header and vertex format (r = g = b = gray); returns their number
     std::size_t exportPLY(const std::string& filename);
     const aria_tsdf_config& config() const { return cfg_; }
-    aria_tsdf_t handle() const { return h_; }
+    aria_tsdf_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipTsdfVolume", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipTsdfVolume", where, rc); }
     aria_tsdf_config cfg_{};
-    aria_tsdf_t h_ = nullptr;
+    detail::StageOwner<aria_tsdf_t, aria_tsdf_destroy> h_;
 };
 
 }  // namespace aria::adapters::hip

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "aria_hip/HipTsdfVolume.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -33,8 +34,6 @@ class HipVolumeMesher {
 public:
     explicit HipVolumeMesher(const VolumeMesherConfig& cfg = {});
     ~HipVolumeMesher();
-    HipVolumeMesher(const HipVolumeMesher&) = delete;
-    HipVolumeMesher& operator=(const HipVolumeMesher&) = delete;
 
     // Remembers the volume's records and rebuilds the word per voxel. A volume of other dims, voxel or origin than this
     // mesher's is refused. The volume's stream is synchronised first through its check(); a deferred error of the volume is
@@ -50,14 +49,15 @@ public:
     // ASCII PLY: the header and vertex lines HipTsdfVolume::exportPLY writes, plus `element face` with
     // `property list uchar int vertex_indices`. Returns the mesh's (vertices, triangles).
     std::pair<std::size_t, std::size_t> exportPLY(const std::string& filename);
-    int check() { return aria_mesh_check(h_); }
+    int check() { return aria_mesh_check(h_.get()); }
     const aria_mesh_config& config() const { return cfg_; }
-    aria_mesh_t handle() const { return h_; }
+    aria_mesh_t handle() const { return h_.get(); }
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipVolumeMesher", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipVolumeMesher", where, rc); }
     aria_mesh_config cfg_{};
-    aria_mesh_t h_ = nullptr;
+    detail::StageOwner<aria_mesh_t, aria_mesh_destroy> h_;
 };
 
 }  // namespace aria::adapters::hip

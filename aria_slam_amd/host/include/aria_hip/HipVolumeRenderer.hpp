@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "aria_hip/HipTsdfVolume.hpp"
+#include "aria_hip/detail/Stage.hpp"
 #include "aria_orb_hip.h"
 
 namespace aria::adapters::hip {
@@ -43,8 +44,6 @@ class HipVolumeRenderer {
 public:
     explicit HipVolumeRenderer(const VolumeRendererConfig& cfg = {});
     ~HipVolumeRenderer();
-    HipVolumeRenderer(const HipVolumeRenderer&) = delete;
-    HipVolumeRenderer& operator=(const HipVolumeRenderer&) = delete;
 
     // Remembers the volume's records and rebuilds the skip words. A volume of other dims, voxel or origin than this renderer's
     // is refused (min_weight is the renderer's own: it may ask for more than the volume's extraction does). The volume's
@@ -60,18 +59,19 @@ public:
                          std::int64_t depth_stride, int depth_pitch, float* d_normal, std::int64_t normal_stride, int normal_pitch,
                          std::uint8_t* d_gray, std::int64_t gray_stride, int gray_pitch, std::uint8_t* d_shade, std::int64_t shade_stride,
                          int shade_pitch, aria_ray_view* d_views);
-    int check() { return aria_ray_check(h_); }
+    int check() { return aria_ray_check(h_.get()); }
     const aria_ray_config& config() const { return cfg_; }
-    aria_ray_t handle() const { return h_; }
+    aria_ray_t handle() const { return h_.get(); }
 
     // Binary PGMs: depth as 16-bit millimetres, most significant byte first (0 = no hit, 65535 = 65.535 m or more); an 8-bit plane.
     static void writeDepthPGM(const std::string& filename, const float* depth, int width, int height);
     static void writeGrayPGM(const std::string& filename, const std::uint8_t* plane, int width, int height);
 
 private:
-    [[noreturn]] static void fail(const char* where, int status);
+    [[noreturn]] static void fail(const char* where, int status) { detail::fail("HipVolumeRenderer", where, status); }
+    static void expect(const char* where, int rc) { detail::expect("HipVolumeRenderer", where, rc); }
     aria_ray_config cfg_{};
-    aria_ray_t h_ = nullptr;
+    detail::StageOwner<aria_ray_t, aria_ray_destroy> h_;
 };
 
 }  // namespace aria::adapters::hip

@@ -6,6 +6,7 @@
 // keypoint order. Errors surface as std::runtime_error (the reference let cv::Exception propagate).
 #pragma once
 #include "aria_hip/compat.hpp"
+#include "aria_hip/detail/Stage.hpp"
 
 struct aria_orb_s;
 
@@ -17,8 +18,6 @@ public:
     // (OrbCudaExtractor.cpp:21-29). device: HIP ordinal (FactoryConfig::cuda_device, PipelineFactory.hpp:24).
     explicit OrbHipExtractor(int max_features = 1000, void* stream = nullptr, int device = 0);
     ~OrbHipExtractor() override;
-    OrbHipExtractor(const OrbHipExtractor&) = delete;
-    OrbHipExtractor& operator=(const OrbHipExtractor&) = delete;
 
     void extract(const std::uint8_t* image_data, int width, int height, core::Frame& frame) override;
     void extractAsync(const std::uint8_t* image_data, int width, int height, core::Frame& frame) override;
@@ -43,7 +42,7 @@ public:
     void reserve(int width, int height) { ensure(width, height); }
 
     // The C handle, for callers that want the device-resident batch entry points.
-    aria_orb_s* handle() const { return h_; }
+    aria_orb_s* handle() const { return h_.get(); }
     void* streamArg() const { return stream_; }      // the stream given to the constructor (nullptr = own stream)
     int device() const { return device_; }
 
@@ -52,7 +51,7 @@ private:
     void fill(core::Frame& frame, int width, int height, int n);
     int refetch(int rows);
 
-    aria_orb_s* h_ = nullptr;
+    detail::StageOwner<aria_orb_t, aria_orb_destroy> h_;
     void* stream_;
     int device_;
     int max_features_;

@@ -69,24 +69,20 @@ struct BatchFrontEnd::Impl {
         aria_stream_destroy(dev, s_in); aria_stream_destroy(dev, s_c); aria_stream_destroy(dev, s_out);
         s_in = s_c = s_out = nullptr;
     }
+    ~Impl() { release(); }
 };
 
 BatchFrontEnd::BatchFrontEnd(const BatchFrontEndConfig& cfg) : p_(new Impl), cfg_(cfg) {
-    if (cfg_.chunk < 1 || cfg_.max_features < 1 || cfg_.decode_threads < 1) { delete p_; throw std::invalid_argument("BatchFrontEnd: bad configuration"); }
+    if (cfg_.chunk < 1 || cfg_.max_features < 1 || cfg_.decode_threads < 1) throw std::invalid_argument("BatchFrontEnd: bad configuration");
     int ndev = 0;
     const int rc = aria_device_count(&ndev);
-    if (rc != ARIA_OK || cfg_.hip_device < 0 || cfg_.hip_device >= ndev) {
-        delete p_;
-        fail("device", rc != ARIA_OK ? rc : ARIA_E_NO_DEVICE);      // no CPU fallback: a front end without its GPU is an error
-    }
+    // no CPU fallback: a front end without its GPU is an error
+    if (rc != ARIA_OK || cfg_.hip_device < 0 || cfg_.hip_device >= ndev) fail("device", rc != ARIA_OK ? rc : ARIA_E_NO_DEVICE);
     p_->dev = cfg_.hip_device;
     p_->chunk = cfg_.chunk;
 }
 
-BatchFrontEnd::~BatchFrontEnd() {
-    p_->release();
-    delete p_;
-}
+BatchFrontEnd::~BatchFrontEnd() = default;
 
 void BatchFrontEnd::run(const io::AslSequence& seq, std::size_t first, std::size_t lo, std::size_t hi, const BatchSink& sink) {
     stats_ = BatchStats{};

@@ -18,25 +18,17 @@ HipBundleAdjuster::HipBundleAdjuster(const PoseIntrinsics& K, double huber_px, d
     c.min_depth = min_depth;
     c.max_iterations = max_iterations;
     c.max_windows = max_windows;
-    const int rc = aria_ba_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_ba_create", rc);
+    expect("aria_ba_create", aria_ba_create(&c, h_.out()));
 }
 
-HipBundleAdjuster::~HipBundleAdjuster() { aria_ba_destroy(h_); }
-
-void HipBundleAdjuster::fail(const char* where, int status) {
-    std::string msg = std::string("HipBundleAdjuster: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+HipBundleAdjuster::~HipBundleAdjuster() = default;
 
 BundleResult HipBundleAdjuster::optimize(BundleWindow& w, int iterations) {
     BundleResult out;
     out.used.assign(w.obs.size(), 0);
-    const int rc = aria_ba_optimize(h_, w.poses.data(), w.pose_fixed.data(), w.nPoses(), w.points.data(), w.point_fixed.data(),
-                                    w.nPoints(), w.obs.data(), (int)w.obs.size(), iterations, &out.record, out.used.data());
-    if (rc != ARIA_OK) fail("aria_ba_optimize", rc);
+    expect("aria_ba_optimize",
+           aria_ba_optimize(h_.get(), w.poses.data(), w.pose_fixed.data(), w.nPoses(), w.points.data(), w.point_fixed.data(),
+                            w.nPoints(), w.obs.data(), (int)w.obs.size(), iterations, &out.record, out.used.data()));
     return out;
 }
 
@@ -44,14 +36,13 @@ void HipBundleAdjuster::optimizeBatchDevice(double* d_poses, const std::uint8_t*
                                             const std::uint8_t* d_point_fixed, const aria_ba_obs* d_obs, const int* d_n_poses,
                                             const int* d_n_points, const int* d_n_obs, int n_windows, int pose_cap, int point_cap,
                                             int obs_cap, int iterations, aria_ba_result* d_out, std::uint8_t* d_used) {
-    const int rc = aria_ba_optimize_batch_device(h_, d_poses, d_pose_fixed, d_points, d_point_fixed, d_obs, d_n_poses, d_n_points,
-                                                 d_n_obs, n_windows, pose_cap, point_cap, obs_cap, iterations, d_out, d_used);
-    if (rc != ARIA_OK) fail("aria_ba_optimize_batch_device", rc);
+    expect("aria_ba_optimize_batch_device",
+           aria_ba_optimize_batch_device(h_.get(), d_poses, d_pose_fixed, d_points, d_point_fixed, d_obs, d_n_poses, d_n_points,
+                                         d_n_obs, n_windows, pose_cap, point_cap, obs_cap, iterations, d_out, d_used));
 }
 
 void HipBundleAdjuster::check() {
-    const int rc = aria_ba_check(h_);
-    if (rc != ARIA_OK) fail("aria_ba_check", rc);
+    expect("aria_ba_check", aria_ba_check(h_.get()));
 }
 
 // ---- WindowBuilder ------------------------------------------------------------------------------------------------------------

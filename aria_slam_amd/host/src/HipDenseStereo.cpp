@@ -9,13 +9,6 @@ namespace aria::adapters::hip {
 
 static_assert(sizeof(core::KeyPoint) == sizeof(aria_keypoint), "layouts");
 
-void HipDenseStereo::fail(const char* where, int status) {
-    std::string msg = std::string("HipDenseStereo: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 double DenseDepth::validShare() const {
     if (disparity.empty()) return 0.0;
     size_t n = 0;
@@ -42,11 +35,10 @@ HipDenseStereo::HipDenseStereo(const DenseStereoConfig& cfg) {
     c.P1 = cfg.P1; c.P2 = cfg.P2; c.uniqueness = cfg.uniqueness; c.lr_max_diff = cfg.lr_max_diff;
     c.max_width = cfg.max_width; c.max_height = cfg.max_height;
     c.scratch_bytes = cfg.scratch_bytes;
-    const int rc = aria_dense_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_dense_create", rc);
+    expect("aria_dense_create", aria_dense_create(&c, h_.out()));
 }
 
-HipDenseStereo::~HipDenseStereo() { aria_dense_destroy(h_); }
+HipDenseStereo::~HipDenseStereo() = default;
 
 DenseDepth HipDenseStereo::compute(const std::uint8_t* image_left, const std::uint8_t* image_right, int width, int height) {
     DenseDepth out;
@@ -54,17 +46,17 @@ DenseDepth HipDenseStereo::compute(const std::uint8_t* image_left, const std::ui
     out.height = height;
     out.disparity.resize((size_t)width * (size_t)height);
     out.depth.resize(out.disparity.size());
-    const int rc = aria_dense_compute(h_, image_left, image_right, width, height, width, out.disparity.data(), out.depth.data());
-    if (rc != ARIA_OK) fail("aria_dense_compute", rc);
+    expect("aria_dense_compute",
+           aria_dense_compute(h_.get(), image_left, image_right, width, height, width, out.disparity.data(), out.depth.data()));
     return out;
 }
 
 std::vector<aria_stereo_obs> HipDenseStereo::sample(const DenseDepth& map, const std::vector<core::KeyPoint>& keypoints) {
     std::vector<aria_stereo_obs> obs(keypoints.size());
     if (keypoints.empty()) return obs;
-    const int rc = aria_dense_sample(h_, map.disparity.data(), map.width, map.height, map.width,
-                                     reinterpret_cast<const aria_keypoint*>(keypoints.data()), (int)keypoints.size(), obs.data());
-    if (rc != ARIA_OK) fail("aria_dense_sample", rc);
+    expect("aria_dense_sample",
+           aria_dense_sample(h_.get(), map.disparity.data(), map.width, map.height, map.width,
+                             reinterpret_cast<const aria_keypoint*>(keypoints.data()), (int)keypoints.size(), obs.data()));
     return obs;
 }
 

@@ -6,13 +6,6 @@
 
 namespace aria::adapters::hip {
 
-void HipDenseTracker::fail(const char* where, int status) {
-    std::string msg = std::string("HipDenseTracker: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 DenseTrackerConfig DenseTrackerConfig::fromRenderer(const HipVolumeRenderer& renderer) {
     const aria_ray_config& r = renderer.config();
     DenseTrackerConfig c;
@@ -36,11 +29,10 @@ HipDenseTracker::HipDenseTracker(const DenseTrackerConfig& cfg) {
         cfg_.stride[l] = l < cfg_.n_levels ? cfg.strides[(std::size_t)l] : 0;
         cfg_.iterations[l] = l < cfg_.n_levels ? cfg.iterations[(std::size_t)l] : 0;
     }
-    const int rc = aria_icp_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_icp_create", rc);
+    expect("aria_icp_create", aria_icp_create(&cfg_, h_.out()));
 }
 
-HipDenseTracker::~HipDenseTracker() { aria_icp_destroy(h_); }
+HipDenseTracker::~HipDenseTracker() = default;
 
 void HipDenseTracker::requireSameIntrinsics(const HipVolumeRenderer& renderer) const {
     const aria_ray_config& r = renderer.config();
@@ -51,9 +43,9 @@ void HipDenseTracker::requireSameIntrinsics(const HipVolumeRenderer& renderer) c
 DenseTrack HipDenseTracker::track(const float* depth, const float* model_depth, const float* model_normal, int width, int height,
                                   const double* model_extrinsics, const double* guess) {
     DenseTrack out;
-    const int rc = aria_icp_track(h_, depth, model_depth, model_normal, model_extrinsics, guess ? guess : model_extrinsics, width, height,
-                                  out.extrinsics.data(), &out.result);
-    if (rc != ARIA_OK) fail("aria_icp_track", rc);
+    expect("aria_icp_track",
+           aria_icp_track(h_.get(), depth, model_depth, model_normal, model_extrinsics, guess ? guess : model_extrinsics, width, height,
+                          out.extrinsics.data(), &out.result));
     return out;
 }
 
@@ -62,10 +54,10 @@ void HipDenseTracker::trackBatchDevice(const float* d_depth, std::int64_t depth_
                                        std::int64_t normal_stride, int normal_pitch, const double* d_model_extrinsics,
                                        const double* d_guess, const std::uint8_t* d_mask, int n_frames, int width, int height,
                                        double* d_extrinsics_out, aria_icp_result* d_results) {
-    const int rc = aria_icp_track_batch_device(h_, d_depth, depth_stride, depth_pitch, d_model_depth, model_depth_stride, model_depth_pitch,
-                                               d_model_normal, normal_stride, normal_pitch, d_model_extrinsics, d_guess, d_mask, n_frames,
-                                               width, height, d_extrinsics_out, d_results);
-    if (rc != ARIA_OK) fail("aria_icp_track_batch_device", rc);
+    expect("aria_icp_track_batch_device",
+           aria_icp_track_batch_device(h_.get(), d_depth, depth_stride, depth_pitch, d_model_depth, model_depth_stride, model_depth_pitch,
+                                       d_model_normal, normal_stride, normal_pitch, d_model_extrinsics, d_guess, d_mask, n_frames,
+                                       width, height, d_extrinsics_out, d_results));
 }
 
 }  // namespace aria::adapters::hip

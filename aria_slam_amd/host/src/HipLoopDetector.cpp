@@ -11,42 +11,35 @@
 namespace aria::adapters::hip {
 
 namespace {
-[[noreturn]] void fail(const char* where, int status) {
-    std::string msg = std::string("HipLoopDetector: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+[[noreturn]] void fail(const char* where, int status) { detail::fail("HipLoopDetector", where, status); }
+void expect(const char* where, int rc) { detail::expect("HipLoopDetector", where, rc); }
 }  // namespace
 
 HipLoopDetector::HipLoopDetector(int min_frames_between, double min_score, int min_matches, int slot_rows, int capacity,
                                  void* stream, int device)
     : matcher_(stream, device), min_frames_between_(min_frames_between), min_score_(min_score), min_matches_(min_matches),
       slot_rows_(slot_rows) {
-    int rc = aria_kfdb_create(device, stream, capacity, slot_rows, &db_);
-    if (rc != ARIA_OK) fail("aria_kfdb_create", rc);
+    expect("aria_kfdb_create", aria_kfdb_create(device, stream, capacity, slot_rows, db_.out()));
     good_.resize((size_t)capacity);
 }
 
-HipLoopDetector::~HipLoopDetector() { aria_kfdb_destroy(db_); }
+HipLoopDetector::~HipLoopDetector() = default;
 
-int HipLoopDetector::size() const { return aria_kfdb_size(db_); }
+int HipLoopDetector::size() const { return aria_kfdb_size(db_.get()); }
 
 std::uint64_t HipLoopDetector::keyframeId(int index) const {
     long long id = -1;
-    int rc = aria_kfdb_info(db_, index, &id, nullptr);
-    if (rc != ARIA_OK) fail("aria_kfdb_info", rc);
+    expect("aria_kfdb_info", aria_kfdb_info(db_.get(), index, &id, nullptr));
     return (std::uint64_t)id;
 }
 
 void HipLoopDetector::addKeyFrame(const core::KeyFrame& kf) {
     const int n = (int)kf.frame.numKeypoints();
     if ((size_t)n * 32 > kf.frame.descriptors.size()) fail("addKeyFrame: descriptors shorter than numKeypoints()*32", ARIA_E_INVALID);
-    int rc = aria_kfdb_add(db_, (long long)kf.id, kf.frame.descriptors.data(), n);       // push_back + pop_front beyond 500
-    if (rc != ARIA_OK) fail("aria_kfdb_add", rc);
+    // push_back + pop_front beyond 500
+    expect("aria_kfdb_add", aria_kfdb_add(db_.get(), (long long)kf.id, kf.frame.descriptors.data(), n));
     if (place_) {                                                                          // the C-ABI directly: this file links without HipPlaceIndex.cpp
-        rc = aria_bow_add(place_->handle(), (long long)kf.id, n ? kf.frame.descriptors.data() : nullptr, n);
-        if (rc != ARIA_OK) fail("aria_bow_add", rc);
+        expect("aria_bow_add", aria_bow_add(place_->handle(), (long long)kf.id, n ? kf.frame.descriptors.data() : nullptr, n));
     }
 }
 
@@ -69,8 +62,8 @@ std::vector<std::pair<int, double>> HipLoopDetector::findCandidates(const core::
         const int shift = aria_bow_size(place_->handle()) - size();
         std::vector<aria_bow_hit> hits((size_t)place_->topK());
         int n_hits = 0;
-        int rc = aria_bow_query(place_->handle(), (long long)query.id, query.frame.descriptors.data(), nq, hits.data(), &n_hits);
-        if (rc != ARIA_OK) fail("aria_bow_query", rc);
+        expect("aria_bow_query",
+               aria_bow_query(place_->handle(), (long long)query.id, query.frame.descriptors.data(), nq, hits.data(), &n_hits));
         place_queries_++;
         hits.resize((size_t)std::max(0, std::min(n_hits, std::min(place_top_k_, place_->topK()))));
         match_buf_.resize((size_t)std::max(nq, 1));
@@ -78,14 +71,14 @@ std::vector<std::pair<int, double>> HipLoopDetector::findCandidates(const core::
             const int i = h.index - shift;
             long long id = 0;
             int cnt = 0;
-            if (i < 0 || aria_kfdb_info(db_, i, &id, &cnt) != ARIA_OK || id != (long long)h.id) continue;
+            if (i < 0 || aria_kfdb_info(db_.get(), i, &id, &cnt) != ARIA_OK || id != (long long)h.id) continue;
             if ((long long)query.id - id < (long long)min_frames_between_) continue;   // :81
             if (cnt <= 0) continue;                                                     // :83
             int good = 0;
             place_candidates_++;
-            rc = aria_kfdb_match(db_, matcher_.handle(), i, query.frame.descriptors.data(), nq, 0.7f,
-                                 reinterpret_cast<aria_match*>(match_buf_.data()), (int)match_buf_.size(), &good);
-            if (rc != ARIA_OK) fail("aria_kfdb_match", rc);
+            expect("aria_kfdb_match",
+                   aria_kfdb_match(db_.get(), matcher_.handle(), i, query.frame.descriptors.data(), nq, 0.7f,
+                                   reinterpret_cast<aria_match*>(match_buf_.data()), (int)match_buf_.size(), &good));
             const double score = (double)good / std::max(1, nq);                       // :98
             if (score > 0.1) candidates.push_back({i, score});                          // :99
         }
@@ -96,12 +89,12 @@ std::vector<std::pair<int, double>> HipLoopDetector::findCandidates(const core::
         return candidates;
     }
     int n_kf = 0;
-    int rc = aria_kfdb_scan(db_, matcher_.handle(), query.frame.descriptors.data(), nq, 0.7, good_.data(), (int)good_.size(), &n_kf);
-    if (rc != ARIA_OK) fail("aria_kfdb_scan", rc);
+    expect("aria_kfdb_scan",
+           aria_kfdb_scan(db_.get(), matcher_.handle(), query.frame.descriptors.data(), nq, 0.7, good_.data(), (int)good_.size(), &n_kf));
     for (int i = 0; i < n_kf; i++) {
         long long id = 0;
         int cnt = 0;
-        aria_kfdb_info(db_, i, &id, &cnt);
+        aria_kfdb_info(db_.get(), i, &id, &cnt);
         if ((long long)query.id - id < (long long)min_frames_between_) continue;   // :81
         if (cnt <= 0) continue;                                                     // :83
         const double score = (double)good_[(size_t)i] / std::max(1, nq);           // :98
@@ -121,15 +114,15 @@ std::optional<core::LoopCandidate> HipLoopDetector::detect(const core::KeyFrame&
         if (score < min_score_) continue;                                           // :42
         long long id = 0;
         int cnt = 0;
-        aria_kfdb_info(db_, idx, &id, &cnt);
+        aria_kfdb_info(db_.get(), idx, &id, &cnt);
         if ((long long)query.id - id < (long long)min_frames_between_) continue;    // :47
         // verification: the ratio-0.7 match list (LoopClosure.cpp:120-131), at least min_matches of them. The keyframe is
         // matched where it lies in the database (no download + upload of its descriptors)
         match_buf_.resize((size_t)std::max(nq, 1));
         int n = 0;
-        int rc = aria_kfdb_match(db_, matcher_.handle(), idx, query.frame.descriptors.data(), nq, 0.7f,
-                                 reinterpret_cast<aria_match*>(match_buf_.data()), (int)match_buf_.size(), &n);
-        if (rc != ARIA_OK) fail("aria_kfdb_match", rc);
+        expect("aria_kfdb_match",
+               aria_kfdb_match(db_.get(), matcher_.handle(), idx, query.frame.descriptors.data(), nq, 0.7f,
+                               reinterpret_cast<aria_match*>(match_buf_.data()), (int)match_buf_.size(), &n));
         core::LoopCandidate cand{};
         cand.matches.assign(match_buf_.begin(), match_buf_.begin() + n);
         if ((int)cand.matches.size() < min_matches_) continue;

@@ -28,18 +28,10 @@ HipMapper::HipMapper(const MapperConfig& cfg) : cfg_(cfg) {
     c.min_parallax_deg = cfg.min_parallax_deg;
     c.max_reproj_px = cfg.max_reproj_px;
     c.capacity = cfg.capacity;
-    const int rc = aria_map_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_map_create", rc);
+    expect("aria_map_create", aria_map_create(&c, h_.out()));
 }
 
-HipMapper::~HipMapper() { aria_map_destroy(h_); }
-
-void HipMapper::fail(const char* where, int status) {
-    std::string msg = std::string("HipMapper: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+HipMapper::~HipMapper() = default;
 
 int HipMapper::triangulateExtrinsics(const core::Frame& first, const core::Frame& second, const std::vector<core::Match>& matches,
                                      const double T1[16], const double T2[16], const std::uint8_t* image1, int width, int height,
@@ -48,17 +40,16 @@ int HipMapper::triangulateExtrinsics(const core::Frame& first, const core::Frame
     const core::Frame& q = query_is_first ? first : second;
     const core::Frame& t = query_is_first ? second : first;
     std::int64_t before = 0;
-    int rc = aria_map_size(h_, &before);
-    if (rc != ARIA_OK) fail("aria_map_size", rc);
+    expect("aria_map_size", aria_map_size(h_.get(), &before));
     int added = 0;
-    rc = aria_map_triangulate(h_, reinterpret_cast<const aria_keypoint*>(q.keypoints.data()), (int)q.keypoints.size(),
-                              reinterpret_cast<const aria_keypoint*>(t.keypoints.data()), (int)t.keypoints.size(),
-                              reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(), query_is_first ? 1 : 0,
-                              T1, T2, image1, width, height, width, nullptr, next_pair_, &added);
-    if (rc != ARIA_OK) fail("aria_map_triangulate", rc);
+    expect("aria_map_triangulate",
+           aria_map_triangulate(h_.get(), reinterpret_cast<const aria_keypoint*>(q.keypoints.data()), (int)q.keypoints.size(),
+                                reinterpret_cast<const aria_keypoint*>(t.keypoints.data()), (int)t.keypoints.size(),
+                                reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(), query_is_first ? 1 : 0,
+                                T1, T2, image1, width, height, width, nullptr, next_pair_, &added));
     next_pair_ = (next_pair_ + 1) & 0x7fffffff;
     std::vector<aria_map_point> recs((std::size_t)added);
-    if (added && (rc = aria_map_read(h_, before, added, recs.data())) != ARIA_OK) fail("aria_map_read", rc);
+    if (added) expect("aria_map_read", aria_map_read(h_.get(), before, added, recs.data()));
     for (const aria_map_point& r : recs) {
         core::MapPoint mp;
         mp.id = r.id;
@@ -93,10 +84,9 @@ void HipMapper::triangulate(const core::Frame& frame1, const core::Frame& frame2
 
 std::vector<aria_map_point> HipMapper::records() const {
     std::int64_t n = 0;
-    int rc = aria_map_size(h_, &n);
-    if (rc != ARIA_OK) fail("aria_map_size", rc);
+    expect("aria_map_size", aria_map_size(h_.get(), &n));
     std::vector<aria_map_point> recs((std::size_t)n);
-    if (n && (rc = aria_map_read(h_, 0, n, recs.data())) != ARIA_OK) fail("aria_map_read", rc);
+    if (n) expect("aria_map_read", aria_map_read(h_.get(), 0, n, recs.data()));
     return recs;
 }
 
@@ -136,29 +126,27 @@ void HipMapper::exportPCD(const std::string& filename) const {
 }
 
 void HipMapper::clear() {
-    const int rc = aria_map_clear(h_);
-    if (rc != ARIA_OK) fail("aria_map_clear", rc);
+    expect("aria_map_clear", aria_map_clear(h_.get()));
     made_.clear();
     cache_.clear();
 }
 
 std::size_t HipMapper::size() const {
     std::int64_t n = 0;
-    const int rc = aria_map_size(h_, &n);
-    if (rc != ARIA_OK) fail("aria_map_size", rc);
+    expect("aria_map_size", aria_map_size(h_.get(), &n));
     return (std::size_t)n;
 }
 
 void HipMapper::filterOutliers() {
-    int rc = aria_map_filter_outliers(h_);
-    if (rc == ARIA_OK) rc = aria_map_check(h_);
-    if (rc != ARIA_OK) fail("aria_map_filter_outliers", rc);
+    int rc = aria_map_filter_outliers(h_.get());
+    if (rc == ARIA_OK) rc = aria_map_check(h_.get());
+    expect("aria_map_filter_outliers", rc);
 }
 
 void HipMapper::filterByDistance(double max_distance) {
-    int rc = aria_map_filter_distance(h_, max_distance);
-    if (rc == ARIA_OK) rc = aria_map_check(h_);
-    if (rc != ARIA_OK) fail("aria_map_filter_distance", rc);
+    int rc = aria_map_filter_distance(h_.get(), max_distance);
+    if (rc == ARIA_OK) rc = aria_map_check(h_.get());
+    expect("aria_map_filter_distance", rc);
 }
 
 }  // namespace aria::adapters::hip

@@ -13,29 +13,23 @@ namespace aria::adapters::hip {
 static_assert(sizeof(core::Match) == sizeof(aria_match), "Match must stay 12 bytes (Types.hpp:97-101)");
 
 namespace {
-[[noreturn]] void fail(const char* where, int status) {
-    std::string msg = std::string("HipMatcher: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+[[noreturn]] void fail(const char* where, int status) { detail::fail("HipMatcher", where, status); }
+void expect(const char* where, int rc) { detail::expect("HipMatcher", where, rc); }
 }  // namespace
 
 HipMatcher::HipMatcher(void* stream, int device) : stream_(stream), device_(device) {}
-HipMatcher::~HipMatcher() { aria_matcher_destroy(m_); }
+HipMatcher::~HipMatcher() = default;
 
 void HipMatcher::ensure(int nq, int nt) {
-    if (m_ && nq <= cap_q_ && nt <= cap_t_) return;
-    aria_matcher_destroy(m_);
-    m_ = nullptr;
+    if (m_.get() && nq <= cap_q_ && nt <= cap_t_) return;
+    m_.reset();
     aria_matcher_config cfg;
     aria_matcher_default_config(&cfg);
     cfg.device = device_;
     cfg.stream = stream_;
     cfg.max_query = std::max({nq, cap_q_, 4096});
     cfg.max_train = std::max({nt, cap_t_, 4096});
-    int rc = aria_matcher_create(&cfg, &m_);
-    if (rc != ARIA_OK) fail("aria_matcher_create", rc);
+    expect("aria_matcher_create", aria_matcher_create(&cfg, m_.out()));
     cap_q_ = cfg.max_query;
     cap_t_ = cfg.max_train;
 }
@@ -49,9 +43,9 @@ void HipMatcher::match(const core::Frame& query, const core::Frame& train, std::
     ensure(nq, nt);
     buf_.resize((size_t)std::max(nq, 1));
     int n = 0;
-    int rc = aria_matcher_match(m_, query.descriptors.data(), nq, train.descriptors.data(), nt, ratio_threshold,
-                                reinterpret_cast<aria_match*>(buf_.data()), (int)buf_.size(), &n);
-    if (rc != ARIA_OK) fail("aria_matcher_match", rc);
+    expect("aria_matcher_match",
+           aria_matcher_match(m_.get(), query.descriptors.data(), nq, train.descriptors.data(), nt, ratio_threshold,
+                              reinterpret_cast<aria_match*>(buf_.data()), (int)buf_.size(), &n));
     matches.insert(matches.end(), buf_.begin(), buf_.begin() + n);            // :65 push_back, never cleared
 }
 
@@ -60,33 +54,32 @@ void HipMatcher::matchDevice(const std::uint8_t* d_query, int nq, const std::uin
     ensure(std::max(nq, 1), std::max(nt, 1));
     buf_.resize((size_t)std::max(nq, 1));
     int n = 0;
-    int rc = aria_matcher_match_device(m_, d_query, nq, d_train, nt, ratio_threshold, reinterpret_cast<aria_match*>(buf_.data()),
-                                       (int)buf_.size(), &n);
-    if (rc != ARIA_OK) fail("aria_matcher_match_device", rc);
+    expect("aria_matcher_match_device",
+           aria_matcher_match_device(m_.get(), d_query, nq, d_train, nt, ratio_threshold, reinterpret_cast<aria_match*>(buf_.data()),
+                                     (int)buf_.size(), &n));
     matches.insert(matches.end(), buf_.begin(), buf_.begin() + n);
 }
 
 void HipMatcher::retainDevice(const std::uint8_t* d_desc, int n) {
     ensure(std::max(n, 1), 1);
-    int rc = aria_matcher_retain_device(m_, d_desc, n);
-    if (rc != ARIA_OK) fail("aria_matcher_retain_device", rc);
+    expect("aria_matcher_retain_device", aria_matcher_retain_device(m_.get(), d_desc, n));
 }
 
-int HipMatcher::residentRows() const { return m_ ? aria_matcher_resident_rows(m_) : -1; }
+int HipMatcher::residentRows() const { return m_.get() ? aria_matcher_resident_rows(m_.get()) : -1; }
 
 bool HipMatcher::matchDeviceAsync(const std::uint8_t* d_new, const int* d_count, int rows_max, bool new_is_query,
                                   float ratio_threshold) {
-    if (!m_ || rows_max > cap_q_ || rows_max > cap_t_ || aria_matcher_resident_rows(m_) < 1) return false;
-    int rc = aria_matcher_match_device_async(m_, d_new, d_count, rows_max, new_is_query ? 1 : 0, ratio_threshold);
-    if (rc != ARIA_OK) fail("aria_matcher_match_device_async", rc);
+    if (!m_.get() || rows_max > cap_q_ || rows_max > cap_t_ || aria_matcher_resident_rows(m_.get()) < 1) return false;
+    expect("aria_matcher_match_device_async",
+           aria_matcher_match_device_async(m_.get(), d_new, d_count, rows_max, new_is_query ? 1 : 0, ratio_threshold));
     return true;
 }
 
 void HipMatcher::finishDevice(int n_new, std::vector<core::Match>& matches) {
     buf_.resize((size_t)std::max(cap_q_, 1));
     int n = 0;
-    int rc = aria_matcher_finish(m_, n_new, reinterpret_cast<aria_match*>(buf_.data()), (int)buf_.size(), &n);
-    if (rc != ARIA_OK) fail("aria_matcher_finish", rc);
+    expect("aria_matcher_finish",
+           aria_matcher_finish(m_.get(), n_new, reinterpret_cast<aria_match*>(buf_.data()), (int)buf_.size(), &n));
     matches.insert(matches.end(), buf_.begin(), buf_.begin() + n);
 }
 
@@ -108,9 +101,9 @@ void HipMatcher::matchMultiple(const core::Frame& query, const std::vector<core:
     }
     ensure(nq, max_nt);
     buf_.resize(candidates.size() * (size_t)nq);
-    int rc = aria_matcher_match_multi(m_, query.descriptors.data(), nq, ptrs.data(), nts.data(), (int)candidates.size(),
-                                      ratio_threshold, reinterpret_cast<aria_match*>(buf_.data()), nq, n_out.data());
-    if (rc != ARIA_OK) fail("aria_matcher_match_multi", rc);
+    expect("aria_matcher_match_multi",
+           aria_matcher_match_multi(m_.get(), query.descriptors.data(), nq, ptrs.data(), nts.data(), (int)candidates.size(),
+                                    ratio_threshold, reinterpret_cast<aria_match*>(buf_.data()), nq, n_out.data()));
     for (size_t i = 0; i < candidates.size(); i++)
         all_matches[i].insert(all_matches[i].end(), buf_.begin() + i * (size_t)nq, buf_.begin() + i * (size_t)nq + n_out[i]);
 }
@@ -141,9 +134,9 @@ std::vector<std::pair<int, double>> HipMatcher::findLoopCandidates(const core::F
     if (which.empty()) return candidates;
     ensure(nq, max_nt);
     std::vector<int> good(which.size());
-    int rc = aria_matcher_count_good_multi(m_, query.descriptors.data(), nq, ptrs.data(), nts.data(), (int)which.size(), 0.7,
-                                           good.data());                       // :90-95, double literal 0.7
-    if (rc != ARIA_OK) fail("aria_matcher_count_good_multi", rc);
+    expect("aria_matcher_count_good_multi",
+           aria_matcher_count_good_multi(m_.get(), query.descriptors.data(), nq, ptrs.data(), nts.data(), (int)which.size(), 0.7,
+                                         good.data()));                       // :90-95, double literal 0.7
     for (size_t k = 0; k < which.size(); k++) {
         const double score = (double)good[k] / std::max(1, nq);               // :98
         if (score > 0.1) candidates.push_back({which[k], score});              // :99

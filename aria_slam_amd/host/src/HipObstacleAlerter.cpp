@@ -49,12 +49,10 @@ void RecordingAudioFeedback::playCriticalAlert(interfaces::AudioDirection direct
     log.push_back(std::string("critical ") + directionName(direction));
 }
 
+// the one adapter whose ARIA_E_INVALID is a std::invalid_argument
 void HipObstacleAlerter::fail(const char* where, int status) {
-    std::string msg = std::string("HipObstacleAlerter: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    if (status == ARIA_E_INVALID) throw std::invalid_argument(msg);
-    throw std::runtime_error(msg);
+    if (status == ARIA_E_INVALID) throw std::invalid_argument(detail::message("HipObstacleAlerter", where, status));
+    detail::fail("HipObstacleAlerter", where, status);
 }
 
 HipObstacleAlerter::HipObstacleAlerter(const ObstacleAlerterConfig& cfg, interfaces::IAudioFeedback* audio, std::vector<std::string> class_names)
@@ -76,16 +74,16 @@ HipObstacleAlerter::HipObstacleAlerter(const ObstacleAlerterConfig& cfg, interfa
     cfg_.max_events_per_frame = cfg.max_events_per_frame;
     for (int i = 0; i < 4; i++) cfg_.cooldown_ns[i] = cfg.cooldown_ns[i];
     events_.resize((std::size_t)cfg.event_cap);
-    int rc = aria_alert_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_alert_create", rc);
+    expect("aria_alert_create", aria_alert_create(&cfg_, h_.out()));
     // the buffers of the device form
     const std::int32_t ints[3] = {0, 1, 0};
+    int rc;
     if ((rc = aria_device_alloc(cfg_.device, sizeof(aria_alert_state), &d_state_)) == ARIA_OK &&
         (rc = aria_device_alloc(cfg_.device, sizeof(aria_alert_event) * events_.size(), &d_events_)) == ARIA_OK &&
         (rc = aria_device_alloc(cfg_.device, sizeof(ints), &d_ints_)) == ARIA_OK &&
         (rc = aria_device_alloc(cfg_.device, sizeof(std::int64_t), &d_ts_)) == ARIA_OK)
-        rc = aria_copy_h2d_async(cfg_.device, aria_alert_stream(h_), d_ints_, ints, sizeof(ints));
-    if (rc == ARIA_OK) rc = aria_stream_synchronize(cfg_.device, aria_alert_stream(h_));   // `ints` leaves scope
+        rc = aria_copy_h2d_async(cfg_.device, aria_alert_stream(h_.get()), d_ints_, ints, sizeof(ints));
+    if (rc == ARIA_OK) rc = aria_stream_synchronize(cfg_.device, aria_alert_stream(h_.get()));   // `ints` leaves scope
     if (rc != ARIA_OK) {
         release();
         fail("device buffers", rc);
@@ -95,8 +93,7 @@ HipObstacleAlerter::HipObstacleAlerter(const ObstacleAlerterConfig& cfg, interfa
 HipObstacleAlerter::~HipObstacleAlerter() { release(); }
 
 void HipObstacleAlerter::release() {
-    aria_alert_destroy(h_);
-    h_ = nullptr;
+    h_.reset();
     for (void** p : {&d_state_, &d_events_, &d_ints_, &d_ts_}) {
         if (*p) aria_device_free(cfg_.device, *p);
         *p = nullptr;
@@ -152,7 +149,7 @@ std::vector<aria_alert_event> HipObstacleAlerter::process(const float* depth, co
     int n_events = 0;
     aria_alert_state after = state_;
     const bool have = n_dets > 0;
-    const int rc = aria_alert_run(h_, depth, (std::int64_t)cfg_.width * cfg_.height, cfg_.width, 1,
+    const int rc = aria_alert_run(h_.get(), depth, (std::int64_t)cfg_.width * cfg_.height, cfg_.width, 1,
                                   have ? reinterpret_cast<const aria_detection*>(detections.data()) : nullptr, have ? &n_dets : nullptr,
                                   have ? n_dets : 0, track_offset, 1, &timestamp_ns, &after, events_.data(), (int)events_.size(), &n_events);
     return finish(rc, n_events, after, timestamp_ns);
@@ -161,24 +158,24 @@ std::vector<aria_alert_event> HipObstacleAlerter::process(const float* depth, co
 std::vector<aria_alert_event> HipObstacleAlerter::processDevice(const float* d_depth, int depth_pitch, const aria_detection* d_detections,
                                                                 const int* d_n_detections, int det_cap, std::int64_t timestamp_ns) {
     accept(timestamp_ns);
-    void* st = aria_alert_stream(h_);
+    void* st = aria_alert_stream(h_.get());
     const int dev = cfg_.device;
     std::int32_t* d_i = static_cast<std::int32_t*>(d_ints_);
     int rc = aria_copy_h2d_async(dev, st, d_state_, &state_, sizeof(state_));
     if (rc == ARIA_OK) rc = aria_copy_h2d_async(dev, st, d_ts_, &timestamp_ns, sizeof(timestamp_ns));
     if (rc == ARIA_OK)
-        rc = aria_alert_run_batch_device(h_, d_depth, 0, depth_pitch, 1, d_detections, d_n_detections, det_cap, d_i, 1,
+        rc = aria_alert_run_batch_device(h_.get(), d_depth, 0, depth_pitch, 1, d_detections, d_n_detections, det_cap, d_i, 1,
                                          static_cast<const std::int64_t*>(d_ts_), static_cast<aria_alert_state*>(d_state_),
                                          static_cast<aria_alert_event*>(d_events_), (int)events_.size(), d_i + 2);
-    if (rc != ARIA_OK) fail("aria_alert_run_batch_device", rc);
-    rc = aria_alert_check(h_);                                           // synchronises: the counts are there
+    expect("aria_alert_run_batch_device", rc);
+    rc = aria_alert_check(h_.get());                                     // synchronises: the counts are there
     std::int32_t n_events = 0;
     int rc2 = aria_copy_d2h_async(dev, st, &n_events, d_i + 2, sizeof(n_events));
     aria_alert_state after;
     if (rc2 == ARIA_OK) rc2 = aria_copy_d2h_async(dev, st, &after, d_state_, sizeof(after));
     if (rc2 == ARIA_OK) rc2 = aria_copy_d2h_async(dev, st, events_.data(), d_events_, sizeof(aria_alert_event) * events_.size());
     if (rc2 == ARIA_OK) rc2 = aria_stream_synchronize(dev, st);
-    if (rc2 != ARIA_OK) fail("copy back", rc2);
+    expect("copy back", rc2);
     return finish(rc, n_events, after, timestamp_ns);
 }
 

@@ -8,13 +8,6 @@
 
 namespace aria::adapters::hip {
 
-void HipPathPlanner::fail(const char* where, int status) {
-    std::string msg = std::string("HipPathPlanner: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 PathPlannerConfig PathPlannerConfig::fromVolume(const HipTsdfVolume& volume) {
     const aria_tsdf_config& v = volume.config();
     PathPlannerConfig c;
@@ -41,51 +34,46 @@ HipPathPlanner::HipPathPlanner(const PathPlannerConfig& cfg) {
     cfg_.unknown_penalty = cfg.unknown_penalty; cfg_.allow_unknown = cfg.allow_unknown; cfg_.max_goals = cfg.max_goals;
     cfg_.voxel = cfg.voxel;
     for (int a = 0; a < 3; a++) cfg_.origin[a] = cfg.origin[a];
-    const int rc = aria_nav_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_nav_create", rc);
+    expect("aria_nav_create", aria_nav_create(&cfg_, h_.out()));
     axis_u_ = cfg_.up_axis == 0 ? 1 : 0;
     axis_v_ = cfg_.up_axis == 2 ? 1 : 2;
     nu_ = dims[axis_u_];
     nv_ = dims[axis_v_];
 }
 
-HipPathPlanner::~HipPathPlanner() { aria_nav_destroy(h_); }
+HipPathPlanner::~HipPathPlanner() = default;
 
 void HipPathPlanner::update(HipTsdfVolume& volume) {
     const aria_tsdf_config& v = volume.config();
     if (v.nx != cfg_.nx || v.ny != cfg_.ny || v.nz != cfg_.nz) fail("update: the volume has another geometry", ARIA_E_INVALID);
     // its stream is not this handle's: drain it. The check reports the volume's deferred error once, so it must not be dropped.
-    const int vrc = volume.check();
-    if (vrc != ARIA_OK) fail("update: the volume reports a deferred error", vrc);
-    const int rc = aria_nav_update_from_volume_device(h_, aria_tsdf_device_voxels(volume.handle()));
-    if (rc != ARIA_OK) fail("aria_nav_update_from_volume_device", rc);
+    expect("update: the volume reports a deferred error", volume.check());
+    expect("aria_nav_update_from_volume_device",
+           aria_nav_update_from_volume_device(h_.get(), aria_tsdf_device_voxels(volume.handle())));
 }
 
 bool HipPathPlanner::setCells(const std::uint8_t* cells) {
-    const int rc = aria_nav_set_cells(h_, cells);
+    const int rc = aria_nav_set_cells(h_.get(), cells);
     if (rc == ARIA_E_INVALID && cells) return false;
-    if (rc != ARIA_OK) fail("aria_nav_set_cells", rc);
+    expect("aria_nav_set_cells", rc);
     return true;
 }
 
 std::vector<std::uint8_t> HipPathPlanner::cells() {
     std::vector<std::uint8_t> out((std::size_t)nu_ * (std::size_t)nv_);
-    const int rc = aria_nav_read_cells(h_, out.data());
-    if (rc != ARIA_OK) fail("aria_nav_read_cells", rc);
+    expect("aria_nav_read_cells", aria_nav_read_cells(h_.get(), out.data()));
     return out;
 }
 
 std::vector<std::uint16_t> HipPathPlanner::clearance() {
     std::vector<std::uint16_t> out((std::size_t)nu_ * (std::size_t)nv_);
-    const int rc = aria_nav_read_clearance(h_, out.data());
-    if (rc != ARIA_OK) fail("aria_nav_read_clearance", rc);
+    expect("aria_nav_read_clearance", aria_nav_read_clearance(h_.get(), out.data()));
     return out;
 }
 
 std::vector<std::uint16_t> HipPathPlanner::costs() {
     std::vector<std::uint16_t> out((std::size_t)nu_ * (std::size_t)nv_);
-    const int rc = aria_nav_read_costs(h_, out.data());
-    if (rc != ARIA_OK) fail("aria_nav_read_costs", rc);
+    expect("aria_nav_read_costs", aria_nav_read_costs(h_.get(), out.data()));
     return out;
 }
 
@@ -96,7 +84,7 @@ PlanResult HipPathPlanner::plan(const std::vector<std::array<std::int32_t, 2>>& 
     r.path_cap = path_cap;
     r.records.resize(queries.size());
     r.paths.assign(queries.size() * (std::size_t)path_cap, 0);
-    const int rc = aria_nav_plan(h_, goals.empty() ? nullptr : goals[0].data(), (int)goals.size(), queries.empty() ? nullptr : queries[0].data(),
+    const int rc = aria_nav_plan(h_.get(), goals.empty() ? nullptr : goals[0].data(), (int)goals.size(), queries.empty() ? nullptr : queries[0].data(),
                                  (int)queries.size(), r.records.data(), r.paths.empty() ? nullptr : r.paths.data(), path_cap);
     if (rc != ARIA_OK && rc != ARIA_E_OUTPUT_TOO_SMALL) fail("aria_nav_plan", rc);
     r.truncated = rc == ARIA_E_OUTPUT_TOO_SMALL;
@@ -105,8 +93,7 @@ PlanResult HipPathPlanner::plan(const std::vector<std::array<std::int32_t, 2>>& 
 
 std::vector<std::int32_t> HipPathPlanner::field(int goal) {
     std::vector<std::int32_t> out((std::size_t)nu_ * (std::size_t)nv_);
-    const int rc = aria_nav_read_field(h_, goal, out.data());
-    if (rc != ARIA_OK) fail("aria_nav_read_field", rc);
+    expect("aria_nav_read_field", aria_nav_read_field(h_.get(), goal, out.data()));
     return out;
 }
 

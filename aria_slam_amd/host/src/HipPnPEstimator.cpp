@@ -7,8 +7,23 @@
 
 namespace aria::adapters::hip {
 
+namespace {
+AbsolutePose fromRecord(const aria_pnp_result& r) {
+    AbsolutePose out;
+    for (int k = 0; k < 9; k++) out.R[(size_t)k] = r.R[k];
+    for (int k = 0; k < 3; k++) out.t[(size_t)k] = r.t[k];
+    out.rms_px = r.rms_px;
+    out.n_corr = r.n_corr;
+    out.n_inliers = r.n_inliers;
+    out.iterations = r.iterations;
+    out.refined = r.refined != 0;
+    return out;
+}
+}  // namespace
+
 HipPnPEstimator::HipPnPEstimator(const PoseIntrinsics& K, int hypotheses, double threshold_px, int refine_iters, std::uint64_t seed,
-                                 void* stream, int device) {
+                                 void* stream, int device)
+    : scratch_("HipPnPEstimator", device) {
     aria_pnp_config c;
     aria_pnp_default_config(&c);
     c.device = device;
@@ -18,42 +33,20 @@ HipPnPEstimator::HipPnPEstimator(const PoseIntrinsics& K, int hypotheses, double
     c.fx = K.fx; c.fy = K.fy; c.cx = K.cx; c.cy = K.cy;
     c.threshold_px = threshold_px;
     c.seed = seed;
-    device_ = device;
-    const int rc = aria_pnp_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_pnp_create", rc);
+    expect("aria_pnp_create", aria_pnp_create(&c, h_.out()));
 }
 
-HipPnPEstimator::~HipPnPEstimator() {
-    aria_pnp_destroy(h_);                                          // drains the stream that reads d_buf_
-    if (d_buf_) aria_device_free(device_, d_buf_);
-}
+HipPnPEstimator::~HipPnPEstimator() = default;
 
-void HipPnPEstimator::fail(const char* where, int status) {
-    std::string msg = std::string("HipPnPEstimator: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
-void HipPnPEstimator::setSolver(int solver) {
-    const int rc = aria_pnp_set_solver(h_, solver);
-    if (rc != ARIA_OK) fail("aria_pnp_set_solver", rc);
-}
+void HipPnPEstimator::setSolver(int solver) { expect("aria_pnp_set_solver", aria_pnp_set_solver(h_.get(), solver)); }
 
 std::optional<AbsolutePose> HipPnPEstimator::estimate(const std::vector<aria_pnp_corr>& corr, int pair_id) {
     aria_pnp_result r{};
-    AbsolutePose out;
-    out.mask.assign(corr.size(), 0);
-    const int rc = aria_pnp_estimate(h_, corr.data(), (int)corr.size(), pair_id, &r, out.mask.data());
-    if (rc != ARIA_OK) fail("aria_pnp_estimate", rc);
+    std::vector<std::uint8_t> mask(corr.size(), 0);
+    expect("aria_pnp_estimate", aria_pnp_estimate(h_.get(), corr.data(), (int)corr.size(), pair_id, &r, mask.data()));
     if (!r.valid) return std::nullopt;
-    for (int k = 0; k < 9; k++) out.R[(size_t)k] = r.R[k];
-    for (int k = 0; k < 3; k++) out.t[(size_t)k] = r.t[k];
-    out.rms_px = r.rms_px;
-    out.n_corr = r.n_corr;
-    out.n_inliers = r.n_inliers;
-    out.iterations = r.iterations;
-    out.refined = r.refined != 0;
+    AbsolutePose out = fromRecord(r);
+    out.mask = std::move(mask);
     return out;
 }
 
@@ -75,55 +68,39 @@ std::optional<AbsolutePose> HipPnPEstimator::estimateAgainstMap(aria_map_t map, 
         m[i].distance = matches[i].distance;
         if (m[i].train_idx >= 0) stride = std::max(stride, (std::size_t)m[i].train_idx + 1);
     }
-    auto up = [](std::size_t b) { return (b + 255) / 256 * 256; };
-    const std::size_t o_kp = 0, o_m = o_kp + up(stride * sizeof(aria_keypoint)), o_cnt = o_m + up(n * sizeof(aria_match)),
-                      o_corr = o_cnt + 256, o_back = o_corr + up(n * sizeof(aria_pnp_corr)), o_out = o_back + up(n * sizeof(int)),
-                      o_mask = o_out + 256, total = o_mask + up(n);
-    int rc;
-    void* st = aria_pnp_stream(h_);
-    if (total > d_cap_) {
-        if ((rc = aria_stream_synchronize(device_, st)) != ARIA_OK) fail("aria_stream_synchronize", rc);
-        if (d_buf_) aria_device_free(device_, d_buf_);
-        d_buf_ = nullptr;
-        d_cap_ = 0;
-        if ((rc = aria_device_alloc(device_, total, &d_buf_)) != ARIA_OK) fail("aria_device_alloc", rc);
-        d_cap_ = total;
-    }
-    char* d = static_cast<char*>(d_buf_);
+    detail::ScratchLayout lay;
+    const std::size_t o_kp = lay.take(stride * sizeof(aria_keypoint)), o_m = lay.take(n * sizeof(aria_match)), o_cnt = lay.take(256),
+                      o_corr = lay.take(n * sizeof(aria_pnp_corr)), o_back = lay.take(n * sizeof(int)), o_out = lay.take(256),
+                      o_mask = lay.take(n);
+    void* st = aria_pnp_stream(h_.get());
+    const int dev = scratch_.device();
+    scratch_.reserve(st, lay.total);
+    char* d = scratch_.data();
     const int counts[3] = {(int)nk, (int)n, 0};                  // nq, n_matches; [2] receives the join's count
-    if ((rc = aria_copy_h2d_async(device_, st, d + o_kp, tracked.keypoints.data(), nk * sizeof(aria_keypoint))) != ARIA_OK ||
-        (rc = aria_copy_h2d_async(device_, st, d + o_m, m.data(), n * sizeof(aria_match))) != ARIA_OK ||
-        (rc = aria_copy_h2d_async(device_, st, d + o_cnt, counts, sizeof(counts))) != ARIA_OK)
-        fail("aria_copy_h2d_async", rc);
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_kp, tracked.keypoints.data(), nk * sizeof(aria_keypoint)));
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_m, m.data(), n * sizeof(aria_match)));
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_cnt, counts, sizeof(counts)));
     int* d_cnt = reinterpret_cast<int*>(d + o_cnt);
-    rc = aria_pnp_associate_batch_device(h_, map, anchor_pair, anchor_view, reinterpret_cast<const aria_keypoint*>(d + o_kp), d_cnt,
-                                         (std::int64_t)stride, reinterpret_cast<const aria_match*>(d + o_m), d_cnt + 1, 1, (int)n,
-                                         reinterpret_cast<aria_pnp_corr*>(d + o_corr), d_cnt + 2, reinterpret_cast<int*>(d + o_back));
-    if (rc != ARIA_OK) fail("aria_pnp_associate_batch_device", rc);
-    rc = aria_pnp_estimate_batch_device(h_, reinterpret_cast<const aria_pnp_corr*>(d + o_corr), d_cnt + 2, 1, (int)n, pair_id,
-                                        reinterpret_cast<aria_pnp_result*>(d + o_out), reinterpret_cast<std::uint8_t*>(d + o_mask));
-    if (rc != ARIA_OK) fail("aria_pnp_estimate_batch_device", rc);
+    expect("aria_pnp_associate_batch_device",
+           aria_pnp_associate_batch_device(h_.get(), map, anchor_pair, anchor_view, reinterpret_cast<const aria_keypoint*>(d + o_kp), d_cnt,
+                                           (std::int64_t)stride, reinterpret_cast<const aria_match*>(d + o_m), d_cnt + 1, 1, (int)n,
+                                           reinterpret_cast<aria_pnp_corr*>(d + o_corr), d_cnt + 2, reinterpret_cast<int*>(d + o_back)));
+    expect("aria_pnp_estimate_batch_device",
+           aria_pnp_estimate_batch_device(h_.get(), reinterpret_cast<const aria_pnp_corr*>(d + o_corr), d_cnt + 2, 1, (int)n, pair_id,
+                                          reinterpret_cast<aria_pnp_result*>(d + o_out), reinterpret_cast<std::uint8_t*>(d + o_mask)));
     aria_pnp_result r{};
     int found = 0;
     std::vector<std::uint8_t> mask(n);
     std::vector<int> back(n);
-    if ((rc = aria_copy_d2h_async(device_, st, &r, d + o_out, sizeof(r))) != ARIA_OK ||
-        (rc = aria_copy_d2h_async(device_, st, &found, d_cnt + 2, sizeof(int))) != ARIA_OK ||
-        (rc = aria_copy_d2h_async(device_, st, mask.data(), d + o_mask, n)) != ARIA_OK ||
-        (rc = aria_copy_d2h_async(device_, st, back.data(), d + o_back, n * sizeof(int))) != ARIA_OK)
-        fail("aria_copy_d2h_async", rc);
-    if ((rc = aria_pnp_check(h_)) != ARIA_OK) fail("aria_pnp_check", rc);   // synchronises the stream
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, &r, d + o_out, sizeof(r)));
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, &found, d_cnt + 2, sizeof(int)));
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, mask.data(), d + o_mask, n));
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, back.data(), d + o_back, n * sizeof(int)));
+    expect("aria_pnp_check", aria_pnp_check(h_.get()));   // synchronises the stream
     if (n_corr) *n_corr = found;
     if (match_index) match_index->assign(back.begin(), back.begin() + found);
     if (!r.valid) return std::nullopt;
-    AbsolutePose out;
-    for (int k = 0; k < 9; k++) out.R[(size_t)k] = r.R[k];
-    for (int k = 0; k < 3; k++) out.t[(size_t)k] = r.t[k];
-    out.rms_px = r.rms_px;
-    out.n_corr = r.n_corr;
-    out.n_inliers = r.n_inliers;
-    out.iterations = r.iterations;
-    out.refined = r.refined != 0;
+    AbsolutePose out = fromRecord(r);
     out.mask.assign(mask.begin(), mask.begin() + found);
     return out;
 }

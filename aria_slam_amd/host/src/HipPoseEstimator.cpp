@@ -1,7 +1,6 @@
 // See aria_hip/HipPoseEstimator.hpp.
 #include "aria_hip/HipPoseEstimator.hpp"
 
-
 namespace aria::adapters::hip {
 
 namespace {

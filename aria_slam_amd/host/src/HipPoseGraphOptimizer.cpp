@@ -27,14 +27,7 @@ HipPoseGraphOptimizer::HipPoseGraphOptimizer(int pcg_max_iters, double pcg_rel_t
     cfg_.max_edges = 0;
 }
 
-HipPoseGraphOptimizer::~HipPoseGraphOptimizer() { aria_graph_destroy(h_); }
-
-void HipPoseGraphOptimizer::fail(const char* where, int status) {
-    std::string msg = std::string("HipPoseGraphOptimizer: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+HipPoseGraphOptimizer::~HipPoseGraphOptimizer() = default;
 
 void HipPoseGraphOptimizer::setInitialPose(int id, const GraphPose& pose) {
     double rows[12];
@@ -75,16 +68,13 @@ void HipPoseGraphOptimizer::addLoopEdge(int from_id, int to_id, const GraphPose&
 void HipPoseGraphOptimizer::optimize(int iterations) {
     const int nv = (int)(poses_.size() / 12), ne = (int)edges_.size();
     if (nv == 0) return;
-    if (!h_ || nv > cfg_.max_vertices || ne > cfg_.max_edges) {
-        aria_graph_destroy(h_);
-        h_ = nullptr;
+    if (!h_.get() || nv > cfg_.max_vertices || ne > cfg_.max_edges) {
+        h_.reset();
         cfg_.max_vertices = std::max(std::max(nv, 2 * cfg_.max_vertices), 256);
         cfg_.max_edges = std::max(std::max(ne, 2 * cfg_.max_edges), 256);
-        const int rc = aria_graph_create(&cfg_, &h_);
-        if (rc != ARIA_OK) fail("aria_graph_create", rc);
+        expect("aria_graph_create", aria_graph_create(&cfg_, h_.out()));
     }
-    const int rc = aria_graph_optimize(h_, poses_.data(), nv, 0, edges_.data(), ne, iterations, &last_);
-    if (rc != ARIA_OK) fail("aria_graph_optimize", rc);
+    expect("aria_graph_optimize", aria_graph_optimize(h_.get(), poses_.data(), nv, 0, edges_.data(), ne, iterations, &last_));
 }
 
 GraphPose HipPoseGraphOptimizer::getOptimizedPose(int id) const {

@@ -18,18 +18,10 @@ HipProjectionMatcher::HipProjectionMatcher(const ProjectionConfig& cfg) {
     c.ratio = cfg.ratio;
     c.th_hamming = cfg.th_hamming;
     c.max_octave_diff = cfg.max_octave_diff;
-    const int rc = aria_proj_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_proj_create", rc);
+    expect("aria_proj_create", aria_proj_create(&c, h_.out()));
 }
 
-HipProjectionMatcher::~HipProjectionMatcher() { aria_proj_destroy(h_); }
-
-void HipProjectionMatcher::fail(const char* where, int status) {
-    std::string msg = std::string("HipProjectionMatcher: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+HipProjectionMatcher::~HipProjectionMatcher() = default;
 
 ProjectionMatches HipProjectionMatcher::search(const double T[16], const core::Frame& frame,
                                                const std::vector<aria_proj_landmark>& landmarks, std::size_t first, std::size_t count,
@@ -42,10 +34,10 @@ ProjectionMatches HipProjectionMatcher::search(const double T[16], const core::F
     out.corr.resize(count);
     out.pairs.resize(count);
     int n = 0;
-    const int rc = aria_proj_search(h_, T, reinterpret_cast<const aria_keypoint*>(frame.keypoints.data()), frame.descriptors.data(),
-                                    (int)frame.keypoints.size(), width, height, landmarks.data() + first, (int)count, out.obs.data(),
-                                    out.corr.data(), out.pairs.data(), &n);   // the first 12 of T are [R|t] row-major
-    if (rc != ARIA_OK) fail("aria_proj_search", rc);
+    expect("aria_proj_search",
+           aria_proj_search(h_.get(), T, reinterpret_cast<const aria_keypoint*>(frame.keypoints.data()), frame.descriptors.data(),
+                            (int)frame.keypoints.size(), width, height, landmarks.data() + first, (int)count, out.obs.data(),
+                            out.corr.data(), out.pairs.data(), &n));   // the first 12 of T are [R|t] row-major
     out.corr.resize((std::size_t)n);
     out.pairs.resize((std::size_t)n);
     for (aria_proj_pair& p : out.pairs) p.landmark += (int)first;
@@ -56,22 +48,21 @@ void HipProjectionMatcher::searchDevice(const double* d_pose, const aria_keypoin
                                         std::int64_t kp_stride, int width, int height, const aria_proj_landmark* d_land, int n_landmarks,
                                         const int* d_range, int land_cap, int n_frames, aria_proj_obs* d_obs, aria_pnp_corr* d_corr,
                                         aria_proj_pair* d_pairs, int* d_ncorr) {
-    const int rc = aria_proj_search_batch_device(h_, d_pose, d_kp, d_desc, d_n, kp_stride, width, height, d_land, n_landmarks, d_range,
-                                                 land_cap, n_frames, d_obs, d_corr, d_pairs, d_ncorr);
-    if (rc != ARIA_OK) fail("aria_proj_search_batch_device", rc);
+    expect("aria_proj_search_batch_device",
+           aria_proj_search_batch_device(h_.get(), d_pose, d_kp, d_desc, d_n, kp_stride, width, height, d_land, n_landmarks, d_range,
+                                         land_cap, n_frames, d_obs, d_corr, d_pairs, d_ncorr));
 }
 
 void HipProjectionMatcher::landmarksFromMapDevice(aria_map_t map, std::int64_t first, std::int64_t max_count, int pair_base, int view,
                                                   const aria_keypoint* d_kp, const std::uint8_t* d_desc, const int* d_n,
                                                   std::int64_t kp_stride, int n_slots, aria_proj_landmark* d_land, int* d_nland) {
-    const int rc = aria_proj_landmarks_from_map_device(h_, map, first, max_count, pair_base, view, d_kp, d_desc, d_n, kp_stride, n_slots,
-                                                       d_land, d_nland);
-    if (rc != ARIA_OK) fail("aria_proj_landmarks_from_map_device", rc);
+    expect("aria_proj_landmarks_from_map_device",
+           aria_proj_landmarks_from_map_device(h_.get(), map, first, max_count, pair_base, view, d_kp, d_desc, d_n, kp_stride, n_slots,
+                                               d_land, d_nland));
 }
 
 void HipProjectionMatcher::check() {
-    const int rc = aria_proj_check(h_);
-    if (rc != ARIA_OK) fail("aria_proj_check", rc);
+    expect("aria_proj_check", aria_proj_check(h_.get()));
 }
 
 aria_proj_landmark landmarkFromPoint(const aria_map_point& point, const core::Frame& frame, int idx, int arena_position) {

@@ -8,13 +8,6 @@ namespace aria::adapters::hip {
 
 static_assert(sizeof(core::KeyPoint) == sizeof(aria_keypoint), "layouts");
 
-void HipRectifier::fail(const char* where, int status) {
-    std::string msg = std::string("HipRectifier: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 HipRectifier::HipRectifier(const RectifierConfig& cfg) {
     aria_rect_default_config(&cfg_);
     cfg_.device = cfg.device;
@@ -36,36 +29,32 @@ HipRectifier::HipRectifier(const RectifierConfig& cfg) {
     if (cfg.n_cameras == 2) {
         const double kl[4] = {cfg.cam[0].K.fx, cfg.cam[0].K.fy, cfg.cam[0].K.cx, cfg.cam[0].K.cy};
         const double kr[4] = {cfg.cam[1].K.fx, cfg.cam[1].K.fy, cfg.cam[1].K.cx, cfg.cam[1].K.cy};
-        const int rc = aria_rect_stereo_geometry(kl, kr, cfg.cam[0].T_BS, cfg.cam[1].T_BS, &cfg_, &baseline_);
-        if (rc != ARIA_OK) fail("aria_rect_stereo_geometry", rc);
+        expect("aria_rect_stereo_geometry", aria_rect_stereo_geometry(kl, kr, cfg.cam[0].T_BS, cfg.cam[1].T_BS, &cfg_, &baseline_));
     } else {                                               // plain undistortion: R = I (the default), new K = K where zero
         if (cfg_.new_fx == 0.0) cfg_.new_fx = cfg_.cam[0].fx;
         if (cfg_.new_fy == 0.0) cfg_.new_fy = cfg_.cam[0].fy;
         if (cfg_.new_cx == 0.0) cfg_.new_cx = cfg_.cam[0].cx;
         if (cfg_.new_cy == 0.0) cfg_.new_cy = cfg_.cam[0].cy;
     }
-    const int rc = aria_rect_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_rect_create", rc);
+    expect("aria_rect_create", aria_rect_create(&cfg_, h_.out()));
 }
 
-HipRectifier::~HipRectifier() { aria_rect_destroy(h_); }
+HipRectifier::~HipRectifier() = default;
 
 void HipRectifier::remap(int cam, const std::uint8_t* src, std::vector<std::uint8_t>& dst) {
     dst.resize((std::size_t)cfg_.dst_width * cfg_.dst_height);
-    const int rc = aria_rect_remap(h_, cam, src, cfg_.src_width, dst.data(), cfg_.dst_width);
-    if (rc != ARIA_OK) fail("aria_rect_remap", rc);
+    expect("aria_rect_remap", aria_rect_remap(h_.get(), cam, src, cfg_.src_width, dst.data(), cfg_.dst_width));
 }
 
 void HipRectifier::points(int cam, std::vector<core::KeyPoint>& keypoints) {
     if (keypoints.empty()) return;
     aria_keypoint* k = reinterpret_cast<aria_keypoint*>(keypoints.data());
-    const int rc = aria_rect_points(h_, cam, k, (int)keypoints.size(), k);
-    if (rc != ARIA_OK) fail("aria_rect_points", rc);
+    expect("aria_rect_points", aria_rect_points(h_.get(), cam, k, (int)keypoints.size(), k));
 }
 
 std::vector<std::uint32_t> HipRectifier::map(int cam) {
     std::vector<std::uint32_t> m((std::size_t)cfg_.dst_width * cfg_.dst_height);
-    const int rc = aria_rect_get_map(h_, cam, m.data(), (int)m.size());
+    const int rc = aria_rect_get_map(h_.get(), cam, m.data(), (int)m.size());
     if (rc < 0) fail("aria_rect_get_map", rc);
     return m;
 }

@@ -37,20 +37,11 @@ void rotOf(const double q[4], double R[9]) {
 HipSensorFusion::HipSensorFusion(const aria_fuse_config* cfg) {
     aria_fuse_default_config(&cfg_);
     if (cfg) cfg_ = *cfg;
-    int rc = aria_fuse_filter_init(&filter_, &cfg_);
-    if (rc != ARIA_OK) fail("aria_fuse_filter_init", rc);
-    rc = aria_fuse_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_fuse_create", rc);
+    expect("aria_fuse_filter_init", aria_fuse_filter_init(&filter_, &cfg_));
+    expect("aria_fuse_create", aria_fuse_create(&cfg_, h_.out()));
 }
 
-HipSensorFusion::~HipSensorFusion() { aria_fuse_destroy(h_); }
-
-void HipSensorFusion::fail(const char* where, int status) {
-    std::string msg = std::string("HipSensorFusion: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+HipSensorFusion::~HipSensorFusion() = default;
 
 void HipSensorFusion::addIMU(double t, const double accel[3], const double gyro[3]) {
     aria_imu_sample s{};
@@ -94,19 +85,18 @@ void HipSensorFusion::flush() const {
     }
     if (visual_.empty()) return;
     states_.assign(visual_.size(), aria_fuse_state{});
-    const int rc = aria_fuse_run(h_, &filter_, imu_.data(), (int)imu_.size(), imu_end_.data(), visual_.data(), (int)visual_.size(),
+    const int rc = aria_fuse_run(h_.get(), &filter_, imu_.data(), (int)imu_.size(), imu_end_.data(), visual_.data(), (int)visual_.size(),
                                  states_.data());
     imu_.clear();
     imu_end_.clear();
     visual_.clear();
-    if (rc != ARIA_OK) fail("aria_fuse_run", rc);
+    expect("aria_fuse_run", rc);
 }
 
 void HipSensorFusion::run(const aria_imu_sample* imu, int n_imu, const int* imu_end, const aria_fuse_visual* visual, int n_frames,
                           aria_fuse_state* states) {
     flush();
-    const int rc = aria_fuse_run(h_, &filter_, imu, n_imu, imu_end, visual, n_frames, states);
-    if (rc != ARIA_OK) fail("aria_fuse_run", rc);
+    expect("aria_fuse_run", aria_fuse_run(h_.get(), &filter_, imu, n_imu, imu_end, visual, n_frames, states));
 }
 
 const aria_fuse_filter& HipSensorFusion::filter() const {
@@ -140,8 +130,7 @@ void HipSensorFusion::reset() {
     imu_end_.clear();
     visual_.clear();
     states_.clear();
-    const int rc = aria_fuse_filter_init(&filter_, &cfg_);
-    if (rc != ARIA_OK) fail("aria_fuse_filter_init", rc);
+    expect("aria_fuse_filter_init", aria_fuse_filter_init(&filter_, &cfg_));
 }
 
 void HipSensorFusion::reset(const core::Pose& initial_pose) {

@@ -10,7 +10,8 @@
 namespace aria::adapters::hip {
 
 HipSim3Aligner::HipSim3Aligner(const PoseIntrinsics& K, int hypotheses, double threshold_px, int refine_iters, bool fix_scale,
-                               std::uint64_t seed, void* stream, int device, double min_scale, double max_scale) {
+                               std::uint64_t seed, void* stream, int device, double min_scale, double max_scale)
+    : scratch_("HipSim3Aligner", device) {
     aria_sim3_config c;
     aria_sim3_default_config(&c);
     c.device = device;
@@ -23,22 +24,10 @@ HipSim3Aligner::HipSim3Aligner(const PoseIntrinsics& K, int hypotheses, double t
     c.seed = seed;
     c.min_scale = min_scale;
     c.max_scale = max_scale;
-    device_ = device;
-    const int rc = aria_sim3_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_sim3_create", rc);
+    expect("aria_sim3_create", aria_sim3_create(&c, h_.out()));
 }
 
-HipSim3Aligner::~HipSim3Aligner() {
-    aria_sim3_destroy(h_);                                         // drains the stream that reads d_buf_
-    if (d_buf_) aria_device_free(device_, d_buf_);
-}
-
-void HipSim3Aligner::fail(const char* where, int status) {
-    std::string msg = std::string("HipSim3Aligner: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+HipSim3Aligner::~HipSim3Aligner() = default;
 
 namespace {
 Similarity fromRecord(const aria_sim3_result& r) {
@@ -58,8 +47,7 @@ Similarity fromRecord(const aria_sim3_result& r) {
 std::optional<Similarity> HipSim3Aligner::estimate(const std::vector<aria_sim3_corr>& corr, int pair_id) {
     aria_sim3_result r{};
     std::vector<std::uint8_t> mask(corr.size(), 0);
-    const int rc = aria_sim3_estimate(h_, corr.data(), (int)corr.size(), pair_id, &r, mask.data());
-    if (rc != ARIA_OK) fail("aria_sim3_estimate", rc);
+    expect("aria_sim3_estimate", aria_sim3_estimate(h_.get(), corr.data(), (int)corr.size(), pair_id, &r, mask.data()));
     if (!r.valid) return std::nullopt;
     Similarity out = fromRecord(r);
     out.mask = std::move(mask);
@@ -76,56 +64,47 @@ std::optional<Similarity> HipSim3Aligner::estimateAgainstMap(aria_map_t map, con
     const std::size_t n = matches.size(), n1 = kf1.frame->keypoints.size(), n2 = kf2.frame->keypoints.size();
     if (!n || !n1 || !n2) return std::nullopt;
     const std::size_t stride = std::max(n1, n2);
-    auto up = [](std::size_t b) { return (b + 255) / 256 * 256; };
+    detail::ScratchLayout lay;
+    const std::size_t o_k1 = lay.take(stride * sizeof(aria_keypoint)), o_k2 = lay.take(stride * sizeof(aria_keypoint)),
+                      o_m = lay.take(n * sizeof(aria_match)), o_cnt = lay.take(256), o_pose = lay.take(256),
+                      o_corr = lay.take(n * sizeof(aria_sim3_corr)), o_back = lay.take(n * sizeof(int)), o_out = lay.take(256),
+                      o_mask = lay.take(n);
+    void* st = aria_sim3_stream(h_.get());
+    const int dev = scratch_.device();
+    scratch_.reserve(st, lay.total);
+    char* d = scratch_.data();
     // counts: [0] n1, [1] n2, [2] n_matches, [3] the join's count, [4] anchor 1, [5] anchor 2
-    const std::size_t o_k1 = 0, o_k2 = o_k1 + up(stride * sizeof(aria_keypoint)), o_m = o_k2 + up(stride * sizeof(aria_keypoint)),
-                      o_cnt = o_m + up(n * sizeof(aria_match)), o_pose = o_cnt + 256, o_corr = o_pose + 256,
-                      o_back = o_corr + up(n * sizeof(aria_sim3_corr)), o_out = o_back + up(n * sizeof(int)), o_mask = o_out + 256,
-                      total = o_mask + up(n);
-    int rc;
-    void* st = aria_sim3_stream(h_);
-    if (total > d_cap_) {
-        if ((rc = aria_stream_synchronize(device_, st)) != ARIA_OK) fail("aria_stream_synchronize", rc);
-        if (d_buf_) aria_device_free(device_, d_buf_);
-        d_buf_ = nullptr;
-        d_cap_ = 0;
-        if ((rc = aria_device_alloc(device_, total, &d_buf_)) != ARIA_OK) fail("aria_device_alloc", rc);
-        d_cap_ = total;
-    }
-    char* d = static_cast<char*>(d_buf_);
     const int counts[6] = {(int)n1, (int)n2, (int)n, 0, kf1.anchor_pair, kf2.anchor_pair};
     double poses[24];
     for (int k = 0; k < 12; k++) {
         poses[k] = kf1.pose[(size_t)k];
         poses[12 + k] = kf2.pose[(size_t)k];
     }
-    if ((rc = aria_copy_h2d_async(device_, st, d + o_k1, kf1.frame->keypoints.data(), n1 * sizeof(aria_keypoint))) != ARIA_OK ||
-        (rc = aria_copy_h2d_async(device_, st, d + o_k2, kf2.frame->keypoints.data(), n2 * sizeof(aria_keypoint))) != ARIA_OK ||
-        (rc = aria_copy_h2d_async(device_, st, d + o_m, matches.data(), n * sizeof(aria_match))) != ARIA_OK ||
-        (rc = aria_copy_h2d_async(device_, st, d + o_cnt, counts, sizeof(counts))) != ARIA_OK ||
-        (rc = aria_copy_h2d_async(device_, st, d + o_pose, poses, sizeof(poses))) != ARIA_OK)
-        fail("aria_copy_h2d_async", rc);
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_k1, kf1.frame->keypoints.data(), n1 * sizeof(aria_keypoint)));
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_k2, kf2.frame->keypoints.data(), n2 * sizeof(aria_keypoint)));
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_m, matches.data(), n * sizeof(aria_match)));
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_cnt, counts, sizeof(counts)));
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d + o_pose, poses, sizeof(poses)));
     int* d_cnt = reinterpret_cast<int*>(d + o_cnt);
     const double* d_pose = reinterpret_cast<const double*>(d + o_pose);
-    rc = aria_sim3_associate_batch_device(h_, map, d_cnt + 4, d_cnt + 5, kf1.anchor_view, kf2.anchor_view, d_pose, d_pose + 12,
-                                          reinterpret_cast<const aria_keypoint*>(d + o_k1), d_cnt,
-                                          reinterpret_cast<const aria_keypoint*>(d + o_k2), d_cnt + 1, (std::int64_t)stride,
-                                          reinterpret_cast<const aria_match*>(d + o_m), d_cnt + 2, 1, (int)n,
-                                          reinterpret_cast<aria_sim3_corr*>(d + o_corr), d_cnt + 3, reinterpret_cast<int*>(d + o_back));
-    if (rc != ARIA_OK) fail("aria_sim3_associate_batch_device", rc);
-    rc = aria_sim3_estimate_batch_device(h_, reinterpret_cast<const aria_sim3_corr*>(d + o_corr), d_cnt + 3, 1, (int)n, pair_id,
-                                         reinterpret_cast<aria_sim3_result*>(d + o_out), reinterpret_cast<std::uint8_t*>(d + o_mask));
-    if (rc != ARIA_OK) fail("aria_sim3_estimate_batch_device", rc);
+    expect("aria_sim3_associate_batch_device",
+           aria_sim3_associate_batch_device(h_.get(), map, d_cnt + 4, d_cnt + 5, kf1.anchor_view, kf2.anchor_view, d_pose, d_pose + 12,
+                                            reinterpret_cast<const aria_keypoint*>(d + o_k1), d_cnt,
+                                            reinterpret_cast<const aria_keypoint*>(d + o_k2), d_cnt + 1, (std::int64_t)stride,
+                                            reinterpret_cast<const aria_match*>(d + o_m), d_cnt + 2, 1, (int)n,
+                                            reinterpret_cast<aria_sim3_corr*>(d + o_corr), d_cnt + 3, reinterpret_cast<int*>(d + o_back)));
+    expect("aria_sim3_estimate_batch_device",
+           aria_sim3_estimate_batch_device(h_.get(), reinterpret_cast<const aria_sim3_corr*>(d + o_corr), d_cnt + 3, 1, (int)n, pair_id,
+                                           reinterpret_cast<aria_sim3_result*>(d + o_out), reinterpret_cast<std::uint8_t*>(d + o_mask)));
     aria_sim3_result r{};
     int found = 0;
     std::vector<std::uint8_t> mask(n);
     std::vector<int> back(n);
-    if ((rc = aria_copy_d2h_async(device_, st, &r, d + o_out, sizeof(r))) != ARIA_OK ||
-        (rc = aria_copy_d2h_async(device_, st, &found, d_cnt + 3, sizeof(int))) != ARIA_OK ||
-        (rc = aria_copy_d2h_async(device_, st, mask.data(), d + o_mask, n)) != ARIA_OK ||
-        (rc = aria_copy_d2h_async(device_, st, back.data(), d + o_back, n * sizeof(int))) != ARIA_OK)
-        fail("aria_copy_d2h_async", rc);
-    if ((rc = aria_sim3_check(h_)) != ARIA_OK) fail("aria_sim3_check", rc);   // synchronises the stream
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, &r, d + o_out, sizeof(r)));
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, &found, d_cnt + 3, sizeof(int)));
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, mask.data(), d + o_mask, n));
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, back.data(), d + o_back, n * sizeof(int)));
+    expect("aria_sim3_check", aria_sim3_check(h_.get()));   // synchronises the stream
     if (n_corr) *n_corr = found;
     if (match_index) match_index->assign(back.begin(), back.begin() + found);
     if (!r.valid) return std::nullopt;

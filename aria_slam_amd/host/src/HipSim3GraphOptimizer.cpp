@@ -60,14 +60,7 @@ HipSim3GraphOptimizer::HipSim3GraphOptimizer(bool fix_scale, int pcg_max_iters, 
     cfg_.max_edges = 0;
 }
 
-HipSim3GraphOptimizer::~HipSim3GraphOptimizer() { aria_sgraph_destroy(h_); }
-
-void HipSim3GraphOptimizer::fail(const char* where, int status) {
-    std::string msg = std::string("HipSim3GraphOptimizer: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
+HipSim3GraphOptimizer::~HipSim3GraphOptimizer() = default;
 
 void HipSim3GraphOptimizer::setInitialPose(int id, const GraphPose& pose) {
     const aria_sgraph_vertex v = vertexOf(pose);
@@ -103,13 +96,11 @@ void HipSim3GraphOptimizer::addLoopEdge(int from_id, int to_id, const GraphPose&
 }
 
 void HipSim3GraphOptimizer::ensureHandle(int nv, int ne) {
-    if (h_ && nv <= cfg_.max_vertices && ne <= cfg_.max_edges) return;
-    aria_sgraph_destroy(h_);
-    h_ = nullptr;
+    if (h_.get() && nv <= cfg_.max_vertices && ne <= cfg_.max_edges) return;
+    h_.reset();
     cfg_.max_vertices = std::max(std::max(nv, 2 * cfg_.max_vertices), 256);
     cfg_.max_edges = std::max(std::max(ne, 2 * cfg_.max_edges), 256);
-    const int rc = aria_sgraph_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_sgraph_create", rc);
+    expect("aria_sgraph_create", aria_sgraph_create(&cfg_, h_.out()));
 }
 
 void HipSim3GraphOptimizer::optimize(int iterations) {
@@ -117,8 +108,7 @@ void HipSim3GraphOptimizer::optimize(int iterations) {
     if (nv == 0) return;
     ensureHandle(nv, ne);
     before_ = verts_;
-    const int rc = aria_sgraph_optimize(h_, verts_.data(), nv, 0, edges_.data(), ne, iterations, &last_);
-    if (rc != ARIA_OK) fail("aria_sgraph_optimize", rc);
+    expect("aria_sgraph_optimize", aria_sgraph_optimize(h_.get(), verts_.data(), nv, 0, edges_.data(), ne, iterations, &last_));
 }
 
 GraphPose HipSim3GraphOptimizer::getOptimizedPose(int id) const {
@@ -163,7 +153,7 @@ aria_sgraph_correct_stats HipSim3GraphOptimizer::correctMap(aria_map_t map, cons
         if (pair_anchor_id[(std::size_t)k] >= 0 && it != index_.end()) table[(std::size_t)k] = it->second;
     }
     const int dev = cfg_.device;
-    void* st = aria_sgraph_stream(h_);
+    void* st = aria_sgraph_stream(h_.get());
     const std::size_t vbytes = sizeof(aria_sgraph_vertex) * (std::size_t)nv;
     DeviceBlock d_table(dev, sizeof(int) * (std::size_t)nt), d_old(dev, vbytes), d_new(dev, vbytes), d_stats(dev, sizeof(stats));
     if (!d_table.p || !d_old.p || !d_new.p || !d_stats.p) fail("aria_device_alloc", ARIA_E_OOM);
@@ -171,14 +161,12 @@ aria_sgraph_correct_stats HipSim3GraphOptimizer::correctMap(aria_map_t map, cons
     if (nt) rc = aria_copy_h2d_async(dev, st, d_table.p, table.data(), sizeof(int) * (std::size_t)nt);
     if (rc == ARIA_OK && nv) rc = aria_copy_h2d_async(dev, st, d_old.p, before_.data(), vbytes);
     if (rc == ARIA_OK && nv) rc = aria_copy_h2d_async(dev, st, d_new.p, verts_.data(), vbytes);
-    if (rc != ARIA_OK) fail("aria_copy_h2d_async", rc);
-    rc = aria_sgraph_correct_map_device(h_, map, (const int*)d_table.p, nt, pair_base, (const aria_sgraph_vertex*)d_old.p,
-                                        (const aria_sgraph_vertex*)d_new.p, nv, (aria_sgraph_correct_stats*)d_stats.p);
-    if (rc != ARIA_OK) fail("aria_sgraph_correct_map_device", rc);
-    rc = aria_copy_d2h_async(dev, st, &stats, d_stats.p, sizeof(stats));
-    if (rc != ARIA_OK) fail("aria_copy_d2h_async", rc);
-    rc = aria_sgraph_check(h_);              // synchronises the stream: the copies and the kernel have run
-    if (rc != ARIA_OK) fail("aria_sgraph_correct_map_device", rc);
+    expect("aria_copy_h2d_async", rc);
+    expect("aria_sgraph_correct_map_device",
+           aria_sgraph_correct_map_device(h_.get(), map, (const int*)d_table.p, nt, pair_base, (const aria_sgraph_vertex*)d_old.p,
+                                          (const aria_sgraph_vertex*)d_new.p, nv, (aria_sgraph_correct_stats*)d_stats.p));
+    expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, &stats, d_stats.p, sizeof(stats)));
+    expect("aria_sgraph_correct_map_device", aria_sgraph_check(h_.get()));   // synchronises: the copies and the kernel have run
     return stats;
 }
 

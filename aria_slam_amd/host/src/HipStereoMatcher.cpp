@@ -9,13 +9,6 @@ namespace aria::adapters::hip {
 
 static_assert(sizeof(core::KeyPoint) == sizeof(aria_keypoint) && sizeof(core::Match) == sizeof(aria_match), "layouts");
 
-void HipStereoMatcher::fail(const char* where, int status) {
-    std::string msg = std::string("HipStereoMatcher: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 float StereoObservations::medianDepth() const {
     std::vector<float> d;
     for (const aria_stereo_obs& o : obs)
@@ -41,11 +34,10 @@ HipStereoMatcher::HipStereoMatcher(const StereoConfig& cfg) {
     c.min_scale_matches = cfg.min_scale_matches;
     c.band_factor = cfg.band_factor;
     c.median_factor = cfg.median_factor;
-    const int rc = aria_stereo_create(&c, &h_);
-    if (rc != ARIA_OK) fail("aria_stereo_create", rc);
+    expect("aria_stereo_create", aria_stereo_create(&c, h_.out()));
 }
 
-HipStereoMatcher::~HipStereoMatcher() { aria_stereo_destroy(h_); }
+HipStereoMatcher::~HipStereoMatcher() = default;
 
 StereoObservations HipStereoMatcher::match(const std::uint8_t* image_left, const std::uint8_t* image_right, int width, int height,
                                            const core::Frame& left, const core::Frame& right) {
@@ -54,11 +46,11 @@ StereoObservations HipStereoMatcher::match(const std::uint8_t* image_left, const
     out.obs.resize((size_t)nl);
     out.matches.resize((size_t)nl);
     int n = 0;
-    const int rc = aria_stereo_match(h_, image_left, image_right, width, height, width,
-                                     reinterpret_cast<const aria_keypoint*>(left.keypoints.data()), left.descriptors.data(), nl,
-                                     reinterpret_cast<const aria_keypoint*>(right.keypoints.data()), right.descriptors.data(), nr,
-                                     out.obs.data(), reinterpret_cast<aria_match*>(out.matches.data()), &n);
-    if (rc != ARIA_OK) fail("aria_stereo_match", rc);
+    expect("aria_stereo_match",
+           aria_stereo_match(h_.get(), image_left, image_right, width, height, width,
+                             reinterpret_cast<const aria_keypoint*>(left.keypoints.data()), left.descriptors.data(), nl,
+                             reinterpret_cast<const aria_keypoint*>(right.keypoints.data()), right.descriptors.data(), nr,
+                             out.obs.data(), reinterpret_cast<aria_match*>(out.matches.data()), &n));
     out.matches.resize((size_t)n);
     return out;
 }
@@ -76,11 +68,11 @@ aria_stereo_scale HipStereoMatcher::scale(const TwoViewPose& pose, const std::ve
     r.valid = 1;
     aria_stereo_scale out{};
     const bool masked = !matches.empty() && pose.mask.size() == matches.size();
-    const int rc = aria_stereo_scale_pose(h_, &r, masked ? pose.mask.data() : nullptr,
-                                          reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(),
-                                          query_is_first ? 1 : 0, obs_query.data(), (int)obs_query.size(), obs_train.data(),
-                                          (int)obs_train.size(), &out);
-    if (rc != ARIA_OK) fail("aria_stereo_scale_pose", rc);
+    expect("aria_stereo_scale_pose",
+           aria_stereo_scale_pose(h_.get(), &r, masked ? pose.mask.data() : nullptr,
+                                  reinterpret_cast<const aria_match*>(matches.data()), (int)matches.size(),
+                                  query_is_first ? 1 : 0, obs_query.data(), (int)obs_query.size(), obs_train.data(),
+                                  (int)obs_train.size(), &out));
     return out;
 }
 

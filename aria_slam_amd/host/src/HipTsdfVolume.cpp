@@ -8,13 +8,6 @@
 
 namespace aria::adapters::hip {
 
-void HipTsdfVolume::fail(const char* where, int status) {
-    std::string msg = std::string("HipTsdfVolume: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 void TsdfVolumeConfig::centreOn(float x, float y, float z) {
     origin[0] = x - 0.5f * (float)nx * voxel;
     origin[1] = y - 0.5f * (float)ny * voxel;
@@ -31,38 +24,36 @@ HipTsdfVolume::HipTsdfVolume(const TsdfVolumeConfig& cfg) {
     cfg_.min_depth = cfg.min_depth; cfg_.max_depth = cfg.max_depth;
     cfg_.max_weight = cfg.max_weight; cfg_.min_weight = cfg.min_weight;
     cfg_.fx = cfg.K.fx; cfg_.fy = cfg.K.fy; cfg_.cx = cfg.K.cx; cfg_.cy = cfg.K.cy;
-    const int rc = aria_tsdf_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_tsdf_create", rc);
+    expect("aria_tsdf_create", aria_tsdf_create(&cfg_, h_.out()));
 }
 
-HipTsdfVolume::~HipTsdfVolume() { aria_tsdf_destroy(h_); }
+HipTsdfVolume::~HipTsdfVolume() = default;
 
 bool HipTsdfVolume::integrate(const float* depth, int width, int height, const double* extrinsics, const std::uint8_t* image) {
-    const int rc = aria_tsdf_integrate(h_, depth, width, height, width, extrinsics, image, width);
+    const int rc = aria_tsdf_integrate(h_.get(), depth, width, height, width, extrinsics, image, width);
     if (rc == ARIA_E_INVALID && depth && extrinsics) {
         for (int k = 0; k < 12; k++)
             if (!(extrinsics[k] - extrinsics[k] == 0.0)) return false;          // NaN or Inf: the frame was refused
     }
-    if (rc != ARIA_OK) fail("aria_tsdf_integrate", rc);
+    expect("aria_tsdf_integrate", rc);
     return true;
 }
 
 void HipTsdfVolume::integrateBatchDevice(const float* d_depth, std::int64_t depth_stride, int depth_pitch, int width, int height,
                                          const double* d_extrinsics, const std::uint8_t* d_frame_mask, const std::uint8_t* d_image,
                                          std::int64_t image_stride, int image_pitch, int n_frames) {
-    const int rc = aria_tsdf_integrate_batch_device(h_, d_depth, depth_stride, depth_pitch, width, height, d_extrinsics, d_frame_mask,
-                                                    d_image, image_stride, image_pitch, n_frames);
-    if (rc != ARIA_OK) fail("aria_tsdf_integrate_batch_device", rc);
+    expect("aria_tsdf_integrate_batch_device",
+           aria_tsdf_integrate_batch_device(h_.get(), d_depth, depth_stride, depth_pitch, width, height, d_extrinsics, d_frame_mask,
+                                            d_image, image_stride, image_pitch, n_frames));
 }
 
 void HipTsdfVolume::clear() {
-    const int rc = aria_tsdf_clear(h_);
-    if (rc != ARIA_OK) fail("aria_tsdf_clear", rc);
+    expect("aria_tsdf_clear", aria_tsdf_clear(h_.get()));
 }
 
 std::int64_t HipTsdfVolume::countPoints() {
     std::int64_t total = 0;
-    const int rc = aria_tsdf_extract_points(h_, nullptr, 0, &total);
+    const int rc = aria_tsdf_extract_points(h_.get(), nullptr, 0, &total);
     if (rc != ARIA_OK && rc != ARIA_E_OUTPUT_TOO_SMALL) fail("aria_tsdf_extract_points", rc);
     return total;
 }
@@ -71,16 +62,14 @@ std::vector<aria_tsdf_point> HipTsdfVolume::extractPoints() {
     std::vector<aria_tsdf_point> pts((std::size_t)countPoints());
     if (pts.empty()) return pts;
     std::int64_t total = 0;
-    const int rc = aria_tsdf_extract_points(h_, pts.data(), (std::int64_t)pts.size(), &total);
-    if (rc != ARIA_OK) fail("aria_tsdf_extract_points", rc);
+    expect("aria_tsdf_extract_points", aria_tsdf_extract_points(h_.get(), pts.data(), (std::int64_t)pts.size(), &total));
     return pts;
 }
 
 std::vector<aria_tsdf_voxel> HipTsdfVolume::readBox(int i0, int j0, int k0, int ni, int nj, int nk) {
     if (ni < 1 || nj < 1 || nk < 1) fail("aria_tsdf_read_box", ARIA_E_INVALID);
     std::vector<aria_tsdf_voxel> out((std::size_t)ni * (std::size_t)nj * (std::size_t)nk);
-    const int rc = aria_tsdf_read_box(h_, i0, j0, k0, ni, nj, nk, out.data());
-    if (rc != ARIA_OK) fail("aria_tsdf_read_box", rc);
+    expect("aria_tsdf_read_box", aria_tsdf_read_box(h_.get(), i0, j0, k0, ni, nj, nk, out.data()));
     return out;
 }
 

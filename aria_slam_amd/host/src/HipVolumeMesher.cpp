@@ -6,13 +6,6 @@
 
 namespace aria::adapters::hip {
 
-void HipVolumeMesher::fail(const char* where, int status) {
-    std::string msg = std::string("HipVolumeMesher: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 VolumeMesherConfig VolumeMesherConfig::fromVolume(const HipTsdfVolume& volume) {
     const aria_tsdf_config& v = volume.config();
     VolumeMesherConfig c;
@@ -32,11 +25,10 @@ HipVolumeMesher::HipVolumeMesher(const VolumeMesherConfig& cfg) {
     cfg_.min_weight = cfg.min_weight;
     cfg_.voxel = cfg.voxel;
     for (int a = 0; a < 3; a++) cfg_.origin[a] = cfg.origin[a];
-    const int rc = aria_mesh_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_mesh_create", rc);
+    expect("aria_mesh_create", aria_mesh_create(&cfg_, h_.out()));
 }
 
-HipVolumeMesher::~HipVolumeMesher() { aria_mesh_destroy(h_); }
+HipVolumeMesher::~HipVolumeMesher() = default;
 
 void HipVolumeMesher::update(HipTsdfVolume& volume) {
     const aria_tsdf_config& v = volume.config();
@@ -44,15 +36,14 @@ void HipVolumeMesher::update(HipTsdfVolume& volume) {
     for (int a = 0; a < 3; a++) same = same && v.origin[a] == cfg_.origin[a];
     if (!same) fail("update: the volume has another geometry (dims, voxel or origin)", ARIA_E_INVALID);
     // its stream is not this handle's: drain it. The check reports the volume's deferred error once, so it must not be dropped.
-    const int vrc = volume.check();
-    if (vrc != ARIA_OK) fail("update: the volume reports a deferred error", vrc);
-    const int rc = aria_mesh_update_from_volume_device(h_, aria_tsdf_device_voxels(volume.handle()));
-    if (rc != ARIA_OK) fail("aria_mesh_update_from_volume_device", rc);
+    expect("update: the volume reports a deferred error", volume.check());
+    expect("aria_mesh_update_from_volume_device",
+           aria_mesh_update_from_volume_device(h_.get(), aria_tsdf_device_voxels(volume.handle())));
 }
 
 std::pair<std::int64_t, std::int64_t> HipVolumeMesher::count() {
     std::int64_t n[2] = {0, 0};
-    const int rc = aria_mesh_extract(h_, nullptr, 0, nullptr, 0, n);
+    const int rc = aria_mesh_extract(h_.get(), nullptr, 0, nullptr, 0, n);
     if (rc != ARIA_OK && rc != ARIA_E_OUTPUT_TOO_SMALL) fail("aria_mesh_extract", rc);
     return {n[0], n[1]};
 }
@@ -63,16 +54,15 @@ VolumeMesh HipVolumeMesher::extract() {
     m.vertices.resize((std::size_t)n.first);
     m.triangles.resize((std::size_t)n.second);
     std::int64_t got[2] = {0, 0};
-    const int rc = aria_mesh_extract(h_, m.vertices.empty() ? nullptr : m.vertices.data(), n.first,
-                                     m.triangles.empty() ? nullptr : m.triangles.data(), n.second, got);
-    if (rc != ARIA_OK) fail("aria_mesh_extract", rc);
+    expect("aria_mesh_extract",
+           aria_mesh_extract(h_.get(), m.vertices.empty() ? nullptr : m.vertices.data(), n.first,
+                             m.triangles.empty() ? nullptr : m.triangles.data(), n.second, got));
     return m;
 }
 
 void HipVolumeMesher::extractDevice(aria_mesh_vertex* d_vertices, std::int64_t vcap, aria_mesh_triangle* d_triangles, std::int64_t tcap,
                                     std::int64_t* d_counts) {
-    const int rc = aria_mesh_extract_device(h_, d_vertices, vcap, d_triangles, tcap, d_counts);
-    if (rc != ARIA_OK) fail("aria_mesh_extract_device", rc);
+    expect("aria_mesh_extract_device", aria_mesh_extract_device(h_.get(), d_vertices, vcap, d_triangles, tcap, d_counts));
 }
 
 std::pair<std::size_t, std::size_t> HipVolumeMesher::exportPLY(const std::string& filename) {

@@ -7,13 +7,6 @@
 
 namespace aria::adapters::hip {
 
-void HipVolumeRenderer::fail(const char* where, int status) {
-    std::string msg = std::string("HipVolumeRenderer: ") + where + ": " + aria_status_string(status);
-    const char* hip = aria_last_hip_error();
-    if (hip && hip[0]) msg += std::string(" [") + hip + "]";
-    throw std::runtime_error(msg);
-}
-
 VolumeRendererConfig VolumeRendererConfig::fromVolume(const HipTsdfVolume& volume) {
     const aria_tsdf_config& v = volume.config();
     VolumeRendererConfig c;
@@ -44,11 +37,10 @@ HipVolumeRenderer::HipVolumeRenderer(const VolumeRendererConfig& cfg) {
     for (int a = 0; a < 3; a++) cfg_.origin[a] = cfg.origin[a];
     cfg_.near = cfg.near_z; cfg_.far = cfg.far_z; cfg_.step = cfg.step;
     cfg_.fx = cfg.K.fx; cfg_.fy = cfg.K.fy; cfg_.cx = cfg.K.cx; cfg_.cy = cfg.K.cy;
-    const int rc = aria_ray_create(&cfg_, &h_);
-    if (rc != ARIA_OK) fail("aria_ray_create", rc);
+    expect("aria_ray_create", aria_ray_create(&cfg_, h_.out()));
 }
 
-HipVolumeRenderer::~HipVolumeRenderer() { aria_ray_destroy(h_); }
+HipVolumeRenderer::~HipVolumeRenderer() = default;
 
 void HipVolumeRenderer::update(HipTsdfVolume& volume) {
     const aria_tsdf_config& v = volume.config();
@@ -56,10 +48,9 @@ void HipVolumeRenderer::update(HipTsdfVolume& volume) {
     for (int a = 0; a < 3; a++) same = same && v.origin[a] == cfg_.origin[a];
     if (!same) fail("update: the volume has another geometry (dims, voxel or origin)", ARIA_E_INVALID);
     // its stream is not this handle's: drain it. The check reports the volume's deferred error once, so it must not be dropped.
-    const int vrc = volume.check();
-    if (vrc != ARIA_OK) fail("update: the volume reports a deferred error", vrc);
-    const int rc = aria_ray_update_from_volume_device(h_, aria_tsdf_device_voxels(volume.handle()));
-    if (rc != ARIA_OK) fail("aria_ray_update_from_volume_device", rc);
+    expect("update: the volume reports a deferred error", volume.check());
+    expect("aria_ray_update_from_volume_device",
+           aria_ray_update_from_volume_device(h_.get(), aria_tsdf_device_voxels(volume.handle())));
 }
 
 void HipVolumeRenderer::castBatchDevice(const double* d_extrinsics, const std::uint8_t* d_view_mask, int n_views, int width, int height,
@@ -67,10 +58,10 @@ void HipVolumeRenderer::castBatchDevice(const double* d_extrinsics, const std::u
                                         std::int64_t normal_stride, int normal_pitch, std::uint8_t* d_gray, std::int64_t gray_stride,
                                         int gray_pitch, std::uint8_t* d_shade, std::int64_t shade_stride, int shade_pitch,
                                         aria_ray_view* d_views) {
-    const int rc = aria_ray_cast_batch_device(h_, d_extrinsics, d_view_mask, n_views, width, height, d_depth, depth_stride, depth_pitch,
-                                              d_normal, normal_stride, normal_pitch, d_gray, gray_stride, gray_pitch, d_shade, shade_stride,
-                                              shade_pitch, d_views);
-    if (rc != ARIA_OK) fail("aria_ray_cast_batch_device", rc);
+    expect("aria_ray_cast_batch_device",
+           aria_ray_cast_batch_device(h_.get(), d_extrinsics, d_view_mask, n_views, width, height, d_depth, depth_stride, depth_pitch,
+                                      d_normal, normal_stride, normal_pitch, d_gray, gray_stride, gray_pitch, d_shade, shade_stride,
+                                      shade_pitch, d_views));
 }
 
 namespace {
@@ -99,28 +90,26 @@ RenderedViews HipVolumeRenderer::castBatch(const std::vector<std::array<double, 
     if (n == 0) return out;
     if (width < 1 || height < 1) fail("castBatch", ARIA_E_INVALID);
     const std::size_t px = (std::size_t)width * height, all = px * n;
-    void* const st = aria_ray_stream(h_);
+    void* const st = aria_ray_stream(h_.get());
     const int dev = cfg_.device;
     DeviceBlock d_ext(dev, sizeof(double) * 12 * n), d_views(dev, sizeof(aria_ray_view) * n);
     DeviceBlock d_depth(dev, (planes & ARIA_RAY_DEPTH) ? all * 4 : 0), d_normal(dev, (planes & ARIA_RAY_NORMAL) ? all * 12 : 0);
     DeviceBlock d_gray(dev, (planes & ARIA_RAY_GRAY) ? all : 0), d_shade(dev, (planes & ARIA_RAY_SHADE) ? all : 0);
-    int rc = aria_copy_h2d_async(dev, st, d_ext.p, extrinsics.data(), sizeof(double) * 12 * n);
-    if (rc != ARIA_OK) fail("aria_copy_h2d_async", rc);
+    expect("aria_copy_h2d_async", aria_copy_h2d_async(dev, st, d_ext.p, extrinsics.data(), sizeof(double) * 12 * n));
     castBatchDevice((const double*)d_ext.p, nullptr, n, width, height, (float*)d_depth.p, (std::int64_t)px, width, (float*)d_normal.p,
                     (std::int64_t)(3 * px), width, (std::uint8_t*)d_gray.p, (std::int64_t)px, width, (std::uint8_t*)d_shade.p, (std::int64_t)px,
                     width, (aria_ray_view*)d_views.p);
     auto back = [&](auto& v, const DeviceBlock& d, std::size_t count) {
         if (!d.p) return;
         v.resize(count);
-        const int e = aria_copy_d2h_async(dev, st, v.data(), d.p, count * sizeof(v[0]));
-        if (e != ARIA_OK) fail("aria_copy_d2h_async", e);
+        expect("aria_copy_d2h_async", aria_copy_d2h_async(dev, st, v.data(), d.p, count * sizeof(v[0])));
     };
     back(out.depth, d_depth, all);
     back(out.normal, d_normal, 3 * all);
     back(out.gray, d_gray, all);
     back(out.shade, d_shade, all);
     back(out.views, d_views, (std::size_t)n);
-    rc = check();                                                      // synchronises: the copies have landed
+    const int rc = check();                                                    // synchronises: the copies have landed
     if (rc == ARIA_E_INVALID) out.invalid = true;
     else if (rc != ARIA_OK) fail("aria_ray_check", rc);
     return out;

@@ -54,6 +54,23 @@ def test_shard_partition_equals_the_python_rule(selftest):
             assert cover == list(range(n))
 
 
+def test_stage_skeleton_message_ownership_and_scratch():
+    """aria_hip/detail/Stage.hpp against stubs of the C-ABI that log their calls (tests/cpp/stage_skeleton_selftest.cpp): the
+    exception text, the handle destroyed before the scratch buffer, one destroy after a constructor that throws, and
+    DeviceScratch::reserve's sequence. Its own program, built with the address and undefined-behaviour sanitizers."""
+    src = os.path.join(ROOT, "tests", "cpp", "stage_skeleton_selftest.cpp")
+    hdr = os.path.join(PKG, "host", "include", "aria_hip", "detail", "Stage.hpp")
+    out_dir = os.path.join(ROOT, "build", "selftest")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "stage_skeleton_selftest")
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
+                               "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"),
+                               "-I" + os.path.join(PKG, "host", "include"), src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and out.stdout.strip() == "OK stage_skeleton", out.stdout + out.stderr
+
+
 @pytest.mark.gpu
 def test_adapters_equal_python_binding_and_reference_conventions(aria, selftest):
     out = subprocess.run([selftest, "gpu"], capture_output=True, text=True, timeout=300)
