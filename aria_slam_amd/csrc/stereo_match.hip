@@ -73,6 +73,7 @@ __device__ __forceinline__ float level_scale(const StereoParams& prm, int o) {
 
 __device__ __forceinline__ int row_key(float y, int H) { return (int)fminf(fmaxf(floorf(y), 0.0f), (float)(H - 1)); }
 
+// ---- pure helpers: plain C++ of one lane, compiled for the host by tests/cpp/stereo_helpers_selftest.cpp ----
 __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
     uint32_t v;
     __builtin_memcpy(&v, p, 4);
@@ -129,6 +130,7 @@ __device__ __forceinline__ int hist_select(const int* hist, int& k) {
     k -= cum;
     return b;
 }
+// ---- end of the pure helpers ----
 
 __global__ __launch_bounds__(ST_BLOCK) void k_stereo_match(
     const uint8_t* __restrict__ img_l, const uint8_t* __restrict__ img_r, int64_t img_stride, int W, int H, int pitch,
@@ -363,6 +365,7 @@ __global__ __launch_bounds__(ST_BLOCK) void k_stereo_match(
     if (tid == 0) nmatches[p] = run;
 }
 
+// ---- pure helpers of the scale ----
 // fp64 -> a 64-bit key whose unsigned order is the numeric order, and back
 __device__ __forceinline__ unsigned long long order_key(double x) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(x);
@@ -372,6 +375,7 @@ __device__ __forceinline__ double key_value(unsigned long long k) {
     const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
     return __longlong_as_double((long long)b);
 }
+// ---- end of the pure helpers of the scale ----
 
 __global__ __launch_bounds__(ST_BLOCK) void k_stereo_scale(
     const aria_pose_result* __restrict__ pose, const uint8_t* __restrict__ mask, const aria_match* __restrict__ matches,

@@ -164,9 +164,10 @@ def test_window_and_slide_sizes(aria, torch_cuda, work, scene, w, L):
     try:
         obs, m, nm, status = _run_match(aria, torch_cuda, work, st, *scene["dev"])
         assert status == 0
-        want = R.stereo_match_ref(*scene["host"][0], sad_half_window=w, sad_slide=L)
-        _assert_pair_equal("w=%d L=%d" % (w, L), obs[0], m[0], nm[0], *want)
-        assert nm[0] > 100
+        for p in range(3):
+            want = R.stereo_match_ref(*scene["host"][p], sad_half_window=w, sad_slide=L)
+            _assert_pair_equal("w=%d L=%d pair %d" % (w, L, p), obs[p], m[p], nm[p], *want)
+        assert nm[0] > 100 and nm[1] > 100 and nm[2] == 0
     finally:
         st.close()
 
