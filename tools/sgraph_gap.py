@@ -4,11 +4,18 @@
             out below, because graph_ref's quaternion helpers return fp64): chi2 relative, b, H_diag and H_off each as
             max |difference| / max |entry|. tests/test_gpu_sgraph.py allows the device's debug_linearize ten times each.
   GAPS      for every case and every iteration count k up to the case's: the largest absolute difference of any vertex entry and
-            the relative differences of lambda and chi2_final between sgraph_ref.optimize(solver="direct") and (solver="pcg");
-            the device is allowed ten times each against the direct solve.
-  MIN_RHO   the smallest |rho| of any trial and the smallest ratio |rho| / |rho_direct - rho_pcg|.
+            the relative differences of lambda and chi2_final between the pcg run of sgraph_ref.optimize and the case's other
+            run (sgraph_cases.other): solver="direct", against which the device is allowed ten times each; for a case whose
+            pcg_max_iters cuts the solver short, the same capped pcg run with the edge list reversed (another summation order of
+            the same sums), and the device is allowed ten times each against the capped pcg run. The two cases without a margin
+            on rho (rho is 0, and NaN, by construction) have no gap: they are compared exactly.
+  MIN_RHO   the smallest |rho| of any trial and the smallest ratio |rho| / |difference of that rho between the two runs|.
   FIX_SCALE_GAP  sgraph_ref.optimize(fix_scale) against graph_ref.optimize on one SE(3) graph, both with pcg.
-Usage: tools/sgraph_gap.py"""
+--search: over seeds and noise levels of random_sgraph(seed, 30, 8, noise) at SEARCH_ITERATIONS iterations, every graph with a
+rejection after an accept: its pattern under both solvers, the smallest |rho|, the direct-vs-pcg margin, the numbers of accepts
+before its rejections, the longest run of rejections and whether an accept is clamped. The rejecting cases of the table came
+from it.
+Usage: tools/sgraph_gap.py [--search [first_seed last_seed]]"""
 import os
 import sys
 
@@ -101,7 +108,47 @@ def fix_scale_gap():
     return float(np.abs(S.poses_of(Vo) - P).max())
 
 
+SEARCH_ITERATIONS = 6
+SEARCH_NOISE = (0.5, 1.0, 2.0, 3.0)
+# The two solves of one trial differ by what the solver's stopping rule leaves, 1e-8 of |b|, and so does any third solve of it;
+# the device's is one (its PCG stops an iteration or two from the restatement's). A gap is that difference sampled once. Where
+# the gap of one iteration count lies this many times below the same figure at the other counts, the two samples cancelled
+# there: ten times it bounds nothing but that accident. --search marks such graphs, and the accepting cases are taken from
+# the others. (A case whose every trial before the first accept is rejected meets the device at large lambda, where all three
+# solves agree to rounding: its small gaps are real.)
+MAX_SPREAD = 30.0
+
+
+def search(first=100, last=130):
+    from aria_slam_amd import sgraph_ref as S
+    print("seed noise  pattern (direct == pcg)   min |rho|  margin   accepts before rejections, longest run, clamped / unclamped "
+          "accepts, spread of the vertex, lambda, chi2 gaps over k")
+    for seed in range(first, last):
+        for noise in SEARCH_NOISE:
+            V, E = S.random_sgraph(seed, 30, 8, noise)
+            runs = {s: [S.optimize(V, E, 0, k, s) for k in range(1, SEARCH_ITERATIONS + 1)] for s in ("direct", "pcg")}
+            rd, rp = runs["direct"][-1][1], runs["pcg"][-1][1]
+            pat = SC.pattern(rp)
+            if SC.pattern(rd) != pat or "Ar" not in pat:
+                continue
+            d, p = np.array([t["rho"] for t in rd["trace"]]), np.array([t["rho"] for t in rp["trace"]])
+            lo = np.minimum(np.abs(d), np.abs(p))
+            margin = (lo / np.maximum(np.abs(d - p), 1e-300)).min()
+            before, run = SC.accepts_before_rejections(pat)
+            acc = [t["rho"] for t in rp["trace"] if t["accepted"]]
+            gaps = np.array([(np.abs(Vp - Vd).max(), SC.rel(b["lambda_"], a["lambda_"]), SC.rel(b["chi2_final"], a["chi2_final"]))
+                             for (Vd, a), (Vp, b) in zip(runs["direct"], runs["pcg"])])
+            spread = gaps.max(0) / np.maximum(gaps.min(0), 1e-300)
+            notes = ("" if lo.min() >= SC.RHO_MIN and margin >= SC.RHO_MARGIN else "   (margin too small)") + \
+                    ("" if spread.max() <= MAX_SPREAD else "   (a gap is small by accident)")
+            print("%4d  %.1f  %-24s %.3f  %8.3g  %s %d  %d / %d  %.0f %.0f %.0f%s" % (
+                seed, noise, pat, lo.min(), margin, before, run, sum(r >= SC.CLAMP_RHO for r in acc),
+                sum(r < SC.CLAMP_RHO for r in acc), spread[0], spread[1], spread[2], notes), flush=True)
+
+
 def main():
+    if "--search" in sys.argv:
+        return search(*[int(a) for a in sys.argv[sys.argv.index("--search") + 1:][:2]])
     if np.finfo(LD).eps >= np.finfo(np.float64).eps:
         sys.exit("numpy.longdouble is no wider than fp64 on this machine: LIN_GAPS cannot be measured here")
     print("LIN_GAPS = {    # graph: (chi2, b, H_diag, H_off), fp64 against long double")
@@ -112,19 +159,25 @@ def main():
     rhos = {}
     print("GAPS = {    # case: per k = 1.., (vertex, lambda, chi2_final)")
     for c in SC.CASES:
-        _Vd, rd = SC.reference(c.name, c.iterations, "direct")
+        oth = SC.other(c.name)
+        _Vd, rd = SC.reference(c.name, c.iterations, oth)
         _Vp, rp = SC.reference(c.name, c.iterations, "pcg")
-        d, p = np.array([t["rho"] for t in rd["trace"]]), np.array([t["rho"] for t in rp["trace"]])
-        rhos[c.name] = (min(np.abs(d).min(), np.abs(p).min()),
-                        (np.minimum(np.abs(d), np.abs(p)) / np.maximum(np.abs(d - p), 1e-300)).min())
-        print("    # %s direct %s pcg %s" % (c.name, SC.pattern(rd), SC.pattern(rp)))
+        note = "%s %s %s pcg %s" % (c.name, oth, SC.pattern(rd), SC.pattern(rp))
+        if c.name in SC.EXEMPT:
+            print("    # %s, rho %s: exact comparison, no gap" % (note, sorted(set(str(t["rho"]) for t in rp["trace"]))))
+            continue
+        rhos[c.name] = SC.rho_margin(c.name)
+        print("    # %s" % note)
         print("    #   accepted rho %s" % " ".join("%.3f" % t["rho"] for t in rp["trace"] if t["accepted"]))
+        if c.pcg_max_iters < 1000:
+            print("    #   %d solver iterations in %d trials; uncapped, the same graph takes %s per trial" % (
+                rp["pcg_iterations"], rp["trials"], " ".join(str(t["solver_iterations"]) for t in SC.uncapped(c.name)["trace"])))
         rows = ["(%.2e, %.2e, %.2e)" % SC.gap(c.name, k) for k in range(1, c.iterations + 1)]
         lines = [", ".join(rows[k:k + 3]) for k in range(0, len(rows), 3)]
         pad = " " * (9 + len(c.name))
         print('    "%s": [%s],' % (c.name, (",\n" + pad).join(lines)), flush=True)
     print("}")
-    print("MIN_RHO = {    # case: smallest |rho| of any trial    (smallest |rho| / |rho_direct - rho_pcg|)")
+    print("MIN_RHO = {    # case: smallest |rho| of any trial    (smallest |rho| / |rho_other - rho_pcg|)")
     for name, (lo, margin) in rhos.items():
         print('    "%s": %.3f,    # %.3g' % (name, lo, margin))
     print("}")
